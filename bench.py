@@ -20,6 +20,16 @@ Contract (one JSON line on rank 0):  python bench.py --gpus N --steps K --warmup
     (lsdsort_u32_device_timed, same stream), against 8 TB/s HBM peak.
   * cpu_baseline: the reference's CPU std::sort path (LSDRadixSort.cu:97) on one host thread,
     on a bounded sample of the same keys; rank 0, N=1 only.  The oracle is used here and only here.
+  * a plain run does only what the headline needs: set up, warm up, time the K steps, check the
+    fault word of the workspace they ran in, write the outputs (--dump-outputs) and print the line.
+    Everything else -- the roofline events and live PMC passes, the secondary configs under
+    "extra", the CPU baseline and the sortedness guards -- runs with --full only; without it
+    "roofline", "stages_ms", "cpu_baseline" and "config.tile_keys" are null and "extra" is empty.
+  * --dump-outputs DIR: after the timed steps, what the last timed step computed, as float64
+    .npy files in DIR (uint32 values are exact in float64): "keys" (and "values" with --pairs)
+    for one GPU, "keys_rank<r>" for the slice rank r holds when N > 1.  An array larger than its
+    share of DUMP_LIMIT_BYTES is sampled at fixed positions: DUMP_SEED's choice of distinct indices, in
+    increasing order.  Inputs are the same in every run with the same arguments.
 """
 from __future__ import annotations
 
@@ -35,6 +45,8 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 TB/s measured copy)
 POOL_LIMIT_BYTES = 96 << 30    # fresh input copies kept resident per GPU (of 288 GB)
+DUMP_LIMIT_BYTES = 48 << 20    # --dump-outputs: all .npy payloads of a run together (under 64 MB with headers)
+DUMP_SEED = 20240901           # --dump-outputs: the sample positions of an array larger than its share
 
 
 def mt19937_keys(n: int, seed: int):
@@ -84,9 +96,16 @@ def parse_args(argv=None):
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not run the two rocprofv3 --pmc passes that measure roofline.traffic in this very run (N = 1 only; "
                          "the committed profiles/pmc_summary.json figure is reported instead, labelled as such)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline events, live PMC traffic, the secondary "
+                         "configs under 'extra', the CPU baseline, the sortedness guards (--no-* switches above narrow it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; a fixed sample of positions above 48 MiB in all)")
     args = ap.parse_args(argv)
     if args.gpus not in (1, 2, 4, 8):
         ap.error("--gpus must be 1, 2, 4 or 8 (MSB buckets: one rank per power-of-two share of the key space)")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     return args
 
 
@@ -277,6 +296,31 @@ class InputPool:
         return k, v
 
 
+def sample_positions(length, m, seed=DUMP_SEED):
+    """The positions --dump-outputs keeps of an array of `length` items when only `m` fit: a fixed function of
+    (seed, length, m), distinct and in increasing order."""
+    import numpy as np
+
+    return np.sort(np.random.default_rng(seed).choice(length, size=m, replace=False))
+
+
+def dump_outputs(outdir, arrays, budget_bytes):
+    """Write each CUDA tensor of `arrays` (int32 bit patterns of uint32 values) to outdir/<name>.npy as float64, all of them
+    together within `budget_bytes`; an array larger than its share is written at sample_positions() only."""
+    import numpy as np
+    import torch
+
+    os.makedirs(outdir, exist_ok=True)
+    share = max(1, budget_bytes // (8 * max(1, len(arrays))))
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        if t.numel() > share:
+            idx = torch.from_numpy(sample_positions(t.numel(), share)).to(t.device)
+            t = t[idx]
+        host = t.cpu().numpy().view(np.uint32).astype(np.float64)
+        np.save(os.path.join(outdir, f"{name}.npy"), host)
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = parse_args(argv)
@@ -378,14 +422,33 @@ def main(argv=None):
             def sharded(keys):
                 return backend.sort(keys)
 
+        last = {}
+
         def run_step(kv):
-            sharded(kv[0])
+            last["res"] = sharded(kv[0])          # this rank's slice, kept for --dump-outputs
 
     elapsed = timed_steps(run_step, pool, args.steps, args.warmup, sync)
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+        assert backend.check_fault() == 0, "device fault word set in the sharded path's workspace"
+    else:
+        # `ws` is the workspace every timed sort ran in
+        check_status = lsd.lib().lsdsort_check_device(ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        assert check_status == 0, f"device fault word set ({check_status})"
+        plain_form = bool(lsd.workspace_form(ws))      # 1 if the last timed sort ran the hybrid form (a word the planner set)
+
+    if args.dump_outputs:
+        # before anything else runs: the sharded sorter's slice is a view into a buffer its next call reuses
+        if distributed:
+            arrays = {f"keys_rank{rank}": last["res"].keys}
+        else:
+            k, v = pool.bufs[(pool.next - 1) % pool.capacity]
+            arrays = {"keys": k} if v is None else {"keys": k, "values": v}
+        dump_outputs(args.dump_outputs, arrays, DUMP_LIMIT_BYTES // world)
+
+    if distributed and args.full:
         # correctness guard for the sharded path (untimed, collective): every rank's slice is sorted, lies
         # in its own MSB bucket, and the slices add up to every key
         res = sharded(pool.fresh()[0])
@@ -399,17 +462,13 @@ def main(argv=None):
         dist.all_reduce(cnt)
         assert int(cnt[0].item()) == n * world and int(cnt[1].item()) == 0, "sharded sort failed its check"
         del res, u
-    else:
-        # `ws` is the workspace every timed sort ran in
-        check_status = lsd.lib().lsdsort_check_device(ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        assert check_status == 0, f"device fault word set ({check_status})"
 
     ms_per_step = elapsed / args.steps * 1e3
     total_keys = n * world
     mkeys = total_keys / (elapsed / args.steps) / 1e6
 
     # correctness guard on the last sorted buffer of this rank (single GPU): sortedness
-    if not distributed:
+    if not distributed and args.full:
         k = pool.bufs[(pool.next - 1) % pool.capacity][0]
         u = k.to(torch.int64) & 0xFFFFFFFF
         assert bool((u[1:] >= u[:-1]).all()), "bench output is not sorted"
@@ -469,7 +528,7 @@ def main(argv=None):
     roofline = None
     stage_ms = None
     sort_tile_keys = None
-    if rank == 0:
+    if rank == 0 and args.full:
         roofline, stage_ms, sort_tile_keys = measure_roofline(lambda: pool.fresh()[0], lambda: pool.bufs[(pool.next - 1) % pool.capacity][1],
                                                               r, args.pairs, n, ws)
         sort_bytes = (4 + 16 * passes) * n if args.pairs else 4 * (2 * passes + 1) * n
@@ -520,7 +579,7 @@ def main(argv=None):
 
     # ---- secondary configs on the same box (N=1 only): configs[1] (r=4) and configs[4] (pairs), stage rows ----
     extra = {}
-    if rank == 0 and not distributed and not args.no_extra and not args.pairs and r == 8 and log2_keys == 28:
+    if rank == 0 and args.full and not distributed and not args.no_extra and not args.pairs and r == 8 and log2_keys == 28:
         def config_line(rb, pairs, nn, steps=8):
             """The same measurement as the headline, on another BASELINE config: `steps` back-to-back sorts of fresh
             copies between two synchronisations, then the kernel's own events for its roofline object."""
@@ -669,7 +728,7 @@ def main(argv=None):
 
     # ---- CPU baseline: the reference's std::sort path on the host, one thread ----
     cpu_baseline = None
-    if rank == 0 and not distributed and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not distributed and not args.no_cpu_baseline:
         import oracle     # test infrastructure; used only for this reported baseline
 
         oracle.lib()
@@ -699,17 +758,20 @@ def main(argv=None):
                                                      "reference tree into oracle/_ref, r=8, same sample, 1 thread")
 
     if rank == 0:
+        # the form the timed sorts ran: from the roofline's sorts with --full, else from the workspace of the single-GPU sorts
+        hybrid_form = bool(stage_ms["hybrid_form"]) if stage_ms else (None if distributed else plain_form)
         if distributed:
             total_txt = f"2^{(n * world).bit_length() - 1} keys over {world} GPU{'s' if world > 1 else ''}" if (n * world) & (n * world - 1) == 0 else f"{n * world} keys"
             workload = (f"{total_txt} = 2^{log2_keys} uniform uint32 keys per GPU (mt19937 seed=rank), "
                         f"{'MSB-bucket' if args.partition == 'msb' else 'sampled-splitter'} partition + {'grouped ncclSend/ncclRecv (C++ step, lsdsort_sharded_u32_device_ex)' if exchange_path == 'c++' else 'torch.distributed all-to-all'} over xGMI + "
                         f"local {r}-bit LSD sort per step (a shard of this size alone: "
-                        + (f"hybrid form, {16 // r} global passes + LDS-resident local stage" if stage_ms and stage_ms.get("hybrid_form") else f"{passes} global passes")
+                        + ("form measured with --full" if hybrid_form is None else
+                           f"hybrid form, {16 // r} global passes + LDS-resident local stage" if hybrid_form else f"{passes} global passes")
                         + "; the step's sort plans below the shard's key prefix)"
                         + (" [BASELINE configs[3]]" if n * world == 1 << 30 and world == 8 else ""))
         else:
             form = (f", hybrid form (bits 16-31 by {16 // r} global passes, the low bits inside each CU's LDS; decided on the device)"
-                    if stage_ms and stage_ms.get("hybrid_form") else f", {passes} global passes")
+                    if hybrid_form else f", {passes} global passes")
             workload = (f"2^{log2_keys} uniform uint32 {'key+payload pairs' if args.pairs else 'keys'} per GPU "
                         f"(mt19937 seed=rank), {r}-bit radix{form}, {args.algorithm}, device-resident")
         line = {
@@ -719,7 +781,7 @@ def main(argv=None):
             "dtype": "u32", "data": "synthetic",
             "config": {"workload": workload, "keys_per_gpu": n, "total_keys": n * world, "radix_bits": r,
                        "algorithm": args.algorithm, "pairs": bool(args.pairs), "tile_keys": sort_tile_keys,
-                       "hybrid_form": bool(stage_ms and stage_ms.get("hybrid_form"))},
+                       "hybrid_form": hybrid_form},
             "roofline": roofline, "cpu_baseline": cpu_baseline, "stages_ms": stage_ms, "extra": extra,
         }
         print(json.dumps(line), flush=True)

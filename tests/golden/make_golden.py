@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/lsd_golden.npz from the REFERENCE's own CPU code.
+"""Generate tests/golden/lsd_golden.npz (an .npz with LZMA-compressed members) from the REFERENCE's own CPU code.
 
 Run in the build container (needs /root/reference):  python tests/golden/make_golden.py
 
@@ -12,9 +12,17 @@ ref LSD (r in 1,2,4,8,16) == std::sort, the same transitive check the reference 
 vectors are what pins the oracle and the HIP path on machines where /root/reference is absent.
 
 Fixtures are data only: inputs and expected outputs, no source text.
+
+`python tests/golden/make_golden.py --recorded` writes tests/golden/ref_recorded.json instead (and leaves
+lsd_golden.npz alone): sha256 digests of what the reference's own functions return for the inputs of the
+tests in tests/test_oracle.py that compare against the reference build, so that those tests check the same
+thing where that build is absent.
 """
+import hashlib
+import json
 import os
 import sys
+import zipfile
 
 import numpy as np
 
@@ -22,6 +30,18 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import oracle  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lsd_golden.npz")
+RECORDED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_recorded.json")
+
+# the inputs of tests/test_oracle.py::test_oracle_equals_reference_build: raw mt19937 streams (n, seed), and a skewed one
+REF_SORT_CASES = ((1, 1), (2, 2), (1000, 3), (65536, 0), (100003, 4))
+
+
+def skew_keys():
+    return (oracle.mt19937_keys(50000, 9) % 5).astype(np.uint32) << np.uint32(13)
+
+
+def sha256(a) -> str:
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 def cases():
@@ -114,9 +134,46 @@ def main():
     # mt19937 known-answer: the 10000th output of default-seeded std::mt19937 (C++ standard).
     out["mt19937_kat"] = np.array([5489, 9999, 4123659995], dtype=np.uint64)
 
-    np.savez_compressed(OUT, **out)
+    np.savez(OUT, **out)
+    _repack_lzma(OUT)
     print(f"wrote {OUT}: {os.path.getsize(OUT)} bytes, {len(names)} sort cases")
 
 
+def _repack_lzma(path):
+    """Same .npy members, LZMA-compressed (np.load reads them through zipfile): keeps the fixture under 1 MiB."""
+    with zipfile.ZipFile(path) as zin:
+        members = [(i.filename, zin.read(i.filename)) for i in zin.infolist()]
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for name, data in members:
+            z.writestr(name, data)
+
+
+def main_recorded():
+    oracle.build()
+    assert oracle.ref_available(), "needs the reference build (make -C oracle ref)"
+    with np.load(OUT, allow_pickle=False) as z:
+        golden = {k: z[k] for k in z.files}
+    sorts = {}
+    inputs = [(f"mt19937_n{n}_seed{seed}", oracle.mt19937_keys(n, seed)) for n, seed in REF_SORT_CASES] + [("skew", skew_keys())]
+    for name, keys in inputs:
+        for r in (1, 2, 4, 8, 16):
+            got = oracle.ref_lsd_sort(keys, r)
+            assert np.array_equal(got, oracle.std_sort(keys)), (name, r)
+            sorts[f"{name}_r{r}"] = sha256(got)
+    rec = {
+        "about": "sha256 of the uint32 (little-endian, C order) arrays the reference's own CPU functions return "
+                 "(oracle/_ref, built from the reference tree); written by tests/golden/make_golden.py --recorded",
+        "ref_lsd_sort": sorts,
+        "ref_rng_keys_4096_seed0": sha256(oracle.ref_rng_keys(4096, 0)),
+        "ref_lsd_sort_uniform_16384_seed0_r8": sha256(oracle.ref_lsd_sort(golden["in__uniform_16384_seed0"], 8)),
+        "ref_build_histograms_hist_in_1024_r8_bg1": sha256(oracle.ref_build_histograms(golden["hist_in"], 1024, 8, 1)),
+        "ref_prefix_sum_scan_in": sha256(oracle.ref_prefix_sum(golden["scan_in"])),
+    }
+    with open(RECORDED, "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"wrote {RECORDED}: {len(sorts)} sort digests")
+
+
 if __name__ == "__main__":
-    main()
+    main_recorded() if sys.argv[1:] == ["--recorded"] else main()

@@ -4,12 +4,20 @@ The oracle (oracle/lsd_oracle.c, oracle/std_sort.cpp) is a restatement of the re
 path; before anything trusts it, it is checked against
   * the committed golden vectors (tests/golden/lsd_golden.npz), which were produced by the
     reference's own functions compiled in place (tests/golden/make_golden.py), and
-  * that reference build itself (oracle/_ref/libref_lsd.so) when present on this machine.
+  * what that reference build returned for the inputs of the tests at the end of this file, recorded
+    as sha256 digests in tests/golden/ref_recorded.json (tests/golden/make_golden.py --recorded), and
+  * that reference build itself (oracle/_ref/libref_lsd.so) when it has been built.
 Mirrors the reference's own checks: CPU LSD == std::sort (LSDRadixSort.cu:120), per-block scan
 vs PrefixSum (.cu:257), histograms vs BuildHistogramsCPU (.cu:785).
 """
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
+
+RECORDED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_recorded.json")
 
 
 def test_mt19937_known_answer(oracle_mod, golden):
@@ -117,35 +125,84 @@ def test_msb_partition(oracle_mod, golden, msb_bits):
 
 
 # ----------------------------------------------------------------------------- against the real reference
-def _need_ref(oracle_mod):
-    if not oracle_mod.ref_available():
-        pytest.skip("oracle/_ref/libref_lsd.so not built (needs /root/reference; golden vectors cover this machine)")
+@pytest.fixture(scope="module")
+def recorded():
+    """What the reference's own functions returned, recorded from its build (tests/golden/make_golden.py --recorded)."""
+    with open(RECORDED) as f:
+        return json.load(f)
+
+
+def _sha256(a) -> str:
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def _libstdcxx_rng_keys(n: int, seed: int) -> np.ndarray:
+    """RNG(seed, 0, UINT32_MAX).Get() of the reference harness (Utils.h:24-33) as libstdc++ computes it:
+    std::default_random_engine is minstd_rand0 (x <- 16807 x mod 2^31 - 1; a seed of 0 is taken as 1; outputs 1 .. 2^31 - 2),
+    and std::uniform_int_distribution<uint32_t> over 0 .. 2^32 - 1, wider than the engine's range, takes
+    (2^31 - 2) * u + (x - 1) with u in 0 .. 2 from a draw below 3 * s divided by s (s = (2^31 - 3) // 3), drawing again
+    when the sum exceeds 2^32 - 1."""
+    m = 2**31 - 1
+    x = seed % m or 1
+    urng_range = 2**31 - 3
+    scaling = urng_range // 3
+    out = np.empty(n, dtype=np.uint32)
+    for i in range(n):
+        while True:
+            while True:
+                x = x * 16807 % m
+                if x - 1 < 3 * scaling:
+                    break
+            tmp = (urng_range + 1) * ((x - 1) // scaling)
+            x = x * 16807 % m
+            ret = tmp + (x - 1)
+            if ret <= 0xFFFFFFFF:
+                break
+        out[i] = ret
+    return out
+
+
+def _ref_sort_inputs(oracle_mod):
+    """The inputs tests/golden/make_golden.py --recorded sorted with the reference's LSDRadixSort."""
+    for n, seed in ((1, 1), (2, 2), (1000, 3), (65536, 0), (100003, 4)):
+        yield f"mt19937_n{n}_seed{seed}", oracle_mod.mt19937_keys(n, seed)
+    yield "skew", (oracle_mod.mt19937_keys(50000, 9) % 5).astype(np.uint32) << np.uint32(13)
 
 
 @pytest.mark.parametrize("r", [1, 2, 4, 8, 16])
-def test_oracle_equals_reference_build(oracle_mod, r):
-    _need_ref(oracle_mod)
-    for n, seed in ((1, 1), (2, 2), (1000, 3), (65536, 0), (100003, 4)):
-        keys = oracle_mod.mt19937_keys(n, seed)
-        assert np.array_equal(oracle_mod.lsd_sort(keys, r), oracle_mod.ref_lsd_sort(keys, r)), (n, r)
-    skew = (oracle_mod.mt19937_keys(50000, 9) % 5).astype(np.uint32) << np.uint32(13)
-    assert np.array_equal(oracle_mod.lsd_sort(skew, r), oracle_mod.ref_lsd_sort(skew, r))
+def test_oracle_equals_reference_build(oracle_mod, recorded, r):
+    live = oracle_mod.ref_available()
+    for name, keys in _ref_sort_inputs(oracle_mod):
+        got = oracle_mod.lsd_sort(keys, r)
+        assert np.array_equal(got, np.sort(keys)), (name, r)
+        assert _sha256(got) == recorded["ref_lsd_sort"][f"{name}_r{r}"], (name, r)
+        if live:
+            assert np.array_equal(got, oracle_mod.ref_lsd_sort(keys, r)), (name, r)
 
 
-def test_reference_rng_stream(oracle_mod, golden):
-    _need_ref(oracle_mod)
+def test_reference_rng_stream(oracle_mod, golden, recorded):
     # RNG(0, 0, UINT32_MAX) on libstdc++ (SURVEY.md section 8c); MSVC differs.
-    assert list(oracle_mod.ref_rng_keys(4, 0)) == [282475248, 2617694917, 1457850877, 3262921810]
-    assert np.array_equal(oracle_mod.ref_rng_keys(4096, 0), golden["in__refrng_4096_seed0"])
+    stream = _libstdcxx_rng_keys(4096, 0)
+    assert list(stream[:4]) == [282475248, 2617694917, 1457850877, 3262921810]
+    assert np.array_equal(stream, golden["in__refrng_4096_seed0"])
+    assert _sha256(stream) == recorded["ref_rng_keys_4096_seed0"]
+    if oracle_mod.ref_available():
+        assert list(oracle_mod.ref_rng_keys(4, 0)) == [282475248, 2617694917, 1457850877, 3262921810]
+        assert np.array_equal(oracle_mod.ref_rng_keys(4096, 0), golden["in__refrng_4096_seed0"])
+        assert np.array_equal(oracle_mod.ref_rng_keys(5000, 7), _libstdcxx_rng_keys(5000, 7))
 
 
-def test_golden_regenerates_identically(oracle_mod, golden):
-    """Where the reference is present, re-derive a sample of the fixtures from it."""
-    _need_ref(oracle_mod)
+def test_golden_regenerates_identically(oracle_mod, golden, recorded):
+    """A sample of the fixtures against what the reference returns for them: its recorded digests everywhere, and its build
+    where that is present."""
     keys = golden["in__uniform_16384_seed0"]
-    assert np.array_equal(oracle_mod.ref_lsd_sort(keys, 8), golden["sorted__uniform_16384_seed0"])
-    assert np.array_equal(oracle_mod.ref_build_histograms(golden["hist_in"], 1024, 8, 1), golden["hist_block1024_r8_bg1"])
-    assert np.array_equal(oracle_mod.ref_prefix_sum(golden["scan_in"]), golden["scan_out"])
+    assert _sha256(golden["sorted__uniform_16384_seed0"]) == recorded["ref_lsd_sort_uniform_16384_seed0_r8"]
+    assert _sha256(golden["hist_block1024_r8_bg1"]) == recorded["ref_build_histograms_hist_in_1024_r8_bg1"]
+    assert _sha256(golden["scan_out"]) == recorded["ref_prefix_sum_scan_in"]
+    if oracle_mod.ref_available():
+        assert np.array_equal(oracle_mod.ref_lsd_sort(keys, 8), golden["sorted__uniform_16384_seed0"])
+        assert np.array_equal(oracle_mod.ref_build_histograms(golden["hist_in"], 1024, 8, 1), golden["hist_block1024_r8_bg1"])
+        assert np.array_equal(oracle_mod.ref_prefix_sum(golden["scan_in"]), golden["scan_out"])
 
 
 def test_u64_legs_against_golden_and_numpy(oracle_mod, golden):

@@ -9,7 +9,7 @@ OUT=$REPO/gpurun_out/prof_$TAG
 rm -rf $OUT   # files of an earlier run with the same tag would be averaged in
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT/trace --output-format csv -- python3 $REPO/bench.py "$@" > $OUT/bench.log 2>&1 || { echo "bench under rocprofv3 failed"; tail -5 $OUT/bench.log; exit 1; }
+rocprofv3 --kernel-trace --stats -d $OUT/trace --output-format csv -- python3 $REPO/bench.py --full "$@" > $OUT/bench.log 2>&1 || { echo "bench under rocprofv3 failed"; tail -5 $OUT/bench.log; exit 1; }
 grep '^{' $OUT/bench.log | tail -1 > $OUT/bench.json
 cp "$(ls -t $(find $OUT/trace -name '*kernel_stats.csv') | head -1)" $OUT/kernel_stats.csv
 head -6 $OUT/kernel_stats.csv
