@@ -156,6 +156,28 @@ LSDSORT_API int lsdsort_records_device(void* d_keys, void* d_vals, int key_bits,
 LSDSORT_API int lsdsort_wide_check_device(void* d_workspace, size_t n, int radix_bits, int key_bits, int val_bits,
                                           void* hip_stream);
 
+/* Segmented sort (no reference counterpart; the counterpart of DeviceSegmentedRadixSort and of torch.sort(x, dim=-1) on rows).
+ * Segment s = keys[d_offsets[s] .. d_offsets[s+1]) for s < num_segments; each segment is sorted in place,
+ * independently, stable; d_vals (may be NULL) is permuted with the keys.  d_offsets: num_segments + 1 ascending
+ * uint32 device words, d_offsets[num_segments] <= n; keys outside [d_offsets[0], d_offsets[num_segments]) are
+ * not touched.  key_type / descending as lsdsort_keys_device (0 uint32, 1 int32, 2 float32 IEEE total order).
+ * Stream-ordered, no host synchronisation, capturable in a graph: every launch is sized from (n, num_segments).
+ * A planner kernel sorts the segments into three size classes on the device: up to 1024 keys one wavefront each, up to
+ * 16384 one workgroup's LDS each (both skip every 8-bit digit that is the same in all keys of the segment), larger ones
+ * four staged passes over tiles that never cross a segment (lsdradixsort_amd/csrc/segmented.hip).  Where the returning-add
+ * rank form is not in force (lsdsort_set_rank_method) every segment takes the staged passes: same result, slower.
+ * Offsets are checked on the device: a segment whose end is below its start or beyond n is left untouched, the call still
+ * returns LSDSORT_OK, and lsdsort_check_device(d_workspace, stream) then returns LSDSORT_ERR_DEVICE_FAULT.  Nothing outside
+ * [0, n) is ever read or written.  Segments that overlap one another (possible only around such a pair) come out in an
+ * unspecified order.  Checks, in order: key_type (INVALID_ARG), n or num_segments above LSDSORT_MAX_KEYS (TOO_LARGE), a NULL
+ * d_keys or d_offsets with n > 0 or num_segments > 0 (INVALID_ARG), n == 0 or num_segments == 0 (OK, nothing launched), the
+ * workspace (WORKSPACE: NULL, not 256-byte aligned, or below lsdsort_segmented_workspace_bytes), the device (NO_DEVICE).
+ * lsdsort_segmented_workspace_bytes is monotonic in n and num_segments and returns 0 above LSDSORT_MAX_KEYS. */
+LSDSORT_API size_t lsdsort_segmented_workspace_bytes(size_t n, size_t num_segments, int pairs);
+LSDSORT_API int lsdsort_segmented_device(void* d_keys, uint32_t* d_vals, const uint32_t* d_offsets,
+                                         size_t num_segments, size_t n, int key_type, int descending,
+                                         void* d_workspace, size_t workspace_bytes, void* hip_stream);
+
 /* After the stream has drained: LSDSORT_OK, or LSDSORT_ERR_DEVICE_FAULT if a kernel of the
  * last sort on this workspace gave up a bounded spin or refused destinations outside the output
  * (never expected; the output is then undefined).  Synchronises hip_stream.  With LSDSORT_REPROBE=1

@@ -76,6 +76,20 @@ inline void sort_device_descending(uint32_t* d_keys, void* d_workspace, size_t w
           "lsdsort_keys_device");
 }
 
+// Many independent segments of one array, each sorted in place and stable (lsdsort_segmented_device): segment s =
+// d_keys[d_offsets[s] .. d_offsets[s + 1]), d_offsets on the device.  Malformed offsets: lsdsort_check_device afterwards.
+inline size_t segmented_workspace_bytes(size_t n, size_t num_segments, bool pairs = false)
+{
+    return lsdsort_segmented_workspace_bytes(n, num_segments, pairs ? 1 : 0);
+}
+inline void sort_segments(void* d_keys, const uint32_t* d_offsets, size_t num_segments, size_t n, void* d_workspace,
+                          size_t workspace_bytes_, lsdsort_key_type key_type = LSDSORT_KEY_U32, bool descending = false,
+                          uint32_t* d_vals = nullptr, void* hip_stream = nullptr)
+{
+    check(lsdsort_segmented_device(d_keys, d_vals, d_offsets, num_segments, n, key_type, descending ? 1 : 0, d_workspace,
+                                   workspace_bytes_, hip_stream), "lsdsort_segmented_device");
+}
+
 // A shard of a range-partitioned array: keys expected to share their top `common_prefix_bits` bits (a hint; the device checks)
 inline void sort_shard_device(uint32_t* d_keys, void* d_workspace, size_t workspace_bytes_, size_t n, int common_prefix_bits,
                               int radix_bits = 8, void* hip_stream = nullptr)

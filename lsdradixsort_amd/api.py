@@ -19,7 +19,7 @@ from .errors import LSDSORT_ALGO_ONESWEEP, LSDSORT_ALGO_STAGED, check
 __all__ = [
     "sort", "sort_pairs", "to_device", "to_host", "workspace_bytes", "GPULSDRadixSort",
     "GPULSDRadixSortTimed", "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
-    "MSBPartition", "SplitterPartition", "GPUSortTyped", "GPUSortWide", "GPUSortMulti", "set_hybrid", "tile_keys", "set_tile_config", "set_rank_method", "rank_method", "set_xcd_chunk", "LSDSORT_ALGO_ONESWEEP", "LSDSORT_ALGO_STAGED",
+    "MSBPartition", "SplitterPartition", "GPUSortTyped", "GPUSortWide", "GPUSortSegmented", "segmented_workspace_bytes", "sort_rows", "GPUSortMulti", "set_hybrid", "tile_keys", "set_tile_config", "set_rank_method", "rank_method", "set_xcd_chunk", "LSDSORT_ALGO_ONESWEEP", "LSDSORT_ALGO_STAGED",
 ]
 
 
@@ -233,6 +233,68 @@ def GPUSortTyped(d_keys, key_type: str = "int32", descending: bool = False, d_va
     if check_fault and n:
         check(lib().lsdsort_check_device(workspace.data_ptr(), _stream(stream)), "lsdsort_check_device")
     return d_keys if not pairs else (d_keys, d_vals)
+
+
+def segmented_workspace_bytes(n: int, num_segments: int, pairs: bool = False) -> int:
+    """Bytes of device workspace ``GPUSortSegmented`` needs for up to ``n`` keys in up to ``num_segments`` segments."""
+    return int(lib().lsdsort_segmented_workspace_bytes(n, num_segments, int(bool(pairs))))
+
+
+def GPUSortSegmented(d_keys, d_offsets, d_vals=None, key_type: str = "uint32", descending: bool = False, workspace=None,
+                     stream=None, check_fault: bool = False):
+    """Sort every segment ``d_keys[d_offsets[s]:d_offsets[s + 1]]`` independently, in place, stable
+    (``lsdsort_segmented_device``).  ``d_keys``: int32 or float32 CUDA tensor whose 32 bits compare as ``key_type``
+    ("uint32" / "int32" / "float32", IEEE total order); ``d_offsets``: int32 CUDA tensor of num_segments + 1 ascending
+    offsets (uint32 bit patterns); ``d_vals``: optional int32 payloads permuted with the keys.  Keys outside
+    ``[d_offsets[0], d_offsets[-1])`` are left alone.  Malformed offsets are reported by ``lsdsort_check_device``
+    (``check_fault=True`` raises)."""
+    torch = _torch()
+    if not (isinstance(d_keys, torch.Tensor) and d_keys.is_cuda and d_keys.is_contiguous() and d_keys.dtype in (torch.int32, torch.float32)):
+        raise TypeError("d_keys: a contiguous int32 or float32 CUDA tensor")
+    _dev_i32(d_offsets, "d_offsets")
+    n = d_keys.numel()
+    segs = max(d_offsets.numel() - 1, 0)
+    pairs = d_vals is not None
+    if pairs:
+        _dev_i32(d_vals, "d_vals")
+        if d_vals.numel() != n:
+            raise ValueError("keys and vals differ in length")
+    if workspace is None:
+        nbytes = segmented_workspace_bytes(n, segs, pairs)
+        if nbytes == 0 and n > 0 and segs > 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_segmented_workspace_bytes", "too many keys or segments")
+        if stream is not None:
+            with torch.cuda.stream(stream):
+                workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=d_keys.device)
+        else:
+            workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=d_keys.device)
+    check(lib().lsdsort_segmented_device(d_keys.data_ptr(), d_vals.data_ptr() if pairs else None, d_offsets.data_ptr(), segs, n,
+                                         _KEY_TYPES[key_type], int(bool(descending)), workspace.data_ptr(), workspace.numel(),
+                                         _stream(stream)),
+          "lsdsort_segmented_device")
+    if check_fault and n and segs:
+        check(lib().lsdsort_check_device(workspace.data_ptr(), _stream(stream)), "lsdsort_check_device")
+    return d_keys if not pairs else (d_keys, d_vals)
+
+
+def sort_rows(x, descending: bool = False, return_indices: bool = False, stream=None):
+    """``torch.sort(x, dim=-1, stable=True)`` for a contiguous 2-D int32 / float32 CUDA tensor: every row sorted by the
+    library's segmented sort (float32 in IEEE total order: -0.0 before +0.0, NaNs by sign at the ends).  Returns the sorted
+    copy, and with ``return_indices`` also the int64 positions within each row."""
+    torch = _torch()
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 2 and x.dtype in (torch.int32, torch.float32)):
+        raise TypeError("x: a 2-D int32 or float32 CUDA tensor")
+    rows, cols = x.shape
+    key_type = "int32" if x.dtype == torch.int32 else "float32"
+    ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.stream(torch.cuda.current_stream())
+    with ctx:
+        out = x.contiguous().clone()
+        offsets = torch.arange(0, rows + 1, dtype=torch.int64, device=x.device).mul_(cols).to(torch.int32)
+        idx = torch.arange(cols, dtype=torch.int32, device=x.device).repeat(rows) if return_indices else None
+        GPUSortSegmented(out.view(-1), offsets, d_vals=idx, key_type=key_type, descending=descending, stream=stream)
+        if return_indices:
+            return out, idx.view(rows, cols).to(torch.int64)
+    return out
 
 
 def GPUSortWide(d_keys, d_vals=None, r: int = 8, workspace=None, stream=None, check_fault: bool = False):

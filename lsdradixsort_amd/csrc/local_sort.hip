@@ -511,4 +511,175 @@ hipError_t launch_local_sort(const LocalSortParams& p, hipStream_t stream)
     return launch_local_inst<32, false>(p, stream);
 }
 
+
+// ---- the segmented sort's workgroup tier (segmented.hip plans it) -------------------------------------------------------------
+// Segment s = keys [offsets[s], offsets[s + 1]), kWaveSegCap < size <= kLocalSortCap, listed by the planner.  sort_bucket's digit
+// pass (same rank, same scan, same reorder, 16384-key variant) over all four bytes of the key, plus what a segment needs that a
+// bucket of the hybrid form does not: the key transform on load as well as on store, and no pass for a byte that is the same in
+// every key of the segment (AND and OR of the keys agree on it: small key ranges, one value per segment).  A function of its own so
+// that sort_bucket's instantiations stay as they are.
+template <bool PAIRS>
+__device__ __forceinline__ void sort_segment(const SegSortParams& p, const uint32_t s)
+{
+    constexpr int T = kLocalThreads, W = kLocalWaves, HW = kLocalMaxBins / 2, K = 32;
+    constexpr int CAP = T * K;
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    lds_u32* const s_keys = (lds_u32*)smem;
+    volatile lds_u32* const s_cnt = (volatile lds_u32*)(s_keys + CAP);
+    volatile lds_u16* const s_cnt16 = (volatile lds_u16*)s_cnt;
+    lds_u32* const s_misc = (lds_u32*)(s_cnt + W * HW);
+
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (s >= p.num_segments) {   // never listed: say so, touch nothing
+        if (tid == 0 && p.fault) atomicOr(p.fault, 128u);
+        return;
+    }
+    const uint32_t lo = p.offsets[s], hi = p.offsets[s + 1];
+    const uint32_t size = hi - lo;
+    if (hi < lo || hi > p.n || size > (uint32_t)CAP) {
+        if (tid == 0 && p.fault) atomicOr(p.fault, 128u);
+        return;
+    }
+    uint32_t* const seg = p.keys + lo;
+    uint32_t* const seg_vals = PAIRS ? p.vals + lo : nullptr;
+    const uint32_t rows = (size + (uint32_t)T - 1u) / (uint32_t)T;
+    const uint32_t wbase = wave * rows * 64u + lane;
+
+    uint32_t key[K], rank[K], val[PAIRS ? K : 1];
+    uint32_t any = 0u, all = ~0u;
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+        key[i] = 0xFFFFFFFFu;   // past the segment: the highest digit in every pass, stays last, never stored
+        if ((uint32_t)i < rows) {
+            const uint32_t pos = wbase + (uint32_t)i * 64u;
+            if (pos < size) {
+                uint32_t k = seg[pos];
+                if (p.xin.on) k = to_sortable(k, p.xin);
+                key[i] = k;
+                any |= k;
+                all &= k;
+            }
+            if (PAIRS) val[i] = pos < size ? seg_vals[pos] : 0u;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        any |= __shfl_xor(any, off, kWave);
+        all &= __shfl_xor(all, off, kWave);
+    }
+    if (lane == 0u) {
+        s_misc[32 + wave] = any;
+        s_misc[40 + wave] = all;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < W; w++) {
+        any |= s_misc[32 + w];
+        all &= s_misc[40 + w];
+    }
+    uint32_t todo = 0;   // bit b: byte b differs somewhere in the segment (uniform)
+#pragma unroll
+    for (int b = 0; b < 4; b++) todo |= (((any ^ all) >> (8 * b)) & 0xFFu) ? 1u << b : 0u;
+
+    while (todo) {
+        const uint32_t shift = 8u * (uint32_t)__builtin_ctz(todo);
+        todo &= todo - 1u;
+        const bool last = todo == 0u;
+        constexpr uint32_t bins = 256u, mask = bins - 1u;
+#pragma unroll
+        for (int j = 0; j < HW / kWave; j++) s_cnt[wave * HW + j * kWave + lane] = 0;
+#pragma unroll
+        for (int i = 0; i < K; i++) {
+            if ((uint32_t)i < rows) {
+                const uint32_t d = (key[i] >> shift) & mask;
+                const uint32_t sh = (d & 1u) * 16u;
+                const uint32_t old = __hip_atomic_fetch_add((lds_u32*)&s_cnt[wave * HW + (d >> 1)], 1u << sh, __ATOMIC_RELAXED,
+                                                            __HIP_MEMORY_SCOPE_WAVEFRONT);
+                rank[i] = (old >> sh) & 0xFFFFu;
+            }
+        }
+        __syncthreads();
+        uint32_t total = 0;
+        uint32_t wave_excl[W];
+        if (tid < bins) {
+#pragma unroll
+            for (int w = 0; w < W; w++) {
+                wave_excl[w] = total;
+                total += s_cnt16[w * kLocalMaxBins + tid];
+            }
+        }
+        const uint32_t incl = wave_inclusive_scan(tid < bins ? total : 0u, lane);
+        if (lane == 63u) s_misc[wave] = incl;
+        __syncthreads();
+        uint32_t carry = 0;
+#pragma unroll
+        for (int w = 0; w < W; w++) carry += (uint32_t)w < wave ? s_misc[w] : 0u;
+        const uint32_t local_off = incl + carry - total;
+        if (tid < bins) {
+#pragma unroll
+            for (int w = 0; w < W; w++) s_cnt16[w * kLocalMaxBins + tid] = (uint16_t)(local_off + wave_excl[w]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < K; i++) {
+            if ((uint32_t)i < rows) {
+                const uint32_t q = s_cnt16[wave * kLocalMaxBins + ((key[i] >> shift) & mask)] + rank[i];
+                if (PAIRS) rank[i] = q;
+                s_keys[q] = key[i];
+            }
+        }
+        __syncthreads();
+        if (last) {
+            for (uint32_t q = tid; q < size; q += (uint32_t)T) seg[q] = p.xout.on ? from_sortable(s_keys[q], p.xout) : s_keys[q];
+        } else {
+#pragma unroll
+            for (int i = 0; i < K; i++)
+                if ((uint32_t)i < rows) key[i] = s_keys[wbase + (uint32_t)i * 64u];
+        }
+        if (PAIRS) {
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < K; i++)
+                if ((uint32_t)i < rows) s_keys[rank[i]] = val[i];
+            __syncthreads();
+            if (last) {
+                for (uint32_t q = tid; q < size; q += (uint32_t)T) seg_vals[q] = s_keys[q];
+            } else {
+#pragma unroll
+                for (int i = 0; i < K; i++)
+                    if ((uint32_t)i < rows) val[i] = s_keys[wbase + (uint32_t)i * 64u];
+            }
+        }
+        __syncthreads();   // the next pass zeroes counters and writes slots others may still read
+    }
+}
+
+template <bool PAIRS>
+__global__ void __launch_bounds__(kLocalThreads, (local_waves_per_simd<32, PAIRS>())) segment_sort_kernel(const SegSortParams p)
+{
+    const uint32_t listed = *p.list_count < p.list_cap ? (uint32_t)*p.list_count : p.list_cap;
+    for (uint32_t item = blockIdx.x; item < listed; item += gridDim.x) {
+        sort_segment<PAIRS>(p, p.list[item]);
+        __syncthreads();   // the next segment reuses the LDS
+    }
+}
+
+hipError_t launch_segment_sort(const SegSortParams& p, uint32_t grid, hipStream_t stream)
+{
+    constexpr size_t lds_bytes = local_lds_words<32>() * sizeof(uint32_t);
+    if (!p.keys || !p.offsets || !p.list || !p.list_count || grid == 0) return hipErrorInvalidValue;
+    if (p.vals) {
+        static std::atomic<uint64_t> told{0};
+        const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(segment_sort_kernel<true>), lds_bytes, told);
+        if (attr != hipSuccess) return attr;
+        hipLaunchKernelGGL(segment_sort_kernel<true>, dim3(grid), dim3(kLocalThreads), lds_bytes, stream, p);
+    } else {
+        static std::atomic<uint64_t> told{0};
+        const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(segment_sort_kernel<false>), lds_bytes, told);
+        if (attr != hipSuccess) return attr;
+        hipLaunchKernelGGL(segment_sort_kernel<false>, dim3(grid), dim3(kLocalThreads), lds_bytes, stream, p);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace lsd

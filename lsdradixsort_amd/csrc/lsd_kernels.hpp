@@ -245,6 +245,27 @@ hipError_t launch_local_sort(const LocalSortParams& p, hipStream_t stream);
 // (the workspace's fault word and form word: no memset launch precedes it).
 hipError_t launch_small_sort(uint32_t* keys, uint32_t* vals, uint32_t n, uint32_t* clear0, uint32_t* clear1, hipStream_t stream);
 
+// ---- the segmented sort (segmented.hip; its workgroup tier is here, next to sort_bucket) --------------------------------
+// Segment s = keys [offsets[s], offsets[s + 1]).  The planner lists each segment of 2 or more keys in one of three size classes:
+// wave (up to kWaveSegCap keys, one wavefront), workgroup (up to kLocalSortCap, one workgroup's LDS) and large (staged passes).
+constexpr int kWaveSegCap = 1024;
+constexpr uint32_t kSegFaultBit = 64u;   // workspace fault word: some segment's offsets are descending or end beyond n
+struct SegSortParams {
+    uint32_t* keys;
+    uint32_t* vals;               // null: keys only
+    const uint32_t* offsets;
+    const uint32_t* list;         // the segments of this tier, *list_count of them (written by the planner)
+    const unsigned long long* list_count;
+    uint32_t list_cap;            // the list's size: *list_count is clamped to it
+    uint32_t num_segments, n;     // an entry that does not name a checked segment of the right size is skipped ...
+    uint32_t* fault;              // ... and raises a bit here (never expected)
+    KeyTransform xin;             // applied to every key as it is loaded
+    KeyTransform xout;            // undone on every key as it is stored
+};
+// The workgroup tier: every listed segment (kWaveSegCap < size <= kLocalSortCap) sorted in place inside one workgroup's LDS,
+// four 8-bit digit passes, those whose digit is the same for every key of the segment skipped.  `grid` workgroups walk the list.
+hipError_t launch_segment_sort(const SegSortParams& p, uint32_t grid, hipStream_t stream);
+
 // ---- the hybrid form's upfront read and planner (hybrid.hip) ------------------------------------------------------------
 // A bucket = the keys that agree on their top `bucket_bits` bits: 14 while what uniform keys put into one of 2^14 buckets (mean
 // + 6 sigma) fits the three-per-CU variant of the local stage (10240 keys, 8192 pairs), 15 while nearly all of 2^15 buckets do (mean + 1.5 sigma),

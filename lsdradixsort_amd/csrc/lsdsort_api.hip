@@ -793,6 +793,14 @@ MsbLayout make_msb_layout(size_t n, int msb_bits)
 namespace lsd {
 int sort_host_multi(uint32_t* keys, size_t n, int radix_bits, int num_gpus, bool loopback);   // sharded.hip
 void set_last_hip_error(hipError_t e) { g_last_hip = e; }
+// segmented.hip: the current device set up (probe included), and the rank form a sort with this radix uses there
+int device_rank_method(int radix_bits, int* rank_method)
+{
+    int dev = 0;
+    LSD_TRY(check_device_ready(&dev));
+    *rank_method = resolve_rank_method(dev, radix_bits);
+    return LSDSORT_OK;
+}
 }  // namespace lsd
 
 // =============================================================================== C-ABI
