@@ -178,6 +178,30 @@ LSDSORT_API int lsdsort_segmented_device(void* d_keys, uint32_t* d_vals, const u
                                          size_t num_segments, size_t n, int key_type, int descending,
                                          void* d_workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Top-k selection (no reference counterpart; the counterpart of torch.topk(x, k, dim=-1, sorted=True) and of a radix-select
+ * entry).  d_keys: rows x cols 32-bit keys, row-major, READ ONLY.  Row r's result is the first k items of the STABLE sort of
+ * the row in the requested order (key_type as lsdsort_keys_device: 0 uint32, 1 int32, 2 float32 IEEE total order; largest != 0 =
+ * descending = ascending on the complemented key): d_out_keys[r * k + j], j < k, best first, in the caller's key type, and
+ * d_out_idx[r * k + j] its position within the row (d_out_idx may be NULL: values only).  Equal keys come out in position order,
+ * and of the duplicates of the k-th value those at the lowest positions are selected: the result equals the row's full stable
+ * sort cut to k columns, bit for bit, on every run.  rows = 1 is the whole-array case.
+ * The row is not sorted: a most-significant-digit-first radix select counts digits (rows of up to 1024 keys in one wavefront,
+ * up to 16384 in one workgroup's LDS, longer ones by many workgroups with at most five reads of the row and no write but the
+ * winners), the winners are written in position order and only those rows x k items are sorted (lsdradixsort_amd/csrc/topk.hip).
+ * Where k is above three quarters of cols the rows are copied into the workspace and sorted whole instead: same result.
+ * Stream-ordered, no host synchronisation, nothing allocated; every launch is sized from (rows, cols, k): capturable in a graph.
+ * lsdsort_check_device(d_workspace, stream) reports the call's fault word (never expected to be set).
+ * Checks, in order: key_type (INVALID_ARG), rows * cols or rows above LSDSORT_MAX_KEYS (TOO_LARGE), k > cols (INVALID_ARG),
+ * rows == 0, cols == 0 or k == 0 (OK, nothing launched), a NULL d_keys or d_out_keys (INVALID_ARG), the workspace (WORKSPACE:
+ * NULL, not 256-byte aligned, or below lsdsort_topk_workspace_bytes), the device (NO_DEVICE).
+ * lsdsort_topk_workspace_bytes is a multiple of 256, monotonic in each argument and 0 above the limits (rows * cols, rows * k or
+ * any argument above LSDSORT_MAX_KEYS).  It is O(rows * k) -- the winners' sort, and the sort route's copy, which only a call with
+ * cols < 4 k / 3 can take -- plus 16 B per row, and for rows above 16384 keys 8 KiB of counters per row and 8 B per 16384 keys. */
+LSDSORT_API size_t lsdsort_topk_workspace_bytes(size_t rows, size_t cols, size_t k);
+LSDSORT_API int lsdsort_topk_device(const void* d_keys, size_t rows, size_t cols, size_t k, int key_type, int largest,
+                                    void* d_out_keys, uint32_t* d_out_idx, void* d_workspace, size_t workspace_bytes,
+                                    void* hip_stream);
+
 /* After the stream has drained: LSDSORT_OK, or LSDSORT_ERR_DEVICE_FAULT if a kernel of the
  * last sort on this workspace gave up a bounded spin or refused destinations outside the output
  * (never expected; the output is then undefined).  Synchronises hip_stream.  With LSDSORT_REPROBE=1

@@ -90,6 +90,16 @@ inline void sort_segments(void* d_keys, const uint32_t* d_offsets, size_t num_se
                                    workspace_bytes_, hip_stream), "lsdsort_segmented_device");
 }
 
+// The k best keys of every row of a row-major [rows x cols] array and their positions in the row, best first, without sorting the
+// rows (lsdsort_topk_device): exactly the first k columns of the rows' stable sort.  d_keys is only read; d_out_idx may be null.
+inline size_t topk_workspace_bytes(size_t rows, size_t cols, size_t k) { return lsdsort_topk_workspace_bytes(rows, cols, k); }
+inline void topk(const void* d_keys, size_t rows, size_t cols, size_t k, void* d_out_keys, uint32_t* d_out_idx, void* d_workspace,
+                 size_t workspace_bytes_, lsdsort_key_type key_type = LSDSORT_KEY_U32, bool largest = true, void* hip_stream = nullptr)
+{
+    check(lsdsort_topk_device(d_keys, rows, cols, k, key_type, largest ? 1 : 0, d_out_keys, d_out_idx, d_workspace, workspace_bytes_,
+                              hip_stream), "lsdsort_topk_device");
+}
+
 // A shard of a range-partitioned array: keys expected to share their top `common_prefix_bits` bits (a hint; the device checks)
 inline void sort_shard_device(uint32_t* d_keys, void* d_workspace, size_t workspace_bytes_, size_t n, int common_prefix_bits,
                               int radix_bits = 8, void* hip_stream = nullptr)

@@ -19,7 +19,7 @@ from .errors import LSDSORT_ALGO_ONESWEEP, LSDSORT_ALGO_STAGED, check
 __all__ = [
     "sort", "sort_pairs", "to_device", "to_host", "workspace_bytes", "GPULSDRadixSort",
     "GPULSDRadixSortTimed", "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
-    "MSBPartition", "SplitterPartition", "GPUSortTyped", "GPUSortWide", "GPUSortSegmented", "segmented_workspace_bytes", "sort_rows", "GPUSortMulti", "set_hybrid", "tile_keys", "set_tile_config", "set_rank_method", "rank_method", "set_xcd_chunk", "LSDSORT_ALGO_ONESWEEP", "LSDSORT_ALGO_STAGED",
+    "MSBPartition", "SplitterPartition", "GPUSortTyped", "GPUSortWide", "GPUSortSegmented", "segmented_workspace_bytes", "sort_rows", "GPUTopK", "topk_workspace_bytes", "topk_rows", "GPUSortMulti", "set_hybrid", "tile_keys", "set_tile_config", "set_rank_method", "rank_method", "set_xcd_chunk", "LSDSORT_ALGO_ONESWEEP", "LSDSORT_ALGO_STAGED",
 ]
 
 
@@ -295,6 +295,60 @@ def sort_rows(x, descending: bool = False, return_indices: bool = False, stream=
         if return_indices:
             return out, idx.view(rows, cols).to(torch.int64)
     return out
+
+
+def topk_workspace_bytes(rows: int, cols: int, k: int) -> int:
+    """Bytes of device workspace ``GPUTopK`` needs for the ``k`` best of each of ``rows`` rows of ``cols`` keys."""
+    return int(lib().lsdsort_topk_workspace_bytes(rows, cols, k))
+
+
+def GPUTopK(d_keys, k: int, key_type: str = "uint32", largest: bool = True, return_indices: bool = True, workspace=None,
+            stream=None, check_fault: bool = False):
+    """The ``k`` best keys of every row of ``d_keys`` (``lsdsort_topk_device``): a contiguous 1-D (one row) or 2-D int32 or
+    float32 CUDA tensor whose 32 bits compare as ``key_type`` ("uint32" / "int32" / "float32", IEEE total order).  Returns
+    ``(values, indices)`` -- ``[rows, k]`` (``[k]`` for 1-D input), best first, ``indices`` the int32 positions within the row,
+    or ``None`` without ``return_indices`` -- exactly the first ``k`` columns of the rows' stable sort: equal keys in position
+    order.  ``d_keys`` is only read.  Stream-ordered; the rows are not sorted (a radix select, then a sort of the winners)."""
+    torch = _torch()
+    if not (isinstance(d_keys, torch.Tensor) and d_keys.is_cuda and d_keys.is_contiguous() and d_keys.dim() in (1, 2)
+            and d_keys.dtype in (torch.int32, torch.float32)):
+        raise TypeError("d_keys: a contiguous 1-D or 2-D int32 or float32 CUDA tensor")
+    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
+    k = int(k)
+    if not 0 <= k <= cols:
+        raise ValueError("k must be within 0 .. the row length")
+    shape = (k,) if d_keys.dim() == 1 else (rows, k)
+    ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.stream(torch.cuda.current_stream())
+    with ctx:   # outputs and a temporary workspace belong to the stream the kernels run on
+        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
+        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
+        if workspace is None:
+            nbytes = topk_workspace_bytes(rows, cols, k)
+            if nbytes == 0:
+                raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_topk_workspace_bytes", "too many keys or rows")
+            workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=d_keys.device)
+    check(lib().lsdsort_topk_device(d_keys.data_ptr(), rows, cols, k, _KEY_TYPES[key_type], int(bool(largest)), values.data_ptr(),
+                                    indices.data_ptr() if return_indices else None, workspace.data_ptr(), workspace.numel(),
+                                    _stream(stream)), "lsdsort_topk_device")
+    if check_fault and rows and cols and k:
+        check(lib().lsdsort_check_device(workspace.data_ptr(), _stream(stream)), "lsdsort_check_device")
+    return values, indices
+
+
+def topk_rows(x, k: int, largest: bool = True, stream=None):
+    """``torch.topk(x, k, dim=-1, largest=largest, sorted=True)`` for a contiguous int32 / float32 CUDA tensor of one or more
+    dimensions: ``(values, int64 indices)``.  float32 follows IEEE total order, not torch's: NaNs by sign at the two ends
+    (+NaN above +inf, -NaN below -inf) and -0.0 below +0.0.  Among equal keys the lower position comes first, always."""
+    torch = _torch()
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() >= 1 and x.dtype in (torch.int32, torch.float32)):
+        raise TypeError("x: an int32 or float32 CUDA tensor")
+    cols = x.shape[-1]
+    ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.stream(torch.cuda.current_stream())
+    with ctx:
+        flat = x.contiguous().view(-1, cols)
+        values, indices = GPUTopK(flat, k, key_type="int32" if x.dtype == torch.int32 else "float32", largest=largest, stream=stream)
+        lead = tuple(x.shape[:-1])
+        return values.view(lead + (k,)), indices.view(lead + (k,)).to(torch.int64)
 
 
 def GPUSortWide(d_keys, d_vals=None, r: int = 8, workspace=None, stream=None, check_fault: bool = False):
