@@ -9,34 +9,22 @@
 #define LSDSORT_BUILD 1
 #include "../../include/lsdsort.h"
 
-#include <hip/hip_runtime.h>
-
 #include <atomic>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 
-#include "lsd_kernels.hpp"
+#include "lsd_host.hpp"
 
 namespace {
 
+using lsd::align_up;
+using lsd::env_flag;
 using lsd::PassParams;
 using lsd::TileShape;
 
 thread_local hipError_t g_last_hip = hipSuccess;
 
-#define LSD_HIP(expr)                         \
-    do {                                      \
-        hipError_t e__ = (expr);              \
-        if (e__ != hipSuccess) {              \
-            g_last_hip = e__;                 \
-            (void)hipGetLastError();          \
-            return LSDSORT_ERR_HIP;           \
-        }                                     \
-    } while (0)
-
-constexpr size_t kAlign = 256;
 constexpr size_t kControlBytes = 512;            // u32[128]: [0] fault word, [16 .. 16 + kPlanWords) the pass plan, then the hybrid form's words
 constexpr size_t kPlanOffsetWords = 16;
 constexpr size_t kHybridOffsetWords = kPlanOffsetWords + lsd::kPlanWords + 1;   // the hybrid form's plan words (hybrid.hip)
@@ -44,10 +32,7 @@ static_assert(kHybridOffsetWords + lsd::kHybridWords <= kControlBytes / sizeof(u
 // what the bucket rule gives BASELINE's sizes: 2^28 keys 2^15 buckets of 8192, 2^27 keys 2^14 of 8192, 2^27 pairs 2^15 of 4096
 static_assert(lsd::hybrid_bucket_bits((size_t)1 << 28, false) == 15 && lsd::hybrid_bucket_bits((size_t)1 << 27, false) == 14 &&
               lsd::hybrid_bucket_bits((size_t)1 << 27, true) == 15 && lsd::hybrid_bucket_bits((size_t)1 << 26, true) == 14, "bucket rule");
-std::atomic<int> g_hybrid{[] {                                          // lsdsort_set_hybrid; LSDSORT_HYBRID=0 starts it off
-    const char* e = getenv("LSDSORT_HYBRID");
-    return (e && e[0] == '0') ? 0 : 1;
-}()};
+std::atomic<int> g_hybrid{env_flag("LSDSORT_HYBRID", true)};            // lsdsort_set_hybrid; LSDSORT_HYBRID=0 starts it off
 // The hybrid form is tried for 8-bit-digit sorts whose AVERAGE bucket (top 15 bits from 2^27 keys, top 14 below) leaves the local
 // stage room: 4096 .. 14648 keys per bucket, 2^14 .. 2^16 buckets (below, tens of thousands of workgroups of almost nothing cost more than the two passes
 // they replace; above, the largest bucket of even uniform keys nears the 16384-key capacity).  Whether it RUNS is decided on the
@@ -65,7 +50,7 @@ constexpr size_t kHybridMaxKeys = (size_t)960 * 1000 * 1000;
 // (mean + 6 sigma); larger buckets go on the planner's list for the 16384-key variant.
 int hybrid_small_cap(size_t n, bool pairs)
 {
-    static const bool tiny = [] { const char* e = getenv("LSDSORT_LOCAL_TINY"); return !(e && e[0] == '0'); }();   // experiment knob
+    static const bool tiny = env_flag("LSDSORT_LOCAL_TINY", true);   // experiment knob
     const double mean = (double)(n >> lsd::hybrid_bucket_bits(n, pairs));
     if (tiny && mean + 6.0 * std::sqrt(mean) <= (double)lsd::kLocalSortCapTiny) return lsd::kLocalSortCapTiny;
     const int small = pairs ? lsd::kLocalSortCapSmallPairs : lsd::kLocalSortCapSmall;
@@ -74,14 +59,8 @@ int hybrid_small_cap(size_t n, bool pairs)
     if (mean + 1.5 * std::sqrt(mean) > (double)small) return lsd::kLocalSortCap;
     return small;
 }
-std::atomic<int> g_small_sort{[] {                                      // lsdsort_set_small_sort; LSDSORT_SMALL_SORT=0 starts it off
-    const char* e = getenv("LSDSORT_SMALL_SORT");
-    return (e && e[0] == '0') ? 0 : 1;
-}()};
-std::atomic<int> g_skip_dead_passes{[] {                                // lsdsort_set_pass_skipping; LSDSORT_PASS_SKIPPING=0 starts it off
-    const char* e = getenv("LSDSORT_PASS_SKIPPING");
-    return (e && e[0] == '0') ? 0 : 1;
-}()};
+std::atomic<int> g_small_sort{env_flag("LSDSORT_SMALL_SORT", true)};                  // lsdsort_set_small_sort; LSDSORT_SMALL_SORT=0 starts it off
+std::atomic<int> g_skip_dead_passes{env_flag("LSDSORT_PASS_SKIPPING", true)};         // lsdsort_set_pass_skipping; LSDSORT_PASS_SKIPPING=0 starts it off
 constexpr uint32_t kMaxXcdChunk = 64;
 
 // Pass-0 regions are by position: R0 keys each, a multiple of the tile (every tile is a multiple of 4096 keys, the
@@ -92,8 +71,6 @@ uint32_t region0_keys(size_t n, size_t tile, int regions)
     const size_t tiles = (per + tile - 1) / tile;
     return (uint32_t)((tiles ? tiles : 1) * tile);
 }
-
-size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 
 bool valid_radix(int r) { return r == 1 || r == 2 || r == 4 || r == 8; }
 
@@ -125,9 +102,8 @@ int class_shape(const ShapeClass& c, int radix_bits)
     return radix_bits == 8 ? c.shape8 : (radix_bits == 4 ? c.shape4 : c.shape_narrow);
 }
 
-const TileShape* current_shape(int radix_bits, bool pairs = false, size_t n = 0, int algorithm = LSDSORT_ALGO_STAGED)
+const TileShape* current_shape(int radix_bits, size_t n = 0, int algorithm = LSDSORT_ALGO_STAGED)
 {
-    (void)pairs;
     const TileShape* shapes = nullptr;
     const int count = lsd::tile_shapes(radix_bits, &shapes);
     if (count == 0) return nullptr;
@@ -242,13 +218,8 @@ std::mutex g_device_mutex;
 
 int check_device_ready(int* device_out = nullptr)
 {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        (void)hipGetLastError();
-        return LSDSORT_ERR_NO_DEVICE;
-    }
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+    int count = 0, dev = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
         (void)hipGetLastError();
         return LSDSORT_ERR_NO_DEVICE;
     }
@@ -315,32 +286,37 @@ int resolve_rank_method(int dev, int radix_bits)
 }
 
 struct StageEvents {
+    // The marks of a timed sort, in the order they are recorded.  Chained form: kStart | kCleared | kCounted after stage 1 |
+    // kScanned after stage 2 | where the hybrid form is tried, kLocalBegin and kLocalEnd around its local stage | one more after
+    // the last pass (last()).  Staged form: kStart | kCleared | kCounted, kScanned (both empty) | then three per pass
+    // (staged_mark): after its histogram, after its offset scan, after its scatter.
+    enum Mark : int { kStart, kCleared, kCounted, kScanned, kLocalBegin, kLocalEnd };
+    enum StagedMark : int { kPassBegin, kStagedHistogram, kStagedOffsets, kStagedScatter };   // kPassBegin: the mark before the pass
+    static int staged_mark(int pass, int which) { return kScanned + (int)kStagedScatter * pass + which; }
     hipEvent_t ev[3 * LSDSORT_MAX_PASSES + 4];
     hipEvent_t kernel_ev[2 * LSDSORT_MAX_PASSES];   // begin/end of each pass's rank-and-scatter kernel
     int kernel_count = 0;
     int count = 0;
-    bool enabled = false;
     hipStream_t stream = nullptr;
     int arm_kernel_events()   // the next rank-and-scatter launch of this thread reports into a fresh pair
     {
-        if (!enabled || kernel_count + 2 > 2 * LSDSORT_MAX_PASSES) return LSDSORT_OK;
-        LSD_HIP(hipEventCreate(&kernel_ev[kernel_count]));
-        kernel_count++;
-        LSD_HIP(hipEventCreate(&kernel_ev[kernel_count]));
-        kernel_count++;
+        if (kernel_count + 2 > 2 * LSDSORT_MAX_PASSES) return LSDSORT_OK;
+        for (int i = 0; i < 2; i++, kernel_count++) LSD_HIP(hipEventCreate(&kernel_ev[kernel_count]));
         lsd::t_launch_start = kernel_ev[kernel_count - 2];
         lsd::t_launch_stop = kernel_ev[kernel_count - 1];
         return LSDSORT_OK;
     }
     static void disarm_kernel_events() { lsd::t_launch_start = lsd::t_launch_stop = nullptr; }
-    int mark()
+    int mark(int which)   // in ascending order, none left out: `which` names the next one
     {
-        if (!enabled) return LSDSORT_OK;
+        if (which != count) return LSDSORT_ERR_INVALID_ARG;
         LSD_HIP(hipEventCreate(&ev[count]));
         LSD_HIP(hipEventRecord(ev[count], stream));
         count++;
         return LSDSORT_OK;
     }
+    int mark_last() { return mark(count); }
+    hipEvent_t last() const { return ev[count - 1]; }
     void destroy()
     {
         disarm_kernel_events();
@@ -349,12 +325,6 @@ struct StageEvents {
         count = kernel_count = 0;
     }
 };
-
-#define LSD_TRY(expr)                  \
-    do {                               \
-        int s__ = (expr);              \
-        if (s__ != LSDSORT_OK) return s__; \
-    } while (0)
 
 // Host-pointer entry (lsdsort_u32 and friends): the input arrives over PCIe in chunks on a copy stream and each
 // chunk's share of the upfront histogram runs behind it on the sort's stream, so stage 1 is hidden under the
@@ -375,312 +345,407 @@ const size_t kFeedChunkKeys = [] {                                      // 64 Mi
 }();
 constexpr int kMaxFeedEvents = (int)(((size_t)LSDSORT_MAX_KEYS >> 22) + 3);
 
-// The pass loop.  Marks (when timing), onesweep: 0 start | 1 after clear | 2 after stage 1 |
-// 3 after stage 2 | 4 after the last pass.  Staged: 0 start | 1 after clear | 2, 3 (empty) | then per
-// pass three marks: after its histogram, after its offset scan, after its scatter.
-int run_sort(uint32_t* d_keys, uint32_t* d_vals, void* d_ws, size_t ws_bytes, size_t n, int radix_bits,
-             int algorithm, hipStream_t stream, StageEvents* ev, lsdsort_timing* timing,
-             const lsd::KeyTransform& xf = lsd::KeyTransform{}, const HostFeed* feed = nullptr,
-             uint32_t* const* d_more = nullptr, int more = 0,   // further payload arrays (0..2), chained form only
-             int prefix = 0)   // lsdsort_u32_device_prefixed's argument: checked, not needed (the device finds the key prefix itself)
+// What a sort is asked to do.  The C entries fill the fields they use.
+struct SortRequest {
+    uint32_t *keys = nullptr, *vals = nullptr;   // vals null: keys only
+    uint32_t* const* more = nullptr;       // further payload arrays, chained form only
+    int num_more = 0;                      // how many: 0..2
+    void* ws = nullptr;
+    size_t ws_bytes = 0, n = 0;
+    int radix_bits = 8, algorithm = LSDSORT_ALGO_ONESWEEP;
+    hipStream_t stream = nullptr;
+    lsd::KeyTransform xf{};                // typed sorts
+    const HostFeed* feed = nullptr;        // the host-pointer entries
+    StageEvents* ev = nullptr;             // lsdsort_u32_device_timed
+    lsdsort_timing* timing = nullptr;
+    SortRequest(uint32_t* d_keys, uint32_t* d_vals, void* d_ws, size_t bytes, size_t count, int radix, void* hip_stream)
+        : keys(d_keys), vals(d_vals), ws(d_ws), ws_bytes(bytes), n(count), radix_bits(radix), stream(static_cast<hipStream_t>(hip_stream)) {}
+};
+
+int mark(const SortRequest& rq, int which) { return rq.ev ? rq.ev->mark(which) : LSDSORT_OK; }
+
+// Where a chain of rank-and-scatter passes keeps its state in a workspace (the sort's, or the MSB partition's single pass).
+struct Chain {
+    uint32_t* control = nullptr;                // word 0: the fault word
+    uint32_t* tickets = nullptr;                // [slots][kMaxRegions] arrival ticket dispensers
+    uint32_t* tables = nullptr;                 // [slots] region tables, table_words each
+    uint32_t* status[2] = {nullptr, nullptr};   // tile-status words: a pass works in one array and clears the other
+    size_t table_words = 0;
+    uint32_t rows = 0;                          // status rows = grid size
+};
+
+// What a sort decided about itself, once, before its first launch; read-only from then on.
+struct SortPlan {
+    const TileShape* shape = nullptr;
+    Layout L;
+    int rank_method = 0, passes = 0;
+    uint32_t payloads = 0, mute_row = 0;   // PassParams::num_payloads (0 = keys only, 1 = pairs, up to 3); mute_row: diagnostic builds only
+    bool small = false;               // the one-launch small sort serves the call
+    Chain chain;                      // chain.control is the control block of either form
+    uint32_t* counts = nullptr;       // chained: [P][H][regions] joint / digit counts
+    uint32_t *alt_keys = nullptr, *alt_vals = nullptr, *alt_more[2] = {nullptr, nullptr};
+    uint32_t* plan = nullptr;         // the pass plan in the control block; null: every pass runs, ping-pong by parity
+    uint32_t* hyb = nullptr;          // the hybrid form's plan words in the control block; null: not tried, and none of its fields below set
+    uint32_t* fields = nullptr;       // 8-bit digits: field A (upfront read) | field B (planner).  4-bit: fields A-D (planner)
+    uint32_t* joint = nullptr;        // 4-bit digits: the joint field (upfront read)
+    uint32_t* bucket = nullptr;       // [32768] bucket counts
+    uint32_t* bases = nullptr;        // [32769] bucket bases, then the list of large buckets
+    int bucket_bits = 0, small_cap = 0;   // small_cap: capacity of the local stage's launch over all buckets
+    uint32_t *tile_hist = nullptr, *tile_global = nullptr, *scratch = nullptr;   // staged form
+};
+
+int validate(const SortRequest& rq)
 {
-    if (prefix < 0 || prefix > 8) return LSDSORT_ERR_INVALID_ARG;
-    if (more < 0 || more > 2 || (more > 0 && (!d_vals || !d_more || algorithm != LSDSORT_ALGO_ONESWEEP || feed))) return LSDSORT_ERR_INVALID_ARG;
-    for (int e = 0; e < more; e++)
-        if (n > 0 && !d_more[e]) return LSDSORT_ERR_INVALID_ARG;
-    if (feed && algorithm != LSDSORT_ALGO_ONESWEEP) return LSDSORT_ERR_INVALID_ARG;
-    if (xf.on && (algorithm != LSDSORT_ALGO_ONESWEEP || radix_bits < 4)) return LSDSORT_ERR_UNSUPPORTED;
-    if (!valid_radix(radix_bits)) return LSDSORT_ERR_INVALID_ARG;
-    if (algorithm != LSDSORT_ALGO_ONESWEEP && algorithm != LSDSORT_ALGO_STAGED) return LSDSORT_ERR_INVALID_ARG;
-    if (n > LSDSORT_MAX_KEYS) return LSDSORT_ERR_TOO_LARGE;
-    if (n == 0) return LSDSORT_OK;
-    if (!d_keys) return LSDSORT_ERR_INVALID_ARG;
+    if (rq.num_more < 0 || rq.num_more > 2) return LSDSORT_ERR_INVALID_ARG;
+    if (rq.num_more > 0 && (!rq.vals || !rq.more || rq.algorithm != LSDSORT_ALGO_ONESWEEP || rq.feed)) return LSDSORT_ERR_INVALID_ARG;
+    for (int e = 0; e < rq.num_more; e++)
+        if (rq.n > 0 && !rq.more[e]) return LSDSORT_ERR_INVALID_ARG;
+    if (rq.feed && rq.algorithm != LSDSORT_ALGO_ONESWEEP) return LSDSORT_ERR_INVALID_ARG;
+    if (rq.xf.on && (rq.algorithm != LSDSORT_ALGO_ONESWEEP || rq.radix_bits < 4)) return LSDSORT_ERR_UNSUPPORTED;
+    if (!valid_radix(rq.radix_bits)) return LSDSORT_ERR_INVALID_ARG;
+    if (rq.algorithm != LSDSORT_ALGO_ONESWEEP && rq.algorithm != LSDSORT_ALGO_STAGED) return LSDSORT_ERR_INVALID_ARG;
+    if (rq.n > LSDSORT_MAX_KEYS) return LSDSORT_ERR_TOO_LARGE;
+    return LSDSORT_OK;
+}
+
+int make_plan(const SortRequest& rq, SortPlan* out)
+{
+    SortPlan& sp = *out;
+    if (!rq.keys) return LSDSORT_ERR_INVALID_ARG;
     int dev = 0;
     LSD_TRY(check_device_ready(&dev));
-    const int rank_method = resolve_rank_method(dev, radix_bits);
-    const bool pairs = d_vals != nullptr;
-    const TileShape* shape = current_shape(radix_bits, pairs, n, algorithm);
-    if (!shape) return LSDSORT_ERR_INVALID_ARG;
-    const Layout L = make_layout(n, radix_bits, pairs ? 1 + more : 0, algorithm, *shape);
-    if (!d_ws || (reinterpret_cast<uintptr_t>(d_ws) & (kAlign - 1)) || ws_bytes < L.total) return LSDSORT_ERR_WORKSPACE;
-
-    char* ws = static_cast<char*>(d_ws);
-    uint32_t* control = reinterpret_cast<uint32_t*>(ws + L.control);
-    uint32_t* alt_keys = reinterpret_cast<uint32_t*>(ws + L.alt_keys);
-    uint32_t* alt_vals = pairs ? reinterpret_cast<uint32_t*>(ws + L.alt_vals) : nullptr;
-    const int passes = 32 / radix_bits;
-    uint32_t mute_row = g_mute_row.load(std::memory_order_relaxed);
+    const int radix_bits = rq.radix_bits;
+    const size_t n = rq.n;
+    const bool pairs = rq.vals != nullptr;
+    const bool chained = rq.algorithm == LSDSORT_ALGO_ONESWEEP;
+    sp.rank_method = resolve_rank_method(dev, radix_bits);
+    sp.shape = current_shape(radix_bits, n, rq.algorithm);
+    if (!sp.shape) return LSDSORT_ERR_INVALID_ARG;
+    sp.payloads = pairs ? (uint32_t)(1 + rq.num_more) : 0u;
+    const Layout& L = sp.L = make_layout(n, radix_bits, (int)sp.payloads, rq.algorithm, *sp.shape);
+    if (!lsd::workspace_ok(rq.ws, rq.ws_bytes, L.total)) return LSDSORT_ERR_WORKSPACE;
+    sp.passes = 32 / radix_bits;
+    sp.mute_row = g_mute_row.load(std::memory_order_relaxed);
 #ifdef LSD_FAULT_INJECT
     {   // "the next k sorts only" (lsdsort_debug_fault_inject_sorts): e.g. the first of the two sorts inside lsdsort_u64_device
         int left = g_mute_sorts.load(std::memory_order_relaxed);
-        if (left == 0) mute_row = 0;
+        if (left == 0) sp.mute_row = 0;
         else if (left > 0) g_mute_sorts.store(left - 1, std::memory_order_relaxed);
     }
 #endif
-    if (timing) {
-        timing->passes = passes;
-        timing->tile_keys = shape->tile();
-        timing->tiles = (int)L.tiles;
-    }
-
     // Up to 16384 items: one workgroup sorts them in its LDS, one launch (local_sort.hip) -- at this size the chained form's eight
     // launches are nothing but their own latencies.  Plain uint32 keys and pairs with the returning-add rank form; not when timed.
-    if (g_small_sort.load(std::memory_order_relaxed) && n <= (size_t)lsd::kLocalSortCap && algorithm == LSDSORT_ALGO_ONESWEEP && !ev && !timing && !xf.on && more == 0 && !feed &&
-        rank_method == lsd::kRankLdsAdd && mute_row == 0) {
-        LSD_HIP(lsd::launch_small_sort(d_keys, d_vals, (uint32_t)n, control, control + kHybridOffsetWords + lsd::kHybridWordOk, stream));
+    sp.small = g_small_sort.load(std::memory_order_relaxed) && n <= (size_t)lsd::kLocalSortCap && chained && !rq.ev && !rq.timing &&
+               !rq.xf.on && rq.num_more == 0 && !rq.feed && sp.rank_method == lsd::kRankLdsAdd && sp.mute_row == 0;
+    // The hybrid form (hybrid.hip): two global passes on the high bytes, then every top-15-bit bucket finished in LDS -- 28 B/key
+    // instead of 36.  Tried here for keys-only sorts of the sizes it pays for; the device decides from the exact bucket counts, and
+    // every kernel of the form that does NOT run returns at once (plan words in the control block).
+    sp.bucket_bits = lsd::hybrid_bucket_bits(n, pairs);
+    const bool try_hybrid = chained && (radix_bits == 8 || radix_bits == 4) && !rq.feed && sp.rank_method == lsd::kRankLdsAdd &&
+                            n >= hybrid_min_items(radix_bits, pairs) && n <= kHybridMaxKeys &&
+                            (n >> sp.bucket_bits) <= lsd::kHybridMaxMeanBucket && sp.shape->tile() == 32768 &&
+                            g_hybrid.load(std::memory_order_relaxed);
+    auto at = [&rq](size_t offset) { return reinterpret_cast<uint32_t*>(static_cast<char*>(rq.ws) + offset); };
+    uint32_t* control = sp.chain.control = at(L.control);
+    sp.alt_keys = at(L.alt_keys);
+    if (pairs) sp.alt_vals = at(L.alt_vals);
+    for (int e = 0; e < rq.num_more; e++) sp.alt_more[e] = at(L.alt_more[e]);
+    if (!chained) {
+        sp.tile_hist = at(L.tile_hist);
+        sp.tile_global = at(L.tile_global);
+        sp.scratch = at(L.scratch);
         return LSDSORT_OK;
     }
-
-    if (ev) LSD_TRY(ev->mark());
-    LSD_HIP(hipMemsetAsync(ws, 0, L.zero_bytes, stream));
-    if (ev) LSD_TRY(ev->mark());
-
-    uint32_t* tables = nullptr;
-    const size_t table_words = lsd::region_table_words(radix_bits);
+    sp.chain.tickets = at(L.tickets);
+    sp.chain.tables = at(L.tables);
+    sp.chain.table_words = lsd::region_table_words(radix_bits);
+    sp.chain.status[0] = at(L.status);
+    sp.chain.status[1] = at(L.status_odd);
+    sp.chain.rows = L.rows;
+    sp.counts = at(L.counts);
     // Passes whose digit is the same for every key are the identity: stage 2 sees that in the counts and writes a plan the
     // pass kernels follow (lsd_kernels.hpp, PassParams::plan) -- small key ranges, dead digits and constant input then cost
     // the passes that move something, plus one copy if their number is odd.  Not for typed sorts (their first and last
     // pass carry the key transform) nor where the plan would not fit the control block.
     // A typed sort gets a plan only where the hybrid form is tried (its kernels are told by the plan which form runs), and that plan
     // never skips a pass.
-    const bool try_hybrid = algorithm == LSDSORT_ALGO_ONESWEEP && (radix_bits == 8 || radix_bits == 4) && !feed &&
-                            rank_method == lsd::kRankLdsAdd && n >= hybrid_min_items(radix_bits, pairs) &&
-                            n <= kHybridMaxKeys &&
-                            (n >> lsd::hybrid_bucket_bits(n, pairs)) <= lsd::kHybridMaxMeanBucket && shape->tile() == 32768 &&
-                            g_hybrid.load(std::memory_order_relaxed);
-    uint32_t* plan = nullptr;
-    if (algorithm == LSDSORT_ALGO_ONESWEEP && (!xf.on || try_hybrid) && 2 * passes + 1 <= lsd::kPlanWords &&
-        g_skip_dead_passes.load(std::memory_order_relaxed))
-        plan = control + kPlanOffsetWords;
-    // The hybrid form (hybrid.hip): two global passes on the high bytes, then every top-15-bit bucket finished in LDS -- 28 B/key
-    // instead of 36.  Tried here for keys-only sorts of the sizes it pays for; the device decides from the exact bucket counts, and
-    // every kernel of the form that does NOT run returns at once (plan words in the control block).
-    uint32_t* hyb = nullptr;
-    if (plan && try_hybrid) hyb = control + kHybridOffsetWords;
-    if (timing) timing->hybrid = hyb ? -1 : 0;   // -1: tried; lsdsort_u32_device_timed reads the device's verdict back
-    if (algorithm == LSDSORT_ALGO_ONESWEEP) {
-        uint32_t* counts = reinterpret_cast<uint32_t*>(ws + L.counts);
-        tables = reinterpret_cast<uint32_t*>(ws + L.tables);
-        if (hyb) {
-            // 8-bit digits: field A (upfront read) | field B (planner).  4-bit: fields A-D (planner) | the joint field (upfront read)
-            uint32_t* fields = reinterpret_cast<uint32_t*>(ws + L.hyb_counts);
-            uint32_t* joint = fields + lsd::hybrid_field_words(radix_bits);
-            uint32_t* bucket = joint + lsd::hybrid_joint_words(radix_bits);
-            const int bb = lsd::hybrid_bucket_bits(n, pairs);
-            LSD_HIP(lsd::launch_hybrid_sample(d_keys, (uint32_t)n, bb, hyb, stream));
-            LSD_HIP(lsd::launch_hybrid_histograms(radix_bits, d_keys, (uint32_t)n, L.region0, radix_bits == 8 ? fields : joint, bucket, bb,
-                                                  hyb, stream, xf));
-            uint32_t* bases = reinterpret_cast<uint32_t*>(ws + L.hyb_bases);
-            LSD_HIP(lsd::launch_hybrid_plan(radix_bits, bucket, (uint32_t)n, bb, bases, radix_bits == 8 ? fields + 2048 : fields, joint, hyb,
-                                            bases + lsd::kHybridBuckets + 1,
-                                            (uint32_t)hybrid_small_cap(n, pairs), stream));
-#ifdef LSD_FAULT_INJECT
-            {   // diagnostic build only: the hybrid form's own fields falsified behind the planner (its verdict stands)
-                CorruptCounts c;
-                {
-                    std::lock_guard<std::mutex> lock(g_corrupt_mutex);
-                    c = g_corrupt;
-                }
-                if (c.delta && (c.keep_sum & 2u)) {
-                    hipLaunchKernelGGL(corrupt_counts_kernel, dim3(1), dim3(1), 0, stream, fields, c);
-                    LSD_HIP(hipGetLastError());
-                }
-            }
-#endif
-            // the global passes' region tables: the first one's regions are by position (like any first pass), the others' by the
-            // top bits of the digit before -- exactly what stage 2 builds for consecutive passes
-            // (no fault word: where the sample or the planner has said no these counts are partial or absent, and nobody uses the tables)
-            LSD_HIP(lsd::launch_scan_regions(radix_bits, lsd::hybrid_global_passes(radix_bits), L.regions, fields, (uint32_t)n,
-                                             (uint32_t)shape->tile(), L.region0, tables + (size_t)passes * table_words, stream, nullptr, nullptr));
-        }
-        // stage 1 over [first, first + len): the whole array at once, or chunk by chunk behind the host's copies
-        auto histogram = [&](size_t first, size_t len) -> int {
-            if (L.regions > 1)
-                LSD_HIP(lsd::launch_joint_histograms(radix_bits, d_keys + first, (uint32_t)len, L.region0, counts, stream, xf, (uint32_t)first,
-                                                     hyb ? hyb + lsd::kHybridWordOk : nullptr));
-            else
-                LSD_HIP(lsd::launch_digit_histograms(radix_bits, passes, 0, d_keys + first, (uint32_t)len, counts, stream));
-            return LSDSORT_OK;
-        };
-        if (!feed) {
-            LSD_TRY(histogram(0, n));
-        } else {
-            int e = 0;
-            for (size_t first = 0; first < n; first += kFeedChunkKeys, e++) {
-                const size_t len = n - first < kFeedChunkKeys ? n - first : kFeedChunkKeys;
-                LSD_HIP(hipMemcpyAsync(d_keys + first, feed->host_keys + first, len * sizeof(uint32_t), hipMemcpyHostToDevice, feed->copy));   // .cu:1001
-                LSD_HIP(hipEventRecord(feed->events[e], feed->copy));
-                LSD_HIP(hipStreamWaitEvent(stream, feed->events[e], 0));
-                LSD_TRY(histogram(first, len));
-            }
-            if (pairs) {
-                LSD_HIP(hipMemcpyAsync(d_vals, feed->host_vals, n * sizeof(uint32_t), hipMemcpyHostToDevice, feed->copy));
-                LSD_HIP(hipEventRecord(feed->events[e], feed->copy));
-                LSD_HIP(hipStreamWaitEvent(stream, feed->events[e], 0));
-            }
-        }
-        if (ev) LSD_TRY(ev->mark());
-#ifdef LSD_FAULT_INJECT
-        {   // diagnostic build only: move counts between two bins so that the tables no longer describe the keys
-            CorruptCounts c;
-            {
-                std::lock_guard<std::mutex> lock(g_corrupt_mutex);
-                c = g_corrupt;
-            }
-            if (c.delta && !(c.keep_sum & 2u)) {
-                hipLaunchKernelGGL(corrupt_counts_kernel, dim3(1), dim3(1), 0, stream, counts, c);
-                LSD_HIP(hipGetLastError());
-            }
-        }
-#endif
-        LSD_HIP(lsd::launch_scan_regions(radix_bits, passes, L.regions, counts, (uint32_t)n, (uint32_t)shape->tile(),
-                                         L.region0, tables, stream, plan, control, hyb ? hyb + lsd::kHybridWordOk : nullptr, !xf.on));
-        if (ev) LSD_TRY(ev->mark());
-        if (hyb) {
-            // bits 16-31, lowest digit first: caller's buffer -> alternate and back (an even number of passes); then the buckets in place
-            const int hyb_passes = lsd::hybrid_global_passes(radix_bits);
-            for (int g = 0; g < hyb_passes; g++) {
-                PassParams p{};
-                p.in = d_keys;
-                p.out = alt_keys;
-                p.vals_in = d_vals;
-                p.vals_out = alt_vals;
-                p.num_payloads = pairs ? (uint32_t)(1 + more) : 0u;
-                for (int e = 0; e < more; e++) {   // the plan word says which way round (as for the first payload array)
-                    p.more_in[e] = d_more[e];
-                    p.more_out[e] = reinterpret_cast<uint32_t*>(ws + L.alt_more[e]);
-                }
-                p.n = (uint32_t)n;
-                p.shift = (uint32_t)(16 + radix_bits * g);
-                p.shift_word = hyb + lsd::kHybridWordShift + g;   // ... less the key prefix the device found: bits [16 - t, 32 - t)
-                p.num_tiles = L.rows;
-                p.fault = control;
-                p.spin_limit = g_spin_limit.load(std::memory_order_relaxed);
-                p.regions = tables + (size_t)(passes + g) * table_words;
-                p.status = reinterpret_cast<uint32_t*>(ws + ((g & 1) ? L.status_odd : L.status));
-                p.status_clear = g + 1 < hyb_passes ? reinterpret_cast<uint32_t*>(ws + ((g & 1) ? L.status : L.status_odd)) : nullptr;
-                p.tickets = reinterpret_cast<uint32_t*>(ws + L.tickets) + (size_t)(passes + g) * lsd::kMaxRegions;
-                p.plan = hyb + lsd::kHybridWordPlan + 2 * g;
-                if (xf.on && g == 0) p.xin = xf;   // typed sorts: sortable keys from the first store on; the local stage's store turns them back
-                p.stats = g_stats.load(std::memory_order_relaxed);
-                if (ev) LSD_TRY(ev->arm_kernel_events());
-                const hipError_t launched = lsd::launch_rank_scatter(radix_bits, *shape, rank_method, true, p, stream);
-                StageEvents::disarm_kernel_events();
-                LSD_HIP(launched);
-            }
-            lsd::LocalSortParams lp{};
-            lp.keys = d_keys;
-            lp.vals = d_vals;
-            lp.num_payloads = pairs ? (uint32_t)(1 + more) : 0u;
-            for (int e = 0; e < more; e++) lp.more[e] = d_more[e];
-            lp.bases = reinterpret_cast<const uint32_t*>(ws + L.hyb_bases);
-            const int bb = lsd::hybrid_bucket_bits(n, pairs);
-            lp.num_buckets = 1u << bb;
-            lp.low_bits_word = hyb + lsd::kHybridWordLowBits;   // the bits below a bucket's own: 32 - bb less the key prefix the device found
-            lp.skip = hyb + lsd::kHybridWordSkipLocal;
-            lp.xout = xf;
-            lp.fault = control;
-            if (ev) LSD_TRY(ev->mark());
-            // buckets of up to 10240 keys (all of them on uniform keys of most sizes): three workgroups per CU; where uniform keys
-            // stay under 5120 a bucket, four
-            const int all_cap = hybrid_small_cap(n, pairs);
-            lp.small_variant = all_cap == lsd::kLocalSortCapTiny ? 2u : all_cap == lsd::kLocalSortCap ? 0u : 1u;
-            lp.larger_elsewhere = 1;
-            LSD_HIP(lsd::launch_local_sort(lp, stream));
-            lp.small_variant = 0;     // the planner's list of larger ones (up to 16384 keys): two per CU, a grid of 512 walks the list
-            lp.larger_elsewhere = 0;
-            lp.list = lp.bases + lsd::kHybridBuckets + 1;
-            lp.list_count = hyb + lsd::kHybridWordLargeCount;
-            LSD_HIP(lsd::launch_local_sort(lp, stream));
-            if (ev) LSD_TRY(ev->mark());
-        }
-    } else if (ev) {
-        LSD_TRY(ev->mark());
-        LSD_TRY(ev->mark());
-    }
-
-    uint32_t* src = d_keys;
-    uint32_t* dst = alt_keys;
-    uint32_t* vsrc = d_vals;
-    uint32_t* vdst = alt_vals;
-    for (int pass = 0; pass < passes; pass++) {
-        PassParams p{};
-        p.in = src;
-        p.out = dst;
-        p.vals_in = vsrc;
-        p.vals_out = vdst;
-        p.n = (uint32_t)n;
-        p.shift = (uint32_t)(pass * radix_bits);
-        p.num_tiles = L.tiles;
-        p.fault = control;
-        p.spin_limit = g_spin_limit.load(std::memory_order_relaxed);
-        p.mute_row = mute_row;
-        p.xcd_chunk = g_xcd_chunk.load(std::memory_order_relaxed);
-        p.stats = g_stats.load(std::memory_order_relaxed);
-        if (algorithm == LSDSORT_ALGO_ONESWEEP) {
-            p.num_tiles = L.rows;
-            p.regions = tables + (size_t)pass * table_words;
-            // The status rows a pass uses depend on its regions, so a row may sit out a pass and the
-            // parity-coded reuse of lsd_device.hpp (every word rewritten every pass) does not apply.
-            // Two status arrays instead: a pass works in one and its workgroups clear the other, one
-            // row each (the grid has exactly `rows` workgroups), for the pass after it -- 1 KiB of plain
-            // stores per 64 KiB tile and no launch between the passes.  The sort's opening memset
-            // covers the even array.
-            p.status = reinterpret_cast<uint32_t*>(ws + ((pass & 1) ? L.status_odd : L.status));
-            p.status_clear = pass + 1 < passes ? reinterpret_cast<uint32_t*>(ws + ((pass & 1) ? L.status : L.status_odd)) : nullptr;
-            p.tickets = reinterpret_cast<uint32_t*>(ws + L.tickets) + (size_t)pass * lsd::kMaxRegions;
-            p.parity = 0;
-            // further payload arrays ping-pong like the first: even passes read the caller's, odd passes the alternates
-            p.num_payloads = pairs ? (uint32_t)(1 + more) : 0u;
-            for (int e = 0; e < more; e++) {
-                uint32_t* mine = d_more[e];
-                uint32_t* alt = reinterpret_cast<uint32_t*>(ws + L.alt_more[e]);
-                p.more_in[e] = (pass & 1) && !plan ? alt : mine;
-                p.more_out[e] = (pass & 1) && !plan ? mine : alt;
-            }
-            if (plan) {   // the same pair for every pass: the plan says which way round (and whether at all)
-                p.in = d_keys;
-                p.out = alt_keys;
-                p.vals_in = d_vals;
-                p.vals_out = alt_vals;
-                p.plan = plan + 2 * pass;
-                p.plan_first = hyb ? 1u : 0u;   // a sort that tried the hybrid form: these passes leave at once if it runs
-            }
-            if (xf.on && pass == 0) p.xin = xf;
-            if (xf.on && pass + 1 == passes) p.xout = xf;
-            if (ev) LSD_TRY(ev->arm_kernel_events());
-            const hipError_t launched = lsd::launch_rank_scatter(radix_bits, *shape, rank_method, true, p, stream);
-            StageEvents::disarm_kernel_events();
-            LSD_HIP(launched);
-        } else {
-            uint32_t* tile_hist = reinterpret_cast<uint32_t*>(ws + L.tile_hist);
-            uint32_t* tile_global = reinterpret_cast<uint32_t*>(ws + L.tile_global);
-            uint32_t* scratch = reinterpret_cast<uint32_t*>(ws + L.scratch);
-            LSD_HIP(lsd::launch_tile_histograms(radix_bits, *shape, src, (uint32_t)n, p.shift, tile_hist, stream));
-            if (ev) LSD_TRY(ev->mark());
-            // local offsets are recomputed inside the rank-and-scatter kernel (it needs them for
-            // ranking anyway); only the global table is materialised here.
-            LSD_HIP(lsd::launch_tile_offsets(radix_bits, tile_hist, nullptr, tile_global, L.tiles, scratch, stream));
-            if (ev) LSD_TRY(ev->mark());
-            p.global_off = tile_global;
-            LSD_HIP(lsd::launch_rank_scatter(radix_bits, *shape, rank_method, false, p, stream));
-        }
-        // Chained form: the passes are launched back to back and only the last one is followed by a
-        // mark -- an event record between two dependent kernels costs ~20 us of queue bubble, which is
-        // not the kernel's time (rocprofv3's kernel trace would disagree by 5 %).
-        if (ev && (algorithm != LSDSORT_ALGO_ONESWEEP || pass + 1 == passes)) LSD_TRY(ev->mark());
-        uint32_t* t = src; src = dst; dst = t;
-        t = vsrc; vsrc = vdst; vdst = t;
-    }
-    // 32 / radix_bits is even for every accepted radix: the result is back in d_keys/d_vals,
-    // as the reference relies on (.cu:905, .cu:1005) -- unless the plan skipped an odd number of passes
-    if (plan) {
-        LSD_HIP(lsd::launch_finish_plan(plan + 2 * passes, d_keys, alt_keys, d_vals, alt_vals, (uint32_t)n, stream));
-        for (int e = 0; e < more; e++)   // the same copy back for each further payload array
-            LSD_HIP(lsd::launch_finish_plan(plan + 2 * passes, d_more[e], reinterpret_cast<uint32_t*>(ws + L.alt_more[e]), nullptr, nullptr,
-                                            (uint32_t)n, stream));
+    if ((!rq.xf.on || try_hybrid) && 2 * sp.passes + 1 <= lsd::kPlanWords && g_skip_dead_passes.load(std::memory_order_relaxed))
+        sp.plan = control + kPlanOffsetWords;
+    if (sp.plan && try_hybrid) {
+        sp.hyb = control + kHybridOffsetWords;
+        sp.fields = at(L.hyb_counts);
+        sp.joint = sp.fields + lsd::hybrid_field_words(radix_bits);
+        sp.bucket = sp.joint + lsd::hybrid_joint_words(radix_bits);
+        sp.bases = at(L.hyb_bases);
+        sp.small_cap = hybrid_small_cap(n, pairs);
     }
     return LSDSORT_OK;
+}
+
+// Diagnostic build only: the count corruption tests/test_fault_path.py asks for, behind the stage that made the counts -- the sort's
+// own table behind stage 1, or (keep_sum bit 1) the hybrid form's fields behind its planner, whose verdict stands.
+int inject_count_fault([[maybe_unused]] const SortRequest& rq, [[maybe_unused]] const SortPlan& sp, [[maybe_unused]] bool hybrid_fields)
+{
+#ifdef LSD_FAULT_INJECT
+    CorruptCounts c;
+    {
+        std::lock_guard<std::mutex> lock(g_corrupt_mutex);
+        c = g_corrupt;
+    }
+    if (c.delta && ((c.keep_sum & 2u) != 0) == hybrid_fields) {
+        hipLaunchKernelGGL(corrupt_counts_kernel, dim3(1), dim3(1), 0, rq.stream, hybrid_fields ? sp.fields : sp.counts, c);
+        LSD_HIP(hipGetLastError());
+    }
+#endif
+    return LSDSORT_OK;
+}
+
+// The fields every chained rank-and-scatter launch fills.  `slot` picks the pass's region table and ticket dispensers, `step`
+// (its place in a run of passes launched back to back) its status array; the last pass of a run clears none.
+PassParams chained_pass(const Chain& c, const uint32_t* in, uint32_t* out, size_t n, uint32_t shift, int slot, int step, bool last)
+{
+    PassParams p{};
+    p.in = in;
+    p.out = out;
+    p.n = (uint32_t)n;
+    p.shift = shift;
+    p.num_tiles = c.rows;
+    p.fault = c.control;
+    p.spin_limit = g_spin_limit.load(std::memory_order_relaxed);
+    p.regions = c.tables + (size_t)slot * c.table_words;
+    // The status rows a pass uses depend on its regions, so a row may sit out a pass and the
+    // parity-coded reuse of lsd_device.hpp (every word rewritten every pass) does not apply.
+    // Two status arrays instead: a pass works in one and its workgroups clear the other, one
+    // row each (the grid has exactly `rows` workgroups), for the pass after it -- 1 KiB of plain
+    // stores per 64 KiB tile and no launch between the passes.  The sort's opening memset
+    // covers the even array.
+    p.status = c.status[step & 1];
+    p.status_clear = last ? nullptr : c.status[(step + 1) & 1];
+    p.tickets = c.tickets + (size_t)slot * lsd::kMaxRegions;
+    p.parity = 0;
+    return p;
+}
+
+// A chained pass of the sort itself: the payload arrays travel with the keys.  back: from the alternates into the caller's arrays.
+PassParams sort_pass(const SortRequest& rq, const SortPlan& sp, uint32_t shift, int slot, int step, bool last, bool back)
+{
+    PassParams p = chained_pass(sp.chain, back ? sp.alt_keys : rq.keys, back ? rq.keys : sp.alt_keys, rq.n, shift, slot, step, last);
+    p.vals_in = back ? sp.alt_vals : rq.vals;
+    p.vals_out = back ? rq.vals : sp.alt_vals;
+    p.num_payloads = sp.payloads;
+    for (int e = 0; e < rq.num_more; e++) {
+        p.more_in[e] = back ? sp.alt_more[e] : rq.more[e];
+        p.more_out[e] = back ? rq.more[e] : sp.alt_more[e];
+    }
+    p.stats = g_stats.load(std::memory_order_relaxed);
+    return p;
+}
+
+int launch_sort_pass(const SortRequest& rq, const SortPlan& sp, const PassParams& p)
+{
+    if (rq.ev) LSD_TRY(rq.ev->arm_kernel_events());
+    const hipError_t launched = lsd::launch_rank_scatter(rq.radix_bits, *sp.shape, sp.rank_method, true, p, rq.stream);
+    StageEvents::disarm_kernel_events();
+    LSD_HIP(launched);
+    return LSDSORT_OK;
+}
+
+int small_sort(const SortRequest& rq, const SortPlan& sp)
+{
+    uint32_t* control = sp.chain.control;
+    LSD_HIP(lsd::launch_small_sort(rq.keys, rq.vals, (uint32_t)rq.n, control, control + kHybridOffsetWords + lsd::kHybridWordOk, rq.stream));
+    return LSDSORT_OK;
+}
+
+// The hybrid form's upfront work: sample, bucket histograms, planner, and the region tables of its global passes.
+int hybrid_upfront(const SortRequest& rq, const SortPlan& sp)
+{
+    const int radix_bits = rq.radix_bits;
+    const uint32_t n = (uint32_t)rq.n;
+    LSD_HIP(lsd::launch_hybrid_sample(rq.keys, n, sp.bucket_bits, sp.hyb, rq.stream));
+    LSD_HIP(lsd::launch_hybrid_histograms(radix_bits, rq.keys, n, sp.L.region0, radix_bits == 8 ? sp.fields : sp.joint, sp.bucket,
+                                          sp.bucket_bits, sp.hyb, rq.stream, rq.xf));
+    LSD_HIP(lsd::launch_hybrid_plan(radix_bits, sp.bucket, n, sp.bucket_bits, sp.bases, radix_bits == 8 ? sp.fields + 2048 : sp.fields,
+                                    sp.joint, sp.hyb, sp.bases + lsd::kHybridBuckets + 1, (uint32_t)sp.small_cap, rq.stream));
+    LSD_TRY(inject_count_fault(rq, sp, true));
+    // the global passes' region tables: the first one's regions are by position (like any first pass), the others' by the
+    // top bits of the digit before -- exactly what stage 2 builds for consecutive passes
+    // (no fault word: where the sample or the planner has said no these counts are partial or absent, and nobody uses the tables)
+    LSD_HIP(lsd::launch_scan_regions(radix_bits, lsd::hybrid_global_passes(radix_bits), sp.L.regions, sp.fields, n, (uint32_t)sp.shape->tile(),
+                                     sp.L.region0, sp.chain.tables + (size_t)sp.passes * sp.chain.table_words, rq.stream, nullptr, nullptr));
+    return LSDSORT_OK;
+}
+
+// Stage 1 (the upfront histograms): the whole array at once, or chunk by chunk behind the host's copies.
+int stage1(const SortRequest& rq, const SortPlan& sp)
+{
+    auto histogram = [&](size_t first, size_t len) -> int {   // over [first, first + len)
+        if (sp.L.regions > 1)
+            LSD_HIP(lsd::launch_joint_histograms(rq.radix_bits, rq.keys + first, (uint32_t)len, sp.L.region0, sp.counts, rq.stream, rq.xf,
+                                                 (uint32_t)first, sp.hyb ? sp.hyb + lsd::kHybridWordOk : nullptr));
+        else
+            LSD_HIP(lsd::launch_digit_histograms(rq.radix_bits, sp.passes, 0, rq.keys + first, (uint32_t)len, sp.counts, rq.stream));
+        return LSDSORT_OK;
+    };
+    const HostFeed* feed = rq.feed;
+    const size_t n = rq.n;
+    if (!feed) return histogram(0, n);
+    int e = 0;
+    for (size_t first = 0; first < n; first += kFeedChunkKeys, e++) {
+        const size_t len = n - first < kFeedChunkKeys ? n - first : kFeedChunkKeys;
+        LSD_HIP(hipMemcpyAsync(rq.keys + first, feed->host_keys + first, len * sizeof(uint32_t), hipMemcpyHostToDevice, feed->copy));   // .cu:1001
+        LSD_HIP(hipEventRecord(feed->events[e], feed->copy));
+        LSD_HIP(hipStreamWaitEvent(rq.stream, feed->events[e], 0));
+        LSD_TRY(histogram(first, len));
+    }
+    if (rq.vals) {
+        LSD_HIP(hipMemcpyAsync(rq.vals, feed->host_vals, n * sizeof(uint32_t), hipMemcpyHostToDevice, feed->copy));
+        LSD_HIP(hipEventRecord(feed->events[e], feed->copy));
+        LSD_HIP(hipStreamWaitEvent(rq.stream, feed->events[e], 0));
+    }
+    return LSDSORT_OK;
+}
+
+// Stage 2: the region tables of every pass from the counts, and the pass plan.
+int stage2(const SortRequest& rq, const SortPlan& sp)
+{
+    LSD_HIP(lsd::launch_scan_regions(rq.radix_bits, sp.passes, sp.L.regions, sp.counts, (uint32_t)rq.n, (uint32_t)sp.shape->tile(), sp.L.region0,
+                                     sp.chain.tables, rq.stream, sp.plan, sp.chain.control, sp.hyb ? sp.hyb + lsd::kHybridWordOk : nullptr,
+                                     !rq.xf.on));
+    return LSDSORT_OK;
+}
+
+int hybrid_passes(const SortRequest& rq, const SortPlan& sp)
+{
+    // the hybrid form's global passes and its local stage (all return at once where the device chose the ordinary form):
+    // bits 16-31, lowest digit first: caller's buffer -> alternate and back (an even number of passes); then the buckets in place
+    const int hyb_passes = lsd::hybrid_global_passes(rq.radix_bits);
+    for (int g = 0; g < hyb_passes; g++) {
+        // the plan word says which way round (for the keys and every payload array)
+        PassParams p = sort_pass(rq, sp, (uint32_t)(16 + rq.radix_bits * g), sp.passes + g, g, g + 1 == hyb_passes, false);
+        p.shift_word = sp.hyb + lsd::kHybridWordShift + g;   // ... less the key prefix the device found: bits [16 - t, 32 - t)
+        p.plan = sp.hyb + lsd::kHybridWordPlan + 2 * g;
+        if (rq.xf.on && g == 0) p.xin = rq.xf;   // typed sorts: sortable keys from the first store on; the local stage's store turns them back
+        LSD_TRY(launch_sort_pass(rq, sp, p));
+    }
+    lsd::LocalSortParams lp{};
+    lp.keys = rq.keys;
+    lp.vals = rq.vals;
+    lp.num_payloads = sp.payloads;
+    for (int e = 0; e < rq.num_more; e++) lp.more[e] = rq.more[e];
+    lp.bases = sp.bases;
+    lp.num_buckets = 1u << sp.bucket_bits;
+    lp.low_bits_word = sp.hyb + lsd::kHybridWordLowBits;   // the bits below a bucket's own: 32 - bb less the key prefix the device found
+    lp.skip = sp.hyb + lsd::kHybridWordSkipLocal;
+    lp.xout = rq.xf;
+    lp.fault = sp.chain.control;
+    LSD_TRY(mark(rq, StageEvents::kLocalBegin));
+    // buckets of up to 10240 keys (all of them on uniform keys of most sizes): three workgroups per CU; where uniform keys
+    // stay under 5120 a bucket, four
+    lp.small_variant = sp.small_cap == lsd::kLocalSortCapTiny ? 2u : sp.small_cap == lsd::kLocalSortCap ? 0u : 1u;
+    lp.larger_elsewhere = 1;
+    LSD_HIP(lsd::launch_local_sort(lp, rq.stream));
+    lp.small_variant = 0;     // the planner's list of larger ones (up to 16384 keys): two per CU, a grid of 512 walks the list
+    lp.larger_elsewhere = 0;
+    lp.list = lp.bases + lsd::kHybridBuckets + 1;
+    lp.list_count = sp.hyb + lsd::kHybridWordLargeCount;
+    LSD_HIP(lsd::launch_local_sort(lp, rq.stream));
+    return mark(rq, StageEvents::kLocalEnd);
+}
+
+int chained_passes(const SortRequest& rq, const SortPlan& sp)
+{
+    for (int pass = 0; pass < sp.passes; pass++) {
+        // every array ping-pongs alike: even passes read the caller's, odd passes the alternates -- or, under a plan, the same pair
+        // for every pass: the plan says which way round (and whether at all)
+        PassParams p = sort_pass(rq, sp, (uint32_t)(pass * rq.radix_bits), pass, pass, pass + 1 == sp.passes, (pass & 1) && !sp.plan);
+        p.mute_row = sp.mute_row;
+        p.xcd_chunk = g_xcd_chunk.load(std::memory_order_relaxed);
+        if (sp.plan) {
+            p.plan = sp.plan + 2 * pass;
+            p.plan_first = sp.hyb ? 1u : 0u;   // a sort that tried the hybrid form: these passes leave at once if it runs
+        }
+        if (rq.xf.on && pass == 0) p.xin = rq.xf;
+        if (rq.xf.on && pass + 1 == sp.passes) p.xout = rq.xf;
+        LSD_TRY(launch_sort_pass(rq, sp, p));
+    }
+    // The passes are launched back to back and only the last one is followed by a
+    // mark -- an event record between two dependent kernels costs ~20 us of queue bubble, which is
+    // not the kernel's time (rocprofv3's kernel trace would disagree by 5 %).
+    return rq.ev ? rq.ev->mark_last() : LSDSORT_OK;
+}
+
+// The staged form: per pass a tile histogram, its offset scan, and the scatter; no upfront stages.
+int staged_passes(const SortRequest& rq, const SortPlan& sp)
+{
+    LSD_TRY(mark(rq, StageEvents::kCounted));
+    LSD_TRY(mark(rq, StageEvents::kScanned));
+    for (int pass = 0; pass < sp.passes; pass++) {
+        const bool back = pass & 1;
+        PassParams p{};
+        p.in = back ? sp.alt_keys : rq.keys;
+        p.out = back ? rq.keys : sp.alt_keys;
+        p.vals_in = back ? sp.alt_vals : rq.vals;
+        p.vals_out = back ? rq.vals : sp.alt_vals;
+        p.n = (uint32_t)rq.n;
+        p.shift = (uint32_t)(pass * rq.radix_bits);
+        p.num_tiles = sp.L.tiles;
+        p.fault = sp.chain.control;
+        p.spin_limit = g_spin_limit.load(std::memory_order_relaxed);
+        p.mute_row = sp.mute_row;
+        p.xcd_chunk = g_xcd_chunk.load(std::memory_order_relaxed);
+        p.stats = g_stats.load(std::memory_order_relaxed);
+        p.global_off = sp.tile_global;
+        LSD_HIP(lsd::launch_tile_histograms(rq.radix_bits, *sp.shape, p.in, p.n, p.shift, sp.tile_hist, rq.stream));
+        LSD_TRY(mark(rq, StageEvents::staged_mark(pass, StageEvents::kStagedHistogram)));
+        // local offsets are recomputed inside the rank-and-scatter kernel (it needs them for
+        // ranking anyway); only the global table is materialised here.
+        LSD_HIP(lsd::launch_tile_offsets(rq.radix_bits, sp.tile_hist, nullptr, sp.tile_global, sp.L.tiles, sp.scratch, rq.stream));
+        LSD_TRY(mark(rq, StageEvents::staged_mark(pass, StageEvents::kStagedOffsets)));
+        LSD_HIP(lsd::launch_rank_scatter(rq.radix_bits, *sp.shape, sp.rank_method, false, p, rq.stream));
+        LSD_TRY(mark(rq, StageEvents::staged_mark(pass, StageEvents::kStagedScatter)));
+    }
+    return LSDSORT_OK;
+}
+
+// 32 / radix_bits is even for every accepted radix: the result is back in the caller's arrays,
+// as the reference relies on (.cu:905, .cu:1005) -- unless the plan skipped an odd number of passes
+int finish(const SortRequest& rq, const SortPlan& sp)
+{
+    if (!sp.plan) return LSDSORT_OK;
+    const uint32_t* swapped = sp.plan + 2 * sp.passes;
+    LSD_HIP(lsd::launch_finish_plan(swapped, rq.keys, sp.alt_keys, rq.vals, sp.alt_vals, (uint32_t)rq.n, rq.stream));
+    for (int e = 0; e < rq.num_more; e++)   // the same copy back for each further payload array
+        LSD_HIP(lsd::launch_finish_plan(swapped, rq.more[e], sp.alt_more[e], nullptr, nullptr, (uint32_t)rq.n, rq.stream));
+    return LSDSORT_OK;
+}
+
+int run_sort(const SortRequest& rq)
+{
+    LSD_TRY(validate(rq));
+    if (rq.n == 0) return LSDSORT_OK;
+    SortPlan sp;
+    LSD_TRY(make_plan(rq, &sp));
+    if (rq.timing) {
+        rq.timing->passes = sp.passes;
+        rq.timing->tile_keys = sp.shape->tile();
+        rq.timing->tiles = (int)sp.L.tiles;
+        rq.timing->hybrid = sp.hyb ? -1 : 0;   // -1: tried; lsdsort_u32_device_timed reads the device's verdict back
+    }
+    if (sp.small) return small_sort(rq, sp);
+    LSD_TRY(mark(rq, StageEvents::kStart));
+    LSD_HIP(hipMemsetAsync(rq.ws, 0, sp.L.zero_bytes, rq.stream));
+    LSD_TRY(mark(rq, StageEvents::kCleared));
+    if (rq.algorithm == LSDSORT_ALGO_STAGED) return staged_passes(rq, sp);
+    if (sp.hyb) LSD_TRY(hybrid_upfront(rq, sp));
+    LSD_TRY(stage1(rq, sp));
+    LSD_TRY(mark(rq, StageEvents::kCounted));
+    LSD_TRY(inject_count_fault(rq, sp, false));
+    LSD_TRY(stage2(rq, sp));
+    LSD_TRY(mark(rq, StageEvents::kScanned));
+    if (sp.hyb) LSD_TRY(hybrid_passes(rq, sp));
+    LSD_TRY(chained_passes(rq, sp));
+    return finish(rq, sp);
 }
 
 int read_fault(void* d_ws, hipStream_t stream)
@@ -741,14 +806,11 @@ int sort_host(uint32_t* keys, uint32_t* vals, size_t n, int radix_bits)
     LSD_TRY(grow(reinterpret_cast<void**>(&C.d_keys), &C.keys_bytes, bytes));
     if (pairs) LSD_TRY(grow(reinterpret_cast<void**>(&C.d_vals), &C.vals_bytes, bytes));
     LSD_TRY(grow(&C.d_ws, &C.ws_bytes, ws_bytes));
-    HostFeed feed;
-    feed.host_keys = keys;
-    feed.host_vals = vals;
-    feed.copy = C.copy;
-    feed.events = C.events;
+    const HostFeed feed{keys, vals, C.copy, C.events};
     // H2D in chunks with stage 1 behind each (.cu:1001), the passes (.cu:1003), the copy back (.cu:1005)
-    const int status = run_sort(C.d_keys, pairs ? C.d_vals : nullptr, C.d_ws, C.ws_bytes, n, radix_bits, LSDSORT_ALGO_ONESWEEP, C.compute,
-                                nullptr, nullptr, lsd::KeyTransform{}, &feed);
+    SortRequest rq(C.d_keys, pairs ? C.d_vals : nullptr, C.d_ws, C.ws_bytes, n, radix_bits, C.compute);
+    rq.feed = &feed;
+    const int status = run_sort(rq);
     if (status != LSDSORT_OK) {
         (void)hipStreamSynchronize(C.copy);       // nothing of the caller's array may still be in flight when we return
         (void)hipStreamSynchronize(C.compute);
@@ -789,11 +851,9 @@ MsbLayout make_msb_layout(size_t n, int msb_bits)
 
 }  // namespace
 
-// internals other translation units of the library use (sharded.hip)
+// internals other translation units of the library use (lsd_host.hpp)
 namespace lsd {
-int sort_host_multi(uint32_t* keys, size_t n, int radix_bits, int num_gpus, bool loopback);   // sharded.hip
 void set_last_hip_error(hipError_t e) { g_last_hip = e; }
-// segmented.hip: the current device set up (probe included), and the rank form a sort with this radix uses there
 int device_rank_method(int radix_bits, int* rank_method)
 {
     int dev = 0;
@@ -912,9 +972,7 @@ LSDSORT_API int lsdsort_debug_fault_inject(unsigned spin_limit, unsigned mute_ro
     g_mute_row.store(mute_row_plus_1, std::memory_order_relaxed);
     return LSDSORT_OK;
 }
-#endif
 
-#ifdef LSD_FAULT_INJECT
 LSDSORT_API int lsdsort_debug_fault_inject_sorts(int sorts)   // the muted row applies to the next `sorts` sorts only (-1: to all)
 {
     g_mute_sorts.store(sorts, std::memory_order_relaxed);
@@ -996,15 +1054,15 @@ size_t lsdsort_workspace_bytes_ex(size_t n, int radix_bits, int pairs, int algor
     // workspace made for n serves every smaller sort as well; each term, hence the figure, is
     // monotonic in n.
     if (pairs < 0 || pairs > 3) return 0;
-    size_t need = make_layout(n, radix_bits, pairs, algorithm, *current_shape(radix_bits, pairs != 0, n, algorithm)).total;
+    size_t need = make_layout(n, radix_bits, pairs, algorithm, *current_shape(radix_bits, n, algorithm)).total;
     if (algorithm == LSDSORT_ALGO_ONESWEEP) {
         for (int c = 0; c < kNumShapeClasses && kShapeClasses[c].below <= n; c++) {
             const size_t m = kShapeClasses[c].below - 1;
-            const size_t t = make_layout(m, radix_bits, pairs, algorithm, *current_shape(radix_bits, pairs != 0, m, algorithm)).total;
+            const size_t t = make_layout(m, radix_bits, pairs, algorithm, *current_shape(radix_bits, m, algorithm)).total;
             if (t > need) need = t;
         }
     }
-    const size_t stage = make_layout(n, radix_bits, pairs, algorithm, *current_shape(radix_bits, pairs != 0, 0, algorithm)).total;
+    const size_t stage = make_layout(n, radix_bits, pairs, algorithm, *current_shape(radix_bits, 0, algorithm)).total;
     return need > stage ? need : stage;
 }
 
@@ -1016,8 +1074,9 @@ size_t lsdsort_workspace_bytes(size_t n, int radix_bits, int pairs)
 int lsdsort_u32_device_ex(uint32_t* d_keys, uint32_t* d_vals, void* d_workspace, size_t workspace_bytes, size_t n,
                           int radix_bits, int algorithm, void* hip_stream)
 {
-    return run_sort(d_keys, d_vals, d_workspace, workspace_bytes, n, radix_bits, algorithm,
-                    static_cast<hipStream_t>(hip_stream), nullptr, nullptr);
+    SortRequest rq(d_keys, d_vals, d_workspace, workspace_bytes, n, radix_bits, hip_stream);
+    rq.algorithm = algorithm;
+    return run_sort(rq);
 }
 
 int lsdsort_u32_device(uint32_t* d_keys, void* d_workspace, size_t workspace_bytes, size_t n, int radix_bits,
@@ -1030,8 +1089,9 @@ int lsdsort_u32_device(uint32_t* d_keys, void* d_workspace, size_t workspace_byt
 int lsdsort_u32_device_prefixed(uint32_t* d_keys, void* d_workspace, size_t workspace_bytes, size_t n, int radix_bits,
                                 int common_prefix_bits, void* hip_stream)
 {
-    return run_sort(d_keys, nullptr, d_workspace, workspace_bytes, n, radix_bits, LSDSORT_ALGO_ONESWEEP, static_cast<hipStream_t>(hip_stream),
-                    nullptr, nullptr, lsd::KeyTransform{}, nullptr, nullptr, 0, common_prefix_bits);
+    // the argument is checked, not needed: the device finds the key prefix itself
+    if (common_prefix_bits < 0 || common_prefix_bits > 8) return LSDSORT_ERR_INVALID_ARG;
+    return run_sort(SortRequest(d_keys, nullptr, d_workspace, workspace_bytes, n, radix_bits, hip_stream));
 }
 
 int lsdsort_pairs_u32_device(uint32_t* d_keys, uint32_t* d_vals, void* d_workspace, size_t workspace_bytes, size_t n,
@@ -1048,30 +1108,24 @@ int lsdsort_multi_u32_device(uint32_t* d_keys, uint32_t* const* d_vals, int num_
     if (num_vals < 1 || num_vals > 3 || !d_vals) return LSDSORT_ERR_INVALID_ARG;
     if (n > 0 && !d_vals[0]) return LSDSORT_ERR_INVALID_ARG;
     // the key/value kernel sends further payload arrays through its single-round shapes only (every default shape is one)
-    const TileShape* shape = current_shape(radix_bits, true, n, LSDSORT_ALGO_ONESWEEP);
+    const TileShape* shape = current_shape(radix_bits, n, LSDSORT_ALGO_ONESWEEP);
     if (num_vals > 1 && shape && valid_radix(radix_bits)) {
         const TileShape* shapes = nullptr;
         (void)lsd::tile_shapes(radix_bits, &shapes);
         if (!lsd::single_round_shape(radix_bits, (int)(shape - shapes))) return LSDSORT_ERR_UNSUPPORTED;
     }
-    return run_sort(d_keys, d_vals[0], d_workspace, workspace_bytes, n, radix_bits, LSDSORT_ALGO_ONESWEEP,
-                    static_cast<hipStream_t>(hip_stream), nullptr, nullptr, lsd::KeyTransform{}, nullptr, d_vals + 1, num_vals - 1);
+    SortRequest rq(d_keys, d_vals[0], d_workspace, workspace_bytes, n, radix_bits, hip_stream);
+    rq.more = d_vals + 1;
+    rq.num_more = num_vals - 1;
+    return run_sort(rq);
 }
 
 int lsdsort_keys_device(void* d_keys, uint32_t* d_vals, void* d_workspace, size_t workspace_bytes, size_t n,
                         int radix_bits, int key_type, int descending, void* hip_stream)
 {
-    lsd::KeyTransform xf{};
-    switch (key_type) {
-        case LSDSORT_KEY_U32: break;
-        case LSDSORT_KEY_I32: xf.b = 0x80000000u; break;
-        case LSDSORT_KEY_F32: xf.a = 0x80000000u; xf.b = 0x80000000u; break;
-        default: return LSDSORT_ERR_INVALID_ARG;
-    }
-    if (descending) xf.c = 0xFFFFFFFFu;
-    xf.on = (xf.a | xf.b | xf.c) != 0u;
-    return run_sort(static_cast<uint32_t*>(d_keys), d_vals, d_workspace, workspace_bytes, n, radix_bits, LSDSORT_ALGO_ONESWEEP,
-                    static_cast<hipStream_t>(hip_stream), nullptr, nullptr, xf);
+    SortRequest rq(static_cast<uint32_t*>(d_keys), d_vals, d_workspace, workspace_bytes, n, radix_bits, hip_stream);
+    LSD_TRY(lsd::key_transform(key_type, descending, &rq.xf));
+    return run_sort(rq);
 }
 
 int lsdsort_check_device(void* d_workspace, void* hip_stream)
@@ -1089,10 +1143,7 @@ int lsdsort_check_device(void* d_workspace, void* hip_stream)
 #else
     constexpr bool always = false;
 #endif
-    static const bool by_env = [] {
-        const char* e = getenv("LSDSORT_REPROBE");
-        return e && e[0] == '1';
-    }();
+    static const bool by_env = env_flag("LSDSORT_REPROBE", false);
     if (status == LSDSORT_OK && (always || by_env) && g_device[dev].lds_add_in_lane_order) {
         bool ok = false;
         LSD_HIP(lsd::probe_lds_add_lane_order(&ok, static_cast<hipStream_t>(hip_stream)));
@@ -1110,19 +1161,22 @@ int lsdsort_u32_device_timed(uint32_t* d_keys, uint32_t* d_vals, void* d_workspa
     if (!out) return LSDSORT_ERR_INVALID_ARG;
     std::memset(out, 0, sizeof(*out));
     StageEvents ev;
-    ev.enabled = true;
     ev.stream = static_cast<hipStream_t>(hip_stream);
-    int status = run_sort(d_keys, d_vals, d_workspace, workspace_bytes, n, radix_bits, algorithm, ev.stream, &ev, out);
-    if (status == LSDSORT_OK && ev.count >= 4) {
-        auto finish = [&]() -> int {
-            LSD_HIP(hipEventSynchronize(ev.ev[ev.count - 1]));
-            LSD_HIP(hipEventElapsedTime(&out->total_ms, ev.ev[0], ev.ev[ev.count - 1]));
-            LSD_HIP(hipEventElapsedTime(&out->clear_ms, ev.ev[0], ev.ev[1]));
-            LSD_HIP(hipEventElapsedTime(&out->histogram_ms, ev.ev[1], ev.ev[2]));
-            LSD_HIP(hipEventElapsedTime(&out->scan_ms, ev.ev[2], ev.ev[3]));
+    SortRequest rq(d_keys, d_vals, d_workspace, workspace_bytes, n, radix_bits, hip_stream);
+    rq.algorithm = algorithm;
+    rq.ev = &ev;
+    rq.timing = out;
+    int status = run_sort(rq);
+    if (status == LSDSORT_OK && ev.count > StageEvents::kScanned) {
+        auto read_marks = [&]() -> int {
+            LSD_HIP(hipEventSynchronize(ev.last()));
+            LSD_HIP(hipEventElapsedTime(&out->total_ms, ev.ev[StageEvents::kStart], ev.last()));
+            LSD_HIP(hipEventElapsedTime(&out->clear_ms, ev.ev[StageEvents::kStart], ev.ev[StageEvents::kCleared]));
+            LSD_HIP(hipEventElapsedTime(&out->histogram_ms, ev.ev[StageEvents::kCleared], ev.ev[StageEvents::kCounted]));
+            LSD_HIP(hipEventElapsedTime(&out->scan_ms, ev.ev[StageEvents::kCounted], ev.ev[StageEvents::kScanned]));
             if (algorithm == LSDSORT_ALGO_ONESWEEP) {
-                // marks: 3 = before the first pass, the last = after the last; per pass: the kernel's own events.  Where the hybrid
-                // form was tried its global passes come first (event pairs 0, 1 and at 4-bit digits 2, 3) and marks 4, 5 bracket the local stage.
+                // per pass: the kernel's own events.  Where the hybrid form was tried its global passes come first (event pairs 0, 1
+                // and at 4-bit digits 2, 3).
                 int first_pair = 0;
                 if (out->hybrid == -1) {
                     uint32_t ok = 0;
@@ -1132,7 +1186,8 @@ int lsdsort_u32_device_timed(uint32_t* d_keys, uint32_t* d_vals, void* d_workspa
                     first_pair = ok ? 0 : lsd::hybrid_global_passes(radix_bits);
                     if (ok) {
                         out->passes = lsd::hybrid_global_passes(radix_bits);
-                        if (ev.count >= 6) LSD_HIP(hipEventElapsedTime(&out->local_ms, ev.ev[4], ev.ev[5]));
+                        if (ev.count > StageEvents::kLocalEnd)
+                            LSD_HIP(hipEventElapsedTime(&out->local_ms, ev.ev[StageEvents::kLocalBegin], ev.ev[StageEvents::kLocalEnd]));
                     }
                 }
                 for (int p = 0; p < out->passes && p < LSDSORT_MAX_PASSES && 2 * (p + first_pair) + 1 < ev.kernel_count; p++)
@@ -1140,18 +1195,19 @@ int lsdsort_u32_device_timed(uint32_t* d_keys, uint32_t* d_vals, void* d_workspa
             } else {
                 out->histogram_ms = 0.f;
                 out->scan_ms = 0.f;
-                for (int p = 0; 3 * p + 6 < ev.count && p < LSDSORT_MAX_PASSES; p++) {
+                for (int p = 0; StageEvents::staged_mark(p, StageEvents::kStagedScatter) < ev.count && p < LSDSORT_MAX_PASSES; p++) {
+                    const hipEvent_t* m = &ev.ev[StageEvents::staged_mark(p, StageEvents::kPassBegin)];
                     float h = 0.f, s = 0.f;
-                    LSD_HIP(hipEventElapsedTime(&h, ev.ev[3 + 3 * p], ev.ev[4 + 3 * p]));
-                    LSD_HIP(hipEventElapsedTime(&s, ev.ev[4 + 3 * p], ev.ev[5 + 3 * p]));
-                    LSD_HIP(hipEventElapsedTime(&out->scatter_ms[p], ev.ev[5 + 3 * p], ev.ev[6 + 3 * p]));
+                    LSD_HIP(hipEventElapsedTime(&h, m[StageEvents::kPassBegin], m[StageEvents::kStagedHistogram]));
+                    LSD_HIP(hipEventElapsedTime(&s, m[StageEvents::kStagedHistogram], m[StageEvents::kStagedOffsets]));
+                    LSD_HIP(hipEventElapsedTime(&out->scatter_ms[p], m[StageEvents::kStagedOffsets], m[StageEvents::kStagedScatter]));
                     out->histogram_ms += h;
                     out->scan_ms += s;
                 }
             }
             return LSDSORT_OK;
         };
-        status = finish();
+        status = read_marks();
     }
     ev.destroy();
     return status;
@@ -1304,12 +1360,14 @@ static int partition_impl(const uint32_t* d_in, uint32_t* d_out, size_t n, int m
     LSD_TRY(check_device_ready(&dev));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const MsbLayout L = make_msb_layout(n, msb_bits);
-    if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & (kAlign - 1)) || workspace_bytes < L.total)
-        return LSDSORT_ERR_WORKSPACE;
+    if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.total)) return LSDSORT_ERR_WORKSPACE;
     char* ws = static_cast<char*>(d_workspace);
-    uint32_t* control = reinterpret_cast<uint32_t*>(ws + L.control);
+    Chain chain;
+    chain.control = reinterpret_cast<uint32_t*>(ws + L.control);
+    chain.tickets = reinterpret_cast<uint32_t*>(ws + L.tickets);
+    chain.tables = reinterpret_cast<uint32_t*>(ws + L.table);
+    chain.status[0] = reinterpret_cast<uint32_t*>(ws + L.status);
     uint32_t* hist = reinterpret_cast<uint32_t*>(ws + L.counts);
-    uint32_t* table = reinterpret_cast<uint32_t*>(ws + L.table);
     const int bins = 1 << msb_bits;
     LSD_HIP(hipMemsetAsync(ws, 0, L.zero_bytes, stream));
     if (msb_bits == 0) {
@@ -1319,52 +1377,38 @@ static int partition_impl(const uint32_t* d_in, uint32_t* d_out, size_t n, int m
         if (n) LSD_HIP(hipMemcpyAsync(d_out, d_in, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
         return LSDSORT_OK;
     }
+    const uint32_t shift = (uint32_t)(32 - msb_bits);
+    const TileShape* shape = current_shape(msb_bits, n, LSDSORT_ALGO_ONESWEEP);
     if (n) {
-        const uint32_t shift = (uint32_t)(32 - msb_bits);
-        const TileShape* shape = current_shape(msb_bits, false, n, LSDSORT_ALGO_ONESWEEP);
         if (splitters)
             LSD_HIP(lsd::launch_bucket_histogram(msb_bits, splitters, live, d_in, (uint32_t)n, hist, stream));
         else
             LSD_HIP(lsd::launch_digit_histograms(msb_bits, 1, shift, d_in, (uint32_t)n, hist, stream));
-        LSD_HIP(lsd::launch_scan_regions(msb_bits, 1, 1, hist, (uint32_t)n, (uint32_t)shape->tile(), 0, table, stream, nullptr, control));
-        // the bucket sizes are final here: hand them out before the partition pass, so that a caller's count
-        // exchange (multi-GPU step, sharded.hip) runs beside it
-        LSD_HIP(lsd::launch_widen_counts(hist, d_counts, bins, stream));
-        if (counts_ready) LSD_HIP(hipEventRecord(counts_ready, stream));
-        PassParams p{};
-        p.in = d_in;
-        p.out = d_out;
-        p.n = (uint32_t)n;
-        p.shift = shift;
-        p.num_tiles = (uint32_t)((n + (size_t)shape->tile() - 1) / (size_t)shape->tile()) + 1u;   // <= L.rows
-        p.regions = table;
-        p.status = reinterpret_cast<uint32_t*>(ws + L.status);
-        p.tickets = reinterpret_cast<uint32_t*>(ws + L.tickets);
-        p.parity = 0;
-        p.fault = control;
-        p.spin_limit = g_spin_limit.load(std::memory_order_relaxed);
-        if (splitters) {
-            p.num_splitters = (1u << msb_bits) - 1u;
-            p.live_splitters = (uint32_t)live;
-            for (uint32_t i = 0; i < p.live_splitters; i++) p.splitters[i] = splitters[i];
-        }
-        LSD_HIP(lsd::launch_rank_scatter(msb_bits, *shape, resolve_rank_method(dev, msb_bits), true, p, stream));
-    } else {
-        LSD_HIP(lsd::launch_widen_counts(hist, d_counts, bins, stream));   // all zero
-        if (counts_ready) LSD_HIP(hipEventRecord(counts_ready, stream));
+        LSD_HIP(lsd::launch_scan_regions(msb_bits, 1, 1, hist, (uint32_t)n, (uint32_t)shape->tile(), 0, chain.tables, stream, nullptr, chain.control));
     }
+    // the bucket sizes are final here (all zero without keys): hand them out before the partition pass, so that a caller's
+    // count exchange (multi-GPU step, sharded.hip) runs beside it
+    LSD_HIP(lsd::launch_widen_counts(hist, d_counts, bins, stream));
+    if (counts_ready) LSD_HIP(hipEventRecord(counts_ready, stream));
+    if (n == 0) return LSDSORT_OK;
+    chain.rows = (uint32_t)((n + (size_t)shape->tile() - 1) / (size_t)shape->tile()) + 1u;   // <= L.rows
+    PassParams p = chained_pass(chain, d_in, d_out, n, shift, 0, 0, true);   // one pass: one table, one status array
+    if (splitters) {
+        p.num_splitters = (1u << msb_bits) - 1u;
+        p.live_splitters = (uint32_t)live;
+        for (uint32_t i = 0; i < p.live_splitters; i++) p.splitters[i] = splitters[i];
+    }
+    LSD_HIP(lsd::launch_rank_scatter(msb_bits, *shape, resolve_rank_method(dev, msb_bits), true, p, stream));
     return LSDSORT_OK;
 }
 
 }  // extern "C"
 namespace lsd {
-// the MSB partition with its bucket counts published (and `counts_ready` recorded) BEFORE the partition pass
 int partition_with_event(const uint32_t* d_in, uint32_t* d_out, size_t n, int msb_bits, uint64_t* d_counts,
                          void* d_workspace, size_t workspace_bytes, hipStream_t stream, hipEvent_t counts_ready)
 {
     return partition_impl(d_in, d_out, n, msb_bits, nullptr, d_counts, d_workspace, workspace_bytes, stream, counts_ready);
 }
-// the same by thresholds: bucket of a key = number of thresholds <= key; ascending values in [0, 2^32], 2^32 = above every key
 int threshold_partition_with_event(const uint32_t* d_in, uint32_t* d_out, size_t n, int log2_buckets, const uint64_t* thresholds,
                                    uint64_t* d_counts, void* d_workspace, size_t workspace_bytes, hipStream_t stream,
                                    hipEvent_t counts_ready)

@@ -26,13 +26,9 @@
 #include "../../include/lsdsort.h"
 
 #include "lsd_device.hpp"
-#include "lsd_kernels.hpp"
+#include "lsd_host.hpp"
 
 namespace lsd {
-
-int device_rank_method(int radix_bits, int* rank_method);   // lsdsort_api.hip: set-up of the current device, the rank form in force
-void set_last_hip_error(hipError_t e);                      // lsdsort_api.hip: what lsdsort_last_hip_error reports
-
 namespace {
 
 constexpr uint32_t kSegTile = 4096;          // keys per large-tier tile: 256 threads x 16
@@ -57,8 +53,6 @@ typedef unsigned long long u64;
 constexpr uint32_t kSegFaultList = 128u, kSegFaultTile = 256u, kSegFaultDest = 512u;
 __device__ __forceinline__ uint32_t clamp_count(u64 count, uint32_t cap) { return count < cap ? (uint32_t)count : cap; }
 
-size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
-size_t min_sz(size_t a, size_t b) { return a < b ? a : b; }
 
 // Workspace: control | wave list | workgroup list | items (uint4 per multi-tile segment) | tile table (uint2 per tile)
 //            | counts [hist tiles][256] | scan block sums | keys buffer | payload buffer
@@ -551,21 +545,6 @@ hipError_t launch_scatter(bool lds_add, uint32_t grid, const LargeParams& lp, hi
     return hipGetLastError();
 }
 
-uint32_t grid_for(size_t items, size_t per_workgroup, size_t cap)
-{
-    const size_t g = (items + per_workgroup - 1) / per_workgroup;
-    return (uint32_t)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
-#define SEG_HIP(expr)                \
-    do {                             \
-        hipError_t e__ = (expr);     \
-        if (e__ != hipSuccess) {     \
-            set_last_hip_error(e__); \
-            return LSDSORT_ERR_HIP;  \
-        }                            \
-    } while (0)
-
 int run_segmented(uint32_t* keys, uint32_t* vals, const uint32_t* offsets, size_t segs, size_t n, const KeyTransform& xf,
                   void* d_ws, size_t ws_bytes, hipStream_t stream)
 {
@@ -573,10 +552,9 @@ int run_segmented(uint32_t* keys, uint32_t* vals, const uint32_t* offsets, size_
     if (!keys || !offsets) return LSDSORT_ERR_INVALID_ARG;
     const bool pairs = vals != nullptr;
     const SegLayout L = seg_layout(n, segs, pairs);
-    if (!d_ws || (reinterpret_cast<uintptr_t>(d_ws) & 255u) || ws_bytes < L.total) return LSDSORT_ERR_WORKSPACE;
+    if (!workspace_ok(d_ws, ws_bytes, L.total)) return LSDSORT_ERR_WORKSPACE;
     int rank_method = 0;
-    const int ready = device_rank_method(8, &rank_method);
-    if (ready != LSDSORT_OK) return ready;
+    LSD_TRY(device_rank_method(8, &rank_method));
     const bool local = rank_method == kRankLdsAdd;
 
     char* ws = static_cast<char*>(d_ws);
@@ -600,7 +578,7 @@ int run_segmented(uint32_t* keys, uint32_t* vals, const uint32_t* offsets, size_
     static_assert(kCtlBytes == 64 * sizeof(uint32_t), "one word per thread");
     hipLaunchKernelGGL(seg_clear_kernel, dim3(1), dim3(64), 0, stream, ctl);
     hipLaunchKernelGGL(seg_plan_kernel, dim3(grid_for(segs, 256, 2048)), dim3(256), 0, stream, pp);
-    SEG_HIP(hipGetLastError());
+    LSD_HIP(hipGetLastError());
 
     const size_t listed = min_sz(segs, n / 2);
     if (local) {
@@ -619,12 +597,12 @@ int run_segmented(uint32_t* keys, uint32_t* vals, const uint32_t* offsets, size_
         const uint32_t wave_grid = grid_for(listed, kWaveTierWaves, 4096);   // measured: wider grids are slower (2.30 -> 2.50 ms at 2^20 x 256)
         if (pairs) hipLaunchKernelGGL(seg_wave_kernel<true>, dim3(wave_grid), dim3(kWaveTierWaves * kWave), 0, stream, sp);
         else hipLaunchKernelGGL(seg_wave_kernel<false>, dim3(wave_grid), dim3(kWaveTierWaves * kWave), 0, stream, sp);
-        SEG_HIP(hipGetLastError());
+        LSD_HIP(hipGetLastError());
         if (n > (size_t)kWaveSegCap) {
             sp.list = pp.group_list;
             sp.list_count = pp.cnt + kCntGroup;
             sp.list_cap = pp.group_cap;
-            SEG_HIP(launch_segment_sort(sp, grid_for(min_sz(segs, n / (kWaveSegCap + 1)), 1, 512), stream));   // two per CU
+            LSD_HIP(launch_segment_sort(sp, grid_for(min_sz(segs, n / (kWaveSegCap + 1)), 1, 512), stream));   // two per CU
         }
     }
     // the large tier: with the local tiers in force only segments above kLocalSortCap keys reach it
@@ -632,7 +610,7 @@ int run_segmented(uint32_t* keys, uint32_t* vals, const uint32_t* offsets, size_
     if (n < smallest_large) return LSDSORT_OK;
     const size_t max_tiles = local ? n / kSegTile + n / smallest_large + 1 : L.max_tiles;
     hipLaunchKernelGGL(seg_tiles_kernel, dim3(grid_for(min_sz(segs, n / smallest_large) + 1, 1, 1024)), dim3(256), 0, stream, pp);
-    SEG_HIP(hipGetLastError());
+    LSD_HIP(hipGetLastError());
     // 64 x 2^22: 8.0 ms with 2048 workgroups walking the table, 6.9 with one per tile (whose empty launches cost 18 us each where no
     // segment is large), 7.07 with 16384
     const uint32_t tile_grid = grid_for(max_tiles, 1, 16384);
@@ -665,8 +643,8 @@ int run_segmented(uint32_t* keys, uint32_t* vals, const uint32_t* offsets, size_
         hipLaunchKernelGGL(seg_scan_reduce_kernel, dim3(scan_grid), dim3(256), 0, stream, lp);
         hipLaunchKernelGGL(seg_scan_sums_kernel, dim3(1), dim3(1024), 0, stream, lp);
         hipLaunchKernelGGL(seg_scan_down_kernel, dim3(scan_grid), dim3(256), 0, stream, lp);
-        SEG_HIP(hipGetLastError());
-        SEG_HIP(pairs ? launch_scatter<true>(local, tile_grid, lp, stream) : launch_scatter<false>(local, tile_grid, lp, stream));
+        LSD_HIP(hipGetLastError());
+        LSD_HIP(pairs ? launch_scatter<true>(local, tile_grid, lp, stream) : launch_scatter<false>(local, tile_grid, lp, stream));
     }
     return LSDSORT_OK;
 }
@@ -685,15 +663,8 @@ size_t lsdsort_segmented_workspace_bytes(size_t n, size_t num_segments, int pair
 int lsdsort_segmented_device(void* d_keys, uint32_t* d_vals, const uint32_t* d_offsets, size_t num_segments, size_t n, int key_type,
                              int descending, void* d_workspace, size_t workspace_bytes, void* hip_stream)
 {
-    lsd::KeyTransform xf{};
-    switch (key_type) {
-        case LSDSORT_KEY_U32: break;
-        case LSDSORT_KEY_I32: xf.b = 0x80000000u; break;
-        case LSDSORT_KEY_F32: xf.a = 0x80000000u; xf.b = 0x80000000u; break;
-        default: return LSDSORT_ERR_INVALID_ARG;
-    }
-    if (descending) xf.c = 0xFFFFFFFFu;
-    xf.on = (xf.a | xf.b | xf.c) != 0u;
+    lsd::KeyTransform xf;
+    LSD_TRY(lsd::key_transform(key_type, descending, &xf));
     if (n > LSDSORT_MAX_KEYS || num_segments > LSDSORT_MAX_KEYS) return LSDSORT_ERR_TOO_LARGE;
     if ((n > 0 || num_segments > 0) && (!d_keys || !d_offsets)) return LSDSORT_ERR_INVALID_ARG;
     if (n == 0 || num_segments == 0) return LSDSORT_OK;

@@ -31,22 +31,11 @@
 #include <thread>
 #include <vector>
 
-#include "lsd_kernels.hpp"
-
-namespace lsd {
-// lsdsort_api.hip
-int partition_with_event(const uint32_t* d_in, uint32_t* d_out, size_t n, int msb_bits, uint64_t* d_counts,
-                         void* d_workspace, size_t workspace_bytes, hipStream_t stream, hipEvent_t counts_ready);
-int threshold_partition_with_event(const uint32_t* d_in, uint32_t* d_out, size_t n, int log2_buckets, const uint64_t* thresholds,
-                                   uint64_t* d_counts, void* d_workspace, size_t workspace_bytes, hipStream_t stream,
-                                   hipEvent_t counts_ready);
-void set_last_hip_error(hipError_t e);
-}  // namespace lsd
+#include "lsd_host.hpp"
 
 namespace {
 
-constexpr size_t kAlign = 256;
-size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
+using lsd::align_up;
 
 thread_local char t_comm_error[256] = "";
 
@@ -96,16 +85,6 @@ Rccl& rccl()
     return r;
 }
 
-#define SH_HIP(expr)                          \
-    do {                                      \
-        hipError_t e__ = (expr);              \
-        if (e__ != hipSuccess) {              \
-            lsd::set_last_hip_error(e__);     \
-            (void)hipGetLastError();          \
-            return LSDSORT_ERR_HIP;           \
-        }                                     \
-    } while (0)
-
 #define SH_NCCL(expr)                                                                                        \
     do {                                                                                                     \
         ncclResult_t r__ = (expr);                                                                           \
@@ -113,12 +92,6 @@ Rccl& rccl()
             std::snprintf(t_comm_error, sizeof(t_comm_error), "%s: %s", #expr, rccl().GetErrorString(r__));  \
             return LSDSORT_ERR_COMM;                                                                         \
         }                                                                                                    \
-    } while (0)
-
-#define SH_TRY(expr)                       \
-    do {                                   \
-        int s__ = (expr);                  \
-        if (s__ != LSDSORT_OK) return s__; \
     } while (0)
 
 int log2_world(int world)
@@ -154,7 +127,7 @@ ShardedLayout make_sharded_layout(size_t n_local_max, size_t out_capacity, int w
     ShardedLayout L;
     size_t off = 0;
     L.sticky = off;
-    off += kAlign;
+    off += lsd::kAlign;
     L.vec = off;
     off = align_up(off + (size_t)(kMaxBuckets + 1) * sizeof(uint64_t));
     L.all = off;
@@ -301,17 +274,17 @@ struct LoopbackTransport final : Transport {
         LoopbackWorld::Post& mine = w->post[rank];
         mine.send = send;
         mine.bytes = bytes_per_rank;
-        SH_HIP(hipEventRecord(mine.ready, stream));
+        LSD_HIP(hipEventRecord(mine.ready, stream));
         if (w->barrier() != LSDSORT_OK) return fail("a rank left the all-gather");
         for (int p = 0; p < w->world; p++) {
             if (w->post[p].bytes != bytes_per_rank) return fail("all-gather sizes differ between ranks");
-            SH_HIP(hipStreamWaitEvent(stream, w->post[p].ready, 0));
-            SH_HIP(hipMemcpyAsync(static_cast<char*>(recv) + (size_t)p * bytes_per_rank, w->post[p].send, bytes_per_rank,
+            LSD_HIP(hipStreamWaitEvent(stream, w->post[p].ready, 0));
+            LSD_HIP(hipMemcpyAsync(static_cast<char*>(recv) + (size_t)p * bytes_per_rank, w->post[p].send, bytes_per_rank,
                                   hipMemcpyDeviceToDevice, stream));
         }
-        SH_HIP(hipEventRecord(mine.done, stream));
+        LSD_HIP(hipEventRecord(mine.done, stream));
         if (w->barrier() != LSDSORT_OK) return fail("a rank left the all-gather");
-        for (int p = 0; p < w->world; p++) SH_HIP(hipStreamWaitEvent(stream, w->post[p].done, 0));
+        for (int p = 0; p < w->world; p++) LSD_HIP(hipStreamWaitEvent(stream, w->post[p].done, 0));
         return LSDSORT_OK;
     }
     int group_start() override
@@ -342,7 +315,7 @@ struct LoopbackTransport final : Transport {
             return first_error;
         }
         LoopbackWorld::Post& mine = w->post[rank];
-        SH_HIP(hipEventRecord(mine.ready, stream));
+        LSD_HIP(hipEventRecord(mine.ready, stream));
         if (w->barrier() != LSDSORT_OK) return fail("a rank left the exchange");
         // my k-th receive from peer p takes p's k-th send to me
         int status = LSDSORT_OK;
@@ -366,7 +339,7 @@ struct LoopbackTransport final : Transport {
             return status;
         }
         if (w->barrier() != LSDSORT_OK) return fail("a rank left the exchange");
-        for (int p = 0; p < w->world; p++) SH_HIP(hipStreamWaitEvent(stream, w->post[p].done, 0));
+        for (int p = 0; p < w->world; p++) LSD_HIP(hipStreamWaitEvent(stream, w->post[p].done, 0));
         return LSDSORT_OK;
     }
     void abort() override { w->abort(); }
@@ -399,15 +372,15 @@ namespace {
 
 int finish_comm(lsdsort_comm* c)
 {
-    SH_HIP(hipGetDevice(&c->device));
-    SH_HIP(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-    SH_HIP(hipStreamCreateWithFlags(&c->sorter, hipStreamNonBlocking));
-    SH_HIP(hipEventCreateWithFlags(&c->counts_ready, hipEventDisableTiming));
-    SH_HIP(hipEventCreateWithFlags(&c->sample_ready, hipEventDisableTiming));
-    SH_HIP(hipEventCreateWithFlags(&c->sorted_all, hipEventDisableTiming));
-    for (hipEvent_t& e : c->arrived) SH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    SH_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_all), (size_t)c->world * (kMaxBuckets + 1) * sizeof(uint64_t), hipHostMallocDefault));
-    SH_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_samples), (size_t)c->world * (1 + LSDSORT_SPLITTER_SAMPLES) * sizeof(uint32_t),
+    LSD_HIP(hipGetDevice(&c->device));
+    LSD_HIP(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+    LSD_HIP(hipStreamCreateWithFlags(&c->sorter, hipStreamNonBlocking));
+    LSD_HIP(hipEventCreateWithFlags(&c->counts_ready, hipEventDisableTiming));
+    LSD_HIP(hipEventCreateWithFlags(&c->sample_ready, hipEventDisableTiming));
+    LSD_HIP(hipEventCreateWithFlags(&c->sorted_all, hipEventDisableTiming));
+    for (hipEvent_t& e : c->arrived) LSD_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    LSD_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_all), (size_t)c->world * (kMaxBuckets + 1) * sizeof(uint64_t), hipHostMallocDefault));
+    LSD_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_samples), (size_t)c->world * (1 + LSDSORT_SPLITTER_SAMPLES) * sizeof(uint32_t),
                          hipHostMallocDefault));
     return LSDSORT_OK;
 }
@@ -433,7 +406,7 @@ int lsdsort_comm_create(const void* id, int world, int rank, lsdsort_comm** out)
 {
     if (!id || !out || log2_world(world) < 0 || rank < 0 || rank >= world) return LSDSORT_ERR_INVALID_ARG;
     *out = nullptr;
-    SH_TRY(lsdsort_prepare_device());          // gfx950 check + probe, on the current device
+    LSD_TRY(lsdsort_prepare_device());          // gfx950 check + probe, on the current device
     if (!rccl().ok) return LSDSORT_ERR_UNSUPPORTED;
     lsdsort_comm* c = new lsdsort_comm;
     c->world = world;
@@ -463,7 +436,7 @@ int lsdsort_comm_create_loopback(int world, lsdsort_comm** out)
 {
     if (!out || log2_world(world) < 0) return LSDSORT_ERR_INVALID_ARG;
     for (int i = 0; i < world; i++) out[i] = nullptr;
-    SH_TRY(lsdsort_prepare_device());
+    LSD_TRY(lsdsort_prepare_device());
     auto shared = std::make_shared<LoopbackWorld>();
     shared->world = world;
     int status = LSDSORT_OK;
@@ -648,14 +621,14 @@ static int sharded_step(lsdsort_comm* c, const uint32_t* d_keys_in, size_t n_loc
     if ((n_local > 0 && !d_keys_in) || (out_capacity > 0 && !d_out)) return LSDSORT_ERR_INVALID_ARG;
     if (lsdsort_workspace_bytes(1, radix_bits, 0) == 0) return LSDSORT_ERR_INVALID_ARG;
     int dev = -1;
-    SH_HIP(hipGetDevice(&dev));
+    LSD_HIP(hipGetDevice(&dev));
     if (dev != c->device) return LSDSORT_ERR_INVALID_ARG;       // the communicator lives on the device it was made on
     const int W = c->world, S = c->sub_buckets, B = W * S;
     int bits = 0;
     while ((1 << bits) < B) bits++;
     if (partition == LSDSORT_PARTITION_SPLITTERS && B > 8) return LSDSORT_ERR_UNSUPPORTED;   // the value partition cuts into eight at most
     const ShardedLayout L = make_sharded_layout(n_local, out_capacity, W, radix_bits);
-    if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & (kAlign - 1)) || workspace_bytes < L.total) return LSDSORT_ERR_WORKSPACE;
+    if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.total)) return LSDSORT_ERR_WORKSPACE;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     char* ws = static_cast<char*>(d_workspace);
     uint64_t* d_vec = reinterpret_cast<uint64_t*>(ws + L.vec);
@@ -663,7 +636,7 @@ static int sharded_step(lsdsort_comm* c, const uint32_t* d_keys_in, size_t n_loc
     uint32_t* d_send = reinterpret_cast<uint32_t*>(ws + L.send);
     uint32_t* sticky = reinterpret_cast<uint32_t*>(ws + L.sticky);
     Transport& T = *c->transport;
-    SH_HIP(hipMemsetAsync(sticky, 0, sizeof(uint32_t), stream));
+    LSD_HIP(hipMemsetAsync(sticky, 0, sizeof(uint32_t), stream));
 
     // 0.  splitter rule only: a regular sample of every shard to every rank (one more host wait, ahead of the partition);
     //     each rank then cuts the sorted (key, source rank) sample into B equal parts and derives ITS thresholds
@@ -672,27 +645,27 @@ static int sharded_step(lsdsort_comm* c, const uint32_t* d_keys_in, size_t n_loc
         constexpr int NS = LSDSORT_SPLITTER_SAMPLES;
         uint32_t* d_samp = reinterpret_cast<uint32_t*>(ws + L.samp);
         uint32_t* d_samp_all = reinterpret_cast<uint32_t*>(ws + L.samp_all);
-        SH_HIP(lsd::launch_sample_keys(d_keys_in, (uint32_t)n_local, (uint32_t)NS, d_samp, stream));
-        SH_HIP(hipEventRecord(c->sample_ready, stream));
-        SH_HIP(hipStreamWaitEvent(c->side, c->sample_ready, 0));
-        SH_TRY(T.all_gather(d_samp, d_samp_all, (size_t)(1 + NS) * sizeof(uint32_t), c->side));
-        SH_HIP(hipMemcpyAsync(c->h_samples, d_samp_all, (size_t)W * (1 + NS) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->side));
-        SH_HIP(hipStreamSynchronize(c->side));
-        SH_TRY(lsdsort_sharded_thresholds_parts(c->h_samples, W, NS, c->rank, B, thresholds));
+        LSD_HIP(lsd::launch_sample_keys(d_keys_in, (uint32_t)n_local, (uint32_t)NS, d_samp, stream));
+        LSD_HIP(hipEventRecord(c->sample_ready, stream));
+        LSD_HIP(hipStreamWaitEvent(c->side, c->sample_ready, 0));
+        LSD_TRY(T.all_gather(d_samp, d_samp_all, (size_t)(1 + NS) * sizeof(uint32_t), c->side));
+        LSD_HIP(hipMemcpyAsync(c->h_samples, d_samp_all, (size_t)W * (1 + NS) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->side));
+        LSD_HIP(hipStreamSynchronize(c->side));
+        LSD_TRY(lsdsort_sharded_thresholds_parts(c->h_samples, W, NS, c->rank, B, thresholds));
     }
 
     // 1 + 2.  main stream: counts, EVENT, partition pass into B buckets (destination rank b / S, its sub-bucket b % S).
     //         side stream: count exchange while the partition runs.
     if (partition == LSDSORT_PARTITION_SPLITTERS)
-        SH_TRY(lsd::threshold_partition_with_event(d_keys_in, d_send, n_local, bits, thresholds, d_vec, ws + L.part_ws, L.part_ws_bytes,
+        LSD_TRY(lsd::threshold_partition_with_event(d_keys_in, d_send, n_local, bits, thresholds, d_vec, ws + L.part_ws, L.part_ws_bytes,
                                                    stream, c->counts_ready));
     else
-        SH_TRY(lsd::partition_with_event(d_keys_in, d_send, n_local, bits, d_vec, ws + L.part_ws, L.part_ws_bytes, stream, c->counts_ready));
-    SH_HIP(hipStreamWaitEvent(c->side, c->counts_ready, 0));
-    SH_HIP(lsd::launch_store_u64(d_vec + B, (uint64_t)out_capacity, c->side));
-    SH_TRY(T.all_gather(d_vec, d_all, (size_t)(B + 1) * sizeof(uint64_t), c->side));
-    SH_HIP(hipMemcpyAsync(c->h_all, d_all, (size_t)W * (B + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->side));
-    SH_HIP(hipStreamSynchronize(c->side));                      // the step's only host wait
+        LSD_TRY(lsd::partition_with_event(d_keys_in, d_send, n_local, bits, d_vec, ws + L.part_ws, L.part_ws_bytes, stream, c->counts_ready));
+    LSD_HIP(hipStreamWaitEvent(c->side, c->counts_ready, 0));
+    LSD_HIP(lsd::launch_store_u64(d_vec + B, (uint64_t)out_capacity, c->side));
+    LSD_TRY(T.all_gather(d_vec, d_all, (size_t)(B + 1) * sizeof(uint64_t), c->side));
+    LSD_HIP(hipMemcpyAsync(c->h_all, d_all, (size_t)W * (B + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->side));
+    LSD_HIP(hipStreamSynchronize(c->side));                      // the step's only host wait
 
     // host: the plan, identical on every rank; so is the verdict on everybody's capacity
     uint64_t m[8 * kMaxBuckets], send_off[kMaxBuckets], recv_off[4 * 8], sub_size[4], total = 0, offset = 0;
@@ -705,7 +678,7 @@ static int sharded_step(lsdsort_comm* c, const uint32_t* d_keys_in, size_t n_loc
             for (int j = 0; j < S; j++) recv += m[src * B + dst * S + j];
         if (recv > c->h_all[(size_t)dst * (B + 1) + B]) fits = false;
     }
-    SH_TRY(lsdsort_sharded_plan_sub(m, W, S, c->rank, send_off, recv_off, sub_size, &total, &offset));
+    LSD_TRY(lsdsort_sharded_plan_sub(m, W, S, c->rank, send_off, recv_off, sub_size, &total, &offset));
     if (counts_matrix)                                          // [src][dst], whole ranks
         for (int src = 0; src < W; src++)
             for (int dst = 0; dst < W; dst++) {
@@ -724,35 +697,35 @@ static int sharded_step(lsdsort_comm* c, const uint32_t* d_keys_in, size_t n_loc
     //         first error of the group.
     uint64_t sub_begin = 0;
     for (int j = 0; j < S; j++) {
-        SH_TRY(T.group_start());
+        LSD_TRY(T.group_start());
         for (int step = 1; step < W; step++) {
             const int to = (c->rank + step) % W, from = (c->rank - step + W) % W;   // a different partner pair per step
             const uint64_t ns = m[c->rank * B + to * S + j], nr = m[from * B + c->rank * S + j];
             if (ns && T.send(d_send + send_off[to * S + j], (size_t)ns * sizeof(uint32_t), to, stream) != LSDSORT_OK) break;
             if (nr && T.recv(d_out + recv_off[j * W + from], (size_t)nr * sizeof(uint32_t), from, stream) != LSDSORT_OK) break;
         }
-        SH_TRY(T.group_end(stream));
+        LSD_TRY(T.group_end(stream));
         const uint64_t mine = m[c->rank * B + c->rank * S + j];
         if (mine)
-            SH_HIP(hipMemcpyAsync(d_out + recv_off[j * W + c->rank], d_send + send_off[c->rank * S + j], (size_t)mine * sizeof(uint32_t),
+            LSD_HIP(hipMemcpyAsync(d_out + recv_off[j * W + c->rank], d_send + send_off[c->rank * S + j], (size_t)mine * sizeof(uint32_t),
                                   hipMemcpyDeviceToDevice, stream));
         // the local LSD passes of what has arrived (the top bits are constant within a sub-bucket; all 32 bits are still sorted)
         hipStream_t sort_on = S > 1 ? c->sorter : stream;
         if (S > 1) {
-            SH_HIP(hipEventRecord(c->arrived[j], stream));
-            SH_HIP(hipStreamWaitEvent(c->sorter, c->arrived[j], 0));
+            LSD_HIP(hipEventRecord(c->arrived[j], stream));
+            LSD_HIP(hipStreamWaitEvent(c->sorter, c->arrived[j], 0));
         }
-        if (sub_size[j] == 0) SH_HIP(hipMemsetAsync(ws + L.sort_ws, 0, sizeof(uint32_t), sort_on));   // an empty sort never touches its fault word
+        if (sub_size[j] == 0) LSD_HIP(hipMemsetAsync(ws + L.sort_ws, 0, sizeof(uint32_t), sort_on));   // an empty sort never touches its fault word
         // under the MSB partition the keys of sub-bucket j of rank r all carry the top `bits` bits (r, j): the hybrid form plans
         // its buckets below such a prefix (hybrid.hip; the device finds it itself -- the argument says what this caller knows)
-        SH_TRY(lsdsort_u32_device_prefixed(d_out + sub_begin, ws + L.sort_ws, L.sort_ws_bytes, (size_t)sub_size[j], radix_bits,
+        LSD_TRY(lsdsort_u32_device_prefixed(d_out + sub_begin, ws + L.sort_ws, L.sort_ws_bytes, (size_t)sub_size[j], radix_bits,
                                            partition == LSDSORT_PARTITION_MSB ? bits : 0, sort_on));
-        SH_HIP(lsd::launch_keep_fault(sticky, reinterpret_cast<const uint32_t*>(ws + L.sort_ws), sort_on));
+        LSD_HIP(lsd::launch_keep_fault(sticky, reinterpret_cast<const uint32_t*>(ws + L.sort_ws), sort_on));
         sub_begin += sub_size[j];
     }
     if (S > 1) {   // the caller's stream sees the step complete
-        SH_HIP(hipEventRecord(c->sorted_all, c->sorter));
-        SH_HIP(hipStreamWaitEvent(stream, c->sorted_all, 0));
+        LSD_HIP(hipEventRecord(c->sorted_all, c->sorter));
+        LSD_HIP(hipStreamWaitEvent(stream, c->sorted_all, 0));
     }
     return LSDSORT_OK;
 }
@@ -817,7 +790,7 @@ int comm_set(int ndev, bool loopback, CommSet** out)
 {
     std::lock_guard<std::mutex> lock(g_sets_mutex);
     int cur = 0;
-    SH_HIP(hipGetDevice(&cur));
+    LSD_HIP(hipGetDevice(&cur));
     CommSet*& slot = loopback ? g_loop_sets[ndev] : g_sets[ndev];
     if (slot && loopback && slot->devices[0] != cur) {   // the loopback set follows the current device
         for (lsdsort_comm* c : slot->comms) (void)lsdsort_comm_destroy(c);
@@ -899,16 +872,16 @@ int sort_shard(CommSet* set, int rank, uint32_t* keys, size_t begin, size_t n_lo
     auto reserve = [&]() -> int {
         ws_bytes = lsdsort_sharded_workspace_bytes(n_local, cap, c->world, radix_bits);
         if (ws_bytes == 0) return LSDSORT_ERR_TOO_LARGE;
-        SH_HIP(hipMalloc(reinterpret_cast<void**>(&d_out), (cap ? cap : 1) * sizeof(uint32_t)));
-        SH_HIP(hipMalloc(&d_ws, ws_bytes));
+        LSD_HIP(hipMalloc(reinterpret_cast<void**>(&d_out), (cap ? cap : 1) * sizeof(uint32_t)));
+        LSD_HIP(hipMalloc(&d_ws, ws_bytes));
         return LSDSORT_OK;
     };
     auto set_up = [&]() -> int {
-        SH_HIP(hipSetDevice(set->devices[rank]));
-        SH_TRY(lsdsort_prepare_device());
-        SH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        SH_HIP(hipMalloc(reinterpret_cast<void**>(&d_in), (n_local ? n_local : 1) * sizeof(uint32_t)));
-        if (n_local) SH_HIP(hipMemcpy(d_in, keys + begin, n_local * sizeof(uint32_t), hipMemcpyHostToDevice));
+        LSD_HIP(hipSetDevice(set->devices[rank]));
+        LSD_TRY(lsdsort_prepare_device());
+        LSD_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        LSD_HIP(hipMalloc(reinterpret_cast<void**>(&d_in), (n_local ? n_local : 1) * sizeof(uint32_t)));
+        if (n_local) LSD_HIP(hipMemcpy(d_in, keys + begin, n_local * sizeof(uint32_t), hipMemcpyHostToDevice));
         return reserve();
     };
     int status = set->agreement.agree(set_up());
@@ -953,7 +926,7 @@ int sort_host_multi(uint32_t* keys, size_t n, int radix_bits, int num_gpus, bool
     int prev = 0;
     (void)hipGetDevice(&prev);
     CommSet* set = nullptr;
-    SH_TRY(comm_set(num_gpus, loopback, &set));
+    LSD_TRY(comm_set(num_gpus, loopback, &set));
     std::lock_guard<std::mutex> busy(set->busy);
     std::vector<int> status(num_gpus, LSDSORT_OK);
     std::vector<std::thread> threads;

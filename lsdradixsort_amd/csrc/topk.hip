@@ -32,13 +32,9 @@
 #include "../../include/lsdsort.h"
 
 #include "lsd_device.hpp"
-#include "lsd_kernels.hpp"
+#include "lsd_host.hpp"
 
 namespace lsd {
-
-int device_rank_method(int radix_bits, int* rank_method);   // lsdsort_api.hip: set-up of the current device
-void set_last_hip_error(hipError_t e);                      // lsdsort_api.hip: what lsdsort_last_hip_error reports
-
 namespace {
 
 // The sort route takes over where k * kLargeKDen > cols * kLargeKNum.  By bytes the select route costs at most 20 B per key of the
@@ -54,8 +50,6 @@ constexpr uint32_t kBins = 2048;              // long rows: counters per row (11
 constexpr uint32_t kLongThreads = 256, kLongWaves = kLongThreads / kWave, kLongTile = kLongThreads * kRegs;
 constexpr uint32_t kMinChunk = 16384, kMaxChunks = 2048;
 
-size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
-size_t min_sz(size_t a, size_t b) { return a < b ? a : b; }
 size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 
 __device__ __forceinline__ void wave_sync()
@@ -527,21 +521,6 @@ size_t sort_route_keys(size_t rows, size_t cols, size_t k)
     return min_sz(min_sz(rows * cols, rows * ((k * kLargeKDen + kLargeKNum - 1) / kLargeKNum)), LSDSORT_MAX_KEYS);
 }
 
-uint32_t grid_for(size_t items, size_t per_workgroup, size_t cap)
-{
-    const size_t g = (items + per_workgroup - 1) / per_workgroup;
-    return (uint32_t)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
-#define TOPK_HIP(expr)               \
-    do {                             \
-        hipError_t e__ = (expr);     \
-        if (e__ != hipSuccess) {     \
-            set_last_hip_error(e__); \
-            return LSDSORT_ERR_HIP;  \
-        }                            \
-    } while (0)
-
 int run_topk(const uint32_t* keys, size_t rows, size_t cols, size_t k, int key_type, int largest, const KeyTransform& xf,
              uint32_t* out_keys, uint32_t* out_idx, char* ws, const TopkLayout& L, hipStream_t stream)
 {
@@ -558,12 +537,11 @@ int run_topk(const uint32_t* keys, size_t rows, size_t cols, size_t k, int key_t
                            (uint32_t)cols);
         hipLaunchKernelGGL(topk_copy_kernel, dim3(grid_for(n, 1024, 8192)), dim3(256), 0, stream, keys, copy, idx, (uint32_t)n,
                            (uint32_t)cols);
-        TOPK_HIP(hipGetLastError());
-        const int st = lsdsort_segmented_device(copy, idx, offsets, rows, n, key_type, largest, ws + L.s_seg, L.s_seg_bytes, stream);
-        if (st != LSDSORT_OK) return st;
+        LSD_HIP(hipGetLastError());
+        LSD_TRY(lsdsort_segmented_device(copy, idx, offsets, rows, n, key_type, largest, ws + L.s_seg, L.s_seg_bytes, stream));
         hipLaunchKernelGGL(topk_take_kernel, dim3(grid_for(rows * k, 1024, 8192)), dim3(256), 0, stream, copy, idx, (uint32_t)cols, out);
-        TOPK_HIP(hipGetLastError());
-        TOPK_HIP(launch_keep_fault(ctl, reinterpret_cast<const uint32_t*>(ws + L.s_seg), stream));
+        LSD_HIP(hipGetLastError());
+        LSD_HIP(launch_keep_fault(ctl, reinterpret_cast<const uint32_t*>(ws + L.s_seg), stream));
         return LSDSORT_OK;
     }
 
@@ -575,7 +553,7 @@ int run_topk(const uint32_t* keys, size_t rows, size_t cols, size_t k, int key_t
             hipLaunchKernelGGL(topk_short_kernel<1>, dim3(grid_for(rows, 8, 16384)), dim3(512), 0, stream, sp);
         else
             hipLaunchKernelGGL(topk_short_kernel<16>, dim3(grid_for(rows, 1, 4096)), dim3(1024), 0, stream, sp);
-        TOPK_HIP(hipGetLastError());
+        LSD_HIP(hipGetLastError());
     } else {
         const Chunks ch = chunks_for(rows, cols);
         LongParams lp{};
@@ -599,17 +577,16 @@ int run_topk(const uint32_t* keys, size_t rows, size_t cols, size_t k, int key_t
         hipLaunchKernelGGL(topk_scan_kernel<1>, dim3(row_grid), dim3(256), 0, stream, lp);
         hipLaunchKernelGGL(topk_hist_kernel<2>, dim3(grid), dim3(kLongThreads), 0, stream, lp);
         hipLaunchKernelGGL(topk_scan_kernel<2>, dim3(row_grid), dim3(256), 0, stream, lp);
-        TOPK_HIP(hipGetLastError());
+        LSD_HIP(hipGetLastError());
         hipLaunchKernelGGL(topk_count_kernel, dim3(grid), dim3(kLongThreads), 0, stream, lp);
         hipLaunchKernelGGL(topk_write_kernel, dim3(grid), dim3(kLongThreads), 0, stream, lp);
-        TOPK_HIP(hipGetLastError());
+        LSD_HIP(hipGetLastError());
     }
     if (k < 2) return LSDSORT_OK;   // one winner per row is in order as it stands
     hipLaunchKernelGGL(topk_offsets_kernel, dim3(grid_for(rows + 1, 256, 1024)), dim3(256), 0, stream, offsets, (uint32_t)rows, (uint32_t)k);
-    TOPK_HIP(hipGetLastError());
-    const int st = lsdsort_segmented_device(out_keys, out_idx, offsets, rows, rows * k, key_type, largest, ws + L.seg, L.seg_bytes, stream);
-    if (st != LSDSORT_OK) return st;
-    TOPK_HIP(launch_keep_fault(ctl, reinterpret_cast<const uint32_t*>(ws + L.seg), stream));
+    LSD_HIP(hipGetLastError());
+    LSD_TRY(lsdsort_segmented_device(out_keys, out_idx, offsets, rows, rows * k, key_type, largest, ws + L.seg, L.seg_bytes, stream));
+    LSD_HIP(launch_keep_fault(ctl, reinterpret_cast<const uint32_t*>(ws + L.seg), stream));
     return LSDSORT_OK;
 }
 
@@ -630,25 +607,17 @@ size_t lsdsort_topk_workspace_bytes(size_t rows, size_t cols, size_t k)
 int lsdsort_topk_device(const void* d_keys, size_t rows, size_t cols, size_t k, int key_type, int largest, void* d_out_keys,
                         uint32_t* d_out_idx, void* d_workspace, size_t workspace_bytes, void* hip_stream)
 {
-    lsd::KeyTransform xf{};
-    switch (key_type) {
-        case LSDSORT_KEY_U32: break;
-        case LSDSORT_KEY_I32: xf.b = 0x80000000u; break;
-        case LSDSORT_KEY_F32: xf.a = 0x80000000u; xf.b = 0x80000000u; break;
-        default: return LSDSORT_ERR_INVALID_ARG;
-    }
-    if (largest) xf.c = 0xFFFFFFFFu;
-    xf.on = (xf.a | xf.b | xf.c) != 0u;
+    lsd::KeyTransform xf;
+    LSD_TRY(lsd::key_transform(key_type, largest, &xf));
     if (rows > LSDSORT_MAX_KEYS || (rows != 0 && cols > LSDSORT_MAX_KEYS / rows)) return LSDSORT_ERR_TOO_LARGE;
     if (k > cols) return LSDSORT_ERR_INVALID_ARG;
     if (rows == 0 || cols == 0 || k == 0) return LSDSORT_OK;
     if (!d_keys || !d_out_keys) return LSDSORT_ERR_INVALID_ARG;
     const lsd::TopkLayout L = lsd::topk_layout(rows, cols, k, lsd::sort_route_keys(rows, cols, k));
     const size_t need = L.total > L.s_total ? L.total : L.s_total;
-    if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255u) || workspace_bytes < need) return LSDSORT_ERR_WORKSPACE;
+    if (!lsd::workspace_ok(d_workspace, workspace_bytes, need)) return LSDSORT_ERR_WORKSPACE;
     int rank_method = 0;
-    const int ready = lsd::device_rank_method(8, &rank_method);
-    if (ready != LSDSORT_OK) return ready;
+    LSD_TRY(lsd::device_rank_method(8, &rank_method));
     return lsd::run_topk(static_cast<const uint32_t*>(d_keys), rows, cols, k, key_type, largest ? 1 : 0, xf,
                          static_cast<uint32_t*>(d_out_keys), d_out_idx, static_cast<char*>(d_workspace), L,
                          static_cast<hipStream_t>(hip_stream));

@@ -16,33 +16,9 @@
 #define LSDSORT_BUILD 1
 #include "../../include/lsdsort.h"
 
-#include <hip/hip_runtime.h>
-
-#include "lsd_kernels.hpp"
-
-namespace lsd {
-void set_last_hip_error(hipError_t e);
-}
+#include "lsd_host.hpp"
 
 namespace {
-
-constexpr size_t kAlign = 256;
-size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
-
-#define W_HIP(expr)                           \
-    do {                                      \
-        hipError_t e__ = (expr);              \
-        if (e__ != hipSuccess) {              \
-            lsd::set_last_hip_error(e__);     \
-            (void)hipGetLastError();          \
-            return LSDSORT_ERR_HIP;           \
-        }                                     \
-    } while (0)
-#define W_TRY(expr)                        \
-    do {                                   \
-        int s__ = (expr);                  \
-        if (s__ != LSDSORT_OK) return s__; \
-    } while (0)
 
 constexpr int kThreads = 256;
 uint32_t grid_for(size_t n, size_t per_thread = 4)
@@ -84,8 +60,8 @@ WideLayout make_wide_layout(size_t n, int radix_bits, int key_bits, int val_bits
 {
     WideLayout L;
     size_t off = 0;
-    L.sticky = off; off += kAlign;
-    const size_t words = align_up(n * sizeof(uint32_t));
+    L.sticky = off; off += lsd::kAlign;
+    const size_t words = lsd::align_up(n * sizeof(uint32_t));
     if (key_bits == 64) {
         L.a = off; off += words;
         L.b = off; off += words;
@@ -98,7 +74,7 @@ WideLayout make_wide_layout(size_t n, int radix_bits, int key_bits, int val_bits
     L.payloads = (key_bits == 64 ? 1 : 0) + val_bits / 32;
     L.sort_ws = off;
     L.sort_ws_bytes = lsdsort_workspace_bytes(n, radix_bits, L.payloads);
-    off += align_up(L.sort_ws_bytes);
+    off += lsd::align_up(L.sort_ws_bytes);
     L.total = off;
     return L;
 }
@@ -114,7 +90,7 @@ int check_common(const void* d_keys, void* ws, size_t ws_bytes, size_t n, int ra
     if (lsdsort_workspace_bytes(1, radix_bits, 1) == 0) return LSDSORT_ERR_INVALID_ARG;
     if (n == 0) return LSDSORT_OK;
     if (!d_keys) return LSDSORT_ERR_INVALID_ARG;
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & (kAlign - 1)) || ws_bytes < L.total) return LSDSORT_ERR_WORKSPACE;
+    if (!lsd::workspace_ok(ws, ws_bytes, L.total)) return LSDSORT_ERR_WORKSPACE;
     return LSDSORT_OK;
 }
 
@@ -128,29 +104,66 @@ size_t lsdsort_wide_workspace_bytes(size_t n, int radix_bits, int key_bits, int 
     return make_wide_layout(n, radix_bits, key_bits, val_bits).total;
 }
 
-int lsdsort_u64_device(uint64_t* d_keys, void* d_workspace, size_t workspace_bytes, size_t n, int radix_bits, void* hip_stream)
+// Any of the wide combinations (key_bits 32 | 64, val_bits 0 | 32 | 64); stable by key.
+static int sort_wide(void* d_keys, void* d_vals, int key_bits, int val_bits, void* d_workspace, size_t workspace_bytes, size_t n,
+                     int radix_bits, void* hip_stream)
 {
-    const WideLayout L = make_wide_layout(n, radix_bits, 64, 0);
-    W_TRY(check_common(d_keys, d_workspace, workspace_bytes, n, radix_bits, L));
+    const WideLayout L = make_wide_layout(n, radix_bits, key_bits, val_bits);
+    LSD_TRY(check_common(d_keys, d_workspace, workspace_bytes, n, radix_bits, L));
     if (n == 0) return LSDSORT_OK;
-    W_TRY(lsdsort_prepare_device());
+    if (val_bits && !d_vals) return LSDSORT_ERR_INVALID_ARG;
+    LSD_TRY(lsdsort_prepare_device());
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     char* ws = static_cast<char*>(d_workspace);
-    uint32_t* lo = reinterpret_cast<uint32_t*>(ws + L.a);
-    uint32_t* hi = reinterpret_cast<uint32_t*>(ws + L.b);
+    const uint32_t g = grid_for(n);
     uint32_t* sticky = reinterpret_cast<uint32_t*>(ws + L.sticky);
     const uint32_t* fault = reinterpret_cast<const uint32_t*>(ws + L.sort_ws);   // the sorts' fault word: first word of their workspace
-    W_HIP(hipMemsetAsync(sticky, 0, sizeof(uint32_t), s));
-    hipLaunchKernelGGL(split_u64_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, reinterpret_cast<const uint2*>(d_keys), lo, hi, n);
-    W_HIP(hipGetLastError());
-    // low word first, then a stable sort on the high word: sorted by (hi, lo) -- the LSD argument, one word at a time
-    W_TRY(lsdsort_pairs_u32_device(lo, hi, ws + L.sort_ws, L.sort_ws_bytes, n, radix_bits, s));
-    W_HIP(lsd::launch_keep_fault(sticky, fault, s));   // the next sort's memset clears that word
-    W_TRY(lsdsort_pairs_u32_device(hi, lo, ws + L.sort_ws, L.sort_ws_bytes, n, radix_bits, s));
-    W_HIP(lsd::launch_keep_fault(sticky, fault, s));
-    hipLaunchKernelGGL(merge_u64_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, lo, hi, reinterpret_cast<uint2*>(d_keys), n);
-    W_HIP(hipGetLastError());
+    LSD_HIP(hipMemsetAsync(sticky, 0, sizeof(uint32_t), s));
+    // the words of the records as arrays of their own: 32-bit members are used where they lie
+    uint32_t* klo = key_bits == 64 ? reinterpret_cast<uint32_t*>(ws + L.a) : static_cast<uint32_t*>(d_keys);
+    uint32_t* khi = key_bits == 64 ? reinterpret_cast<uint32_t*>(ws + L.b) : nullptr;
+    uint32_t* vlo = val_bits == 64 ? reinterpret_cast<uint32_t*>(ws + L.c) : static_cast<uint32_t*>(d_vals);   // null: keys only
+    uint32_t* vhi = val_bits == 64 ? reinterpret_cast<uint32_t*>(ws + L.d) : nullptr;
+    if (key_bits == 64) {
+        hipLaunchKernelGGL(split_u64_kernel, dim3(g), dim3(kThreads), 0, s, static_cast<const uint2*>(d_keys), klo, khi, n);
+        LSD_HIP(hipGetLastError());
+    }
+    if (val_bits == 64) {
+        hipLaunchKernelGGL(split_u64_kernel, dim3(g), dim3(kThreads), 0, s, static_cast<const uint2*>(d_vals), vlo, vhi, n);
+        LSD_HIP(hipGetLastError());
+    }
+    // LSD over the key's words, low word first, then a stable sort on the high word: sorted by (hi, lo) -- the LSD argument, one
+    // word at a time; everything else rides as payload arrays (stable: ties keep their order)
+    {
+        uint32_t* pay[3];
+        int np = 0;
+        if (khi) pay[np++] = khi;
+        if (vlo) pay[np++] = vlo;
+        if (vhi) pay[np++] = vhi;
+        LSD_TRY(lsdsort_multi_u32_device(klo, pay, np, ws + L.sort_ws, L.sort_ws_bytes, n, radix_bits, s));
+        LSD_HIP(lsd::launch_keep_fault(sticky, fault, s));   // the next sort's memset clears that word
+    }
+    if (khi) {
+        uint32_t* pay[3];
+        int np = 0;
+        pay[np++] = klo;
+        if (vlo) pay[np++] = vlo;
+        if (vhi) pay[np++] = vhi;
+        LSD_TRY(lsdsort_multi_u32_device(khi, pay, np, ws + L.sort_ws, L.sort_ws_bytes, n, radix_bits, s));
+        LSD_HIP(lsd::launch_keep_fault(sticky, fault, s));
+        hipLaunchKernelGGL(merge_u64_kernel, dim3(g), dim3(kThreads), 0, s, klo, khi, static_cast<uint2*>(d_keys), n);
+        LSD_HIP(hipGetLastError());
+    }
+    if (vhi) {
+        hipLaunchKernelGGL(merge_u64_kernel, dim3(g), dim3(kThreads), 0, s, vlo, vhi, static_cast<uint2*>(d_vals), n);
+        LSD_HIP(hipGetLastError());
+    }
     return LSDSORT_OK;
+}
+
+int lsdsort_u64_device(uint64_t* d_keys, void* d_workspace, size_t workspace_bytes, size_t n, int radix_bits, void* hip_stream)
+{
+    return sort_wide(d_keys, nullptr, 64, 0, d_workspace, workspace_bytes, n, radix_bits, hip_stream);
 }
 
 // Records: keys of key_bits (32 | 64) with payloads of val_bits (32 | 64, not both 32); stable by key.
@@ -158,56 +171,7 @@ int lsdsort_records_device(void* d_keys, void* d_vals, int key_bits, int val_bit
                            size_t n, int radix_bits, void* hip_stream)
 {
     if (!wide_combo(key_bits, val_bits) || val_bits == 0) return LSDSORT_ERR_INVALID_ARG;
-    const WideLayout L = make_wide_layout(n, radix_bits, key_bits, val_bits);
-    W_TRY(check_common(d_keys, d_workspace, workspace_bytes, n, radix_bits, L));
-    if (n == 0) return LSDSORT_OK;
-    if (!d_vals) return LSDSORT_ERR_INVALID_ARG;
-    W_TRY(lsdsort_prepare_device());
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    char* ws = static_cast<char*>(d_workspace);
-    const uint32_t g = grid_for(n);
-    uint32_t* sticky = reinterpret_cast<uint32_t*>(ws + L.sticky);
-    const uint32_t* fault = reinterpret_cast<const uint32_t*>(ws + L.sort_ws);
-    W_HIP(hipMemsetAsync(sticky, 0, sizeof(uint32_t), s));
-    // the words of the records as arrays of their own: 32-bit members are used where they lie
-    uint32_t* klo = key_bits == 64 ? reinterpret_cast<uint32_t*>(ws + L.a) : static_cast<uint32_t*>(d_keys);
-    uint32_t* khi = key_bits == 64 ? reinterpret_cast<uint32_t*>(ws + L.b) : nullptr;
-    uint32_t* vlo = val_bits == 64 ? reinterpret_cast<uint32_t*>(ws + L.c) : static_cast<uint32_t*>(d_vals);
-    uint32_t* vhi = val_bits == 64 ? reinterpret_cast<uint32_t*>(ws + L.d) : nullptr;
-    if (key_bits == 64) {
-        hipLaunchKernelGGL(split_u64_kernel, dim3(g), dim3(kThreads), 0, s, static_cast<const uint2*>(d_keys), klo, khi, n);
-        W_HIP(hipGetLastError());
-    }
-    if (val_bits == 64) {
-        hipLaunchKernelGGL(split_u64_kernel, dim3(g), dim3(kThreads), 0, s, static_cast<const uint2*>(d_vals), vlo, vhi, n);
-        W_HIP(hipGetLastError());
-    }
-    // LSD over the key's words, low word first; everything else rides as payload arrays (stable: ties keep their order)
-    {
-        uint32_t* pay[3];
-        int np = 0;
-        if (khi) pay[np++] = khi;
-        pay[np++] = vlo;
-        if (vhi) pay[np++] = vhi;
-        W_TRY(lsdsort_multi_u32_device(klo, pay, np, ws + L.sort_ws, L.sort_ws_bytes, n, radix_bits, s));
-        W_HIP(lsd::launch_keep_fault(sticky, fault, s));
-    }
-    if (khi) {
-        uint32_t* pay[3];
-        int np = 0;
-        pay[np++] = klo;
-        pay[np++] = vlo;
-        if (vhi) pay[np++] = vhi;
-        W_TRY(lsdsort_multi_u32_device(khi, pay, np, ws + L.sort_ws, L.sort_ws_bytes, n, radix_bits, s));
-        W_HIP(lsd::launch_keep_fault(sticky, fault, s));
-        hipLaunchKernelGGL(merge_u64_kernel, dim3(g), dim3(kThreads), 0, s, klo, khi, static_cast<uint2*>(d_keys), n);
-        W_HIP(hipGetLastError());
-    }
-    if (vhi) {
-        hipLaunchKernelGGL(merge_u64_kernel, dim3(g), dim3(kThreads), 0, s, vlo, vhi, static_cast<uint2*>(d_vals), n);
-        W_HIP(hipGetLastError());
-    }
-    return LSDSORT_OK;
+    return sort_wide(d_keys, d_vals, key_bits, val_bits, d_workspace, workspace_bytes, n, radix_bits, hip_stream);
 }
 
 int lsdsort_wide_check_device(void* d_workspace, size_t n, int radix_bits, int key_bits, int val_bits, void* hip_stream)
