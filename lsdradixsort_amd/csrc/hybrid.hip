@@ -55,9 +55,7 @@ __global__ void __launch_bounds__(1024) hybrid_sample_kernel(const uint32_t* __r
     // the key prefix: bits in which no sampled key differs from the first key of the array.  All 64 workgroups OR into the plan
     // word (the upfront read takes its leading zeros, and checks them against every key); for ITS look at the buckets a workgroup
     // uses what its own 1024 samples say -- they span the whole array, and this look is a heuristic.
-    uint32_t d = k ^ keys[0];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) d |= __shfl_xor(d, off, kWave);
+    const uint32_t d = wave_or(k ^ keys[0]);
     if ((tid & 63u) == 0u) atomicOr(&s_differ, d);
     __syncthreads();
     const uint32_t differ = s_differ;
@@ -73,11 +71,7 @@ hipError_t launch_hybrid_sample(const uint32_t* keys, uint32_t n, int bucket_bit
     if (n < 65536u * 64u || bucket_bits < 11 || (1 << bucket_bits) > kHybridBuckets || !words) return hipErrorInvalidValue;
     const uint32_t bucket_shift = 32u - (uint32_t)bucket_bits;
     constexpr size_t lds_bytes = (size_t)32768 * sizeof(uint32_t);
-    static std::atomic<uint64_t> told{0};
-        const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(hybrid_sample_kernel), lds_bytes, told);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(hybrid_sample_kernel, dim3(64), dim3(1024), lds_bytes, stream, keys, n, bucket_shift, words);
-    return hipGetLastError();
+    return launch_dynamic_lds<hybrid_sample_kernel>(dim3(64), dim3(1024), lds_bytes, stream, keys, n, bucket_shift, words);
 }
 
 // R: digit width of the global passes, 8 or 4.  XF: typed keys, counted as to_sortable(key, xf).  The key prefix (0 .. 7 bits, from
@@ -381,27 +375,17 @@ __global__ void __launch_bounds__(1024) hybrid_plan_kernel(const uint32_t* __res
             fields_out[256u + byte] = b;
         }
     }
-    uint32_t incl = wave_inclusive_scan(sum, lane);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const uint32_t other = __shfl_xor(mx, off, kWave);
-        mx = other > mx ? other : mx;
-    }
-    if (lane == 63u) s_wave[wave] = incl;
+    mx = wave_max(mx);
     if (lane == 0u) s_max[wave] = mx;
-    __syncthreads();
+    uint32_t total = 0;
+    uint32_t run = group_exclusive_scan<16>(sum, lane, wave, s_wave, &total);
     if (R == 4 && tid < 256) {
         fields_out[512u + tid] = s_c[tid];
         fields_out[768u + tid] = s_d[tid];
     }
-    uint32_t carry = 0, total = 0, largest = 0;
+    uint32_t largest = 0;
 #pragma unroll
-    for (int w = 0; w < 16; w++) {
-        carry += (uint32_t)w < wave ? s_wave[w] : 0u;
-        total += s_wave[w];
-        largest = s_max[w] > largest ? s_max[w] : largest;
-    }
-    uint32_t run = carry + incl - sum;
+    for (int w = 0; w < 16; w++) largest = s_max[w] > largest ? s_max[w] : largest;
 #pragma unroll
     for (int j = 0; j < (int)PER; j++) {
         bases[(size_t)tid * PER + j] = run;

@@ -20,6 +20,9 @@
 //   store             : from LDS, linear.
 // Counters are 16 bits wide, two to a word (a wave holds at most 2048 keys): 8 waves x 512 digits in 8 KiB, so that two
 // workgroups share a CU (72 KiB each) and one's loads and barriers hide under the other's LDS work.
+//
+// The pass is written once (LocalGroup and the steps that follow it); sort_bucket, sort_bucket_multi and sort_segment are what is
+// particular to each: how keys are loaded, which digits run, and what leaves.
 #include "lsd_device.hpp"
 #include "lsd_kernels.hpp"
 
@@ -35,140 +38,220 @@ static_assert(kLocalThreads * 20 == kLocalSortCapSmall && kLocalThreads * 16 == 
 template <int K>
 constexpr size_t local_lds_words() { return (size_t)kLocalThreads * K + kLocalWaves * (kLocalMaxBins / 2) + 64; }
 
+// ---- the workgroup's LDS, one bucket's place in it, and the steps of a digit pass ---------------------------------------------
+// K registers per thread and array: key[i], rank[i], val[i] belong to position wbase + 64 i, rows of them in use.
+template <int K>
+struct LocalGroup {
+    lds_u32* s_keys;              // [T * K]: keys (then payloads) in their new order
+    volatile lds_u32* s_cnt;      // [W][256] words = [W][512] 16-bit counters, then bases
+    volatile lds_u16* s_cnt16;
+    lds_u32* s_misc;              // 64 words: the scan's partials [0, W), the callers' reductions over waves from 32
+    uint32_t tid, lane, wave;
+    uint32_t size, rows, wbase;   // rows = ceil(size / T), uniform, 1 .. K
+};
+template <int K>
+__device__ __forceinline__ LocalGroup<K> local_group(uint32_t size)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    LocalGroup<K> g;
+    g.s_keys = (lds_u32*)smem;
+    g.s_cnt = (volatile lds_u32*)(g.s_keys + kLocalThreads * K);
+    g.s_cnt16 = (volatile lds_u16*)g.s_cnt;
+    g.s_misc = (lds_u32*)(g.s_cnt + kLocalWaves * (kLocalMaxBins / 2));
+    g.tid = threadIdx.x;
+    g.lane = g.tid & 63u;
+    g.wave = g.tid >> 6;
+    g.size = size;
+    g.rows = (size + (uint32_t)kLocalThreads - 1u) / (uint32_t)kLocalThreads;
+    g.wbase = g.wave * g.rows * 64u + g.lane;
+    return g;
+}
+
+__device__ __forceinline__ void raise_fault(uint32_t* fault, uint32_t bit)
+{
+    if (threadIdx.x == 0 && fault) atomicOr(fault, bit);
+}
+
+// r[i] = src[position of register i], 0xFFFFFFFF past the end and in the rows past the last (the paired scatter looks at one)
+template <int K>
+__device__ __forceinline__ void load_rows(const LocalGroup<K>& g, const uint32_t* src, uint32_t (&r)[K])
+{
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+        r[i] = 0xFFFFFFFFu;
+        if ((uint32_t)i < g.rows) {
+            const uint32_t pos = g.wbase + (uint32_t)i * 64u;
+            if (pos < g.size) r[i] = src[pos];
+        }
+    }
+}
+// LDS -> registers in position order; registers -> LDS at slot[i]; LDS -> global memory, linear (x: the key transform to undo)
+template <int K>
+__device__ __forceinline__ void read_rows(const LocalGroup<K>& g, uint32_t (&r)[K])
+{
+#pragma unroll
+    for (int i = 0; i < K; i++)
+        if ((uint32_t)i < g.rows) r[i] = g.s_keys[g.wbase + (uint32_t)i * 64u];
+}
+template <int K>
+__device__ __forceinline__ void write_slots(const LocalGroup<K>& g, const uint32_t (&slot)[K], const uint32_t (&r)[K])
+{
+#pragma unroll
+    for (int i = 0; i < K; i++)
+        if ((uint32_t)i < g.rows) g.s_keys[slot[i]] = r[i];
+}
+template <int K>
+__device__ __forceinline__ void store_linear(const LocalGroup<K>& g, uint32_t* dst, const KeyTransform* x = nullptr)
+{
+    for (uint32_t q = g.tid; q < g.size; q += (uint32_t)kLocalThreads) dst[q] = x ? from_sortable(g.s_keys[q], *x) : g.s_keys[q];
+}
+
+// Count and rank: rank[i] = the keys of this wave with key[i]'s digit that stand before it, by one returning add per key.
+template <int K>
+__device__ __forceinline__ void count_and_rank(const LocalGroup<K>& g, const uint32_t (&key)[K], uint32_t (&rank)[K], uint32_t shift,
+                                               uint32_t mask)
+{
+    constexpr int HW = kLocalMaxBins / 2;   // counter words per wave
+    // this wave's counters start at zero (its own words only: LDS operations of a wave are served in order, and nobody
+    // else reads them before the barrier below)
+#pragma unroll
+    for (int j = 0; j < HW / kWave; j++) g.s_cnt[g.wave * HW + j * kWave + g.lane] = 0;
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+        if ((uint32_t)i < g.rows) {
+            const uint32_t d = (key[i] >> shift) & mask;
+            const uint32_t sh = (d & 1u) * 16u;
+            const uint32_t old = __hip_atomic_fetch_add((lds_u32*)&g.s_cnt[g.wave * HW + (d >> 1)], 1u << sh, __ATOMIC_RELAXED,
+                                                        __HIP_MEMORY_SCOPE_WAVEFRONT);
+            rank[i] = (old >> sh) & 0xFFFFu;
+        }
+    }
+    __syncthreads();
+}
+// Counts to bases, one thread per digit: the waves' counts become their bases inside the digit's range, the digits' totals an
+// exclusive scan.
+template <int K>
+__device__ __forceinline__ void counts_to_bases(const LocalGroup<K>& g, uint32_t bins)
+{
+    constexpr int W = kLocalWaves;
+    uint32_t total = 0;
+    uint32_t wave_excl[W];
+    if (g.tid < bins) {
+#pragma unroll
+        for (int w = 0; w < W; w++) {
+            wave_excl[w] = total;
+            total += g.s_cnt16[w * kLocalMaxBins + g.tid];
+        }
+    }
+    const uint32_t local_off = group_exclusive_scan<W>(total, g.lane, g.wave, g.s_misc);   // total = 0 past the last digit
+    if (g.tid < bins) {
+#pragma unroll
+        for (int w = 0; w < W; w++) g.s_cnt16[w * kLocalMaxBins + g.tid] = (uint16_t)(local_off + wave_excl[w]);
+    }
+    __syncthreads();
+}
+// Scatter: key[i] to LDS slot base + rank.  KEEP: rank[i] becomes that slot (a payload follows its key there).
+template <int K, bool KEEP>
+__device__ __forceinline__ void scatter_keys(const LocalGroup<K>& g, const uint32_t (&key)[K], uint32_t (&rank)[K], uint32_t shift,
+                                             uint32_t mask)
+{
+    // two rows per uniform branch: both base reads are in flight before the first write waits for its own (0.590 -> 0.584 ms per
+    // 2^28 keys).  A row past the bucket's last reads a counter it never uses -- its key register holds whatever it holds,
+    // masked into the table.
+    static_assert(K % 2 == 0, "rows are scattered in pairs");
+#pragma unroll
+    for (int i = 0; i < K; i += 2) {
+        if ((uint32_t)i < g.rows) {
+            const uint32_t b0 = g.s_cnt16[g.wave * kLocalMaxBins + ((key[i] >> shift) & mask)];
+            const uint32_t b1 = g.s_cnt16[g.wave * kLocalMaxBins + ((key[i + 1] >> shift) & mask)];
+            const uint32_t pos0 = b0 + rank[i];
+            if (KEEP) rank[i] = pos0;
+            g.s_keys[pos0] = key[i];
+            if ((uint32_t)(i + 1) < g.rows) {
+                const uint32_t pos1 = b1 + rank[i + 1];
+                if (KEEP) rank[i + 1] = pos1;
+                g.s_keys[pos1] = key[i + 1];
+            }
+        }
+    }
+    __syncthreads();
+}
+// One digit pass over key[] (position order): afterwards the keys lie in LDS in their new order, and with KEEP rank[i] says
+// where key[i] went.
+template <int K, bool KEEP>
+__device__ __forceinline__ void digit_pass(const LocalGroup<K>& g, const uint32_t (&key)[K], uint32_t (&rank)[K], uint32_t shift,
+                                           uint32_t width)
+{
+    const uint32_t bins = 1u << width, mask = bins - 1u;
+    count_and_rank(g, key, rank, shift, mask);
+    counts_to_bases(g, bins);
+    scatter_keys<K, KEEP>(g, key, rank, shift, mask);
+}
+// After a pass the keys are in LDS in their new order.  `last`: they leave for global memory (linear store, `x` undone); otherwise
+// they come back into registers in position order (the next pass's first barrier keeps its LDS writes behind these reads).  With
+// payloads: the same for them, through the same slots, once the keys have been taken out -- two more barriers per pass.
+template <int K, bool PAIRS>
+__device__ __forceinline__ void take_out(const LocalGroup<K>& g, bool last, uint32_t (&key)[K], const uint32_t (&slot)[K],
+                                         uint32_t (&val)[K], uint32_t* keys_out, const KeyTransform* x, uint32_t* vals_out)
+{
+    if (last) store_linear(g, keys_out, x);
+    else read_rows(g, key);
+    if (PAIRS) {
+        __syncthreads();   // every key has been taken out
+        write_slots(g, slot, val);
+        __syncthreads();
+        if (last) store_linear(g, vals_out);
+        else read_rows(g, val);
+    }
+}
+
+// The size of bucket [lo, hi), or 0 where this workgroup has nothing to do: an empty bucket, or one above the capacity -- the
+// small variant leaves larger buckets to the listed launch; above the large capacity the planner promised otherwise: say so,
+// touch nothing.
+template <int K>
+__device__ __forceinline__ uint32_t bucket_size(const LocalSortParams& p, uint32_t lo, uint32_t hi)
+{
+    if (hi < lo) return 0u;
+    if (hi - lo > (uint32_t)(kLocalThreads * K)) {
+        if (!p.larger_elsewhere) raise_fault(p.fault, 8u);
+        return 0u;
+    }
+    return hi - lo;
+}
+
 // K = 32: buckets of up to 16384 keys, 72 KiB of LDS, two workgroups per CU.  K = 20: up to 10240 keys, 48 KiB, THREE per CU
 // (and at most 80 registers): the stage is bound by LDS work that one workgroup's barriers and loads leave idle, so the third
 // resident workgroup is worth about a fifth of its time.  The planner knows the largest bucket and picks (LocalSortParams::skip
 // of the other launch); uniform keys at 2^28 have buckets of 8192 +- 300.
 // PAIRS: a payload word follows each key (LocalSortParams::vals).  It takes the key's LDS slot in a second round of every pass, as
-// in the global pass kernel: keys to LDS, keys back, payloads to the same slots, payloads back -- two more barriers per pass.
+// in the global pass kernel: keys to LDS, keys back, payloads to the same slots, payloads back (take_out).
+// XOUT: a typed sort's keys leave as what they were (int32, float32, descending order).  A kernel of its own: the five
+// instructions per key cost the uint32 sort 0.025 ms of 0.59 when they sat in the one store loop.
 // WHOLE: the bucket is the whole array [0, p.num_buckets) and a fourth digit pass may follow (launch_small_sort)
 template <int K, bool PAIRS, bool XOUT, bool WHOLE = false>
 __device__ __forceinline__ void sort_bucket(const LocalSortParams& p, const uint32_t b)
 {
-    constexpr int T = kLocalThreads, W = kLocalWaves, HW = kLocalMaxBins / 2;   // HW: counter words per wave
-    constexpr int CAP = T * K;
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    lds_u32* const s_keys = (lds_u32*)smem;                               // [CAP]
-    volatile lds_u32* const s_cnt = (volatile lds_u32*)(s_keys + CAP);   // [W][HW] words = [W][512] 16-bit counters, then bases
-    volatile lds_u16* const s_cnt16 = (volatile lds_u16*)s_cnt;
-    lds_u32* const s_misc = (lds_u32*)(s_cnt + W * HW);
-
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t lo = WHOLE ? 0u : p.bases[b], hi = WHOLE ? p.num_buckets : p.bases[b + 1];
-    const uint32_t size = hi - lo;
-    if (size == 0u || hi < lo) return;
-    if (size > (uint32_t)CAP) {
-        // the small variant leaves larger buckets to the listed launch; above the large capacity the planner promised
-        // otherwise: say so, touch nothing
-        if (!p.larger_elsewhere && tid == 0 && p.fault) atomicOr(p.fault, 8u);
-        return;
-    }
+    const uint32_t lo = WHOLE ? 0u : p.bases[b];
+    const uint32_t size = bucket_size<K>(p, lo, WHOLE ? p.num_buckets : p.bases[b + 1]);
+    if (size == 0u) return;
+    const LocalGroup<K> g = local_group<K>(size);
     uint32_t* const bucket = p.keys + lo;
-    const uint32_t rows = (size + (uint32_t)T - 1u) / (uint32_t)T;   // uniform, 1 .. K
-    const uint32_t wbase = wave * rows * 64u + lane;
-
     uint32_t* const bucket_vals = PAIRS ? p.vals + lo : nullptr;
-    uint32_t key[K], rank[K], val[PAIRS ? K : 1];
+    uint32_t key[K], rank[K], val[K];   // val: PAIRS only
+    // keys and payloads in one loop, written out here: through load_rows, or one array after the other, the pairs kernels take ten
+    // registers more (K = 16 spills, the K = 32 list kernel loses a wave per SIMD)
 #pragma unroll
     for (int i = 0; i < K; i++) {
-        key[i] = 0xFFFFFFFFu;   // rows past the bucket's last are never ranked or stored; the paired scatter below looks at one
-        if ((uint32_t)i < rows) {
-            const uint32_t pos = wbase + (uint32_t)i * 64u;
+        key[i] = 0xFFFFFFFFu;   // rows past the bucket's last are never ranked or stored; the paired scatter looks at one
+        if ((uint32_t)i < g.rows) {
+            const uint32_t pos = g.wbase + (uint32_t)i * 64u;
             if (pos < size) key[i] = bucket[pos];
             if (PAIRS) val[i] = pos < size ? bucket_vals[pos] : 0u;
         }
     }
-
-    auto digit_pass = [&](uint32_t shift, uint32_t width) {
-        const uint32_t bins = 1u << width, mask = bins - 1u;
-        // this wave's counters start at zero (its own words only: LDS operations of a wave are served in order, and nobody
-        // else reads them before the barrier below)
-#pragma unroll
-        for (int j = 0; j < HW / kWave; j++) s_cnt[wave * HW + j * kWave + lane] = 0;
-#pragma unroll
-        for (int i = 0; i < K; i++) {
-            if ((uint32_t)i < rows) {
-                const uint32_t d = (key[i] >> shift) & mask;
-                const uint32_t sh = (d & 1u) * 16u;
-                const uint32_t old = __hip_atomic_fetch_add((lds_u32*)&s_cnt[wave * HW + (d >> 1)], 1u << sh, __ATOMIC_RELAXED,
-                                                            __HIP_MEMORY_SCOPE_WAVEFRONT);
-                rank[i] = (old >> sh) & 0xFFFFu;
-            }
-        }
-        __syncthreads();
-        // one thread per digit: the waves' counts become their bases inside the digit's range, the digits' totals an exclusive scan
-        uint32_t total = 0;
-        uint32_t wave_excl[W];
-        if (tid < bins) {
-#pragma unroll
-            for (int w = 0; w < W; w++) {
-                wave_excl[w] = total;
-                total += s_cnt16[w * kLocalMaxBins + tid];
-            }
-        }
-        uint32_t incl = wave_inclusive_scan(tid < bins ? total : 0u, lane);
-        if (lane == 63u) s_misc[wave] = incl;
-        __syncthreads();
-        uint32_t part[W];
-#pragma unroll
-        for (int w = 0; w < W; w++) part[w] = s_misc[w];
-        uint32_t carry = 0;
-#pragma unroll
-        for (int w = 0; w < W; w++) carry += (uint32_t)w < wave ? part[w] : 0u;
-        const uint32_t local_off = incl + carry - total;
-        if (tid < bins) {
-#pragma unroll
-            for (int w = 0; w < W; w++) s_cnt16[w * kLocalMaxBins + tid] = (uint16_t)(local_off + wave_excl[w]);
-        }
-        __syncthreads();
-        // two rows per uniform branch: both base reads are in flight before the first write waits for its own (0.590 -> 0.584 ms per
-        // 2^28 keys).  A row past the bucket's last reads a counter it never uses -- its key register holds whatever it holds,
-        // masked into the table.
-        static_assert(K % 2 == 0, "rows are scattered in pairs");
-#pragma unroll
-        for (int i = 0; i < K; i += 2) {
-            if ((uint32_t)i < rows) {
-                const uint32_t b0 = s_cnt16[wave * kLocalMaxBins + ((key[i] >> shift) & mask)];
-                const uint32_t b1 = s_cnt16[wave * kLocalMaxBins + ((key[i + 1] >> shift) & mask)];
-                const uint32_t pos0 = b0 + rank[i];
-                if (PAIRS) rank[i] = pos0;   // the payload's slot
-                s_keys[pos0] = key[i];
-                if ((uint32_t)(i + 1) < rows) {
-                    const uint32_t pos1 = b1 + rank[i + 1];
-                    if (PAIRS) rank[i + 1] = pos1;
-                    s_keys[pos1] = key[i + 1];
-                }
-            }
-        }
-        __syncthreads();
-    };
-    // after a pass the keys are in LDS in their new order.  `last`: they leave for global memory (linear store); otherwise they
-    // come back into registers in position order (the next pass's first barrier keeps its LDS writes behind these reads).  With
-    // payloads: the same for them, through the same slots, once the keys have been taken out.
-    auto take_out = [&](bool last) {
-        if (last) {
-            // XOUT: a typed sort's keys leave as what they were (int32, float32, descending order).  A kernel of its own: the
-            // five instructions per key cost the uint32 sort 0.025 ms of 0.59 when they sat in the one store loop
-            for (uint32_t q = tid; q < size; q += (uint32_t)T) bucket[q] = XOUT ? from_sortable(s_keys[q], p.xout) : s_keys[q];
-        } else {
-#pragma unroll
-            for (int i = 0; i < K; i++)
-                if ((uint32_t)i < rows) key[i] = s_keys[wbase + (uint32_t)i * 64u];
-        }
-        if (PAIRS) {
-            __syncthreads();   // every key has been taken out
-#pragma unroll
-            for (int i = 0; i < K; i++)
-                if ((uint32_t)i < rows) s_keys[rank[i]] = val[i];
-            __syncthreads();
-            if (last) {
-                for (uint32_t q = tid; q < size; q += (uint32_t)T) bucket_vals[q] = s_keys[q];
-            } else {
-#pragma unroll
-                for (int i = 0; i < K; i++)
-                    if ((uint32_t)i < rows) val[i] = s_keys[wbase + (uint32_t)i * 64u];
-            }
-        }
+    auto pass = [&](uint32_t shift, uint32_t width, bool last) {
+        digit_pass<K, PAIRS>(g, key, rank, shift, width);
+        take_out<K, PAIRS>(g, last, key, rank, val, bucket, XOUT ? &p.xout : nullptr, bucket_vals);
     };
 
     // the digits: as given, or (the hybrid form, planned on the device) bits [0, low) in one or two passes: nine bits, then the rest
@@ -189,32 +272,19 @@ __device__ __forceinline__ void sort_bucket(const LocalSortParams& p, const uint
         uint32_t diff = 0;
 #pragma unroll
         for (int i = 0; i < K; i++)
-            if ((uint32_t)i < rows) diff |= wbase + (uint32_t)i * 64u < size ? key[i] ^ ref : 0u;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) diff |= __shfl_xor(diff, off, kWave);
-        if (lane == 0u) s_misc[32 + wave] = diff;
+            if ((uint32_t)i < g.rows) diff |= g.wbase + (uint32_t)i * 64u < size ? key[i] ^ ref : 0u;
+        diff = wave_or(diff);
+        if (g.lane == 0u) g.s_misc[32 + g.wave] = diff;
         __syncthreads();
 #pragma unroll
-        for (int w = 0; w < W; w++) diff |= s_misc[32 + w];
+        for (int w = 0; w < kLocalWaves; w++) diff |= g.s_misc[32 + w];
         dead0 = ((diff >> sh0) & ((1u << wd0) - 1u)) == 0u;                  // uniform
         dead1 = !dead0 && ((diff >> sh1) & ((1u << wd1) - 1u)) == 0u;
     }
-    if (!dead0) {
-        digit_pass(sh0, wd0);
-        take_out(wd1 == 0u || dead1);
-    }
-    if (wd1 && !dead1) {
-        digit_pass(sh1, wd1);
-        take_out(wd2 == 0u);
-    }
-    if (wd2) {
-        digit_pass(p.shift[2], wd2);
-        take_out(!WHOLE || p.width[3] == 0u);
-    }
-    if (WHOLE && wd2 && p.width[3]) {
-        digit_pass(p.shift[3], p.width[3]);
-        take_out(true);
-    }
+    if (!dead0) pass(sh0, wd0, wd1 == 0u || dead1);
+    if (wd1 && !dead1) pass(sh1, wd1, wd2 == 0u);
+    if (wd2) pass(p.shift[2], wd2, !WHOLE || p.width[3] == 0u);
+    if (WHOLE && wd2 && p.width[3]) pass(p.shift[3], p.width[3], true);
 }
 
 // Several payload arrays (records: lsdsort_multi_u32_device): carrying each of them through every digit pass, as PAIRS does with
@@ -227,123 +297,44 @@ __device__ __forceinline__ void sort_bucket(const LocalSortParams& p, const uint
 template <int K>
 __device__ __forceinline__ void sort_bucket_multi(const LocalSortParams& p, const uint32_t b)
 {
-    constexpr int T = kLocalThreads, W = kLocalWaves, HW = kLocalMaxBins / 2;
-    constexpr int CAP = T * K;
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    lds_u32* const s_keys = (lds_u32*)smem;
-    volatile lds_u32* const s_cnt = (volatile lds_u32*)(s_keys + CAP);
-    volatile lds_u16* const s_cnt16 = (volatile lds_u16*)s_cnt;
-    lds_u32* const s_misc = (lds_u32*)(s_cnt + W * HW);
-
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t lo = p.bases[b], hi = p.bases[b + 1];
-    const uint32_t size = hi - lo;
-    if (size == 0u || hi < lo) return;
-    if (size > (uint32_t)CAP) {
-        if (!p.larger_elsewhere && tid == 0 && p.fault) atomicOr(p.fault, 8u);
-        return;
-    }
+    const uint32_t lo = p.bases[b];
+    const uint32_t size = bucket_size<K>(p, lo, p.bases[b + 1]);
+    if (size == 0u) return;
+    const LocalGroup<K> g = local_group<K>(size);
     uint32_t* const bucket = p.keys + lo;
-    const uint32_t rows = (size + (uint32_t)T - 1u) / (uint32_t)T;
-    const uint32_t wbase = wave * rows * 64u + lane;
-
     uint32_t key[K], slot[K], first_slot[K];
-#pragma unroll
-    for (int i = 0; i < K; i++) {
-        if ((uint32_t)i < rows) {
-            const uint32_t pos = wbase + (uint32_t)i * 64u;
-            key[i] = pos < size ? bucket[pos] : 0xFFFFFFFFu;
-        }
-    }
-    // one digit pass over key[] (position order): afterwards the keys lie in LDS in their new order and slot[i] says where key[i] went
-    auto digit_pass = [&](uint32_t shift, uint32_t width) {
-        const uint32_t bins = 1u << width, mask = bins - 1u;
-#pragma unroll
-        for (int j = 0; j < HW / kWave; j++) s_cnt[wave * HW + j * kWave + lane] = 0;
-#pragma unroll
-        for (int i = 0; i < K; i++) {
-            if ((uint32_t)i < rows) {
-                const uint32_t d = (key[i] >> shift) & mask;
-                const uint32_t sh = (d & 1u) * 16u;
-                const uint32_t old = __hip_atomic_fetch_add((lds_u32*)&s_cnt[wave * HW + (d >> 1)], 1u << sh, __ATOMIC_RELAXED,
-                                                            __HIP_MEMORY_SCOPE_WAVEFRONT);
-                slot[i] = (old >> sh) & 0xFFFFu;
-            }
-        }
-        __syncthreads();
-        uint32_t total = 0;
-        uint32_t wave_excl[W];
-        if (tid < bins) {
-#pragma unroll
-            for (int w = 0; w < W; w++) {
-                wave_excl[w] = total;
-                total += s_cnt16[w * kLocalMaxBins + tid];
-            }
-        }
-        uint32_t incl = wave_inclusive_scan(tid < bins ? total : 0u, lane);
-        if (lane == 63u) s_misc[wave] = incl;
-        __syncthreads();
-        uint32_t carry = 0;
-#pragma unroll
-        for (int w = 0; w < W; w++) carry += (uint32_t)w < wave ? s_misc[w] : 0u;
-        const uint32_t local_off = incl + carry - total;
-        if (tid < bins) {
-#pragma unroll
-            for (int w = 0; w < W; w++) s_cnt16[w * kLocalMaxBins + tid] = (uint16_t)(local_off + wave_excl[w]);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < K; i++) {
-            if ((uint32_t)i < rows) {
-                const uint32_t d = (key[i] >> shift) & mask;
-                slot[i] += (uint32_t)s_cnt16[wave * kLocalMaxBins + d];
-                s_keys[slot[i]] = key[i];
-            }
-        }
-        __syncthreads();
-    };
+    load_rows(g, bucket, key);
     uint32_t sh0 = p.shift[0], wd0 = p.width[0], sh1 = p.shift[1], wd1 = p.width[1];
     if (p.low_bits_word) {   // the hybrid form: bits [0, low), nine first (see sort_bucket)
         const uint32_t low = *p.low_bits_word;
         sh0 = 0u; wd0 = low < 9u ? low : 9u;
         sh1 = wd0; wd1 = low - wd0;
     }
-    digit_pass(sh0, wd0);
+    digit_pass<K, true>(g, key, slot, sh0, wd0);
     if (wd1) {
 #pragma unroll
-        for (int i = 0; i < K; i++)
-            if ((uint32_t)i < rows) {
-                first_slot[i] = slot[i];
-                key[i] = s_keys[wbase + (uint32_t)i * 64u];
-            }
-        digit_pass(sh1, wd1);
+        for (int i = 0; i < K; i++) first_slot[i] = slot[i];
+        read_rows(g, key);
+        digit_pass<K, true>(g, key, slot, sh1, wd1);
     }
-    for (uint32_t q = tid; q < size; q += (uint32_t)T) bucket[q] = s_keys[q];   // the keys are done
+    store_linear(g, bucket);   // the keys are done
     if (wd1) {
         __syncthreads();   // the keys have left the LDS: it now holds the second pass's slots by position ...
 #pragma unroll
         for (int i = 0; i < K; i++)
-            if ((uint32_t)i < rows) s_keys[wbase + (uint32_t)i * 64u] = slot[i];
+            if ((uint32_t)i < g.rows) g.s_keys[g.wbase + (uint32_t)i * 64u] = slot[i];
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < K; i++)   // ... and the element that started at position wbase + 64 i ends in slot2[slot1]
-            if ((uint32_t)i < rows) slot[i] = s_keys[first_slot[i]];
+            if ((uint32_t)i < g.rows) slot[i] = g.s_keys[first_slot[i]];
     }
     for (uint32_t e = 0; e < p.num_payloads; e++) {
         uint32_t* const pay = (e == 0 ? p.vals : p.more[e - 1]) + lo;
         __syncthreads();   // the LDS is free again (slots read, or the previous array stored)
-#pragma unroll
-        for (int i = 0; i < K; i++) {
-            if ((uint32_t)i < rows) {
-                const uint32_t pos = wbase + (uint32_t)i * 64u;
-                key[i] = pos < size ? pay[pos] : 0u;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < K; i++)
-            if ((uint32_t)i < rows) s_keys[slot[i]] = key[i];
+        load_rows(g, pay, key);
+        write_slots(g, slot, key);
         __syncthreads();
-        for (uint32_t q = tid; q < size; q += (uint32_t)T) pay[q] = s_keys[q];
+        store_linear(g, pay);
     }
 }
 
@@ -364,29 +355,6 @@ __global__ void __launch_bounds__(kLocalThreads, (K <= 16 ? 6 : 2)) local_sort_m
         sort_bucket_multi<K>(p, p.list[item]);
         __syncthreads();
     }
-}
-
-template <int K>
-static hipError_t launch_local_multi(const LocalSortParams& p, hipStream_t stream)
-{
-    constexpr size_t lds_bytes = local_lds_words<K>() * sizeof(uint32_t);
-    if (p.list) {
-        if constexpr (K == 32) {   // the list is the large variant's (three register arrays of 32: one workgroup per CU, as the pairs')
-            auto kernel = local_sort_multi_list_kernel<K>;
-            static std::atomic<uint64_t> told{0};
-        const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds_bytes, told);
-            if (attr != hipSuccess) return attr;
-            hipLaunchKernelGGL(kernel, dim3(256), dim3(kLocalThreads), lds_bytes, stream, p);
-            return hipGetLastError();
-        }
-        return hipErrorInvalidValue;
-    }
-    auto kernel = local_sort_multi_kernel<K>;
-    static std::atomic<uint64_t> told{0};
-        const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds_bytes, told);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(kernel, dim3(p.num_buckets), dim3(kLocalThreads), lds_bytes, stream, p);
-    return hipGetLastError();
 }
 
 // registers: three workgroups per CU need 80 or fewer (keys K <= 20; pairs K <= 16), two 128; the 16384-pair variant keeps three
@@ -415,36 +383,30 @@ __global__ void __launch_bounds__(kLocalThreads, (local_waves_per_simd<K, PAIRS>
     }
 }
 
-template <int K, bool PAIRS, bool XOUT>
-static hipError_t launch_local_inst_x(const LocalSortParams& p, hipStream_t stream);
-template <int K, bool PAIRS>
-static hipError_t launch_local_inst(const LocalSortParams& p, hipStream_t stream)
+// One workgroup per bucket, or (the list is the large variant's: K = 32) a small grid that walks the planner's list: 512
+// workgroups, two per CU; 256 with several payload arrays (three register arrays of 32: one workgroup per CU, as the pairs').
+template <int K>
+static hipError_t launch_local_multi(const LocalSortParams& p, hipStream_t stream)
 {
-    return p.xout.on ? launch_local_inst_x<K, PAIRS, true>(p, stream) : launch_local_inst_x<K, PAIRS, false>(p, stream);
+    constexpr size_t lds_bytes = local_lds_words<K>() * sizeof(uint32_t);
+    const dim3 block(kLocalThreads);
+    if (!p.list) return launch_dynamic_lds<local_sort_multi_kernel<K>>(dim3(p.num_buckets), block, lds_bytes, stream, p);
+    if constexpr (K == 32) return launch_dynamic_lds<local_sort_multi_list_kernel<K>>(dim3(256), block, lds_bytes, stream, p);
+    return hipErrorInvalidValue;
 }
 template <int K, bool PAIRS, bool XOUT>
 static hipError_t launch_local_inst_x(const LocalSortParams& p, hipStream_t stream)
 {
     constexpr size_t lds_bytes = local_lds_words<K>() * sizeof(uint32_t);
-    if (p.list) {
-        if constexpr (K == 32) {   // the list is the large variant's
-            auto kernel = local_sort_list_kernel<K, PAIRS, XOUT>;
-            static std::atomic<uint64_t> told{0};
-        const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds_bytes, told);
-            if (attr != hipSuccess) return attr;
-            hipLaunchKernelGGL(kernel, dim3(512), dim3(kLocalThreads), lds_bytes, stream, p);   // two workgroups per CU walk the list
-            return hipGetLastError();
-        }
-        return hipErrorInvalidValue;
-    }
-    auto kernel = local_sort_kernel<K, PAIRS, XOUT>;
-    if (lds_bytes > 64 * 1024) {
-        static std::atomic<uint64_t> told{0};
-        const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds_bytes, told);
-        if (attr != hipSuccess) return attr;
-    }
-    hipLaunchKernelGGL(kernel, dim3(p.num_buckets), dim3(kLocalThreads), lds_bytes, stream, p);
-    return hipGetLastError();
+    const dim3 block(kLocalThreads);
+    if (!p.list) return launch_dynamic_lds<local_sort_kernel<K, PAIRS, XOUT>>(dim3(p.num_buckets), block, lds_bytes, stream, p);
+    if constexpr (K == 32) return launch_dynamic_lds<local_sort_list_kernel<K, PAIRS, XOUT>>(dim3(512), block, lds_bytes, stream, p);
+    return hipErrorInvalidValue;
+}
+template <int K, bool PAIRS>
+static hipError_t launch_local_inst(const LocalSortParams& p, hipStream_t stream)
+{
+    return p.xout.on ? launch_local_inst_x<K, PAIRS, true>(p, stream) : launch_local_inst_x<K, PAIRS, false>(p, stream);
 }
 
 // A sort of up to 16384 items is one workgroup's work: one launch instead of the eight of the chained form (whose kernels are
@@ -471,18 +433,9 @@ hipError_t launch_small_sort(uint32_t* keys, uint32_t* vals, uint32_t n, uint32_
         p.width[i] = 8u;
     }
     constexpr size_t lds_bytes = local_lds_words<32>() * sizeof(uint32_t);
-    if (vals) {
-        static std::atomic<uint64_t> told{0};
-        const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(small_sort_kernel<true>), lds_bytes, told);
-        if (attr != hipSuccess) return attr;
-        hipLaunchKernelGGL(small_sort_kernel<true>, dim3(1), dim3(kLocalThreads), lds_bytes, stream, p, clear0, clear1);
-    } else {
-        static std::atomic<uint64_t> told{0};
-        const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(small_sort_kernel<false>), lds_bytes, told);
-        if (attr != hipSuccess) return attr;
-        hipLaunchKernelGGL(small_sort_kernel<false>, dim3(1), dim3(kLocalThreads), lds_bytes, stream, p, clear0, clear1);
-    }
-    return hipGetLastError();
+    const dim3 block(kLocalThreads);
+    if (vals) return launch_dynamic_lds<small_sort_kernel<true>>(dim3(1), block, lds_bytes, stream, p, clear0, clear1);
+    return launch_dynamic_lds<small_sort_kernel<false>>(dim3(1), block, lds_bytes, stream, p, clear0, clear1);
 }
 
 hipError_t launch_local_sort(const LocalSortParams& p, hipStream_t stream)
@@ -513,69 +466,49 @@ hipError_t launch_local_sort(const LocalSortParams& p, hipStream_t stream)
 
 
 // ---- the segmented sort's workgroup tier (segmented.hip plans it) -------------------------------------------------------------
-// Segment s = keys [offsets[s], offsets[s + 1]), kWaveSegCap < size <= kLocalSortCap, listed by the planner.  sort_bucket's digit
-// pass (same rank, same scan, same reorder, 16384-key variant) over all four bytes of the key, plus what a segment needs that a
-// bucket of the hybrid form does not: the key transform on load as well as on store, and no pass for a byte that is the same in
-// every key of the segment (AND and OR of the keys agree on it: small key ranges, one value per segment).  A function of its own so
-// that sort_bucket's instantiations stay as they are.
+// Segment s = keys [offsets[s], offsets[s + 1]), kWaveSegCap < size <= kLocalSortCap, listed by the planner.  The digit pass above
+// (16384-key variant) over the four bytes of the key, plus what a segment needs that a bucket of the hybrid form does not: the
+// key transform on load as well as on store, and no pass for a byte that is the same in every key of the segment (AND and OR of
+// the keys agree on it: small key ranges, one value per segment).
 template <bool PAIRS>
 __device__ __forceinline__ void sort_segment(const SegSortParams& p, const uint32_t s)
 {
-    constexpr int T = kLocalThreads, W = kLocalWaves, HW = kLocalMaxBins / 2, K = 32;
-    constexpr int CAP = T * K;
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    lds_u32* const s_keys = (lds_u32*)smem;
-    volatile lds_u32* const s_cnt = (volatile lds_u32*)(s_keys + CAP);
-    volatile lds_u16* const s_cnt16 = (volatile lds_u16*)s_cnt;
-    lds_u32* const s_misc = (lds_u32*)(s_cnt + W * HW);
-
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (s >= p.num_segments) {   // never listed: say so, touch nothing
-        if (tid == 0 && p.fault) atomicOr(p.fault, 128u);
-        return;
-    }
+    constexpr int K = 32;
+    if (s >= p.num_segments) return raise_fault(p.fault, 128u);   // never listed: say so, touch nothing
     const uint32_t lo = p.offsets[s], hi = p.offsets[s + 1];
-    const uint32_t size = hi - lo;
-    if (hi < lo || hi > p.n || size > (uint32_t)CAP) {
-        if (tid == 0 && p.fault) atomicOr(p.fault, 128u);
-        return;
-    }
+    if (hi < lo || hi > p.n || hi - lo > (uint32_t)(kLocalThreads * K)) return raise_fault(p.fault, 128u);
+    const LocalGroup<K> g = local_group<K>(hi - lo);
     uint32_t* const seg = p.keys + lo;
     uint32_t* const seg_vals = PAIRS ? p.vals + lo : nullptr;
-    const uint32_t rows = (size + (uint32_t)T - 1u) / (uint32_t)T;
-    const uint32_t wbase = wave * rows * 64u + lane;
 
-    uint32_t key[K], rank[K], val[PAIRS ? K : 1];
+    uint32_t key[K], rank[K], val[K];   // val: PAIRS only
     uint32_t any = 0u, all = ~0u;
 #pragma unroll
     for (int i = 0; i < K; i++) {
         key[i] = 0xFFFFFFFFu;   // past the segment: the highest digit in every pass, stays last, never stored
-        if ((uint32_t)i < rows) {
-            const uint32_t pos = wbase + (uint32_t)i * 64u;
-            if (pos < size) {
+        if ((uint32_t)i < g.rows) {
+            const uint32_t pos = g.wbase + (uint32_t)i * 64u;
+            if (pos < g.size) {
                 uint32_t k = seg[pos];
                 if (p.xin.on) k = to_sortable(k, p.xin);
                 key[i] = k;
                 any |= k;
                 all &= k;
             }
-            if (PAIRS) val[i] = pos < size ? seg_vals[pos] : 0u;
+            if (PAIRS) val[i] = pos < g.size ? seg_vals[pos] : 0u;
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        any |= __shfl_xor(any, off, kWave);
-        all &= __shfl_xor(all, off, kWave);
-    }
-    if (lane == 0u) {
-        s_misc[32 + wave] = any;
-        s_misc[40 + wave] = all;
+    any = wave_or(any);
+    all = wave_and(all);
+    if (g.lane == 0u) {
+        g.s_misc[32 + g.wave] = any;
+        g.s_misc[40 + g.wave] = all;
     }
     __syncthreads();
 #pragma unroll
-    for (int w = 0; w < W; w++) {
-        any |= s_misc[32 + w];
-        all &= s_misc[40 + w];
+    for (int w = 0; w < kLocalWaves; w++) {
+        any |= g.s_misc[32 + w];
+        all &= g.s_misc[40 + w];
     }
     uint32_t todo = 0;   // bit b: byte b differs somewhere in the segment (uniform)
 #pragma unroll
@@ -584,73 +517,8 @@ __device__ __forceinline__ void sort_segment(const SegSortParams& p, const uint3
     while (todo) {
         const uint32_t shift = 8u * (uint32_t)__builtin_ctz(todo);
         todo &= todo - 1u;
-        const bool last = todo == 0u;
-        constexpr uint32_t bins = 256u, mask = bins - 1u;
-#pragma unroll
-        for (int j = 0; j < HW / kWave; j++) s_cnt[wave * HW + j * kWave + lane] = 0;
-#pragma unroll
-        for (int i = 0; i < K; i++) {
-            if ((uint32_t)i < rows) {
-                const uint32_t d = (key[i] >> shift) & mask;
-                const uint32_t sh = (d & 1u) * 16u;
-                const uint32_t old = __hip_atomic_fetch_add((lds_u32*)&s_cnt[wave * HW + (d >> 1)], 1u << sh, __ATOMIC_RELAXED,
-                                                            __HIP_MEMORY_SCOPE_WAVEFRONT);
-                rank[i] = (old >> sh) & 0xFFFFu;
-            }
-        }
-        __syncthreads();
-        uint32_t total = 0;
-        uint32_t wave_excl[W];
-        if (tid < bins) {
-#pragma unroll
-            for (int w = 0; w < W; w++) {
-                wave_excl[w] = total;
-                total += s_cnt16[w * kLocalMaxBins + tid];
-            }
-        }
-        const uint32_t incl = wave_inclusive_scan(tid < bins ? total : 0u, lane);
-        if (lane == 63u) s_misc[wave] = incl;
-        __syncthreads();
-        uint32_t carry = 0;
-#pragma unroll
-        for (int w = 0; w < W; w++) carry += (uint32_t)w < wave ? s_misc[w] : 0u;
-        const uint32_t local_off = incl + carry - total;
-        if (tid < bins) {
-#pragma unroll
-            for (int w = 0; w < W; w++) s_cnt16[w * kLocalMaxBins + tid] = (uint16_t)(local_off + wave_excl[w]);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < K; i++) {
-            if ((uint32_t)i < rows) {
-                const uint32_t q = s_cnt16[wave * kLocalMaxBins + ((key[i] >> shift) & mask)] + rank[i];
-                if (PAIRS) rank[i] = q;
-                s_keys[q] = key[i];
-            }
-        }
-        __syncthreads();
-        if (last) {
-            for (uint32_t q = tid; q < size; q += (uint32_t)T) seg[q] = p.xout.on ? from_sortable(s_keys[q], p.xout) : s_keys[q];
-        } else {
-#pragma unroll
-            for (int i = 0; i < K; i++)
-                if ((uint32_t)i < rows) key[i] = s_keys[wbase + (uint32_t)i * 64u];
-        }
-        if (PAIRS) {
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < K; i++)
-                if ((uint32_t)i < rows) s_keys[rank[i]] = val[i];
-            __syncthreads();
-            if (last) {
-                for (uint32_t q = tid; q < size; q += (uint32_t)T) seg_vals[q] = s_keys[q];
-            } else {
-#pragma unroll
-                for (int i = 0; i < K; i++)
-                    if ((uint32_t)i < rows) val[i] = s_keys[wbase + (uint32_t)i * 64u];
-            }
-        }
-        __syncthreads();   // the next pass zeroes counters and writes slots others may still read
+        digit_pass<K, PAIRS>(g, key, rank, shift, 8u);
+        take_out<K, PAIRS>(g, todo == 0u, key, rank, val, seg, p.xout.on ? &p.xout : nullptr, seg_vals);
     }
 }
 
@@ -668,18 +536,9 @@ hipError_t launch_segment_sort(const SegSortParams& p, uint32_t grid, hipStream_
 {
     constexpr size_t lds_bytes = local_lds_words<32>() * sizeof(uint32_t);
     if (!p.keys || !p.offsets || !p.list || !p.list_count || grid == 0) return hipErrorInvalidValue;
-    if (p.vals) {
-        static std::atomic<uint64_t> told{0};
-        const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(segment_sort_kernel<true>), lds_bytes, told);
-        if (attr != hipSuccess) return attr;
-        hipLaunchKernelGGL(segment_sort_kernel<true>, dim3(grid), dim3(kLocalThreads), lds_bytes, stream, p);
-    } else {
-        static std::atomic<uint64_t> told{0};
-        const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(segment_sort_kernel<false>), lds_bytes, told);
-        if (attr != hipSuccess) return attr;
-        hipLaunchKernelGGL(segment_sort_kernel<false>, dim3(grid), dim3(kLocalThreads), lds_bytes, stream, p);
-    }
-    return hipGetLastError();
+    const dim3 block(kLocalThreads);
+    if (p.vals) return launch_dynamic_lds<segment_sort_kernel<true>>(dim3(grid), block, lds_bytes, stream, p);
+    return launch_dynamic_lds<segment_sort_kernel<false>>(dim3(grid), block, lds_bytes, stream, p);
 }
 
 }  // namespace lsd

@@ -56,10 +56,33 @@ __device__ __forceinline__ uint32_t mbcnt_add(uint64_t m, uint32_t base)
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, base));
 }
 
+// (the form rank_scatter.hpp was tuned with: two 32-bit counts and the add; popc64 below is the plain 64-bit count)
 __device__ __forceinline__ uint32_t popc64_add(uint64_t m, uint32_t base)
 {
     return __builtin_popcount((uint32_t)m) + __builtin_popcount((uint32_t)(m >> 32)) + base;
 }
+
+__device__ __forceinline__ uint32_t popc64(uint64_t m) { return (uint32_t)__popcll(m); }
+
+// Orders this wave's LDS operations among its own lanes (a slice of LDS that only one wave touches needs no workgroup barrier).
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Reductions over the 64 lanes of a wave (xor butterfly): every lane ends with the result.  All 64 lanes must be active.
+template <class Op>
+__device__ __forceinline__ uint32_t wave_reduce(uint32_t v, Op op)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = op(v, (uint32_t)__shfl_xor(v, off, kWave));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_or(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return a | b; }); }
+__device__ __forceinline__ uint32_t wave_and(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return a & b; }); }
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return a + b; }); }
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return b > a ? b : a; }); }
 
 // Peers of this lane: the 64-bit mask of lanes whose R-bit digit equals ours, from R
 // wave-wide ballots.  All 64 lanes must be active.
@@ -100,6 +123,26 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lan
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2 and 3
     return v;
 #endif
+}
+
+// Exclusive scan of one value per thread over a workgroup of WAVES wavefronts: the wave's scan, its total into part[wave] (LDS,
+// WAVES words), a barrier, the totals of the waves before mine.  *total (may be null): the workgroup's sum.  The barrier that
+// keeps the next writer of `part` behind these reads is the caller's.
+template <int WAVES, class Part>
+__device__ __forceinline__ uint32_t group_exclusive_scan(uint32_t v, uint32_t lane, uint32_t wave, Part part, uint32_t* total = nullptr)
+{
+    const uint32_t incl = wave_inclusive_scan(v, lane);
+    if (lane == 63u) part[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; w++) {
+        const uint32_t t = part[w];
+        before += (uint32_t)w < wave ? t : 0u;
+        all += t;
+    }
+    if (total) *total = all;
+    return before + incl - v;
 }
 
 // Number of LDS replicas of a small histogram so that 64 lanes do not pile onto a handful

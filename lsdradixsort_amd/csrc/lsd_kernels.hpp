@@ -87,6 +87,19 @@ inline hipError_t allow_dynamic_lds(const void* kernel, size_t bytes, std::atomi
     if (e == hipSuccess) done.fetch_or(bit, std::memory_order_release);
     return e;
 }
+// Launch of a kernel with dynamic LDS: each kernel has its own set of devices already told.
+template <auto Kernel>
+inline std::atomic<uint64_t> dynamic_lds_told{0};
+template <auto Kernel, class... Args>
+hipError_t launch_dynamic_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const Args&... args)
+{
+    if (lds_bytes > 64 * 1024) {
+        const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(Kernel), lds_bytes, dynamic_lds_told<Kernel>);
+        if (attr != hipSuccess) return attr;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, args...);
+    return hipGetLastError();
+}
 
 // Set (per host thread) around a rank-and-scatter launch by lsdsort_u32_device_timed: events that
 // receive the kernel's own begin and end timestamps (hipExtLaunchKernelGGL).

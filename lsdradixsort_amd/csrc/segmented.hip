@@ -176,12 +176,6 @@ __global__ void __launch_bounds__(256) seg_tiles_kernel(const PlanParams p)
     }
 }
 
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // ---- wave tier ------------------------------------------------------------------------------------------------------------
 // One wavefront per segment of at most kWaveSegCap keys: lane l's register i holds position 64 i + l.  Per digit pass: zero the
 // wave's 256 counters, rank = returning LDS add (lane order within a row, rows in order: stable), exclusive scan of the counters
@@ -224,11 +218,8 @@ __global__ void __launch_bounds__(kWaveTierWaves * kWave) seg_wave_kernel(const 
                 if (PAIRS) val[i] = seg_vals[pos];
             }
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            any |= __shfl_xor(any, off, kWave);
-            all &= __shfl_xor(all, off, kWave);
-        }
+        any = wave_or(any);
+        all = wave_and(all);
         uint32_t todo = 0;   // bit b: digit b differs somewhere in the segment
 #pragma unroll
         for (int b = 0; b < 4; b++) todo |= (((any ^ all) >> (8 * b)) & 0xFFu) ? 1u << b : 0u;
@@ -377,8 +368,7 @@ __global__ void __launch_bounds__(256) seg_scan_reduce_kernel(const LargeParams 
     if (b0 >= total) return;
     uint32_t sum = 0;
     for (uint32_t q = b0 + threadIdx.x; q < b0 + kScanBlock && q < total; q += 256u) sum += p.hist[q];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, kWave);
+    sum = wave_sum(sum);
     if ((threadIdx.x & 63u) == 0u) s_part[threadIdx.x >> 6] = sum;
     __syncthreads();
     if (threadIdx.x == 0) p.sums[blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
@@ -394,15 +384,9 @@ __global__ void __launch_bounds__(1024) seg_scan_sums_kernel(const LargeParams p
     for (uint32_t c0 = 0; c0 < blocks; c0 += 1024u) {
         const uint32_t q = c0 + tid;
         const uint32_t v = q < blocks ? p.sums[q] : 0u;
-        const uint32_t incl = wave_inclusive_scan(v, lane);
-        if (lane == 63u) s_part[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-        for (uint32_t w = 0; w < 16u; w++) {
-            before += w < wave ? s_part[w] : 0u;
-            all += s_part[w];
-        }
-        if (q < blocks) p.sums[q] = carry + before + incl - v;
+        uint32_t all = 0;
+        const uint32_t before = group_exclusive_scan<16>(v, lane, wave, s_part, &all);
+        if (q < blocks) p.sums[q] = carry + before;
         carry += all;
         __syncthreads();
     }
@@ -422,11 +406,7 @@ __global__ void __launch_bounds__(256) seg_scan_down_kernel(const LargeParams p)
         v[e] = first + e < total ? p.hist[first + e] : 0u;
         sum += v[e];
     }
-    const uint32_t incl = wave_inclusive_scan(sum, lane);
-    if (lane == 63u) s_part[wave] = incl;
-    __syncthreads();
-    uint32_t run = p.sums[blockIdx.x] + incl - sum;
-    for (uint32_t w = 0; w < 4u; w++) run += w < wave ? s_part[w] : 0u;
+    uint32_t run = p.sums[blockIdx.x] + group_exclusive_scan<4>(sum, lane, wave, s_part);
 #pragma unroll
     for (uint32_t e = 0; e < E; e++) {
         if (first + e < total) p.hist[first + e] = run;
@@ -497,11 +477,7 @@ __global__ void __launch_bounds__(kSegThreads) seg_scatter_kernel(const LargePar
                 wave_excl[w] = total;
                 total += s_cnt[w * 256 + d];
             }
-            const uint32_t incl = wave_inclusive_scan(total, lane);
-            if (lane == 63u) s_part[wave] = incl;
-            __syncthreads();
-            uint32_t excl = incl - total;
-            for (uint32_t w = 0; w < wave; w++) excl += s_part[w];
+            const uint32_t excl = group_exclusive_scan<kSegWaves>(total, lane, wave, s_part);
 #pragma unroll
             for (int w = 0; w < kSegWaves; w++) s_cnt[w * 256 + d] = excl + wave_excl[w];
             uint32_t gbase;

@@ -52,18 +52,12 @@ constexpr uint32_t kMinChunk = 16384, kMaxChunks = 2048;
 
 size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 template <int WAVES>
 __device__ __forceinline__ void group_sync()
 {
     if (WAVES == 1) wave_sync();
     else __syncthreads();
 }
-__device__ __forceinline__ uint32_t popc64(uint64_t m) { return (uint32_t)__popcll(m); }
 
 struct Outputs {
     uint32_t* keys;       // [rows][k], raw keys
@@ -324,12 +318,8 @@ __global__ void __launch_bounds__(256) topk_scan_kernel(const LongParams p)
         h[tid * E + e] = 0u;
         sum += c[e];
     }
-    const uint32_t incl = wave_inclusive_scan(sum, lane);
-    if (lane == 63u) s_part[wave] = incl;
     if (tid == 0u) s_found[0] = 0xFFFFFFFFu;
-    __syncthreads();
-    uint32_t run = incl - sum;
-    for (uint32_t w = 0; w < 4u; w++) run += w < wave ? s_part[w] : 0u;
+    uint32_t run = group_exclusive_scan<4>(sum, lane, wave, s_part);
     const uint32_t need = st.z;
 #pragma unroll
     for (uint32_t e = 0; e < E; e++) {
@@ -378,11 +368,8 @@ __global__ void __launch_bounds__(kLongThreads) topk_count_kernel(const LongPara
             }
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        nb += __shfl_xor(nb, off, kWave);
-        ne += __shfl_xor(ne, off, kWave);
-    }
+    nb = wave_sum(nb);
+    ne = wave_sum(ne);
     if (lane == 0u) {
         s_part[2u * wave] = nb;
         s_part[2u * wave + 1u] = ne;
@@ -415,11 +402,8 @@ __global__ void __launch_bounds__(kLongThreads) topk_write_kernel(const LongPara
         base_b += v.x;
         base_e += v.y;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        base_b += __shfl_xor(base_b, off, kWave);
-        base_e += __shfl_xor(base_e, off, kWave);
-    }
+    base_b = wave_sum(base_b);
+    base_e = wave_sum(base_e);
     if (lane == 0u) {
         s_part[2u * wave] = base_b;
         s_part[2u * wave + 1u] = base_e;

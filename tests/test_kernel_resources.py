@@ -1,32 +1,32 @@
-"""CPU suite: the hybrid form's kernels compile for gfx950 WITHOUT scratch.
+"""CPU suite: the kernels of the local stage, the hybrid planner, the segmented sort and top-k compile for gfx950 WITHOUT
+scratch, and with the occupancy and the static LDS they were measured with.
 
 A register spill in these kernels does not break a parity test -- it multiplies the kernel's memory traffic (round 3: a loop
 around the local stage's body spilled 49 registers and took the stage from 0.55 to 2.07 ms; the parity tests stayed green).
-hipcc's own resource remarks are the check: ScratchSize 0 and no VGPR spill for every kernel of local_sort.hip and
-hybrid.hip (seconds to compile; the rank-and-scatter translation units take minutes and are read by hand)."""
+hipcc's own resource remarks are the check: ScratchSize 0 and no VGPR spill for every kernel of the four files (seconds to
+compile; the rank-and-scatter translation units take minutes and are read by hand), and against
+tests/golden/kernel_resources.json (file -> mangled name -> occupancy, static LDS; the device-side counterpart of
+workspace_sizes.json): the same set of kernels -- bench.py and tools/profile_bench.sh classify by name --, no fewer waves per SIMD,
+the same static LDS."""
+import json
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "lsdradixsort_amd", "csrc")
+from _kernel_resources import hipcc, kernel_resources
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kernel_resources.json")
 
 
-@pytest.mark.parametrize("source", ["local_sort.hip", "hybrid.hip"])
-def test_no_scratch(source, tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
+@pytest.mark.parametrize("source", ["local_sort.hip", "hybrid.hip", "segmented.hip", "topk.hip"])
+def test_no_scratch(source):
+    if hipcc() is None:
         pytest.skip("no hipcc on this machine")
-    p = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, source), "-o", str(tmp_path / "x.o")],
-                       capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", p.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", p.stderr)]
-    spills = [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", p.stderr)]
-    assert names and len(names) == len(scratch) == len(spills)
-    for name, sc, sp in zip(names, scratch, spills):
-        assert sc == 0 and sp == 0, f"{name}: scratch {sc} B/lane, {sp} VGPRs spilled"
+    got = kernel_resources(source)
+    for name, r in got.items():
+        assert r["scratch"] == 0 and r["vgpr_spill"] == 0, f"{name}: scratch {r['scratch']} B/lane, {r['vgpr_spill']} VGPRs spilled"
+    want = json.load(open(GOLDEN))[source]
+    assert sorted(got) == sorted(want), f"kernels gone: {sorted(set(want) - set(got))}, new: {sorted(set(got) - set(want))}"
+    for name, w in want.items():
+        assert got[name]["occupancy"] >= w["occupancy"], f"{name}: {got[name]['occupancy']} waves/SIMD, recorded {w['occupancy']}"
+        assert got[name]["lds_bytes"] == w["lds_bytes"], f"{name}: {got[name]['lds_bytes']} B of static LDS, recorded {w['lds_bytes']}"

@@ -2,13 +2,10 @@
 resources (ScratchSize 0, no VGPR spill) from hipcc's own remarks."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "lsdradixsort_amd", "csrc")
 NEW = ("lsdsort_segmented_workspace_bytes", "lsdsort_segmented_device")
 
 
@@ -82,19 +79,12 @@ def test_workspace_bytes_monotone_and_bounded():
 
 
 @pytest.mark.parametrize("source", ["segmented.hip", "local_sort.hip"])
-def test_segmented_kernels_no_scratch(source, tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
+def test_segmented_kernels_no_scratch(source):
+    from _kernel_resources import hipcc, kernel_resources
+
+    if hipcc() is None:
         pytest.skip("no hipcc on this machine")
-    p = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, source), "-o", str(tmp_path / "x.o")],
-                       capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", p.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", p.stderr)]
-    spills = [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", p.stderr)]
-    assert names and len(names) == len(scratch) == len(spills)
-    seg = [i for i, name in enumerate(names) if "seg" in name]   # seg_*_kernel, segment_sort_kernel
+    seg = {name: r for name, r in kernel_resources(source).items() if "seg" in name}   # seg_*_kernel, segment_sort_kernel
     assert seg, "no segmented-sort kernel in " + source
-    for i in seg:
-        assert scratch[i] == 0 and spills[i] == 0, f"{names[i]}: scratch {scratch[i]} B/lane, {spills[i]} VGPRs spilled"
+    for name, r in seg.items():
+        assert r["scratch"] == 0 and r["vgpr_spill"] == 0, f"{name}: scratch {r['scratch']} B/lane, {r['vgpr_spill']} VGPRs spilled"
