@@ -29,7 +29,7 @@ constexpr int kHybridVpt = 4;              // 16-byte vectors per thread per gro
 
 // Upfront read of the hybrid form.  fieldA[(digit of bits 16-23) * 8 + position region] and bucket[key >> bucket_shift] (global, zero on
 // entry) receive the counts.  Grid-stride over chunks of 4096 keys, two register buffers, non-temporal loads (as stage 1 of the
-// ordinary form, aux_kernels.hip).  Heavy values are handled as there: keys equal to a sticky candidate value (zeros, a default
+// ordinary form, histograms.hip).  Heavy values are handled as there: keys equal to a sticky candidate value (zeros, a default
 // value) are counted by ballot for both fields at once, and per field the holders of the first lane's counter are counted by
 // ballot when sixteen lanes or more share it (sorted or constant input, dead digits, small ranges).
 // The sample: 65536 keys at a regular stride, 1024 per workgroup over 64 workgroups, each workgroup counting ITS samples by bucket
@@ -120,7 +120,7 @@ __global__ void __launch_bounds__(kHybridHistThreads) hybrid_histograms_kernel(c
     uint32_t key1 = 0, key2 = 0;   // sticky heavy-key candidates (uniform)
     bool have1 = false, have2 = false;
     auto count_group = [&](uint32_t c, uint4 (&v)[VPT]) {
-        // heavy keys: see joint_histograms_kernel (aux_kernels.hip)
+        // heavy keys: see joint_histograms_kernel (histograms.hip)
         {
             const uint32_t k0 = v[0].x;
             const uint32_t n1 = (uint32_t)__builtin_popcountll(__ballot(k0 == key1));

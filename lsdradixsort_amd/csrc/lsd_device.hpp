@@ -102,18 +102,9 @@ __device__ __forceinline__ uint64_t match_ballot(uint32_t d)
 // Inclusive scan across the 64 lanes of a wave, on the DPP network (no LDS round trips): row_shr 1/2/4/8 scans the four
 // rows of 16 lanes, row_bcast15 carries row 0's total into row 1 and row 2's into row 3, row_bcast31 carries the first
 // half's total into the second (the sequence LLVM's atomic optimiser emits for wave64 on GFX9-family targets).
-// -DLSD_SCAN_SHFL builds the ds_bpermute (__shfl_up) form this replaced (A/B in DESIGN.md section 4.8).
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lane)
+// It replaced a ds_bpermute (__shfl_up) form (A/B in DESIGN.md section 4.8).
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v)
 {
-#ifdef LSD_SCAN_SHFL
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const uint32_t up = __shfl_up(v, off, kWave);
-        if (lane >= (uint32_t)off) v += up;
-    }
-    return v;
-#else
-    (void)lane;
     // update_dpp(old, src, dpp_ctrl, row_mask, bank_mask, bound_ctrl): lanes without a source keep `old` = 0
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
@@ -122,7 +113,6 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lan
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1 and 3
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2 and 3
     return v;
-#endif
 }
 
 // Exclusive scan of one value per thread over a workgroup of WAVES wavefronts: the wave's scan, its total into part[wave] (LDS,
@@ -131,7 +121,7 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lan
 template <int WAVES, class Part>
 __device__ __forceinline__ uint32_t group_exclusive_scan(uint32_t v, uint32_t lane, uint32_t wave, Part part, uint32_t* total = nullptr)
 {
-    const uint32_t incl = wave_inclusive_scan(v, lane);
+    const uint32_t incl = wave_inclusive_scan(v);
     if (lane == 63u) part[wave] = incl;
     __syncthreads();
     uint32_t before = 0, all = 0;

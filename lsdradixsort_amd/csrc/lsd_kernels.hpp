@@ -40,15 +40,13 @@ bool single_round_shape(int radix_bits, int id);
 // LDS counters per workgroup in the upfront histogram, which is as fast as with 8: it is bound by the
 // number of LDS atomics, not by the table) sort uniform keys 1 % faster -- whole-sort A/B at 2^28 keys:
 // 8 regions 2.181 ms, 16 regions 2.160 ms, 32 regions 2.205 ms -- but lose 10 % on sorted, reversed and
-// few-valued inputs (104 -> 93 Gkeys/s sorted, 95 -> 84 with 16 values per digit), so 8 stays
-// (-DLSD_R8_REGION_BITS=4 builds the other).  4-bit digits: 16 regions (the whole previous digit).
+// few-valued inputs (104 -> 93 Gkeys/s sorted, 95 -> 84 with 16 values per digit), so 8 stays.
+// 4-bit digits: 16 regions (the whole previous digit).
 // Narrower digits and the multi-GPU partition: one region, i.e. one chain.
-constexpr int kMaxRegions = 32;
+constexpr int kMaxRegions = 32;   // the region tables' layout (workspace size): more than any radix uses today
 constexpr int kXcds = 8;
-#ifndef LSD_R8_REGION_BITS
-#define LSD_R8_REGION_BITS 3
-#endif
-inline constexpr int region_bits_for_radix(int radix_bits) { return radix_bits == 8 ? LSD_R8_REGION_BITS : (radix_bits == 4 ? 4 : 0); }
+constexpr int kR8RegionBits = 3;
+inline constexpr int region_bits_for_radix(int radix_bits) { return radix_bits == 8 ? kR8RegionBits : (radix_bits == 4 ? 4 : 0); }
 inline constexpr int regions_for_radix(int radix_bits) { return 1 << region_bits_for_radix(radix_bits); }
 // Per-pass region table, uint32 words: start[32] | len[32] | tiles[32] | tile_off[32] | base[regions][2^R]
 constexpr int kRegionHeaderWords = 4 * kMaxRegions;
@@ -197,7 +195,7 @@ hipError_t launch_joint_histograms(int radix_bits, const uint32_t* keys, uint32_
                                    uint32_t* joint, hipStream_t stream, const KeyTransform& xform = KeyTransform{},
                                    uint32_t first_key = 0, const uint32_t* skip = nullptr);   // *skip != 0: the launch does nothing
 
-// Stage 2, onesweep: region tables of every pass from the joint counts (`regions` = 16 or 32) or
+// Stage 2, onesweep: region tables of every pass from the joint counts (`regions` = regions_for_radix: 8 or 16) or
 // from plain digit histograms (`regions` = 1; passes may then be 1 for the multi-GPU partition).
 // counts: [passes][2^R][regions]; tables: [passes][region_table_words(R)].
 // `fault` (may be null): the workspace fault word, raised (bit 2) if a pass's counts do not sum to n.

@@ -77,7 +77,7 @@ bool valid_radix(int r) { return r == 1 || r == 2 || r == 4 || r == 8; }
 std::atomic<int> g_shape_override[9];   // per radix_bits: 0 = default, k + 1 = compiled shape k forced
 
 // Tile shape of a sort: the one lsdsort_set_tile_config pinned, else the compiled default for the
-// job.  The chained form picks by size (tools/size_sweep.py, shape ids of aux_kernels.hip):
+// job.  The chained form picks by size (tools/size_sweep.py, shape ids of rank_scatter.hip):
 //   n >= 2^23 : the one-workgroup-per-CU 1024x32 tile (32768 keys: half the status rows per key, 32
 //               instead of 64 tiles in flight per chain; fastest on uniform keys and the most even
 //               across key distributions);

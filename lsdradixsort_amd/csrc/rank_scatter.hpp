@@ -101,15 +101,9 @@ struct Lookback {
     // 8-bit digits: a step costs a round trip whatever its width, but every row is 1 KiB of status reads
     // Small sorts (the 16-keys-per-thread shapes, n < 2^21): every tile of a chain starts at the same moment, nobody has a
     // prefix to offer early, and a tile walks its whole chain of aggregates -- there the width of a step is what counts
-    // (LSD_LB_SMALL, tools/size_sweep.py).
-#ifndef LSD_LB_SMALL
-#define LSD_LB_SMALL 2
-#endif
-#ifdef LSD_LB   // experiment builds (make variant / stats DEFS=-DLSD_LB=n)
-    static constexpr int LB = H >= 64 ? (K <= 16 && T <= 512 ? LSD_LB_SMALL : LSD_LB) : 8;
-#else
-    static constexpr int LB = H >= 64 ? (K <= 16 && T <= 512 ? LSD_LB_SMALL : 2) : 8;
-#endif
+    // (tools/size_sweep.py); 2 won there as well.
+    static constexpr int kRows = 2, kRowsSmall = 2;
+    static constexpr int LB = H >= 64 ? (K <= 16 && T <= 512 ? kRowsSmall : kRows) : 8;
     static constexpr int SLOTS = 1;   // measured: helper slots (2 or 4) buy nothing here, the extra barrier costs a little
     static constexpr int LDS_WORDS = (SLOTS - 1) * LB * H;
 };
@@ -401,15 +395,12 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
     if (full) {
 #pragma unroll
         for (int i = 0; i < K; i++) key[i] = keys_in[i * kWave];
-#ifndef LSD_NO_RANK_HALVES   // (-DLSD_NO_RANK_HALVES builds the form that waits for every load first: +1.3 % kernel time)
         // Full tile, returning-LDS-add rank, no key transform: rank the first half of the rows as soon as THEIR loads are
         // in (the loads retire in issue order) and the second half behind a second wait, in the basic block of the loads --
-        // behind the join with the tail-tile path the compiler can only wait for everything (vmcnt(0)).
+        // behind the join with the tail-tile path the compiler can only wait for everything (vmcnt(0)).  (Waiting for
+        // every load first: +1.3 % kernel time.)
         if constexpr (RANK == kRankLdsAdd && K >= 16 && !XF) {
-#ifndef LSD_RANK_BATCHES
-#define LSD_RANK_BATCHES 2
-#endif
-            constexpr int NB = LSD_RANK_BATCHES, PER = K / NB;
+            constexpr int NB = 2, PER = K / NB;   // two batches: the second one's wait is for every load
             static_assert(K % NB == 0, "batches divide the rows");
             asm volatile("s_waitcnt vmcnt(%0)" : : "n"(K - PER) : "memory");
             if (!row_is_heavy(digit_of(key[0]))) {   // heavy digits take the path below (phase 2)
@@ -418,9 +409,7 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
                     if (b > 0) {
                         // batch b's keys become usable only behind its own wait: without the pins their digit extraction is
                         // hoisted above the earlier batches' atomics, and the wait for them with it
-                        if (b == 1) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(K - 2 * PER < 0 ? 0 : K - 2 * PER) : "memory");
-                        else if (b == 2) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(K - 3 * PER < 0 ? 0 : K - 3 * PER) : "memory");
-                        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
                         for (int i = b * PER; i < (b + 1) * PER; i++) asm volatile("" : "+v"(key[i]));
                     }
@@ -432,7 +421,6 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
                 ranked = true;
             }
         }
-#endif
     } else {
 #pragma unroll
         for (int i = 0; i < K; i++) {
@@ -583,7 +571,7 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
         store_status(p.status + (size_t)tile * H + tid, (pub_total << 2) | code);
     }
 
-    uint32_t incl = wave_inclusive_scan(tid < (uint32_t)H ? total : 0u, lane);
+    uint32_t incl = wave_inclusive_scan(tid < (uint32_t)H ? total : 0u);
     if (H > kWave) {
         if (lane == 63u) s_misc[1 + wave] = incl;
         lds_barrier();
@@ -667,25 +655,10 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
             else if ((pos_at(i) / (uint32_t)CAP) == (uint32_t)round) s_keys[pos_at(i) % (uint32_t)CAP] = key[i];
         }
         if (PAIRS && ROUNDS == 1) load_vals();   // the key registers are free now
-        // One workgroup per CU (the 32768-key tile), keys only: nothing else runs on the CU while this
-        // tile waits for its predecessors, so fetch the tile-ordered keys back from LDS BEFORE the
-        // look-back is consumed and leave only destination lookups and stores behind it (+0.7 %; with
-        // two workgroups per CU the extra barrier costs more than it hides: -1.5 %).
-        // Round 1 kept this on for the 32768-key tile (+0.7 % then).  Since the read-back issues its destination-base reads in
-        // batches (round 2) it LOSES 0.9 % (kernel 1.9 %): the slots' LDS reads now overlap the stores anyway, and the 32
-        // registers it holds across the look-back are better spent there.  -DLSD_PREREAD builds it.
-#ifdef LSD_PREREAD
-        constexpr bool PREREAD = !PAIRS && ROUNDS == 1 && TILE >= 32768;
-#else
-        constexpr bool PREREAD = false;
-#endif
-        uint32_t back[PREREAD ? SLOTS : 1];
-        if (PREREAD) {
-            lds_barrier();   // the whole tile is in LDS
-#pragma unroll
-            for (int s2 = 0; s2 < SLOTS; s2++) back[s2] = s_keys[s2 * T + tid];
-        }
-
+        // (Fetching the tile-ordered keys back from LDS HERE, before the look-back is consumed, was tried for the one-workgroup-
+        // per-CU 32768-key tile, keys only: +0.7 % in round 1, but since the read-back issues its destination-base reads in
+        // batches it LOSES 0.9 % (kernel 1.9 %) -- the slots' LDS reads overlap the stores anyway, and the 32 registers it
+        // holds across the look-back are better spent there; with two workgroups per CU the extra barrier cost 1.5 %.)
         if (round == 0) {
             LSD_STAMP(4);   // first round's LDS writes
             // ---- 4. tile base per digit ("global offsets", .cu:885-894) ----------------------------
@@ -829,18 +802,6 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
             };
             if (full) key_slots(std::true_type{});
             else key_slots(std::false_type{});
-        } else if (PREREAD) {
-            auto key_slots = [&](auto all_valid) {
-#pragma unroll
-                for (int s2 = 0; s2 < SLOTS; s2++) {
-                    const uint32_t q = s2 * T + tid;
-                    const uint32_t k = back[PREREAD ? s2 : 0];
-                    const uint32_t d = digit_of(k);
-                    if (decltype(all_valid)::value || q < valid) out_keys[s_gdelta[d] + q] = leaving(k);
-                }
-            };
-            if (full) key_slots(std::true_type{});
-            else key_slots(std::false_type{});
         } else {
             // keys only: sixteen slots at a time, which bounds the registers of the read-back
             // slots per batch.  One 16-wave workgroup per CU (1024 threads): 2 / 4 / 8 / 16 / 32 slots measure 2.006 / 2.011-2.016 /
@@ -848,12 +809,8 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
             // stores of the one before; a single slot is two dependent LDS round trips with every wave of the CU in the same
             // phase).  With two 8-wave workgroups per CU (512 threads) the OTHER workgroup is what overlaps, and one slot at
             // a time is fastest (table-driven pass, 512 x 32 tile: 1 / 2 / 4 / 16 slots 0.430 / 0.437 / 0.456 / 0.467 ms).
-#ifdef LSD_READBACK_STEP
-            constexpr int STEP_WANTED = LSD_READBACK_STEP;
-#else
-            constexpr int STEP_WANTED = T >= 1024 ? 4 : 1;
-#endif
-            constexpr int STEP = SLOTS < STEP_WANTED ? SLOTS : STEP_WANTED;
+            constexpr int kReadbackStep = T >= 1024 ? 4 : 1;
+            constexpr int STEP = SLOTS < kReadbackStep ? SLOTS : kReadbackStep;
             auto key_slots = [&](auto all_valid) {
 #pragma unroll 1
                 for (int s0 = 0; s0 < SLOTS; s0 += STEP) {
@@ -915,10 +872,9 @@ template <int R, int T, int K, int CAP, int RANK, bool PAIRS, bool CHAINED, bool
 hipError_t launch_rank_scatter_inst(const PassParams& p, hipStream_t stream)
 {
     constexpr size_t lds_bytes = (size_t)rank_scatter_lds_words<R, T, K, CAP, RANK>() * sizeof(uint32_t);
-    auto kernel = rank_scatter_kernel<R, T, K, CAP, RANK, PAIRS, CHAINED, XF>;
+    constexpr auto kernel = rank_scatter_kernel<R, T, K, CAP, RANK, PAIRS, CHAINED, XF>;
     if (lds_bytes > 64 * 1024) {
-        static std::atomic<uint64_t> told{0};
-        const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds_bytes, told);
+        const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds_bytes, dynamic_lds_told<kernel>);
         if (attr != hipSuccess) return attr;
     }
 #ifdef LSD_PHASE_STATS

@@ -1,5 +1,5 @@
 // rank_scatter_r4.hip -- 4-bit-digit instantiations of the rank-and-scatter kernel
-// (BASELINE.json configs[1]).  Shape ids index kShapesR4 in aux_kernels.hip.
+// (BASELINE.json configs[1]).  Shape ids index kShapesR4 in rank_scatter.hip.
 #include "rank_scatter.hpp"
 
 namespace lsd {

@@ -1,5 +1,5 @@
 // rank_scatter_r8.hip -- 8-bit-digit instantiations of the rank-and-scatter kernel
-// (BASELINE.json configs[2] and configs[4]).  Shape ids index kShapesR8 in aux_kernels.hip.
+// (BASELINE.json configs[2] and configs[4]).  Shape ids index kShapesR8 in rank_scatter.hip.
 #include "rank_scatter.hpp"
 
 namespace lsd {

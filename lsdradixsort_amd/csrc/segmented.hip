@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(kWaveTierWaves * kWave) seg_wave_kernel(const 
                 c[j] = s_cnt[lane * 4 + j];
                 sum += c[j];
             }
-            uint32_t base = wave_inclusive_scan(sum, lane) - sum;
+            uint32_t base = wave_inclusive_scan(sum) - sum;
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 s_cnt[lane * 4 + j] = base;

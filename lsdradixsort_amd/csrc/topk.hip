@@ -186,7 +186,7 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) topk_short_kernel(con
                     c[j] = s_cnt[lane * 4u + j];
                     sum += c[j];
                 }
-                uint32_t run = wave_inclusive_scan(sum, lane) - sum;
+                uint32_t run = wave_inclusive_scan(sum) - sum;
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     if (run < need && need - run <= c[j]) {   // at most one bin of the row
