@@ -134,7 +134,11 @@ LSDSORT_API int lsdsort_u32_device_ex(uint32_t* d_keys, uint32_t* d_vals, void* 
  * traffic as lsdsort_u32_device.  float32 sorts in IEEE total order (-NaN < -inf < ... < -0 < +0 < ... <
  * +inf < +NaN).  Descending = ascending on the complemented key; with payloads it is stable (equal keys
  * keep their input order).  d_vals may be NULL.  Chained algorithm, radix_bits 4 or 8. */
-typedef enum lsdsort_key_type { LSDSORT_KEY_U32 = 0, LSDSORT_KEY_I32 = 1, LSDSORT_KEY_F32 = 2 } lsdsort_key_type;
+typedef enum lsdsort_key_type {
+    LSDSORT_KEY_U32 = 0, LSDSORT_KEY_I32 = 1, LSDSORT_KEY_F32 = 2,
+    /* 64-bit keys: lsdsort_keys64_device only; every 32-bit entry answers them with LSDSORT_ERR_INVALID_ARG */
+    LSDSORT_KEY_U64 = 3, LSDSORT_KEY_I64 = 4, LSDSORT_KEY_F64 = 5
+} lsdsort_key_type;
 LSDSORT_API int lsdsort_keys_device(void* d_keys, uint32_t* d_vals, void* d_workspace, size_t workspace_bytes,
                                     size_t n, int radix_bits, int key_type, int descending, void* hip_stream);
 
@@ -146,6 +150,8 @@ LSDSORT_API int lsdsort_keys_device(void* d_keys, uint32_t* d_vals, void* d_work
  *   lsdsort_records_device : keys of key_bits (32 | 64) with payloads of val_bits (32 | 64; 32/32 is
  *                            lsdsort_pairs_u32_device), stable by key: every word that is not the key word being sorted on
  *                            rides through the passes as a payload array of its own (lsdsort_multi_u32_device); no gather.
+ *                            A NULL d_vals is LSDSORT_ERR_INVALID_ARG and is reported BEFORE a bad workspace (the order of
+ *                            lsdsort_keys64_device below and of the segmented and top-k entries; it used to come after).
  * lsdsort_wide_workspace_bytes(n, radix_bits, key_bits, val_bits) sizes the workspace (val_bits 0 = keys only);
  * lsdsort_wide_check_device reads the fault word of the sorts inside it (like lsdsort_check_device). */
 LSDSORT_API size_t lsdsort_wide_workspace_bytes(size_t n, int radix_bits, int key_bits, int val_bits);
@@ -155,6 +161,24 @@ LSDSORT_API int lsdsort_records_device(void* d_keys, void* d_vals, int key_bits,
                                        size_t workspace_bytes, size_t n, int radix_bits, void* hip_stream);
 LSDSORT_API int lsdsort_wide_check_device(void* d_workspace, size_t n, int radix_bits, int key_bits, int val_bits,
                                           void* hip_stream);
+/* 64-bit keys of another type or order, alone (val_bits 0, d_vals NULL) or with 32- or 64-bit payloads: key_type LSDSORT_KEY_U64,
+ * _I64 or _F64 (a 32-bit key type is LSDSORT_ERR_INVALID_ARG), descending != 0 for the largest key first.  The keys are mapped to
+ * the uint64 whose unsigned order is the requested one where they are split into words, and mapped back where the sorted words
+ * are merged into d_keys -- the two kernels that touch every key once in any case: same passes, same traffic as
+ * lsdsort_u64_device, and the sorts in between are plain uint32 sorts (pass skipping and the hybrid form included).  uint64: t = k;
+ * int64: t = k ^ 2^63; float64: t = ~k for a negative key (ALL 64 bits), k ^ 2^63 otherwise -- IEEE total order, -NaN < -inf < ...
+ * < -0 < +0 < ... < +inf < +NaN; descending: t = ~t afterwards, i.e. ascending on the complemented key, so it is stable as
+ * well: equal keys keep their input order (what torch.sort(stable=True, descending=True) does).  Payloads are never mapped.
+ * Workspace: lsdsort_wide_workspace_bytes(n, radix_bits, 64, val_bits); fault word: lsdsort_wide_check_device(ws, n, radix_bits,
+ * 64, val_bits, stream).  d_keys 8-byte aligned (16-byte accesses are used where it is 16-byte aligned).  Stream-ordered, nothing
+ * allocated, capturable in a graph (lsdsort_prepare_device first).  Checks, in order: key_type and val_bits (INVALID_ARG), n above
+ * LSDSORT_MAX_KEYS (TOO_LARGE), radix_bits (INVALID_ARG), n == 0 (OK, nothing launched), a NULL d_keys, or a NULL d_vals with
+ * val_bits != 0 (INVALID_ARG), the workspace (WORKSPACE), the device (NO_DEVICE).  lsdsort_u64_device and lsdsort_records_device
+ * with key_bits 64 are this entry with (LSDSORT_KEY_U64, ascending).  NOT served: typed 32-bit keys with 64-bit payloads --
+ * lsdsort_records_device(32, 64) stays uint32 ascending (the multi-payload pass kernel has no typed instantiation). */
+LSDSORT_API int lsdsort_keys64_device(void* d_keys, void* d_vals, int val_bits /* 0 | 32 | 64 */, void* d_workspace,
+                                      size_t workspace_bytes, size_t n, int radix_bits, int key_type, int descending,
+                                      void* hip_stream);
 
 /* Segmented sort (no reference counterpart; the counterpart of DeviceSegmentedRadixSort and of torch.sort(x, dim=-1) on rows).
  * Segment s = keys[d_offsets[s] .. d_offsets[s+1]) for s < num_segments; each segment is sorted in place,

@@ -76,6 +76,42 @@ inline void sort_device_descending(uint32_t* d_keys, void* d_workspace, size_t w
           "lsdsort_keys_device");
 }
 
+// 64-bit keys (lsdsort_keys64_device): the overload picks the key type; workspace of wide_workspace_bytes(n, radix_bits, val_bits).
+// float64 sorts in IEEE total order; descending is stable too.  sort_records_device: the same with a 32- or 64-bit payload per key.
+inline size_t wide_workspace_bytes(size_t n, int radix_bits = 8, int val_bits = 0) { return lsdsort_wide_workspace_bytes(n, radix_bits, 64, val_bits); }
+inline void sort_device(uint64_t* d_keys, void* d_workspace, size_t workspace_bytes_, size_t n, bool descending = false,
+                        int radix_bits = 8, void* hip_stream = nullptr)
+{
+    check(lsdsort_keys64_device(d_keys, nullptr, 0, d_workspace, workspace_bytes_, n, radix_bits, LSDSORT_KEY_U64, descending ? 1 : 0,
+                                hip_stream), "lsdsort_keys64_device");
+}
+inline void sort_device(int64_t* d_keys, void* d_workspace, size_t workspace_bytes_, size_t n, bool descending = false,
+                        int radix_bits = 8, void* hip_stream = nullptr)
+{
+    check(lsdsort_keys64_device(d_keys, nullptr, 0, d_workspace, workspace_bytes_, n, radix_bits, LSDSORT_KEY_I64, descending ? 1 : 0,
+                                hip_stream), "lsdsort_keys64_device");
+}
+inline void sort_device(double* d_keys, void* d_workspace, size_t workspace_bytes_, size_t n, bool descending = false,
+                        int radix_bits = 8, void* hip_stream = nullptr)
+{
+    check(lsdsort_keys64_device(d_keys, nullptr, 0, d_workspace, workspace_bytes_, n, radix_bits, LSDSORT_KEY_F64, descending ? 1 : 0,
+                                hip_stream), "lsdsort_keys64_device");
+}
+namespace detail {
+inline lsdsort_key_type key64_type(const uint64_t*) { return LSDSORT_KEY_U64; }
+inline lsdsort_key_type key64_type(const int64_t*) { return LSDSORT_KEY_I64; }
+inline lsdsort_key_type key64_type(const double*) { return LSDSORT_KEY_F64; }
+}  // namespace detail
+// Key = uint64_t, int64_t or double; Val = a 32- or 64-bit type (its bits travel untouched)
+template <class Key, class Val>
+inline void sort_records_device(Key* d_keys, Val* d_vals, void* d_workspace, size_t workspace_bytes_, size_t n, bool descending = false,
+                                int radix_bits = 8, void* hip_stream = nullptr)
+{
+    static_assert(sizeof(Val) == 4 || sizeof(Val) == 8, "payloads of 32 or 64 bits");
+    check(lsdsort_keys64_device(d_keys, d_vals, (int)sizeof(Val) * 8, d_workspace, workspace_bytes_, n, radix_bits,
+                                detail::key64_type(d_keys), descending ? 1 : 0, hip_stream), "lsdsort_keys64_device");
+}
+
 // Many independent segments of one array, each sorted in place and stable (lsdsort_segmented_device): segment s =
 // d_keys[d_offsets[s] .. d_offsets[s + 1]), d_offsets on the device.  Malformed offsets: lsdsort_check_device afterwards.
 inline size_t segmented_workspace_bytes(size_t n, size_t num_segments, bool pairs = false)

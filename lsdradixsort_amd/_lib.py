@@ -74,6 +74,8 @@ SIGNATURES = {
     "lsdsort_u64_device": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_size, c_size, c_int, ctypes.c_void_p]),
     "lsdsort_records_device": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_int, c_int, ctypes.c_void_p, c_size, c_size, c_int,
                                        ctypes.c_void_p]),
+    "lsdsort_keys64_device": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_int, ctypes.c_void_p, c_size, c_size, c_int, c_int, c_int,
+                                      ctypes.c_void_p]),
     "lsdsort_wide_check_device": (c_int, [ctypes.c_void_p, c_size, c_int, c_int, c_int, ctypes.c_void_p]),
     "lsdsort_check_device": (c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "lsdsort_segmented_workspace_bytes": (c_size, [c_size, c_size, c_int]),

@@ -19,7 +19,7 @@ from .errors import LSDSORT_ALGO_ONESWEEP, LSDSORT_ALGO_STAGED, check
 __all__ = [
     "sort", "sort_pairs", "to_device", "to_host", "workspace_bytes", "GPULSDRadixSort",
     "GPULSDRadixSortTimed", "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
-    "MSBPartition", "SplitterPartition", "GPUSortTyped", "GPUSortWide", "GPUSortSegmented", "segmented_workspace_bytes", "sort_rows", "GPUTopK", "topk_workspace_bytes", "topk_rows", "GPUSortMulti", "set_hybrid", "tile_keys", "set_tile_config", "set_rank_method", "rank_method", "set_xcd_chunk", "LSDSORT_ALGO_ONESWEEP", "LSDSORT_ALGO_STAGED",
+    "MSBPartition", "SplitterPartition", "GPUSortTyped", "GPUSortWide", "sort64", "GPUSortSegmented", "segmented_workspace_bytes", "sort_rows", "GPUTopK", "topk_workspace_bytes", "topk_rows", "GPUSortMulti", "set_hybrid", "tile_keys", "set_tile_config", "set_rank_method", "rank_method", "set_xcd_chunk", "LSDSORT_ALGO_ONESWEEP", "LSDSORT_ALGO_STAGED",
 ]
 
 
@@ -351,15 +351,26 @@ def topk_rows(x, k: int, largest: bool = True, stream=None):
         return values.view(lead + (k,)), indices.view(lead + (k,)).to(torch.int64)
 
 
-def GPUSortWide(d_keys, d_vals=None, r: int = 8, workspace=None, stream=None, check_fault: bool = False):
-    """64-bit keys and / or 64-bit payloads, in place (``lsdsort_u64_device`` / ``lsdsort_records_device``).
-    ``d_keys``: int64 CUDA tensor (uint64 bit patterns) or int32 (uint32 bit patterns); ``d_vals``: None (64-bit keys
-    only), int32 or int64.  The 32/32 combination is ``GPULSDRadixSort``.  Stable by key."""
+_KEY_TYPES_64 = {"uint64": 3, "int64": 4, "float64": 5}
+
+
+def GPUSortWide(d_keys, d_vals=None, r: int = 8, workspace=None, stream=None, check_fault: bool = False, key_type: str = "uint64",
+                descending: bool = False):
+    """64-bit keys and / or 64-bit payloads, in place (``lsdsort_keys64_device`` / ``lsdsort_records_device``).
+    ``d_keys``: int64 CUDA tensor whose 64 bits compare as ``key_type`` ("uint64", the default: uint64 bit patterns, so negative
+    int64 values sort AFTER the positive ones; "int64"; "float64": the bit patterns of doubles), a float64 tensor with ``key_type="float64"`` (IEEE total
+    order: NaNs by sign at the two ends, -0.0 below +0.0), or int32 (uint32 bit patterns; ascending only); ``d_vals``: None (64-bit keys only),
+    int32 or int64.  The 32/32 combination is ``GPULSDRadixSort``.  Stable by key, ``descending`` too."""
     torch = _torch()
     bits = {torch.int32: 32, torch.int64: 64}
-    if not (isinstance(d_keys, torch.Tensor) and d_keys.is_cuda and d_keys.is_contiguous() and d_keys.dtype in bits):
-        raise TypeError("d_keys: a contiguous int32 or int64 CUDA tensor")
-    kb = bits[d_keys.dtype]
+    if key_type not in _KEY_TYPES_64:
+        raise ValueError('key_type: "uint64", "int64" or "float64"')
+    if not (isinstance(d_keys, torch.Tensor) and d_keys.is_cuda and d_keys.is_contiguous()
+            and (d_keys.dtype in bits or d_keys.dtype == torch.float64)):
+        raise TypeError("d_keys: a contiguous int32, int64 or float64 CUDA tensor")
+    if d_keys.dtype == torch.float64 and key_type != "float64":
+        raise TypeError('a float64 tensor sorts with key_type="float64" only')
+    kb = 32 if d_keys.dtype == torch.int32 else 64
     vb = 0
     if d_vals is not None:
         if not (isinstance(d_vals, torch.Tensor) and d_vals.is_cuda and d_vals.is_contiguous() and d_vals.dtype in bits):
@@ -369,6 +380,8 @@ def GPUSortWide(d_keys, d_vals=None, r: int = 8, workspace=None, stream=None, ch
         vb = bits[d_vals.dtype]
     if (kb, vb) in ((32, 0), (32, 32)):
         raise ValueError("32-bit keys with no or 32-bit payloads: use GPULSDRadixSort")
+    if kb == 32 and (key_type != "uint64" or descending):
+        raise ValueError("32-bit keys with 64-bit payloads sort as uint32, ascending, only")
     n = d_keys.numel()
     need = int(lib().lsdsort_wide_workspace_bytes(n, r, kb, vb))
     if need == 0:
@@ -379,9 +392,10 @@ def GPUSortWide(d_keys, d_vals=None, r: int = 8, workspace=None, stream=None, ch
                 workspace = torch.empty(need, dtype=torch.uint8, device=d_keys.device)
         else:
             workspace = torch.empty(need, dtype=torch.uint8, device=d_keys.device)
-    if vb == 0:
-        st = lib().lsdsort_u64_device(d_keys.data_ptr(), workspace.data_ptr(), workspace.numel(), n, r, _stream(stream))
-        check(st, "lsdsort_u64_device")
+    if kb == 64:
+        st = lib().lsdsort_keys64_device(d_keys.data_ptr(), d_vals.data_ptr() if vb else None, vb, workspace.data_ptr(),
+                                         workspace.numel(), n, r, _KEY_TYPES_64[key_type], int(bool(descending)), _stream(stream))
+        check(st, "lsdsort_keys64_device")
     else:
         st = lib().lsdsort_records_device(d_keys.data_ptr(), d_vals.data_ptr(), kb, vb, workspace.data_ptr(), workspace.numel(), n, r,
                                           _stream(stream))
@@ -389,6 +403,25 @@ def GPUSortWide(d_keys, d_vals=None, r: int = 8, workspace=None, stream=None, ch
     if check_fault and n:
         check(lib().lsdsort_wide_check_device(workspace.data_ptr(), n, r, kb, vb, _stream(stream)), "lsdsort_wide_check_device")
     return d_keys if d_vals is None else (d_keys, d_vals)
+
+
+def sort64(x, descending: bool = False, return_indices: bool = False, stream=None):
+    """``torch.sort(x, stable=True, descending=descending)`` for a 1-D int64 / float64 CUDA tensor, the 64-bit counterpart of
+    ``sort_rows``: returns the sorted copy, and with ``return_indices`` also the int64 positions (a 64/32 records sort with the
+    positions as payload, so equal keys keep their input order in either direction).  float64 follows IEEE total order, not
+    torch's: NaNs by sign at the two ends (+NaN above +inf, -NaN below -inf) and -0.0 below +0.0."""
+    torch = _torch()
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 1 and x.dtype in (torch.int64, torch.float64)):
+        raise TypeError("x: a 1-D int64 or float64 CUDA tensor")
+    key_type = "int64" if x.dtype == torch.int64 else "float64"
+    ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.stream(torch.cuda.current_stream())
+    with ctx:
+        out = x.clone(memory_format=torch.contiguous_format)
+        idx = torch.arange(x.numel(), dtype=torch.int32, device=x.device) if return_indices else None
+        GPUSortWide(out, idx, key_type=key_type, descending=descending, stream=stream)
+        if return_indices:
+            return out, idx.to(torch.int64)
+    return out
 
 
 def GPULSDRadixSortTimed(d_keys, r: int = 8, d_vals=None, algorithm: int = LSDSORT_ALGO_ONESWEEP, workspace=None,
