@@ -7,9 +7,13 @@ library, or without a gfx950 device, every entry raises.
 """
 from .errors import (LSDSORT_ALGO_ONESWEEP, LSDSORT_ALGO_STAGED, LSDSORT_MAX_KEYS, LsdsortError)  # noqa: F401
 from ._lib import LIB_PATH, lib  # noqa: F401
-from .api import (BuildHistograms, BuildOffsets, DigitHistograms, GPULSDRadixSort, GPULSDRadixSortTimed, GPUSortMulti, GPUSortTyped, GPUSortWide,  # noqa: F401
-                  GPUSortSegmented, MSBPartition, RankScatter, SplitterPartition, segmented_workspace_bytes, sort_rows, sort64, GPUTopK, topk_workspace_bytes, topk_rows, ThresholdPartition, sharded_thresholds, alloc_workspace, rank_method, set_hybrid, set_pass_skipping, set_small_sort, workspace_form, set_rank_method, set_tile_config, set_xcd_chunk, sort,
-                  sort_pairs, tile_keys,
-                  to_device, to_host, workspace_bytes)
+from .api import (  # noqa: F401  (api.__all__, name for name)
+    sort, sort_pairs, to_device, to_host, workspace_bytes, alloc_workspace, workspace_form, tile_keys,
+    set_tile_config, set_xcd_chunk, set_hybrid, set_small_sort, set_pass_skipping, set_rank_method, rank_method,
+    GPULSDRadixSort, GPULSDRadixSortTimed, GPUSortMulti, GPUSortTyped, GPUSortWide, sort64,
+    GPUSortSegmented, segmented_workspace_bytes, sort_rows, GPUTopK, topk_workspace_bytes, topk_rows,
+    BuildHistograms, BuildOffsets, RankScatter, DigitHistograms,
+    MSBPartition, SplitterPartition, ThresholdPartition, sharded_thresholds,
+)
 
 __version__ = "0.1.0"

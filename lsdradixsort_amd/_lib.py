@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes
 import os
 
+from .errors import LSDSORT_MAX_PASSES
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 PRODUCT_LIB = os.path.join(_HERE, "liblsdsort.so")
 
@@ -35,8 +37,6 @@ LIB_PATH = _library_path()
 c_u32p = ctypes.c_void_p   # device or host addresses are passed as integers
 c_size = ctypes.c_size_t
 c_int = ctypes.c_int
-
-LSDSORT_MAX_PASSES = 32
 
 
 class LsdsortTiming(ctypes.Structure):

@@ -14,12 +14,16 @@ import numpy as np
 
 from . import errors
 from ._lib import LsdsortTiming, lib
-from .errors import LSDSORT_ALGO_ONESWEEP, LSDSORT_ALGO_STAGED, check
+from .errors import KEY_TYPES_32, KEY_TYPES_64, LSDSORT_ALGO_ONESWEEP, LSDSORT_ALGO_STAGED, check  # noqa: F401
 
+# exactly what __init__.py re-exports from here (tests/test_python_face_cpu.py)
 __all__ = [
-    "sort", "sort_pairs", "to_device", "to_host", "workspace_bytes", "GPULSDRadixSort",
-    "GPULSDRadixSortTimed", "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
-    "MSBPartition", "SplitterPartition", "GPUSortTyped", "GPUSortWide", "sort64", "GPUSortSegmented", "segmented_workspace_bytes", "sort_rows", "GPUTopK", "topk_workspace_bytes", "topk_rows", "GPUSortMulti", "set_hybrid", "tile_keys", "set_tile_config", "set_rank_method", "rank_method", "set_xcd_chunk", "LSDSORT_ALGO_ONESWEEP", "LSDSORT_ALGO_STAGED",
+    "sort", "sort_pairs", "to_device", "to_host", "workspace_bytes", "alloc_workspace", "workspace_form", "tile_keys",
+    "set_tile_config", "set_xcd_chunk", "set_hybrid", "set_small_sort", "set_pass_skipping", "set_rank_method", "rank_method",
+    "GPULSDRadixSort", "GPULSDRadixSortTimed", "GPUSortMulti", "GPUSortTyped", "GPUSortWide", "sort64",
+    "GPUSortSegmented", "segmented_workspace_bytes", "sort_rows", "GPUTopK", "topk_workspace_bytes", "topk_rows",
+    "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
+    "MSBPartition", "SplitterPartition", "ThresholdPartition", "sharded_thresholds",
 ]
 
 
@@ -68,11 +72,33 @@ def to_host(t) -> np.ndarray:
     return t.detach().cpu().numpy().view(np.uint32)
 
 
-def _dev_i32(t, name: str):
+def _dev(t, name: str, dtypes=None, dims=None, contiguous: bool = True):
+    """The tensor check of every wrapper: ``t`` is a CUDA tensor of one of ``dtypes`` (default: int32, holding uint32 bit
+    patterns), with one of ``dims`` dimensions where that is given, and contiguous -- except where the wrapper sorts a copy it
+    makes itself."""
     torch = _torch()
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
-        raise TypeError(f"{name} must be a contiguous torch.int32 CUDA tensor (uint32 bit patterns)")
+    dtypes = dtypes or (torch.int32,)
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in dtypes and (t.is_contiguous() or not contiguous)
+            and (dims is None or t.dim() in dims)):
+        shape = "" if dims is None else " or ".join(f"{d}-D" for d in dims) + " "
+        kinds = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise TypeError(f"{name}: a {'contiguous ' if contiguous else ''}{shape}{kinds} CUDA tensor")
     return t
+
+
+def _payload(d_vals, n: int, name: str = "d_vals", dtypes=None, what: str = "vals"):
+    """A payload array: the tensor check, and as long as the keys."""
+    _dev(d_vals, name, dtypes)
+    if d_vals.numel() != n:
+        raise ValueError(f"keys and {what} differ in length")
+    return d_vals
+
+
+def _key_type(key_type: str, table: dict) -> int:
+    """The header's code of a key type name; ``table`` is KEY_TYPES_32 or KEY_TYPES_64."""
+    if key_type not in table:
+        raise ValueError("key_type: " + " or ".join(f'"{name}"' for name in table) + f", got {key_type!r}")
+    return table[key_type]
 
 
 def _stream(stream=None) -> int:
@@ -81,24 +107,44 @@ def _stream(stream=None) -> int:
     return int(s.cuda_stream)
 
 
-def workspace_bytes(n: int, radix_bits: int = 8, pairs: bool = False, algorithm: int = LSDSORT_ALGO_ONESWEEP) -> int:
+def _on_stream(stream):
+    """Context in which torch allocates and enqueues on ``stream``; ``None``: on the current stream, as it does anyway."""
+    torch = _torch()
+    return torch.cuda.stream(stream)
+
+
+def _temp_workspace(nbytes: int, device, stream):
+    """The one place a workspace tensor is made.  A wrapper returns while its kernels are still running, so a temporary
+    workspace must belong to THEIR stream: allocated under ``stream`` (where that is not torch's current stream, ``None``), the
+    caching allocator orders the block's reuse after the sort's kernels instead of after whatever the current stream is doing."""
+    torch = _torch()
+    with _on_stream(stream):
+        # torch's caching allocator returns 512-byte aligned blocks; the ABI needs 256.
+        return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+
+
+def _check_fault(workspace, stream, entry: str = "lsdsort_check_device", *shape, quiet: bool = False) -> int:
+    """Read back the fault word of the work queued in ``workspace`` and raise if it is set (synchronises ``stream``); ``quiet``:
+    return the status instead.  ``entry`` and ``shape``: the wide sorts' check.  Callers ask only where kernels ran at all."""
+    status = int(getattr(lib(), entry)(workspace.data_ptr(), *shape, _stream(stream)))
+    if not quiet:
+        check(status, entry)
+    return status
+
+
+def workspace_bytes(n: int, radix_bits: int = 8, pairs: int = False, algorithm: int = LSDSORT_ALGO_ONESWEEP) -> int:
+    """Bytes of device workspace for a sort of up to ``n`` keys; ``pairs``: the number of payload arrays (False / True / 2 / 3)."""
     return int(lib().lsdsort_workspace_bytes_ex(n, radix_bits, int(pairs), algorithm))
 
 
-def alloc_workspace(n: int, radix_bits: int = 8, pairs: bool = False, algorithm: int = LSDSORT_ALGO_ONESWEEP,
+def alloc_workspace(n: int, radix_bits: int = 8, pairs: int = False, algorithm: int = LSDSORT_ALGO_ONESWEEP,
                     device: str = "cuda", stream=None):
-    """Workspace tensor for a sort of up to ``n`` keys.  ``stream``: the stream the sort will run on when that is not
-    torch's current stream -- the block is then allocated under it, so the caching allocator orders its reuse
-    after the sort's kernels instead of after whatever the current stream is doing."""
-    torch = _torch()
+    """Workspace tensor for a sort of up to ``n`` keys with ``pairs`` payload arrays.  ``stream``: the stream the sort will
+    run on when that is not torch's current stream (see ``_temp_workspace``)."""
     nbytes = workspace_bytes(n, radix_bits, pairs, algorithm)
     if nbytes == 0 and n > 0:
         raise errors.LsdsortError(errors.LSDSORT_ERR_INVALID_ARG, "lsdsort_workspace_bytes_ex", "bad (n, radix_bits)")
-    # torch's caching allocator returns 512-byte aligned blocks; the ABI needs 256.
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
-    return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+    return _temp_workspace(nbytes, device, stream)
 
 
 def tile_keys(radix_bits: int) -> int:
@@ -127,8 +173,6 @@ def set_small_sort(on: bool) -> None:
 
 def workspace_form(workspace, stream=None) -> int:
     """1 if the last sort queued in ``workspace`` ran the hybrid form, 0 if the ordinary passes (``lsdsort_workspace_form``)."""
-    import ctypes
-
     out = ctypes.c_int(0)
     check(lib().lsdsort_workspace_form(workspace.data_ptr(), _stream(stream), ctypes.byref(out)), "lsdsort_workspace_form")
     return out.value
@@ -160,55 +204,39 @@ def GPULSDRadixSort(d_keys, r: int = 8, d_vals=None, algorithm: int = LSDSORT_AL
     in ``d_keys`` like the reference's ``a``.  Stream-ordered, no synchronisation unless
     ``check_fault`` (then the workspace fault word is read back).
     """
-    _dev_i32(d_keys, "d_keys")
+    _dev(d_keys, "d_keys")
     n = d_keys.numel()
     pairs = d_vals is not None
     if pairs:
-        _dev_i32(d_vals, "d_vals")
-        if d_vals.numel() != n:
-            raise ValueError("keys and vals differ in length")
+        _payload(d_vals, n)
     if workspace is None:
-        # the call returns while the passes are still running: a temporary workspace must belong to THEIR stream
-        workspace = alloc_workspace(n, r, pairs, algorithm, d_keys.device, stream=stream)
+        workspace = alloc_workspace(n, r, pairs, algorithm, d_keys.device, stream)
     st = lib().lsdsort_u32_device_ex(d_keys.data_ptr(), d_vals.data_ptr() if pairs else None, workspace.data_ptr(),
                                      workspace.numel(), n, r, algorithm, _stream(stream))
     check(st, "lsdsort_u32_device_ex")
     if check_fault and n:
-        check(lib().lsdsort_check_device(workspace.data_ptr(), _stream(stream)), "lsdsort_check_device")
+        _check_fault(workspace, stream)
     return d_keys if not pairs else (d_keys, d_vals)
 
 
 def GPUSortMulti(d_keys, payloads, r: int = 8, workspace=None, stream=None, check_fault: bool = False):
     """Keys with one to three 32-bit payload arrays (``lsdsort_multi_u32_device``): every array in ``payloads`` (int32 CUDA
     tensors as long as ``d_keys``) is permuted exactly like the keys, stable by key.  In place."""
-    import ctypes
-
-    _dev_i32(d_keys, "d_keys")
+    _dev(d_keys, "d_keys")
     n = d_keys.numel()
     payloads = list(payloads)
     if not 1 <= len(payloads) <= 3:
         raise ValueError("one to three payload arrays")
     for i, v in enumerate(payloads):
-        _dev_i32(v, f"payloads[{i}]")
-        if v.numel() != n:
-            raise ValueError("keys and payloads differ in length")
+        _payload(v, n, f"payloads[{i}]", what="payloads")
     if workspace is None:
-        need = int(lib().lsdsort_workspace_bytes(n, r, len(payloads)))
-        torch = _torch()
-        if stream is not None:
-            with torch.cuda.stream(stream):
-                workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=d_keys.device)
-        else:
-            workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=d_keys.device)
+        workspace = alloc_workspace(n, r, len(payloads), LSDSORT_ALGO_ONESWEEP, d_keys.device, stream)
     ptrs = (ctypes.c_void_p * len(payloads))(*[v.data_ptr() for v in payloads])
     check(lib().lsdsort_multi_u32_device(d_keys.data_ptr(), ptrs, len(payloads), workspace.data_ptr(), workspace.numel(), n, r,
                                          _stream(stream)), "lsdsort_multi_u32_device")
     if check_fault and n:
-        check(lib().lsdsort_check_device(workspace.data_ptr(), _stream(stream)), "lsdsort_check_device")
+        _check_fault(workspace, stream)
     return d_keys, payloads
-
-
-_KEY_TYPES = {"uint32": 0, "int32": 1, "float32": 2}
 
 
 def GPUSortTyped(d_keys, key_type: str = "int32", descending: bool = False, d_vals=None, r: int = 8, workspace=None,
@@ -217,21 +245,19 @@ def GPUSortTyped(d_keys, key_type: str = "int32", descending: bool = False, d_va
     "uint32" / "int32" / "float32" says how the 32 bits of each element of ``d_keys`` (an int32 or float32 CUDA
     tensor) compare; float32 uses IEEE total order.  Stable with ``d_vals`` (int32 payloads).  In place."""
     torch = _torch()
-    if not (d_keys.is_cuda and d_keys.is_contiguous() and d_keys.dtype in (torch.int32, torch.float32)):
-        raise TypeError("d_keys: a contiguous int32 or float32 CUDA tensor")
+    _dev(d_keys, "d_keys", (torch.int32, torch.float32))
     n = d_keys.numel()
     pairs = d_vals is not None
     if pairs:
-        _dev_i32(d_vals, "d_vals")
-        if d_vals.numel() != n:
-            raise ValueError("keys and vals differ in length")
+        _payload(d_vals, n)
+    code = _key_type(key_type, KEY_TYPES_32)
     if workspace is None:
-        workspace = alloc_workspace(n, r, pairs, LSDSORT_ALGO_ONESWEEP, d_keys.device, stream=stream)
+        workspace = alloc_workspace(n, r, pairs, LSDSORT_ALGO_ONESWEEP, d_keys.device, stream)
     check(lib().lsdsort_keys_device(d_keys.data_ptr(), d_vals.data_ptr() if pairs else None, workspace.data_ptr(),
-                                    workspace.numel(), n, r, _KEY_TYPES[key_type], int(bool(descending)), _stream(stream)),
+                                    workspace.numel(), n, r, code, int(bool(descending)), _stream(stream)),
           "lsdsort_keys_device")
     if check_fault and n:
-        check(lib().lsdsort_check_device(workspace.data_ptr(), _stream(stream)), "lsdsort_check_device")
+        _check_fault(workspace, stream)
     return d_keys if not pairs else (d_keys, d_vals)
 
 
@@ -246,34 +272,27 @@ def GPUSortSegmented(d_keys, d_offsets, d_vals=None, key_type: str = "uint32", d
     (``lsdsort_segmented_device``).  ``d_keys``: int32 or float32 CUDA tensor whose 32 bits compare as ``key_type``
     ("uint32" / "int32" / "float32", IEEE total order); ``d_offsets``: int32 CUDA tensor of num_segments + 1 ascending
     offsets (uint32 bit patterns); ``d_vals``: optional int32 payloads permuted with the keys.  Keys outside
-    ``[d_offsets[0], d_offsets[-1])`` are left alone.  Malformed offsets are reported by ``lsdsort_check_device``
+    ``[d_offsets[0], d_offsets[-1])`` are left alone.  Malformed offsets are reported by the fault check
     (``check_fault=True`` raises)."""
     torch = _torch()
-    if not (isinstance(d_keys, torch.Tensor) and d_keys.is_cuda and d_keys.is_contiguous() and d_keys.dtype in (torch.int32, torch.float32)):
-        raise TypeError("d_keys: a contiguous int32 or float32 CUDA tensor")
-    _dev_i32(d_offsets, "d_offsets")
+    _dev(d_keys, "d_keys", (torch.int32, torch.float32))
+    _dev(d_offsets, "d_offsets")
     n = d_keys.numel()
     segs = max(d_offsets.numel() - 1, 0)
     pairs = d_vals is not None
     if pairs:
-        _dev_i32(d_vals, "d_vals")
-        if d_vals.numel() != n:
-            raise ValueError("keys and vals differ in length")
+        _payload(d_vals, n)
+    code = _key_type(key_type, KEY_TYPES_32)
     if workspace is None:
         nbytes = segmented_workspace_bytes(n, segs, pairs)
         if nbytes == 0 and n > 0 and segs > 0:
             raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_segmented_workspace_bytes", "too many keys or segments")
-        if stream is not None:
-            with torch.cuda.stream(stream):
-                workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=d_keys.device)
-        else:
-            workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=d_keys.device)
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
     check(lib().lsdsort_segmented_device(d_keys.data_ptr(), d_vals.data_ptr() if pairs else None, d_offsets.data_ptr(), segs, n,
-                                         _KEY_TYPES[key_type], int(bool(descending)), workspace.data_ptr(), workspace.numel(),
-                                         _stream(stream)),
+                                         code, int(bool(descending)), workspace.data_ptr(), workspace.numel(), _stream(stream)),
           "lsdsort_segmented_device")
     if check_fault and n and segs:
-        check(lib().lsdsort_check_device(workspace.data_ptr(), _stream(stream)), "lsdsort_check_device")
+        _check_fault(workspace, stream)
     return d_keys if not pairs else (d_keys, d_vals)
 
 
@@ -282,12 +301,10 @@ def sort_rows(x, descending: bool = False, return_indices: bool = False, stream=
     library's segmented sort (float32 in IEEE total order: -0.0 before +0.0, NaNs by sign at the ends).  Returns the sorted
     copy, and with ``return_indices`` also the int64 positions within each row."""
     torch = _torch()
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 2 and x.dtype in (torch.int32, torch.float32)):
-        raise TypeError("x: a 2-D int32 or float32 CUDA tensor")
+    _dev(x, "x", (torch.int32, torch.float32), dims=(2,), contiguous=False)
     rows, cols = x.shape
     key_type = "int32" if x.dtype == torch.int32 else "float32"
-    ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.stream(torch.cuda.current_stream())
-    with ctx:
+    with _on_stream(stream):
         out = x.contiguous().clone()
         offsets = torch.arange(0, rows + 1, dtype=torch.int64, device=x.device).mul_(cols).to(torch.int32)
         idx = torch.arange(cols, dtype=torch.int32, device=x.device).repeat(rows) if return_indices else None
@@ -310,28 +327,26 @@ def GPUTopK(d_keys, k: int, key_type: str = "uint32", largest: bool = True, retu
     or ``None`` without ``return_indices`` -- exactly the first ``k`` columns of the rows' stable sort: equal keys in position
     order.  ``d_keys`` is only read.  Stream-ordered; the rows are not sorted (a radix select, then a sort of the winners)."""
     torch = _torch()
-    if not (isinstance(d_keys, torch.Tensor) and d_keys.is_cuda and d_keys.is_contiguous() and d_keys.dim() in (1, 2)
-            and d_keys.dtype in (torch.int32, torch.float32)):
-        raise TypeError("d_keys: a contiguous 1-D or 2-D int32 or float32 CUDA tensor")
+    _dev(d_keys, "d_keys", (torch.int32, torch.float32), dims=(1, 2))
     rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
     k = int(k)
     if not 0 <= k <= cols:
         raise ValueError("k must be within 0 .. the row length")
+    code = _key_type(key_type, KEY_TYPES_32)
     shape = (k,) if d_keys.dim() == 1 else (rows, k)
-    ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.stream(torch.cuda.current_stream())
-    with ctx:   # outputs and a temporary workspace belong to the stream the kernels run on
+    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
         values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
         indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
-        if workspace is None:
-            nbytes = topk_workspace_bytes(rows, cols, k)
-            if nbytes == 0:
-                raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_topk_workspace_bytes", "too many keys or rows")
-            workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=d_keys.device)
-    check(lib().lsdsort_topk_device(d_keys.data_ptr(), rows, cols, k, _KEY_TYPES[key_type], int(bool(largest)), values.data_ptr(),
+    if workspace is None:
+        nbytes = topk_workspace_bytes(rows, cols, k)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_topk_workspace_bytes", "too many keys or rows")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    check(lib().lsdsort_topk_device(d_keys.data_ptr(), rows, cols, k, code, int(bool(largest)), values.data_ptr(),
                                     indices.data_ptr() if return_indices else None, workspace.data_ptr(), workspace.numel(),
                                     _stream(stream)), "lsdsort_topk_device")
     if check_fault and rows and cols and k:
-        check(lib().lsdsort_check_device(workspace.data_ptr(), _stream(stream)), "lsdsort_check_device")
+        _check_fault(workspace, stream)
     return values, indices
 
 
@@ -340,18 +355,15 @@ def topk_rows(x, k: int, largest: bool = True, stream=None):
     dimensions: ``(values, int64 indices)``.  float32 follows IEEE total order, not torch's: NaNs by sign at the two ends
     (+NaN above +inf, -NaN below -inf) and -0.0 below +0.0.  Among equal keys the lower position comes first, always."""
     torch = _torch()
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() >= 1 and x.dtype in (torch.int32, torch.float32)):
-        raise TypeError("x: an int32 or float32 CUDA tensor")
+    _dev(x, "x", (torch.int32, torch.float32), contiguous=False)
+    if x.dim() == 0:
+        raise TypeError("x: at least one dimension")
     cols = x.shape[-1]
-    ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.stream(torch.cuda.current_stream())
-    with ctx:
+    with _on_stream(stream):
         flat = x.contiguous().view(-1, cols)
         values, indices = GPUTopK(flat, k, key_type="int32" if x.dtype == torch.int32 else "float32", largest=largest, stream=stream)
         lead = tuple(x.shape[:-1])
         return values.view(lead + (k,)), indices.view(lead + (k,)).to(torch.int64)
-
-
-_KEY_TYPES_64 = {"uint64": 3, "int64": 4, "float64": 5}
 
 
 def GPUSortWide(d_keys, d_vals=None, r: int = 8, workspace=None, stream=None, check_fault: bool = False, key_type: str = "uint64",
@@ -362,22 +374,15 @@ def GPUSortWide(d_keys, d_vals=None, r: int = 8, workspace=None, stream=None, ch
     order: NaNs by sign at the two ends, -0.0 below +0.0), or int32 (uint32 bit patterns; ascending only); ``d_vals``: None (64-bit keys only),
     int32 or int64.  The 32/32 combination is ``GPULSDRadixSort``.  Stable by key, ``descending`` too."""
     torch = _torch()
-    bits = {torch.int32: 32, torch.int64: 64}
-    if key_type not in _KEY_TYPES_64:
-        raise ValueError('key_type: "uint64", "int64" or "float64"')
-    if not (isinstance(d_keys, torch.Tensor) and d_keys.is_cuda and d_keys.is_contiguous()
-            and (d_keys.dtype in bits or d_keys.dtype == torch.float64)):
-        raise TypeError("d_keys: a contiguous int32, int64 or float64 CUDA tensor")
+    code = _key_type(key_type, KEY_TYPES_64)
+    _dev(d_keys, "d_keys", (torch.int32, torch.int64, torch.float64))
     if d_keys.dtype == torch.float64 and key_type != "float64":
         raise TypeError('a float64 tensor sorts with key_type="float64" only')
     kb = 32 if d_keys.dtype == torch.int32 else 64
     vb = 0
     if d_vals is not None:
-        if not (isinstance(d_vals, torch.Tensor) and d_vals.is_cuda and d_vals.is_contiguous() and d_vals.dtype in bits):
-            raise TypeError("d_vals: a contiguous int32 or int64 CUDA tensor")
-        if d_vals.numel() != d_keys.numel():
-            raise ValueError("keys and vals differ in length")
-        vb = bits[d_vals.dtype]
+        _payload(d_vals, d_keys.numel(), dtypes=(torch.int32, torch.int64))
+        vb = 32 if d_vals.dtype == torch.int32 else 64
     if (kb, vb) in ((32, 0), (32, 32)):
         raise ValueError("32-bit keys with no or 32-bit payloads: use GPULSDRadixSort")
     if kb == 32 and (key_type != "uint64" or descending):
@@ -387,21 +392,17 @@ def GPUSortWide(d_keys, d_vals=None, r: int = 8, workspace=None, stream=None, ch
     if need == 0:
         raise errors.LsdsortError(errors.LSDSORT_ERR_INVALID_ARG, "lsdsort_wide_workspace_bytes", "bad (n, radix_bits)")
     if workspace is None:
-        if stream is not None:
-            with torch.cuda.stream(stream):
-                workspace = torch.empty(need, dtype=torch.uint8, device=d_keys.device)
-        else:
-            workspace = torch.empty(need, dtype=torch.uint8, device=d_keys.device)
+        workspace = _temp_workspace(need, d_keys.device, stream)
     if kb == 64:
         st = lib().lsdsort_keys64_device(d_keys.data_ptr(), d_vals.data_ptr() if vb else None, vb, workspace.data_ptr(),
-                                         workspace.numel(), n, r, _KEY_TYPES_64[key_type], int(bool(descending)), _stream(stream))
+                                         workspace.numel(), n, r, code, int(bool(descending)), _stream(stream))
         check(st, "lsdsort_keys64_device")
     else:
         st = lib().lsdsort_records_device(d_keys.data_ptr(), d_vals.data_ptr(), kb, vb, workspace.data_ptr(), workspace.numel(), n, r,
                                           _stream(stream))
         check(st, "lsdsort_records_device")
     if check_fault and n:
-        check(lib().lsdsort_wide_check_device(workspace.data_ptr(), n, r, kb, vb, _stream(stream)), "lsdsort_wide_check_device")
+        _check_fault(workspace, stream, "lsdsort_wide_check_device", n, r, kb, vb)
     return d_keys if d_vals is None else (d_keys, d_vals)
 
 
@@ -411,11 +412,9 @@ def sort64(x, descending: bool = False, return_indices: bool = False, stream=Non
     positions as payload, so equal keys keep their input order in either direction).  float64 follows IEEE total order, not
     torch's: NaNs by sign at the two ends (+NaN above +inf, -NaN below -inf) and -0.0 below +0.0."""
     torch = _torch()
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 1 and x.dtype in (torch.int64, torch.float64)):
-        raise TypeError("x: a 1-D int64 or float64 CUDA tensor")
+    _dev(x, "x", (torch.int64, torch.float64), dims=(1,), contiguous=False)
     key_type = "int64" if x.dtype == torch.int64 else "float64"
-    ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.stream(torch.cuda.current_stream())
-    with ctx:
+    with _on_stream(stream):
         out = x.clone(memory_format=torch.contiguous_format)
         idx = torch.arange(x.numel(), dtype=torch.int32, device=x.device) if return_indices else None
         GPUSortWide(out, idx, key_type=key_type, descending=descending, stream=stream)
@@ -427,11 +426,13 @@ def sort64(x, descending: bool = False, return_indices: bool = False, stream=Non
 def GPULSDRadixSortTimed(d_keys, r: int = 8, d_vals=None, algorithm: int = LSDSORT_ALGO_ONESWEEP, workspace=None,
                          stream=None) -> dict:
     """Same sort with per-kernel hipEvent times (``lsdsort_u32_device_timed``).  Blocking."""
-    _dev_i32(d_keys, "d_keys")
+    _dev(d_keys, "d_keys")
     n = d_keys.numel()
     pairs = d_vals is not None
+    if pairs:
+        _payload(d_vals, n)
     if workspace is None:
-        workspace = alloc_workspace(n, r, pairs, algorithm, d_keys.device, stream=stream)
+        workspace = alloc_workspace(n, r, pairs, algorithm, d_keys.device, stream)
     t = LsdsortTiming()
     st = lib().lsdsort_u32_device_timed(d_keys.data_ptr(), d_vals.data_ptr() if pairs else None, workspace.data_ptr(),
                                         workspace.numel(), n, r, algorithm, _stream(stream), ctypes.byref(t))
@@ -447,7 +448,7 @@ def GPULSDRadixSortTimed(d_keys, r: int = 8, d_vals=None, algorithm: int = LSDSO
 def BuildHistograms(d_keys, r: int, bit_group: int, stream=None):
     """h[tile][digit] for one digit: ``BuildHistogramsKernel`` (.cu:660-702)."""
     torch = _torch()
-    _dev_i32(d_keys, "d_keys")
+    _dev(d_keys, "d_keys")
     n = d_keys.numel()
     tk = tile_keys(r)
     tiles = (n + tk - 1) // tk
@@ -460,12 +461,11 @@ def BuildHistograms(d_keys, r: int, bit_group: int, stream=None):
 def BuildOffsets(d_hist, r: int, stream=None):
     """(local, global) offset tables from h[tile][digit]: the reference's .cu:862-895."""
     torch = _torch()
-    _dev_i32(d_hist, "d_hist")
+    _dev(d_hist, "d_hist")
     tiles = d_hist.shape[0]
     local = torch.empty_like(d_hist)
     glob = torch.empty_like(d_hist)
-    scratch = torch.empty(max(int(lib().lsdsort_tile_offsets_scratch_bytes(tiles, r)), 256), dtype=torch.uint8,
-                          device=d_hist.device)
+    scratch = _temp_workspace(int(lib().lsdsort_tile_offsets_scratch_bytes(tiles, r)), d_hist.device, None)   # with the outputs
     check(lib().lsdsort_tile_offsets_u32_device(d_hist.data_ptr(), local.data_ptr(), glob.data_ptr(), tiles, r,
                                                 scratch.data_ptr(), _stream(stream)),
           "lsdsort_tile_offsets_u32_device")
@@ -475,8 +475,8 @@ def BuildOffsets(d_hist, r: int, stream=None):
 def RankScatter(d_in, d_global, r: int, bit_group: int, d_vals=None, stream=None):
     """One rank-and-scatter pass from a global offset table: ``LSDRadixSortKernel`` (.cu:795-837)."""
     torch = _torch()
-    _dev_i32(d_in, "d_in")
-    _dev_i32(d_global, "d_global")
+    _dev(d_in, "d_in")
+    _dev(d_global, "d_global")
     out = torch.empty_like(d_in)
     vout = torch.empty_like(d_vals) if d_vals is not None else None
     check(lib().lsdsort_rank_scatter_u32_device(d_in.data_ptr(), out.data_ptr(),
@@ -490,85 +490,65 @@ def RankScatter(d_in, d_global, r: int, bit_group: int, d_vals=None, stream=None
 def DigitHistograms(d_keys, r: int, stream=None):
     """All 32/r digit histograms in one read (stage 1 of the default pass structure)."""
     torch = _torch()
-    _dev_i32(d_keys, "d_keys")
+    _dev(d_keys, "d_keys")
     h = torch.empty((32 // r, 1 << r), dtype=torch.int32, device=d_keys.device)
     check(lib().lsdsort_digit_histograms_u32_device(d_keys.data_ptr(), d_keys.numel(), r, h.data_ptr(),
                                                     _stream(stream)), "lsdsort_digit_histograms_u32_device")
     return h
 
 
-def MSBPartition(d_keys, msb_bits: int, stream=None):
-    """Stable partition by the top ``msb_bits`` bits -> (partitioned keys, int64 bucket counts)."""
+def _partition(entry: str, d_keys, bits: int, stream, *cuts):
+    """The body of the three partition faces: ``entry`` cuts ``d_keys`` into ``1 << bits`` buckets (``cuts``: its array of
+    bounds, for the two that take one) -> (partitioned keys, int64 bucket counts).  Outputs and workspace are allocated on
+    torch's current stream; the fault check synchronises ``stream`` before they are handed back."""
     torch = _torch()
-    _dev_i32(d_keys, "d_keys")
     n = d_keys.numel()
     out = torch.empty_like(d_keys)
-    counts = torch.zeros(1 << msb_bits, dtype=torch.int64, device=d_keys.device)
-    ws = torch.empty(max(int(lib().lsdsort_msb_partition_workspace_bytes(n, msb_bits)), 256), dtype=torch.uint8,
-                     device=d_keys.device)
-    check(lib().lsdsort_msb_partition_u32_device(d_keys.data_ptr(), out.data_ptr(), n, msb_bits, counts.data_ptr(),
-                                                 ws.data_ptr(), ws.numel(), _stream(stream)),
-          "lsdsort_msb_partition_u32_device")
+    counts = torch.zeros(1 << bits, dtype=torch.int64, device=d_keys.device)
+    ws = _temp_workspace(int(lib().lsdsort_msb_partition_workspace_bytes(n, bits)), d_keys.device, None)
+    check(getattr(lib(), entry)(d_keys.data_ptr(), out.data_ptr(), n, bits, *cuts, counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                _stream(stream)), entry)
     if n:
-        check(lib().lsdsort_check_device(ws.data_ptr(), _stream(stream)), "lsdsort_check_device")
+        _check_fault(ws, stream)
     return out, counts
+
+
+def _cuts(values, what: str, ctype):
+    """(bits, ctypes array) of a partition's 0, 1, 3 or 7 ascending bounds."""
+    if len(values) not in (0, 1, 3, 7):
+        raise ValueError(f"{what} count must be 0, 1, 3 or 7 (2, 4 or 8 buckets)")
+    return (len(values) + 1).bit_length() - 1, (ctype * max(len(values), 1))(*values)
+
+
+def MSBPartition(d_keys, msb_bits: int, stream=None):
+    """Stable partition by the top ``msb_bits`` bits -> (partitioned keys, int64 bucket counts)."""
+    _dev(d_keys, "d_keys")
+    return _partition("lsdsort_msb_partition_u32_device", d_keys, msb_bits, stream)
 
 
 def ThresholdPartition(d_keys, thresholds, stream=None):
     """Stable partition by 64-bit thresholds (1, 3 or 7 ascending values in [0, 2^32]; 2^32 = above every key):
     bucket(key) = number of thresholds <= key -> (partitioned keys, int64 bucket counts).  The form the sharded step's
     splitter rule uses (``lsdsort_threshold_partition_u32_device``)."""
-    torch = _torch()
-    _dev_i32(d_keys, "d_keys")
-    th = [int(x) for x in thresholds]
-    if len(th) not in (0, 1, 3, 7):
-        raise ValueError("threshold count must be 0, 1, 3 or 7 (2, 4 or 8 buckets)")
-    bits = (len(th) + 1).bit_length() - 1
-    n = d_keys.numel()
-    out = torch.empty_like(d_keys)
-    counts = torch.zeros(1 << bits, dtype=torch.int64, device=d_keys.device)
-    ws = torch.empty(max(int(lib().lsdsort_msb_partition_workspace_bytes(n, bits)), 256), dtype=torch.uint8,
-                     device=d_keys.device)
-    arr = (ctypes.c_uint64 * max(len(th), 1))(*th)
-    check(lib().lsdsort_threshold_partition_u32_device(d_keys.data_ptr(), out.data_ptr(), n, bits, arr, counts.data_ptr(),
-                                                       ws.data_ptr(), ws.numel(), _stream(stream)),
-          "lsdsort_threshold_partition_u32_device")
-    if n:
-        check(lib().lsdsort_check_device(ws.data_ptr(), _stream(stream)), "lsdsort_check_device")
-    return out, counts
+    _dev(d_keys, "d_keys")
+    bits, arr = _cuts([int(x) for x in thresholds], "threshold", ctypes.c_uint64)
+    return _partition("lsdsort_threshold_partition_u32_device", d_keys, bits, stream, arr)
+
+
+def SplitterPartition(d_keys, splitters, stream=None):
+    """Stable partition by value: bucket(key) = number of ``splitters`` (ascending uint32 values, 1, 3 or 7 of
+    them) <= key -> (partitioned keys, int64 bucket counts).  No splitters: one bucket."""
+    _dev(d_keys, "d_keys")
+    bits, arr = _cuts([int(x) & 0xFFFFFFFF for x in splitters], "splitter", ctypes.c_uint32)
+    return _partition("lsdsort_splitter_partition_u32_device", d_keys, bits, stream, arr)
 
 
 def sharded_thresholds(gathered, world: int, samples_per_rank: int, rank: int):
     """Host arithmetic of the sharded step's splitter rule (``lsdsort_sharded_thresholds``; no GPU): ``gathered`` is a
     [world][1 + samples_per_rank] uint32 array (valid count, then samples, per source rank) -> world - 1 thresholds
     of rank ``rank`` (Python ints in [0, 2^32])."""
-    import numpy as np
-
     g = np.ascontiguousarray(gathered, dtype=np.uint32).reshape(world, 1 + samples_per_rank)
     out = (ctypes.c_uint64 * max(world - 1, 1))()
     check(lib().lsdsort_sharded_thresholds(g.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), world, samples_per_rank, rank, out),
           "lsdsort_sharded_thresholds")
     return [int(out[i]) for i in range(world - 1)]
-
-
-def SplitterPartition(d_keys, splitters, stream=None):
-    """Stable partition by value: bucket(key) = number of ``splitters`` (ascending uint32 values, 1, 3 or 7 of
-    them) <= key -> (partitioned keys, int64 bucket counts).  No splitters: one bucket."""
-    torch = _torch()
-    _dev_i32(d_keys, "d_keys")
-    sp = [int(x) & 0xFFFFFFFF for x in splitters]
-    if len(sp) not in (0, 1, 3, 7):
-        raise ValueError("splitter count must be 0, 1, 3 or 7 (2, 4 or 8 buckets)")
-    bits = (len(sp) + 1).bit_length() - 1
-    n = d_keys.numel()
-    out = torch.empty_like(d_keys)
-    counts = torch.zeros(1 << bits, dtype=torch.int64, device=d_keys.device)
-    ws = torch.empty(max(int(lib().lsdsort_msb_partition_workspace_bytes(n, bits)), 256), dtype=torch.uint8,
-                     device=d_keys.device)
-    arr = (ctypes.c_uint32 * max(len(sp), 1))(*sp)
-    check(lib().lsdsort_splitter_partition_u32_device(d_keys.data_ptr(), out.data_ptr(), n, bits, arr, counts.data_ptr(),
-                                                      ws.data_ptr(), ws.numel(), _stream(stream)),
-          "lsdsort_splitter_partition_u32_device")
-    if n:
-        check(lib().lsdsort_check_device(ws.data_ptr(), _stream(stream)), "lsdsort_check_device")
-    return out, counts

@@ -27,7 +27,11 @@ Two drivers of the same step live here:
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
+
+from . import api, errors
+from .errors import LSDSORT_ERR_CAPACITY, check
 
 
 def _log2_exact(world: int) -> int:
@@ -41,24 +45,21 @@ class HipBackend:
     """The product's compute backend: liblsdsort.so on the current CUDA/HIP device."""
 
     def __init__(self, radix_bits: int = 8):
-        from . import api
-
-        self._api = api
         self.radix_bits = radix_bits
         self._ws = None
 
     def msb_partition(self, keys, msb_bits: int):
-        return self._api.MSBPartition(keys, msb_bits)
+        return api.MSBPartition(keys, msb_bits)
 
     def splitter_partition(self, keys, splitters):
-        return self._api.SplitterPartition(keys, splitters)
+        return api.SplitterPartition(keys, splitters)
 
     def sort_inplace(self, keys):
         n = keys.numel()
-        need = self._api.workspace_bytes(n, self.radix_bits)
+        need = api.workspace_bytes(n, self.radix_bits)
         if self._ws is None or self._ws.numel() < need:
-            self._ws = self._api.alloc_workspace(n, self.radix_bits, device=keys.device)
-        self._api.GPULSDRadixSort(keys, self.radix_bits, workspace=self._ws)
+            self._ws = api.alloc_workspace(n, self.radix_bits, device=keys.device)
+        api.GPULSDRadixSort(keys, self.radix_bits, workspace=self._ws)
         return keys
 
     def empty_like(self, ref, n: int):
@@ -67,12 +68,8 @@ class HipBackend:
         return torch.empty(n, dtype=ref.dtype, device=ref.device)
 
     def check_fault(self) -> int:
-        """lsdsort_check_device on the workspace this backend's sorts ran in (0 = ok; synchronises the stream)."""
-        if self._ws is None:
-            return 0
-        import torch
-
-        return int(self._api.lib().lsdsort_check_device(self._ws.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        """The fault word of the workspace this backend's sorts ran in, as a status (0 = ok; synchronises the stream)."""
+        return api._check_fault(self._ws, None, quiet=True) if self._ws is not None else 0
 
 
 @dataclass
@@ -82,6 +79,21 @@ class ShardResult:
     counts: object          # world x world int64 matrix: counts[src][dst] = keys src sent to dst
 
 
+def _sharded_call(comm, world: int, keys, out, capacity: int, ws, ws_bytes: int, radix_bits: int, partition: str, raw_stream):
+    """One rank's call of the C++ step: ``keys`` into ``out`` (room for ``capacity``) through the workspace ``ws``, declared
+    as ``ws_bytes`` long, on ``raw_stream`` -> (status, n_out, global offset, world x world int64 counts or, on failure, None)."""
+    import torch
+
+    n_out = ctypes.c_size_t(0)
+    offset = ctypes.c_uint64(0)
+    matrix = (ctypes.c_uint64 * (world * world))()
+    st = api.lib().lsdsort_sharded_u32_device_ex(comm, keys.data_ptr(), keys.numel(), out.data_ptr(), capacity, ctypes.byref(n_out),
+                                                 ctypes.byref(offset), matrix, ws.data_ptr(), ws_bytes, radix_bits,
+                                                 errors.PARTITIONS[partition], raw_stream)
+    counts = torch.tensor(list(matrix), dtype=torch.int64).view(world, world) if st == 0 else None
+    return int(st), int(n_out.value), int(offset.value), counts
+
+
 class ShardedSorter:
     """One rank of the multi-GPU sort through the C++ step (``partition``: "msb" buckets, or "splitters" sampled
     and cut inside the step for keys MSB buckets would not balance).  Collective construction: rank 0 makes
@@ -89,18 +101,12 @@ class ShardedSorter:
     on its current CUDA/HIP device.  Without an initialised process group it is a world of one (the RCCL calls
     are still made: a one-GPU box rehearses the whole path)."""
 
-    PARTITIONS = {"msb": 0, "splitters": 1}     # LSDSORT_PARTITION_MSB / LSDSORT_PARTITION_SPLITTERS
+    PARTITIONS = errors.PARTITIONS
 
     def __init__(self, radix_bits: int = 8, group=None, slack: float = 0.25, partition: str = "msb", sub_buckets: int = 1):
-        import ctypes
-
         import torch
         import torch.distributed as dist
 
-        from . import api
-        from .errors import check
-
-        self._api, self._ctypes, self._check = api, ctypes, check
         if partition not in self.PARTITIONS:
             raise ValueError(f"partition must be 'msb' or 'splitters', got {partition!r}")
         self.partition = partition
@@ -150,7 +156,7 @@ class ShardedSorter:
 
     def close(self):
         if getattr(self, "_comm", None):
-            self._api.lib().lsdsort_comm_destroy(self._comm)
+            api.lib().lsdsort_comm_destroy(self._comm)
             self._comm = None
 
     def __del__(self):
@@ -162,8 +168,7 @@ class ShardedSorter:
     def _buffers(self, n_local: int, capacity: int, device):
         import torch
 
-        L = self._api.lib()
-        need = int(L.lsdsort_sharded_workspace_bytes(n_local, capacity, self.world, self.radix_bits))
+        need = int(api.lib().lsdsort_sharded_workspace_bytes(n_local, capacity, self.world, self.radix_bits))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
         if self._out is None or self._out.numel() < capacity:
@@ -177,27 +182,20 @@ class ShardedSorter:
         every rank learns it before the exchange and the step is repeated once with exact sizes."""
         import torch
 
-        ctypes = self._ctypes
-        L = self._api.lib()
         n_local = local_keys.numel()
         stream = torch.cuda.current_stream().cuda_stream
         cap = capacity if capacity is not None else int(n_local * (1.0 + self.slack)) + 4096
         for attempt in (0, 1):
             ws, out = self._buffers(n_local, cap, local_keys.device)
-            n_out = ctypes.c_size_t(0)
-            offset = ctypes.c_uint64(0)
-            matrix = (ctypes.c_uint64 * (self.world * self.world))()
-            st = L.lsdsort_sharded_u32_device_ex(self._comm, local_keys.data_ptr(), n_local, out.data_ptr(), cap, ctypes.byref(n_out),
-                                                 ctypes.byref(offset), matrix, ws.data_ptr(), ws.numel(), self.radix_bits,
-                                                 self.PARTITIONS[self.partition], stream)
-            if st == -9 and attempt == 0:            # LSDSORT_ERR_CAPACITY: collective, EVERY rank got it (skewed keys): exact sizes this time
-                cap = max(int(n_out.value), 1)
+            st, n_out, offset, counts = _sharded_call(self._comm, self.world, local_keys, out, cap, ws, ws.numel(), self.radix_bits,
+                                                      self.partition, stream)
+            if st == LSDSORT_ERR_CAPACITY and attempt == 0:      # collective, EVERY rank got it (skewed keys): exact sizes this time
+                cap = max(n_out, 1)
                 continue
-            self._check(st, "lsdsort_sharded_u32_device")
+            check(st, "lsdsort_sharded_u32_device")
             self._last = (n_local, cap)
             break
-        counts = torch.tensor(list(matrix), dtype=torch.int64).view(self.world, self.world)
-        return ShardResult(out[: n_out.value], int(offset.value), counts)
+        return ShardResult(out[:n_out], offset, counts)
 
     def check_fault(self) -> int:
         """Fault words of the last step's partition pass and local sort (0 = ok; synchronises the stream)."""
@@ -206,8 +204,8 @@ class ShardedSorter:
         if self._ws is None or getattr(self, "_last", None) is None:
             return 0
         n_local, cap = self._last
-        return int(self._api.lib().lsdsort_sharded_check_device(self._ws.data_ptr(), n_local, cap, self.world, self.radix_bits,
-                                                                torch.cuda.current_stream().cuda_stream))
+        return int(api.lib().lsdsort_sharded_check_device(self._ws.data_ptr(), n_local, cap, self.world, self.radix_bits,
+                                                          torch.cuda.current_stream().cuda_stream))
 
 
 SAMPLES_PER_RANK = 4096
@@ -298,12 +296,6 @@ class LoopbackWorld:
     PARTITIONS = ShardedSorter.PARTITIONS
 
     def __init__(self, world: int, radix_bits: int = 8, sub_buckets: int = 1):
-        import ctypes
-
-        from . import api
-        from .errors import check
-
-        self._api = api
         _log2_exact(world)
         self.world = world
         self.radix_bits = radix_bits
@@ -316,7 +308,7 @@ class LoopbackWorld:
 
     def close(self):
         for c in getattr(self, "_comms", []):
-            self._api.lib().lsdsort_comm_destroy(c)
+            api.lib().lsdsort_comm_destroy(c)
         self._comms = []
 
     def __del__(self):
@@ -329,12 +321,11 @@ class LoopbackWorld:
         """One collective step: ``shards[r]`` is rank r's int32 CUDA tensor (left untouched), ``capacities[r]`` its output
         capacity (default: everything, so that nothing can overflow).  ``workspace_bytes[r]`` overrides rank r's workspace
         size (tests use a too-small one to make a rank fail on its own)."""
-        import ctypes
         import threading
 
         import torch
 
-        L = self._api.lib()
+        L = api.lib()
         W = self.world
         total = sum(int(s.numel()) for s in shards)
         caps = list(capacities) if capacities is not None else [total] * W
@@ -350,22 +341,15 @@ class LoopbackWorld:
             with torch.cuda.stream(stream):
                 ws = torch.empty(max(given, 256), dtype=torch.uint8, device="cuda")
                 out = torch.empty(max(caps[r], 1), dtype=torch.int32, device="cuda")
-            n_out = ctypes.c_size_t(0)
-            offset = ctypes.c_uint64(0)
-            matrix = (ctypes.c_uint64 * (W * W))()
-            st = L.lsdsort_sharded_u32_device_ex(self._comms[r], shards[r].data_ptr(), n_local, out.data_ptr(), caps[r], ctypes.byref(n_out),
-                                                 ctypes.byref(offset), matrix, ws.data_ptr(), given, self.radix_bits,
-                                                 self.PARTITIONS[partition], stream.cuda_stream)
+            st, n_out, offset, counts = _sharded_call(self._comms[r], W, shards[r], out, caps[r], ws, given, self.radix_bits, partition,
+                                                      stream.cuda_stream)
             res = None
             if st == 0:
-                fault = int(L.lsdsort_sharded_check_device(ws.data_ptr(), n_local, caps[r], W, self.radix_bits, stream.cuda_stream))
-                if fault != 0:
-                    st = fault
-                else:
-                    counts = torch.tensor(list(matrix), dtype=torch.int64).view(W, W)
-                    res = ShardResult(out[: n_out.value], int(offset.value), counts)
+                st = int(L.lsdsort_sharded_check_device(ws.data_ptr(), n_local, caps[r], W, self.radix_bits, stream.cuda_stream))
+                if st == 0:
+                    res = ShardResult(out[:n_out], offset, counts)
             stream.synchronize()
-            results[r] = (int(st), res, int(n_out.value))
+            results[r] = (st, res, n_out)
 
         threads = [threading.Thread(target=run, args=(r,), daemon=True) for r in range(W)]
         for t in threads:

@@ -1,4 +1,5 @@
-"""Status codes of include/lsdsort.h as Python exceptions."""
+"""The numbers of include/lsdsort.h, each once (tests/test_python_face_cpu.py holds them to the header), and its status
+codes as Python exceptions."""
 from __future__ import annotations
 
 LSDSORT_OK = 0
@@ -16,6 +17,16 @@ LSDSORT_ALGO_ONESWEEP = 0
 LSDSORT_ALGO_STAGED = 1
 
 LSDSORT_MAX_KEYS = 0x3FFFFFFF
+LSDSORT_MAX_PASSES = 32
+
+LSDSORT_KEY_U32, LSDSORT_KEY_I32, LSDSORT_KEY_F32 = 0, 1, 2
+LSDSORT_KEY_U64, LSDSORT_KEY_I64, LSDSORT_KEY_F64 = 3, 4, 5
+KEY_TYPES_32 = {"uint32": LSDSORT_KEY_U32, "int32": LSDSORT_KEY_I32, "float32": LSDSORT_KEY_F32}
+KEY_TYPES_64 = {"uint64": LSDSORT_KEY_U64, "int64": LSDSORT_KEY_I64, "float64": LSDSORT_KEY_F64}
+
+LSDSORT_PARTITION_MSB = 0
+LSDSORT_PARTITION_SPLITTERS = 1
+PARTITIONS = {"msb": LSDSORT_PARTITION_MSB, "splitters": LSDSORT_PARTITION_SPLITTERS}
 
 
 class LsdsortError(RuntimeError):
