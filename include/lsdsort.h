@@ -301,7 +301,10 @@ LSDSORT_API int lsdsort_digit_histograms_u32_device(const uint32_t* d_keys, size
 /* Stable partition of this rank's shard by the top msb_bits bits (0..4): d_out holds bucket
  * 0, bucket 1, ... contiguously, d_counts[b] (uint64, 2^msb_bits entries) their sizes.  The
  * caller exchanges buckets with its RCCL communicator (all-to-all over xGMI) and then runs
- * lsdsort_u32_device on what it received.  New work; the reference is single-GPU. */
+ * lsdsort_u32_device on what it received.  New work; the reference is single-GPU.
+ * n == 0 is NOT a no-op here (nor in the two forms below): d_counts is written (all
+ * zero) and the workspace's control block cleared, so d_counts and a workspace of
+ * lsdsort_msb_partition_workspace_bytes(0, msb_bits) are needed; d_in / d_out may be NULL. */
 LSDSORT_API size_t lsdsort_msb_partition_workspace_bytes(size_t n, int msb_bits);
 LSDSORT_API int lsdsort_msb_partition_u32_device(const uint32_t* d_in, uint32_t* d_out, size_t n,
                                                  int msb_bits, uint64_t* d_counts, void* d_workspace,

@@ -397,9 +397,12 @@ struct SortPlan {
 int validate(const SortRequest& rq)
 {
     if (rq.num_more < 0 || rq.num_more > 2) return LSDSORT_ERR_INVALID_ARG;
-    if (rq.num_more > 0 && (!rq.vals || !rq.more || rq.algorithm != LSDSORT_ALGO_ONESWEEP || rq.feed)) return LSDSORT_ERR_INVALID_ARG;
-    for (int e = 0; e < rq.num_more; e++)
-        if (rq.n > 0 && !rq.more[e]) return LSDSORT_ERR_INVALID_ARG;
+    if (rq.num_more > 0 && (rq.algorithm != LSDSORT_ALGO_ONESWEEP || rq.feed)) return LSDSORT_ERR_INVALID_ARG;
+    if (rq.num_more > 0 && rq.n > 0) {   // an empty sort may come with null arrays
+        if (!rq.vals || !rq.more) return LSDSORT_ERR_INVALID_ARG;
+        for (int e = 0; e < rq.num_more; e++)
+            if (!rq.more[e]) return LSDSORT_ERR_INVALID_ARG;
+    }
     if (rq.feed && rq.algorithm != LSDSORT_ALGO_ONESWEEP) return LSDSORT_ERR_INVALID_ARG;
     if (rq.xf.on && (rq.algorithm != LSDSORT_ALGO_ONESWEEP || rq.radix_bits < 4)) return LSDSORT_ERR_UNSUPPORTED;
     if (!valid_radix(rq.radix_bits)) return LSDSORT_ERR_INVALID_ARG;
@@ -1105,8 +1108,8 @@ int lsdsort_pairs_u32_device(uint32_t* d_keys, uint32_t* d_vals, void* d_workspa
 int lsdsort_multi_u32_device(uint32_t* d_keys, uint32_t* const* d_vals, int num_vals, void* d_workspace, size_t workspace_bytes,
                              size_t n, int radix_bits, void* hip_stream)
 {
-    if (num_vals < 1 || num_vals > 3 || !d_vals) return LSDSORT_ERR_INVALID_ARG;
-    if (n > 0 && !d_vals[0]) return LSDSORT_ERR_INVALID_ARG;
+    if (num_vals < 1 || num_vals > 3) return LSDSORT_ERR_INVALID_ARG;
+    if (n > 0 && (!d_vals || !d_vals[0])) return LSDSORT_ERR_INVALID_ARG;
     // the key/value kernel sends further payload arrays through its single-round shapes only (every default shape is one)
     const TileShape* shape = current_shape(radix_bits, n, LSDSORT_ALGO_ONESWEEP);
     if (num_vals > 1 && shape && valid_radix(radix_bits)) {
@@ -1114,8 +1117,8 @@ int lsdsort_multi_u32_device(uint32_t* d_keys, uint32_t* const* d_vals, int num_
         (void)lsd::tile_shapes(radix_bits, &shapes);
         if (!lsd::single_round_shape(radix_bits, (int)(shape - shapes))) return LSDSORT_ERR_UNSUPPORTED;
     }
-    SortRequest rq(d_keys, d_vals[0], d_workspace, workspace_bytes, n, radix_bits, hip_stream);
-    rq.more = d_vals + 1;
+    SortRequest rq(d_keys, d_vals ? d_vals[0] : nullptr, d_workspace, workspace_bytes, n, radix_bits, hip_stream);
+    rq.more = d_vals ? d_vals + 1 : nullptr;
     rq.num_more = num_vals - 1;
     return run_sort(rq);
 }

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
+from _guarded import assert_intact, guarded, guarded_workspace
 
 assert "faultinject" in lsd.LIB_PATH, lsd.LIB_PATH
 L = lsd.lib()
@@ -62,33 +63,25 @@ if mode == "wide":
     sys.exit(0)
 r = 8
 n = (1 << 23) + 123 if mode != "hybrid_counts" else (1 << 26) + 123     # hybrid_counts: a size where the hybrid form runs
-GUARD = 1 << 16                     # int32 words on either side of the keys / bytes on either side of the workspace
-SENT = 0x7E7E7E7E
 rng = np.random.default_rng(5)
 host = rng.integers(0, 1 << 32, size=n, dtype=np.uint64).astype(np.uint32)
 
-
-def guarded_i32(fill):
-    big = torch.full((GUARD + n + GUARD,), SENT, dtype=torch.int32, device="cuda")
-    big[GUARD:GUARD + n] = fill
-    return big, big[GUARD:GUARD + n]
-
-
-kbig, keys = guarded_i32(torch.from_numpy(host.view(np.int32)).cuda())
-vbig, vals = guarded_i32(torch.arange(n, dtype=torch.int32, device="cuda")) if pairs else (None, None)
+# guard zones (tests/_guarded.py): 65536 words on either side of the keys and the payload, 65536 bytes on either side of a
+# workspace of exactly the reported size
+kbig, keys = guarded(host)
+vbig, vals = guarded(np.arange(n, dtype=np.uint32)) if pairs else (None, None)
 wbytes = lsd.workspace_bytes(n, r, pairs)
-wbig = torch.full((GUARD + wbytes + GUARD,), 0x7E, dtype=torch.uint8, device="cuda")
-ws = wbig[GUARD:GUARD + wbytes]
-assert ws.data_ptr() % 256 == 0
+wbig, ws = guarded_workspace(wbytes)
 stream = torch.cuda.current_stream().cuda_stream
 
 
 def guards_intact():
-    ok = bool((kbig[:GUARD] == SENT).all()) and bool((kbig[GUARD + n:] == SENT).all())
-    ok = ok and bool((wbig[:GUARD] == 0x7E).all()) and bool((wbig[GUARD + wbytes:] == 0x7E).all())
-    if pairs:
-        ok = ok and bool((vbig[:GUARD] == SENT).all()) and bool((vbig[GUARD + n:] == SENT).all())
-    return ok
+    try:
+        assert_intact(keys=kbig, payload=vbig, workspace=wbig)
+    except AssertionError as e:
+        print(e, file=sys.stderr, flush=True)
+        return False
+    return True
 
 
 out = {"pairs": pairs, "n": n}

@@ -123,12 +123,13 @@ def test_full_size_nonuniform_pairs(gpu):
 def test_multi_payload_arrays_follow_their_keys(gpu, r):
     """lsdsort_multi_u32_device: keys with two and three payload arrays (the building block of the record sorts): every array
     comes out in the order of torch's STABLE argsort of the keys.  Sizes in every tile class (4096 .. 32768 keys per tile),
-    duplicate-heavy keys, dead digits (pass skipping: the copy back covers every array), a constant key."""
+    duplicate-heavy keys, dead digits (pass skipping: the copy back covers every array), a constant key, and no keys at all (empty
+    tensors, whose data_ptr() is 0: a no-op like every other empty sort)."""
     import torch
 
     gen = torch.Generator(device="cuda")
     for case, (n, mask) in enumerate([(4097, 0xFFFFFFFF), ((1 << 19) + 5, 0x00FF00FF), ((1 << 21) + 77, 0xFFFFFFFF),
-                                      ((1 << 23) + 4321, 0x0000FFFF), ((1 << 23) + 4321, 0xFFFFFFFF), (70001, 0), (1, 0xFFFFFFFF)]):
+                                      ((1 << 23) + 4321, 0x0000FFFF), ((1 << 23) + 4321, 0xFFFFFFFF), (70001, 0), (1, 0xFFFFFFFF), (0, 0xFFFFFFFF)]):
         gen.manual_seed(900 + case + r)
         base = torch.randint(-(1 << 31), (1 << 31) - 1, (n,), dtype=torch.int32, device="cuda", generator=gen)
         keys = (base.to(torch.int64) & mask & 0xFFFFFFFF)
