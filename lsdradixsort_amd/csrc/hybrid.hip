@@ -26,6 +26,8 @@ namespace lsd {
 constexpr int kHybridHistThreads = 1024;
 constexpr int kHybridCopiesA = 2;          // lane-class copies of the first pass's 2048 (region, digit) counters
 constexpr int kHybridVpt = 4;              // 16-byte vectors per thread per group
+static_assert(region_bits_for_radix(8) == 3 && region_bits_for_radix(4) == 4,
+              "the kernels below write 8 regions (3 bits) for 8-bit digits and 16 (4 bits) for 4-bit digits as literals");
 
 // Upfront read of the hybrid form.  fieldA[(digit of bits 16-23) * 8 + position region] and bucket[key >> bucket_shift] (global, zero on
 // entry) receive the counts.  Grid-stride over chunks of 4096 keys, two register buffers, non-temporal loads (as stage 1 of the

@@ -36,12 +36,20 @@
 //      growing the LDS footprint.
 //   6. key/value: the payload takes the same LDS slot and the same dst.
 //
+// Where things are: the sizes and the LDS carve-up in ScatterShape (the launcher reads its word count from there too), the
+// s_misc scratch words as kMisc* constants, the heavy-digit helpers pick_heavy / row_is_heavy as free functions, the
+// diagnostic stamps in phase_stats.hpp.  The phases themselves are one function body with lambdas, on purpose: every cut
+// that was tried -- even digit_of, leaving and clear_next as functions with explicit arguments -- changed the compiled
+// kernels (registers, scratch; profiles/scatter_refactor/compare.txt).  The compiler simplifies a function before it inlines
+// it and a lambda's captures after, and the two do not meet.  A cut is accepted when tools/isa_diff.py says `same`.
+//
 // Tail tile: missing keys are 0xFFFFFFFF; they carry the highest digit any key of the tile can have (H - 1 for a bit
 // field, the number of live splitters under the splitter partition) and the highest positions, so they sort to the end of
 // the tile and are neither counted nor stored.
 #pragma once
 #include "lsd_device.hpp"
 #include "lsd_kernels.hpp"
+#include "phase_stats.hpp"
 #include <cstdio>
 #include <type_traits>
 #include <hip/hip_ext.h>
@@ -54,32 +62,6 @@ __device__ __forceinline__ void lds_barrier()
 {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
-
-// Diagnostic build only (make STATS=1 -> liblsdsort_stats.so, never the product): wave 0 of every
-// tile stamps s_memrealtime (100 MHz) at phase boundaries and adds the differences to
-// a per-tile record p.stats[tile][0..6]; [7] look-back refills, [8] empty polls (thread 0's digit).
-constexpr int kStatsStride = 16;   // [0..6] phases, [7] refills, [8] empty polls, [9] start, [10] rows walked,
-                                   // [11] t(prefix stored), [12] t(prefix met), [13] chain pos it was met at, [14] t(walk start), [15] t(first step consumed)
-#ifdef LSD_PHASE_STATS
-#define LSD_SET(idx, v)                                                                     \
-    do {                                                                                    \
-        if (p.stats) p.stats[(size_t)stat_row__ * kStatsStride + (idx)] = (unsigned long long)(v); \
-    } while (0)
-#define LSD_STAMP(idx)                                                                      \
-    do {                                                                                    \
-        const unsigned long long now__ = __builtin_amdgcn_s_memrealtime();                  \
-        if (tid == 0 && p.stats) p.stats[(size_t)stat_row__ * kStatsStride + (idx)] = now__ - stamp__; \
-        stamp__ = now__;                                                                    \
-    } while (0)
-#define LSD_COUNT(idx, v)                                                                   \
-    do {                                                                                    \
-        if (p.stats) p.stats[(size_t)stat_row__ * kStatsStride + (idx)] += (unsigned long long)(v);   \
-    } while (0)
-#else
-#define LSD_STAMP(idx) do { } while (0)
-#define LSD_COUNT(idx, v) do { } while (0)
-#define LSD_SET(idx, v) do { } while (0)
-#endif
 
 // Register budget: a K=16 tile at 73 VGPRs lands exactly on the 6-waves-per-SIMD step, where a
 // third 512-thread workgroup only fits a CU when every SIMD happens to have two free slots; in
@@ -108,15 +90,80 @@ struct Lookback {
     static constexpr int LDS_WORDS = (SLOTS - 1) * LB * H;
 };
 
+// The s_misc scratch words of a workgroup.
+constexpr int kMiscWaveTotal = 1;      // [1 + wave], wave < 16: the waves' totals of the digit scan
+constexpr int kMiscClaimStart = 24;    // [24..29] the claimed tile: its region's first key,
+constexpr int kMiscClaimLen = 25;      //          the region's length,
+constexpr int kMiscClaimRow0 = 26;     //          the region's first status row,
+constexpr int kMiscClaimRegion = 28;   //          the region (kNoTile: none left),
+constexpr int kMiscClaimTicket = 29;   //          the ticket = the tile's position in the region's chain
+constexpr int kMiscGiveUp = 30;        // "this tile stores nothing" (look-back expiry, destination guard)
+constexpr int kMiscWords = 32;
+constexpr uint32_t kNoTile = 0xFFFFFFFFu;
+
+// Sizes and the LDS carve-up of one tile shape: the kernel and its launcher both read them here.
+template <int R, int T, int K, int CAP, int RANK>
+struct ScatterShape {
+    static constexpr int H = 1 << R;
+    static constexpr int W = T / kWave;
+    static constexpr int TILE = T * K;
+    static constexpr int ROUNDS = TILE / CAP;        // the LDS reorder buffer holds CAP keys at a time
+    static constexpr int SLOTS = CAP / T;            // read-back slots per thread per round
+    static constexpr int LB = Lookback<R, T, K>::LB;          // status rows per thread per look-back step
+    static constexpr int LSLOTS = Lookback<R, T, K>::SLOTS;   // thread slots sharing the first step
+    static_assert(T % kWave == 0 && H <= T, "one thread per digit in the tile scan");
+    static_assert(TILE % CAP == 0 && CAP % T == 0 && (CAP & (CAP - 1)) == 0, "rounds must tile the tile");
+    static_assert(kMiscWaveTotal + W <= kMiscClaimStart, "the wave totals end below the claimed tile");
+    // LDS, in uint32 words: keys [CAP], overlaid by the kRankLdsOr tables ([W][H] 64-bit masks) | counters [W][H] | gdelta [H] |
+    // misc [kMiscWords] | look [LSLOTS - 1][LB][H]
+    static constexpr int KEYS_WORDS = CAP;
+    static constexpr int TAB_WORDS = RANK == kRankLdsOr ? W * H * 2 : 0;
+    static constexpr int BUF_WORDS = KEYS_WORDS > TAB_WORDS ? KEYS_WORDS : TAB_WORDS;
+    static constexpr int CNT_AT = BUF_WORDS;
+    static constexpr int GDELTA_AT = CNT_AT + W * H;
+    static constexpr int MISC_AT = GDELTA_AT + H;
+    static constexpr int LOOK_AT = MISC_AT + kMiscWords;
+    static constexpr int LDS_WORDS = LOOK_AT + Lookback<R, T, K>::LDS_WORDS;
+};
+
 template <int R, int T, int K, int CAP, int RANK>
 constexpr int rank_scatter_lds_words()
 {
-    constexpr int H = 1 << R;
-    constexpr int W = T / kWave;
-    constexpr int keys_words = CAP;
-    constexpr int tab_words = RANK == kRankLdsOr ? W * H * 2 : 0;
-    constexpr int buf = keys_words > tab_words ? keys_words : tab_words;
-    return buf + W * H + H + 32 + Lookback<R, T, K>::LDS_WORDS;
+    return ScatterShape<R, T, K, CAP, RANK>::LDS_WORDS;
+}
+
+// Heavy digit values of a wave row (see the rank phase): h1 = the value of lane 0 or of lane 32, whichever more lanes
+// share, if at least kHeavy lanes do (a quarter of the wave: below that the atomics cost less than the care);
+// h2 = the first value in the row that differs from it (kNoDigit if there is none).
+constexpr uint32_t kHeavy = 16;
+constexpr uint32_t kNoDigit = 0xFFFFFFFFu;
+__device__ __forceinline__ bool pick_heavy(uint32_t d, uint32_t d_last, uint32_t& h1, uint32_t& h2)
+{
+    const uint32_t a = __builtin_amdgcn_readfirstlane(d), b = (uint32_t)__builtin_amdgcn_readlane((int)d, 32);
+    const uint64_t ma = __ballot(d == a), mb = __ballot(d == b);
+    const uint32_t na = popc64_add(ma, 0u), nb = popc64_add(mb, 0u);
+    if ((na > nb ? na : nb) < kHeavy) return false;
+    h1 = na >= nb ? a : b;
+    const uint64_t rest = ~(na >= nb ? ma : mb);
+    h2 = rest != 0ull ? (uint32_t)__builtin_amdgcn_readlane((int)d, (int)__builtin_ctzll(rest)) : kNoDigit;
+    // a second value is worth its ballots only if it is frequent as well (eight lanes of the row); otherwise its
+    // few holders take their atomics like everybody else and the careful loop counts ONE value
+    if (h2 != kNoDigit && popc64_add(__ballot(d == h2), 0u) < 8u) h2 = kNoDigit;
+    // Runs (sorted input, or the hybrid form's passes on position-correlated high bits: 4096 keys of one digit in a row, a
+    // wave holds 2048): the first row knows only the run the wave STARTS in; half of the waves end in the next one, whose keys
+    // would all take the same atomic, 64 lanes on one word, row after row (round 3: 10.7 us of rank phase per tile instead
+    // of 3.2).  The wave's last key names that second value.
+    if (h2 == kNoDigit) {
+        const uint32_t z = (uint32_t)__builtin_amdgcn_readlane((int)d_last, 63);
+        if (z != h1) h2 = z;
+    }
+    return true;
+}
+__device__ __forceinline__ bool row_is_heavy(uint32_t d)
+{
+    const uint32_t a = __builtin_amdgcn_readfirstlane(d), b = (uint32_t)__builtin_amdgcn_readlane((int)d, 32);
+    const uint32_t na = popc64_add(__ballot(d == a), 0u), nb = popc64_add(__ballot(d == b), 0u);
+    return (na > nb ? na : nb) >= kHeavy;
 }
 
 // XF: this launch may carry a key transform (PassParams::xin on a sort's first pass, ::xout on its last);
@@ -125,22 +172,9 @@ template <int R, int T, int K, int CAP, int RANK, bool PAIRS, bool CHAINED, bool
 __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_kernel(const PassParams p)
 {
     if (CHAINED && p.plan_first && p.plan[0] == 2u) return;   // uniform (PassParams::plan_first)
-#ifdef LSD_PHASE_STATS
-    unsigned long long stamp__ = __builtin_amdgcn_s_memrealtime();
-    uint32_t stat_row__ = 0;   // status row of the tile being stamped
-#endif
-    constexpr int H = 1 << R;
-    constexpr int W = T / kWave;
-    constexpr int TILE = T * K;
-    constexpr int ROUNDS = TILE / CAP;        // the LDS reorder buffer holds CAP keys at a time
-    constexpr int SLOTS = CAP / T;            // read-back slots per thread per round
-    constexpr int KEYS_WORDS = CAP;
-    constexpr int TAB_WORDS = RANK == kRankLdsOr ? W * H * 2 : 0;
-    constexpr int BUF_WORDS = KEYS_WORDS > TAB_WORDS ? KEYS_WORDS : TAB_WORDS;
-    constexpr int LB = Lookback<R, T, K>::LB;          // status rows per thread per look-back step
-    constexpr int LSLOTS = Lookback<R, T, K>::SLOTS;   // thread slots sharing the first step
-    static_assert(T % kWave == 0 && H <= T, "one thread per digit in the tile scan");
-    static_assert(TILE % CAP == 0 && CAP % T == 0 && (CAP & (CAP - 1)) == 0, "rounds must tile the tile");
+    LSD_STATS_BEGIN(st, p, threadIdx.x);
+    using S = ScatterShape<R, T, K, CAP, RANK>;
+    constexpr int H = S::H, W = S::W, TILE = S::TILE, ROUNDS = S::ROUNDS, SLOTS = S::SLOTS, LB = S::LB, LSLOTS = S::LSLOTS;
 
     // Explicit LDS (address space 3) pointers: the volatile accesses below would otherwise be
     // lowered to flat_* instructions (address-space inference skips volatile operations).
@@ -148,10 +182,10 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
     lds_u32* const s_base = (lds_u32*)smem;
     lds_u32* const s_keys = s_base;                                   // [CAP]    (phase 5/6, one round at a time)
     volatile lds_u64* const s_tab = (volatile lds_u64*)smem;          // [W][H]   (phase 2, kRankLdsOr, overlays s_keys)
-    volatile lds_u32* const s_cnt = (volatile lds_u32*)(s_base + BUF_WORDS);  // [W][H] counters, then wave bases
-    lds_u32* const s_gdelta = s_base + BUF_WORDS + W * H;             // [H] global base - local offset
-    lds_u32* const s_misc = s_gdelta + H;                             // [1..17] wave totals, [24..29] claimed tile
-    lds_u32* const s_look = s_misc + 32;                              // [LSLOTS-1][LB][H] first-step status rows
+    volatile lds_u32* const s_cnt = (volatile lds_u32*)(s_base + S::CNT_AT);  // [W][H] counters, then wave bases
+    lds_u32* const s_gdelta = s_base + S::GDELTA_AT;                  // [H] global base - local offset
+    lds_u32* const s_misc = s_base + S::MISC_AT;                      // kMisc* above
+    lds_u32* const s_look = s_base + S::LOOK_AT;                          // [LSLOTS-1][LB][H] first-step status rows
 
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -175,38 +209,6 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
     auto leaving = [&](uint32_t k) -> uint32_t {
         if constexpr (XF) return undo ? from_sortable(k, p.xout) : k;
         return k;
-    };
-
-    // Heavy digit values of a wave row (see the rank phase): h1 = the value of lane 0 or of lane 32, whichever more lanes
-    // share, if at least kHeavy lanes do (a quarter of the wave: below that the atomics cost less than the care);
-    // h2 = the first value in the row that differs from it (kNoDigit if there is none).
-    constexpr uint32_t kHeavy = 16;
-    constexpr uint32_t kNoDigit = 0xFFFFFFFFu;
-    auto pick_heavy = [&](uint32_t d, uint32_t d_last, uint32_t& h1, uint32_t& h2) -> bool {
-        const uint32_t a = __builtin_amdgcn_readfirstlane(d), b = (uint32_t)__builtin_amdgcn_readlane((int)d, 32);
-        const uint64_t ma = __ballot(d == a), mb = __ballot(d == b);
-        const uint32_t na = popc64_add(ma, 0u), nb = popc64_add(mb, 0u);
-        if ((na > nb ? na : nb) < kHeavy) return false;
-        h1 = na >= nb ? a : b;
-        const uint64_t rest = ~(na >= nb ? ma : mb);
-        h2 = rest != 0ull ? (uint32_t)__builtin_amdgcn_readlane((int)d, (int)__builtin_ctzll(rest)) : kNoDigit;
-        // a second value is worth its ballots only if it is frequent as well (eight lanes of the row); otherwise its
-        // few holders take their atomics like everybody else and the careful loop counts ONE value
-        if (h2 != kNoDigit && popc64_add(__ballot(d == h2), 0u) < 8u) h2 = kNoDigit;
-        // Runs (sorted input, or the hybrid form's passes on position-correlated high bits: 4096 keys of one digit in a row, a
-        // wave holds 2048): the first row knows only the run the wave STARTS in; half of the waves end in the next one, whose keys
-        // would all take the same atomic, 64 lanes on one word, row after row (round 3: 10.7 us of rank phase per tile instead
-        // of 3.2).  The wave's last key names that second value.
-        if (h2 == kNoDigit) {
-            const uint32_t z = (uint32_t)__builtin_amdgcn_readlane((int)d_last, 63);
-            if (z != h1) h2 = z;
-        }
-        return true;
-    };
-    auto row_is_heavy = [&](uint32_t d) -> bool {
-        const uint32_t a = __builtin_amdgcn_readfirstlane(d), b = (uint32_t)__builtin_amdgcn_readlane((int)d, 32);
-        const uint32_t na = popc64_add(__ballot(d == a), 0u), nb = popc64_add(__ballot(d == b), 0u);
-        return (na > nb ? na : nb) >= kHeavy;
     };
 
     // Housekeeping for the NEXT pass (it runs in the other status array): the grid's workgroups share the
@@ -241,7 +243,7 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
 
     // "this tile stores nothing": set by a digit thread whose look-back gives up (bounded spin) or whose destinations
     // would leave the output (destination guard), both below; read by everybody behind the look-back's barrier
-    if (tid == 0) s_misc[30] = 0;
+    if (tid == 0) s_misc[kMiscGiveUp] = 0;
 
     uint32_t tile;             // row of this tile in the status array
     uint32_t chain_pos = 0;    // position in its region's chain (chained form)
@@ -308,24 +310,24 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
                 }
             }
             if (lane == winner) {   // no lane when there is no tile left
-                s_misc[24] = r_start;
-                s_misc[25] = r_len;
-                s_misc[26] = row0;
-                s_misc[29] = my_ticket;
-                s_misc[28] = x;
+                s_misc[kMiscClaimStart] = r_start;
+                s_misc[kMiscClaimLen] = r_len;
+                s_misc[kMiscClaimRow0] = row0;
+                s_misc[kMiscClaimTicket] = my_ticket;
+                s_misc[kMiscClaimRegion] = x;
             }
-            if (winner == 64u && lane == 0) s_misc[28] = 0xFFFFFFFFu;
+            if (winner == 64u && lane == 0) s_misc[kMiscClaimRegion] = kNoTile;
         }
         __syncthreads();
-        region = __builtin_amdgcn_readfirstlane(s_misc[28]);
-        if (region == 0xFFFFFFFFu) {         // uniform: the grid is an upper bound on the tile count
+        region = __builtin_amdgcn_readfirstlane(s_misc[kMiscClaimRegion]);
+        if (region == kNoTile) {         // uniform: the grid is an upper bound on the tile count
             if (plan_skip != 2u) clear_next();   // 2: the other form of the sort runs (hybrid.hip); this pass owns nothing
             return;
         }
-        chain_pos = __builtin_amdgcn_readfirstlane(s_misc[29]);
-        const uint32_t r_start = __builtin_amdgcn_readfirstlane(s_misc[24]);
-        const uint32_t r_len = __builtin_amdgcn_readfirstlane(s_misc[25]);
-        chain_row0 = __builtin_amdgcn_readfirstlane(s_misc[26]);
+        chain_pos = __builtin_amdgcn_readfirstlane(s_misc[kMiscClaimTicket]);
+        const uint32_t r_start = __builtin_amdgcn_readfirstlane(s_misc[kMiscClaimStart]);
+        const uint32_t r_len = __builtin_amdgcn_readfirstlane(s_misc[kMiscClaimLen]);
+        chain_row0 = __builtin_amdgcn_readfirstlane(s_misc[kMiscClaimRow0]);
         tile = chain_row0 + chain_pos;
         tile_base = r_start + chain_pos * (uint32_t)TILE;
         range_end = r_start + r_len;
@@ -369,17 +371,7 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
         return swapped ? const_cast<uint32_t*>(p.more_in[e - 1]) : p.more_out[e - 1];
     };
     const uint32_t num_payloads = PAIRS ? (p.num_payloads > 1u ? p.num_payloads : 1u) : 0u;   // uniform
-#ifdef LSD_PHASE_STATS
-    stat_row__ = tile;
-    if (tid == 0 && p.stats) {
-        p.stats[(size_t)stat_row__ * kStatsStride + 9] = stamp__;
-        // counters are per pass: the rows are reused by every pass of a sort
-        p.stats[(size_t)stat_row__ * kStatsStride + 7] = 0;
-        p.stats[(size_t)stat_row__ * kStatsStride + 8] = 0;
-        p.stats[(size_t)stat_row__ * kStatsStride + 10] = 0;
-    }
-    LSD_STAMP(0);   // ticket
-#endif
+    LSD_STATS_TILE(st, tile);   // ticket
 
     const uint32_t remaining = range_end - tile_base;
     const uint32_t valid = remaining < (uint32_t)TILE ? remaining : (uint32_t)TILE;
@@ -438,10 +430,7 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
     }
 
     // ---- 2. intra-wave stable rank ----------------------------------------------------------
-#ifdef LSD_PHASE_STATS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    LSD_STAMP(1);   // key load
-#endif
+    LSD_STAMP_DRAINED(st, 1);   // key load
     if (ranked) {
         // done above
     } else if (RANK == kRankLdsAdd) {
@@ -518,7 +507,7 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
         }
     }
     __syncthreads();
-    LSD_STAMP(2);   // rank + barrier
+    LSD_STAMP(st, 2);   // rank + barrier
 
     // ---- 3. per-wave bases, tile digit totals, local offsets -------------------------------
     uint32_t total = 0;
@@ -573,13 +562,13 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
 
     uint32_t incl = wave_inclusive_scan(tid < (uint32_t)H ? total : 0u);
     if (H > kWave) {
-        if (lane == 63u) s_misc[1 + wave] = incl;
+        if (lane == 63u) s_misc[kMiscWaveTotal + wave] = incl;
         lds_barrier();
         // all wave totals are read as one batch and selected afterwards: a read per `if` is a basic block of its own
         // with its own lgkmcnt(0), i.e. H / 64 dependent LDS round trips on the tile's critical path
         uint32_t part[(H / kWave) > 0 ? H / kWave : 1];
 #pragma unroll
-        for (int w = 0; w < H / kWave; w++) part[w] = s_misc[1 + w];
+        for (int w = 0; w < H / kWave; w++) part[w] = s_misc[kMiscWaveTotal + w];
         uint32_t carry = 0;
 #pragma unroll
         for (int w = 0; w < H / kWave; w++) carry += (uint32_t)w < wave ? part[w] : 0u;
@@ -591,7 +580,7 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
         for (int w = 0; w < W; w++) s_cnt[w * H + tid] = local_off + wave_excl[w];
     }
     lds_barrier();
-    LSD_STAMP(3);   // totals, publish, scan, bases
+    LSD_STAMP(st, 3);   // totals, publish, scan, bases
 
     // Payload loads.  With a single reorder round they are issued only after the keys have gone to
     // LDS (below), so a payload never shares the register file with a live key: 2 registers per
@@ -660,7 +649,7 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
         // batches it LOSES 0.9 % (kernel 1.9 %) -- the slots' LDS reads overlap the stores anyway, and the 32 registers it
         // holds across the look-back are better spent there; with two workgroups per CU the extra barrier cost 1.5 %.)
         if (round == 0) {
-            LSD_STAMP(4);   // first round's LDS writes
+            LSD_STAMP(st, 4);   // first round's LDS writes
             // ---- 4. tile base per digit ("global offsets", .cu:885-894) ----------------------------
             if (CHAINED && LSLOTS > 1) {
                 // the helper slots hand their share of the first step to the digit's owner
@@ -689,7 +678,7 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
                         // first step: own window, then the helper slots' rows, in chain order
                         int consumed = 0;
                         bool found = false;
-                        if (tid == 0) LSD_SET(14, __builtin_amdgcn_s_memrealtime());
+                        if (tid == 0) LSD_SET(st, 14, __builtin_amdgcn_s_memrealtime());
 #pragma unroll
                         for (int m = 0; m < LSLOTS * LB; m++) {
                             const uint32_t word = m < LB ? window[m] : s_look[(m - LB) * H + tid];
@@ -702,8 +691,8 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
                         }
                         j -= consumed;
                         if (tid == 0) {
-                            LSD_COUNT(10, consumed);
-                            LSD_SET(15, __builtin_amdgcn_s_memrealtime());   // first (prefetched) step consumed
+                            LSD_COUNT(st, 10, consumed);
+                            LSD_SET(st, 15, __builtin_amdgcn_s_memrealtime());   // first (prefetched) step consumed
                         }
                         uint32_t spins = 0;
                         bool gave_up = false;
@@ -722,7 +711,7 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
                                     found = (code == c_prefix) || (j - l == 0);
                                 }
                             }
-                            if (tid == 0) LSD_COUNT(7, 1);
+                            if (tid == 0) LSD_COUNT(st, 7, 1);
                             if (consumed == 0) {
                                 // Bounded wait.  On expiry: raise the fault word and give the tile up -- no prefix is
                                 // published from the partial sum and nothing of this tile is stored (below).  Every
@@ -734,18 +723,18 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
                                     break;
                                 }
                                 __builtin_amdgcn_s_sleep(1);
-                                if (tid == 0) LSD_COUNT(8, 1);
+                                if (tid == 0) LSD_COUNT(st, 8, 1);
                             }
                             j -= consumed;
-                            if (tid == 0) LSD_COUNT(10, consumed);
+                            if (tid == 0) LSD_COUNT(st, 10, consumed);
                         }
                         if (tid == 0) {
-                            LSD_SET(12, __builtin_amdgcn_s_memrealtime());
-                            LSD_SET(13, j + 1);
+                            LSD_SET(st, 12, __builtin_amdgcn_s_memrealtime());
+                            LSD_SET(st, 13, j + 1);
                         }
-                        if (gave_up) s_misc[30] = 1u;
+                        if (gave_up) s_misc[kMiscGiveUp] = 1u;
                         else if (!muted) store_status(p.status + (size_t)tile * H + tid, ((excl + pub_total) << 2) | c_prefix);
-                        if (tid == 0) LSD_SET(11, __builtin_amdgcn_s_memrealtime());
+                        if (tid == 0) LSD_SET(st, 11, __builtin_amdgcn_s_memrealtime());
                     }
                     gbase = region_base + excl;
                     run_end = (uint64_t)region_base + excl + pub_total;
@@ -761,14 +750,14 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
                 // nothing; its prefix is already published, so nobody behind it waits.
                 if (run_end > (uint64_t)p.n) {
                     if (p.fault) atomicOr(p.fault, 2u);
-                    s_misc[30] = 1u;
+                    s_misc[kMiscGiveUp] = 1u;
                 }
                 s_gdelta[tid] = gbase - local_off;
             }
         }
         lds_barrier();
-        if (round == 0) LSD_STAMP(5);   // look-back (wave 0's digits) + barrier
-        if (round == 0 && s_misc[30] != 0u) {   // the look-back gave up or the destination guard fired (uniform): the sort has
+        if (round == 0) LSD_STAMP(st, 5);   // look-back (wave 0's digits) + barrier
+        if (round == 0 && s_misc[kMiscGiveUp] != 0u) {   // the look-back gave up or the destination guard fired (uniform): the sort has
             clear_next();                       // failed (fault word set); store nothing from a base that is not known
             return;
         }
@@ -861,10 +850,7 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
     // in round 1, the compiler's vmcnt(0) at the join behind its store loop made the four waves that hold the digit threads
     // sit out these stores' acknowledgements before their first key store.)
     clear_next();
-#ifdef LSD_PHASE_STATS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    LSD_STAMP(6);   // read-back + stores drained
-#endif
+    LSD_STAMP_DRAINED(st, 6);   // read-back + stores drained
 }
 
 // Launch one instantiation.  LDS above 64 KiB needs the attribute raised once per function.
