@@ -6,6 +6,7 @@
 // form (tile_histograms_kernel).
 #include "lsd_device.hpp"
 #include "lsd_kernels.hpp"
+#include "stage1_stream.hpp"
 
 namespace lsd {
 
@@ -20,23 +21,6 @@ namespace lsd {
 constexpr int kHistThreads = 256;
 constexpr int kHistVecPerThread = 4;   // uint4 loads in flight per thread per iteration
 
-// Launch geometry of the kernels that stream the whole array (digit, bucket and joint histograms): chunks of THREADS uint4
-// loads, `per_block` chunks per workgroup and iteration.  16-byte loads need a 16-byte aligned base; otherwise there are no
-// chunks (vec_chunks == 0: a slice of a larger buffer) and every key goes through the kernels' grid-wide scalar loop.
-struct StreamGrid {
-    uint32_t vec_chunks;   // whole chunks of THREADS * 4 keys
-    uint32_t blocks;
-};
-static StreamGrid stream_grid(const uint32_t* keys, uint32_t n, uint32_t threads, uint32_t per_block, uint32_t max_blocks)
-{
-    const bool aligned = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0;
-    StreamGrid g;
-    g.vec_chunks = aligned ? n / (threads * 4) : 0;
-    g.blocks = aligned ? (g.vec_chunks + per_block - 1) / per_block : (n + threads * 16 - 1) / (threads * 16);
-    if (g.blocks > max_blocks) g.blocks = max_blocks;
-    if (g.blocks == 0) g.blocks = 1;
-    return g;
-}
 // Grid cap of the stage-1 kernels, in waves: enough to cover HBM latency (256 CUs x 8 workgroups of 256 threads, or 512
 // workgroups of 1024).
 constexpr uint32_t kHistGridWaves = 2048 * 4;
@@ -317,7 +301,6 @@ __global__ void __launch_bounds__(THREADS) joint_histograms_kernel(const uint32_
     // that hold a candidate value are counted in scalar registers (a compare and a population count per wave row, no LDS
     // operation), everybody else adds for itself.  A group without one takes the plain path; both paths count every key
     // exactly, the choice is speed only.
-    constexpr uint32_t kHeavyLanes = 16;
     constexpr uint32_t kNoCandidate = 0xFFFFFFFFu;   // never a slot
     // Software-pipelined with TWO register buffers that swap roles (the loop is unrolled by two): while one group of
     // 16-byte loads goes through the LDS atomics the next is in flight, and the wait in front of a group is a COUNTED one
@@ -328,7 +311,7 @@ __global__ void __launch_bounds__(THREADS) joint_histograms_kernel(const uint32_
     // FULL groups only and always loads: past its last group a workgroup reloads the group it already holds (an L2 hit)
     // and does not count it.  Chunks beyond the last full group go with the tail below.
     constexpr int VPT = kHistVecPerThread;
-    const uint32_t full_chunks = vec_chunks / VPT * VPT;
+    const uint32_t full_chunks = full_group_chunks<VPT>(vec_chunks);
     auto load_group = [&](uint32_t c, uint4 (&v)[VPT]) {
         // non-temporal loads: a read-only stream of them runs 8 % faster than plain ones (profiles/r3_ceilings.txt:
         // 5.67-5.88 against 5.24-5.40 TB/s), and the keys are not read again before 2 GiB of other traffic has
@@ -377,7 +360,7 @@ __global__ void __launch_bounds__(THREADS) joint_histograms_kernel(const uint32_
                 }
                 if (have1 && ~m != 0ull) {   // a second one: the first value that differs, if eight lanes hold it
                     const uint32_t other = (uint32_t)__builtin_amdgcn_readlane((int)k0, (int)__builtin_ctzll(~m));
-                    if ((uint32_t)__builtin_popcountll(__ballot(k0 == other)) >= 8u) {
+                    if ((uint32_t)__builtin_popcountll(__ballot(k0 == other)) >= kHeavySecondLanes) {
                         key2 = other;
                         have2 = true;
                     }
@@ -465,7 +448,7 @@ __global__ void __launch_bounds__(THREADS) joint_histograms_kernel(const uint32_
                         const unsigned long long rest = ~mf;
                         if (rest) {
                             const uint32_t other = (uint32_t)__builtin_amdgcn_readlane((int)a, (int)__builtin_ctzll(rest));
-                            if ((uint32_t)__builtin_popcountll(__ballot(a == other)) >= 8u) c2 = other;
+                            if ((uint32_t)__builtin_popcountll(__ballot(a == other)) >= kHeavySecondLanes) c2 = other;
                         }
                     }
                 }

@@ -20,6 +20,7 @@
 // Same stable rank, same kernels for the global passes; nothing here is derived from the reference's kernels.
 #include "lsd_device.hpp"
 #include "lsd_kernels.hpp"
+#include "stage1_stream.hpp"
 
 namespace lsd {
 
@@ -122,28 +123,28 @@ __global__ void __launch_bounds__(kHybridHistThreads) hybrid_histograms_kernel(c
     uint32_t key1 = 0, key2 = 0;   // sticky heavy-key candidates (uniform)
     bool have1 = false, have2 = false;
     auto count_group = [&](uint32_t c, uint4 (&v)[VPT]) {
-        // heavy keys: see joint_histograms_kernel (histograms.hip)
+        // heavy keys: see joint_histograms_kernel (histograms.hip); a change to this picker is a change to that one
         {
             const uint32_t k0 = v[0].x;
             const uint32_t n1 = (uint32_t)__builtin_popcountll(__ballot(k0 == key1));
-            if (!have1 || n1 < 16u) {
+            if (!have1 || n1 < kHeavyLanes) {
                 have1 = have2 = false;
                 const uint32_t a = __builtin_amdgcn_readfirstlane(k0);
                 unsigned long long m = __ballot(k0 == a);
-                if ((uint32_t)__builtin_popcountll(m) >= 16u) {
+                if ((uint32_t)__builtin_popcountll(m) >= kHeavyLanes) {
                     key1 = a;
                     have1 = true;
                 } else {
                     const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)k0, 32);
                     m = __ballot(k0 == b);
-                    if ((uint32_t)__builtin_popcountll(m) >= 16u) {
+                    if ((uint32_t)__builtin_popcountll(m) >= kHeavyLanes) {
                         key1 = b;
                         have1 = true;
                     }
                 }
                 if (have1 && ~m != 0ull) {
                     const uint32_t other = (uint32_t)__builtin_amdgcn_readlane((int)k0, (int)__builtin_ctzll(~m));
-                    if ((uint32_t)__builtin_popcountll(__ballot(k0 == other)) >= 8u) {
+                    if ((uint32_t)__builtin_popcountll(__ballot(k0 == other)) >= kHeavySecondLanes) {
                         key2 = other;
                         have2 = true;
                     }
@@ -182,7 +183,7 @@ __global__ void __launch_bounds__(kHybridHistThreads) hybrid_histograms_kernel(c
             // itself.  Uniform keys pay the two looks (a few scalar instructions per vector).
             {
                 const uint32_t a0 = slot_a(k4[0], region0), a_first = (uint32_t)__builtin_amdgcn_readfirstlane(a0);
-                if ((uint32_t)__builtin_popcountll(__ballot(a0 == a_first)) >= 16u) {
+                if ((uint32_t)__builtin_popcountll(__ballot(a0 == a_first)) >= kHeavyLanes) {
                     uint32_t held = 0;
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
@@ -197,7 +198,7 @@ __global__ void __launch_bounds__(kHybridHistThreads) hybrid_histograms_kernel(c
                     for (int q = 0; q < 4; q++) atomicAdd(&s_a[slot_a(k4[q], region0) + copy], 1u);
                 }
                 const uint32_t b0 = slot_b(k4[0]), b_first = (uint32_t)__builtin_amdgcn_readfirstlane(b0);
-                if ((uint32_t)__builtin_popcountll(__ballot(b0 == b_first)) >= 16u) {
+                if ((uint32_t)__builtin_popcountll(__ballot(b0 == b_first)) >= kHeavyLanes) {
                     uint32_t held = 0;
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
@@ -224,7 +225,8 @@ __global__ void __launch_bounds__(kHybridHistThreads) hybrid_histograms_kernel(c
                       : make_uint4(t.x, t.y, t.z, t.w);
         }
     };
-    const uint32_t full_chunks = vec_chunks / VPT * VPT;
+    // the loop of joint_histograms_kernel (histograms.hip: why its loads sit in one straight line and always run)
+    const uint32_t full_chunks = full_group_chunks<VPT>(vec_chunks);
     const uint32_t stride = gridDim.x * VPT;
     uint32_t c = blockIdx.x * VPT;
     if (c < full_chunks) {
@@ -270,51 +272,48 @@ __global__ void __launch_bounds__(kHybridHistThreads) hybrid_histograms_kernel(c
     }
 }
 
-hipError_t launch_hybrid_histograms(int radix_bits, const uint32_t* keys, uint32_t n, uint32_t region0_keys, uint32_t* field_a, uint32_t* bucket,
-                                    int bucket_bits, uint32_t* words, hipStream_t stream, const KeyTransform& xf)
+// One resident workgroup per CU, each flushing 34816 counters once: more workgroups would only flush more.
+constexpr uint32_t kHybridHistMaxBlocks = 256;
+
+struct HybridHistArgs {
+    const uint32_t* keys;
+    uint32_t n, region0_keys;
+    uint32_t *field_a, *bucket;
+    uint32_t bucket_shift;
+    uint32_t* words;
+    KeyTransform xf;
+};
+template <int R, bool XF, bool B16>
+static hipError_t launch_hybrid_hist_inst(const HybridHistArgs& a, hipStream_t stream)
 {
-    if (!words) return hipErrorInvalidValue;
-    if (bucket_bits < 11 || (1 << bucket_bits) > kHybridBuckets || (radix_bits != 8 && radix_bits != 4)) return hipErrorInvalidValue;
     constexpr int T = kHybridHistThreads;
     constexpr size_t lds_bytes = (size_t)(4096 + 32768) * sizeof(uint32_t);   // 2^15 bucket counters of 32 bits or 2^16 of 16
     static_assert(2048 * kHybridCopiesA == 4096, "both digit widths keep 4096 field counters");
     static_assert(lds_bytes <= 160 * 1024, "one workgroup per CU");
-    if (region0_keys == 0 || region0_keys % (T * 4) != 0) return hipErrorInvalidValue;
-    static std::atomic<uint64_t> told{0};
-    hipError_t attr = hipSuccess;
-    {
-        int dev = 0;
-        attr = hipGetDevice(&dev);
-        if (attr == hipSuccess && !(told.load(std::memory_order_acquire) & (1ull << (dev & 63)))) {
-#define LSD_K(R, XF, B16) reinterpret_cast<const void*>(hybrid_histograms_kernel<R, XF, B16>)
-            const void* kernels[8] = {LSD_K(8, false, false), LSD_K(8, true, false), LSD_K(4, false, false), LSD_K(4, true, false),
-                                      LSD_K(8, false, true),  LSD_K(8, true, true),  LSD_K(4, false, true),  LSD_K(4, true, true)};
-#undef LSD_K
-            for (const void* k : kernels) {
-                attr = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-                if (attr != hipSuccess) break;
-            }
-            if (attr == hipSuccess) told.fetch_or(1ull << (dev & 63), std::memory_order_release);
-        }
+    const StreamGrid g = stream_grid(a.keys, a.n, T, kHybridVpt, kHybridHistMaxBlocks);
+    return launch_dynamic_lds<hybrid_histograms_kernel<R, XF, B16>>(dim3(g.blocks), dim3(T), lds_bytes, stream, a.keys, a.n, a.region0_keys,
+                                                                    a.field_a, a.bucket, g.vec_chunks, a.words, a.bucket_shift, a.xf);
+}
+template <int R>
+static hipError_t launch_hybrid_hist_radix(bool typed, bool b16, const HybridHistArgs& a, hipStream_t stream)
+{
+    if (typed) return b16 ? launch_hybrid_hist_inst<R, true, true>(a, stream) : launch_hybrid_hist_inst<R, true, false>(a, stream);
+    return b16 ? launch_hybrid_hist_inst<R, false, true>(a, stream) : launch_hybrid_hist_inst<R, false, false>(a, stream);
+}
+
+hipError_t launch_hybrid_histograms(int radix_bits, const uint32_t* keys, uint32_t n, uint32_t region0_keys, uint32_t* field_a, uint32_t* bucket,
+                                    int bucket_bits, uint32_t* words, hipStream_t stream, const KeyTransform& xf)
+{
+    if (!words) return hipErrorInvalidValue;
+    if (bucket_bits < 11 || (1 << bucket_bits) > kHybridBuckets) return hipErrorInvalidValue;
+    if (region0_keys == 0 || region0_keys % (kHybridHistThreads * 4) != 0) return hipErrorInvalidValue;
+    const HybridHistArgs a{keys, n, region0_keys, field_a, bucket, 32u - (uint32_t)bucket_bits, words, xf};
+    const bool typed = xf.on != 0, b16 = bucket_bits == 16;
+    switch (radix_bits) {
+        case 8: return launch_hybrid_hist_radix<8>(typed, b16, a, stream);
+        case 4: return launch_hybrid_hist_radix<4>(typed, b16, a, stream);
+        default: return hipErrorInvalidValue;
     }
-    if (attr != hipSuccess) return attr;
-    const bool aligned = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0;
-    const uint32_t vec_chunks = aligned ? n / (T * 4) : 0;
-    // one resident workgroup per CU, each flushing 34816 counters once: more workgroups would only flush more
-    uint32_t blocks = aligned ? (vec_chunks + kHybridVpt - 1) / kHybridVpt : (n + T * 16 - 1) / (T * 16);
-    if (blocks > 256) blocks = 256;
-    if (blocks == 0) blocks = 1;
-#define LSD_HYB_HIST(R, XF, B16) hipLaunchKernelGGL((hybrid_histograms_kernel<R, XF, B16>), dim3(blocks), dim3(T), lds_bytes, stream, keys, n, region0_keys, field_a, bucket, vec_chunks, words, 32u - (uint32_t)bucket_bits, xf)
-    const bool general = xf.on != 0, b16 = bucket_bits == 16;
-    if (radix_bits == 8) {
-        if (b16) { if (general) LSD_HYB_HIST(8, true, true); else LSD_HYB_HIST(8, false, true); }
-        else     { if (general) LSD_HYB_HIST(8, true, false); else LSD_HYB_HIST(8, false, false); }
-    } else {
-        if (b16) { if (general) LSD_HYB_HIST(4, true, true); else LSD_HYB_HIST(4, false, true); }
-        else     { if (general) LSD_HYB_HIST(4, true, false); else LSD_HYB_HIST(4, false, false); }
-    }
-#undef LSD_HYB_HIST
-    return hipGetLastError();
 }
 
 // The planner: one workgroup.  From the bucket counts: the verdict (largest bucket <= kLocalSortCap and the counts sum to n),

@@ -99,6 +99,25 @@ hipError_t launch_dynamic_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream
     return hipGetLastError();
 }
 
+// Launch geometry of the kernels that stream the whole array (digit, bucket and joint histograms, the hybrid form's upfront
+// read): chunks of THREADS uint4 loads, `per_block` chunks per workgroup and iteration.  16-byte loads need a 16-byte aligned
+// base; otherwise there are no chunks (vec_chunks == 0: a slice of a larger buffer) and every key goes through the kernels'
+// grid-wide scalar loop.
+struct StreamGrid {
+    uint32_t vec_chunks;   // whole chunks of THREADS * 4 keys
+    uint32_t blocks;
+};
+inline StreamGrid stream_grid(const uint32_t* keys, uint32_t n, uint32_t threads, uint32_t per_block, uint32_t max_blocks)
+{
+    const bool aligned = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0;
+    StreamGrid g;
+    g.vec_chunks = aligned ? n / (threads * 4) : 0;
+    g.blocks = aligned ? (g.vec_chunks + per_block - 1) / per_block : (n + threads * 16 - 1) / (threads * 16);
+    if (g.blocks > max_blocks) g.blocks = max_blocks;
+    if (g.blocks == 0) g.blocks = 1;
+    return g;
+}
+
 // Set (per host thread) around a rank-and-scatter launch by lsdsort_u32_device_timed: events that
 // receive the kernel's own begin and end timestamps (hipExtLaunchKernelGGL).
 inline thread_local hipEvent_t t_launch_start = nullptr;

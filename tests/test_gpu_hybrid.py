@@ -145,6 +145,34 @@ def test_hybrid_pairs_are_stable(gpu, n):
         del keys, expect
 
 
+@pytest.mark.parametrize("radix,pairs,n", [(4, False, (1 << 24) + 4099), (8, True, 24_000_000)])
+@pytest.mark.parametrize("skip", [0, 1])
+def test_sorted_runs_of_64_take_the_hybrid_form(gpu, radix, pairs, n, skip):
+    """The smallest sizes at which the form is tried (2^24 items at 4-bit digits, 2.2e7 pairs at 8-bit digits), on keys that
+    steer what the upfront read has in common with stage 1 of the ordinary form INSIDE the hybrid kernel: sorted keys in runs of 64, key[i] =
+    (i // 64) * floor(2^32 / runs) -- every wave's 64 first keys are equal (the sticky heavy-key picker, heavy fields in every
+    vector), the keys span all 32 bits (no prefix), a bucket of the 2^14 holds some 1000 .. 1500 keys and the sample's neighbours
+    lie 16 buckets apart, so the form must be TAKEN: a miscount would otherwise only make the planner say no and hide behind the
+    ordinary passes.  skip = 1: the same keys from a base 4 bytes past a 16-byte boundary -- no 16-byte chunks, every key
+    through the kernel's tail loop.  Pairs: payload = input position, which must stay in input order among equal keys."""
+    import torch
+
+    runs = (n + 63) // 64
+    whole = _i32((torch.arange(n + skip, device="cuda", dtype=torch.int64) - skip).clamp(min=0) // 64 * ((1 << 32) // runs))
+    d = whole[skip:]
+    assert d.data_ptr() % 16 == 4 * skip and d.is_contiguous()
+    keys = d.clone()
+    expect = torch.sort(_u64(keys), stable=True)
+    v = torch.arange(n, dtype=torch.int32, device="cuda") if pairs else None
+    ws = gpu.alloc_workspace(n, radix, pairs)
+    gpu.GPULSDRadixSort(d, radix, d_vals=v, workspace=ws)          # raises unless the status is OK
+    assert gpu.lib().lsdsort_check_device(ws.data_ptr(), torch.cuda.current_stream().cuda_stream) == 0
+    assert gpu.workspace_form(ws) == 1, "the hybrid form was refused"
+    assert torch.equal(_u64(d), expect.values)
+    if pairs:
+        assert torch.equal(v.to(torch.int64), expect.indices), "order among equal keys"
+
+
 def test_hybrid_is_not_tried_outside_its_range(gpu):
     """Below 3.8e7 keys at 8-bit digits (2.2e7 pairs, 2^24 items at 4-bit digits) and at 1- and 2-bit digits the ordinary form runs."""
     import torch
