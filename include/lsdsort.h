@@ -180,6 +180,39 @@ LSDSORT_API int lsdsort_keys64_device(void* d_keys, void* d_vals, int val_bits /
                                       size_t workspace_bytes, size_t n, int radix_bits, int key_type, int descending,
                                       void* hip_stream);
 
+/* 16-bit keys: uint16, int16, float16, bfloat16 (no reference counterpart, .cu:62; lsdradixsort_amd/csrc/keys16.hip).  In place,
+ * stream-ordered, nothing allocated, no host synchronisation, every launch sized from n alone: capturable in a graph
+ * (lsdsort_prepare_device first).  The sortable 16-bit value t of key k: uint16 t = k; int16 t = k ^ 0x8000; float16 and bfloat16
+ * (one map: both are sign-magnitude; the two enumerators are kept apart so that callers say what they have) t = ~k where the sign
+ * bit is set, k ^ 0x8000 otherwise -- IEEE total order, -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN; descending: t = ~t
+ * afterwards.  The map is applied where a key is read; the raw key is what is stored.
+ *   d_vals == NULL : keys only.  A 16-bit key has 65536 values, so from a measured size on (the automatic rule) the sort is a
+ *                    COUNT of the values into 65536 counters, a scan of the counters and a FILL of d_keys with runs: one read of
+ *                    the keys per half of the value range and one write, no key is moved (equal 16-bit keys are the same bits).
+ *                    Smaller sorts take the widen route below.
+ *   d_vals given   : the 32-bit payloads are permuted with the keys, stable in either direction (equal keys keep their input
+ *                    order).  WIDEN route: the keys are mapped to uint32 with t in the low half-word, lsdsort_pairs_u32_device
+ *                    (keys only: lsdsort_u32_device) runs on them inside this call's workspace -- its pass skipping drops the two
+ *                    dead high passes on the device, the payloads are sorted where they lie -- and one kernel narrows and un-maps.
+ * d_keys needs 2-byte alignment only: 16-byte accesses are used from the first 16-byte line on, the keys in front of it and behind
+ * the last whole line go one by one.  Checks, in order, each before a device is touched: key_type (INVALID_ARG), n above
+ * LSDSORT_MAX_KEYS (TOO_LARGE), n == 0 (OK, nothing launched), a NULL (or odd) d_keys (INVALID_ARG), the workspace (WORKSPACE: NULL,
+ * not 256-byte aligned, or below lsdsort_keys16_workspace_bytes(n, d_vals != NULL)), the device (NO_DEVICE).
+ * lsdsort_keys16_workspace_bytes is a multiple of 256, monotonic in n, covers BOTH routes (a workspace serves whichever the library
+ * picks) and is 0 for pairs outside {0, 1} or n above the limit.
+ * lsdsort_set_keys16_route: -1 the automatic rule (default), 0 always widen, 1 count wherever it applies (keys only); process-wide
+ * like the other setters, anything else is INVALID_ARG.  It exists so that both routes can be tested at small sizes.
+ * lsdsort_keys16_check_device reads the call's fault word -- set by the fill kernel where the scanned total is not n, or taken over
+ * from the sort inside the widen route -- and synchronises the stream. */
+typedef enum lsdsort_key16_type {
+    LSDSORT_KEY16_U16 = 0, LSDSORT_KEY16_I16 = 1, LSDSORT_KEY16_F16 = 2, LSDSORT_KEY16_BF16 = 3
+} lsdsort_key16_type;
+LSDSORT_API size_t lsdsort_keys16_workspace_bytes(size_t n, int pairs /* 0 | 1 */);
+LSDSORT_API int lsdsort_keys16_device(void* d_keys, uint32_t* d_vals, void* d_workspace, size_t workspace_bytes, size_t n,
+                                      int key_type, int descending, void* hip_stream);
+LSDSORT_API int lsdsort_keys16_check_device(void* d_workspace, size_t n, int pairs, void* hip_stream);
+LSDSORT_API int lsdsort_set_keys16_route(int route);   /* -1 auto (default), 0 widen, 1 count */
+
 /* Segmented sort (no reference counterpart; the counterpart of DeviceSegmentedRadixSort and of torch.sort(x, dim=-1) on rows).
  * Segment s = keys[d_offsets[s] .. d_offsets[s+1]) for s < num_segments; each segment is sorted in place,
  * independently, stable; d_vals (may be NULL) is permuted with the keys.  d_offsets: num_segments + 1 ascending

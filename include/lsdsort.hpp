@@ -112,6 +112,23 @@ inline void sort_records_device(Key* d_keys, Val* d_vals, void* d_workspace, siz
                                 detail::key64_type(d_keys), descending ? 1 : 0, hip_stream), "lsdsort_keys64_device");
 }
 
+// 16-bit keys (lsdsort_keys16_device): uint16_t or int16_t by overload; float16 and bfloat16 have no standard C++ type, so their
+// bits are passed as uint16_t with the key type named.  Workspace of keys16_workspace_bytes(n, pairs).  Keys only: large sorts
+// count the 65536 values instead of moving keys.  With d_vals: stable, descending too.
+inline size_t keys16_workspace_bytes(size_t n, bool pairs = false) { return lsdsort_keys16_workspace_bytes(n, pairs ? 1 : 0); }
+inline void sort16_device(uint16_t* d_keys, void* d_workspace, size_t workspace_bytes_, size_t n, bool descending = false,
+                          uint32_t* d_vals = nullptr, lsdsort_key16_type key_type = LSDSORT_KEY16_U16, void* hip_stream = nullptr)
+{
+    check(lsdsort_keys16_device(d_keys, d_vals, d_workspace, workspace_bytes_, n, key_type, descending ? 1 : 0, hip_stream),
+          "lsdsort_keys16_device");
+}
+inline void sort16_device(int16_t* d_keys, void* d_workspace, size_t workspace_bytes_, size_t n, bool descending = false,
+                          uint32_t* d_vals = nullptr, void* hip_stream = nullptr)
+{
+    check(lsdsort_keys16_device(d_keys, d_vals, d_workspace, workspace_bytes_, n, LSDSORT_KEY16_I16, descending ? 1 : 0, hip_stream),
+          "lsdsort_keys16_device");
+}
+
 // Many independent segments of one array, each sorted in place and stable (lsdsort_segmented_device): segment s =
 // d_keys[d_offsets[s] .. d_offsets[s + 1]), d_offsets on the device.  Malformed offsets: lsdsort_check_device afterwards.
 inline size_t segmented_workspace_bytes(size_t n, size_t num_segments, bool pairs = false)

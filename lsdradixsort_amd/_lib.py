@@ -77,6 +77,10 @@ SIGNATURES = {
     "lsdsort_keys64_device": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_int, ctypes.c_void_p, c_size, c_size, c_int, c_int, c_int,
                                       ctypes.c_void_p]),
     "lsdsort_wide_check_device": (c_int, [ctypes.c_void_p, c_size, c_int, c_int, c_int, ctypes.c_void_p]),
+    "lsdsort_keys16_workspace_bytes": (c_size, [c_size, c_int]),
+    "lsdsort_keys16_device": (c_int, [ctypes.c_void_p, c_u32p, ctypes.c_void_p, c_size, c_size, c_int, c_int, ctypes.c_void_p]),
+    "lsdsort_keys16_check_device": (c_int, [ctypes.c_void_p, c_size, c_int, ctypes.c_void_p]),
+    "lsdsort_set_keys16_route": (c_int, [c_int]),
     "lsdsort_check_device": (c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "lsdsort_segmented_workspace_bytes": (c_size, [c_size, c_size, c_int]),
     "lsdsort_segmented_device": (c_int, [ctypes.c_void_p, c_u32p, ctypes.c_void_p, c_size, c_size, c_int, c_int, ctypes.c_void_p,

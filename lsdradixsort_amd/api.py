@@ -14,13 +14,14 @@ import numpy as np
 
 from . import errors
 from ._lib import LsdsortTiming, lib
-from .errors import KEY_TYPES_32, KEY_TYPES_64, LSDSORT_ALGO_ONESWEEP, LSDSORT_ALGO_STAGED, check  # noqa: F401
+from .errors import KEY_TYPES_16, KEY_TYPES_32, KEY_TYPES_64, LSDSORT_ALGO_ONESWEEP, LSDSORT_ALGO_STAGED, check  # noqa: F401
 
 # exactly what __init__.py re-exports from here (tests/test_python_face_cpu.py)
 __all__ = [
     "sort", "sort_pairs", "to_device", "to_host", "workspace_bytes", "alloc_workspace", "workspace_form", "tile_keys",
     "set_tile_config", "set_xcd_chunk", "set_hybrid", "set_small_sort", "set_pass_skipping", "set_rank_method", "rank_method",
     "GPULSDRadixSort", "GPULSDRadixSortTimed", "GPUSortMulti", "GPUSortTyped", "GPUSortWide", "sort64",
+    "GPUSort16", "keys16_workspace_bytes", "set_keys16_route", "sort16",
     "GPUSortSegmented", "segmented_workspace_bytes", "sort_rows", "GPUTopK", "topk_workspace_bytes", "topk_rows",
     "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
     "MSBPartition", "SplitterPartition", "ThresholdPartition", "sharded_thresholds",
@@ -95,7 +96,7 @@ def _payload(d_vals, n: int, name: str = "d_vals", dtypes=None, what: str = "val
 
 
 def _key_type(key_type: str, table: dict) -> int:
-    """The header's code of a key type name; ``table`` is KEY_TYPES_32 or KEY_TYPES_64."""
+    """The header's code of a key type name; ``table`` is KEY_TYPES_32, KEY_TYPES_64 or KEY_TYPES_16."""
     if key_type not in table:
         raise ValueError("key_type: " + " or ".join(f'"{name}"' for name in table) + f", got {key_type!r}")
     return table[key_type]
@@ -418,6 +419,63 @@ def sort64(x, descending: bool = False, return_indices: bool = False, stream=Non
         out = x.clone(memory_format=torch.contiguous_format)
         idx = torch.arange(x.numel(), dtype=torch.int32, device=x.device) if return_indices else None
         GPUSortWide(out, idx, key_type=key_type, descending=descending, stream=stream)
+        if return_indices:
+            return out, idx.to(torch.int64)
+    return out
+
+
+def keys16_workspace_bytes(n: int, pairs: bool = False) -> int:
+    """Bytes of device workspace ``GPUSort16`` needs for up to ``n`` 16-bit keys (``pairs``: with 32-bit payloads); the figure
+    covers both routes."""
+    return int(lib().lsdsort_keys16_workspace_bytes(n, int(bool(pairs))))
+
+
+def set_keys16_route(route: int) -> None:
+    """How ``GPUSort16`` sorts keys without payloads: -1 by size (default), 0 always the widen route (map to uint32, the ordinary
+    sort, narrow), 1 always the count route (count the 65536 values, scan, fill).  Payloads always take the widen route."""
+    check(lib().lsdsort_set_keys16_route(route), "lsdsort_set_keys16_route")
+
+
+def GPUSort16(d_keys, key_type: str = "int16", descending: bool = False, d_vals=None, workspace=None, stream=None,
+              check_fault: bool = False):
+    """Device-resident sort of 16-bit keys, in place (``lsdsort_keys16_device``).  ``d_keys``: a contiguous 1-D int16, float16 or
+    bfloat16 CUDA tensor whose 16 bits compare as ``key_type``: "uint16" / "int16" for an int16 tensor ("uint16" sorts its bit
+    patterns), "float16" / "bfloat16" for the tensor of that dtype (IEEE total order: NaNs by sign at the two ends, -0.0 below
+    +0.0).  ``d_vals``: optional int32 payloads permuted with the keys, stable in either direction."""
+    torch = _torch()
+    _dev(d_keys, "d_keys", (torch.int16, torch.float16, torch.bfloat16), dims=(1,))
+    code = _key_type(key_type, KEY_TYPES_16)
+    fits = {torch.int16: ("uint16", "int16"), torch.float16: ("float16",), torch.bfloat16: ("bfloat16",)}[d_keys.dtype]
+    if key_type not in fits:
+        raise TypeError(f"a {str(d_keys.dtype).replace('torch.', '')} tensor sorts with key_type " + " or ".join(f'"{k}"' for k in fits))
+    n = d_keys.numel()
+    pairs = d_vals is not None
+    if pairs:
+        _payload(d_vals, n)
+    if workspace is None:
+        nbytes = keys16_workspace_bytes(n, pairs)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_keys16_workspace_bytes", "too many keys")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    check(lib().lsdsort_keys16_device(d_keys.data_ptr(), d_vals.data_ptr() if pairs else None, workspace.data_ptr(),
+                                      workspace.numel(), n, code, int(bool(descending)), _stream(stream)), "lsdsort_keys16_device")
+    if check_fault and n:
+        _check_fault(workspace, stream, "lsdsort_keys16_check_device", n, int(pairs))
+    return d_keys if not pairs else (d_keys, d_vals)
+
+
+def sort16(x, descending: bool = False, return_indices: bool = False, stream=None):
+    """``torch.sort(x, stable=True, descending=descending)`` for a 1-D int16 / float16 / bfloat16 CUDA tensor, the 16-bit
+    counterpart of ``sort64``: returns the sorted copy (large sorts by counting the 65536 values: no key is moved), and with
+    ``return_indices`` also the int64 positions (the positions ride as payloads, so equal keys keep their input order in either
+    direction).  The float types follow IEEE total order, not torch's: NaNs by sign at the two ends and -0.0 below +0.0."""
+    torch = _torch()
+    _dev(x, "x", (torch.int16, torch.float16, torch.bfloat16), dims=(1,), contiguous=False)
+    key_type = str(x.dtype).replace("torch.", "")
+    with _on_stream(stream):
+        out = x.clone(memory_format=torch.contiguous_format)
+        idx = torch.arange(x.numel(), dtype=torch.int32, device=x.device) if return_indices else None
+        GPUSort16(out, key_type=key_type, descending=descending, d_vals=idx, stream=stream)
         if return_indices:
             return out, idx.to(torch.int64)
     return out
