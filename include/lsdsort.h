@@ -259,6 +259,34 @@ LSDSORT_API int lsdsort_topk_device(const void* d_keys, size_t rows, size_t cols
                                     void* d_out_keys, uint32_t* d_out_idx, void* d_workspace, size_t workspace_bytes,
                                     void* hip_stream);
 
+/* Top-k selection for 16-bit keys (lsdradixsort_amd/csrc/topk16.hip): lsdsort_topk_device's contract, word for word, with the key
+ * types of lsdsort_keys16_device (lsdsort_key16_type; float16 and bfloat16 in IEEE total order; largest != 0 = ascending on the
+ * complemented sortable value).  d_keys: rows x cols 16-bit keys, row-major, READ ONLY.  Row r's result is the first k items of the
+ * STABLE sort of the row in the requested order: d_out_keys[r * k + j], j < k, best first, 16-bit words in the caller's key type,
+ * and d_out_idx[r * k + j] its position within the row (d_out_idx may be NULL: values only, and no position is written anywhere
+ * the caller can see).  Equal keys come out in position order, and of the duplicates of the k-th value those at the lowest
+ * positions are selected; the result is identical on every run and under graph replay.
+ * d_keys and d_out_keys need 2-byte alignment only and cols may be odd: every row is read by 16-byte loads of eight keys from ITS
+ * first 16-byte line on, the keys in front of that line and behind the row's last whole line one by one.
+ * The row is not sorted: a counting radix select of at most TWO digit levels (rows of up to 1024 keys in one wavefront, up to 16384
+ * in one workgroup, two rounds of 8-bit digits; longer rows by many workgroups, 11 bits then 5, at most four reads of the row --
+ * 8 B/key -- and nothing written but the winners), an ordered write of the winners into the workspace, a segmented sort of those
+ * rows x k items alone (none for k = 1), and one kernel that narrows them into the outputs.  Where k is above three quarters of
+ * cols the rows are widened into the workspace and sorted whole instead: same result (the 3/4 is the 32-bit entry's, not tuned for
+ * 2-byte keys).  Stream-ordered, no host synchronisation, nothing allocated; every launch is sized from (rows, cols, k):
+ * capturable in a graph after lsdsort_prepare_device.  The fault word is the first word of the workspace:
+ * lsdsort_check_device(d_workspace, stream) reports it (never expected to be set).
+ * Checks, in order, each before a device is touched: key_type (INVALID_ARG), rows or rows * cols above LSDSORT_MAX_KEYS
+ * (TOO_LARGE), k > cols (INVALID_ARG), rows == 0, cols == 0 or k == 0 (OK, nothing launched), a NULL or odd d_keys or d_out_keys
+ * (INVALID_ARG), the workspace (WORKSPACE: NULL, not 256-byte aligned, or below lsdsort_topk16_workspace_bytes), the device
+ * (NO_DEVICE).  lsdsort_topk16_workspace_bytes is a multiple of 256, monotonic in each argument, 0 above the limits (rows * cols,
+ * rows * k or any argument above LSDSORT_MAX_KEYS), sized for the call with indices, and covers both routes. */
+LSDSORT_API size_t lsdsort_topk16_workspace_bytes(size_t rows, size_t cols, size_t k);
+LSDSORT_API int lsdsort_topk16_device(const void* d_keys, size_t rows, size_t cols, size_t k, int key_type /* lsdsort_key16_type */,
+                                      int largest, void* d_out_keys /* [rows][k] 16-bit, caller's type */,
+                                      uint32_t* d_out_idx /* [rows][k] or NULL */, void* d_workspace, size_t workspace_bytes,
+                                      void* hip_stream);
+
 /* After the stream has drained: LSDSORT_OK, or LSDSORT_ERR_DEVICE_FAULT if a kernel of the
  * last sort on this workspace gave up a bounded spin or refused destinations outside the output
  * (never expected; the output is then undefined).  Synchronises hip_stream.  With LSDSORT_REPROBE=1

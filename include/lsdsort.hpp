@@ -153,6 +153,23 @@ inline void topk(const void* d_keys, size_t rows, size_t cols, size_t k, void* d
                               hip_stream), "lsdsort_topk_device");
 }
 
+// The same for 16-bit keys (lsdsort_topk16_device): uint16_t or int16_t by overload; float16 and bfloat16 bits are passed as
+// uint16_t with the key type named, as in sort16_device.  Workspace of topk16_workspace_bytes(rows, cols, k).
+inline size_t topk16_workspace_bytes(size_t rows, size_t cols, size_t k) { return lsdsort_topk16_workspace_bytes(rows, cols, k); }
+inline void topk16_device(const uint16_t* d_keys, size_t rows, size_t cols, size_t k, uint16_t* d_out_keys, uint32_t* d_out_idx,
+                          void* d_workspace, size_t workspace_bytes_, bool largest = true,
+                          lsdsort_key16_type key_type = LSDSORT_KEY16_U16, void* hip_stream = nullptr)
+{
+    check(lsdsort_topk16_device(d_keys, rows, cols, k, key_type, largest ? 1 : 0, d_out_keys, d_out_idx, d_workspace, workspace_bytes_,
+                                hip_stream), "lsdsort_topk16_device");
+}
+inline void topk16_device(const int16_t* d_keys, size_t rows, size_t cols, size_t k, int16_t* d_out_keys, uint32_t* d_out_idx,
+                          void* d_workspace, size_t workspace_bytes_, bool largest = true, void* hip_stream = nullptr)
+{
+    check(lsdsort_topk16_device(d_keys, rows, cols, k, LSDSORT_KEY16_I16, largest ? 1 : 0, d_out_keys, d_out_idx, d_workspace,
+                                workspace_bytes_, hip_stream), "lsdsort_topk16_device");
+}
+
 // A shard of a range-partitioned array: keys expected to share their top `common_prefix_bits` bits (a hint; the device checks)
 inline void sort_shard_device(uint32_t* d_keys, void* d_workspace, size_t workspace_bytes_, size_t n, int common_prefix_bits,
                               int radix_bits = 8, void* hip_stream = nullptr)

@@ -21,7 +21,7 @@ __all__ = [
     "sort", "sort_pairs", "to_device", "to_host", "workspace_bytes", "alloc_workspace", "workspace_form", "tile_keys",
     "set_tile_config", "set_xcd_chunk", "set_hybrid", "set_small_sort", "set_pass_skipping", "set_rank_method", "rank_method",
     "GPULSDRadixSort", "GPULSDRadixSortTimed", "GPUSortMulti", "GPUSortTyped", "GPUSortWide", "sort64",
-    "GPUSort16", "keys16_workspace_bytes", "set_keys16_route", "sort16",
+    "GPUSort16", "keys16_workspace_bytes", "set_keys16_route", "sort16", "GPUTopK16", "topk16_workspace_bytes", "topk16_rows",
     "GPUSortSegmented", "segmented_workspace_bytes", "sort_rows", "GPUTopK", "topk_workspace_bytes", "topk_rows",
     "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
     "MSBPartition", "SplitterPartition", "ThresholdPartition", "sharded_thresholds",
@@ -479,6 +479,64 @@ def sort16(x, descending: bool = False, return_indices: bool = False, stream=Non
         if return_indices:
             return out, idx.to(torch.int64)
     return out
+
+
+def topk16_workspace_bytes(rows: int, cols: int, k: int) -> int:
+    """Bytes of device workspace ``GPUTopK16`` needs for the ``k`` best of each of ``rows`` rows of ``cols`` 16-bit keys."""
+    return int(lib().lsdsort_topk16_workspace_bytes(rows, cols, k))
+
+
+def GPUTopK16(d_keys, k: int, key_type: str = "int16", largest: bool = True, return_indices: bool = True, workspace=None,
+              stream=None, check_fault: bool = False):
+    """The ``k`` best keys of every row of ``d_keys`` (``lsdsort_topk16_device``): a contiguous 1-D (one row) or 2-D int16, float16
+    or bfloat16 CUDA tensor whose 16 bits compare as ``key_type``, paired with the dtype as in ``GPUSort16``: "uint16" / "int16" for
+    an int16 tensor, "float16" / "bfloat16" for the tensor of that dtype (IEEE total order).  Returns ``(values, indices)`` --
+    ``[rows, k]`` (``[k]`` for 1-D input), best first, ``values`` in the input's dtype, ``indices`` the int32 positions within the
+    row, or ``None`` without ``return_indices`` -- exactly the first ``k`` columns of the rows' stable sort: equal keys in position
+    order.  ``d_keys`` is only read.  Stream-ordered; the rows are not sorted (a radix select of at most two digit levels, then a
+    sort of the winners)."""
+    torch = _torch()
+    _dev(d_keys, "d_keys", (torch.int16, torch.float16, torch.bfloat16), dims=(1, 2))
+    code = _key_type(key_type, KEY_TYPES_16)
+    fits = {torch.int16: ("uint16", "int16"), torch.float16: ("float16",), torch.bfloat16: ("bfloat16",)}[d_keys.dtype]
+    if key_type not in fits:
+        raise TypeError(f"a {str(d_keys.dtype).replace('torch.', '')} tensor selects with key_type " + " or ".join(f'"{k}"' for k in fits))
+    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
+    k = int(k)
+    if not 0 <= k <= cols:
+        raise ValueError("k must be within 0 .. the row length")
+    shape = (k,) if d_keys.dim() == 1 else (rows, k)
+    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
+        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
+        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
+    if workspace is None:
+        nbytes = topk16_workspace_bytes(rows, cols, k)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_topk16_workspace_bytes", "too many keys or rows")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    check(lib().lsdsort_topk16_device(d_keys.data_ptr(), rows, cols, k, code, int(bool(largest)), values.data_ptr(),
+                                      indices.data_ptr() if return_indices else None, workspace.data_ptr(), workspace.numel(),
+                                      _stream(stream)), "lsdsort_topk16_device")
+    if check_fault and rows and cols and k:
+        _check_fault(workspace, stream)
+    return values, indices
+
+
+def topk16_rows(x, k: int, largest: bool = True, stream=None):
+    """``torch.topk(x, k, dim=-1, largest=largest, sorted=True)`` for a contiguous int16 / float16 / bfloat16 CUDA tensor of one or
+    more dimensions, the 16-bit counterpart of ``topk_rows``: ``(values, int64 indices)``.  The float types follow IEEE total
+    order, not torch's: NaNs by sign at the two ends (+NaN above +inf, -NaN below -inf) and -0.0 below +0.0.  Among equal keys the
+    lower position comes first, always."""
+    torch = _torch()
+    _dev(x, "x", (torch.int16, torch.float16, torch.bfloat16), contiguous=False)
+    if x.dim() == 0:
+        raise TypeError("x: at least one dimension")
+    cols = x.shape[-1]
+    with _on_stream(stream):
+        flat = x.contiguous().view(-1, cols)
+        values, indices = GPUTopK16(flat, k, key_type=str(x.dtype).replace("torch.", ""), largest=largest, stream=stream)
+        lead = tuple(x.shape[:-1])
+        return values.view(lead + (k,)), indices.view(lead + (k,)).to(torch.int64)
 
 
 def GPULSDRadixSortTimed(d_keys, r: int = 8, d_vals=None, algorithm: int = LSDSORT_ALGO_ONESWEEP, workspace=None,

@@ -21,13 +21,13 @@
 
 #include <atomic>
 
+#include "keys16_map.hpp"
 #include "lsd_host.hpp"
 
 namespace {
 
 constexpr uint32_t kValues = 65536;          // values of a 16-bit key
 constexpr uint32_t kHalfValues = 32768;      // counters of one count workgroup: 128 KiB of LDS
-constexpr uint32_t kGroupKeys = 8;           // keys of one 16-byte access
 constexpr int kCountThreads = 1024;
 constexpr int kCountUnroll = 4;              // 16-byte loads in flight per thread
 constexpr uint32_t kMaxSlices = 128;         // x 2 halves = 256 workgroups: one per CU
@@ -44,49 +44,8 @@ constexpr size_t kKeys16CountMinKeys = (size_t)1 << 23;
 
 std::atomic<int> g_route{-1};   // lsdsort_set_keys16_route: -1 auto, 0 widen, 1 count
 
-// The caller's key type and order as the map to the sortable 16-bit value: t = k ^ (k & a ? 0xFFFF : b) ^ c.  uint16 (0, 0),
-// int16 (0, 0x8000), float16 and bfloat16 (0x8000, 0x8000): a negative key is complemented, a non-negative one gets its sign bit
-// flipped (IEEE total order); c = 0xFFFF for descending.  The 16-bit form of lsd::KeyTransform.
-struct Key16Map {
-    uint32_t a, b, c;
-};
-__device__ __forceinline__ uint32_t to_sortable16(uint32_t k, const Key16Map& m) { return k ^ ((k & m.a) ? 0xFFFFu : m.b) ^ m.c; }
-// the inverse: u = t ^ c has its top bit SET where the key was not negative
-__device__ __forceinline__ uint32_t from_sortable16(uint32_t t, const Key16Map& m)
-{
-    const uint32_t u = t ^ m.c;
-    return u ^ ((~u & m.a) ? 0xFFFFu : m.b);
-}
-
-int key16_map(int key_type, int descending, Key16Map* m)
-{
-    *m = Key16Map{0, 0, descending ? 0xFFFFu : 0u};
-    switch (key_type) {
-        case LSDSORT_KEY16_U16: break;
-        case LSDSORT_KEY16_I16: m->b = 0x8000u; break;
-        case LSDSORT_KEY16_F16:
-        case LSDSORT_KEY16_BF16: m->a = 0x8000u; m->b = 0x8000u; break;
-        default: return LSDSORT_ERR_INVALID_ARG;
-    }
-    return LSDSORT_OK;
-}
-
-// The keys by address: `head` keys in front of the first 16-byte line (0..7), `groups` whole groups of eight from there on, and
-// `tail` keys behind them (0..7).  Key i of group g is key head + 8 g + i.
-struct Span {
-    uint32_t head, groups, tail;
-};
-Span span_of(const void* keys, size_t n)
-{
-    Span s;
-    const size_t to_line = ((16 - ((uintptr_t)keys & 15)) & 15) / sizeof(uint16_t);
-    s.head = (uint32_t)lsd::min_sz(to_line, n);
-    s.groups = (uint32_t)((n - s.head) / kGroupKeys);
-    s.tail = (uint32_t)(n - s.head - (size_t)s.groups * kGroupKeys);
-    return s;
-}
-__device__ __forceinline__ const uint4* body_of(const uint16_t* keys, const Span& sp) { return reinterpret_cast<const uint4*>(keys + sp.head); }
-__device__ __forceinline__ uint32_t first_tail_key(const Span& sp) { return sp.head + sp.groups * kGroupKeys; }
+// The key map (Key16Map, to_sortable16, from_sortable16, key16_map) and the head / 16-byte groups / tail split (Span, span_of,
+// body_of, first_tail_key) are keys16_map.hpp's: the 16-bit top-k (topk16.hip) reads keys the same way.
 
 // ------------------------------------------------------------------------------------------------ both routes: clear
 // The fault word (widen route: quads = 1) and with it the table (count route) start at zero: `quads` 16-byte stores, one per

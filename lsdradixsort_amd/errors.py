@@ -23,7 +23,7 @@ LSDSORT_KEY_U32, LSDSORT_KEY_I32, LSDSORT_KEY_F32 = 0, 1, 2
 LSDSORT_KEY_U64, LSDSORT_KEY_I64, LSDSORT_KEY_F64 = 3, 4, 5
 KEY_TYPES_32 = {"uint32": LSDSORT_KEY_U32, "int32": LSDSORT_KEY_I32, "float32": LSDSORT_KEY_F32}
 KEY_TYPES_64 = {"uint64": LSDSORT_KEY_U64, "int64": LSDSORT_KEY_I64, "float64": LSDSORT_KEY_F64}
-# lsdsort_key16_type: an enum of its own (lsdsort_keys16_device)
+# lsdsort_key16_type: an enum of its own (lsdsort_keys16_device, lsdsort_topk16_device)
 LSDSORT_KEY16_U16, LSDSORT_KEY16_I16, LSDSORT_KEY16_F16, LSDSORT_KEY16_BF16 = 0, 1, 2, 3
 KEY_TYPES_16 = {"uint16": LSDSORT_KEY16_U16, "int16": LSDSORT_KEY16_I16, "float16": LSDSORT_KEY16_F16, "bfloat16": LSDSORT_KEY16_BF16}
 
