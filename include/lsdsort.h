@@ -287,6 +287,43 @@ LSDSORT_API int lsdsort_topk16_device(const void* d_keys, size_t rows, size_t co
                                       uint32_t* d_out_idx /* [rows][k] or NULL */, void* d_workspace, size_t workspace_bytes,
                                       void* hip_stream);
 
+/* Stable sort of every row of 16-bit keys, with positions (lsdradixsort_amd/csrc/rows16.hip; the counterpart of
+ * torch.sort(x, dim=-1, stable=True) on [batch x vocab] float16 / bfloat16 logits).  d_keys: rows x cols 16-bit keys, row-major.
+ * Row r of d_out_keys is the STABLE sort of row r of d_keys in the requested order (key types and key map of
+ * lsdsort_keys16_device: lsdsort_key16_type, float16 and bfloat16 in IEEE total order; descending != 0 = ascending on the
+ * complemented sortable value), and d_out_idx[r * cols + j] the position within the row of the key now at column j (d_out_idx may
+ * be NULL: keys only, and no position is written anywhere the caller can see).  Equal keys come out in position order, in either
+ * direction; the result is identical on every run and under graph replay.
+ * d_out_keys may be d_keys itself (in place); any other overlap is the caller's error and is not checked; d_keys is otherwise only
+ * read.  d_keys and d_out_keys need 2-byte alignment only and cols may be odd: rows are read and written by 16-byte accesses of
+ * eight keys from a 16-byte line on, the keys in front of it and behind the last whole group one by one.
+ * The host chooses the route by cols.  Rows of up to 1024 keys are sorted by one wavefront each, up to 16384 by one workgroup each:
+ * the row is read once into LDS as words of (sortable key << 16 | position), sorted there by at most two 8-bit digit passes (a byte
+ * that is the same in every key of the row is no pass) and stored -- no key is widened through memory.  Rows of up to
+ * LSDSORT_ROWS16_NATIVE_MAX_COLS keys take two global passes (low byte, high byte) over tiles of 8192 row positions: per pass a
+ * histogram kernel, a scan per row and a scatter kernel; pass 1 leaves a uint32 key and a uint32 position per item in the workspace.
+ * Longer rows, and every row where the returning-add rank form is not in force (lsdsort_set_rank_method), take the WIDEN route: the
+ * keys go to the workspace as sortable uint32 words with their positions, lsdsort_segmented_device sorts the pairs with the rows as
+ * segments, one kernel un-maps and narrows.  Same result on every route.
+ * Stream-ordered, no host synchronisation, nothing allocated; every launch is sized from (rows, cols): capturable in a graph after
+ * lsdsort_prepare_device.  Phases are ordered by kernel boundaries.  The fault word is the first word of the workspace:
+ * lsdsort_check_device(d_workspace, stream) reports it (never expected to be set); every store into the outputs is guarded
+ * against its row.
+ * Checks, in order, each before a device is touched: key_type (INVALID_ARG), rows or rows * cols above LSDSORT_MAX_KEYS
+ * (TOO_LARGE), rows == 0 or cols == 0 (OK, nothing launched), a NULL or odd d_keys or d_out_keys (INVALID_ARG), the workspace
+ * (WORKSPACE: NULL, not 256-byte aligned, or below lsdsort_rows16_workspace_bytes), the device (NO_DEVICE).
+ * lsdsort_rows16_workspace_bytes is a multiple of 256, monotonic in each argument, 0 above the limits (rows, cols or rows * cols
+ * above LSDSORT_MAX_KEYS), sized for the call with indices, and covers BOTH routes whatever the route setting says.
+ * lsdsort_set_rows16_route: -1 by size (default), 0 always the widen route, 1 native wherever it exists; process-wide like the other
+ * setters, anything else is INVALID_ARG. */
+#define LSDSORT_ROWS16_NATIVE_MAX_COLS 262144   /* rows longer than this take the widen route */
+LSDSORT_API size_t lsdsort_rows16_workspace_bytes(size_t rows, size_t cols);
+LSDSORT_API int lsdsort_rows16_device(const void* d_keys, size_t rows, size_t cols, int key_type /* lsdsort_key16_type */,
+                                      int descending, void* d_out_keys /* [rows][cols] 16-bit; may be d_keys itself */,
+                                      uint32_t* d_out_idx /* [rows][cols] or NULL */, void* d_workspace, size_t workspace_bytes,
+                                      void* hip_stream);
+LSDSORT_API int lsdsort_set_rows16_route(int route);   /* -1 by size (default), 0 always the widen route, 1 native wherever it exists */
+
 /* After the stream has drained: LSDSORT_OK, or LSDSORT_ERR_DEVICE_FAULT if a kernel of the
  * last sort on this workspace gave up a bounded spin or refused destinations outside the output
  * (never expected; the output is then undefined).  Synchronises hip_stream.  With LSDSORT_REPROBE=1

@@ -170,6 +170,24 @@ inline void topk16_device(const int16_t* d_keys, size_t rows, size_t cols, size_
                                 workspace_bytes_, hip_stream), "lsdsort_topk16_device");
 }
 
+// The stable sort of every row of a row-major [rows x cols] array of 16-bit keys with each key's position in its row
+// (lsdsort_rows16_device): uint16_t or int16_t by overload; float16 and bfloat16 bits are passed as uint16_t with the key type named.
+// d_out_keys may be d_keys (in place); d_out_idx may be null.  Workspace of rows16_workspace_bytes(rows, cols).
+inline size_t rows16_workspace_bytes(size_t rows, size_t cols) { return lsdsort_rows16_workspace_bytes(rows, cols); }
+inline void sort_rows16_device(const uint16_t* d_keys, size_t rows, size_t cols, uint16_t* d_out_keys, uint32_t* d_out_idx, void* d_workspace,
+                               size_t workspace_bytes_, bool descending = false, lsdsort_key16_type key_type = LSDSORT_KEY16_U16,
+                               void* hip_stream = nullptr)
+{
+    check(lsdsort_rows16_device(d_keys, rows, cols, key_type, descending ? 1 : 0, d_out_keys, d_out_idx, d_workspace, workspace_bytes_,
+                                hip_stream), "lsdsort_rows16_device");
+}
+inline void sort_rows16_device(const int16_t* d_keys, size_t rows, size_t cols, int16_t* d_out_keys, uint32_t* d_out_idx, void* d_workspace,
+                               size_t workspace_bytes_, bool descending = false, void* hip_stream = nullptr)
+{
+    check(lsdsort_rows16_device(d_keys, rows, cols, LSDSORT_KEY16_I16, descending ? 1 : 0, d_out_keys, d_out_idx, d_workspace,
+                                workspace_bytes_, hip_stream), "lsdsort_rows16_device");
+}
+
 // A shard of a range-partitioned array: keys expected to share their top `common_prefix_bits` bits (a hint; the device checks)
 inline void sort_shard_device(uint32_t* d_keys, void* d_workspace, size_t workspace_bytes_, size_t n, int common_prefix_bits,
                               int radix_bits = 8, void* hip_stream = nullptr)

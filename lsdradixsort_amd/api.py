@@ -22,6 +22,7 @@ __all__ = [
     "set_tile_config", "set_xcd_chunk", "set_hybrid", "set_small_sort", "set_pass_skipping", "set_rank_method", "rank_method",
     "GPULSDRadixSort", "GPULSDRadixSortTimed", "GPUSortMulti", "GPUSortTyped", "GPUSortWide", "sort64",
     "GPUSort16", "keys16_workspace_bytes", "set_keys16_route", "sort16", "GPUTopK16", "topk16_workspace_bytes", "topk16_rows",
+    "GPUSortRows16", "rows16_workspace_bytes", "set_rows16_route", "sort_rows16",
     "GPUSortSegmented", "segmented_workspace_bytes", "sort_rows", "GPUTopK", "topk_workspace_bytes", "topk_rows",
     "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
     "MSBPartition", "SplitterPartition", "ThresholdPartition", "sharded_thresholds",
@@ -537,6 +538,72 @@ def topk16_rows(x, k: int, largest: bool = True, stream=None):
         values, indices = GPUTopK16(flat, k, key_type=str(x.dtype).replace("torch.", ""), largest=largest, stream=stream)
         lead = tuple(x.shape[:-1])
         return values.view(lead + (k,)), indices.view(lead + (k,)).to(torch.int64)
+
+
+def rows16_workspace_bytes(rows: int, cols: int) -> int:
+    """Bytes of device workspace ``GPUSortRows16`` needs for ``rows`` rows of ``cols`` 16-bit keys; the figure covers both routes."""
+    return int(lib().lsdsort_rows16_workspace_bytes(rows, cols))
+
+
+def set_rows16_route(route: int) -> None:
+    """How ``GPUSortRows16`` sorts: -1 by row length (default), 0 always the widen route (map to uint32 with positions, the
+    segmented sort, narrow), 1 the native kernels wherever they exist (rows of up to ``LSDSORT_ROWS16_NATIVE_MAX_COLS`` keys)."""
+    check(lib().lsdsort_set_rows16_route(route), "lsdsort_set_rows16_route")
+
+
+def GPUSortRows16(d_keys, key_type: str = "int16", descending: bool = False, return_indices: bool = True, out=None, workspace=None,
+                  stream=None, check_fault: bool = False):
+    """The stable sort of every row of ``d_keys`` (``lsdsort_rows16_device``): a contiguous 1-D (one row) or 2-D int16, float16 or
+    bfloat16 CUDA tensor whose 16 bits compare as ``key_type``, paired with the dtype as in ``GPUSort16``: "uint16" / "int16" for an
+    int16 tensor, "float16" / "bfloat16" for the tensor of that dtype (IEEE total order).  Returns ``(values, indices)``: ``values``
+    in the input's shape and dtype (``out`` where one is given; ``out=d_keys`` sorts in place), ``indices`` the int32 positions
+    within the row, or ``None`` without ``return_indices``.  Equal keys come out in position order in either direction.
+    Stream-ordered; ``d_keys`` is only read unless it is ``out``."""
+    torch = _torch()
+    kinds = (torch.int16, torch.float16, torch.bfloat16)
+    _dev(d_keys, "d_keys", kinds, dims=(1, 2))
+    code = _key_type(key_type, KEY_TYPES_16)
+    fits = {torch.int16: ("uint16", "int16"), torch.float16: ("float16",), torch.bfloat16: ("bfloat16",)}[d_keys.dtype]
+    if key_type not in fits:
+        raise TypeError(f"a {str(d_keys.dtype).replace('torch.', '')} tensor sorts with key_type " + " or ".join(f'"{k}"' for k in fits))
+    if out is not None:
+        _dev(out, "out", (d_keys.dtype,), dims=(d_keys.dim(),))
+        if out.shape != d_keys.shape:
+            raise ValueError("out: the shape of d_keys")
+    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
+    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
+        values = out if out is not None else torch.empty_like(d_keys)
+        indices = torch.empty(d_keys.shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
+    if workspace is None:
+        nbytes = rows16_workspace_bytes(rows, cols)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_rows16_workspace_bytes", "too many keys or rows")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    check(lib().lsdsort_rows16_device(d_keys.data_ptr(), rows, cols, code, int(bool(descending)), values.data_ptr(),
+                                      indices.data_ptr() if return_indices else None, workspace.data_ptr(), workspace.numel(),
+                                      _stream(stream)), "lsdsort_rows16_device")
+    if check_fault and rows and cols:
+        _check_fault(workspace, stream)
+    return values, indices
+
+
+def sort_rows16(x, descending: bool = False, return_indices: bool = False, stream=None):
+    """``torch.sort(x, dim=-1, stable=True, descending=descending)`` for an int16 / float16 / bfloat16 CUDA tensor of one or more
+    dimensions, the 16-bit counterpart of ``sort_rows``: returns the sorted copy, and with ``return_indices`` also the int64
+    positions within each row (equal keys keep their input order in either direction).  The float types follow IEEE total order,
+    not torch's: NaNs by sign at the two ends and -0.0 below +0.0."""
+    torch = _torch()
+    _dev(x, "x", (torch.int16, torch.float16, torch.bfloat16), contiguous=False)
+    if x.dim() == 0:
+        raise TypeError("x: at least one dimension")
+    cols = x.shape[-1]
+    with _on_stream(stream):
+        flat = x.contiguous().view(-1, cols)
+        values, indices = GPUSortRows16(flat, key_type=str(x.dtype).replace("torch.", ""), descending=descending,
+                                        return_indices=return_indices, stream=stream)
+        if return_indices:
+            return values.view(x.shape), indices.view(x.shape).to(torch.int64)
+    return values.view(x.shape)
 
 
 def GPULSDRadixSortTimed(d_keys, r: int = 8, d_vals=None, algorithm: int = LSDSORT_ALGO_ONESWEEP, workspace=None,

@@ -1,0 +1,329 @@
+"""GPU suite: lsdsort_rows16_device (GPUSortRows16, sort_rows16), bit-exact over every output word, positions included.
+
+Contract: row r of the output is the stable sort of row r of the input in the requested order, with each key's position in its row.
+Expected result: numpy, per row np.lexsort((positions, sortable16)) with a numpy restatement of the key map -- never the code under
+test.  torch.sort(stable=True) is a second witness where its order is the library's (int16, NaN-free and -0-free floats).
+
+Boundaries of the implementation (lsdradixsort_amd/csrc/rows16.hip): rows of up to 1024 keys take one wavefront (eight rows per
+workgroup), up to 16384 one workgroup, up to LSDSORT_ROWS16_NATIVE_MAX_COLS two global passes over tiles of 8192 row positions,
+longer ones the widen route (the segmented sort on uint32 words).  Every tile is split by ITS address into the keys in front of its
+first 16-byte line, 16-byte groups, and the rest: odd cols and the byte offsets 0, 2, 6, 14 of the arrays put rows at every even
+offset within a line.  Every raw call here runs on outputs and a workspace inside sentinel zones, with the workspace exactly as
+large as the library says; the fault word and the zones are checked after each call."""
+import numpy as np
+import pytest
+import torch
+
+import lsdradixsort_amd as lsd
+from _guarded import assert_intact, guarded, guarded_workspace
+from _guarded16 import assert_intact16, bits_of, guarded16
+
+pytestmark = pytest.mark.gpu
+
+KEY_TYPES = {"uint16": 0, "int16": 1, "float16": 2, "bfloat16": 3}
+DTYPES = {"uint16": torch.int16, "int16": torch.int16, "float16": torch.float16, "bfloat16": torch.bfloat16}
+ALL_TYPES = ["uint16", "int16", "float16", "bfloat16"]
+OFFSETS = (0, 2, 6, 14)
+CAP = lsd.errors.LSDSORT_ROWS16_NATIVE_MAX_COLS
+TILE = 8192   # the long tier's tile
+# +-0, +-inf, +-NaN (quiet, signalling, all ones), denormals, the largest finite values
+SPECIALS = {
+    "float16": np.array([0x0000, 0x8000, 0x7C00, 0xFC00, 0x7E00, 0xFE00, 0x7C01, 0xFFFF, 0x7FFF, 0x0001, 0x8001, 0x03FF, 0x83FF,
+                         0x7BFF, 0xFBFF, 0x3C00, 0xBC00], dtype=np.uint16),
+    "bfloat16": np.array([0x0000, 0x8000, 0x7F80, 0xFF80, 0x7FC0, 0xFFC0, 0x7F81, 0xFFFF, 0x7FFF, 0x0001, 0x8001, 0x007F, 0x807F,
+                          0x7F7F, 0xFF7F, 0x3F80, 0xBF80], dtype=np.uint16),
+}
+FILL16, FILL32 = 0xA5A5, 0x3C3C3C3C   # what the outputs hold before a call
+CLASSES = [(9, 700), (3, 9000), (2, 40001), (1, CAP + 1)]   # wave, workgroup, long, widen
+
+
+@pytest.fixture(autouse=True)
+def default_routes():
+    yield
+    lsd.set_rows16_route(-1)
+    lsd.set_rank_method(-1)
+
+
+def sortable16_np(u, key_type, descending):
+    """the map of include/lsdsort.h restated: the uint16 whose unsigned order is the requested one"""
+    u = u.astype(np.uint32)
+    if key_type == "int16":
+        u = u ^ np.uint32(0x8000)
+    elif key_type in ("float16", "bfloat16"):
+        u = u ^ np.where(u & np.uint32(0x8000), np.uint32(0xFFFF), np.uint32(0x8000))
+    return (u ^ np.uint32(0xFFFF)) if descending else u
+
+
+def expected_np(keys, key_type, descending):
+    """keys: [rows, cols] uint16 bits -> the stable order of every row: (sorted keys, positions)"""
+    s = sortable16_np(keys, key_type, descending)
+    rows, cols = keys.shape
+    pos = np.arange(cols)
+    order = np.empty((rows, cols), dtype=np.int64)
+    for r in range(rows):
+        order[r] = np.lexsort((pos, s[r]))
+    return np.take_along_axis(keys, order, axis=1), order.astype(np.uint32)
+
+
+def make_keys(rows, cols, key_type, seed):
+    """random bits; the float types with 30 % specials"""
+    rng = np.random.default_rng(seed)
+    n = rows * cols
+    keys = rng.integers(0, 1 << 16, n, dtype=np.uint32).astype(np.uint16)
+    if key_type in SPECIALS:
+        pick = rng.random(n) < 0.3
+        keys[pick] = SPECIALS[key_type][rng.integers(0, SPECIALS[key_type].size, int(pick.sum()))]
+    return keys.reshape(rows, cols)
+
+
+def assert_equal(a, b, what):
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.shape == b.shape, f"{what}: shape {a.shape} against {b.shape}"
+    if not np.array_equal(a, b):
+        bad = np.argwhere(a != b)
+        at = tuple(bad[0])
+        raise AssertionError(f"{what}: {len(bad)} words differ, first at {at}: got {a[at]:#x} want {b[at]:#x}")
+
+
+def stream_ptr(stream=None):
+    return int((stream or torch.cuda.current_stream()).cuda_stream)
+
+
+class Call:
+    """one raw call of the C entry: outputs and workspace inside sentinel zones, the values at byte offset `skip`; `in_place`: the
+    values are the keys' own buffer (`keys_whole` is then what holds the zones around them)"""
+
+    def __init__(self, view, rows, cols, key_type, descending, skip=0, with_idx=True, stream=None, launch=True, in_place=False,
+                 keys_whole=None):
+        L = lsd.lib()
+        self.rows, self.cols, self.with_idx, self.stream = rows, cols, with_idx, stream
+        if in_place:
+            self.vals_whole, self.vals = keys_whole, view
+        else:
+            self.vals_whole, self.vals = guarded16(np.full(rows * cols, FILL16, dtype=np.uint16), skip)
+        self.idx_whole, self.idx = guarded(np.full(rows * cols, FILL32, dtype=np.uint32))
+        self.ws_whole, self.ws = guarded_workspace(L.lsdsort_rows16_workspace_bytes(rows, cols))
+        self.args = (view.data_ptr(), rows, cols, KEY_TYPES[key_type], int(descending), self.vals.data_ptr(),
+                     self.idx.data_ptr() if with_idx else None, self.ws.data_ptr(), self.ws.numel(), stream_ptr(stream))
+        torch.cuda.synchronize()
+        if launch:
+            self.launch()
+
+    def launch(self):
+        st = lsd.lib().lsdsort_rows16_device(*self.args)
+        assert st == 0, st
+        return self
+
+    def result(self):
+        """(values, positions) as [rows, cols] uint16 / uint32 bits, after the fault word and every guard zone have been checked"""
+        assert lsd.lib().lsdsort_check_device(self.ws.data_ptr(), stream_ptr(self.stream)) == 0
+        torch.cuda.synchronize()
+        fault = int(self.ws[:4].view(torch.int32).item())
+        assert fault == 0, f"fault word {fault:#x}"
+        assert_intact16(values=self.vals_whole)
+        assert_intact(indices=self.idx_whole, workspace=self.ws_whole)
+        idx = self.idx.cpu().numpy().view(np.uint32).reshape(self.rows, self.cols)
+        if not self.with_idx:
+            assert (idx == FILL32).all(), "no index buffer was given: nothing may be written"
+        return bits_of(self.vals).reshape(self.rows, self.cols), idx
+
+
+def check_case(view, shape, key_type, descending, ek, ei, what, skip=0, with_idx=True):
+    rows, cols = shape
+    values, indices = Call(view, rows, cols, key_type, descending, skip, with_idx).result()
+    assert_equal(values, ek, f"{what} values")
+    if with_idx:
+        assert_equal(indices, ei, f"{what} positions")
+
+
+# ---- size classes and their edges -----------------------------------------------------------------------------------------------
+COLS = [1, 2, 63, 64, 65, 1023, 1024, 1025, 4097, 16383, 16384, 16385, 32768 + 3, 65535, 65536, 65537, 128256, CAP, CAP + 1]
+
+
+@pytest.mark.parametrize("cols", COLS)
+def test_size_classes_against_numpy(cols):
+    """1, 3 and 9 rows (9 spill into a second workgroup of the wave tier), 1 and 2 for the long rows; every key type, both orders"""
+    for rows in ((1, 3, 9) if cols < 65536 else (1, 2)):
+        for key_type in ALL_TYPES:
+            keys = make_keys(rows, cols, key_type, seed=cols + rows)
+            whole, view = guarded16(keys, 0, DTYPES[key_type])
+            for descending in (False, True):
+                ek, ei = expected_np(keys, key_type, descending)
+                check_case(view, (rows, cols), key_type, descending, ek, ei, f"{rows}x{cols} {key_type} descending={descending}")
+            assert_equal(bits_of(view), keys.reshape(-1), "input unchanged")
+            assert_intact16(keys=whole)
+
+
+# ---- alignment ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cols", [65, 66, 1025, 1026, 16385, 16386, 40001, 40002])
+def test_rows_at_every_even_offset_of_a_line(cols):
+    """three rows from array byte offsets 0, 2, 6, 14, the output skewed the same way"""
+    rows = 3
+    keys = make_keys(rows, cols, "bfloat16", seed=cols)
+    ek, ei = expected_np(keys, "bfloat16", True)
+    for skip in OFFSETS:
+        whole, view = guarded16(keys, skip, torch.bfloat16)
+        check_case(view, (rows, cols), "bfloat16", True, ek, ei, f"{rows}x{cols} offset {skip}", skip)
+        assert_equal(bits_of(view), keys.reshape(-1), f"input unchanged (offset {skip})")
+        assert_intact16(keys=whole)
+    whole, view = guarded16(keys, 6, torch.bfloat16)
+    check_case(view, (rows, cols), "bfloat16", True, ek, ei, f"{rows}x{cols} input at 6, output at 14", 14)
+
+
+# ---- stability and degenerate rows ----------------------------------------------------------------------------------------------
+def degenerate_inputs(rows, cols, key_type, seed):
+    rng = np.random.default_rng(seed)
+    out = {}
+    out["all equal"] = np.full((rows, cols), 0x9E37, dtype=np.uint16)
+    out["two values"] = np.array([0x0100, 0xFFF0], dtype=np.uint16)[rng.integers(0, 2, (rows, cols))]
+    out["low byte constant"] = (rng.integers(0, 256, (rows, cols)).astype(np.uint16) << 8) | np.uint16(0x5A)
+    out["high byte constant"] = np.uint16(0x3B00) | rng.integers(0, 256, (rows, cols)).astype(np.uint16)
+    rnd = rng.integers(0, 1 << 16, (rows, cols), dtype=np.uint32).astype(np.uint16)
+    asc = np.take_along_axis(rnd, np.argsort(sortable16_np(rnd, key_type, False), axis=1, kind="stable"), axis=1)
+    out["sorted"] = asc
+    out["reverse sorted"] = np.ascontiguousarray(asc[:, ::-1])
+    out["one value per tile"] = np.broadcast_to((np.arange(cols) // min(TILE, max(cols // 5, 1)) * 0x0101 + 7).astype(np.uint16),
+                                                (rows, cols)).copy()
+    return out
+
+
+@pytest.mark.parametrize("key_type", ["uint16", "bfloat16"])
+@pytest.mark.parametrize("shape", CLASSES[:3], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_stability_and_degenerate_rows(shape, key_type):
+    rows, cols = shape
+    for name, keys in degenerate_inputs(rows, cols, key_type, seed=cols).items():
+        whole, view = guarded16(keys, 2, DTYPES[key_type])
+        for descending in (False, True):
+            ek, ei = expected_np(keys, key_type, descending)
+            if name == "all equal":
+                assert (ei == np.arange(cols)).all()
+            check_case(view, shape, key_type, descending, ek, ei, f"{name} {rows}x{cols} {key_type} descending={descending}", 2)
+        assert_intact16(keys=whole)
+
+
+# ---- variants -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", CLASSES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_null_positions_and_in_place(shape):
+    rows, cols = shape
+    keys = make_keys(rows, cols, "float16", seed=cols)
+    ek, ei = expected_np(keys, "float16", True)
+    whole, view = guarded16(keys, 6, torch.float16)
+    check_case(view, shape, "float16", True, ek, ei, f"{rows}x{cols} no positions", 14, with_idx=False)
+    assert_equal(bits_of(view), keys.reshape(-1), "input unchanged")
+    for with_idx in (True, False):
+        whole, view = guarded16(keys, 6, torch.float16)
+        values, indices = Call(view, rows, cols, "float16", True, with_idx=with_idx, in_place=True, keys_whole=whole).result()
+        assert_equal(values, ek, f"{rows}x{cols} in place, positions={with_idx}: values")
+        if with_idx:
+            assert_equal(indices, ei, f"{rows}x{cols} in place: positions")
+
+
+# ---- routes agree ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", CLASSES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_every_route_gives_the_same_words(shape):
+    rows, cols = shape
+    keys = make_keys(rows, cols, "int16", seed=cols + 1)
+    ek, ei = expected_np(keys, "int16", False)
+    whole, view = guarded16(keys, 0, torch.int16)
+    default = Call(view, rows, cols, "int16", False).result()
+    assert_equal(default[0], ek, "default route: values")
+    assert_equal(default[1], ei, "default route: positions")
+    for name, setting in (("route 0", lambda: lsd.set_rows16_route(0)), ("route 1", lambda: lsd.set_rows16_route(1)),
+                          ("rank method 0", lambda: lsd.set_rank_method(0))):
+        setting()
+        got = Call(view, rows, cols, "int16", False).result()
+        lsd.set_rows16_route(-1)
+        lsd.set_rank_method(-1)
+        assert_equal(got[0], default[0], f"{name}: values")
+        assert_equal(got[1], default[1], f"{name}: positions")
+    assert_intact16(keys=whole)
+
+
+# ---- streams and replay ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", CLASSES[:3], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_two_streams_two_workspaces(shape):
+    rows, cols = shape
+    a = make_keys(rows, cols, "bfloat16", seed=1)
+    b = make_keys(rows, cols, "bfloat16", seed=2)
+    (_, da), (_, db) = guarded16(a, 2, torch.bfloat16), guarded16(b, 6, torch.bfloat16)
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    s1.wait_stream(torch.cuda.current_stream())
+    s2.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s1):
+        par_a = Call(da, rows, cols, "bfloat16", True, stream=s1, launch=False)
+    with torch.cuda.stream(s2):
+        par_b = Call(db, rows, cols, "bfloat16", False, stream=s2, launch=False)
+    torch.cuda.synchronize()
+    par_a.launch()   # both are queued before either is waited for
+    par_b.launch()
+    torch.cuda.synchronize()
+    for par, keys, descending in ((par_a, a, True), (par_b, b, False)):
+        values, indices = par.result()
+        ek, ei = expected_np(keys, "bfloat16", descending)
+        assert_equal(values, ek, "values")
+        assert_equal(indices, ei, "positions")
+
+
+@pytest.mark.parametrize("shape", CLASSES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_graph_replay_on_fresh_inputs(shape):
+    rows, cols = shape
+    L = lsd.lib()
+    assert L.lsdsort_prepare_device() == 0
+    dk = torch.zeros((rows, cols), dtype=torch.int16, device="cuda")
+    out_k = torch.zeros((rows, cols), dtype=torch.int16, device="cuda")
+    out_i = torch.zeros((rows, cols), dtype=torch.int32, device="cuda")
+    ws = torch.empty(L.lsdsort_rows16_workspace_bytes(rows, cols), dtype=torch.uint8, device="cuda")
+
+    def call():
+        st = L.lsdsort_rows16_device(dk.data_ptr(), rows, cols, KEY_TYPES["int16"], 1, out_k.data_ptr(), out_i.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), stream_ptr())
+        assert st == 0, st
+
+    dk.copy_(torch.from_numpy(make_keys(rows, cols, "int16", 1).view(np.int16)))
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        call()   # warm-up: device set-up stays out of the capture
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        call()
+    for seed in (2, 3, 4):
+        keys = make_keys(rows, cols, "int16", seed)
+        if seed == 3:
+            keys = np.full((rows, cols), 0xFF85, dtype=np.uint16)   # all equal
+        dk.copy_(torch.from_numpy(keys.view(np.int16)))
+        out_k.zero_()
+        out_i.zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        fault = int(ws[:4].view(torch.int32).item())
+        assert fault == 0, f"replay {seed}: fault word {fault:#x}"
+        ek, ei = expected_np(keys, "int16", True)
+        assert_equal(bits_of(out_k).reshape(rows, cols), ek, f"replay {seed} values")
+        assert_equal(out_i.cpu().numpy().view(np.uint32), ei, f"replay {seed} positions")
+    assert L.lsdsort_check_device(ws.data_ptr(), None) == 0
+
+
+# ---- the torch-shaped face ------------------------------------------------------------------------------------------------------
+def test_sort_rows16_is_torch_sort():
+    g = torch.Generator(device="cuda").manual_seed(5)
+    x = torch.randint(-(1 << 15), 1 << 15, (3, 5, 4000), generator=g, device="cuda", dtype=torch.int32).to(torch.int16)
+    h = torch.randn((6, 3000), generator=g, device="cuda").to(torch.float16)   # NaN-free
+    h[h == 0] = 1.0                                                             # and free of zeros of either sign
+    for t in (x, h.t()):                                                        # a 3-D tensor; a view that is not contiguous
+        assert t is x or not t.is_contiguous()
+        for descending in (False, True):
+            v, i = lsd.sort_rows16(t, descending=descending, return_indices=True)
+            tv, ti = torch.sort(t, dim=-1, stable=True, descending=descending)
+            assert v.shape == t.shape and v.dtype == t.dtype and i.dtype == torch.int64
+            assert torch.equal(v, tv)
+            assert torch.equal(i, ti)
+            assert torch.equal(torch.gather(t, -1, i), v)
+            assert torch.equal(lsd.sort_rows16(t, descending=descending), tv)
+    row = x[0, 0].contiguous()
+    v1, i1 = lsd.GPUSortRows16(row, key_type="int16", check_fault=True)
+    assert v1.shape == (4000,) and i1.dtype == torch.int32 and torch.equal(v1, torch.sort(row, stable=True).values)
+    v2, i2 = lsd.GPUSortRows16(row, key_type="int16", return_indices=False, out=row)
+    assert i2 is None and v2 is row and torch.equal(row, v1)
