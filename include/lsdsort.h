@@ -324,6 +324,38 @@ LSDSORT_API int lsdsort_rows16_device(const void* d_keys, size_t rows, size_t co
                                       void* hip_stream);
 LSDSORT_API int lsdsort_set_rows16_route(int route);   /* -1 by size (default), 0 always the widen route, 1 native wherever it exists */
 
+/* K-th value selection: ONE order statistic per row, no sort (lsdradixsort_amd/csrc/kth.hip; the counterpart of
+ * torch.kthvalue(x, k, dim=-1), torch.median(x, dim=-1) and the `lower` / `higher` / `nearest` forms of torch.quantile).
+ * d_keys: rows x cols 32-bit keys, row-major, READ ONLY; it needs 4-byte alignment only and cols may be anything: every row is read
+ * by 16-byte loads of four keys from ITS first 16-byte line on, the keys in front of that line and behind the row's last whole
+ * group one by one.  Let S_r be the STABLE sort of row r in the requested order (key_type as lsdsort_keys_device: 0 uint32, 1 int32,
+ * 2 float32 IEEE total order; largest != 0 = descending = ascending on the complemented key, so equal keys keep their position order
+ * in either direction).  d_out_keys[r] = S_r[rank] (rank is 0-based), in the caller's key type, and d_out_idx[r] the position within
+ * the row of that same item -- among the duplicates of the value the one the stable sort puts at `rank`, not "some occurrence"
+ * (d_out_idx may be NULL: values only).  The result equals column `rank` of lsdsort_topk_device(.., k = rank + 1, ..), bit for bit,
+ * values and positions; it is identical on every run and under graph replay.  rows = 1 is the whole-array case.
+ * The row is not sorted and no winner is written: a most-significant-digit-first radix select counts digits until ONE key is left
+ * under the prefix or all 32 bits are fixed (rows of up to 1024 keys in one wavefront, up to 16384 in one workgroup: one read of the
+ * row; longer ones by many workgroups, digits of 11, 11 and 10 bits), then the wanted key is located among the keys of that value in
+ * position order (long rows: one count pass, then ONE chunk is read again): at most four reads of a long row plus one chunk, and
+ * nothing written but counters and 8 B per row.
+ * Stream-ordered, no host synchronisation, nothing allocated; every launch is sized from (rows, cols) alone: capturable in a graph
+ * after lsdsort_prepare_device.  Counters and row states are zeroed by a kernel of the call; phases are ordered by kernel boundaries.
+ * The fault word is the first word of the workspace: lsdsort_check_device(d_workspace, stream) reports it -- set where a row's digit
+ * counts do not reach the rank or no key is located (neither is expected).  The result does not depend on lsdsort_set_rank_method.
+ * Checks, in order, each before a device is touched: key_type outside U32 / I32 / F32 (INVALID_ARG), rows or rows * cols above
+ * LSDSORT_MAX_KEYS (TOO_LARGE), rows == 0 or cols == 0 (OK, nothing launched -- before the rank: an empty row has no valid rank),
+ * rank >= cols (INVALID_ARG), a NULL d_keys or d_out_keys or either not 4-byte aligned (INVALID_ARG), the workspace (WORKSPACE:
+ * NULL, not 256-byte aligned, or below lsdsort_kth_workspace_bytes), the device (NO_DEVICE).
+ * lsdsort_kth_workspace_bytes is a multiple of 256, monotonic in each argument, 0 where rows, cols or rows * cols is above
+ * LSDSORT_MAX_KEYS, and does not depend on the rank.  It is O(rows), never O(rows * cols): the control block, 16 B per row, and for
+ * rows above 16384 keys 8 KiB of counters per row and 4 B per 16384 keys. */
+LSDSORT_API size_t lsdsort_kth_workspace_bytes(size_t rows, size_t cols);
+LSDSORT_API int lsdsort_kth_device(const void* d_keys, size_t rows, size_t cols, size_t rank /* 0-based */,
+                                   int key_type /* lsdsort_key_type: U32, I32, F32 */, int largest,
+                                   void* d_out_keys /* [rows], caller's type */, uint32_t* d_out_idx /* [rows] or NULL */,
+                                   void* d_workspace, size_t workspace_bytes, void* hip_stream);
+
 /* After the stream has drained: LSDSORT_OK, or LSDSORT_ERR_DEVICE_FAULT if a kernel of the
  * last sort on this workspace gave up a bounded spin or refused destinations outside the output
  * (never expected; the output is then undefined).  Synchronises hip_stream.  With LSDSORT_REPROBE=1

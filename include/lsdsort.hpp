@@ -170,6 +170,29 @@ inline void topk16_device(const int16_t* d_keys, size_t rows, size_t cols, size_
                                 workspace_bytes_, hip_stream), "lsdsort_topk16_device");
 }
 
+// The key at 0-based `rank` of every row's stable sort and its position in the row, without sorting the rows or writing any winner
+// (lsdsort_kth_device): column `rank` of topk(.., k = rank + 1, ..).  uint32_t, int32_t or float by overload; d_keys is only read;
+// d_out_idx may be null.  Workspace of kth_workspace_bytes(rows, cols).
+inline size_t kth_workspace_bytes(size_t rows, size_t cols) { return lsdsort_kth_workspace_bytes(rows, cols); }
+inline void kth_device(const uint32_t* d_keys, size_t rows, size_t cols, size_t rank, uint32_t* d_out_keys, uint32_t* d_out_idx,
+                       void* d_workspace, size_t workspace_bytes_, bool largest = false, void* hip_stream = nullptr)
+{
+    check(lsdsort_kth_device(d_keys, rows, cols, rank, LSDSORT_KEY_U32, largest ? 1 : 0, d_out_keys, d_out_idx, d_workspace,
+                             workspace_bytes_, hip_stream), "lsdsort_kth_device");
+}
+inline void kth_device(const int32_t* d_keys, size_t rows, size_t cols, size_t rank, int32_t* d_out_keys, uint32_t* d_out_idx,
+                       void* d_workspace, size_t workspace_bytes_, bool largest = false, void* hip_stream = nullptr)
+{
+    check(lsdsort_kth_device(d_keys, rows, cols, rank, LSDSORT_KEY_I32, largest ? 1 : 0, d_out_keys, d_out_idx, d_workspace,
+                             workspace_bytes_, hip_stream), "lsdsort_kth_device");
+}
+inline void kth_device(const float* d_keys, size_t rows, size_t cols, size_t rank, float* d_out_keys, uint32_t* d_out_idx,
+                       void* d_workspace, size_t workspace_bytes_, bool largest = false, void* hip_stream = nullptr)
+{
+    check(lsdsort_kth_device(d_keys, rows, cols, rank, LSDSORT_KEY_F32, largest ? 1 : 0, d_out_keys, d_out_idx, d_workspace,
+                             workspace_bytes_, hip_stream), "lsdsort_kth_device");
+}
+
 // The stable sort of every row of a row-major [rows x cols] array of 16-bit keys with each key's position in its row
 // (lsdsort_rows16_device): uint16_t or int16_t by overload; float16 and bfloat16 bits are passed as uint16_t with the key type named.
 // d_out_keys may be d_keys (in place); d_out_idx may be null.  Workspace of rows16_workspace_bytes(rows, cols).

@@ -14,6 +14,7 @@ from .api import (  # noqa: F401  (api.__all__, name for name)
     GPUSort16, keys16_workspace_bytes, set_keys16_route, sort16, GPUTopK16, topk16_workspace_bytes, topk16_rows,
     GPUSortRows16, rows16_workspace_bytes, set_rows16_route, sort_rows16,
     GPUSortSegmented, segmented_workspace_bytes, sort_rows, GPUTopK, topk_workspace_bytes, topk_rows,
+    GPUKth, kth_workspace_bytes, kthvalue_rows, median_rows,
     BuildHistograms, BuildOffsets, RankScatter, DigitHistograms,
     MSBPartition, SplitterPartition, ThresholdPartition, sharded_thresholds,
 )

@@ -24,6 +24,7 @@ __all__ = [
     "GPUSort16", "keys16_workspace_bytes", "set_keys16_route", "sort16", "GPUTopK16", "topk16_workspace_bytes", "topk16_rows",
     "GPUSortRows16", "rows16_workspace_bytes", "set_rows16_route", "sort_rows16",
     "GPUSortSegmented", "segmented_workspace_bytes", "sort_rows", "GPUTopK", "topk_workspace_bytes", "topk_rows",
+    "GPUKth", "kth_workspace_bytes", "kthvalue_rows", "median_rows",
     "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
     "MSBPartition", "SplitterPartition", "ThresholdPartition", "sharded_thresholds",
 ]
@@ -366,6 +367,79 @@ def topk_rows(x, k: int, largest: bool = True, stream=None):
         values, indices = GPUTopK(flat, k, key_type="int32" if x.dtype == torch.int32 else "float32", largest=largest, stream=stream)
         lead = tuple(x.shape[:-1])
         return values.view(lead + (k,)), indices.view(lead + (k,)).to(torch.int64)
+
+
+def kth_workspace_bytes(rows: int, cols: int) -> int:
+    """Bytes of device workspace ``GPUKth`` needs for one rank of each of ``rows`` rows of ``cols`` keys (whatever the rank)."""
+    return int(lib().lsdsort_kth_workspace_bytes(rows, cols))
+
+
+def GPUKth(d_keys, rank: int, key_type: str = "uint32", largest: bool = False, return_indices: bool = True, workspace=None,
+           stream=None, check_fault: bool = False):
+    """The key at 0-based ``rank`` of every row's stable sort (``lsdsort_kth_device``): ``d_keys`` is a contiguous 1-D (one row) or
+    2-D int32 or float32 CUDA tensor whose 32 bits compare as ``key_type`` ("uint32" / "int32" / "float32", IEEE total order);
+    ``largest`` counts the rank from the largest key down.  Returns ``(values, indices)`` -- ``[rows]`` (0-D for 1-D input),
+    ``indices`` the int32 position within the row of that very item, or ``None`` without ``return_indices`` -- exactly column
+    ``rank`` of ``GPUTopK(d_keys, rank + 1, ...)``: among equal keys the stable sort's position, on every run.  ``d_keys`` is only
+    read.  A float32 tensor goes with ``key_type="float32"`` only; an int32 tensor holds the bit patterns of any of the three.
+    Stream-ordered; the rows are not sorted and no winner is written (a radix select, then a locate)."""
+    torch = _torch()
+    _dev(d_keys, "d_keys", (torch.int32, torch.float32), dims=(1, 2))
+    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
+    rank = int(rank)
+    if not 0 <= rank < cols:
+        raise ValueError("rank must be within 0 .. the row length - 1")
+    code = _key_type(key_type, KEY_TYPES_32)
+    if d_keys.dtype == torch.float32 and key_type != "float32":
+        raise TypeError('a float32 tensor selects with key_type="float32" only (an int32 tensor holds any of the three bit patterns)')
+    shape = () if d_keys.dim() == 1 else (rows,)
+    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
+        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
+        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
+    if workspace is None:
+        nbytes = kth_workspace_bytes(rows, cols)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_kth_workspace_bytes", "too many keys or rows")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    check(lib().lsdsort_kth_device(d_keys.data_ptr(), rows, cols, rank, code, int(bool(largest)), values.data_ptr(),
+                                   indices.data_ptr() if return_indices else None, workspace.data_ptr(), workspace.numel(),
+                                   _stream(stream)), "lsdsort_kth_device")
+    if check_fault and rows and cols:
+        _check_fault(workspace, stream)
+    return values, indices
+
+
+def kthvalue_rows(x, k: int, stream=None):
+    """``torch.kthvalue(x, k, dim=-1)`` for a contiguous int32 / float32 CUDA tensor of one or more dimensions: ``k`` is 1-based,
+    the k-th smallest of every row -> ``(values, int64 indices)`` of the leading shape.  float32 follows IEEE total order, not
+    torch's: a row with NaNs does NOT propagate NaN as ``torch.kthvalue`` / ``torch.median`` do -- NaNs sort by sign at the two
+    ends (+NaN above +inf, -NaN below -inf), and -0.0 below +0.0.  The index is the stable sort's (among equal keys the one the
+    stable sort puts at that rank), where torch leaves it unspecified among ties."""
+    torch = _torch()
+    _dev(x, "x", (torch.int32, torch.float32), contiguous=False)
+    if x.dim() == 0:
+        raise TypeError("x: at least one dimension")
+    cols = x.shape[-1]
+    k = int(k)
+    if not 1 <= k <= cols:
+        raise ValueError("k must be within 1 .. the row length")
+    with _on_stream(stream):
+        flat = x.contiguous().view(-1, cols)
+        values, indices = GPUKth(flat, k - 1, key_type="int32" if x.dtype == torch.int32 else "float32", stream=stream)
+        lead = tuple(x.shape[:-1])
+        return values.view(lead), indices.view(lead).to(torch.int64)
+
+
+def median_rows(x, stream=None):
+    """``torch.median(x, dim=-1)`` for a contiguous int32 / float32 CUDA tensor of one or more dimensions: ``kthvalue_rows`` at
+    rank ``(cols - 1) // 2``, the lower median torch returns -> ``(values, int64 indices)``.  float32 follows IEEE total order: a
+    row with NaNs does NOT propagate NaN as ``torch.median`` does (NaNs sort by sign at the two ends).  The index is the stable
+    sort's, where torch leaves it unspecified among ties."""
+    torch = _torch()
+    _dev(x, "x", (torch.int32, torch.float32), contiguous=False)
+    if x.dim() == 0 or x.shape[-1] == 0:
+        raise ValueError("x: at least one dimension, and a last one that is not empty")
+    return kthvalue_rows(x, (x.shape[-1] - 1) // 2 + 1, stream=stream)
 
 
 def GPUSortWide(d_keys, d_vals=None, r: int = 8, workspace=None, stream=None, check_fault: bool = False, key_type: str = "uint64",

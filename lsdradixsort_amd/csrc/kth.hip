@@ -1,0 +1,612 @@
+// kth.hip -- the key at ONE rank of every row of a [rows x cols] array, with its position (lsdsort_kth_device; DESIGN.md
+// section 6.8).  The counterpart of torch.kthvalue / torch.median on rows and of the `lower` / `higher` / `nearest` quantiles.
+//
+// No counterpart in the reference (it sorts one whole array, LSDRadixSort.cu:839-910).  Row r's result is item `rank` of the stable
+// sort of the row in the requested order: the key transform of lsd_kernels.hpp (to_sortable, with the complement for largest) is
+// applied where a key is read, and the raw key is what is stored.
+//
+// A radix SELECT by counting only, as in topk.hip, and a LOCATE instead of top-k's compact + sort:
+//   select   most significant digit first, count the digit of the keys that still match the prefix found so far, walk the counts
+//            from the best end to the bin that holds the wanted key: that bin's digit joins the prefix and `need` (which of the
+//            prefix's keys, in sorted order, is wanted; 1-based) shrinks by the number of keys in better bins.  Unlike top-k it
+//            cannot stop where the bin holds exactly `need` keys (the wanted one is then the LAST of them by value, not yet
+//            known): it stops where the bin holds ONE key, at the latest with all 32 bits in the prefix.
+//   locate   every key under the final prefix has the same value (one key, or all 32 bits fixed), so the wanted item is the
+//            `need`-th of them in POSITION order: per-lane counts, a wave scan, per-wave counts through LDS (and per-chunk counts
+//            through memory for long rows).  One lane stores the key, un-mapped, and its position.  No atomic-arrival order shows.
+//
+// Key reads.  A row starts 4 r cols bytes past d_keys, at any multiple of 4 within a 16-byte line.  Every kernel therefore splits
+// EACH ROW by address (Row, as topk16.hip does for 2-byte keys): `head` keys in front of the row's first 16-byte line (0..3), read
+// one by one, and the `body` from that line on, read as 16-byte groups of four keys; the last group of a row (or chunk) that is
+// not whole is read one by one too.  A lane holds four groups of its wave's tile: register 4 j + e is body position
+// q0 + 4 (64 j + lane) + e.
+// A key that does not exist.  Every 32-bit pattern is a real key, so no padding value can stand for "no key" (the 16-bit select's
+// 0xFFFFFFFF does not carry over).  Instead every tile comes with a per-lane VALIDITY MASK (bit i: register i holds a key of the
+// row; bit 16: the head register does), made from the positions alone where the tile is loaded, and every count and every match
+// is the AND of that bit with the comparison: a register without a key matches no (prefix, shift) whatever it holds.
+// Size classes (those of topk.hip, by cols):
+//   cols <= kWaveSegCap (1024)      one wavefront per row, eight rows per workgroup, no workgroup barrier: the row in its registers,
+//                                   8-bit digits counted in its own LDS slice.  4 B/key read, 8 B/row written.
+//   cols <= kLocalSortCap (16384)   one workgroup per row: the same with 16 wavefronts
+//   longer                          many workgroups per row (chunks of body positions; chunk 0 owns the head): digits of 11, 11 and
+//                                   10 bits counted in LDS, flushed into [row][2048] by global atomics, one workgroup per row walks
+//                                   the bins between the reads; a row whose bin holds one key skips the remaining levels.  Then one
+//                                   count pass (keys equal to the prefix, per chunk), a per-row pick of the chunk that holds the
+//                                   `need`-th of them, and a locate that reads that ONE chunk.  At most four reads of the row plus
+//                                   one chunk (16 B/key); nothing written but the counters and 8 B per row.
+// Every launch is sized from (rows, cols); phases are ordered by kernel boundaries; every store into the outputs is guarded by
+// row < rows.  Counts that do not reach the rank, or a locate that finds no key, raise a fault bit instead -- never expected.
+// Nothing here needs the returning-add rank form: the result does not depend on lsdsort_set_rank_method.
+#define LSDSORT_BUILD 1
+#include "../../include/lsdsort.h"
+
+#include "lsd_device.hpp"
+#include "lsd_host.hpp"
+
+namespace lsd {
+namespace {
+
+constexpr uint32_t kKthFaultCount = 1024u;    // fault word: the digit counts of a row do not reach the rank (never expected)
+constexpr uint32_t kKthFaultLocate = 2048u;   // fault word: no key was located for a row (never expected; nothing stored)
+constexpr size_t kCtlBytes = 256;
+constexpr int kRegs = 16;                     // keys per lane of a tile: four groups of four
+constexpr uint32_t kGroup = 4;                // keys of one 16-byte load
+constexpr uint32_t kHeadBit = 1u << kRegs;    // validity mask: the head register
+constexpr uint32_t kWaveTile = 64u * kRegs;   // body positions of one wave's tile
+constexpr uint32_t kBins = 2048;              // long rows: counters per row (11-bit digits)
+constexpr uint32_t kLongThreads = 256, kLongWaves = kLongThreads / kWave, kLongTile = kLongThreads * kRegs;
+constexpr uint32_t kMinChunk = 16384, kMaxChunks = 2048;
+constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
+
+size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
+
+template <int WAVES>
+__device__ __forceinline__ void group_sync()
+{
+    if (WAVES == 1) wave_sync();
+    else __syncthreads();
+}
+
+// One row by address: key p of the row is keys[p]; keys [0, head) lie in front of the row's first 16-byte line, the `body` keys
+// from there on are keys[head + q], q < body, and q = 4 g is the start of a 16-byte line.
+struct Row {
+    const uint32_t* keys;
+    uint32_t head, body;
+};
+__device__ __forceinline__ Row row_of(const uint32_t* keys, uint32_t row, uint32_t cols)
+{
+    Row r;
+    r.keys = keys + (size_t)row * cols;
+    const uint32_t to_line = ((16u - ((uint32_t)(uintptr_t)r.keys & 15u)) & 15u) / (uint32_t)sizeof(uint32_t);
+    r.head = to_line < cols ? to_line : cols;
+    r.body = cols - r.head;
+    return r;
+}
+
+// The wave's tile from body position q0 (a multiple of four) on, valid below `end`: a whole group by one 16-byte load, the others
+// key by key.  Returns the validity mask of the sixteen registers; a register without a key holds zero and its bit is clear.
+__device__ __forceinline__ uint32_t load_tile(const Row& r, uint32_t q0, uint32_t end, uint32_t lane, const KeyTransform& xf,
+                                              uint32_t (&t)[kRegs])
+{
+    uint32_t vm = 0u;
+#pragma unroll
+    for (int j = 0; j < kRegs / 4; j++) {
+        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroup;
+        if (q < end && end - q >= kGroup) {
+            const uint4 v = *reinterpret_cast<const uint4*>(r.keys + r.head + q);
+            t[4 * j] = to_sortable(v.x, xf);
+            t[4 * j + 1] = to_sortable(v.y, xf);
+            t[4 * j + 2] = to_sortable(v.z, xf);
+            t[4 * j + 3] = to_sortable(v.w, xf);
+            vm |= 0xFu << (4 * j);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                t[4 * j + e] = 0u;
+                if (q < end && q + (uint32_t)e < end) {
+                    t[4 * j + e] = to_sortable(r.keys[r.head + q + (uint32_t)e], xf);
+                    vm |= 1u << (4 * j + e);
+                }
+            }
+        }
+    }
+    return vm;
+}
+// head key `lane` of the row, for the one wave that owns the head: its validity bit, and the key into h
+__device__ __forceinline__ uint32_t load_head(const Row& r, uint32_t lane, const KeyTransform& xf, uint32_t& h)
+{
+    h = 0u;
+    if (lane >= r.head) return 0u;
+    h = to_sortable(r.keys[lane], xf);
+    return kHeadBit;
+}
+
+struct Outputs {
+    uint32_t* keys;       // [rows], raw keys
+    uint32_t* idx;        // [rows] positions, may be null
+    uint32_t rows;
+    uint32_t* fault;
+};
+
+// Locate within one tile held in registers (load_tile at q0, validity mask vm; with kHeadBit in vm of some lanes: the head keys h
+// in front of it).  `base`: the keys under the prefix before this tile in the row; it moves on past the tile.  If the `need`-th
+// (1-based) such key of the row lies in this tile, the lane that holds it stores it.  Returns whether it did (uniform over the
+// group).  s_wc: WAVES words.
+template <int WAVES>
+__device__ __forceinline__ bool locate_tile(const uint32_t (&t)[kRegs], uint32_t h, uint32_t vm, uint32_t q0, const Row& r, uint32_t prefix,
+                                            uint32_t shift, uint32_t need, uint32_t& base, volatile lds_u32* s_wc, uint32_t wave,
+                                            uint32_t lane, uint32_t row, const Outputs& o, const KeyTransform& xf)
+{
+    uint32_t em = ((vm & kHeadBit) != 0u && (h >> shift) == prefix) ? kHeadBit : 0u;   // the keys under the prefix
+#pragma unroll
+    for (int i = 0; i < kRegs; i++) em |= (((vm >> i) & 1u) != 0u && (t[i] >> shift) == prefix) ? 1u << i : 0u;
+    const uint32_t mine = wave_sum((uint32_t)__builtin_popcount(em));
+    uint32_t before = base, all = mine;
+    if (WAVES > 1) {
+        if (lane == 0u) s_wc[wave] = mine;
+        __syncthreads();
+        all = 0u;
+        for (uint32_t w = 0; w < (uint32_t)WAVES; w++) {
+            const uint32_t c = s_wc[w];
+            if (w < wave) before += c;
+            all += c;
+        }
+        __syncthreads();   // the next tile writes s_wc again
+    }
+    const bool here = base < need && need - base <= all;   // uniform
+    if (here) {
+        auto store = [&](uint32_t key, uint32_t pos) {
+            if (row < o.rows) {
+                o.keys[row] = from_sortable(key, xf);
+                if (o.idx) o.idx[row] = pos;
+            }
+        };
+        // position order: the head keys by lane, then group j of lane 0, 1, .. 63, j = 0 .. 3
+        const uint32_t ch = em >> kRegs;
+        const uint32_t hi = wave_inclusive_scan(ch);
+        if (ch != 0u && before + hi == need) store(h, lane);
+        before += (uint32_t)__builtin_amdgcn_readlane((int)hi, 63);
+#pragma unroll
+        for (int j = 0; j < kRegs / 4; j++) {
+            const uint32_t g = (em >> (4 * j)) & 0xFu, c = (uint32_t)__builtin_popcount(g);
+            const uint32_t incl = wave_inclusive_scan(c), lo = before + incl - c;
+            if (lo < need && need - lo <= c) {
+                uint32_t left = need - lo;   // 1 .. c: which of this group's matching keys
+                const uint32_t pos = r.head + q0 + ((uint32_t)j * 64u + lane) * kGroup;
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    if (((g >> e) & 1u) != 0u && --left == 0u) store(t[4 * j + e], pos + (uint32_t)e);
+                }
+            }
+            before += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        }
+    }
+    base += all;
+    return here;
+}
+
+// ---- short rows: one wavefront (WAVES = 1, eight rows per workgroup) or one workgroup (WAVES = 16) per row ----------------------
+struct ShortParams {
+    const uint32_t* keys;
+    uint32_t cols, rank;
+    KeyTransform xf;
+    Outputs out;
+};
+
+template <int WAVES>
+__global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) kth_short_kernel(const ShortParams p)
+{
+    constexpr int kGroups = WAVES == 1 ? 8 : 1;      // rows in flight per workgroup
+    constexpr int kSlice = 256 + 8 + WAVES;          // per row: digit counters, the found bin, per-wave counts
+    __shared__ uint32_t smem[kGroups * kSlice];
+    const uint32_t lane = threadIdx.x & 63u, wave_of_block = threadIdx.x >> 6;
+    const uint32_t group = WAVES == 1 ? wave_of_block : 0u, wave = WAVES == 1 ? 0u : wave_of_block;
+    volatile lds_u32* const s_cnt = (volatile lds_u32*)((lds_u32*)smem + group * kSlice);
+    volatile lds_u32* const s_found = s_cnt + 256;
+    volatile lds_u32* const s_wc = s_cnt + 264;
+    // `row` is the same for every thread of a group (a wave, or the whole workgroup): its barriers are reached together
+    for (uint32_t row = blockIdx.x * kGroups + group; row < p.out.rows; row += gridDim.x * kGroups) {
+        const Row r = row_of(p.keys, row, p.cols);
+        const uint32_t q0 = wave * kWaveTile;
+        uint32_t t[kRegs], h = 0u;
+        uint32_t vm = load_tile(r, q0, r.body, lane, p.xf, t);
+        if (wave == 0u) vm |= load_head(r, lane, p.xf, h);
+        uint32_t prefix = 0u, shift = 24u, need = p.rank + 1u;
+#pragma unroll 1
+        for (int round = 0; round < 4; round++) {
+            shift = 24u - 8u * (uint32_t)round;
+            if (wave == 0u) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) s_cnt[j * 64 + lane] = 0u;
+                if (lane == 0u) s_found[0] = 0xFFFFFFFFu;
+            }
+            group_sync<WAVES>();
+            // round 0: every key there is; later: those whose bits above the digit are the prefix.  Always under the validity bit.
+            auto count = [&](uint32_t key, bool valid) {
+                const bool match = round == 0 || ((key >> shift) >> 8) == prefix;
+                if (valid && match)
+                    __hip_atomic_fetch_add((lds_u32*)&s_cnt[(key >> shift) & 0xFFu], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            };
+#pragma unroll
+            for (int i = 0; i < kRegs; i++) count(t[i], ((vm >> i) & 1u) != 0u);
+            count(h, (vm & kHeadBit) != 0u);
+            group_sync<WAVES>();
+            if (wave == 0u) {   // four bins per lane, from the best end
+                uint32_t c[4], sum = 0u;
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    c[j] = s_cnt[lane * 4u + j];
+                    sum += c[j];
+                }
+                uint32_t run = wave_inclusive_scan(sum) - sum;
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    if (run < need && need - run <= c[j]) {   // at most one bin of the row
+                        s_found[0] = lane * 4u + j;
+                        s_found[1] = run;
+                        s_found[2] = c[j];
+                    }
+                    run += c[j];
+                }
+            }
+            group_sync<WAVES>();
+            const uint32_t bin = s_found[0], before = s_found[1], count_in_bin = s_found[2];
+            group_sync<WAVES>();   // the next round writes s_found again
+            if (bin > 0xFFu) {     // (uniform) the counts do not reach the rank: nothing is located
+                if (wave == 0u && lane == 0u) atomicOr(p.out.fault, kKthFaultCount);
+                prefix = 0u;
+                shift = 0u;
+                need = 0u;
+                break;
+            }
+            prefix = (prefix << 8) | bin;
+            need -= before;
+            if (count_in_bin == 1u) break;   // (uniform) one key under the prefix: it is the one (need is 1)
+        }
+        uint32_t base = 0u;
+        const bool found = locate_tile<WAVES>(t, h, vm, q0, r, prefix, shift, need, base, s_wc, wave, lane, row, p.out, p.xf);
+        if (!found && need != 0u && wave == 0u && lane == 0u) atomicOr(p.out.fault, kKthFaultLocate);
+        group_sync<WAVES>();
+    }
+}
+
+// ---- long rows ------------------------------------------------------------------------------------------------------------------
+// Row state in the workspace (uint4).  During the select: x prefix, y shift (32: no level has run), z need, w done (the select
+// stopped: later levels return at once).  After the pick: x prefix, y shift, z which of the chunk's keys under the prefix is the
+// wanted one (1-based; 0: none), w the chunk that holds it.
+struct LongParams {
+    const uint32_t* keys;
+    uint32_t cols;
+    uint32_t chunk, chunks;       // body positions per chunk (a multiple of kLongTile), chunks per row
+    uint32_t chunk_cap;           // row stride of `counts`
+    uint4* state;
+    uint32_t* hist;               // [rows][kBins], zero on entry to every level
+    uint32_t* counts;             // [rows][chunk_cap]: keys under the prefix, per chunk
+    KeyTransform xf;
+    Outputs out;
+};
+__device__ __forceinline__ uint32_t level_shift(int level) { return level == 0 ? 21u : (level == 1 ? 10u : 0u); }
+__device__ __forceinline__ uint32_t level_bits(int level) { return level == 2 ? 10u : 11u; }
+
+// Chunk c of a row is body positions [lo, hi) -- in EVERY kernel below -- and chunk 0 owns the head keys as well.  A row whose
+// head is not empty may leave its last chunk empty (lo == hi): the chunks are counted from cols.
+struct ChunkRange {
+    uint32_t lo, hi;
+};
+__device__ __forceinline__ ChunkRange chunk_of(const Row& r, const LongParams& p, uint32_t c)
+{
+    ChunkRange g;
+    g.lo = c * p.chunk < r.body ? c * p.chunk : r.body;
+    g.hi = r.body - g.lo < p.chunk ? r.body : g.lo + p.chunk;
+    return g;
+}
+
+// control block, counters and row states of a call (a kernel rather than memsets: one kind of node in a captured graph)
+__global__ void __launch_bounds__(256) kth_clear_kernel(uint32_t* ctl, uint32_t* hist, uint32_t hist_words, uint4* state, uint32_t rows,
+                                                        uint32_t need)
+{
+    const uint32_t at = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
+    if (at < (uint32_t)(kCtlBytes / 4)) ctl[at] = 0u;
+    for (uint32_t q = at; q < hist_words; q += step) hist[q] = 0u;
+    if (state)
+        for (uint32_t r = at; r < rows; r += step) state[r] = make_uint4(0u, 32u, need, 0u);
+}
+
+// One register of every lane into the LDS counters.  A wave whose matching keys all carry one digit (a shared prefix, few values,
+// all equal) adds their number once instead of piling 64 adds onto one word.
+__device__ __forceinline__ void count_digit(uint32_t* s_hist, bool match, uint32_t bin, uint32_t lane)
+{
+    const uint64_t m = __ballot(match);
+    if (m == 0ull) return;   // uniform
+    const uint32_t leader = (uint32_t)__builtin_ctzll(m);
+    const uint32_t lead_bin = (uint32_t)__builtin_amdgcn_readlane((int)bin, (int)leader);
+    if (__ballot(match && bin != lead_bin) == 0ull) {
+        if (lane == leader) atomicAdd(&s_hist[lead_bin], popc64(m));
+    } else if (match) {
+        atomicAdd(&s_hist[bin], 1u);
+    }
+}
+
+// One chunk of one row per workgroup: the digit of every key under the row's prefix, counted in LDS.
+template <int LEVEL>
+__global__ void __launch_bounds__(kLongThreads) kth_hist_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_hist[kBins];
+    const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    if (st.w != 0u) return;   // uniform
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    for (uint32_t b = tid; b < kBins; b += kLongThreads) s_hist[b] = 0u;
+    __syncthreads();
+    const Row r = row_of(p.keys, row, p.cols);
+    const ChunkRange g = chunk_of(r, p, c);
+    const uint32_t shift = level_shift(LEVEL), mask = (1u << level_bits(LEVEL)) - 1u;
+    auto count = [&](uint32_t key, bool valid) {
+        const bool match = valid && (LEVEL == 0 || (key >> st.y) == st.x);
+        count_digit(s_hist, match, (key >> shift) & mask, lane);
+    };
+    if (c == 0u && wave == 0u) {   // uniform
+        uint32_t h;
+        const uint32_t hv = load_head(r, lane, p.xf, h);
+        count(h, hv != 0u);
+    }
+    for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
+        uint32_t t[kRegs];
+        const uint32_t vm = load_tile(r, tile + wave * kWaveTile, g.hi, lane, p.xf, t);
+#pragma unroll
+        for (int i = 0; i < kRegs; i++) count(t[i], ((vm >> i) & 1u) != 0u);
+    }
+    __syncthreads();
+    uint32_t* const out = p.hist + (size_t)row * kBins;
+    for (uint32_t b = tid; b < kBins; b += kLongThreads) {
+        const uint32_t v = s_hist[b];
+        if (v != 0u) atomicAdd(out + b, v);
+    }
+}
+
+// One workgroup per row: walk the bins from the best end to the one that holds the wanted key; the counters go back to zero.
+template <int LEVEL>
+__global__ void __launch_bounds__(256) kth_scan_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_part[4];
+    __shared__ uint32_t s_found[3];
+    const uint32_t row = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    if (st.w != 0u) return;   // uniform
+    uint32_t* const h = p.hist + (size_t)row * kBins;
+    constexpr uint32_t E = kBins / 256u;
+    uint32_t c[E], sum = 0u;
+#pragma unroll
+    for (uint32_t e = 0; e < E; e++) {
+        c[e] = h[tid * E + e];
+        h[tid * E + e] = 0u;
+        sum += c[e];
+    }
+    if (tid == 0u) s_found[0] = 0xFFFFFFFFu;
+    uint32_t run = group_exclusive_scan<4>(sum, lane, wave, s_part);
+    const uint32_t need = st.z;
+#pragma unroll
+    for (uint32_t e = 0; e < E; e++) {
+        if (run < need && need - run <= c[e]) {   // at most one bin of the row
+            s_found[0] = tid * E + e;
+            s_found[1] = run;
+            s_found[2] = c[e];
+        }
+        run += c[e];
+    }
+    __syncthreads();
+    if (tid != 0u) return;
+    const uint32_t bin = s_found[0], before = s_found[1], count = s_found[2];
+    if (bin >= kBins) {   // the counts do not reach the rank: nothing is located
+        atomicOr(p.out.fault, kKthFaultCount);
+        p.state[row] = make_uint4(0u, 0u, 0u, 1u);
+        return;
+    }
+    const uint32_t prefix = LEVEL == 0 ? bin : ((st.x << level_bits(LEVEL)) | bin);
+    p.state[row] = make_uint4(prefix, level_shift(LEVEL), need - before, (LEVEL == 2 || count == 1u) ? 1u : 0u);
+}
+
+// the keys under the prefix, per chunk
+__global__ void __launch_bounds__(kLongThreads) kth_count_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_part[kLongWaves];
+    const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const Row r = row_of(p.keys, row, p.cols);
+    const ChunkRange g = chunk_of(r, p, c);
+    uint32_t ne = 0u;
+    if (st.y < 32u && st.z != 0u) {   // (uniform) else: a row no scan has visited, or one whose counts fell short -- never
+        if (c == 0u && wave == 0u) {   // uniform
+            uint32_t h;
+            const uint32_t hv = load_head(r, lane, p.xf, h);
+            ne += (hv != 0u && (h >> st.y) == st.x) ? 1u : 0u;
+        }
+        for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
+            uint32_t t[kRegs];
+            const uint32_t vm = load_tile(r, tile + wave * kWaveTile, g.hi, lane, p.xf, t);
+#pragma unroll
+            for (int i = 0; i < kRegs; i++) ne += (((vm >> i) & 1u) != 0u && (t[i] >> st.y) == st.x) ? 1u : 0u;
+        }
+    }
+    ne = wave_sum(ne);
+    if (lane == 0u) s_part[wave] = ne;
+    __syncthreads();
+    if (tid == 0u) {
+        uint32_t e = 0u;
+        for (uint32_t w = 0; w < kLongWaves; w++) e += s_part[w];
+        p.counts[(size_t)row * p.chunk_cap + c] = e;
+    }
+}
+
+// One workgroup per row: the chunk that holds the `need`-th key under the prefix, and which of that chunk's such keys it is.
+__global__ void __launch_bounds__(256) kth_pick_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_part[4];
+    __shared__ uint32_t s_found[2];
+    const uint32_t row = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    const uint32_t* const counts = p.counts + (size_t)row * p.chunk_cap;
+    constexpr uint32_t E = kMaxChunks / 256u;
+    uint32_t c[E], sum = 0u;
+#pragma unroll
+    for (uint32_t e = 0; e < E; e++) {
+        c[e] = tid * E + e < p.chunks ? counts[tid * E + e] : 0u;
+        sum += c[e];
+    }
+    if (tid == 0u) s_found[0] = kNoChunk;
+    uint32_t run = group_exclusive_scan<4>(sum, lane, wave, s_part);
+    const uint32_t need = st.y < 32u ? st.z : 0u;
+#pragma unroll
+    for (uint32_t e = 0; e < E; e++) {
+        if (run < need && need - run <= c[e]) {   // at most one chunk of the row
+            s_found[0] = tid * E + e;
+            s_found[1] = need - run;
+        }
+        run += c[e];
+    }
+    __syncthreads();
+    if (tid != 0u) return;
+    const uint32_t chunk = s_found[0];
+    if (chunk == kNoChunk) {   // the keys under the prefix are fewer than `need`: nothing is located
+        atomicOr(p.out.fault, kKthFaultLocate);
+        p.state[row] = make_uint4(0u, 0u, 0u, kNoChunk);
+        return;
+    }
+    p.state[row] = make_uint4(st.x, st.y, s_found[1], chunk);
+}
+
+// One workgroup per row reads the picked chunk, and only up to the tile that holds the key.
+__global__ void __launch_bounds__(kLongThreads) kth_locate_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_wc_raw[kLongWaves];
+    const uint32_t row = blockIdx.x;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    if (st.z == 0u || st.w >= p.chunks) return;   // (uniform) nothing was picked: the fault bit is already set
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const Row r = row_of(p.keys, row, p.cols);
+    const ChunkRange g = chunk_of(r, p, st.w);
+    volatile lds_u32* const s_wc = (volatile lds_u32*)(lds_u32*)s_wc_raw;
+    uint32_t base = 0u;
+    bool found = false;
+    // chunk 0 has at least one tile (a long row's body is longer than its head), and its first tile carries the head
+    for (uint32_t tile = g.lo; tile < g.hi && !found; tile += kLongTile) {   // uniform
+        const uint32_t q0 = tile + wave * kWaveTile;
+        uint32_t t[kRegs], h = 0u;
+        uint32_t vm = load_tile(r, q0, g.hi, lane, p.xf, t);
+        if (st.w == 0u && tile == g.lo && wave == 0u) vm |= load_head(r, lane, p.xf, h);   // uniform
+        found = locate_tile<(int)kLongWaves>(t, h, vm, q0, r, st.x, st.y, st.z, base, s_wc, wave, lane, row, p.out, p.xf);
+    }
+    if (!found && tid == 0u) atomicOr(p.out.fault, kKthFaultLocate);
+}
+
+// Long rows are cut into chunks of a multiple of kLongTile keys, about kMaxChunks of them over the whole array.
+struct Chunks {
+    uint32_t chunk, per_row;
+};
+Chunks chunks_for(size_t rows, size_t cols)
+{
+    const size_t n = rows * cols;
+    size_t chunk = max_sz(kMinChunk, (n + kMaxChunks - 1) / kMaxChunks);
+    chunk = (chunk + kLongTile - 1) / kLongTile * kLongTile;
+    return Chunks{(uint32_t)chunk, (uint32_t)((cols + chunk - 1) / chunk)};
+}
+size_t chunk_cap_for(size_t cols) { return min_sz(kMaxChunks, (cols + kMinChunk - 1) / kMinChunk); }
+
+// Workspace: control | row states (16 B per row) | counters [rows][2048] | chunk counts (4 B per chunk) -- the last two for rows
+// above kLocalSortCap keys only.  At most 256 + rows (16 + 8192 + 4 ceil(cols / 16384)) + 3 * 255 bytes; never O(rows * cols).
+struct KthLayout {
+    size_t state, hist, counts, total;
+};
+KthLayout kth_layout(size_t rows, size_t cols)
+{
+    KthLayout L{};
+    const bool is_long = cols > (size_t)kLocalSortCap;
+    size_t off = kCtlBytes;
+    L.state = off;    off = align_up(off + rows * 16);
+    L.hist = off;     off = align_up(off + (is_long ? rows * kBins * 4 : 0));
+    L.counts = off;   off = align_up(off + (is_long ? rows * chunk_cap_for(cols) * 4 : 0));
+    L.total = off;
+    return L;
+}
+
+int run_kth(const uint32_t* keys, size_t rows, size_t cols, size_t rank, const KeyTransform& xf, uint32_t* out_keys, uint32_t* out_idx,
+            char* ws, const KthLayout& L, hipStream_t stream)
+{
+    uint32_t* const ctl = reinterpret_cast<uint32_t*>(ws);
+    const Outputs out{out_keys, out_idx, (uint32_t)rows, ctl};
+    if (cols <= (size_t)kLocalSortCap) {
+        const ShortParams sp{keys, (uint32_t)cols, (uint32_t)rank, xf, out};
+        hipLaunchKernelGGL(kth_clear_kernel, dim3(1), dim3(256), 0, stream, ctl, (uint32_t*)nullptr, 0u, (uint4*)nullptr, 0u, 0u);
+        if (cols <= (size_t)kWaveSegCap)
+            hipLaunchKernelGGL(kth_short_kernel<1>, dim3(grid_for(rows, 8, 16384)), dim3(512), 0, stream, sp);
+        else
+            hipLaunchKernelGGL(kth_short_kernel<16>, dim3(grid_for(rows, 1, 4096)), dim3(1024), 0, stream, sp);
+        LSD_HIP(hipGetLastError());
+        return LSDSORT_OK;
+    }
+    const Chunks ch = chunks_for(rows, cols);
+    LongParams lp{};
+    lp.keys = keys;
+    lp.cols = (uint32_t)cols;
+    lp.chunk = ch.chunk;
+    lp.chunks = ch.per_row;
+    lp.chunk_cap = (uint32_t)chunk_cap_for(cols);
+    lp.state = reinterpret_cast<uint4*>(ws + L.state);
+    lp.hist = reinterpret_cast<uint32_t*>(ws + L.hist);
+    lp.counts = reinterpret_cast<uint32_t*>(ws + L.counts);
+    lp.xf = xf;
+    lp.out = out;
+    if (lp.chunks > lp.chunk_cap) return LSDSORT_ERR_INVALID_ARG;   // never: chunks are at least kMinChunk keys
+    const uint32_t grid = (uint32_t)(rows * lp.chunks), row_grid = (uint32_t)rows;
+    hipLaunchKernelGGL(kth_clear_kernel, dim3(grid_for(rows * kBins, 1024, 4096)), dim3(256), 0, stream, ctl, lp.hist,
+                       (uint32_t)(rows * kBins), lp.state, (uint32_t)rows, (uint32_t)rank + 1u);
+    hipLaunchKernelGGL(kth_hist_kernel<0>, dim3(grid), dim3(kLongThreads), 0, stream, lp);
+    hipLaunchKernelGGL(kth_scan_kernel<0>, dim3(row_grid), dim3(256), 0, stream, lp);
+    hipLaunchKernelGGL(kth_hist_kernel<1>, dim3(grid), dim3(kLongThreads), 0, stream, lp);
+    hipLaunchKernelGGL(kth_scan_kernel<1>, dim3(row_grid), dim3(256), 0, stream, lp);
+    hipLaunchKernelGGL(kth_hist_kernel<2>, dim3(grid), dim3(kLongThreads), 0, stream, lp);
+    hipLaunchKernelGGL(kth_scan_kernel<2>, dim3(row_grid), dim3(256), 0, stream, lp);
+    LSD_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kth_count_kernel, dim3(grid), dim3(kLongThreads), 0, stream, lp);
+    hipLaunchKernelGGL(kth_pick_kernel, dim3(row_grid), dim3(256), 0, stream, lp);
+    hipLaunchKernelGGL(kth_locate_kernel, dim3(row_grid), dim3(kLongThreads), 0, stream, lp);
+    LSD_HIP(hipGetLastError());
+    return LSDSORT_OK;
+}
+
+}  // namespace
+}  // namespace lsd
+
+extern "C" {
+
+size_t lsdsort_kth_workspace_bytes(size_t rows, size_t cols)
+{
+    if (rows > LSDSORT_MAX_KEYS || cols > LSDSORT_MAX_KEYS) return 0;
+    if (rows != 0 && cols > LSDSORT_MAX_KEYS / rows) return 0;
+    return lsd::kth_layout(rows, cols).total;
+}
+
+int lsdsort_kth_device(const void* d_keys, size_t rows, size_t cols, size_t rank, int key_type, int largest, void* d_out_keys,
+                       uint32_t* d_out_idx, void* d_workspace, size_t workspace_bytes, void* hip_stream)
+{
+    lsd::KeyTransform xf;
+    LSD_TRY(lsd::key_transform(key_type, largest, &xf));
+    if (rows > LSDSORT_MAX_KEYS || (rows != 0 && cols > LSDSORT_MAX_KEYS / rows)) return LSDSORT_ERR_TOO_LARGE;
+    if (rows == 0 || cols == 0) return LSDSORT_OK;   // before the rank: an empty row has no valid rank
+    if (rank >= cols) return LSDSORT_ERR_INVALID_ARG;
+    if (!d_keys || !d_out_keys || (((uintptr_t)d_keys | (uintptr_t)d_out_keys) & 3)) return LSDSORT_ERR_INVALID_ARG;
+    const lsd::KthLayout L = lsd::kth_layout(rows, cols);
+    if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.total)) return LSDSORT_ERR_WORKSPACE;
+    int rank_method = 0;   // asked for the device set-up alone: nothing here ranks with the returning add
+    LSD_TRY(lsd::device_rank_method(8, &rank_method));
+    return lsd::run_kth(static_cast<const uint32_t*>(d_keys), rows, cols, rank, xf, static_cast<uint32_t*>(d_out_keys), d_out_idx,
+                        static_cast<char*>(d_workspace), L, static_cast<hipStream_t>(hip_stream));
+}
+
+}  // extern "C"
