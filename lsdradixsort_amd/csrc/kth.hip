@@ -5,7 +5,9 @@
 // sort of the row in the requested order: the key transform of lsd_kernels.hpp (to_sortable, with the complement for largest) is
 // applied where a key is read, and the raw key is what is stored.
 //
-// A radix SELECT by counting only, as in topk.hip, and a LOCATE instead of top-k's compact + sort:
+// A radix SELECT by counting only, as in topk.hip, and a LOCATE instead of top-k's compact + sort.  The select's skeleton is
+// radix_select.hpp's, shared with topk.hip and topk16.hip, with the stop rule StopKth; this unit adds the loads (Row<uint32_t> with
+// a validity mask), locate_tile and the count, pick and locate kernels.
 //   select   most significant digit first, count the digit of the keys that still match the prefix found so far, walk the counts
 //            from the best end to the bin that holds the wanted key: that bin's digit joins the prefix and `need` (which of the
 //            prefix's keys, in sorted order, is wanted; 1-based) shrinks by the number of keys in better bins.  Unlike top-k it
@@ -42,50 +44,21 @@
 
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
+#include "radix_select.hpp"
 
 namespace lsd {
 namespace {
 
 constexpr uint32_t kKthFaultCount = 1024u;    // fault word: the digit counts of a row do not reach the rank (never expected)
 constexpr uint32_t kKthFaultLocate = 2048u;   // fault word: no key was located for a row (never expected; nothing stored)
-constexpr size_t kCtlBytes = 256;
-constexpr int kRegs = 16;                     // keys per lane of a tile: four groups of four
 constexpr uint32_t kGroup = 4;                // keys of one 16-byte load
 constexpr uint32_t kHeadBit = 1u << kRegs;    // validity mask: the head register
-constexpr uint32_t kWaveTile = 64u * kRegs;   // body positions of one wave's tile
-constexpr uint32_t kBins = 2048;              // long rows: counters per row (11-bit digits)
-constexpr uint32_t kLongThreads = 256, kLongWaves = kLongThreads / kWave, kLongTile = kLongThreads * kRegs;
-constexpr uint32_t kMinChunk = 16384, kMaxChunks = 2048;
 constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
-
-size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
-
-template <int WAVES>
-__device__ __forceinline__ void group_sync()
-{
-    if (WAVES == 1) wave_sync();
-    else __syncthreads();
-}
-
-// One row by address: key p of the row is keys[p]; keys [0, head) lie in front of the row's first 16-byte line, the `body` keys
-// from there on are keys[head + q], q < body, and q = 4 g is the start of a 16-byte line.
-struct Row {
-    const uint32_t* keys;
-    uint32_t head, body;
-};
-__device__ __forceinline__ Row row_of(const uint32_t* keys, uint32_t row, uint32_t cols)
-{
-    Row r;
-    r.keys = keys + (size_t)row * cols;
-    const uint32_t to_line = ((16u - ((uint32_t)(uintptr_t)r.keys & 15u)) & 15u) / (uint32_t)sizeof(uint32_t);
-    r.head = to_line < cols ? to_line : cols;
-    r.body = cols - r.head;
-    return r;
-}
+using Row32 = Row<uint32_t>;   // a lane holds four 16-byte groups of four keys of its wave's tile
 
 // The wave's tile from body position q0 (a multiple of four) on, valid below `end`: a whole group by one 16-byte load, the others
 // key by key.  Returns the validity mask of the sixteen registers; a register without a key holds zero and its bit is clear.
-__device__ __forceinline__ uint32_t load_tile(const Row& r, uint32_t q0, uint32_t end, uint32_t lane, const KeyTransform& xf,
+__device__ __forceinline__ uint32_t load_tile(const Row32& r, uint32_t q0, uint32_t end, uint32_t lane, const KeyTransform& xf,
                                               uint32_t (&t)[kRegs])
 {
     uint32_t vm = 0u;
@@ -113,7 +86,7 @@ __device__ __forceinline__ uint32_t load_tile(const Row& r, uint32_t q0, uint32_
     return vm;
 }
 // head key `lane` of the row, for the one wave that owns the head: its validity bit, and the key into h
-__device__ __forceinline__ uint32_t load_head(const Row& r, uint32_t lane, const KeyTransform& xf, uint32_t& h)
+__device__ __forceinline__ uint32_t load_head(const Row32& r, uint32_t lane, const KeyTransform& xf, uint32_t& h)
 {
     h = 0u;
     if (lane >= r.head) return 0u;
@@ -133,7 +106,7 @@ struct Outputs {
 // (1-based) such key of the row lies in this tile, the lane that holds it stores it.  Returns whether it did (uniform over the
 // group).  s_wc: WAVES words.
 template <int WAVES>
-__device__ __forceinline__ bool locate_tile(const uint32_t (&t)[kRegs], uint32_t h, uint32_t vm, uint32_t q0, const Row& r, uint32_t prefix,
+__device__ __forceinline__ bool locate_tile(const uint32_t (&t)[kRegs], uint32_t h, uint32_t vm, uint32_t q0, const Row32& r, uint32_t prefix,
                                             uint32_t shift, uint32_t need, uint32_t& base, volatile lds_u32* s_wc, uint32_t wave,
                                             uint32_t lane, uint32_t row, const Outputs& o, const KeyTransform& xf)
 {
@@ -206,66 +179,25 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) kth_short_kernel(cons
     volatile lds_u32* const s_wc = s_cnt + 264;
     // `row` is the same for every thread of a group (a wave, or the whole workgroup): its barriers are reached together
     for (uint32_t row = blockIdx.x * kGroups + group; row < p.out.rows; row += gridDim.x * kGroups) {
-        const Row r = row_of(p.keys, row, p.cols);
+        const Row32 r = row_of(p.keys, row, p.cols);
         const uint32_t q0 = wave * kWaveTile;
         uint32_t t[kRegs], h = 0u;
         uint32_t vm = load_tile(r, q0, r.body, lane, p.xf, t);
         if (wave == 0u) vm |= load_head(r, lane, p.xf, h);
-        uint32_t prefix = 0u, shift = 24u, need = p.rank + 1u;
-#pragma unroll 1
-        for (int round = 0; round < 4; round++) {
-            shift = 24u - 8u * (uint32_t)round;
-            if (wave == 0u) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) s_cnt[j * 64 + lane] = 0u;
-                if (lane == 0u) s_found[0] = 0xFFFFFFFFu;
-            }
-            group_sync<WAVES>();
-            // round 0: every key there is; later: those whose bits above the digit are the prefix.  Always under the validity bit.
-            auto count = [&](uint32_t key, bool valid) {
+        // round 0: every key there is; later: those whose bits above the digit are the prefix.  Always under the validity bit.
+        auto count = [&](int round, uint32_t shift, uint32_t prefix, auto add) __attribute__((always_inline)) {
+            auto one = [&](uint32_t key, bool valid) __attribute__((always_inline)) {
                 const bool match = round == 0 || ((key >> shift) >> 8) == prefix;
-                if (valid && match)
-                    __hip_atomic_fetch_add((lds_u32*)&s_cnt[(key >> shift) & 0xFFu], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (valid && match) add(key);
             };
 #pragma unroll
-            for (int i = 0; i < kRegs; i++) count(t[i], ((vm >> i) & 1u) != 0u);
-            count(h, (vm & kHeadBit) != 0u);
-            group_sync<WAVES>();
-            if (wave == 0u) {   // four bins per lane, from the best end
-                uint32_t c[4], sum = 0u;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    c[j] = s_cnt[lane * 4u + j];
-                    sum += c[j];
-                }
-                uint32_t run = wave_inclusive_scan(sum) - sum;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    if (run < need && need - run <= c[j]) {   // at most one bin of the row
-                        s_found[0] = lane * 4u + j;
-                        s_found[1] = run;
-                        s_found[2] = c[j];
-                    }
-                    run += c[j];
-                }
-            }
-            group_sync<WAVES>();
-            const uint32_t bin = s_found[0], before = s_found[1], count_in_bin = s_found[2];
-            group_sync<WAVES>();   // the next round writes s_found again
-            if (bin > 0xFFu) {     // (uniform) the counts do not reach the rank: nothing is located
-                if (wave == 0u && lane == 0u) atomicOr(p.out.fault, kKthFaultCount);
-                prefix = 0u;
-                shift = 0u;
-                need = 0u;
-                break;
-            }
-            prefix = (prefix << 8) | bin;
-            need -= before;
-            if (count_in_bin == 1u) break;   // (uniform) one key under the prefix: it is the one (need is 1)
-        }
+            for (int i = 0; i < kRegs; i++) one(t[i], ((vm >> i) & 1u) != 0u);
+            one(h, (vm & kHeadBit) != 0u);
+        };
+        const Selected sel = select_short<WAVES, 4, StopKth>(s_cnt, s_found, wave, lane, p.rank + 1u, p.out.fault, kKthFaultCount, count);
         uint32_t base = 0u;
-        const bool found = locate_tile<WAVES>(t, h, vm, q0, r, prefix, shift, need, base, s_wc, wave, lane, row, p.out, p.xf);
-        if (!found && need != 0u && wave == 0u && lane == 0u) atomicOr(p.out.fault, kKthFaultLocate);
+        const bool found = locate_tile<WAVES>(t, h, vm, q0, r, sel.prefix, sel.shift, sel.need, base, s_wc, wave, lane, row, p.out, p.xf);
+        if (!found && sel.need != 0u && wave == 0u && lane == 0u) atomicOr(p.out.fault, kKthFaultLocate);
         group_sync<WAVES>();
     }
 }
@@ -285,46 +217,12 @@ struct LongParams {
     KeyTransform xf;
     Outputs out;
 };
-__device__ __forceinline__ uint32_t level_shift(int level) { return level == 0 ? 21u : (level == 1 ? 10u : 0u); }
-__device__ __forceinline__ uint32_t level_bits(int level) { return level == 2 ? 10u : 11u; }
-
-// Chunk c of a row is body positions [lo, hi) -- in EVERY kernel below -- and chunk 0 owns the head keys as well.  A row whose
-// head is not empty may leave its last chunk empty (lo == hi): the chunks are counted from cols.
-struct ChunkRange {
-    uint32_t lo, hi;
-};
-__device__ __forceinline__ ChunkRange chunk_of(const Row& r, const LongParams& p, uint32_t c)
-{
-    ChunkRange g;
-    g.lo = c * p.chunk < r.body ? c * p.chunk : r.body;
-    g.hi = r.body - g.lo < p.chunk ? r.body : g.lo + p.chunk;
-    return g;
-}
 
 // control block, counters and row states of a call (a kernel rather than memsets: one kind of node in a captured graph)
 __global__ void __launch_bounds__(256) kth_clear_kernel(uint32_t* ctl, uint32_t* hist, uint32_t hist_words, uint4* state, uint32_t rows,
                                                         uint32_t need)
 {
-    const uint32_t at = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
-    if (at < (uint32_t)(kCtlBytes / 4)) ctl[at] = 0u;
-    for (uint32_t q = at; q < hist_words; q += step) hist[q] = 0u;
-    if (state)
-        for (uint32_t r = at; r < rows; r += step) state[r] = make_uint4(0u, 32u, need, 0u);
-}
-
-// One register of every lane into the LDS counters.  A wave whose matching keys all carry one digit (a shared prefix, few values,
-// all equal) adds their number once instead of piling 64 adds onto one word.
-__device__ __forceinline__ void count_digit(uint32_t* s_hist, bool match, uint32_t bin, uint32_t lane)
-{
-    const uint64_t m = __ballot(match);
-    if (m == 0ull) return;   // uniform
-    const uint32_t leader = (uint32_t)__builtin_ctzll(m);
-    const uint32_t lead_bin = (uint32_t)__builtin_amdgcn_readlane((int)bin, (int)leader);
-    if (__ballot(match && bin != lead_bin) == 0ull) {
-        if (lane == leader) atomicAdd(&s_hist[lead_bin], popc64(m));
-    } else if (match) {
-        atomicAdd(&s_hist[bin], 1u);
-    }
+    clear_select(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, ctl, hist, hist_words, state, rows, need, Levels32::kNoLevel);
 }
 
 // One chunk of one row per workgroup: the digit of every key under the row's prefix, counted in LDS.
@@ -332,37 +230,26 @@ template <int LEVEL>
 __global__ void __launch_bounds__(kLongThreads) kth_hist_kernel(const LongParams p)
 {
     __shared__ uint32_t s_hist[kBins];
-    const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
-    if (row >= p.out.rows) return;
-    const uint4 st = p.state[row];
-    if (st.w != 0u) return;   // uniform
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    for (uint32_t b = tid; b < kBins; b += kLongThreads) s_hist[b] = 0u;
-    __syncthreads();
-    const Row r = row_of(p.keys, row, p.cols);
-    const ChunkRange g = chunk_of(r, p, c);
-    const uint32_t shift = level_shift(LEVEL), mask = (1u << level_bits(LEVEL)) - 1u;
-    auto count = [&](uint32_t key, bool valid) {
-        const bool match = valid && (LEVEL == 0 || (key >> st.y) == st.x);
-        count_digit(s_hist, match, (key >> shift) & mask, lane);
-    };
-    if (c == 0u && wave == 0u) {   // uniform
-        uint32_t h;
-        const uint32_t hv = load_head(r, lane, p.xf, h);
-        count(h, hv != 0u);
-    }
-    for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
-        uint32_t t[kRegs];
-        const uint32_t vm = load_tile(r, tile + wave * kWaveTile, g.hi, lane, p.xf, t);
+    hist_level(p, s_hist, [&](uint32_t row, uint32_t c, const uint4& st, uint32_t lane, uint32_t wave) __attribute__((always_inline)) {
+        const Row32 r = row_of(p.keys, row, p.cols);
+        const ChunkRange g = chunk_of(r, p.chunk, c);
+        const uint32_t shift = Levels32::shift(LEVEL), mask = (1u << Levels32::bits(LEVEL)) - 1u;
+        auto count = [&](uint32_t key, bool valid) __attribute__((always_inline)) {
+            const bool match = valid && (LEVEL == 0 || (key >> st.y) == st.x);
+            count_digit(s_hist, match, (key >> shift) & mask, lane);
+        };
+        if (c == 0u && wave == 0u) {   // uniform
+            uint32_t h;
+            const uint32_t hv = load_head(r, lane, p.xf, h);
+            count(h, hv != 0u);
+        }
+        for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
+            uint32_t t[kRegs];
+            const uint32_t vm = load_tile(r, tile + wave * kWaveTile, g.hi, lane, p.xf, t);
 #pragma unroll
-        for (int i = 0; i < kRegs; i++) count(t[i], ((vm >> i) & 1u) != 0u);
-    }
-    __syncthreads();
-    uint32_t* const out = p.hist + (size_t)row * kBins;
-    for (uint32_t b = tid; b < kBins; b += kLongThreads) {
-        const uint32_t v = s_hist[b];
-        if (v != 0u) atomicAdd(out + b, v);
-    }
+            for (int i = 0; i < kRegs; i++) count(t[i], ((vm >> i) & 1u) != 0u);
+        }
+    });
 }
 
 // One workgroup per row: walk the bins from the best end to the one that holds the wanted key; the counters go back to zero.
@@ -371,41 +258,7 @@ __global__ void __launch_bounds__(256) kth_scan_kernel(const LongParams p)
 {
     __shared__ uint32_t s_part[4];
     __shared__ uint32_t s_found[3];
-    const uint32_t row = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (row >= p.out.rows) return;
-    const uint4 st = p.state[row];
-    if (st.w != 0u) return;   // uniform
-    uint32_t* const h = p.hist + (size_t)row * kBins;
-    constexpr uint32_t E = kBins / 256u;
-    uint32_t c[E], sum = 0u;
-#pragma unroll
-    for (uint32_t e = 0; e < E; e++) {
-        c[e] = h[tid * E + e];
-        h[tid * E + e] = 0u;
-        sum += c[e];
-    }
-    if (tid == 0u) s_found[0] = 0xFFFFFFFFu;
-    uint32_t run = group_exclusive_scan<4>(sum, lane, wave, s_part);
-    const uint32_t need = st.z;
-#pragma unroll
-    for (uint32_t e = 0; e < E; e++) {
-        if (run < need && need - run <= c[e]) {   // at most one bin of the row
-            s_found[0] = tid * E + e;
-            s_found[1] = run;
-            s_found[2] = c[e];
-        }
-        run += c[e];
-    }
-    __syncthreads();
-    if (tid != 0u) return;
-    const uint32_t bin = s_found[0], before = s_found[1], count = s_found[2];
-    if (bin >= kBins) {   // the counts do not reach the rank: nothing is located
-        atomicOr(p.out.fault, kKthFaultCount);
-        p.state[row] = make_uint4(0u, 0u, 0u, 1u);
-        return;
-    }
-    const uint32_t prefix = LEVEL == 0 ? bin : ((st.x << level_bits(LEVEL)) | bin);
-    p.state[row] = make_uint4(prefix, level_shift(LEVEL), need - before, (LEVEL == 2 || count == 1u) ? 1u : 0u);
+    scan_level<Levels32, LEVEL, StopKth>(p, s_part, s_found, kKthFaultCount);
 }
 
 // the keys under the prefix, per chunk
@@ -416,10 +269,10 @@ __global__ void __launch_bounds__(kLongThreads) kth_count_kernel(const LongParam
     if (row >= p.out.rows) return;
     const uint4 st = p.state[row];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const Row r = row_of(p.keys, row, p.cols);
-    const ChunkRange g = chunk_of(r, p, c);
+    const Row32 r = row_of(p.keys, row, p.cols);
+    const ChunkRange g = chunk_of(r, p.chunk, c);
     uint32_t ne = 0u;
-    if (st.y < 32u && st.z != 0u) {   // (uniform) else: a row no scan has visited, or one whose counts fell short -- never
+    if (st.y < Levels32::kNoLevel && st.z != 0u) {   // (uniform) else: a row no scan has visited, or one whose counts fell short -- never
         if (c == 0u && wave == 0u) {   // uniform
             uint32_t h;
             const uint32_t hv = load_head(r, lane, p.xf, h);
@@ -460,7 +313,7 @@ __global__ void __launch_bounds__(256) kth_pick_kernel(const LongParams p)
     }
     if (tid == 0u) s_found[0] = kNoChunk;
     uint32_t run = group_exclusive_scan<4>(sum, lane, wave, s_part);
-    const uint32_t need = st.y < 32u ? st.z : 0u;
+    const uint32_t need = st.y < Levels32::kNoLevel ? st.z : 0u;
 #pragma unroll
     for (uint32_t e = 0; e < E; e++) {
         if (run < need && need - run <= c[e]) {   // at most one chunk of the row
@@ -489,8 +342,8 @@ __global__ void __launch_bounds__(kLongThreads) kth_locate_kernel(const LongPara
     const uint4 st = p.state[row];
     if (st.z == 0u || st.w >= p.chunks) return;   // (uniform) nothing was picked: the fault bit is already set
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const Row r = row_of(p.keys, row, p.cols);
-    const ChunkRange g = chunk_of(r, p, st.w);
+    const Row32 r = row_of(p.keys, row, p.cols);
+    const ChunkRange g = chunk_of(r, p.chunk, st.w);
     volatile lds_u32* const s_wc = (volatile lds_u32*)(lds_u32*)s_wc_raw;
     uint32_t base = 0u;
     bool found = false;
@@ -505,35 +358,10 @@ __global__ void __launch_bounds__(kLongThreads) kth_locate_kernel(const LongPara
     if (!found && tid == 0u) atomicOr(p.out.fault, kKthFaultLocate);
 }
 
-// Long rows are cut into chunks of a multiple of kLongTile keys, about kMaxChunks of them over the whole array.
-struct Chunks {
-    uint32_t chunk, per_row;
-};
-Chunks chunks_for(size_t rows, size_t cols)
-{
-    const size_t n = rows * cols;
-    size_t chunk = max_sz(kMinChunk, (n + kMaxChunks - 1) / kMaxChunks);
-    chunk = (chunk + kLongTile - 1) / kLongTile * kLongTile;
-    return Chunks{(uint32_t)chunk, (uint32_t)((cols + chunk - 1) / chunk)};
-}
-size_t chunk_cap_for(size_t cols) { return min_sz(kMaxChunks, (cols + kMinChunk - 1) / kMinChunk); }
-
 // Workspace: control | row states (16 B per row) | counters [rows][2048] | chunk counts (4 B per chunk) -- the last two for rows
 // above kLocalSortCap keys only.  At most 256 + rows (16 + 8192 + 4 ceil(cols / 16384)) + 3 * 255 bytes; never O(rows * cols).
-struct KthLayout {
-    size_t state, hist, counts, total;
-};
-KthLayout kth_layout(size_t rows, size_t cols)
-{
-    KthLayout L{};
-    const bool is_long = cols > (size_t)kLocalSortCap;
-    size_t off = kCtlBytes;
-    L.state = off;    off = align_up(off + rows * 16);
-    L.hist = off;     off = align_up(off + (is_long ? rows * kBins * 4 : 0));
-    L.counts = off;   off = align_up(off + (is_long ? rows * chunk_cap_for(cols) * 4 : 0));
-    L.total = off;
-    return L;
-}
+using KthLayout = SelectLayout;   // no offsets, and nothing behind the chunk counts: `end` is the figure
+KthLayout kth_layout(size_t rows, size_t cols) { return select_layout(rows, cols, false, 4); }
 
 int run_kth(const uint32_t* keys, size_t rows, size_t cols, size_t rank, const KeyTransform& xf, uint32_t* out_keys, uint32_t* out_idx,
             char* ws, const KthLayout& L, hipStream_t stream)
@@ -550,29 +378,14 @@ int run_kth(const uint32_t* keys, size_t rows, size_t cols, size_t rank, const K
         LSD_HIP(hipGetLastError());
         return LSDSORT_OK;
     }
-    const Chunks ch = chunks_for(rows, cols);
+    static const LevelKernels<LongParams> levels[] = {{kth_hist_kernel<0>, kth_scan_kernel<0>},
+                                                      {kth_hist_kernel<1>, kth_scan_kernel<1>},
+                                                      {kth_hist_kernel<2>, kth_scan_kernel<2>}};
     LongParams lp{};
-    lp.keys = keys;
-    lp.cols = (uint32_t)cols;
-    lp.chunk = ch.chunk;
-    lp.chunks = ch.per_row;
-    lp.chunk_cap = (uint32_t)chunk_cap_for(cols);
-    lp.state = reinterpret_cast<uint4*>(ws + L.state);
-    lp.hist = reinterpret_cast<uint32_t*>(ws + L.hist);
-    lp.counts = reinterpret_cast<uint32_t*>(ws + L.counts);
     lp.xf = xf;
     lp.out = out;
-    if (lp.chunks > lp.chunk_cap) return LSDSORT_ERR_INVALID_ARG;   // never: chunks are at least kMinChunk keys
+    LSD_TRY(select_long(lp, keys, rows, cols, (uint32_t)rank + 1u, ws, L, kth_clear_kernel, levels, stream));
     const uint32_t grid = (uint32_t)(rows * lp.chunks), row_grid = (uint32_t)rows;
-    hipLaunchKernelGGL(kth_clear_kernel, dim3(grid_for(rows * kBins, 1024, 4096)), dim3(256), 0, stream, ctl, lp.hist,
-                       (uint32_t)(rows * kBins), lp.state, (uint32_t)rows, (uint32_t)rank + 1u);
-    hipLaunchKernelGGL(kth_hist_kernel<0>, dim3(grid), dim3(kLongThreads), 0, stream, lp);
-    hipLaunchKernelGGL(kth_scan_kernel<0>, dim3(row_grid), dim3(256), 0, stream, lp);
-    hipLaunchKernelGGL(kth_hist_kernel<1>, dim3(grid), dim3(kLongThreads), 0, stream, lp);
-    hipLaunchKernelGGL(kth_scan_kernel<1>, dim3(row_grid), dim3(256), 0, stream, lp);
-    hipLaunchKernelGGL(kth_hist_kernel<2>, dim3(grid), dim3(kLongThreads), 0, stream, lp);
-    hipLaunchKernelGGL(kth_scan_kernel<2>, dim3(row_grid), dim3(256), 0, stream, lp);
-    LSD_HIP(hipGetLastError());
     hipLaunchKernelGGL(kth_count_kernel, dim3(grid), dim3(kLongThreads), 0, stream, lp);
     hipLaunchKernelGGL(kth_pick_kernel, dim3(row_grid), dim3(256), 0, stream, lp);
     hipLaunchKernelGGL(kth_locate_kernel, dim3(row_grid), dim3(kLongThreads), 0, stream, lp);
@@ -589,7 +402,7 @@ size_t lsdsort_kth_workspace_bytes(size_t rows, size_t cols)
 {
     if (rows > LSDSORT_MAX_KEYS || cols > LSDSORT_MAX_KEYS) return 0;
     if (rows != 0 && cols > LSDSORT_MAX_KEYS / rows) return 0;
-    return lsd::kth_layout(rows, cols).total;
+    return lsd::kth_layout(rows, cols).end;
 }
 
 int lsdsort_kth_device(const void* d_keys, size_t rows, size_t cols, size_t rank, int key_type, int largest, void* d_out_keys,
@@ -602,7 +415,7 @@ int lsdsort_kth_device(const void* d_keys, size_t rows, size_t cols, size_t rank
     if (rank >= cols) return LSDSORT_ERR_INVALID_ARG;
     if (!d_keys || !d_out_keys || (((uintptr_t)d_keys | (uintptr_t)d_out_keys) & 3)) return LSDSORT_ERR_INVALID_ARG;
     const lsd::KthLayout L = lsd::kth_layout(rows, cols);
-    if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.total)) return LSDSORT_ERR_WORKSPACE;
+    if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.end)) return LSDSORT_ERR_WORKSPACE;
     int rank_method = 0;   // asked for the device set-up alone: nothing here ranks with the returning add
     LSD_TRY(lsd::device_rank_method(8, &rank_method));
     return lsd::run_kth(static_cast<const uint32_t*>(d_keys), rows, cols, rank, xf, static_cast<uint32_t*>(d_out_keys), d_out_idx,

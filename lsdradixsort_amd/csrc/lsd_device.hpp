@@ -71,6 +71,14 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_wave_barrier();
 }
 
+// The barrier of a group of WAVES wavefronts that share a piece of LDS: one wave orders itself, more take the workgroup's.
+template <int WAVES>
+__device__ __forceinline__ void group_sync()
+{
+    if (WAVES == 1) wave_sync();
+    else __syncthreads();
+}
+
 // Reductions over the 64 lanes of a wave (xor butterfly): every lane ends with the result.  All 64 lanes must be active.
 template <class Op>
 __device__ __forceinline__ uint32_t wave_reduce(uint32_t v, Op op)
@@ -133,6 +141,28 @@ __device__ __forceinline__ uint32_t group_exclusive_scan(uint32_t v, uint32_t la
     }
     if (total) *total = all;
     return before + incl - v;
+}
+
+// One register of every lane into LDS counters.  A wave whose matching keys all carry one digit (a shared prefix, a constant byte,
+// few values, all equal) adds their number once instead of piling 64 adds onto one word.  All 64 lanes must be active.
+__device__ __forceinline__ void count_digit(uint32_t* s_hist, bool match, uint32_t bin, uint32_t lane)
+{
+    const uint64_t m = __ballot(match);
+    if (m == 0ull) return;   // uniform
+    const uint32_t leader = (uint32_t)__builtin_ctzll(m);
+    const uint32_t lead_bin = (uint32_t)__builtin_amdgcn_readlane((int)bin, (int)leader);
+    if (__ballot(match && bin != lead_bin) == 0ull) {
+        if (lane == leader) atomicAdd(&s_hist[lead_bin], popc64(m));
+    } else if (match) {
+        atomicAdd(&s_hist[bin], 1u);
+    }
+}
+
+// keys in front of the first 16-byte line at or after p (p is aligned to its key type)
+template <class Key>
+__device__ __forceinline__ uint32_t keys_to_line(const Key* p)
+{
+    return ((16u - ((uint32_t)(uintptr_t)p & 15u)) & 15u) / (uint32_t)sizeof(Key);
 }
 
 // Number of LDS replicas of a small histogram so that 64 lanes do not pile onto a handful

@@ -42,8 +42,10 @@ int sort_host_multi(uint32_t* keys, size_t n, int radix_bits, int num_gpus, bool
     } while (0)
 
 constexpr size_t kAlign = 256;   // every workspace, and every array inside one
+constexpr size_t kCtlBytes = 256;   // the control block at the front of a workspace whose first word is the entry's fault word
 inline size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 inline size_t min_sz(size_t a, size_t b) { return a < b ? a : b; }
+inline size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 inline bool workspace_ok(const void* ws, size_t bytes, size_t need) { return ws && !((uintptr_t)ws & (kAlign - 1)) && bytes >= need; }
 
 // key_type (LSDSORT_KEY_*) and direction as the transform the kernels apply (lsd_kernels.hpp, KeyTransform)

@@ -46,7 +46,6 @@ constexpr size_t kRows16NativeMinCols = 1;
 std::atomic<int> g_rows16_route{-1};   // lsdsort_set_rows16_route: -1 by size, 0 widen, 1 native wherever it exists
 
 constexpr uint32_t kRowsFaultDest = 4096u;   // fault word: a destination outside its row (never expected; not stored)
-constexpr size_t kCtlBytes = 256;
 constexpr uint32_t kPad = 0xFFFFFFFFu;       // an item that does not exist: the highest digit in every pass, at the highest positions
 constexpr int kGroupThreads = 512, kGroupWaves = kGroupThreads / kWave;
 constexpr int kWaveRegs = kWaveSegCap / kWave;                  // 16 items per lane
@@ -59,19 +58,12 @@ constexpr int kMiscWords = 32;               // per group: the scan's partials [
 static_assert(LSDSORT_ROWS16_NATIVE_MAX_COLS >= 262144 && LSDSORT_ROWS16_NATIVE_MAX_COLS % kLongTile == 0, "the long tier's cap");
 static_assert(kLongTile <= 65536 && kLocalSortCap <= 65536, "an index within a tile fits the low half-word");
 
-template <int WAVES>
-__device__ __forceinline__ void group_sync()
-{
-    if (WAVES == 1) wave_sync();
-    else __syncthreads();
-}
-
 // ---- a tile between global memory and LDS ---------------------------------------------------------------------------------------
 // s_items[q] = sortable(src[q]) << 16 | q, q < size, by thread t of `threads`: 16-byte loads from the tile's first 16-byte line on.
 __device__ __forceinline__ void stage_raw(const uint16_t* src, uint32_t size, const Key16Map& m, lds_u32* s_items, uint32_t t,
                                           uint32_t threads)
 {
-    const uint32_t to_line = ((16u - ((uint32_t)(uintptr_t)src & 15u)) & 15u) / (uint32_t)sizeof(uint16_t);
+    const uint32_t to_line = keys_to_line(src);
     const uint32_t head = to_line < size ? to_line : size;
     const uint32_t groups = (size - head) / kGroupKeys, tail0 = head + groups * kGroupKeys;
     auto one = [&](uint32_t q) { s_items[q] = (to_sortable16(src[q], m) << 16) | q; };
@@ -93,7 +85,7 @@ __device__ __forceinline__ void stage_raw(const uint16_t* src, uint32_t size, co
 __device__ __forceinline__ void store_row(const lds_u32* s_items, uint32_t size, const Key16Map& m, uint16_t* dst, uint32_t* idx, uint32_t t,
                                           uint32_t threads)
 {
-    const uint32_t to_line = ((16u - ((uint32_t)(uintptr_t)dst & 15u)) & 15u) / (uint32_t)sizeof(uint16_t);
+    const uint32_t to_line = keys_to_line(dst);
     const uint32_t head = to_line < size ? to_line : size;
     const uint32_t groups = (size - head) / kGroupKeys, tail0 = head + groups * kGroupKeys;
     auto key_at = [&](uint32_t q) { return from_sortable16(s_items[q] >> 16, m); };
@@ -285,21 +277,6 @@ struct LongParams {
     uint32_t* fault;
 };
 
-// One register of every lane into the LDS counters.  A wave whose keys all carry one digit (a constant byte, few values, all equal)
-// adds their number once instead of piling 64 adds onto one word.
-__device__ __forceinline__ void count_digit(uint32_t* s_hist, bool valid, uint32_t bin, uint32_t lane)
-{
-    const uint64_t m = __ballot(valid);
-    if (m == 0ull) return;   // uniform
-    const uint32_t leader = (uint32_t)__builtin_ctzll(m);
-    const uint32_t lead_bin = (uint32_t)__builtin_amdgcn_readlane((int)bin, (int)leader);
-    if (__ballot(valid && bin != lead_bin) == 0ull) {
-        if (lane == leader) atomicAdd(&s_hist[lead_bin], popc64(m));
-    } else if (valid) {
-        atomicAdd(&s_hist[bin], 1u);
-    }
-}
-
 // One tile per workgroup.  PASS 1: the low byte of the sortable value of the raw keys; PASS 2: the high byte of pass 1's output.
 template <int PASS>
 __global__ void __launch_bounds__(kHistThreads) rows16_hist_kernel(const LongParams p)
@@ -314,7 +291,7 @@ __global__ void __launch_bounds__(kHistThreads) rows16_hist_kernel(const LongPar
     const size_t at = (size_t)row * p.cols + lo;
     if (PASS == 1) {
         const uint16_t* const src = p.keys + at;
-        const uint32_t to_line = ((16u - ((uint32_t)(uintptr_t)src & 15u)) & 15u) / (uint32_t)sizeof(uint16_t);
+        const uint32_t to_line = keys_to_line(src);
         const uint32_t head = to_line < size ? to_line : size;
         const uint32_t groups = (size - head) / kGroupKeys, tail0 = head + groups * kGroupKeys;
         if (tid < 64u) {   // wave 0: the keys outside the whole groups

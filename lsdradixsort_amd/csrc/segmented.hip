@@ -46,7 +46,6 @@ constexpr int kWaveSliceWords = kWaveSegCap + 256;   // per wave: keys, then 256
 // counters from byte 8 (64 bits: no sum of sizes, however the offsets overlap, wraps one round to an index already handed out)
 enum : int { kCtlFault = 0 };
 enum : int { kCntWave = 1, kCntGroup = 2, kCntItems = 3, kCntTiles = 4, kCntHistTiles = 5 };   // index into the u64 view
-constexpr size_t kCtlBytes = 256;
 typedef unsigned long long u64;
 // Fault bits besides kSegFaultBit: tables that do not describe the offsets (never expected: a tier then skips the entry, and no
 // key is read or written outside the array)

@@ -4,7 +4,10 @@
 // stable sort of the row in the requested order.  "Best" is always "smallest sortable key": the key transform of lsd_kernels.hpp
 // (to_sortable, with the complement for largest) is applied where a key is read, and the raw key is what is stored.
 //
-// A radix SELECT by counting only, then a sort of the k winners alone:
+// A radix SELECT by counting only, then a sort of the k winners alone.  The select's skeleton -- the short rows' rounds, the long
+// rows' clear / hist / scan levels, chunking, the select's workspace and the sort route's threshold -- is radix_select.hpp's, shared
+// with topk16.hip and kth.hip; this unit adds the loads (strided, validity by position), compact_tile, the count and write kernels
+// and the sort route's copy and take.
 //   select   most significant digit first, count the digit of the keys that still match the prefix found so far, walk the counts
 //            from the best end to the bin that holds the k-th key: that bin's digit joins the prefix, the keys in better bins are
 //            certain winners and `need` (how many the prefix's keys still have to supply) shrinks by their number.  It stops as soon
@@ -33,31 +36,10 @@
 
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
+#include "radix_select.hpp"
 
 namespace lsd {
 namespace {
-
-// The sort route takes over where k * kLargeKDen > cols * kLargeKNum.  By bytes the select route costs at most 20 B per key of the
-// row plus the sort of k items, the sort route 12 B per key (copy with positions) plus the sort of the whole row and the gather:
-// the select stays ahead until k is most of the row.
-constexpr size_t kLargeKNum = 3, kLargeKDen = 4;
-
-constexpr uint32_t kTopkFaultCount = 1024u;   // fault word: the digit counts of a row do not reach k (never expected)
-constexpr uint32_t kTopkFaultDest = 2048u;    // fault word: a winner's slot is not below k (never expected; not stored)
-constexpr size_t kCtlBytes = 256;
-constexpr int kRegs = 16;                     // keys per lane of a tile: wave w of a tile holds positions [1024 w, 1024 (w + 1))
-constexpr uint32_t kBins = 2048;              // long rows: counters per row (11-bit digits)
-constexpr uint32_t kLongThreads = 256, kLongWaves = kLongThreads / kWave, kLongTile = kLongThreads * kRegs;
-constexpr uint32_t kMinChunk = 16384, kMaxChunks = 2048;
-
-size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
-
-template <int WAVES>
-__device__ __forceinline__ void group_sync()
-{
-    if (WAVES == 1) wave_sync();
-    else __syncthreads();
-}
 
 struct Outputs {
     uint32_t* keys;       // [rows][k], raw keys
@@ -160,59 +142,18 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) topk_short_kernel(con
             t[i] = 0xFFFFFFFFu;
             if (first + (uint32_t)i * 64u < p.cols && pos < p.cols) t[i] = to_sortable(in[pos], p.xf);
         }
-        uint32_t prefix = 0u, shift = 24u, need = p.out.k;
-#pragma unroll 1
-        for (int round = 0; round < 4; round++) {
-            shift = 24u - 8u * (uint32_t)round;
-            if (wave == 0u) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) s_cnt[j * 64 + lane] = 0u;
-                if (lane == 0u) s_found[0] = 0xFFFFFFFFu;
-            }
-            group_sync<WAVES>();
+        // round 0: every key matches; later: those whose bits above the digit are the prefix
+        auto count = [&](int round, uint32_t shift, uint32_t prefix, auto add) __attribute__((always_inline)) {
 #pragma unroll
             for (int i = 0; i < kRegs; i++) {
                 const bool valid = first + (uint32_t)i * 64u + lane < p.cols;
-                // round 0: every key matches; later: those whose bits above the digit are the prefix
                 const bool match = round == 0 || ((t[i] >> shift) >> 8) == prefix;
-                if (valid && match)
-                    __hip_atomic_fetch_add((lds_u32*)&s_cnt[(t[i] >> shift) & 0xFFu], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (valid && match) add(t[i]);
             }
-            group_sync<WAVES>();
-            if (wave == 0u) {   // four bins per lane, from the best end
-                uint32_t c[4], sum = 0u;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    c[j] = s_cnt[lane * 4u + j];
-                    sum += c[j];
-                }
-                uint32_t run = wave_inclusive_scan(sum) - sum;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    if (run < need && need - run <= c[j]) {   // at most one bin of the row
-                        s_found[0] = lane * 4u + j;
-                        s_found[1] = run;
-                        s_found[2] = c[j];
-                    }
-                    run += c[j];
-                }
-            }
-            group_sync<WAVES>();
-            const uint32_t bin = s_found[0], before = s_found[1], count = s_found[2];
-            group_sync<WAVES>();   // the next round writes s_found again
-            if (bin > 0xFFu) {     // (uniform) the counts do not reach k: nothing is selected
-                if (wave == 0u && lane == 0u) atomicOr(p.out.fault, kTopkFaultCount);
-                prefix = 0u;
-                shift = 0u;
-                need = 0u;
-                break;
-            }
-            prefix = (prefix << 8) | bin;
-            need -= before;
-            if (count == need) break;   // (uniform) the remainder is decided: every key under the prefix wins
-        }
+        };
+        const Selected sel = select_short<WAVES, 4, StopTopk>(s_cnt, s_found, wave, lane, p.out.k, p.out.fault, kTopkFaultCount, count);
         uint32_t base_b = 0u, base_e = 0u;
-        compact_tile<WAVES>(t, first, p.cols, prefix, shift, need, base_b, base_e, s_wc, wave, lane, row, p.out, p.xf);
+        compact_tile<WAVES>(t, first, p.cols, sel.prefix, sel.shift, sel.need, base_b, base_e, s_wc, wave, lane, row, p.out, p.xf);
         group_sync<WAVES>();
     }
 }
@@ -230,18 +171,12 @@ struct LongParams {
     KeyTransform xf;
     Outputs out;
 };
-__device__ __forceinline__ uint32_t level_shift(int level) { return level == 0 ? 21u : (level == 1 ? 10u : 0u); }
-__device__ __forceinline__ uint32_t level_bits(int level) { return level == 2 ? 10u : 11u; }
 
 // control block, counters and row states of a call (a kernel rather than memsets: one kind of node in a captured graph)
 __global__ void __launch_bounds__(256) topk_clear_kernel(uint32_t* ctl, uint32_t* hist, uint32_t hist_words, uint4* state, uint32_t rows,
                                                          uint32_t k)
 {
-    const uint32_t at = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
-    if (at < (uint32_t)(kCtlBytes / 4)) ctl[at] = 0u;
-    for (uint32_t q = at; q < hist_words; q += step) hist[q] = 0u;
-    if (state)
-        for (uint32_t r = at; r < rows; r += step) state[r] = make_uint4(0u, 32u, k, 0u);
+    clear_select(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, ctl, hist, hist_words, state, rows, k, Levels32::kNoLevel);
 }
 
 __device__ __forceinline__ void load_tile(const uint32_t* in, uint32_t first, uint32_t end, uint32_t lane, const KeyTransform& xf,
@@ -255,48 +190,27 @@ __device__ __forceinline__ void load_tile(const uint32_t* in, uint32_t first, ui
     }
 }
 
-// One chunk of one row per workgroup: the digit of every key under the row's prefix, counted in LDS.  A wave whose matching keys
-// all carry one digit (a shared prefix, few values, all equal) adds their number once instead of piling 64 adds onto one word.
+// One chunk of one row per workgroup: the digit of every key under the row's prefix, counted in LDS.
 template <int LEVEL>
 __global__ void __launch_bounds__(kLongThreads) topk_hist_kernel(const LongParams p)
 {
     __shared__ uint32_t s_hist[kBins];
-    const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
-    if (row >= p.out.rows) return;
-    const uint4 st = p.state[row];
-    if (st.w != 0u) return;   // uniform
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    for (uint32_t b = tid; b < kBins; b += kLongThreads) s_hist[b] = 0u;
-    __syncthreads();
-    const uint32_t* const in = p.keys + (size_t)row * p.cols;
-    const uint32_t lo = c * p.chunk, hi = p.cols - lo < p.chunk ? p.cols : lo + p.chunk;
-    const uint32_t shift = level_shift(LEVEL), mask = (1u << level_bits(LEVEL)) - 1u;
-    for (uint32_t tile = lo; tile < hi; tile += kLongTile) {   // uniform
-        const uint32_t first = tile + wave * 1024u;
-        uint32_t t[kRegs];
-        load_tile(in, first, hi, lane, p.xf, t);
+    hist_level(p, s_hist, [&](uint32_t row, uint32_t c, const uint4& st, uint32_t lane, uint32_t wave) __attribute__((always_inline)) {
+        const uint32_t* const in = p.keys + (size_t)row * p.cols;
+        const uint32_t lo = c * p.chunk, hi = p.cols - lo < p.chunk ? p.cols : lo + p.chunk;
+        const uint32_t shift = Levels32::shift(LEVEL), mask = (1u << Levels32::bits(LEVEL)) - 1u;
+        for (uint32_t tile = lo; tile < hi; tile += kLongTile) {   // uniform
+            const uint32_t first = tile + wave * 1024u;
+            uint32_t t[kRegs];
+            load_tile(in, first, hi, lane, p.xf, t);
 #pragma unroll
-        for (int i = 0; i < kRegs; i++) {
-            const bool valid = first + (uint32_t)i * 64u + lane < hi;
-            const bool match = valid && (LEVEL == 0 || (t[i] >> st.y) == st.x);
-            const uint32_t bin = (t[i] >> shift) & mask;
-            const uint64_t m = __ballot(match);
-            if (m == 0ull) continue;   // uniform
-            const uint32_t leader = (uint32_t)__builtin_ctzll(m);
-            const uint32_t lead_bin = (uint32_t)__builtin_amdgcn_readlane((int)bin, (int)leader);
-            if (__ballot(match && bin != lead_bin) == 0ull) {
-                if (lane == leader) atomicAdd(&s_hist[lead_bin], popc64(m));
-            } else if (match) {
-                atomicAdd(&s_hist[bin], 1u);
+            for (int i = 0; i < kRegs; i++) {
+                const bool valid = first + (uint32_t)i * 64u + lane < hi;
+                const bool match = valid && (LEVEL == 0 || (t[i] >> st.y) == st.x);
+                count_digit(s_hist, match, (t[i] >> shift) & mask, lane);
             }
         }
-    }
-    __syncthreads();
-    uint32_t* const out = p.hist + (size_t)row * kBins;
-    for (uint32_t b = tid; b < kBins; b += kLongThreads) {
-        const uint32_t v = s_hist[b];
-        if (v != 0u) atomicAdd(out + b, v);
-    }
+    });
 }
 
 // One workgroup per row: walk the bins from the best end to the one that holds the k-th key; the counters go back to zero.
@@ -305,42 +219,7 @@ __global__ void __launch_bounds__(256) topk_scan_kernel(const LongParams p)
 {
     __shared__ uint32_t s_part[4];
     __shared__ uint32_t s_found[3];
-    const uint32_t row = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (row >= p.out.rows) return;
-    const uint4 st = p.state[row];
-    if (st.w != 0u) return;   // uniform
-    uint32_t* const h = p.hist + (size_t)row * kBins;
-    constexpr uint32_t E = kBins / 256u;
-    uint32_t c[E], sum = 0u;
-#pragma unroll
-    for (uint32_t e = 0; e < E; e++) {
-        c[e] = h[tid * E + e];
-        h[tid * E + e] = 0u;
-        sum += c[e];
-    }
-    if (tid == 0u) s_found[0] = 0xFFFFFFFFu;
-    uint32_t run = group_exclusive_scan<4>(sum, lane, wave, s_part);
-    const uint32_t need = st.z;
-#pragma unroll
-    for (uint32_t e = 0; e < E; e++) {
-        if (run < need && need - run <= c[e]) {   // at most one bin of the row
-            s_found[0] = tid * E + e;
-            s_found[1] = run;
-            s_found[2] = c[e];
-        }
-        run += c[e];
-    }
-    __syncthreads();
-    if (tid != 0u) return;
-    const uint32_t bin = s_found[0], before = s_found[1], count = s_found[2];
-    if (bin >= kBins) {   // the counts do not reach k: nothing is selected
-        atomicOr(p.out.fault, kTopkFaultCount);
-        p.state[row] = make_uint4(0u, 0u, 0u, 1u);
-        return;
-    }
-    const uint32_t prefix = LEVEL == 0 ? bin : ((st.x << level_bits(LEVEL)) | bin);
-    const uint32_t left = need - before;
-    p.state[row] = make_uint4(prefix, level_shift(LEVEL), left, (LEVEL == 2 || count == left) ? 1u : 0u);
+    scan_level<Levels32, LEVEL, StopTopk>(p, s_part, s_found, kTopkFaultCount);
 }
 
 // better / equal keys of every chunk
@@ -354,7 +233,7 @@ __global__ void __launch_bounds__(kLongThreads) topk_count_kernel(const LongPara
     const uint32_t* const in = p.keys + (size_t)row * p.cols;
     const uint32_t lo = c * p.chunk, hi = p.cols - lo < p.chunk ? p.cols : lo + p.chunk;
     uint32_t nb = 0u, ne = 0u;
-    if (st.y < 32u) {
+    if (st.y < Levels32::kNoLevel) {
         for (uint32_t tile = lo; tile < hi; tile += kLongTile) {   // uniform
             const uint32_t first = tile + wave * 1024u;
             uint32_t t[kRegs];
@@ -393,7 +272,7 @@ __global__ void __launch_bounds__(kLongThreads) topk_write_kernel(const LongPara
     const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
     if (row >= p.out.rows) return;
     const uint4 st = p.state[row];
-    if (st.y >= 32u) return;   // (uniform) a row no scan has visited: never
+    if (st.y >= Levels32::kNoLevel) return;   // (uniform) a row no scan has visited: never
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint2* const counts = p.counts + (size_t)row * p.chunk_cap;
     uint32_t base_b = 0u, base_e = 0u;
@@ -429,10 +308,9 @@ __global__ void __launch_bounds__(kLongThreads) topk_write_kernel(const LongPara
 }
 
 // ---- plumbing -------------------------------------------------------------------------------------------------------------------
-// off[r] = r * stride, r <= rows: the rows as segments
 __global__ void __launch_bounds__(256) topk_offsets_kernel(uint32_t* off, uint32_t rows, uint32_t stride)
 {
-    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r <= rows; r += gridDim.x * blockDim.x) off[r] = r * stride;
+    row_offsets(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, off, rows, stride);
 }
 
 // the sort route: the rows and their positions into the workspace ...
@@ -456,53 +334,24 @@ __global__ void __launch_bounds__(256) topk_take_kernel(const uint32_t* sorted, 
     }
 }
 
-bool sort_route(size_t cols, size_t k) { return k * kLargeKDen > cols * kLargeKNum; }
-
-// Long rows are cut into chunks of a multiple of kLongTile keys, about kMaxChunks of them over the whole array.
-struct Chunks {
-    uint32_t chunk, per_row;
-};
-Chunks chunks_for(size_t rows, size_t cols)
-{
-    const size_t n = rows * cols;
-    size_t chunk = max_sz(kMinChunk, (n + kMaxChunks - 1) / kMaxChunks);
-    chunk = (chunk + kLongTile - 1) / kLongTile * kLongTile;
-    return Chunks{(uint32_t)chunk, (uint32_t)((cols + chunk - 1) / chunk)};
-}
-size_t chunk_cap_for(size_t cols) { return min_sz(kMaxChunks, (cols + kMinChunk - 1) / kMinChunk); }
-
-// Workspace.  Select route: control | row states | offsets | counters [rows][2048] | chunk counts | segmented sort of rows x k pairs.
-// Sort route: control | offsets | copy of the keys | their positions | segmented sort of rows x cols pairs.  The size is the larger
-// of the two, the sort route's taken at the most keys a sort-route call with this (rows, k) can have: monotonic in each argument.
+// Workspace.  Select route: the select's part (with offsets) | segmented sort of rows x k pairs.  Sort route: control | offsets |
+// copy of the keys | their positions | segmented sort of rows x cols pairs.  The size is the larger of the two, the sort route's
+// taken at the most keys a sort-route call with this (rows, k) can have: monotonic in each argument.
 struct TopkLayout {
-    size_t state, offsets, hist, counts, seg, seg_bytes, total;             // select route
-    size_t s_offsets, s_keys, s_idx, s_seg, s_seg_bytes, s_total;           // sort route, for `sort_keys` keys
+    SelectLayout sel;
+    size_t seg, seg_bytes, total;   // select route
+    SortRouteLayout sort;           // sort route, for `sort_keys` keys
+    size_t bytes() const { return max_sz(total, sort.total); }
 };
-TopkLayout topk_layout(size_t rows, size_t cols, size_t k, size_t sort_keys)
+TopkLayout topk_layout(size_t rows, size_t cols, size_t k)
 {
     TopkLayout L{};
-    const bool is_long = cols > (size_t)kLocalSortCap;
-    size_t off = kCtlBytes;
-    L.state = off;    off = align_up(off + rows * 16);
-    L.offsets = off;  off = align_up(off + (rows + 1) * 4);
-    L.hist = off;     off = align_up(off + (is_long ? rows * kBins * 4 : 0));
-    L.counts = off;   off = align_up(off + (is_long ? rows * chunk_cap_for(cols) * 8 : 0));
-    L.seg = off;
+    L.sel = select_layout(rows, cols, true, 8);
+    L.seg = L.sel.end;
     L.seg_bytes = lsdsort_segmented_workspace_bytes(min_sz(rows * k, LSDSORT_MAX_KEYS), rows, 1);
-    L.total = align_up(off + L.seg_bytes);
-    off = kCtlBytes;
-    L.s_offsets = off;  off = align_up(off + (rows + 1) * 4);
-    L.s_keys = off;     off = align_up(off + sort_keys * 4);
-    L.s_idx = off;      off = align_up(off + sort_keys * 4);
-    L.s_seg = off;
-    L.s_seg_bytes = lsdsort_segmented_workspace_bytes(sort_keys, rows, 1);
-    L.s_total = align_up(off + L.s_seg_bytes);
+    L.total = align_up(L.seg + L.seg_bytes);
+    L.sort = sort_route_layout(rows, sort_route_keys(rows, cols, k));
     return L;
-}
-size_t sort_route_keys(size_t rows, size_t cols, size_t k)
-{
-    // a call takes the sort route only if cols < 4 k / 3
-    return min_sz(min_sz(rows * cols, rows * ((k * kLargeKDen + kLargeKNum - 1) / kLargeKNum)), LSDSORT_MAX_KEYS);
 }
 
 int run_topk(const uint32_t* keys, size_t rows, size_t cols, size_t k, int key_type, int largest, const KeyTransform& xf,
@@ -513,23 +362,23 @@ int run_topk(const uint32_t* keys, size_t rows, size_t cols, size_t k, int key_t
     const size_t n = rows * cols;
 
     if (sort_route(cols, k)) {
-        uint32_t* const offsets = reinterpret_cast<uint32_t*>(ws + L.s_offsets);
-        uint32_t* const copy = reinterpret_cast<uint32_t*>(ws + L.s_keys);
-        uint32_t* const idx = out_idx ? reinterpret_cast<uint32_t*>(ws + L.s_idx) : nullptr;
+        uint32_t* const offsets = reinterpret_cast<uint32_t*>(ws + L.sort.offsets);
+        uint32_t* const copy = reinterpret_cast<uint32_t*>(ws + L.sort.keys);
+        uint32_t* const idx = out_idx ? reinterpret_cast<uint32_t*>(ws + L.sort.idx) : nullptr;
         hipLaunchKernelGGL(topk_clear_kernel, dim3(1), dim3(256), 0, stream, ctl, (uint32_t*)nullptr, 0u, (uint4*)nullptr, 0u, 0u);
         hipLaunchKernelGGL(topk_offsets_kernel, dim3(grid_for(rows + 1, 256, 1024)), dim3(256), 0, stream, offsets, (uint32_t)rows,
                            (uint32_t)cols);
         hipLaunchKernelGGL(topk_copy_kernel, dim3(grid_for(n, 1024, 8192)), dim3(256), 0, stream, keys, copy, idx, (uint32_t)n,
                            (uint32_t)cols);
         LSD_HIP(hipGetLastError());
-        LSD_TRY(lsdsort_segmented_device(copy, idx, offsets, rows, n, key_type, largest, ws + L.s_seg, L.s_seg_bytes, stream));
+        LSD_TRY(lsdsort_segmented_device(copy, idx, offsets, rows, n, key_type, largest, ws + L.sort.seg, L.sort.seg_bytes, stream));
         hipLaunchKernelGGL(topk_take_kernel, dim3(grid_for(rows * k, 1024, 8192)), dim3(256), 0, stream, copy, idx, (uint32_t)cols, out);
         LSD_HIP(hipGetLastError());
-        LSD_HIP(launch_keep_fault(ctl, reinterpret_cast<const uint32_t*>(ws + L.s_seg), stream));
+        LSD_HIP(launch_keep_fault(ctl, reinterpret_cast<const uint32_t*>(ws + L.sort.seg), stream));
         return LSDSORT_OK;
     }
 
-    uint32_t* const offsets = reinterpret_cast<uint32_t*>(ws + L.offsets);
+    uint32_t* const offsets = reinterpret_cast<uint32_t*>(ws + L.sel.offsets);
     if (cols <= (size_t)kLocalSortCap) {
         ShortParams sp{keys, (uint32_t)cols, xf, out};
         hipLaunchKernelGGL(topk_clear_kernel, dim3(1), dim3(256), 0, stream, ctl, (uint32_t*)nullptr, 0u, (uint4*)nullptr, 0u, 0u);
@@ -539,29 +388,14 @@ int run_topk(const uint32_t* keys, size_t rows, size_t cols, size_t k, int key_t
             hipLaunchKernelGGL(topk_short_kernel<16>, dim3(grid_for(rows, 1, 4096)), dim3(1024), 0, stream, sp);
         LSD_HIP(hipGetLastError());
     } else {
-        const Chunks ch = chunks_for(rows, cols);
+        static const LevelKernels<LongParams> levels[] = {{topk_hist_kernel<0>, topk_scan_kernel<0>},
+                                                          {topk_hist_kernel<1>, topk_scan_kernel<1>},
+                                                          {topk_hist_kernel<2>, topk_scan_kernel<2>}};
         LongParams lp{};
-        lp.keys = keys;
-        lp.cols = (uint32_t)cols;
-        lp.chunk = ch.chunk;
-        lp.chunks = ch.per_row;
-        lp.chunk_cap = (uint32_t)chunk_cap_for(cols);
-        lp.state = reinterpret_cast<uint4*>(ws + L.state);
-        lp.hist = reinterpret_cast<uint32_t*>(ws + L.hist);
-        lp.counts = reinterpret_cast<uint2*>(ws + L.counts);
         lp.xf = xf;
         lp.out = out;
-        if (lp.chunks > lp.chunk_cap) return LSDSORT_ERR_INVALID_ARG;   // never: chunks are at least kMinChunk keys
-        const uint32_t grid = (uint32_t)(rows * lp.chunks), row_grid = (uint32_t)rows;
-        hipLaunchKernelGGL(topk_clear_kernel, dim3(grid_for(rows * kBins, 1024, 4096)), dim3(256), 0, stream, ctl, lp.hist,
-                           (uint32_t)(rows * kBins), lp.state, (uint32_t)rows, (uint32_t)k);
-        hipLaunchKernelGGL(topk_hist_kernel<0>, dim3(grid), dim3(kLongThreads), 0, stream, lp);
-        hipLaunchKernelGGL(topk_scan_kernel<0>, dim3(row_grid), dim3(256), 0, stream, lp);
-        hipLaunchKernelGGL(topk_hist_kernel<1>, dim3(grid), dim3(kLongThreads), 0, stream, lp);
-        hipLaunchKernelGGL(topk_scan_kernel<1>, dim3(row_grid), dim3(256), 0, stream, lp);
-        hipLaunchKernelGGL(topk_hist_kernel<2>, dim3(grid), dim3(kLongThreads), 0, stream, lp);
-        hipLaunchKernelGGL(topk_scan_kernel<2>, dim3(row_grid), dim3(256), 0, stream, lp);
-        LSD_HIP(hipGetLastError());
+        LSD_TRY(select_long(lp, keys, rows, cols, (uint32_t)k, ws, L.sel, topk_clear_kernel, levels, stream));
+        const uint32_t grid = (uint32_t)(rows * lp.chunks);
         hipLaunchKernelGGL(topk_count_kernel, dim3(grid), dim3(kLongThreads), 0, stream, lp);
         hipLaunchKernelGGL(topk_write_kernel, dim3(grid), dim3(kLongThreads), 0, stream, lp);
         LSD_HIP(hipGetLastError());
@@ -584,8 +418,7 @@ size_t lsdsort_topk_workspace_bytes(size_t rows, size_t cols, size_t k)
     if (rows > LSDSORT_MAX_KEYS || cols > LSDSORT_MAX_KEYS || k > LSDSORT_MAX_KEYS) return 0;
     if (rows != 0 && cols > LSDSORT_MAX_KEYS / rows) return 0;
     if (rows != 0 && k > LSDSORT_MAX_KEYS / rows) return 0;
-    const lsd::TopkLayout L = lsd::topk_layout(rows, cols, k, lsd::sort_route_keys(rows, cols, k));
-    return L.total > L.s_total ? L.total : L.s_total;
+    return lsd::topk_layout(rows, cols, k).bytes();
 }
 
 int lsdsort_topk_device(const void* d_keys, size_t rows, size_t cols, size_t k, int key_type, int largest, void* d_out_keys,
@@ -597,9 +430,8 @@ int lsdsort_topk_device(const void* d_keys, size_t rows, size_t cols, size_t k, 
     if (k > cols) return LSDSORT_ERR_INVALID_ARG;
     if (rows == 0 || cols == 0 || k == 0) return LSDSORT_OK;
     if (!d_keys || !d_out_keys) return LSDSORT_ERR_INVALID_ARG;
-    const lsd::TopkLayout L = lsd::topk_layout(rows, cols, k, lsd::sort_route_keys(rows, cols, k));
-    const size_t need = L.total > L.s_total ? L.total : L.s_total;
-    if (!lsd::workspace_ok(d_workspace, workspace_bytes, need)) return LSDSORT_ERR_WORKSPACE;
+    const lsd::TopkLayout L = lsd::topk_layout(rows, cols, k);
+    if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.bytes())) return LSDSORT_ERR_WORKSPACE;
     int rank_method = 0;
     LSD_TRY(lsd::device_rank_method(8, &rank_method));
     return lsd::run_topk(static_cast<const uint32_t*>(d_keys), rows, cols, k, key_type, largest ? 1 : 0, xf,

@@ -1,5 +1,6 @@
 """CPU suite: the kernels of stage 1 (histograms.hip), stage 2 (scans.hip), the local stage, the hybrid planner, the segmented
-sort and top-k compile for gfx950 WITHOUT scratch, and with the occupancy and the static LDS they were measured with.
+sort and the row selections and sorts (topk.hip, topk16.hip, kth.hip, rows16.hip) compile for gfx950 WITHOUT scratch, and with the
+occupancy and the static LDS they were measured with.
 
 A register spill in these kernels does not break a parity test -- it multiplies the kernel's memory traffic (round 3: a loop
 around the local stage's body spilled 49 registers and took the stage from 0.55 to 2.07 ms; the parity tests stayed green).
@@ -18,7 +19,8 @@ from _kernel_resources import hipcc, kernel_resources
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kernel_resources.json")
 
 
-@pytest.mark.parametrize("source", ["histograms.hip", "scans.hip", "local_sort.hip", "hybrid.hip", "segmented.hip", "topk.hip"])
+@pytest.mark.parametrize("source", ["histograms.hip", "scans.hip", "local_sort.hip", "hybrid.hip", "segmented.hip", "topk.hip", "topk16.hip",
+                                    "kth.hip", "rows16.hip"])
 def test_no_scratch(source):
     if hipcc() is None:
         pytest.skip("no hipcc on this machine")

@@ -2,10 +2,10 @@
 resources (ScratchSize 0, no VGPR spill) from hipcc's own remarks."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
+
+from _kernel_resources import hipcc, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lsdradixsort_amd", "csrc")
@@ -117,18 +117,11 @@ def test_workspace_bytes_monotone_multiple_of_256_and_bounded():
     assert f(1, 1 << 28, 1024) < 1 << 20
 
 
-def test_topk_kernels_no_scratch(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
+def test_topk_kernels_no_scratch():
+    if hipcc() is None:
         pytest.skip("no hipcc on this machine")
-    p = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, "topk.hip"), "-o", str(tmp_path / "x.o")],
-                       capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", p.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", p.stderr)]
-    spills = [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", p.stderr)]
-    assert names and len(names) == len(scratch) == len(spills)
+    res = kernel_resources("topk.hip")
+    names = list(res)
     assert sum("topk" in name for name in names) >= 10 and all("topk" in name for name in names), names
-    for name, sc, sp in zip(names, scratch, spills):
-        assert sc == 0 and sp == 0, f"{name}: scratch {sc} B/lane, {sp} VGPRs spilled"
+    for name, r in res.items():
+        assert r["scratch"] == 0 and r["vgpr_spill"] == 0, f"{name}: scratch {r['scratch']} B/lane, {r['vgpr_spill']} VGPRs spilled"

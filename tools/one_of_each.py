@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""One of each kind of sort, once, for a kernel trace (GPU box):
+"""One of each kind of sort and of row selection (top-k, 16-bit top-k, sort_rows16, k-th value; each in every size class), once,
+for a kernel trace (GPU box):
     rocprofv3 --kernel-trace --stats -d DIR --output-format csv -- python tools/one_of_each.py
 Kernel names and call counts of two builds of the library can then be compared row by row (profiles/device_refactor)."""
 import os, sys
@@ -37,5 +38,17 @@ lsd.topk_rows(keys(1 << 28).view(1 << 14, 1 << 14), 32)
 lsd.topk_rows(keys(1 << 28).view(1 << 20, 256), 8)
 lsd.topk_rows(keys(1 << 28), 1024)
 lsd.topk_rows(keys(1 << 24).view(1 << 12, 1 << 12), 4000)                               # the sort route
+def keys16(n): return torch.randint(-(1 << 15), (1 << 15) - 1, (n,), dtype=torch.int16, device="cuda", generator=g)
+lsd.topk16_rows(keys16(1 << 26).view(1 << 12, 1 << 14), 32)                             # 16-bit top-k: workgroup tier
+lsd.topk16_rows(keys16(1 << 26).view(1 << 18, 256), 8)                                  # wave tier
+lsd.topk16_rows(keys16(1 << 26).view(64, 1 << 20), 1024)                                # long rows
+lsd.topk16_rows(keys16(1 << 24).view(1 << 12, 1 << 12), 4000)                           # the sort route
+lsd.sort_rows16(keys16(1 << 26).view(1 << 12, 1 << 14), return_indices=True)            # rows of 16-bit keys: workgroup tier
+lsd.sort_rows16(keys16(1 << 26).view(1 << 18, 256), return_indices=True)                # wave tier
+lsd.sort_rows16(keys16(1 << 26).view(512, 1 << 17), return_indices=True)                # long tier
+lsd.sort_rows16(keys16(1 << 26).view(16, 1 << 22), return_indices=True)                 # widen route
+lsd.median_rows(keys(1 << 26).view(1 << 12, 1 << 14))                                   # k-th value: workgroup tier
+lsd.median_rows(keys(1 << 26).view(1 << 18, 256))                                       # wave tier
+lsd.median_rows(keys(1 << 26).view(64, 1 << 20))                                        # long rows
 torch.cuda.synchronize()
 print("one of each: done")
