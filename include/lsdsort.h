@@ -356,6 +356,41 @@ LSDSORT_API int lsdsort_kth_device(const void* d_keys, size_t rows, size_t cols,
                                    void* d_out_keys /* [rows], caller's type */, uint32_t* d_out_idx /* [rows] or NULL */,
                                    void* d_workspace, size_t workspace_bytes, void* hip_stream);
 
+/* K-th value selection for 16-bit keys (lsdradixsort_amd/csrc/kth16.hip; the median, a percentile or a clipping threshold of
+ * float16 / bfloat16 rows without a conversion to float32): lsdsort_kth_device's contract, word for word, with the key types of
+ * lsdsort_keys16_device (lsdsort_key16_type; float16 and bfloat16 in IEEE total order; largest != 0 = ascending on the complemented
+ * sortable value).  d_keys: rows x cols 16-bit keys, row-major, READ ONLY.  Let S_r be the STABLE sort of row r in the requested
+ * order.  d_out_keys[r] = S_r[rank] (rank is 0-based), a 16-bit word in the caller's key type, and d_out_idx[r] the position within
+ * the row of that same item -- among the duplicates of the value the one the stable sort puts at `rank` (d_out_idx may be NULL:
+ * values only, and no position is written anywhere the caller can see).  The result equals column `rank` of
+ * lsdsort_topk16_device(.., k = rank + 1, ..), bit for bit, values and positions; it is identical on every run and under graph
+ * replay.  rows = 1 is the whole-array case.
+ * d_keys and d_out_keys need 2-byte alignment only and cols may be odd: every row is read by 16-byte loads of eight keys from ITS
+ * first 16-byte line on, the keys in front of that line and behind the row's last whole group one by one.
+ * The row is not sorted and no winner is written: a counting radix select of at most TWO digit levels stops where ONE key is left
+ * under the prefix or all 16 bits are fixed (rows of up to 1024 keys in one wavefront, up to 16384 in one workgroup, two rounds of
+ * 8-bit digits: one read of the row; longer ones by many workgroups, 11 bits then 5), then the wanted key is located among the keys
+ * of that value in position order (long rows: one count pass, then ONE chunk is read again): at most three reads of a long row plus
+ * one chunk -- 6 B/key by byte accounting, not measured -- and nothing written but counters and 6 B per row.  With d_out_idx == NULL a long row needs no locate: both
+ * levels run, the prefix is the value and one small kernel stores it -- two reads of the row.
+ * Stream-ordered, no host synchronisation, nothing allocated; every launch is sized from (rows, cols) and from whether d_out_idx
+ * was given: capturable in a graph after lsdsort_prepare_device.  Counters and row states are zeroed by a kernel of the call; phases
+ * are ordered by kernel boundaries.  The fault word is the first word of the workspace: lsdsort_check_device(d_workspace, stream)
+ * reports it -- set where a row's digit counts do not reach the rank or no key is located (neither is expected).  The result does
+ * not depend on lsdsort_set_rank_method.
+ * Checks, in order, each before a device is touched: key_type outside lsdsort_key16_type (INVALID_ARG), rows or rows * cols above
+ * LSDSORT_MAX_KEYS (TOO_LARGE), rows == 0 or cols == 0 (OK, nothing launched -- before the rank: an empty row has no valid rank),
+ * rank >= cols (INVALID_ARG), a NULL or odd d_keys or d_out_keys (INVALID_ARG), the workspace (WORKSPACE: NULL, not 256-byte
+ * aligned, or below lsdsort_kth16_workspace_bytes), the device (NO_DEVICE).
+ * lsdsort_kth16_workspace_bytes is a multiple of 256, monotonic in each argument, 0 where rows, cols or rows * cols is above
+ * LSDSORT_MAX_KEYS, and depends neither on the rank nor on d_out_idx.  It is O(rows), never O(rows * cols): the control block, 16 B
+ * per row, and for rows above 16384 keys 8 KiB of counters per row and 4 B per 16384 keys. */
+LSDSORT_API size_t lsdsort_kth16_workspace_bytes(size_t rows, size_t cols);
+LSDSORT_API int lsdsort_kth16_device(const void* d_keys, size_t rows, size_t cols, size_t rank /* 0-based */,
+                                     int key_type /* lsdsort_key16_type */, int largest,
+                                     void* d_out_keys /* [rows] 16-bit, caller's type */, uint32_t* d_out_idx /* [rows] or NULL */,
+                                     void* d_workspace, size_t workspace_bytes, void* hip_stream);
+
 /* After the stream has drained: LSDSORT_OK, or LSDSORT_ERR_DEVICE_FAULT if a kernel of the
  * last sort on this workspace gave up a bounded spin or refused destinations outside the output
  * (never expected; the output is then undefined).  Synchronises hip_stream.  With LSDSORT_REPROBE=1

@@ -193,6 +193,24 @@ inline void kth_device(const float* d_keys, size_t rows, size_t cols, size_t ran
                              workspace_bytes_, hip_stream), "lsdsort_kth_device");
 }
 
+// The same for 16-bit keys (lsdsort_kth16_device): column `rank` of topk16(.., k = rank + 1, ..).  uint16_t or int16_t by overload;
+// float16 and bfloat16 bits are passed as uint16_t with the key type named, as in topk16_device.  d_keys is only read; d_out_idx may
+// be null (long rows then need no locate).  Workspace of kth16_workspace_bytes(rows, cols).
+inline size_t kth16_workspace_bytes(size_t rows, size_t cols) { return lsdsort_kth16_workspace_bytes(rows, cols); }
+inline void kth16_device(const uint16_t* d_keys, size_t rows, size_t cols, size_t rank, uint16_t* d_out_keys, uint32_t* d_out_idx,
+                         void* d_workspace, size_t workspace_bytes_, bool largest = false,
+                         lsdsort_key16_type key_type = LSDSORT_KEY16_U16, void* hip_stream = nullptr)
+{
+    check(lsdsort_kth16_device(d_keys, rows, cols, rank, key_type, largest ? 1 : 0, d_out_keys, d_out_idx, d_workspace, workspace_bytes_,
+                               hip_stream), "lsdsort_kth16_device");
+}
+inline void kth16_device(const int16_t* d_keys, size_t rows, size_t cols, size_t rank, int16_t* d_out_keys, uint32_t* d_out_idx,
+                         void* d_workspace, size_t workspace_bytes_, bool largest = false, void* hip_stream = nullptr)
+{
+    check(lsdsort_kth16_device(d_keys, rows, cols, rank, LSDSORT_KEY16_I16, largest ? 1 : 0, d_out_keys, d_out_idx, d_workspace,
+                               workspace_bytes_, hip_stream), "lsdsort_kth16_device");
+}
+
 // The stable sort of every row of a row-major [rows x cols] array of 16-bit keys with each key's position in its row
 // (lsdsort_rows16_device): uint16_t or int16_t by overload; float16 and bfloat16 bits are passed as uint16_t with the key type named.
 // d_out_keys may be d_keys (in place); d_out_idx may be null.  Workspace of rows16_workspace_bytes(rows, cols).

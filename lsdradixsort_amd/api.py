@@ -25,6 +25,7 @@ __all__ = [
     "GPUSortRows16", "rows16_workspace_bytes", "set_rows16_route", "sort_rows16",
     "GPUSortSegmented", "segmented_workspace_bytes", "sort_rows", "GPUTopK", "topk_workspace_bytes", "topk_rows",
     "GPUKth", "kth_workspace_bytes", "kthvalue_rows", "median_rows",
+    "GPUKth16", "kth16_workspace_bytes", "kthvalue16_rows", "median16_rows",
     "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
     "MSBPartition", "SplitterPartition", "ThresholdPartition", "sharded_thresholds",
 ]
@@ -612,6 +613,82 @@ def topk16_rows(x, k: int, largest: bool = True, stream=None):
         values, indices = GPUTopK16(flat, k, key_type=str(x.dtype).replace("torch.", ""), largest=largest, stream=stream)
         lead = tuple(x.shape[:-1])
         return values.view(lead + (k,)), indices.view(lead + (k,)).to(torch.int64)
+
+
+def kth16_workspace_bytes(rows: int, cols: int) -> int:
+    """Bytes of device workspace ``GPUKth16`` needs for one rank of each of ``rows`` rows of ``cols`` 16-bit keys (whatever the
+    rank, with or without indices)."""
+    return int(lib().lsdsort_kth16_workspace_bytes(rows, cols))
+
+
+def GPUKth16(d_keys, rank: int, key_type: str = "int16", largest: bool = False, return_indices: bool = True, workspace=None,
+             stream=None, check_fault: bool = False):
+    """The key at 0-based ``rank`` of every row's stable sort (``lsdsort_kth16_device``): ``d_keys`` is a contiguous 1-D (one row)
+    or 2-D int16, float16 or bfloat16 CUDA tensor whose 16 bits compare as ``key_type``, paired with the dtype as in ``GPUTopK16``:
+    "uint16" / "int16" for an int16 tensor, "float16" / "bfloat16" for the tensor of that dtype (IEEE total order); ``largest``
+    counts the rank from the largest key down.  Returns ``(values, indices)`` -- ``[rows]`` (0-D for 1-D input), ``values`` in the
+    input's dtype, ``indices`` the int32 position within the row of that very item, or ``None`` without ``return_indices`` --
+    exactly column ``rank`` of ``GPUTopK16(d_keys, rank + 1, ...)``: among equal keys the stable sort's position, on every run.
+    ``d_keys`` is only read and never widened.  Stream-ordered; the rows are not sorted and no winner is written (a radix select of
+    at most two digit levels, then a locate; without indices a row above 16384 keys needs no locate)."""
+    torch = _torch()
+    _dev(d_keys, "d_keys", (torch.int16, torch.float16, torch.bfloat16), dims=(1, 2))
+    code = _key_type(key_type, KEY_TYPES_16)
+    fits = {torch.int16: ("uint16", "int16"), torch.float16: ("float16",), torch.bfloat16: ("bfloat16",)}[d_keys.dtype]
+    if key_type not in fits:
+        raise TypeError(f"a {str(d_keys.dtype).replace('torch.', '')} tensor selects with key_type " + " or ".join(f'"{k}"' for k in fits))
+    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
+    rank = int(rank)
+    if not 0 <= rank < cols:
+        raise ValueError("rank must be within 0 .. the row length - 1")
+    shape = () if d_keys.dim() == 1 else (rows,)
+    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
+        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
+        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
+    if workspace is None:
+        nbytes = kth16_workspace_bytes(rows, cols)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_kth16_workspace_bytes", "too many keys or rows")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    check(lib().lsdsort_kth16_device(d_keys.data_ptr(), rows, cols, rank, code, int(bool(largest)), values.data_ptr(),
+                                     indices.data_ptr() if return_indices else None, workspace.data_ptr(), workspace.numel(),
+                                     _stream(stream)), "lsdsort_kth16_device")
+    if check_fault and rows and cols:
+        _check_fault(workspace, stream)
+    return values, indices
+
+
+def kthvalue16_rows(x, k: int, stream=None):
+    """``torch.kthvalue(x, k, dim=-1)`` for an int16 / float16 / bfloat16 CUDA tensor of one or more dimensions, the 16-bit
+    counterpart of ``kthvalue_rows``: ``k`` is 1-based, the k-th smallest of every row -> ``(values, int64 indices)`` of the leading
+    shape.  The float types follow IEEE total order, not torch's: a row with NaNs does NOT propagate NaN as ``torch.kthvalue`` /
+    ``torch.median`` do -- NaNs sort by sign at the two ends (+NaN above +inf, -NaN below -inf), and -0.0 below +0.0.  The index is
+    the stable sort's (among equal keys the one the stable sort puts at that rank), where torch leaves it unspecified among ties."""
+    torch = _torch()
+    _dev(x, "x", (torch.int16, torch.float16, torch.bfloat16), contiguous=False)
+    if x.dim() == 0:
+        raise TypeError("x: at least one dimension")
+    cols = x.shape[-1]
+    k = int(k)
+    if not 1 <= k <= cols:
+        raise ValueError("k must be within 1 .. the row length")
+    with _on_stream(stream):
+        flat = x.contiguous().view(-1, cols)
+        values, indices = GPUKth16(flat, k - 1, key_type=str(x.dtype).replace("torch.", ""), stream=stream)
+        lead = tuple(x.shape[:-1])
+        return values.view(lead), indices.view(lead).to(torch.int64)
+
+
+def median16_rows(x, stream=None):
+    """``torch.median(x, dim=-1)`` for an int16 / float16 / bfloat16 CUDA tensor of one or more dimensions: ``kthvalue16_rows`` at
+    rank ``(cols - 1) // 2``, the lower median torch returns -> ``(values, int64 indices)``.  The float types follow IEEE total
+    order: a row with NaNs does NOT propagate NaN as ``torch.median`` does (NaNs sort by sign at the two ends), and -0.0 lies below
+    +0.0.  The index is the stable sort's, where torch leaves it unspecified among ties."""
+    torch = _torch()
+    _dev(x, "x", (torch.int16, torch.float16, torch.bfloat16), contiguous=False)
+    if x.dim() == 0 or x.shape[-1] == 0:
+        raise ValueError("x: at least one dimension, and a last one that is not empty")
+    return kthvalue16_rows(x, (x.shape[-1] - 1) // 2 + 1, stream=stream)
 
 
 def rows16_workspace_bytes(rows: int, cols: int) -> int:

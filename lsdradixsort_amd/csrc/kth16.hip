@@ -1,0 +1,424 @@
+// kth16.hip -- the 16-bit key at ONE rank of every row of a [rows x cols] array, with its position (lsdsort_kth16_device; DESIGN.md
+// section 6.9).  The 16-bit sibling of kth.hip: same contract, same size classes, and the same select skeleton, radix_select.hpp's,
+// here with Levels16 (11 then 5 bits; two rounds of 8-bit digits for the short rows) under the stop rule StopKth.  The median, a
+// percentile or a clipping threshold of float16 / bfloat16 rows, selected from the 2-byte keys as they lie in memory.
+//
+// No counterpart in the reference (it sorts one whole array of uint32, LSDRadixSort.cu:839-910).  Row r's result is item `rank` of
+// the stable sort of the row in the requested order: the map of keys16_map.hpp (to_sortable16, with the complement for largest) is
+// applied where a key is read, and the caller's 16-bit word is what is stored.
+//
+//   select   as in kth.hip, on 16 bits: it stops where the found bin holds ONE key, at the latest with all 16 bits in the prefix.
+//   locate   every key under the final prefix has the same value, so the wanted item is the `need`-th of them in POSITION order:
+//            per-lane match masks, a wave sum, per-wave counts through LDS (per-chunk counts through memory for long rows), and in
+//            the one wave that holds it a wave scan per group of eight.  One lane stores the key, un-mapped, by a 2-byte store, and
+//            its position.  No atomic-arrival order shows.
+//   values only, long rows   a 16-bit value is fully known once both levels have run: without an index buffer the select runs under
+//            StopNever16 (no early stop) and kth16_value_kernel stores from_sortable16(prefix) per row -- two reads of the row, six
+//            launches, no count, pick or locate.
+//
+// Key reads are topk16.hip's (Row<uint16_t>): `head` keys in front of the row's first 16-byte line (0..7) one by one, the `body` in
+// 16-byte groups of eight, two groups per lane per tile (register 8 j + e is body position q0 + 8 (64 j + lane) + e), the last group
+// that is not whole one by one.  A register without a key holds kNoKey = 0xFFFFFFFF: a sortable value is below 65536, so no
+// (prefix, shift) of a select matches it and kth.hip's validity mask is not needed.  The two loaders below are this unit's own copy
+// of topk16.hip's (one header once an ISA diff proves the move).
+// Size classes (those of every select here, by cols):
+//   cols <= kWaveSegCap (1024)      one wavefront per row, eight rows per workgroup, no workgroup barrier.  2 B/key read.
+//   cols <= kLocalSortCap (16384)   one workgroup of 16 wavefronts per row: the same
+//   longer                          many workgroups per row (chunks of body positions; chunk 0 owns the head): the two levels, then
+//                                   one count pass (keys under the prefix, per chunk), a per-row pick of the chunk that holds the
+//                                   `need`-th of them, and a locate that reads that ONE chunk up to the tile that holds the key.
+//                                   At most three reads of the row plus one chunk (6 B/key); a row whose bin holds one key after
+//                                   level 0 skips level 1.
+// Every launch is sized from (rows, cols) and from whether an index buffer was given; phases are ordered by kernel boundaries; every
+// store into the outputs is guarded by row < rows.  Counts that do not reach the rank, or a locate that finds no key, raise a fault
+// bit instead -- never expected.  Nothing here ranks with the returning add: the result does not depend on lsdsort_set_rank_method.
+#define LSDSORT_BUILD 1
+#include "../../include/lsdsort.h"
+
+#include "keys16_map.hpp"
+#include "lsd_device.hpp"
+#include "lsd_host.hpp"
+#include "radix_select.hpp"
+
+namespace lsd {
+namespace {
+
+constexpr uint32_t kKth16FaultCount = 1024u;    // fault word: the digit counts of a row do not reach the rank (never expected)
+constexpr uint32_t kKth16FaultLocate = 2048u;   // fault word: no key was located for a row (never expected; nothing stored)
+constexpr uint32_t kNoKey = 0xFFFFFFFFu;        // a sortable value is below 65536
+constexpr uint32_t kHeadBit = 1u << kRegs;      // match mask: the head register
+constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
+using Row16 = Row<uint16_t>;   // a lane holds two 16-byte groups of eight keys of its wave's tile
+
+// the values-only select of long rows: both levels always run, so that the prefix is the whole value
+struct StopNever16 {
+    static __device__ __forceinline__ bool stops(uint32_t, uint32_t) { return false; }
+};
+
+// The wave's tile from body position q0 on, valid below `end`: a whole group by one 16-byte load, the others key by key.
+__device__ __forceinline__ void load_tile(const Row16& r, uint32_t q0, uint32_t end, uint32_t lane, const Key16Map& m, uint32_t (&t)[kRegs])
+{
+#pragma unroll
+    for (int j = 0; j < kRegs / 8; j++) {
+        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
+        if (q < end && end - q >= kGroupKeys) {
+            const uint4 v = *reinterpret_cast<const uint4*>(r.keys + r.head + q);
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                t[8 * j + 2 * i] = to_sortable16(w[i] & 0xFFFFu, m);
+                t[8 * j + 2 * i + 1] = to_sortable16(w[i] >> 16, m);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                t[8 * j + e] = kNoKey;
+                if (q + (uint32_t)e < end) t[8 * j + e] = to_sortable16(r.keys[r.head + q + (uint32_t)e], m);
+            }
+        }
+    }
+}
+// head key `lane` of the row, for the one wave that owns the head
+__device__ __forceinline__ uint32_t load_head(const Row16& r, uint32_t lane, const Key16Map& m)
+{
+    return lane < r.head ? to_sortable16(r.keys[lane], m) : kNoKey;
+}
+
+struct Outputs {
+    uint16_t* keys;       // [rows], the caller's 16-bit words
+    uint32_t* idx;        // [rows] positions, may be null
+    uint32_t rows;
+    uint32_t* fault;
+};
+
+// Locate within one tile held in registers (load_tile at q0; h: the head keys in front of it, kNoKey where there is none).  `base`:
+// the keys under the prefix before this tile in the row; it moves on past the tile.  If the `need`-th (1-based) such key of the row
+// lies in this tile, the lane that holds it stores it.  Returns whether it did (uniform over the group).  s_wc: WAVES words.
+template <int WAVES>
+__device__ __forceinline__ bool locate_tile(const uint32_t (&t)[kRegs], uint32_t h, uint32_t q0, const Row16& r, uint32_t prefix,
+                                            uint32_t shift, uint32_t need, uint32_t& base, volatile lds_u32* s_wc, uint32_t wave,
+                                            uint32_t lane, uint32_t row, const Outputs& o, const Key16Map& m)
+{
+    uint32_t em = (h >> shift) == prefix ? kHeadBit : 0u;   // the keys under the prefix (kNoKey never is)
+#pragma unroll
+    for (int i = 0; i < kRegs; i++) em |= (t[i] >> shift) == prefix ? 1u << i : 0u;
+    const uint32_t mine = wave_sum((uint32_t)__builtin_popcount(em));
+    uint32_t before = base, all = mine;
+    if (WAVES > 1) {
+        if (lane == 0u) s_wc[wave] = mine;
+        __syncthreads();
+        all = 0u;
+        for (uint32_t w = 0; w < (uint32_t)WAVES; w++) {
+            const uint32_t c = s_wc[w];
+            if (w < wave) before += c;
+            all += c;
+        }
+        __syncthreads();   // the next tile writes s_wc again
+    }
+    const bool here = base < need && need - base <= all;   // uniform
+    if (here) {
+        auto store = [&](uint32_t key, uint32_t pos) {
+            if (row < o.rows) {
+                o.keys[row] = (uint16_t)from_sortable16(key, m);
+                if (o.idx) o.idx[row] = pos;
+            }
+        };
+        // position order: the head keys by lane, then group j of lane 0, 1, .. 63, j = 0, 1
+        const uint32_t ch = em >> kRegs;
+        const uint32_t hi = wave_inclusive_scan(ch);
+        if (ch != 0u && before + hi == need) store(h, lane);
+        before += (uint32_t)__builtin_amdgcn_readlane((int)hi, 63);
+#pragma unroll
+        for (int j = 0; j < kRegs / 8; j++) {
+            const uint32_t g = (em >> (8 * j)) & 0xFFu, c = (uint32_t)__builtin_popcount(g);
+            const uint32_t incl = wave_inclusive_scan(c), lo = before + incl - c;
+            if (lo < need && need - lo <= c) {
+                uint32_t left = need - lo;   // 1 .. c: which of this group's matching keys
+                const uint32_t pos = r.head + q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    if (((g >> e) & 1u) != 0u && --left == 0u) store(t[8 * j + e], pos + (uint32_t)e);
+                }
+            }
+            before += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        }
+    }
+    base += all;
+    return here;
+}
+
+// ---- short rows: one wavefront (WAVES = 1, eight rows per workgroup) or one workgroup (WAVES = 16) per row ----------------------
+struct ShortParams {
+    const uint16_t* keys;
+    uint32_t cols, rank;
+    Key16Map map;
+    Outputs out;
+};
+
+template <int WAVES>
+__global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) kth16_short_kernel(const ShortParams p)
+{
+    constexpr int kGroups = WAVES == 1 ? 8 : 1;      // rows in flight per workgroup
+    constexpr int kSlice = 256 + 8 + WAVES;          // per row: digit counters, the found bin, per-wave counts
+    __shared__ uint32_t smem[kGroups * kSlice];
+    const uint32_t lane = threadIdx.x & 63u, wave_of_block = threadIdx.x >> 6;
+    const uint32_t group = WAVES == 1 ? wave_of_block : 0u, wave = WAVES == 1 ? 0u : wave_of_block;
+    volatile lds_u32* const s_cnt = (volatile lds_u32*)((lds_u32*)smem + group * kSlice);
+    volatile lds_u32* const s_found = s_cnt + 256;
+    volatile lds_u32* const s_wc = s_cnt + 264;
+    // `row` is the same for every thread of a group (a wave, or the whole workgroup): its barriers are reached together
+    for (uint32_t row = blockIdx.x * kGroups + group; row < p.out.rows; row += gridDim.x * kGroups) {
+        const Row16 r = row_of(p.keys, row, p.cols);
+        const uint32_t q0 = wave * kWaveTile;
+        uint32_t t[kRegs];
+        load_tile(r, q0, r.body, lane, p.map, t);
+        const uint32_t h = wave == 0u ? load_head(r, lane, p.map) : kNoKey;
+        // round 0: every key there is; round 1: those whose top byte is the prefix (kNoKey never is)
+        auto count = [&](int round, uint32_t, uint32_t prefix, auto add) __attribute__((always_inline)) {
+            auto one = [&](uint32_t key) __attribute__((always_inline)) {
+                if (round == 0 ? key != kNoKey : (key >> 8) == prefix) add(key);
+            };
+#pragma unroll
+            for (int i = 0; i < kRegs; i++) one(t[i]);
+            one(h);
+        };
+        const Selected sel = select_short<WAVES, 2, StopKth>(s_cnt, s_found, wave, lane, p.rank + 1u, p.out.fault, kKth16FaultCount, count);
+        uint32_t base = 0u;
+        const bool found = locate_tile<WAVES>(t, h, q0, r, sel.prefix, sel.shift, sel.need, base, s_wc, wave, lane, row, p.out, p.map);
+        if (!found && sel.need != 0u && wave == 0u && lane == 0u) atomicOr(p.out.fault, kKth16FaultLocate);
+        group_sync<WAVES>();
+    }
+}
+
+// ---- long rows ------------------------------------------------------------------------------------------------------------------
+// Row state in the workspace (uint4).  During the select: x prefix, y shift (16: no level has run), z need, w done (the select
+// stopped: later levels return at once).  After the pick: x prefix, y shift, z which of the chunk's keys under the prefix is the
+// wanted one (1-based; 0: none), w the chunk that holds it.
+struct LongParams {
+    const uint16_t* keys;
+    uint32_t cols;
+    uint32_t chunk, chunks;       // body positions per chunk (a multiple of kLongTile), chunks per row
+    uint32_t chunk_cap;           // row stride of `counts`
+    uint4* state;
+    uint32_t* hist;               // [rows][kBins], zero on entry to every level
+    uint32_t* counts;             // [rows][chunk_cap]: keys under the prefix, per chunk
+    Key16Map map;
+    Outputs out;
+};
+
+// control block, counters and row states of a call (a kernel rather than memsets: one kind of node in a captured graph)
+__global__ void __launch_bounds__(256) kth16_clear_kernel(uint32_t* ctl, uint32_t* hist, uint32_t hist_words, uint4* state, uint32_t rows,
+                                                          uint32_t need)
+{
+    clear_select(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, ctl, hist, hist_words, state, rows, need, Levels16::kNoLevel);
+}
+
+// One chunk of one row per workgroup: the digit of every key under the row's prefix, counted in LDS.  LEVEL 0: the top 11 bits
+// of every key; LEVEL 1: the low 5 bits of the keys whose top 11 are the prefix.
+template <int LEVEL>
+__global__ void __launch_bounds__(kLongThreads) kth16_hist_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_hist[kBins];
+    hist_level(p, s_hist, [&](uint32_t row, uint32_t c, const uint4& st, uint32_t lane, uint32_t wave) __attribute__((always_inline)) {
+        const Row16 r = row_of(p.keys, row, p.cols);
+        const ChunkRange g = chunk_of(r, p.chunk, c);
+        auto count = [&](uint32_t key) __attribute__((always_inline)) {
+            const bool match = LEVEL == 0 ? key != kNoKey : (key >> Levels16::shift(0)) == st.x;
+            count_digit(s_hist, match, (key >> Levels16::shift(LEVEL)) & ((1u << Levels16::bits(LEVEL)) - 1u), lane);
+        };
+        if (c == 0u && wave == 0u) count(load_head(r, lane, p.map));   // uniform
+        for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
+            uint32_t t[kRegs];
+            load_tile(r, tile + wave * kWaveTile, g.hi, lane, p.map, t);
+#pragma unroll
+            for (int i = 0; i < kRegs; i++) count(t[i]);
+        }
+    });
+}
+
+// One workgroup per row: walk the bins from the best end to the one that holds the wanted key; the counters go back to zero.
+// The last level ends the select whatever the stop rule: both rules share its kernel.
+template <int LEVEL, class Stop>
+__global__ void __launch_bounds__(256) kth16_scan_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_part[4];
+    __shared__ uint32_t s_found[3];
+    scan_level<Levels16, LEVEL, Stop>(p, s_part, s_found, kKth16FaultCount);
+}
+
+// the keys under the prefix, per chunk
+__global__ void __launch_bounds__(kLongThreads) kth16_count_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_part[kLongWaves];
+    const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const Row16 r = row_of(p.keys, row, p.cols);
+    const ChunkRange g = chunk_of(r, p.chunk, c);
+    uint32_t ne = 0u;
+    if (st.y < Levels16::kNoLevel && st.z != 0u) {   // (uniform) else: a row no scan has visited, or one whose counts fell short -- never
+        if (c == 0u && wave == 0u) ne += (load_head(r, lane, p.map) >> st.y) == st.x ? 1u : 0u;   // uniform
+        for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
+            uint32_t t[kRegs];
+            load_tile(r, tile + wave * kWaveTile, g.hi, lane, p.map, t);
+#pragma unroll
+            for (int i = 0; i < kRegs; i++) ne += (t[i] >> st.y) == st.x ? 1u : 0u;
+        }
+    }
+    ne = wave_sum(ne);
+    if (lane == 0u) s_part[wave] = ne;
+    __syncthreads();
+    if (tid == 0u) {
+        uint32_t e = 0u;
+        for (uint32_t w = 0; w < kLongWaves; w++) e += s_part[w];
+        p.counts[(size_t)row * p.chunk_cap + c] = e;
+    }
+}
+
+// One workgroup per row: the chunk that holds the `need`-th key under the prefix, and which of that chunk's such keys it is.
+__global__ void __launch_bounds__(256) kth16_pick_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_part[4];
+    __shared__ uint32_t s_found[2];
+    const uint32_t row = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    const uint32_t* const counts = p.counts + (size_t)row * p.chunk_cap;
+    constexpr uint32_t E = kMaxChunks / 256u;
+    uint32_t c[E], sum = 0u;
+#pragma unroll
+    for (uint32_t e = 0; e < E; e++) {
+        c[e] = tid * E + e < p.chunks ? counts[tid * E + e] : 0u;
+        sum += c[e];
+    }
+    if (tid == 0u) s_found[0] = kNoChunk;
+    uint32_t run = group_exclusive_scan<4>(sum, lane, wave, s_part);
+    const uint32_t need = st.y < Levels16::kNoLevel ? st.z : 0u;
+#pragma unroll
+    for (uint32_t e = 0; e < E; e++) {
+        if (run < need && need - run <= c[e]) {   // at most one chunk of the row
+            s_found[0] = tid * E + e;
+            s_found[1] = need - run;
+        }
+        run += c[e];
+    }
+    __syncthreads();
+    if (tid != 0u) return;
+    const uint32_t chunk = s_found[0];
+    if (chunk == kNoChunk) {   // the keys under the prefix are fewer than `need`: nothing is located
+        atomicOr(p.out.fault, kKth16FaultLocate);
+        p.state[row] = make_uint4(0u, 0u, 0u, kNoChunk);
+        return;
+    }
+    p.state[row] = make_uint4(st.x, st.y, s_found[1], chunk);
+}
+
+// One workgroup per row reads the picked chunk, and only up to the tile that holds the key.
+__global__ void __launch_bounds__(kLongThreads) kth16_locate_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_wc_raw[kLongWaves];
+    const uint32_t row = blockIdx.x;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    if (st.z == 0u || st.w >= p.chunks) return;   // (uniform) nothing was picked: the fault bit is already set
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const Row16 r = row_of(p.keys, row, p.cols);
+    const ChunkRange g = chunk_of(r, p.chunk, st.w);
+    volatile lds_u32* const s_wc = (volatile lds_u32*)(lds_u32*)s_wc_raw;
+    uint32_t base = 0u;
+    bool found = false;
+    // chunk 0 has at least one tile (a long row's body is longer than its head), and its first tile carries the head
+    for (uint32_t tile = g.lo; tile < g.hi && !found; tile += kLongTile) {   // uniform
+        const uint32_t q0 = tile + wave * kWaveTile;
+        uint32_t t[kRegs];
+        load_tile(r, q0, g.hi, lane, p.map, t);
+        const uint32_t h = (st.w == 0u && tile == g.lo && wave == 0u) ? load_head(r, lane, p.map) : kNoKey;   // uniform
+        found = locate_tile<(int)kLongWaves>(t, h, q0, r, st.x, st.y, st.z, base, s_wc, wave, lane, row, p.out, p.map);
+    }
+    if (!found && tid == 0u) atomicOr(p.out.fault, kKth16FaultLocate);
+}
+
+// Values only: after both levels the prefix is the row's whole sortable value (shift 0, need not 0).  Anything else is a row whose
+// counts fell short (its fault bit is set) or one no scan has visited -- never: nothing is stored for it.
+__global__ void __launch_bounds__(256) kth16_value_kernel(const LongParams p)
+{
+    for (uint32_t row = blockIdx.x * blockDim.x + threadIdx.x; row < p.out.rows; row += gridDim.x * blockDim.x) {
+        const uint4 st = p.state[row];
+        if (st.y == 0u && st.z != 0u) p.out.keys[row] = (uint16_t)from_sortable16(st.x & 0xFFFFu, p.map);
+        else atomicOr(p.out.fault, kKth16FaultLocate);
+    }
+}
+
+// Workspace: control | row states (16 B per row) | counters [rows][2048] | chunk counts (4 B per chunk) -- the last two for rows
+// above kLocalSortCap keys only.  At most 256 + rows (16 + 8192 + 4 ceil(cols / 16384)) + 3 * 255 bytes; never O(rows * cols).
+using Kth16Layout = SelectLayout;   // no offsets, and nothing behind the chunk counts: `end` is the figure
+Kth16Layout kth16_layout(size_t rows, size_t cols) { return select_layout(rows, cols, false, 4); }
+
+int run_kth16(const uint16_t* keys, size_t rows, size_t cols, size_t rank, const Key16Map& map, uint16_t* out_keys, uint32_t* out_idx,
+              char* ws, const Kth16Layout& L, hipStream_t stream)
+{
+    uint32_t* const ctl = reinterpret_cast<uint32_t*>(ws);
+    const Outputs out{out_keys, out_idx, (uint32_t)rows, ctl};
+    if (cols <= (size_t)kLocalSortCap) {
+        const ShortParams sp{keys, (uint32_t)cols, (uint32_t)rank, map, out};
+        hipLaunchKernelGGL(kth16_clear_kernel, dim3(1), dim3(256), 0, stream, ctl, (uint32_t*)nullptr, 0u, (uint4*)nullptr, 0u, 0u);
+        if (cols <= (size_t)kWaveSegCap)
+            hipLaunchKernelGGL(kth16_short_kernel<1>, dim3(grid_for(rows, 8, 16384)), dim3(512), 0, stream, sp);
+        else
+            hipLaunchKernelGGL(kth16_short_kernel<16>, dim3(grid_for(rows, 1, 4096)), dim3(1024), 0, stream, sp);
+        LSD_HIP(hipGetLastError());
+        return LSDSORT_OK;
+    }
+    LongParams lp{};
+    lp.map = map;
+    lp.out = out;
+    if (!out_idx) {   // values only: both levels, then the prefix is the value
+        static const LevelKernels<LongParams> levels[] = {{kth16_hist_kernel<0>, kth16_scan_kernel<0, StopNever16>},
+                                                          {kth16_hist_kernel<1>, kth16_scan_kernel<1, StopKth>}};
+        LSD_TRY(select_long(lp, keys, rows, cols, (uint32_t)rank + 1u, ws, L, kth16_clear_kernel, levels, stream));
+        hipLaunchKernelGGL(kth16_value_kernel, dim3(grid_for(rows, 256, 1024)), dim3(256), 0, stream, lp);
+        LSD_HIP(hipGetLastError());
+        return LSDSORT_OK;
+    }
+    static const LevelKernels<LongParams> levels[] = {{kth16_hist_kernel<0>, kth16_scan_kernel<0, StopKth>},
+                                                      {kth16_hist_kernel<1>, kth16_scan_kernel<1, StopKth>}};
+    LSD_TRY(select_long(lp, keys, rows, cols, (uint32_t)rank + 1u, ws, L, kth16_clear_kernel, levels, stream));
+    const uint32_t grid = (uint32_t)(rows * lp.chunks), row_grid = (uint32_t)rows;
+    hipLaunchKernelGGL(kth16_count_kernel, dim3(grid), dim3(kLongThreads), 0, stream, lp);
+    hipLaunchKernelGGL(kth16_pick_kernel, dim3(row_grid), dim3(256), 0, stream, lp);
+    hipLaunchKernelGGL(kth16_locate_kernel, dim3(row_grid), dim3(kLongThreads), 0, stream, lp);
+    LSD_HIP(hipGetLastError());
+    return LSDSORT_OK;
+}
+
+}  // namespace
+}  // namespace lsd
+
+extern "C" {
+
+size_t lsdsort_kth16_workspace_bytes(size_t rows, size_t cols)
+{
+    if (rows > LSDSORT_MAX_KEYS || cols > LSDSORT_MAX_KEYS) return 0;
+    if (rows != 0 && cols > LSDSORT_MAX_KEYS / rows) return 0;
+    return lsd::kth16_layout(rows, cols).end;
+}
+
+int lsdsort_kth16_device(const void* d_keys, size_t rows, size_t cols, size_t rank, int key_type, int largest, void* d_out_keys,
+                         uint32_t* d_out_idx, void* d_workspace, size_t workspace_bytes, void* hip_stream)
+{
+    Key16Map map;
+    LSD_TRY(key16_map(key_type, largest, &map));
+    if (rows > LSDSORT_MAX_KEYS || (rows != 0 && cols > LSDSORT_MAX_KEYS / rows)) return LSDSORT_ERR_TOO_LARGE;
+    if (rows == 0 || cols == 0) return LSDSORT_OK;   // before the rank: an empty row has no valid rank
+    if (rank >= cols) return LSDSORT_ERR_INVALID_ARG;
+    if (!d_keys || !d_out_keys || (((uintptr_t)d_keys | (uintptr_t)d_out_keys) & 1)) return LSDSORT_ERR_INVALID_ARG;
+    const lsd::Kth16Layout L = lsd::kth16_layout(rows, cols);
+    if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.end)) return LSDSORT_ERR_WORKSPACE;
+    int rank_method = 0;   // asked for the device set-up alone: nothing here ranks with the returning add
+    LSD_TRY(lsd::device_rank_method(8, &rank_method));
+    return lsd::run_kth16(static_cast<const uint16_t*>(d_keys), rows, cols, rank, map, static_cast<uint16_t*>(d_out_keys), d_out_idx,
+                          static_cast<char*>(d_workspace), L, static_cast<hipStream_t>(hip_stream));
+}
+
+}  // extern "C"

@@ -1,0 +1,364 @@
+"""GPU suite: lsdsort_kth16_device (GPUKth16, kthvalue16_rows, median16_rows), bit-exact, positions included.
+
+Contract: row r's result is item `rank` of the stable sort of the row in the requested order, with its position.  Every case is
+checked against TWO oracles: numpy (the 16-bit sortable map, then np.argsort(kind="stable") per row) and the library's own
+GPUTopK16(x, rank + 1, ..)[:, -1].  The fault word is read after every call (check_fault=True).
+
+Boundaries of the implementation (lsdradixsort_amd/csrc/kth16.hip): rows of up to 1024 keys take one wavefront (eight rows per
+workgroup), up to 16384 one workgroup, longer ones many workgroups per row (chunks of 16384 keys or more, 11 bits then 5); every
+row is read from its own first 16-byte line on, so odd row lengths and offset views move the head / body / tail split; without an
+index buffer a long row takes a launch sequence of its own (both levels, then the prefix is the value)."""
+import numpy as np
+import pytest
+import torch
+
+import lsdradixsort_amd as lsd
+from _guarded import assert_intact, guarded, guarded_workspace
+from _guarded16 import assert_intact16, bits_of, guarded16
+
+pytestmark = pytest.mark.gpu
+
+KEY_TYPES = {"uint16": 0, "int16": 1, "float16": 2, "bfloat16": 3}
+DTYPES = {"uint16": torch.int16, "int16": torch.int16, "float16": torch.float16, "bfloat16": torch.bfloat16}
+ALL_TYPES = list(KEY_TYPES)
+# +-0, +-inf, NaNs of both signs (quiet, signalling, all ones), denormals, the largest finite values
+SPECIALS = {
+    "float16": np.array([0x0000, 0x8000, 0x7C00, 0xFC00, 0x7E00, 0xFE00, 0x7C01, 0xFC01, 0xFFFF, 0x7FFF, 0x0001, 0x8001, 0x03FF,
+                         0x83FF, 0x7BFF, 0xFBFF], dtype=np.uint16),
+    "bfloat16": np.array([0x0000, 0x8000, 0x7F80, 0xFF80, 0x7FC0, 0xFFC0, 0x7F81, 0xFF81, 0xFFFF, 0x7FFF, 0x0001, 0x8001, 0x007F,
+                          0x807F, 0x7F7F, 0xFF7F], dtype=np.uint16),
+}
+
+
+def sortable16_np(u, key_type, largest):
+    """the map of include/lsdsort.h restated: the uint16 whose unsigned order is the requested one"""
+    u = u.astype(np.uint32)
+    if key_type == "int16":
+        u = u ^ np.uint32(0x8000)
+    elif key_type in ("float16", "bfloat16"):
+        u = u ^ np.where(u & np.uint32(0x8000), np.uint32(0xFFFF), np.uint32(0x8000))
+    return ((u ^ np.uint32(0xFFFF)) if largest else u).astype(np.uint16)
+
+
+def expected_np(keys, key_type, largest):
+    """keys: [rows, cols] uint16 bits -> the full stable order of every row: (sorted keys, positions)"""
+    order = np.argsort(sortable16_np(keys, key_type, largest), axis=1, kind="stable")
+    return np.take_along_axis(keys, order, axis=1), order.astype(np.uint32)
+
+
+def ranks_of(cols):
+    return sorted({r for r in (0, 1, cols // 2, cols - 2, cols - 1) if 0 <= r < cols})
+
+
+def inputs(rows, cols, key_type, seed):
+    """name -> [rows, cols] uint16 bit patterns"""
+    rng = np.random.default_rng(seed)
+
+    def rnd(hi):
+        return rng.integers(0, hi, (rows, cols), dtype=np.uint32).astype(np.uint16)
+
+    out = {"uniform bits": rnd(1 << 16)}
+    four = np.array([5, 0x0100, 0x7FFF, 0xFFF0], dtype=np.uint16)
+    out["four values"] = four[rng.integers(0, 4, (rows, cols))]                  # tie runs across lanes, waves and chunks
+    out["all equal"] = np.full((rows, cols), 0x9E37, dtype=np.uint16)            # the position must equal the rank
+    out["shared top 11 bits"] = np.uint16(0xABC0) | rnd(32)                      # the second level decides; long rows are all ties
+    out["shared top 8 bits"] = np.uint16(0xAB00) | rnd(256)
+    lone = np.full((rows, cols), 0x4000, dtype=np.uint16)                        # one 0x0001 among 0x4000s: the select stops after
+    lone[np.arange(rows), rng.integers(0, cols, rows)] = 0x0001                  # the first level or round, with a nonzero shift
+    out["lone minimum"] = lone
+    if key_type in SPECIALS:
+        f = rnd(1 << 16).reshape(-1)
+        pick = rng.random(rows * cols) < 0.3
+        f[pick] = SPECIALS[key_type][rng.integers(0, SPECIALS[key_type].size, int(pick.sum()))]
+        out["float specials"] = f.reshape(rows, cols)
+    return out
+
+
+def to_dev(keys, key_type, offset=0):
+    """the keys on the device as a contiguous [rows, cols] view `offset` elements into a 512-byte aligned buffer"""
+    rows, cols = keys.shape
+    flat = torch.empty(rows * cols + offset, dtype=torch.int16, device="cuda")
+    assert flat.data_ptr() % 512 == 0
+    view = flat[offset:].view(rows, cols)
+    view.copy_(torch.from_numpy(np.ascontiguousarray(keys).view(np.int16)))
+    assert view.is_contiguous() and view.data_ptr() % 16 == (2 * offset) % 16
+    return view.view(DTYPES[key_type])
+
+
+def bits(t):
+    """uint16 bit patterns of a 16-bit tensor, uint32 of an int32 one"""
+    t = t.contiguous()
+    if t.dtype == torch.int32:
+        return t.cpu().numpy().view(np.uint32)
+    return t.view(torch.int16).cpu().numpy().view(np.uint16)
+
+
+def check_ranks(dk, keys, key_type, what, ranks=None):
+    """every rank, both orders: against numpy and against GPUTopK16's last column, values and positions bit for bit"""
+    rows, cols = keys.shape
+    for largest in (False, True):
+        ek, ei = expected_np(keys, key_type, largest)
+        for rank in ranks_of(cols) if ranks is None else ranks:
+            values, indices = lsd.GPUKth16(dk, rank, key_type=key_type, largest=largest, check_fault=True)
+            tag = f"{what} {rows}x{cols} {key_type} largest={largest} rank={rank}"
+            assert values.shape == (rows,) and indices.shape == (rows,), tag
+            assert values.dtype == DTYPES[key_type] and indices.dtype == torch.int32, tag
+            gv, gi = bits(values), bits(indices)
+            assert np.array_equal(gv, ek[:, rank]), f"{tag}: values differ from numpy: {gv[:4]} want {ek[:4, rank]}"
+            assert np.array_equal(gi, ei[:, rank]), f"{tag}: positions differ from numpy: {gi[:4]} want {ei[:4, rank]}"
+            tv, ti = lsd.GPUTopK16(dk, rank + 1, key_type=key_type, largest=largest, check_fault=True)
+            assert np.array_equal(gv, bits(tv[:, -1])), f"{tag}: values differ from GPUTopK16"
+            assert np.array_equal(gi, bits(ti[:, -1])), f"{tag}: positions differ from GPUTopK16"
+            if "all equal" in what:
+                assert (gi == rank).all(), f"{tag}: the position must equal the rank"
+    assert np.array_equal(bits(dk), keys), f"{what}: input changed"
+
+
+def check_shape(rows, cols, key_type):
+    for name, keys in inputs(rows, cols, key_type, seed=1000 * rows + cols).items():
+        check_ranks(to_dev(keys, key_type), keys, key_type, name)
+
+
+WAVE = [(rows, cols) for cols in (1, 2, 7, 8, 9, 63, 64, 65, 255, 1000, 1023, 1024) for rows in (1, 9, 17)]
+GROUP = [(3, 1025), (3, 4099), (3, 16384)]
+LONG = [(3, 16385), (3, 32773), (3, 70001)]
+
+
+@pytest.mark.parametrize("key_type", ALL_TYPES)
+@pytest.mark.parametrize("shape", WAVE, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_wave_tier(shape, key_type):
+    check_shape(*shape, key_type)
+
+
+@pytest.mark.parametrize("key_type", ALL_TYPES)
+@pytest.mark.parametrize("shape", GROUP, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_workgroup_tier(shape, key_type):
+    check_shape(*shape, key_type)
+
+
+@pytest.mark.parametrize("key_type", ALL_TYPES)
+@pytest.mark.parametrize("shape", LONG, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_long_tier(shape, key_type):
+    check_shape(*shape, key_type)
+
+
+@pytest.mark.parametrize("key_type", ["bfloat16", "uint16"])
+def test_one_long_row_of_many_chunks(key_type):
+    """[1 x (2^20 + 13)]: 65 chunks, so the pick of the chunk and the remainder of `need` matter"""
+    check_shape(1, (1 << 20) + 13, key_type)
+
+
+TIER_SHAPES = [(9, 1000), (3, 4099), (3, 70001)]   # one per tier, all with odd or unaligned rows
+
+
+@pytest.mark.parametrize("offset", [1, 3, 4, 7])
+@pytest.mark.parametrize("shape", TIER_SHAPES + [(2, 1024), (2, 16384), (2, 32768)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_views_off_the_16_byte_line(shape, offset):
+    rows, cols = shape
+    for name, keys in inputs(rows, cols, "bfloat16", seed=offset + cols).items():
+        if name in ("uniform bits", "four values", "float specials"):
+            check_ranks(to_dev(keys, "bfloat16", offset), keys, "bfloat16", f"{name} offset {offset}")
+
+
+@pytest.mark.parametrize("key_type", ["int16", "float16"])
+@pytest.mark.parametrize("shape", TIER_SHAPES + [(3, 16385), (2, 32768)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_values_only_and_one_row_input(shape, key_type):
+    """without an index buffer: the same values (the long shapes take the launch sequence without a locate); 1-D input: 0-D"""
+    rows, cols = shape
+    for name in ("four values", "shared top 11 bits", "lone minimum", "uniform bits"):
+        keys = inputs(rows, cols, key_type, seed=cols)[name]
+        dk = to_dev(keys, key_type, 3)
+        for largest in (False, True):
+            ek, ei = expected_np(keys, key_type, largest)
+            for rank in ranks_of(cols):
+                with_v, with_i = lsd.GPUKth16(dk, rank, key_type=key_type, largest=largest, check_fault=True)
+                values, indices = lsd.GPUKth16(dk, rank, key_type=key_type, largest=largest, return_indices=False, check_fault=True)
+                assert indices is None and values.shape == (rows,) and values.dtype == DTYPES[key_type]
+                assert np.array_equal(bits(values), ek[:, rank]), (name, largest, rank)
+                assert np.array_equal(bits(values), bits(with_v)) and np.array_equal(bits(with_i), ei[:, rank]), (name, largest, rank)
+                v1, i1 = lsd.GPUKth16(dk[1], rank, key_type=key_type, largest=largest, check_fault=True)   # 1-D: the whole-array case
+                assert v1.shape == () and i1.shape == ()
+                assert int(bits(v1)) == ek[1, rank] and int(bits(i1)) == ei[1, rank], (name, largest, rank)
+                v0, i0 = lsd.GPUKth16(dk[1], rank, key_type=key_type, largest=largest, return_indices=False, check_fault=True)
+                assert i0 is None and v0.shape == () and int(bits(v0)) == ek[1, rank], (name, largest, rank)
+        assert np.array_equal(bits(dk), keys)
+
+
+def raw_call(keys, rank, key_type, largest, with_idx, skip_bytes, short_by=0):
+    """the C entry with every array inside guard zones and a workspace of exactly the reported figure"""
+    rows, cols = keys.shape
+    L = lsd.lib()
+    kw, kv = guarded16(keys, skip_bytes, DTYPES[key_type])
+    ow, ov = guarded16(np.zeros(rows, dtype=np.uint16), skip_bytes)
+    iw, iv = guarded(np.zeros(rows, dtype=np.uint32))
+    need = L.lsdsort_kth16_workspace_bytes(rows, cols)
+    assert need > 0 and need % 256 == 0
+    ww, wv = guarded_workspace(need)
+    torch.cuda.synchronize()
+    st = L.lsdsort_kth16_device(kv.data_ptr(), rows, cols, rank, KEY_TYPES[key_type], int(largest), ov.data_ptr(),
+                                iv.data_ptr() if with_idx else None, wv.data_ptr(), need - short_by,
+                                int(torch.cuda.current_stream().cuda_stream))
+    return st, (kw, kv), (ow, ov), (iw, iv), (ww, wv)
+
+
+@pytest.mark.parametrize("skip_bytes", [0, 2, 6, 14])
+@pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_guard_bands_exact_workspace_and_null_indices(shape, skip_bytes):
+    rows, cols = shape
+    keys = inputs(rows, cols, "float16", seed=cols + skip_bytes)["float specials"]
+    rank = cols // 2
+    ek, ei = expected_np(keys, "float16", True)
+    st, *_ = raw_call(keys, rank, "float16", True, True, skip_bytes, short_by=1)
+    assert st == lsd.errors.LSDSORT_ERR_WORKSPACE, "one byte less than the figure is refused"
+    for with_idx in (True, False):
+        st, (kw, kv), (ow, ov), (iw, iv), (ww, wv) = raw_call(keys, rank, "float16", True, with_idx, skip_bytes)
+        assert st == 0, st
+        assert lsd.lib().lsdsort_check_device(wv.data_ptr(), None) == 0
+        assert int(wv[:4].view(torch.int32).item()) == 0, "fault word"
+        assert np.array_equal(bits_of(ov), ek[:, rank]), f"values (indices={with_idx})"
+        if with_idx:
+            assert np.array_equal(bits(iv), ei[:, rank]), "positions"
+        else:
+            assert (bits(iv) == 0).all(), "no index buffer was given: nothing may be written"
+        assert_intact16(keys=kw, values=ow)
+        assert_intact(indices=iw, workspace=ww)
+        assert np.array_equal(bits_of(kv), keys.reshape(-1)), "a read-only input was changed"
+
+
+@pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_same_result_without_the_returning_add_rank_form(shape):
+    rows, cols = shape
+    keys = inputs(rows, cols, "int16", seed=cols + 1)["shared top 8 bits"]
+    dk = to_dev(keys, "int16")
+    lsd.set_rank_method(0)
+    try:
+        for largest in (False, True):
+            ek, ei = expected_np(keys, "int16", largest)
+            for rank in ranks_of(cols):
+                values, indices = lsd.GPUKth16(dk, rank, key_type="int16", largest=largest, check_fault=True)
+                assert np.array_equal(bits(values), ek[:, rank]) and np.array_equal(bits(indices), ei[:, rank]), (largest, rank)
+                values, _ = lsd.GPUKth16(dk, rank, key_type="int16", largest=largest, return_indices=False, check_fault=True)
+                assert np.array_equal(bits(values), ek[:, rank]), (largest, rank)
+    finally:
+        lsd.set_rank_method(-1)
+
+
+@pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_two_eager_calls_agree(shape):
+    rows, cols = shape
+    keys = inputs(rows, cols, "uint16", seed=cols + 2)["four values"]
+    dk = to_dev(keys, "uint16")
+    ws = torch.empty(lsd.kth16_workspace_bytes(rows, cols), dtype=torch.uint8, device="cuda")
+    a = lsd.GPUKth16(dk, cols // 2, key_type="uint16", largest=True, workspace=ws, check_fault=True)
+    b = lsd.GPUKth16(dk, cols // 2, key_type="uint16", largest=True, workspace=ws, check_fault=True)   # the same workspace, used again
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    ek, ei = expected_np(keys, "uint16", True)
+    assert np.array_equal(bits(b[0]), ek[:, cols // 2]) and np.array_equal(bits(b[1]), ei[:, cols // 2])
+
+
+@pytest.mark.parametrize("shape,with_idx", [(s, True) for s in TIER_SHAPES] + [(TIER_SHAPES[-1], False)],
+                         ids=lambda v: str(v).replace(" ", ""))
+def test_graph_replay_on_changed_input(shape, with_idx):
+    rows, cols = shape
+    rank = cols // 2
+    L = lsd.lib()
+    assert L.lsdsort_prepare_device() == 0
+    dk = torch.zeros((rows, cols), dtype=torch.int16, device="cuda")
+    out_k = torch.zeros(rows, dtype=torch.int16, device="cuda")
+    out_i = torch.zeros(rows, dtype=torch.int32, device="cuda")
+    ws = torch.empty(L.lsdsort_kth16_workspace_bytes(rows, cols), dtype=torch.uint8, device="cuda")
+
+    def call():
+        st = L.lsdsort_kth16_device(dk.data_ptr(), rows, cols, rank, KEY_TYPES["int16"], 1, out_k.data_ptr(),
+                                    out_i.data_ptr() if with_idx else None, ws.data_ptr(), ws.numel(),
+                                    int(torch.cuda.current_stream().cuda_stream))
+        assert st == 0, st
+
+    kinds = inputs(rows, cols, "int16", seed=cols + 3)
+    dk.copy_(torch.from_numpy(kinds["uniform bits"].view(np.int16)))
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        call()   # warm-up: device set-up stays out of the capture
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        call()
+    for name in ("four values", "shared top 11 bits"):   # two replays, each on changed input
+        keys = kinds[name]
+        dk.copy_(torch.from_numpy(keys.view(np.int16)))
+        out_k.zero_()
+        out_i.zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        fault = int(ws[:4].view(torch.int32).item())
+        assert fault == 0, f"replay on {name}: fault word {fault:#x}"
+        ek, ei = expected_np(keys, "int16", True)
+        assert np.array_equal(bits(out_k), ek[:, rank]), f"replay on {name}: values"
+        if with_idx:
+            assert np.array_equal(bits(out_i), ei[:, rank]), f"replay on {name}: positions"
+        else:
+            assert (bits(out_i) == 0).all(), "no index buffer was given: nothing may be written"
+    assert L.lsdsort_check_device(ws.data_ptr(), None) == 0
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=lambda d: str(d).replace("torch.", ""))
+@pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_against_the_32_bit_entry(shape, dtype):
+    """NaN-free rows only: the conversion to float32 is exact and order-preserving (IEEE total order, -0.0 and +-inf and denormals
+    included) only without NaNs, whose payloads a conversion may change"""
+    rows, cols = shape
+    key_type = str(dtype).replace("torch.", "")
+    g = torch.Generator(device="cuda").manual_seed(cols)
+    x = torch.randn((rows, cols), generator=g, device="cuda").to(dtype)
+    x[:, ::97] = float("inf")
+    x[:, 1::89] = float("-inf")
+    x[:, 2::83] = -0.0
+    x[:, 3::79] = 0.0
+    x[:, 4::73] = torch.tensor(1, dtype=torch.int16).view(dtype).item()   # the smallest denormal
+    assert not torch.isnan(x).any()
+    wide = x.float()
+    for largest in (False, True):
+        for rank in ranks_of(cols):
+            v16, i16 = lsd.GPUKth16(x, rank, key_type=key_type, largest=largest, check_fault=True)
+            v32, i32 = lsd.GPUKth(wide, rank, key_type="float32", largest=largest, check_fault=True)
+            assert torch.equal(i16, i32), (largest, rank)
+            assert torch.equal(v16.float().view(torch.int32), v32.view(torch.int32)), (largest, rank)
+
+
+@pytest.mark.parametrize("shape", [(5, 1000), (3, 4099), (3, 70001)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_values_against_torch_kthvalue_and_median(shape):
+    """NaN-free float16 / bfloat16 (no -0.0 either: torch calls the zeros equal) and int16, where torch's order is the library's;
+    torch leaves the index among ties unspecified, so the index is checked by what it points at"""
+    rows, cols = shape
+    rng = np.random.default_rng(cols)
+    hosts = []
+    for dtype in (torch.float16, torch.bfloat16):
+        f = torch.from_numpy(rng.standard_normal((2, rows, cols)).astype(np.float32)).to(dtype)
+        f[f == 0] = 1.0
+        f[..., ::97] = float("inf")
+        f[..., 1::89] = float("-inf")
+        f[..., 2::83] = torch.tensor(3, dtype=torch.int16).view(dtype).item()   # a denormal
+        hosts.append(f)
+    i = rng.integers(-1 << 15, 1 << 15, (2, rows, cols), dtype=np.int64).astype(np.int16)
+    i[..., ::5] = 7
+    hosts.append(torch.from_numpy(i))
+    for host in hosts:
+        x = host.cuda()
+        for k in sorted({1, 2, cols // 2, cols - 1, cols}):
+            v, idx = lsd.kthvalue16_rows(x, k)
+            tv = torch.kthvalue(host, k, dim=-1).values
+            assert v.shape == tv.shape == (2, rows) and idx.dtype == torch.int64 and v.dtype == host.dtype
+            assert torch.equal(v.cpu(), tv), f"{host.dtype} k={k}: values differ from torch.kthvalue"
+            assert torch.equal(torch.gather(x, -1, idx.unsqueeze(-1)).squeeze(-1), v), f"{host.dtype} k={k}: index"
+        v, idx = lsd.median16_rows(x)
+        tv = torch.median(host, dim=-1).values
+        assert v.shape == (2, rows) and idx.shape == (2, rows) and idx.dtype == torch.int64
+        assert torch.equal(v.cpu(), tv), f"{host.dtype}: values differ from torch.median"
+        assert torch.equal(torch.gather(x, -1, idx.unsqueeze(-1)).squeeze(-1), v)
+        v1, i1 = lsd.kthvalue16_rows(x[0, 0], 3)   # one row: 0-D results
+        assert v1.shape == () and i1.shape == () and torch.equal(v1.cpu(), torch.kthvalue(host[0, 0], 3).values)
+        assert x[0, 0, int(i1)] == v1
+        m1, j1 = lsd.median16_rows(x[0, 0])
+        assert m1.shape == () and j1.shape == () and x[0, 0, int(j1)] == m1
