@@ -356,6 +356,45 @@ LSDSORT_API int lsdsort_kth_device(const void* d_keys, size_t rows, size_t cols,
                                    void* d_out_keys /* [rows], caller's type */, uint32_t* d_out_idx /* [rows] or NULL */,
                                    void* d_workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Multi-rank k-th value selection: SEVERAL order statistics of every row in one call (lsdradixsort_amd/csrc/kth_multi.hip) --
+ * quartiles, a set of percentiles, the two clipping thresholds of a row, and the two adjacent order statistics floor(q (n - 1)) and
+ * ceil(q (n - 1)) that an interpolating quantile (torch.quantile's `linear` and `midpoint`) is made of.
+ * `ranks` is a HOST array of num_ranks (at most LSDSORT_KTH_MAX_RANKS) 0-based ranks, each below cols, in any order, repeats
+ * allowed; it is copied into the launches (as the splitters of lsdsort_splitter_partition_u32_device are), so it is fixed in a
+ * captured graph.  d_out_keys[r * num_ranks + j] and d_out_idx[r * num_ranks + j] are exactly what
+ * lsdsort_kth_device(.., rank = ranks[j], ..) stores for row r -- item ranks[j] of the row's STABLE sort in the requested order and
+ * the position of that very item, values and positions bit for bit; slot j is defined by ranks[j] alone.  d_out_idx may be NULL:
+ * values only, and no position is written anywhere the caller can see.  Everything else is lsdsort_kth_device's contract: d_keys is
+ * READ ONLY and needs 4-byte alignment only, cols may be anything, key_type U32 / I32 / F32 (IEEE total order), largest != 0 =
+ * ascending on the complemented key; the result is identical on every run and under graph replay.
+ * The reads of the row are shared by the ranks.  Rows of up to 1024 keys (one wavefront) and up to 16384 (one workgroup) are loaded
+ * into registers once and every rank selects and locates there: one read of the row, one launch.  Longer rows: the first digit level
+ * is ONE histogram per row that every rank walks; at the two later levels each key is tested against the prefixes of the ranks still
+ * open, and ranks that share a prefix are counted once; one count pass serves every rank; then each rank reads its ONE chunk again.
+ * At most four reads of a long row plus num_ranks chunks, in the ten launches of the single-rank call.
+ * Stream-ordered, no host synchronisation, nothing allocated; every launch is sized from (rows, cols, num_ranks) alone: capturable
+ * in a graph after lsdsort_prepare_device.  Control block, counters and states are zeroed by a kernel of the call; phases are
+ * ordered by kernel boundaries.  The fault word is the first word of the workspace: lsdsort_check_device(d_workspace, stream)
+ * reports it -- bit 1024 where a row's digit counts do not reach a rank, bit 2048 where no key is located (neither is expected).
+ * The result does not depend on lsdsort_set_rank_method.
+ * Checks, in order, each before a device is touched: key_type outside U32 / I32 / F32 (INVALID_ARG), num_ranks above
+ * LSDSORT_KTH_MAX_RANKS (INVALID_ARG), rows, rows * cols or rows * num_ranks above LSDSORT_MAX_KEYS (TOO_LARGE), rows == 0,
+ * cols == 0 or num_ranks == 0 (OK, nothing launched), a NULL `ranks` or any ranks[j] >= cols (INVALID_ARG), a NULL d_keys or
+ * d_out_keys or either not 4-byte aligned (INVALID_ARG), the workspace (WORKSPACE: NULL, not 256-byte aligned, or below
+ * lsdsort_kth_multi_workspace_bytes), the device (NO_DEVICE).
+ * lsdsort_kth_multi_workspace_bytes is a multiple of 256, monotonic in each argument, 0 above the limits and for num_ranks above
+ * LSDSORT_KTH_MAX_RANKS, and depends neither on the rank values nor on d_out_idx.  It is O(rows * num_ranks), never O(rows * cols):
+ * the control block, 16 B per row and rank, and for rows above 16384 keys 8 KiB of counters per row and rank and 4 B per 16384 keys
+ * and rank. */
+#define LSDSORT_KTH_MAX_RANKS 8
+LSDSORT_API size_t lsdsort_kth_multi_workspace_bytes(size_t rows, size_t cols, size_t num_ranks);
+LSDSORT_API int lsdsort_kth_multi_device(const void* d_keys, size_t rows, size_t cols,
+                                         const size_t* ranks /* HOST array, num_ranks entries, 0-based */, size_t num_ranks,
+                                         int key_type /* lsdsort_key_type: U32, I32, F32 */, int largest,
+                                         void* d_out_keys /* [rows][num_ranks], caller's type */,
+                                         uint32_t* d_out_idx /* [rows][num_ranks] or NULL */, void* d_workspace,
+                                         size_t workspace_bytes, void* hip_stream);
+
 /* K-th value selection for 16-bit keys (lsdradixsort_amd/csrc/kth16.hip; the median, a percentile or a clipping threshold of
  * float16 / bfloat16 rows without a conversion to float32): lsdsort_kth_device's contract, word for word, with the key types of
  * lsdsort_keys16_device (lsdsort_key16_type; float16 and bfloat16 in IEEE total order; largest != 0 = ascending on the complemented

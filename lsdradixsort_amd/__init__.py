@@ -15,6 +15,7 @@ from .api import (  # noqa: F401  (api.__all__, name for name)
     GPUSortRows16, rows16_workspace_bytes, set_rows16_route, sort_rows16,
     GPUSortSegmented, segmented_workspace_bytes, sort_rows, GPUTopK, topk_workspace_bytes, topk_rows,
     GPUKth, kth_workspace_bytes, kthvalue_rows, median_rows,
+    GPUKthMulti, kth_multi_workspace_bytes, quantile_rows, quantile_ranks,
     GPUKth16, kth16_workspace_bytes, kthvalue16_rows, median16_rows,
     BuildHistograms, BuildOffsets, RankScatter, DigitHistograms,
     MSBPartition, SplitterPartition, ThresholdPartition, sharded_thresholds,

@@ -25,6 +25,7 @@ __all__ = [
     "GPUSortRows16", "rows16_workspace_bytes", "set_rows16_route", "sort_rows16",
     "GPUSortSegmented", "segmented_workspace_bytes", "sort_rows", "GPUTopK", "topk_workspace_bytes", "topk_rows",
     "GPUKth", "kth_workspace_bytes", "kthvalue_rows", "median_rows",
+    "GPUKthMulti", "kth_multi_workspace_bytes", "quantile_rows", "quantile_ranks",
     "GPUKth16", "kth16_workspace_bytes", "kthvalue16_rows", "median16_rows",
     "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
     "MSBPartition", "SplitterPartition", "ThresholdPartition", "sharded_thresholds",
@@ -441,6 +442,129 @@ def median_rows(x, stream=None):
     if x.dim() == 0 or x.shape[-1] == 0:
         raise ValueError("x: at least one dimension, and a last one that is not empty")
     return kthvalue_rows(x, (x.shape[-1] - 1) // 2 + 1, stream=stream)
+
+
+def kth_multi_workspace_bytes(rows: int, cols: int, num_ranks: int) -> int:
+    """Bytes of device workspace ``GPUKthMulti`` needs for ``num_ranks`` ranks of each of ``rows`` rows of ``cols`` keys (whatever
+    the ranks)."""
+    return int(lib().lsdsort_kth_multi_workspace_bytes(rows, cols, num_ranks))
+
+
+def GPUKthMulti(d_keys, ranks, key_type: str = "uint32", largest: bool = False, return_indices: bool = True, workspace=None,
+                stream=None, check_fault: bool = False):
+    """The keys at several 0-based ``ranks`` of every row's stable sort, in one call (``lsdsort_kth_multi_device``): ``GPUKth``
+    argument for argument, with a sequence of 1 .. ``LSDSORT_KTH_MAX_RANKS`` ranks in ``0 .. cols - 1`` -- in any order, repeats
+    allowed -- where it has one.  Returns ``(values, indices)`` of shape ``[rows, m]`` (``[m]`` for 1-D input): column ``j`` is
+    exactly ``GPUKth(d_keys, ranks[j], ...)``, values and int32 positions bit for bit; ``indices`` is ``None`` without
+    ``return_indices``.  ``d_keys`` is only read, and read once for all ranks where ``GPUKth`` reads it once per rank.  The ranks
+    are host values: they are fixed in a captured graph."""
+    torch = _torch()
+    _dev(d_keys, "d_keys", (torch.int32, torch.float32), dims=(1, 2))
+    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
+    try:
+        ranks = [int(r) for r in ranks]
+    except TypeError:
+        raise ValueError("ranks: a sequence of ints") from None
+    if not 1 <= len(ranks) <= errors.LSDSORT_KTH_MAX_RANKS:
+        raise ValueError(f"ranks: 1 .. {errors.LSDSORT_KTH_MAX_RANKS} of them, got {len(ranks)}")
+    if not all(0 <= r < cols for r in ranks):
+        raise ValueError("every rank must be within 0 .. the row length - 1")
+    code = _key_type(key_type, KEY_TYPES_32)
+    if d_keys.dtype == torch.float32 and key_type != "float32":
+        raise TypeError('a float32 tensor selects with key_type="float32" only (an int32 tensor holds any of the three bit patterns)')
+    m = len(ranks)
+    shape = (m,) if d_keys.dim() == 1 else (rows, m)
+    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
+        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
+        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
+    if workspace is None:
+        nbytes = kth_multi_workspace_bytes(rows, cols, m)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_kth_multi_workspace_bytes", "too many keys or rows")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    check(lib().lsdsort_kth_multi_device(d_keys.data_ptr(), rows, cols, (ctypes.c_size_t * m)(*ranks), m, code, int(bool(largest)),
+                                         values.data_ptr(), indices.data_ptr() if return_indices else None, workspace.data_ptr(),
+                                         workspace.numel(), _stream(stream)), "lsdsort_kth_multi_device")
+    if check_fault and rows and cols:
+        _check_fault(workspace, stream)
+    return values, indices
+
+
+QUANTILE_MODES = ("linear", "lower", "higher", "midpoint", "nearest")
+
+
+def quantile_ranks(q, cols: int, interpolation: str = "linear"):
+    """The host half of ``quantile_rows``, torch.quantile's own arithmetic: ``q`` (a float, a sequence, or a 0-D or 1-D tensor
+    with values in [0, 1]) and the row length -> ``(below, above, weights, scalar)``.  ``below`` and ``above`` are lists of the
+    order statistics every quantile is made of, ``weights`` a float32 CPU tensor, ``scalar`` whether ``q`` had no dimension:
+    quantile i is ``torch.lerp(sorted[below[i]], sorted[above[i]], weights[i])``; for ``lower`` / ``higher`` / ``nearest`` it is
+    ``sorted[below[i]]`` itself, and ``above`` and ``weights`` are ``None``.
+    ``ranks = q.to(float32) * (cols - 1)``, in float32; ``lower`` floors it, ``higher`` takes the ceiling, ``nearest`` rounds half
+    to even; ``linear`` takes floor and ceiling with the weight ``ranks - floor``, ``midpoint`` the same two with the weight 0.5.
+    Needs no device and no library."""
+    torch = _torch()
+    if interpolation not in QUANTILE_MODES:
+        raise ValueError("interpolation: " + " or ".join(f'"{m}"' for m in QUANTILE_MODES) + f", got {interpolation!r}")
+    cols = int(cols)
+    if cols < 1:
+        raise ValueError("x: a last dimension that is not empty")
+    qt = q.detach().cpu().to(torch.float32) if isinstance(q, torch.Tensor) else torch.as_tensor(q, dtype=torch.float32)
+    if qt.dim() > 1:
+        raise ValueError("q: a float, a sequence of floats, or a 0-D or 1-D tensor")
+    scalar = qt.dim() == 0
+    qt = qt.reshape(-1)
+    if not bool(((qt >= 0) & (qt <= 1)).all()):
+        raise ValueError("q: values within [0, 1]")
+    ranks = qt * (cols - 1)
+    if interpolation == "lower":
+        ranks = ranks.floor()
+    elif interpolation == "higher":
+        ranks = ranks.ceil()
+    elif interpolation == "nearest":
+        ranks = ranks.round()
+    below = ranks.floor()
+    if interpolation not in ("linear", "midpoint"):
+        return below.to(torch.int64).tolist(), None, None, scalar
+    weights = torch.full_like(ranks, 0.5) if interpolation == "midpoint" else ranks - below
+    return below.to(torch.int64).tolist(), ranks.ceil().to(torch.int64).tolist(), weights, scalar
+
+
+def quantile_rows(x, q, interpolation: str = "linear", stream=None):
+    """``torch.quantile(x, q, dim=-1, keepdim=False, interpolation=...)`` for a float32 CUDA tensor of one or more dimensions,
+    without sorting a row: the order statistics the quantiles are made of come from ``GPUKthMulti``.  ``q`` is a float, a sequence,
+    or a 0-D or 1-D tensor with values in [0, 1]; it is brought to the host, because ranks are host arguments.  The result has
+    torch's shape: the leading shape of ``x`` for a scalar ``q``, ``(len(q),)`` + the leading shape for a 1-D ``q``.
+    The arithmetic is torch's own (``quantile_ranks``): ``ranks = q.to(float32) * (cols - 1)`` in float32; ``lower`` takes the
+    value at the floor, ``higher`` at the ceiling, ``nearest`` at ``round`` (half to even); ``linear`` is
+    ``torch.lerp(v[floor], v[ceil], ranks - floor)`` and ``midpoint`` ``torch.lerp(v[floor], v[ceil], 0.5)``.  The distinct integer
+    ranks of a call are de-duplicated and selected in groups of at most ``LSDSORT_KTH_MAX_RANKS``: more distinct ranks than that
+    mean more than one read of ``x``.
+    float32 follows IEEE total order, not torch's: a row with NaNs does NOT propagate NaN as ``torch.quantile`` does -- NaNs sort
+    by sign at the two ends (+NaN above +inf, -NaN below -inf), and -0.0 below +0.0."""
+    torch = _torch()
+    _dev(x, "x", (torch.float32,), contiguous=False)
+    if x.dim() == 0:
+        raise TypeError("x: at least one dimension")
+    cols = x.shape[-1]
+    below, above, weights, scalar = quantile_ranks(q, cols, interpolation)
+    distinct = sorted(set(below) | set(above or ()))
+    slot = {rank: i for i, rank in enumerate(distinct)}
+    group = errors.LSDSORT_KTH_MAX_RANKS
+    lead = tuple(x.shape[:-1])
+    with _on_stream(stream):
+        flat = x.contiguous().view(-1, cols)
+        parts = [GPUKthMulti(flat, distinct[at:at + group], key_type="float32", return_indices=False, stream=stream)[0]
+                 for at in range(0, len(distinct), group)]
+        stats = torch.cat(parts, dim=1) if parts else flat.new_empty((flat.shape[0], 0))   # [rows, distinct ranks]
+
+        def take(ranks):
+            return stats.index_select(1, torch.tensor([slot[r] for r in ranks], dtype=torch.int64).to(x.device, non_blocking=True))
+
+        values = take(below)
+        if above is not None:
+            values = torch.lerp(values, take(above), weights.to(x.device, non_blocking=True))
+        values = values.view(lead + (len(below),)).movedim(-1, 0)
+        return values[0] if scalar else values
 
 
 def GPUSortWide(d_keys, d_vals=None, r: int = 8, workspace=None, stream=None, check_fault: bool = False, key_type: str = "uint64",
