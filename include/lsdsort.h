@@ -430,6 +430,48 @@ LSDSORT_API int lsdsort_kth16_device(const void* d_keys, size_t rows, size_t col
                                      void* d_out_keys /* [rows] 16-bit, caller's type */, uint32_t* d_out_idx /* [rows] or NULL */,
                                      void* d_workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Multi-rank k-th value selection for 16-bit keys: SEVERAL order statistics of every row in one call
+ * (lsdradixsort_amd/csrc/kth16_multi.hip) -- the quartiles, a set of percentiles or the clipping thresholds of float16 / bfloat16
+ * rows, and the two adjacent order statistics an interpolating quantile is made of, without a conversion to float32.  It is to
+ * lsdsort_kth16_device what lsdsort_kth_multi_device is to lsdsort_kth_device.
+ * `ranks` is a HOST array of num_ranks (at most LSDSORT_KTH_MAX_RANKS) 0-based ranks, each below cols, in any order, repeats
+ * allowed; it is copied into the launches, so it is fixed in a captured graph.  d_out_keys[r * num_ranks + j] and
+ * d_out_idx[r * num_ranks + j] are exactly what lsdsort_kth16_device(.., rank = ranks[j], ..) stores for row r -- item ranks[j] of
+ * the row's STABLE sort in the requested order and the position of that very item, values and positions bit for bit; slot j is
+ * defined by ranks[j] alone.  d_out_idx may be NULL: values only, and no position is written anywhere the caller can see.
+ * Everything else is lsdsort_kth16_device's contract: d_keys is READ ONLY; d_keys and d_out_keys need 2-byte alignment only and cols
+ * may be odd; the key types are lsdsort_key16_type (float16 and bfloat16 in IEEE total order; largest != 0 = ascending on the
+ * complemented sortable value); the result is identical on every run and under graph replay.
+ * The reads of the row are shared by the ranks.  Rows of up to 1024 keys (one wavefront) and up to 16384 (one workgroup) are loaded
+ * into registers once and every rank selects and locates there: one read of the row, one launch after the clear.  Longer rows: the
+ * first digit level (11 bits) is ONE histogram per row in which every rank finds its bin; at the second (5 bits) each key is tested
+ * against the prefixes of the ranks still open, and ranks that share a prefix share 32 counters; one count pass serves every rank;
+ * then each rank reads its ONE chunk again: at most three reads of a long row plus num_ranks chunks, in eight launches.  With
+ * d_out_idx == NULL a long row needs no locate: both levels run for every rank, the prefix is the value and one small kernel stores
+ * it -- two reads of the row (4 B/key by byte accounting) in six launches, whatever num_ranks.
+ * Stream-ordered, no host synchronisation, nothing allocated; every launch is sized from (rows, cols, num_ranks) and from whether
+ * d_out_idx was given: capturable in a graph after lsdsort_prepare_device.  Control block, counters and states are zeroed by a
+ * kernel of the call; phases are ordered by kernel boundaries.  The fault word is the first word of the workspace:
+ * lsdsort_check_device(d_workspace, stream) reports it -- bit 1024 where a row's digit counts do not reach a rank, bit 2048 where
+ * nothing is located or a values-only state is not a whole value (neither is expected).  The result does not depend on
+ * lsdsort_set_rank_method.
+ * Checks, in order, each before a device is touched: key_type outside lsdsort_key16_type (INVALID_ARG), num_ranks above
+ * LSDSORT_KTH_MAX_RANKS (INVALID_ARG), rows, rows * cols or rows * num_ranks above LSDSORT_MAX_KEYS (TOO_LARGE), rows == 0,
+ * cols == 0 or num_ranks == 0 (OK, nothing launched), a NULL `ranks` or any ranks[j] >= cols (INVALID_ARG), a NULL or odd d_keys or
+ * d_out_keys (INVALID_ARG), the workspace (WORKSPACE: NULL, not 256-byte aligned, or below lsdsort_kth16_multi_workspace_bytes), the
+ * device (NO_DEVICE).
+ * lsdsort_kth16_multi_workspace_bytes is a multiple of 256, monotonic in each argument, 0 above the limits and for num_ranks above
+ * LSDSORT_KTH_MAX_RANKS, and depends neither on the rank values nor on d_out_idx.  It is O(rows * num_ranks), never O(rows * cols):
+ * the control block, 16 B per row and rank, and for rows above 16384 keys 8 KiB of counters per ROW, 128 B of counters per row and
+ * rank and 4 B per 16384 keys and rank.  It need not equal lsdsort_kth16_workspace_bytes at num_ranks = 1. */
+LSDSORT_API size_t lsdsort_kth16_multi_workspace_bytes(size_t rows, size_t cols, size_t num_ranks);
+LSDSORT_API int lsdsort_kth16_multi_device(const void* d_keys, size_t rows, size_t cols,
+                                           const size_t* ranks /* HOST array, num_ranks entries, 0-based */, size_t num_ranks,
+                                           int key_type /* lsdsort_key16_type */, int largest,
+                                           void* d_out_keys /* [rows][num_ranks] 16-bit, caller's type */,
+                                           uint32_t* d_out_idx /* [rows][num_ranks] or NULL */, void* d_workspace,
+                                           size_t workspace_bytes, void* hip_stream);
+
 /* After the stream has drained: LSDSORT_OK, or LSDSORT_ERR_DEVICE_FAULT if a kernel of the
  * last sort on this workspace gave up a bounded spin or refused destinations outside the output
  * (never expected; the output is then undefined).  Synchronises hip_stream.  With LSDSORT_REPROBE=1

@@ -17,6 +17,7 @@ from .api import (  # noqa: F401  (api.__all__, name for name)
     GPUKth, kth_workspace_bytes, kthvalue_rows, median_rows,
     GPUKthMulti, kth_multi_workspace_bytes, quantile_rows, quantile_ranks,
     GPUKth16, kth16_workspace_bytes, kthvalue16_rows, median16_rows,
+    GPUKth16Multi, kth16_multi_workspace_bytes, quantile16_rows,
     BuildHistograms, BuildOffsets, RankScatter, DigitHistograms,
     MSBPartition, SplitterPartition, ThresholdPartition, sharded_thresholds,
 )

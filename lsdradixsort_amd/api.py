@@ -27,6 +27,7 @@ __all__ = [
     "GPUKth", "kth_workspace_bytes", "kthvalue_rows", "median_rows",
     "GPUKthMulti", "kth_multi_workspace_bytes", "quantile_rows", "quantile_ranks",
     "GPUKth16", "kth16_workspace_bytes", "kthvalue16_rows", "median16_rows",
+    "GPUKth16Multi", "kth16_multi_workspace_bytes", "quantile16_rows",
     "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
     "MSBPartition", "SplitterPartition", "ThresholdPartition", "sharded_thresholds",
 ]
@@ -543,6 +544,17 @@ def quantile_rows(x, q, interpolation: str = "linear", stream=None):
     by sign at the two ends (+NaN above +inf, -NaN below -inf), and -0.0 below +0.0."""
     torch = _torch()
     _dev(x, "x", (torch.float32,), contiguous=False)
+
+    def select(flat, ranks):
+        return GPUKthMulti(flat, ranks, key_type="float32", return_indices=False, stream=stream)[0]
+
+    return _quantile_of(x, q, interpolation, stream, select)
+
+
+def _quantile_of(x, q, interpolation, stream, select):
+    """What ``quantile_rows`` and ``quantile16_rows`` share: ``select(flat, ranks)`` -> the float32 ``[rows, len(ranks)]`` order
+    statistics of at most ``LSDSORT_KTH_MAX_RANKS`` distinct ranks; the rest is ``quantile_ranks`` and torch's own arithmetic."""
+    torch = _torch()
     if x.dim() == 0:
         raise TypeError("x: at least one dimension")
     cols = x.shape[-1]
@@ -553,9 +565,8 @@ def quantile_rows(x, q, interpolation: str = "linear", stream=None):
     lead = tuple(x.shape[:-1])
     with _on_stream(stream):
         flat = x.contiguous().view(-1, cols)
-        parts = [GPUKthMulti(flat, distinct[at:at + group], key_type="float32", return_indices=False, stream=stream)[0]
-                 for at in range(0, len(distinct), group)]
-        stats = torch.cat(parts, dim=1) if parts else flat.new_empty((flat.shape[0], 0))   # [rows, distinct ranks]
+        parts = [select(flat, distinct[at:at + group]) for at in range(0, len(distinct), group)]
+        stats = torch.cat(parts, dim=1) if parts else flat.new_empty((flat.shape[0], 0), dtype=torch.float32)   # [rows, distinct ranks]
 
         def take(ranks):
             return stats.index_select(1, torch.tensor([slot[r] for r in ranks], dtype=torch.int64).to(x.device, non_blocking=True))
@@ -813,6 +824,73 @@ def median16_rows(x, stream=None):
     if x.dim() == 0 or x.shape[-1] == 0:
         raise ValueError("x: at least one dimension, and a last one that is not empty")
     return kthvalue16_rows(x, (x.shape[-1] - 1) // 2 + 1, stream=stream)
+
+
+def kth16_multi_workspace_bytes(rows: int, cols: int, num_ranks: int) -> int:
+    """Bytes of device workspace ``GPUKth16Multi`` needs for ``num_ranks`` ranks of each of ``rows`` rows of ``cols`` 16-bit keys
+    (whatever the ranks, with or without indices)."""
+    return int(lib().lsdsort_kth16_multi_workspace_bytes(rows, cols, num_ranks))
+
+
+def GPUKth16Multi(d_keys, ranks, key_type: str = "int16", largest: bool = False, return_indices: bool = True, workspace=None,
+                  stream=None, check_fault: bool = False):
+    """The 16-bit keys at several 0-based ``ranks`` of every row's stable sort, in one call (``lsdsort_kth16_multi_device``):
+    ``GPUKth16`` argument for argument -- the same tensors, and the same pairing of dtype and ``key_type`` -- with a sequence of
+    1 .. ``LSDSORT_KTH_MAX_RANKS`` ranks in ``0 .. cols - 1``, in any order, repeats allowed, where it has one.  Returns
+    ``(values, indices)`` of shape ``[rows, m]`` (``[m]`` for 1-D input): column ``j`` is exactly ``GPUKth16(d_keys, ranks[j], ...)``,
+    values in the input's dtype and int32 positions bit for bit; ``indices`` is ``None`` without ``return_indices``.  ``d_keys`` is
+    only read and never widened, and read once for all ranks where ``GPUKth16`` reads it once per rank; without indices a row above
+    16384 keys is read twice, whatever the number of ranks.  The ranks are host values: they are fixed in a captured graph."""
+    torch = _torch()
+    _dev(d_keys, "d_keys", (torch.int16, torch.float16, torch.bfloat16), dims=(1, 2))
+    code = _key_type(key_type, KEY_TYPES_16)
+    fits = {torch.int16: ("uint16", "int16"), torch.float16: ("float16",), torch.bfloat16: ("bfloat16",)}[d_keys.dtype]
+    if key_type not in fits:
+        raise TypeError(f"a {str(d_keys.dtype).replace('torch.', '')} tensor selects with key_type " + " or ".join(f'"{k}"' for k in fits))
+    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
+    try:
+        ranks = [int(r) for r in ranks]
+    except TypeError:
+        raise ValueError("ranks: a sequence of ints") from None
+    if not 1 <= len(ranks) <= errors.LSDSORT_KTH_MAX_RANKS:
+        raise ValueError(f"ranks: 1 .. {errors.LSDSORT_KTH_MAX_RANKS} of them, got {len(ranks)}")
+    if not all(0 <= r < cols for r in ranks):
+        raise ValueError("every rank must be within 0 .. the row length - 1")
+    m = len(ranks)
+    shape = (m,) if d_keys.dim() == 1 else (rows, m)
+    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
+        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
+        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
+    if workspace is None:
+        nbytes = kth16_multi_workspace_bytes(rows, cols, m)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_kth16_multi_workspace_bytes", "too many keys or rows")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    check(lib().lsdsort_kth16_multi_device(d_keys.data_ptr(), rows, cols, (ctypes.c_size_t * m)(*ranks), m, code, int(bool(largest)),
+                                           values.data_ptr(), indices.data_ptr() if return_indices else None, workspace.data_ptr(),
+                                           workspace.numel(), _stream(stream)), "lsdsort_kth16_multi_device")
+    if check_fault and rows and cols:
+        _check_fault(workspace, stream)
+    return values, indices
+
+
+def quantile16_rows(x, q, interpolation: str = "linear", stream=None):
+    """``torch.quantile(x.float(), q, dim=-1, keepdim=False, interpolation=...)`` for a float16 / bfloat16 CUDA tensor of one or
+    more dimensions -- which ``torch.quantile`` itself refuses -- without widening ``x`` and without sorting a row: the 16-bit
+    counterpart of ``quantile_rows``.  The result is **float32**, in torch's shapes.  ``quantile_ranks`` gives the order statistics
+    the quantiles are made of; the distinct ones come from ``GPUKth16Multi(..., return_indices=False)`` in groups of at most
+    ``LSDSORT_KTH_MAX_RANKS`` (two reads of a long row per group), are converted with ``.float()`` -- exact -- and go through
+    ``quantile_rows``' own ``index_select`` / ``torch.lerp``.
+    As in ``kthvalue16_rows`` the float types follow IEEE total order, not torch's: a row with NaNs does NOT propagate NaN as
+    ``torch.quantile`` does -- NaNs sort by sign at the two ends (+NaN above +inf, -NaN below -inf), and -0.0 below +0.0."""
+    torch = _torch()
+    _dev(x, "x", (torch.float16, torch.bfloat16), contiguous=False)
+    key_type = str(x.dtype).replace("torch.", "")
+
+    def select(flat, ranks):
+        return GPUKth16Multi(flat, ranks, key_type=key_type, return_indices=False, stream=stream)[0].float()
+
+    return _quantile_of(x, q, interpolation, stream, select)
 
 
 def rows16_workspace_bytes(rows: int, cols: int) -> int:
