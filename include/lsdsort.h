@@ -472,6 +472,74 @@ LSDSORT_API int lsdsort_kth16_multi_device(const void* d_keys, size_t rows, size
                                            uint32_t* d_out_idx /* [rows][num_ranks] or NULL */, void* d_workspace,
                                            size_t workspace_bytes, void* hip_stream);
 
+/* K-th value selection for 16-bit keys with a rank of its own for EVERY row, read from device memory
+ * (lsdradixsort_amd/csrc/kth16_rowk.hip): lsdsort_kth16_device's contract, word for word, with one change -- row r uses
+ * d_ranks[r], a DEVICE array of `rows` 0-based ranks (4-byte aligned) that a kernel of the call reads.  For every row with
+ * d_ranks[r] < cols, d_out_keys[r] and d_out_idx[r] are exactly what lsdsort_kth16_device(.., rank = d_ranks[r], ..) stores for that
+ * row, bit for bit: item d_ranks[r] of the row's STABLE sort in the requested order and the position of that very item, the float
+ * types in IEEE total order, largest != 0 = ascending on the complemented sortable value.  d_keys is READ ONLY; d_keys and d_out_keys
+ * need 2-byte alignment only and cols may be odd; d_out_idx may be NULL (values only).
+ * The host never reads d_ranks and NO value in it sizes a launch: every launch is sized from (rows, cols) and from whether d_out_idx
+ * was given.  Changing the contents of d_ranks between replays of a captured graph changes the result accordingly -- a batch of
+ * requests with mixed ranks is one call, and a decode loop that replays a graph follows a changed rank without a recapture (the
+ * host ranks of lsdsort_kth16_device and of the multi-rank entries are fixed in a captured graph).
+ * A rank outside its row cannot be refused by the host (as the offsets of lsdsort_segmented_device cannot): a row with
+ * d_ranks[r] >= cols has NOTHING stored for it in either output, the call still returns LSDSORT_OK, bit 4096 -- and only that bit --
+ * is set in the fault word (the first word of the workspace), lsdsort_check_device(d_workspace, stream) then reports
+ * LSDSORT_ERR_DEVICE_FAULT, and every other row of the call is correct.  A flag in a software word; nothing faults.  Bits 1024 (a
+ * row's digit counts do not reach the rank) and 2048 (no key is located) are lsdsort_kth16_device's and never expected.
+ * Kernels: lsdsort_kth16_device's three size classes (rows of up to 1024 keys one wavefront, up to 16384 one workgroup: one read of
+ * the row; longer ones by many workgroups: at most three reads plus one chunk, two reads without d_out_idx).  Stream-ordered, no host
+ * synchronisation, nothing allocated; capturable after lsdsort_prepare_device; phases are ordered by kernel boundaries.  The result
+ * does not depend on lsdsort_set_rank_method.
+ * Checks, in order, each before a device is touched: key_type outside lsdsort_key16_type (INVALID_ARG), rows or rows * cols above
+ * LSDSORT_MAX_KEYS (TOO_LARGE), rows == 0 or cols == 0 (OK, nothing launched), a NULL or odd d_keys or d_out_keys (INVALID_ARG), a
+ * NULL d_ranks or one that is not 4-byte aligned (INVALID_ARG), the workspace (WORKSPACE: NULL, not 256-byte aligned, or below
+ * lsdsort_kth16_perrow_workspace_bytes), the device (NO_DEVICE).
+ * lsdsort_kth16_perrow_workspace_bytes is a multiple of 256, monotonic in each argument, 0 where rows, cols or rows * cols is above
+ * LSDSORT_MAX_KEYS, and depends neither on the ranks nor on d_out_idx.  It is O(rows), never O(rows * cols): the control block, 16 B
+ * per row, and for rows above 16384 keys 8 KiB of counters per row and 4 B per 16384 keys. */
+LSDSORT_API size_t lsdsort_kth16_perrow_workspace_bytes(size_t rows, size_t cols);
+LSDSORT_API int lsdsort_kth16_perrow_device(const void* d_keys, size_t rows, size_t cols,
+                                            const uint32_t* d_ranks /* DEVICE, [rows], 0-based */,
+                                            int key_type /* lsdsort_key16_type */, int largest,
+                                            void* d_out_keys /* [rows] 16-bit, caller's type */, uint32_t* d_out_idx /* [rows] or NULL */,
+                                            void* d_workspace, size_t workspace_bytes, void* hip_stream);
+
+/* Top-k FILTER for 16-bit rows with a k of its own for every row, read from device memory (lsdradixsort_amd/csrc/kth16_rowk.hip):
+ * the last step of top-k sampling over [batch x vocab] float16 / bfloat16 logits, "keep the k_r best logits of request r, set the
+ * rest to -inf" -- logits.masked_fill_(logits < kth, -inf) with the k-th value selected and applied in one call.
+ * d_k is a DEVICE array of `rows` uint32 (4-byte aligned); let k_r = d_k[r].  If k_r == 0 or k_r >= cols the filter is OFF for the
+ * row: row r of d_out is row r of d_keys (the serving convention; an int32 -1 reads as 0xFFFFFFFF, which is also off).  Otherwise let
+ * T_r be item k_r - 1 of the row's STABLE sort in the requested order (largest != 0: the k_r-th largest): d_out[r][p] = d_keys[r][p]
+ * where the key is at least as good as T_r -- sortable(key) <= sortable(T_r) under the map of the 16-bit entries -- and fill_bits
+ * elsewhere.  EVERY duplicate of the threshold value is kept, so a row keeps at least k_r keys; kept keys are copied bit for bit.
+ * The comparison is the library's total order, not IEEE's `<`: -0.0 ranks below +0.0 (with largest, a threshold of +0.0 fills the
+ * -0.0s), and NaNs sort by sign at the two ends (+NaN above +inf, -NaN below -inf) instead of comparing false.
+ * d_out may be d_keys itself (in place); any other overlap is the caller's error and is not checked.  d_keys and d_out need 2-byte
+ * alignment only, their alignments may differ from each other, and cols may be odd.  There is no bad-argument flag: every value of
+ * d_k means something.  The host never reads d_k and no value in it sizes a launch: capturable after lsdsort_prepare_device, and d_k
+ * is read again on every replay.
+ * Kernels: rows of up to 1024 keys (one wavefront) and up to 16384 (one workgroup) are loaded into registers once, selected there,
+ * and the same registers are compared and stored: one read and one write of the row (4 B/key by byte accounting).  Longer rows: the
+ * values-only select of lsdsort_kth16_device (two reads), then one kernel reads every tile again, compares and stores: 8 B/key.  Rows
+ * whose filter is off skip the select; they are copied, or not touched at all in place.  Stores are 16-byte groups where a row of
+ * d_out has the 16-byte phase of its row of d_keys (always in place), key by key otherwise.
+ * Stream-ordered, no host synchronisation, nothing allocated; phases are ordered by kernel boundaries; every store stays within its
+ * row.  The fault word is the first word of the workspace: bit 1024 where a row's digit counts do not reach k_r (never expected;
+ * nothing is stored for the row).  The result does not depend on lsdsort_set_rank_method.
+ * Checks, in order, each before a device is touched: key_type outside lsdsort_key16_type (INVALID_ARG), rows or rows * cols above
+ * LSDSORT_MAX_KEYS (TOO_LARGE), rows == 0 or cols == 0 (OK, nothing launched), a NULL or odd d_keys or d_out, a NULL d_k or one that
+ * is not 4-byte aligned (INVALID_ARG), the workspace (WORKSPACE: NULL, not 256-byte aligned, or below
+ * lsdsort_topk16_filter_workspace_bytes), the device (NO_DEVICE).
+ * lsdsort_topk16_filter_workspace_bytes is a multiple of 256, monotonic in each argument, 0 above the limits, independent of d_k,
+ * and O(rows): the control block, 16 B per row, and for rows above 16384 keys 8 KiB of counters per row. */
+LSDSORT_API size_t lsdsort_topk16_filter_workspace_bytes(size_t rows, size_t cols);
+LSDSORT_API int lsdsort_topk16_filter_device(const void* d_keys, size_t rows, size_t cols, const uint32_t* d_k /* DEVICE, [rows] */,
+                                             int key_type /* lsdsort_key16_type */, int largest, uint16_t fill_bits,
+                                             void* d_out /* [rows][cols] 16-bit; may be d_keys itself */, void* d_workspace,
+                                             size_t workspace_bytes, void* hip_stream);
+
 /* After the stream has drained: LSDSORT_OK, or LSDSORT_ERR_DEVICE_FAULT if a kernel of the
  * last sort on this workspace gave up a bounded spin or refused destinations outside the output
  * (never expected; the output is then undefined).  Synchronises hip_stream.  With LSDSORT_REPROBE=1

@@ -18,6 +18,7 @@ from .api import (  # noqa: F401  (api.__all__, name for name)
     GPUKthMulti, kth_multi_workspace_bytes, quantile_rows, quantile_ranks,
     GPUKth16, kth16_workspace_bytes, kthvalue16_rows, median16_rows,
     GPUKth16Multi, kth16_multi_workspace_bytes, quantile16_rows,
+    GPUKth16PerRow, kth16_perrow_workspace_bytes, GPUTopK16Filter, topk16_filter_workspace_bytes, topk16_filter_rows,
     BuildHistograms, BuildOffsets, RankScatter, DigitHistograms,
     MSBPartition, SplitterPartition, ThresholdPartition, sharded_thresholds,
 )

@@ -28,6 +28,7 @@ __all__ = [
     "GPUKthMulti", "kth_multi_workspace_bytes", "quantile_rows", "quantile_ranks",
     "GPUKth16", "kth16_workspace_bytes", "kthvalue16_rows", "median16_rows",
     "GPUKth16Multi", "kth16_multi_workspace_bytes", "quantile16_rows",
+    "GPUKth16PerRow", "kth16_perrow_workspace_bytes", "GPUTopK16Filter", "topk16_filter_workspace_bytes", "topk16_filter_rows",
     "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
     "MSBPartition", "SplitterPartition", "ThresholdPartition", "sharded_thresholds",
 ]
@@ -891,6 +892,182 @@ def quantile16_rows(x, q, interpolation: str = "linear", stream=None):
         return GPUKth16Multi(flat, ranks, key_type=key_type, return_indices=False, stream=stream)[0].float()
 
     return _quantile_of(x, q, interpolation, stream, select)
+
+
+def _keys16(d_keys, key_type: str, verb: str = "selects"):
+    """The tensor and key-type checks of the 16-bit row entries -> (code, rows, cols)."""
+    torch = _torch()
+    _dev(d_keys, "d_keys", (torch.int16, torch.float16, torch.bfloat16), dims=(1, 2))
+    code = _key_type(key_type, KEY_TYPES_16)
+    fits = {torch.int16: ("uint16", "int16"), torch.float16: ("float16",), torch.bfloat16: ("bfloat16",)}[d_keys.dtype]
+    if key_type not in fits:
+        raise TypeError(f"a {str(d_keys.dtype).replace('torch.', '')} tensor {verb} with key_type " + " or ".join(f'"{k}"' for k in fits))
+    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
+    return code, rows, cols
+
+
+def _per_row_i32(t, name: str, rows: int):
+    """A per-row device array: a contiguous int32 CUDA tensor with one entry per row (its 32 bits are read as uint32)."""
+    torch = _torch()
+    _dev(t, name, (torch.int32,))
+    if t.numel() != rows:
+        raise ValueError(f"{name}: one entry per row ({rows}), got {t.numel()}")
+    return t
+
+
+def kth16_perrow_workspace_bytes(rows: int, cols: int) -> int:
+    """Bytes of device workspace ``GPUKth16PerRow`` needs for ``rows`` rows of ``cols`` 16-bit keys (whatever the ranks, with or
+    without indices)."""
+    return int(lib().lsdsort_kth16_perrow_workspace_bytes(rows, cols))
+
+
+def GPUKth16PerRow(d_keys, d_ranks, key_type: str = "int16", largest: bool = False, return_indices: bool = True, workspace=None,
+                   stream=None, check_fault: bool = False):
+    """``GPUKth16`` with a rank of its own for every row, read on the device (``lsdsort_kth16_perrow_device``): ``d_ranks`` is a
+    contiguous int32 CUDA tensor with one 0-based rank per row.  Returns ``(values, indices)`` as ``GPUKth16`` does, and row ``r``
+    holds exactly what ``GPUKth16(d_keys, d_ranks[r], ...)`` gives for it, values and int32 positions bit for bit.  The host never
+    reads ``d_ranks``: a captured graph follows its contents from replay to replay, and no launch depends on them.  A row whose rank
+    is outside ``0 .. cols - 1`` (as uint32) has nothing stored for it -- its slots of the returned tensors are uninitialised --, the
+    other rows are right, and ``check_fault=True`` raises ``LsdsortError`` (``LSDSORT_ERR_DEVICE_FAULT``: bit 4096 of the workspace's
+    first word)."""
+    torch = _torch()
+    code, rows, cols = _keys16(d_keys, key_type)
+    _per_row_i32(d_ranks, "d_ranks", rows)
+    shape = () if d_keys.dim() == 1 else (rows,)
+    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
+        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
+        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
+    if workspace is None:
+        nbytes = kth16_perrow_workspace_bytes(rows, cols)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_kth16_perrow_workspace_bytes", "too many keys or rows")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    check(lib().lsdsort_kth16_perrow_device(d_keys.data_ptr(), rows, cols, d_ranks.data_ptr(), code, int(bool(largest)),
+                                            values.data_ptr(), indices.data_ptr() if return_indices else None, workspace.data_ptr(),
+                                            workspace.numel(), _stream(stream)), "lsdsort_kth16_perrow_device")
+    if check_fault and rows and cols:
+        _check_fault(workspace, stream)
+    return values, indices
+
+
+def topk16_filter_workspace_bytes(rows: int, cols: int) -> int:
+    """Bytes of device workspace ``GPUTopK16Filter`` needs for ``rows`` rows of ``cols`` 16-bit keys (whatever the k's)."""
+    return int(lib().lsdsort_topk16_filter_workspace_bytes(rows, cols))
+
+
+def _worst_bits16(key_type: str, largest: bool) -> int:
+    """The 16-bit word that ranks last in the requested order among the values a caller fills with: -inf / +inf for the float
+    types (NaNs rank beyond them, but a filter fills with a number), the type's lowest / highest value for the integer ones."""
+    lowest, highest = {"uint16": (0x0000, 0xFFFF), "int16": (0x8000, 0x7FFF), "float16": (0xFC00, 0x7C00),
+                       "bfloat16": (0xFF80, 0x7F80)}[key_type]
+    return lowest if largest else highest
+
+
+def _fill_bits16(dtype, fill, largest: bool) -> int:
+    """The 16-bit word ``topk16_filter_rows`` fills with: ``fill`` as a value of ``dtype`` (``None``: the worst value in the
+    requested order)."""
+    torch = _torch()
+    key_type = str(dtype).replace("torch.", "")
+    if fill is None:
+        return _worst_bits16(key_type, largest)
+    if dtype == torch.int16:
+        if isinstance(fill, float) and not fill.is_integer():
+            raise ValueError("fill: an integer for an int16 tensor")
+        if not -(1 << 15) <= int(fill) < (1 << 15):
+            raise ValueError("fill: within the range of int16")
+        return int(fill) & 0xFFFF
+    return int(torch.tensor(float(fill), dtype=dtype).view(torch.int16).item()) & 0xFFFF
+
+
+def _k_per_row(k, rows: int, device):
+    """``k`` of ``topk16_filter_rows`` as the int32 vector the library reads, one entry per row, on ``device``: an int (every row),
+    a sequence of ints, or an int32 / int64 tensor.  Values outside int32 are clamped into it first -- both ends mean "filter off"
+    (a negative entry reads as a uint32 above every row length).  An int32 tensor on ``device`` is used as it is."""
+    torch = _torch()
+    lo, hi = -(1 << 31), (1 << 31) - 1
+    if isinstance(k, torch.Tensor):
+        if k.dtype not in (torch.int32, torch.int64):
+            raise TypeError("k: an int, a sequence of ints, or an int32 / int64 tensor")
+        if k.numel() != rows:
+            raise ValueError(f"k: one entry per row ({rows}), got {k.numel()}")
+        if k.dtype == torch.int64:
+            k = k.clamp(lo, hi).to(torch.int32)
+        return k.to(device).contiguous().view(-1)
+    if isinstance(k, (bool, str, bytes)):
+        raise TypeError("k: an int, a sequence of ints, or an int32 / int64 tensor")
+    if isinstance(k, int):
+        return torch.full((rows,), min(max(k, lo), hi), dtype=torch.int32, device=device)
+    try:
+        values = [min(max(int(v), lo), hi) for v in k]
+    except TypeError:
+        raise TypeError("k: an int, a sequence of ints, or an int32 / int64 tensor") from None
+    if len(values) != rows:
+        raise ValueError(f"k: one entry per row ({rows}), got {len(values)}")
+    return torch.tensor(values, dtype=torch.int32).to(device)
+
+
+def GPUTopK16Filter(d_keys, d_k, key_type: str = "int16", largest: bool = True, fill: int | None = None, out=None, workspace=None,
+                    stream=None, check_fault: bool = False):
+    """The top-k filter of every row with a k of its own per row, read on the device (``lsdsort_topk16_filter_device``):
+    ``d_keys`` as for ``GPUTopK16``, ``d_k`` a contiguous int32 CUDA tensor with one entry per row.  Row ``r`` of the result is row
+    ``r`` of ``d_keys`` where ``d_k[r]`` (as uint32) is 0 or at least the row length -- the filter is off, -1 included.  Otherwise
+    the keys at least as good as the ``d_k[r]``-th best of the row (``largest``: the largest) are kept bit for bit, every duplicate
+    of that value included, and the others become the 16-bit word ``fill`` (an int in 0 .. 0xFFFF; ``None``: -inf / +inf for the
+    float types, the type's lowest / highest value for the integer ones, by ``largest``).  The order is the library's total order:
+    -0.0 below +0.0, NaNs by sign at the two ends.  Returns the result: ``out`` where one is given (``out=d_keys`` runs in place),
+    else a new tensor.  The host never reads ``d_k``: a captured graph follows its contents.  Stream-ordered; short rows are read
+    once and written once, rows above 16384 keys read three times and written once."""
+    torch = _torch()
+    code, rows, cols = _keys16(d_keys, key_type, "is filtered")
+    _per_row_i32(d_k, "d_k", rows)
+    if fill is None:
+        fill = _worst_bits16(key_type, bool(largest))
+    if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 0xFFFF:
+        raise ValueError("fill: a 16-bit word, an int within 0 .. 0xFFFF")
+    if out is not None:
+        _dev(out, "out", (d_keys.dtype,), dims=(d_keys.dim(),))
+        if out.shape != d_keys.shape:
+            raise ValueError("out: the shape of d_keys")
+    with _on_stream(stream):   # the output, like a temporary workspace, belongs to the stream the kernels run on
+        result = out if out is not None else torch.empty_like(d_keys)
+    if workspace is None:
+        nbytes = topk16_filter_workspace_bytes(rows, cols)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_topk16_filter_workspace_bytes", "too many keys or rows")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    check(lib().lsdsort_topk16_filter_device(d_keys.data_ptr(), rows, cols, d_k.data_ptr(), code, int(bool(largest)), fill,
+                                             result.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(stream)),
+          "lsdsort_topk16_filter_device")
+    if check_fault and rows and cols:
+        _check_fault(workspace, stream)
+    return result
+
+
+def topk16_filter_rows(x, k, largest: bool = True, fill=None, inplace: bool = False, stream=None):
+    """The top-k filter of a sampling step for a float16 / bfloat16 / int16 CUDA tensor of one or more dimensions: per row of the
+    last dimension, ``thr = torch.topk(row, k_r, largest=largest).values[-1]`` and ``row.masked_fill(row < thr, fill)`` (``>`` for
+    smallest), without the top-k, its gather and the mask: every key at least as good as the ``k_r``-th best stays, ties of it
+    included.  ``k`` is an int for every row, or one entry per row as a sequence or an int32 / int64 tensor; ``k_r <= 0`` or
+    ``k_r >= `` the row length leaves the row as it is.  A host value becomes a device tensor here; an int32 CUDA tensor is used as
+    it is, so a captured caller pays no conversion and may change its contents between replays.  ``fill``: a value of ``x``'s dtype;
+    ``None`` is -inf for ``largest`` and +inf for smallest, on int16 the lowest / highest value.  ``inplace`` filters ``x`` itself
+    (contiguous) and returns it.  The order is the library's total order, not torch's: -0.0 ranks below +0.0 and NaNs sort by sign
+    at the two ends."""
+    torch = _torch()
+    _dev(x, "x", (torch.int16, torch.float16, torch.bfloat16), contiguous=bool(inplace))
+    if x.dim() == 0:
+        raise TypeError("x: at least one dimension")
+    cols = x.shape[-1]
+    rows = int(np.prod(x.shape[:-1], dtype=np.int64))
+    bits = _fill_bits16(x.dtype, fill, bool(largest))
+    with _on_stream(stream):
+        d_k = _k_per_row(k, rows, x.device)
+        if rows == 0 or cols == 0:
+            return x if inplace else x.clone()
+        flat = (x if inplace else x.contiguous()).view(-1, cols)
+        out = GPUTopK16Filter(flat, d_k, key_type=str(x.dtype).replace("torch.", ""), largest=largest, fill=bits,
+                              out=flat if inplace else None, stream=stream)
+        return x if inplace else out.view(x.shape)
 
 
 def rows16_workspace_bytes(rows: int, cols: int) -> int:

@@ -1,0 +1,632 @@
+// kth16_rowk.hip -- the 16-bit row selects with a k of their own for EVERY row, read from device memory:
+//   lsdsort_kth16_perrow_device    kth16.hip's contract with row r's rank in d_ranks[r]
+//   lsdsort_topk16_filter_device   the top-k filter of a sampling step: row r keeps the keys at least as good as its k_r-th best
+//                                  (every duplicate of that value included), the others become `fill_bits`
+// A batch of requests with mixed top_k is one call, and a captured graph follows a changed k: the values are read by the kernels,
+// never by the host, and no launch is sized from them.
+//
+// No counterpart in the reference (it sorts one whole array of uint32, LSDRadixSort.cu:839-910).  The select is radix_select.hpp's
+// with Levels16, in kth16.hip's three size classes:
+//   cols <= kWaveSegCap (1024)      one wavefront per row, eight rows per workgroup; `need` is loaded once per row, uniformly
+//   cols <= kLocalSortCap (16384)   one workgroup of 16 wavefronts per row: the same
+//   longer                          many workgroups per row.  This unit's clear kernel writes the row states from the device array
+//                                   (select_long takes one `need` for all rows), then the two levels run.  Per-row rank: count,
+//                                   pick and locate, or without an index buffer both levels and the value kernel, as in kth16.hip.
+//                                   Filter: both levels (the state then holds the whole threshold), then ONE apply kernel over the
+//                                   same chunks reads a tile, compares and stores.
+// The filter's short kernels compare and store the registers the select ran on: one read and one write of the row (4 B/key by byte
+// accounting; long rows 2 reads + 1 read + 1 write = 8 B/key).  A kept key is stored as from_sortable16(to_sortable16(key)), which
+// is the key bit for bit (the map is a bijection of the 16-bit words).  A row is stored by 16-byte groups where source and
+// destination rows share their 16-byte phase (in place always), otherwise key by key.  In place every position is read and written by
+// the same lane, a row's select has ended before its first store (registers in the short tiers, a kernel boundary in the long one).
+//
+// A rank outside its row cannot be refused by the host.  Such a row of the per-row entry stores nothing, raises kRowkFaultRank and
+// no other bit, and leaves every other row as it is: short tiers skip the row; the clear kernel gives a long one a done state
+// (w = kBadRow) that hist, scan, count and locate pass over, and the kernel that would have reported "nothing located" for it
+// (pick, or the value kernel) reports kRowkFaultRank instead.  The filter has no such rank: k_r == 0 or k_r >= cols is "filter
+// off" (state w = kOffRow), the row is copied, or left alone in place.
+//
+// load_tile, load_head and locate_tile are this unit's copy of kth16.hip's, count / pick / locate / value follow kth16.hip's line by
+// line (one header once an ISA diff proves the move).  Every launch is sized from (rows, cols) and from whether
+// an index buffer was given; phases are ordered by kernel boundaries; every store into the outputs is guarded by row < rows and
+// stays within the row.  Nothing here ranks with the returning add: the result does not depend on lsdsort_set_rank_method.
+#define LSDSORT_BUILD 1
+#include "../../include/lsdsort.h"
+
+#include "keys16_map.hpp"
+#include "lsd_device.hpp"
+#include "lsd_host.hpp"
+#include "radix_select.hpp"
+
+namespace lsd {
+namespace {
+
+constexpr uint32_t kRowkFaultCount = 1024u;    // fault word: the digit counts of a row do not reach the rank (never expected)
+constexpr uint32_t kRowkFaultLocate = 2048u;   // fault word: no key was located for a row (never expected; nothing stored)
+constexpr uint32_t kRowkFaultRank = 4096u;     // fault word: d_ranks[r] >= cols for some row (the caller's error; nothing stored for it)
+constexpr uint32_t kNoKey = 0xFFFFFFFFu;       // a sortable value is below 65536
+constexpr uint32_t kHeadBit = 1u << kRegs;     // match mask: the head register
+constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
+constexpr uint32_t kBadRow = 2u, kOffRow = 3u; // row state w: done from the start (1: the select stopped or fell short)
+using Row16 = Row<uint16_t>;   // a lane holds two 16-byte groups of eight keys of its wave's tile
+
+// the values-only select of long rows and the filter's: both levels always run, so that the prefix is the whole value
+struct StopNever16 {
+    static __device__ __forceinline__ bool stops(uint32_t, uint32_t) { return false; }
+};
+
+// The wave's tile from body position q0 on, valid below `end`: a whole group by one 16-byte load, the others key by key.
+__device__ __forceinline__ void load_tile(const Row16& r, uint32_t q0, uint32_t end, uint32_t lane, const Key16Map& m, uint32_t (&t)[kRegs])
+{
+#pragma unroll
+    for (int j = 0; j < kRegs / 8; j++) {
+        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
+        if (q < end && end - q >= kGroupKeys) {
+            const uint4 v = *reinterpret_cast<const uint4*>(r.keys + r.head + q);
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                t[8 * j + 2 * i] = to_sortable16(w[i] & 0xFFFFu, m);
+                t[8 * j + 2 * i + 1] = to_sortable16(w[i] >> 16, m);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                t[8 * j + e] = kNoKey;
+                if (q + (uint32_t)e < end) t[8 * j + e] = to_sortable16(r.keys[r.head + q + (uint32_t)e], m);
+            }
+        }
+    }
+}
+// head key `lane` of the row, for the one wave that owns the head
+__device__ __forceinline__ uint32_t load_head(const Row16& r, uint32_t lane, const Key16Map& m)
+{
+    return lane < r.head ? to_sortable16(r.keys[lane], m) : kNoKey;
+}
+
+struct Outputs {
+    uint16_t* keys;       // [rows], the caller's 16-bit words
+    uint32_t* idx;        // [rows] positions, may be null
+    uint32_t rows;
+    uint32_t* fault;
+};
+
+// Locate within one tile held in registers (load_tile at q0; h: the head keys in front of it, kNoKey where there is none).  `base`:
+// the keys under the prefix before this tile in the row; it moves on past the tile.  If the `need`-th (1-based) such key of the row
+// lies in this tile, the lane that holds it stores it.  Returns whether it did (uniform over the group).  s_wc: WAVES words.
+template <int WAVES>
+__device__ __forceinline__ bool locate_tile(const uint32_t (&t)[kRegs], uint32_t h, uint32_t q0, const Row16& r, uint32_t prefix,
+                                            uint32_t shift, uint32_t need, uint32_t& base, volatile lds_u32* s_wc, uint32_t wave,
+                                            uint32_t lane, uint32_t row, const Outputs& o, const Key16Map& m)
+{
+    uint32_t em = (h >> shift) == prefix ? kHeadBit : 0u;   // the keys under the prefix (kNoKey never is)
+#pragma unroll
+    for (int i = 0; i < kRegs; i++) em |= (t[i] >> shift) == prefix ? 1u << i : 0u;
+    const uint32_t mine = wave_sum((uint32_t)__builtin_popcount(em));
+    uint32_t before = base, all = mine;
+    if (WAVES > 1) {
+        if (lane == 0u) s_wc[wave] = mine;
+        __syncthreads();
+        all = 0u;
+        for (uint32_t w = 0; w < (uint32_t)WAVES; w++) {
+            const uint32_t c = s_wc[w];
+            if (w < wave) before += c;
+            all += c;
+        }
+        __syncthreads();   // the next tile writes s_wc again
+    }
+    const bool here = base < need && need - base <= all;   // uniform
+    if (here) {
+        auto store = [&](uint32_t key, uint32_t pos) {
+            if (row < o.rows) {
+                o.keys[row] = (uint16_t)from_sortable16(key, m);
+                if (o.idx) o.idx[row] = pos;
+            }
+        };
+        // position order: the head keys by lane, then group j of lane 0, 1, .. 63, j = 0, 1
+        const uint32_t ch = em >> kRegs;
+        const uint32_t hi = wave_inclusive_scan(ch);
+        if (ch != 0u && before + hi == need) store(h, lane);
+        before += (uint32_t)__builtin_amdgcn_readlane((int)hi, 63);
+#pragma unroll
+        for (int j = 0; j < kRegs / 8; j++) {
+            const uint32_t g = (em >> (8 * j)) & 0xFFu, c = (uint32_t)__builtin_popcount(g);
+            const uint32_t incl = wave_inclusive_scan(c), lo = before + incl - c;
+            if (lo < need && need - lo <= c) {
+                uint32_t left = need - lo;   // 1 .. c: which of this group's matching keys
+                const uint32_t pos = r.head + q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    if (((g >> e) & 1u) != 0u && --left == 0u) store(t[8 * j + e], pos + (uint32_t)e);
+                }
+            }
+            before += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        }
+    }
+    base += all;
+    return here;
+}
+
+// The filter's store of one tile held in registers (load_tile at q0, valid below `end`) into the destination row `orow`: a key is
+// kept where (key >> shift) <= prefix and becomes `fill` elsewhere.  `vec`: the destination row has the source row's 16-byte phase,
+// so a whole group is one 16-byte store at the address the load had; otherwise, and behind the last whole group, key by key.
+// Every store is below `end`, that is inside the row.
+__device__ __forceinline__ void store_tile(uint16_t* orow, bool vec, const Row16& r, uint32_t q0, uint32_t end, uint32_t lane,
+                                           const uint32_t (&t)[kRegs], uint32_t prefix, uint32_t shift, uint32_t fill, const Key16Map& m)
+{
+#pragma unroll
+    for (int j = 0; j < kRegs / 8; j++) {
+        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
+        if (q >= end) continue;
+        uint32_t w[8];
+#pragma unroll
+        for (int e = 0; e < 8; e++) w[e] = (t[8 * j + e] >> shift) <= prefix ? from_sortable16(t[8 * j + e], m) & 0xFFFFu : fill;
+        if (vec && end - q >= kGroupKeys) {
+            *reinterpret_cast<uint4*>(orow + r.head + q) = make_uint4(w[0] | (w[1] << 16), w[2] | (w[3] << 16), w[4] | (w[5] << 16), w[6] | (w[7] << 16));
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; e++)
+                if (q + (uint32_t)e < end) orow[r.head + q + (uint32_t)e] = (uint16_t)w[e];
+        }
+    }
+}
+// the head keys of the row, by the one wave that owns them
+__device__ __forceinline__ void store_head(uint16_t* orow, const Row16& r, uint32_t lane, uint32_t h, uint32_t prefix, uint32_t shift,
+                                           uint32_t fill, const Key16Map& m)
+{
+    if (lane < r.head) orow[lane] = (uint16_t)((h >> shift) <= prefix ? from_sortable16(h, m) : fill);
+}
+__device__ __forceinline__ bool same_phase(const void* a, const void* b) { return (((uintptr_t)a ^ (uintptr_t)b) & 15u) == 0u; }
+
+// ---- short rows: one wavefront (WAVES = 1, eight rows per workgroup) or one workgroup (WAVES = 16) per row ----------------------
+struct ShortParams {
+    const uint16_t* keys;
+    const uint32_t* ranks;   // [rows], device: the 0-based rank (per-row entry) or k (filter) of every row
+    uint32_t cols;
+    Key16Map map;
+    Outputs out;             // the filter: rows and fault only
+    uint16_t* dst;           // the filter: [rows][cols], may be `keys`
+    uint32_t fill;
+};
+
+template <int WAVES>
+__global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) kth16r_short_kernel(const ShortParams p)
+{
+    constexpr int kGroups = WAVES == 1 ? 8 : 1;      // rows in flight per workgroup
+    constexpr int kSlice = 256 + 8 + WAVES;          // per row: digit counters, the found bin, per-wave counts
+    __shared__ uint32_t smem[kGroups * kSlice];
+    const uint32_t lane = threadIdx.x & 63u, wave_of_block = threadIdx.x >> 6;
+    const uint32_t group = WAVES == 1 ? wave_of_block : 0u, wave = WAVES == 1 ? 0u : wave_of_block;
+    volatile lds_u32* const s_cnt = (volatile lds_u32*)((lds_u32*)smem + group * kSlice);
+    volatile lds_u32* const s_found = s_cnt + 256;
+    volatile lds_u32* const s_wc = s_cnt + 264;
+    // `row` is the same for every thread of a group (a wave, or the whole workgroup): its barriers are reached together
+    for (uint32_t row = blockIdx.x * kGroups + group; row < p.out.rows; row += gridDim.x * kGroups) {
+        const uint32_t rank_load = p.ranks[row];   // issued in front of the row's loads and used behind them: no wait of its own
+        const Row16 r = row_of(p.keys, row, p.cols);
+        const uint32_t q0 = wave * kWaveTile;
+        uint32_t t[kRegs];
+        load_tile(r, q0, r.body, lane, p.map, t);
+        const uint32_t h = wave == 0u ? load_head(r, lane, p.map) : kNoKey;
+        const uint32_t rank = (uint32_t)__builtin_amdgcn_readfirstlane((int)rank_load);   // one value per row
+        if (rank >= p.cols) {   // (uniform) the caller's error: nothing is stored for the row, and no other bit is raised
+            if (wave == 0u && lane == 0u) atomicOr(p.out.fault, kRowkFaultRank);
+            continue;
+        }
+        // round 0: every key there is; round 1: those whose top byte is the prefix (kNoKey never is)
+        auto count = [&](int round, uint32_t, uint32_t prefix, auto add) __attribute__((always_inline)) {
+            auto one = [&](uint32_t key) __attribute__((always_inline)) {
+                if (round == 0 ? key != kNoKey : (key >> 8) == prefix) add(key);
+            };
+#pragma unroll
+            for (int i = 0; i < kRegs; i++) one(t[i]);
+            one(h);
+        };
+        const Selected sel = select_short<WAVES, 2, StopKth>(s_cnt, s_found, wave, lane, rank + 1u, p.out.fault, kRowkFaultCount, count);
+        uint32_t base = 0u;
+        const bool found = locate_tile<WAVES>(t, h, q0, r, sel.prefix, sel.shift, sel.need, base, s_wc, wave, lane, row, p.out, p.map);
+        if (!found && sel.need != 0u && wave == 0u && lane == 0u) atomicOr(p.out.fault, kRowkFaultLocate);
+        group_sync<WAVES>();
+    }
+}
+
+// The filter: the select at need = k_r, then the same registers are compared and stored.  Where the select stopped with one key
+// under a prefix of fewer than 16 bits, that key is the threshold and (key >> shift) <= prefix keeps exactly the keys up to it.
+template <int WAVES>
+__global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) topk16f_short_kernel(const ShortParams p)
+{
+    constexpr int kGroups = WAVES == 1 ? 8 : 1;
+    constexpr int kSlice = 256 + 8;                  // per row: digit counters, the found bin
+    __shared__ uint32_t smem[kGroups * kSlice];
+    const uint32_t lane = threadIdx.x & 63u, wave_of_block = threadIdx.x >> 6;
+    const uint32_t group = WAVES == 1 ? wave_of_block : 0u, wave = WAVES == 1 ? 0u : wave_of_block;
+    volatile lds_u32* const s_cnt = (volatile lds_u32*)((lds_u32*)smem + group * kSlice);
+    volatile lds_u32* const s_found = s_cnt + 256;
+    const bool in_place = p.dst == p.keys;
+    for (uint32_t row = blockIdx.x * kGroups + group; row < p.out.rows; row += gridDim.x * kGroups) {
+        const uint32_t k = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.ranks[row]);   // one value per row
+        const bool off = k == 0u || k >= p.cols;   // (uniform) the filter is off: the row is copied
+        if (off && in_place) continue;
+        const Row16 r = row_of(p.keys, row, p.cols);
+        const uint32_t q0 = wave * kWaveTile;
+        uint32_t t[kRegs];
+        load_tile(r, q0, r.body, lane, p.map, t);
+        const uint32_t h = wave == 0u ? load_head(r, lane, p.map) : kNoKey;
+        uint32_t prefix = 0xFFFFu, shift = 0u;   // every key there is
+        bool selected = true;
+        if (!off) {
+            auto count = [&](int round, uint32_t, uint32_t pre, auto add) __attribute__((always_inline)) {
+                auto one = [&](uint32_t key) __attribute__((always_inline)) {
+                    if (round == 0 ? key != kNoKey : (key >> 8) == pre) add(key);
+                };
+#pragma unroll
+                for (int i = 0; i < kRegs; i++) one(t[i]);
+                one(h);
+            };
+            const Selected sel = select_short<WAVES, 2, StopKth>(s_cnt, s_found, wave, lane, k, p.out.fault, kRowkFaultCount, count);
+            prefix = sel.prefix;
+            shift = sel.shift;
+            selected = sel.need != 0u;   // else the counts fell short (never; the fault bit is set): nothing is stored
+        }
+        if (selected) {
+            uint16_t* const orow = p.dst + (size_t)row * p.cols;
+            store_tile(orow, same_phase(orow, r.keys), r, q0, r.body, lane, t, prefix, shift, p.fill, p.map);
+            if (wave == 0u) store_head(orow, r, lane, h, prefix, shift, p.fill, p.map);
+        }
+        group_sync<WAVES>();
+    }
+}
+
+// ---- long rows ------------------------------------------------------------------------------------------------------------------
+// Row state in the workspace (uint4).  During the select: x prefix, y shift (16: no level has run), z need, w done (1: the select
+// stopped; kBadRow / kOffRow: from the start).  After the pick: x prefix, y shift, z which of the chunk's keys under the prefix is
+// the wanted one (1-based; 0: none), w the chunk that holds it.
+struct LongParams {
+    const uint16_t* keys;
+    uint32_t cols;
+    uint32_t chunk, chunks;       // body positions per chunk (a multiple of kLongTile), chunks per row
+    uint32_t chunk_cap;           // row stride of `counts`
+    uint4* state;
+    uint32_t* hist;               // [rows][kBins], zero on entry to every level
+    uint32_t* counts;             // [rows][chunk_cap]: keys under the prefix, per chunk (per-row entry with indices)
+    Key16Map map;
+    Outputs out;
+    uint16_t* dst;                // the filter: [rows][cols], may be `keys`
+    uint32_t fill;
+};
+
+// Control block, counters and row states of a call, the states from the device array.  Per-row entry: need = rank + 1, a rank
+// outside the row gives a done state.  FILTER: need = k, k == 0 or k >= cols gives the "off" state.  With state == nullptr (short
+// rows) it is the control block alone.
+template <bool FILTER>
+__global__ void __launch_bounds__(256) kth16r_clear_kernel(uint32_t* ctl, uint32_t* hist, uint32_t hist_words, uint4* state, uint32_t rows,
+                                                           const uint32_t* ranks, uint32_t cols)
+{
+    const uint32_t at = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
+    if (at < (uint32_t)(kCtlBytes / 4)) ctl[at] = 0u;
+    for (uint32_t q = at; q < hist_words; q += step) hist[q] = 0u;
+    if (!state) return;
+    for (uint32_t r = at; r < rows; r += step) {
+        const uint32_t v = ranks[r];
+        if (FILTER) state[r] = (v == 0u || v >= cols) ? make_uint4(0u, Levels16::kNoLevel, 0u, kOffRow) : make_uint4(0u, Levels16::kNoLevel, v, 0u);
+        else state[r] = v >= cols ? make_uint4(0u, Levels16::kNoLevel, 0u, kBadRow) : make_uint4(0u, Levels16::kNoLevel, v + 1u, 0u);
+    }
+}
+
+// One chunk of one row per workgroup: the digit of every key under the row's prefix, counted in LDS.  LEVEL 0: the top 11 bits
+// of every key; LEVEL 1: the low 5 bits of the keys whose top 11 are the prefix.  A done row returns at once.
+template <int LEVEL>
+__global__ void __launch_bounds__(kLongThreads) kth16r_hist_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_hist[kBins];
+    hist_level(p, s_hist, [&](uint32_t row, uint32_t c, const uint4& st, uint32_t lane, uint32_t wave) __attribute__((always_inline)) {
+        const Row16 r = row_of(p.keys, row, p.cols);
+        const ChunkRange g = chunk_of(r, p.chunk, c);
+        auto count = [&](uint32_t key) __attribute__((always_inline)) {
+            const bool match = LEVEL == 0 ? key != kNoKey : (key >> Levels16::shift(0)) == st.x;
+            count_digit(s_hist, match, (key >> Levels16::shift(LEVEL)) & ((1u << Levels16::bits(LEVEL)) - 1u), lane);
+        };
+        if (c == 0u && wave == 0u) count(load_head(r, lane, p.map));   // uniform
+        for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
+            uint32_t t[kRegs];
+            load_tile(r, tile + wave * kWaveTile, g.hi, lane, p.map, t);
+#pragma unroll
+            for (int i = 0; i < kRegs; i++) count(t[i]);
+        }
+    });
+}
+
+// One workgroup per row: walk the bins from the best end to the one that holds the wanted key; the counters go back to zero.
+template <int LEVEL, class Stop>
+__global__ void __launch_bounds__(256) kth16r_scan_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_part[4];
+    __shared__ uint32_t s_found[3];
+    scan_level<Levels16, LEVEL, Stop>(p, s_part, s_found, kRowkFaultCount);
+}
+
+// the keys under the prefix, per chunk
+__global__ void __launch_bounds__(kLongThreads) kth16r_count_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_part[kLongWaves];
+    const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const Row16 r = row_of(p.keys, row, p.cols);
+    const ChunkRange g = chunk_of(r, p.chunk, c);
+    uint32_t ne = 0u;
+    if (st.y < Levels16::kNoLevel && st.z != 0u) {   // (uniform) else: a row with a rank outside it, or one whose counts fell short
+        if (c == 0u && wave == 0u) ne += (load_head(r, lane, p.map) >> st.y) == st.x ? 1u : 0u;   // uniform
+        for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
+            uint32_t t[kRegs];
+            load_tile(r, tile + wave * kWaveTile, g.hi, lane, p.map, t);
+#pragma unroll
+            for (int i = 0; i < kRegs; i++) ne += (t[i] >> st.y) == st.x ? 1u : 0u;
+        }
+    }
+    ne = wave_sum(ne);
+    if (lane == 0u) s_part[wave] = ne;
+    __syncthreads();
+    if (tid == 0u) {
+        uint32_t e = 0u;
+        for (uint32_t w = 0; w < kLongWaves; w++) e += s_part[w];
+        p.counts[(size_t)row * p.chunk_cap + c] = e;
+    }
+}
+
+// One workgroup per row: the chunk that holds the `need`-th key under the prefix, and which of that chunk's such keys it is.  A row
+// whose rank lies outside it is reported here, by its own bit, and has nothing picked.
+__global__ void __launch_bounds__(256) kth16r_pick_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_part[4];
+    __shared__ uint32_t s_found[2];
+    const uint32_t row = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    if (st.y == Levels16::kNoLevel && st.w == kBadRow) {   // uniform
+        if (tid == 0u) {
+            atomicOr(p.out.fault, kRowkFaultRank);
+            p.state[row] = make_uint4(0u, 0u, 0u, kNoChunk);
+        }
+        return;
+    }
+    const uint32_t* const counts = p.counts + (size_t)row * p.chunk_cap;
+    constexpr uint32_t E = kMaxChunks / 256u;
+    uint32_t c[E], sum = 0u;
+#pragma unroll
+    for (uint32_t e = 0; e < E; e++) {
+        c[e] = tid * E + e < p.chunks ? counts[tid * E + e] : 0u;
+        sum += c[e];
+    }
+    if (tid == 0u) s_found[0] = kNoChunk;
+    uint32_t run = group_exclusive_scan<4>(sum, lane, wave, s_part);
+    const uint32_t need = st.y < Levels16::kNoLevel ? st.z : 0u;
+#pragma unroll
+    for (uint32_t e = 0; e < E; e++) {
+        if (run < need && need - run <= c[e]) {   // at most one chunk of the row
+            s_found[0] = tid * E + e;
+            s_found[1] = need - run;
+        }
+        run += c[e];
+    }
+    __syncthreads();
+    if (tid != 0u) return;
+    const uint32_t chunk = s_found[0];
+    if (chunk == kNoChunk) {   // the keys under the prefix are fewer than `need`: nothing is located
+        atomicOr(p.out.fault, kRowkFaultLocate);
+        p.state[row] = make_uint4(0u, 0u, 0u, kNoChunk);
+        return;
+    }
+    p.state[row] = make_uint4(st.x, st.y, s_found[1], chunk);
+}
+
+// One workgroup per row reads the picked chunk, and only up to the tile that holds the key.
+__global__ void __launch_bounds__(kLongThreads) kth16r_locate_kernel(const LongParams p)
+{
+    __shared__ uint32_t s_wc_raw[kLongWaves];
+    const uint32_t row = blockIdx.x;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    if (st.z == 0u || st.w >= p.chunks) return;   // (uniform) nothing was picked: the pick has set the row's fault bit
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const Row16 r = row_of(p.keys, row, p.cols);
+    const ChunkRange g = chunk_of(r, p.chunk, st.w);
+    volatile lds_u32* const s_wc = (volatile lds_u32*)(lds_u32*)s_wc_raw;
+    uint32_t base = 0u;
+    bool found = false;
+    // chunk 0 has at least one tile (a long row's body is longer than its head), and its first tile carries the head
+    for (uint32_t tile = g.lo; tile < g.hi && !found; tile += kLongTile) {   // uniform
+        const uint32_t q0 = tile + wave * kWaveTile;
+        uint32_t t[kRegs];
+        load_tile(r, q0, g.hi, lane, p.map, t);
+        const uint32_t h = (st.w == 0u && tile == g.lo && wave == 0u) ? load_head(r, lane, p.map) : kNoKey;   // uniform
+        found = locate_tile<(int)kLongWaves>(t, h, q0, r, st.x, st.y, st.z, base, s_wc, wave, lane, row, p.out, p.map);
+    }
+    if (!found && tid == 0u) atomicOr(p.out.fault, kRowkFaultLocate);
+}
+
+// Values only: after both levels the prefix is the row's whole sortable value (shift 0, need not 0).  A row whose rank lies outside
+// it is reported by its own bit; anything else is a row whose counts fell short (its fault bit is set) -- never.  Nothing is stored
+// for either.
+__global__ void __launch_bounds__(256) kth16r_value_kernel(const LongParams p)
+{
+    for (uint32_t row = blockIdx.x * blockDim.x + threadIdx.x; row < p.out.rows; row += gridDim.x * blockDim.x) {
+        const uint4 st = p.state[row];
+        if (st.y == 0u && st.z != 0u) p.out.keys[row] = (uint16_t)from_sortable16(st.x & 0xFFFFu, p.map);
+        else atomicOr(p.out.fault, (st.y == Levels16::kNoLevel && st.w == kBadRow) ? kRowkFaultRank : kRowkFaultLocate);
+    }
+}
+
+// The filter over one chunk of one row per workgroup, the chunks of the select: after both levels the state holds the row's whole
+// threshold (shift 0, need not 0); an "off" row is copied, or left alone in place.  Anything else is a row whose counts fell short
+// (its fault bit is set) -- never: nothing is stored for it.
+__global__ void __launch_bounds__(kLongThreads) topk16f_apply_kernel(const LongParams p)
+{
+    const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    const bool off = st.y == Levels16::kNoLevel && st.w == kOffRow;   // uniform
+    if (off ? p.dst == p.keys : !(st.y == 0u && st.z != 0u)) return;
+    const uint32_t prefix = off ? 0xFFFFu : (st.x & 0xFFFFu);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const Row16 r = row_of(p.keys, row, p.cols);
+    const ChunkRange g = chunk_of(r, p.chunk, c);
+    uint16_t* const orow = p.dst + (size_t)row * p.cols;
+    const bool vec = same_phase(orow, r.keys);
+    if (c == 0u && wave == 0u) store_head(orow, r, lane, load_head(r, lane, p.map), prefix, 0u, p.fill, p.map);   // uniform
+    for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
+        const uint32_t q0 = tile + wave * kWaveTile;
+        uint32_t t[kRegs];
+        load_tile(r, q0, g.hi, lane, p.map, t);
+        store_tile(orow, vec, r, q0, g.hi, lane, t, prefix, 0u, p.fill, p.map);
+    }
+}
+
+// Workspace of the per-row entry, kth16.hip's: control | row states (16 B per row) | counters [rows][2048] | chunk counts (4 B per
+// chunk) -- the last two for rows above kLocalSortCap keys only.  The filter's has no chunk counts.
+using RowkLayout = SelectLayout;
+RowkLayout perrow_layout(size_t rows, size_t cols) { return select_layout(rows, cols, false, 4); }
+RowkLayout filter_layout(size_t rows, size_t cols) { return select_layout(rows, cols, false, 0); }
+
+// The long rows' select with the needs from the device array: radix_select.hpp's select_long with this unit's clear kernel.
+template <bool FILTER, class Stop0>
+int select_long_rowk(LongParams& lp, const uint16_t* keys, size_t rows, size_t cols, const uint32_t* ranks, char* ws, const RowkLayout& L,
+                     hipStream_t stream)
+{
+    const Chunks ch = chunks_for(rows, cols);
+    lp.keys = keys;
+    lp.cols = (uint32_t)cols;
+    lp.chunk = ch.chunk;
+    lp.chunks = ch.per_row;
+    lp.chunk_cap = (uint32_t)chunk_cap_for(cols);
+    lp.state = reinterpret_cast<uint4*>(ws + L.state);
+    lp.hist = reinterpret_cast<uint32_t*>(ws + L.hist);
+    lp.counts = reinterpret_cast<uint32_t*>(ws + L.counts);
+    if (lp.chunks > lp.chunk_cap) return LSDSORT_ERR_INVALID_ARG;   // never: chunks are at least kMinChunk keys
+    const uint32_t grid = (uint32_t)(rows * lp.chunks), row_grid = (uint32_t)rows;
+    hipLaunchKernelGGL(kth16r_clear_kernel<FILTER>, dim3(grid_for(rows * kBins, 1024, 4096)), dim3(256), 0, stream,
+                       reinterpret_cast<uint32_t*>(ws), lp.hist, (uint32_t)(rows * kBins), lp.state, (uint32_t)rows, ranks, (uint32_t)cols);
+    hipLaunchKernelGGL(kth16r_hist_kernel<0>, dim3(grid), dim3(kLongThreads), 0, stream, lp);
+    hipLaunchKernelGGL((kth16r_scan_kernel<0, Stop0>), dim3(row_grid), dim3(256), 0, stream, lp);
+    hipLaunchKernelGGL(kth16r_hist_kernel<1>, dim3(grid), dim3(kLongThreads), 0, stream, lp);
+    hipLaunchKernelGGL((kth16r_scan_kernel<1, StopKth>), dim3(row_grid), dim3(256), 0, stream, lp);
+    LSD_HIP(hipGetLastError());
+    return LSDSORT_OK;
+}
+
+int run_perrow(const uint16_t* keys, size_t rows, size_t cols, const uint32_t* ranks, const Key16Map& map, uint16_t* out_keys,
+               uint32_t* out_idx, char* ws, const RowkLayout& L, hipStream_t stream)
+{
+    uint32_t* const ctl = reinterpret_cast<uint32_t*>(ws);
+    const Outputs out{out_keys, out_idx, (uint32_t)rows, ctl};
+    if (cols <= (size_t)kLocalSortCap) {
+        const ShortParams sp{keys, ranks, (uint32_t)cols, map, out, nullptr, 0u};
+        hipLaunchKernelGGL(kth16r_clear_kernel<false>, dim3(1), dim3(256), 0, stream, ctl, (uint32_t*)nullptr, 0u, (uint4*)nullptr, 0u,
+                           (const uint32_t*)nullptr, 0u);
+        if (cols <= (size_t)kWaveSegCap)
+            hipLaunchKernelGGL(kth16r_short_kernel<1>, dim3(grid_for(rows, 8, 16384)), dim3(512), 0, stream, sp);
+        else
+            hipLaunchKernelGGL(kth16r_short_kernel<16>, dim3(grid_for(rows, 1, 4096)), dim3(1024), 0, stream, sp);
+        LSD_HIP(hipGetLastError());
+        return LSDSORT_OK;
+    }
+    LongParams lp{};
+    lp.map = map;
+    lp.out = out;
+    if (!out_idx) {   // values only: both levels, then the prefix is the value
+        LSD_TRY((select_long_rowk<false, StopNever16>(lp, keys, rows, cols, ranks, ws, L, stream)));
+        hipLaunchKernelGGL(kth16r_value_kernel, dim3(grid_for(rows, 256, 1024)), dim3(256), 0, stream, lp);
+        LSD_HIP(hipGetLastError());
+        return LSDSORT_OK;
+    }
+    LSD_TRY((select_long_rowk<false, StopKth>(lp, keys, rows, cols, ranks, ws, L, stream)));
+    const uint32_t grid = (uint32_t)(rows * lp.chunks), row_grid = (uint32_t)rows;
+    hipLaunchKernelGGL(kth16r_count_kernel, dim3(grid), dim3(kLongThreads), 0, stream, lp);
+    hipLaunchKernelGGL(kth16r_pick_kernel, dim3(row_grid), dim3(256), 0, stream, lp);
+    hipLaunchKernelGGL(kth16r_locate_kernel, dim3(row_grid), dim3(kLongThreads), 0, stream, lp);
+    LSD_HIP(hipGetLastError());
+    return LSDSORT_OK;
+}
+
+int run_filter(const uint16_t* keys, size_t rows, size_t cols, const uint32_t* k, const Key16Map& map, uint32_t fill, uint16_t* dst,
+               char* ws, const RowkLayout& L, hipStream_t stream)
+{
+    uint32_t* const ctl = reinterpret_cast<uint32_t*>(ws);
+    const Outputs out{nullptr, nullptr, (uint32_t)rows, ctl};
+    if (cols <= (size_t)kLocalSortCap) {
+        const ShortParams sp{keys, k, (uint32_t)cols, map, out, dst, fill};
+        hipLaunchKernelGGL(kth16r_clear_kernel<true>, dim3(1), dim3(256), 0, stream, ctl, (uint32_t*)nullptr, 0u, (uint4*)nullptr, 0u,
+                           (const uint32_t*)nullptr, 0u);
+        if (cols <= (size_t)kWaveSegCap)
+            hipLaunchKernelGGL(topk16f_short_kernel<1>, dim3(grid_for(rows, 8, 16384)), dim3(512), 0, stream, sp);
+        else
+            hipLaunchKernelGGL(topk16f_short_kernel<16>, dim3(grid_for(rows, 1, 4096)), dim3(1024), 0, stream, sp);
+        LSD_HIP(hipGetLastError());
+        return LSDSORT_OK;
+    }
+    LongParams lp{};
+    lp.map = map;
+    lp.out = out;
+    lp.dst = dst;
+    lp.fill = fill;
+    LSD_TRY((select_long_rowk<true, StopNever16>(lp, keys, rows, cols, k, ws, L, stream)));
+    hipLaunchKernelGGL(topk16f_apply_kernel, dim3((uint32_t)(rows * lp.chunks)), dim3(kLongThreads), 0, stream, lp);
+    LSD_HIP(hipGetLastError());
+    return LSDSORT_OK;
+}
+
+bool sizes_ok(size_t rows, size_t cols) { return rows <= LSDSORT_MAX_KEYS && (rows == 0 || cols <= LSDSORT_MAX_KEYS / rows); }
+
+}  // namespace
+}  // namespace lsd
+
+extern "C" {
+
+size_t lsdsort_kth16_perrow_workspace_bytes(size_t rows, size_t cols)
+{
+    if (cols > LSDSORT_MAX_KEYS || !lsd::sizes_ok(rows, cols)) return 0;
+    return lsd::perrow_layout(rows, cols).end;
+}
+
+int lsdsort_kth16_perrow_device(const void* d_keys, size_t rows, size_t cols, const uint32_t* d_ranks, int key_type, int largest,
+                                void* d_out_keys, uint32_t* d_out_idx, void* d_workspace, size_t workspace_bytes, void* hip_stream)
+{
+    Key16Map map;
+    LSD_TRY(key16_map(key_type, largest, &map));
+    if (!lsd::sizes_ok(rows, cols)) return LSDSORT_ERR_TOO_LARGE;
+    if (rows == 0 || cols == 0) return LSDSORT_OK;
+    if (!d_keys || !d_out_keys || (((uintptr_t)d_keys | (uintptr_t)d_out_keys) & 1)) return LSDSORT_ERR_INVALID_ARG;
+    if (!d_ranks || ((uintptr_t)d_ranks & 3)) return LSDSORT_ERR_INVALID_ARG;   // their values are the device's to check
+    const lsd::RowkLayout L = lsd::perrow_layout(rows, cols);
+    if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.end)) return LSDSORT_ERR_WORKSPACE;
+    int rank_method = 0;   // asked for the device set-up alone: nothing here ranks with the returning add
+    LSD_TRY(lsd::device_rank_method(8, &rank_method));
+    return lsd::run_perrow(static_cast<const uint16_t*>(d_keys), rows, cols, d_ranks, map, static_cast<uint16_t*>(d_out_keys), d_out_idx,
+                           static_cast<char*>(d_workspace), L, static_cast<hipStream_t>(hip_stream));
+}
+
+size_t lsdsort_topk16_filter_workspace_bytes(size_t rows, size_t cols)
+{
+    if (cols > LSDSORT_MAX_KEYS || !lsd::sizes_ok(rows, cols)) return 0;
+    return lsd::filter_layout(rows, cols).end;
+}
+
+int lsdsort_topk16_filter_device(const void* d_keys, size_t rows, size_t cols, const uint32_t* d_k, int key_type, int largest,
+                                 uint16_t fill_bits, void* d_out, void* d_workspace, size_t workspace_bytes, void* hip_stream)
+{
+    Key16Map map;
+    LSD_TRY(key16_map(key_type, largest, &map));
+    if (!lsd::sizes_ok(rows, cols)) return LSDSORT_ERR_TOO_LARGE;
+    if (rows == 0 || cols == 0) return LSDSORT_OK;
+    if (!d_keys || !d_out || (((uintptr_t)d_keys | (uintptr_t)d_out) & 1)) return LSDSORT_ERR_INVALID_ARG;
+    if (!d_k || ((uintptr_t)d_k & 3)) return LSDSORT_ERR_INVALID_ARG;
+    const lsd::RowkLayout L = lsd::filter_layout(rows, cols);
+    if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.end)) return LSDSORT_ERR_WORKSPACE;
+    int rank_method = 0;   // asked for the device set-up alone: nothing here ranks with the returning add
+    LSD_TRY(lsd::device_rank_method(8, &rank_method));
+    return lsd::run_filter(static_cast<const uint16_t*>(d_keys), rows, cols, d_k, map, (uint32_t)fill_bits, static_cast<uint16_t*>(d_out),
+                           static_cast<char*>(d_workspace), L, static_cast<hipStream_t>(hip_stream));
+}
+
+}  // extern "C"
