@@ -14,7 +14,8 @@
 // Per workgroup (T = 512 threads, up to K = 32 keys each, two workgroups per CU):
 //   load, wave-striped: wave w owns positions [w * rows * 64, (w + 1) * rows * 64) of the bucket, lane l's i-th register holds
 //                       position w * rows * 64 + i * 64 + l, rows = ceil(size / T); positions past the bucket hold 0xFFFFFFFF
-//                       (the highest digit in every pass and the highest positions: they stay at the end and are never stored)
+//                       (the highest digit in every pass and the highest positions: they would stay at the end and are never
+//                       stored) and are neither ranked nor scattered (LocalGroup::live, ::inside)
 //   per digit pass    : zero the wave's counters | rank = returning add | barrier | one thread per digit: wave bases + exclusive
 //                       scan over digits | barrier | keys -> LDS at (base + rank) | barrier | read back in position order
 //   store             : from LDS, linear.
@@ -48,8 +49,23 @@ struct LocalGroup {
     lds_u32* s_misc;              // 64 words: the scan's partials [0, W), the callers' reductions over waves from 32
     uint32_t tid, lane, wave;
     uint32_t size, rows, wbase;   // rows = ceil(size / T), uniform, 1 .. K
+    // Padding: the wave's rows from `live` on (0 .. rows, uniform per wave) lie wholly past the bucket's end and take no part in a
+    // pass; in the one partial row, lane l holds a key in row i iff 64 i < inside.  Ranked like keys, the padding of a wave would
+    // all add to the highest digit's counter, which the LDS serves a lane per clock (about 64 clocks a row against 8 for random
+    // digits), on the last wave's way to the barrier.  It was the last of the highest digit and was never stored, so every key
+    // keeps its slot.
+    // INVARIANT: s_keys[size, rows * T) belongs to the padding lanes of the partial rows, each lane to its own position wbase + 64 i.
+    // No key's slot lies there (slots are ranks below size), store_linear stops at size, and only the owner reads or writes a
+    // position.  Such a lane is not switched off -- an exec mask around the adds costs more than the padding did --
+    // but made harmless: its add is of 0 to word [wave][lane] of the wave's own counters (lane < 64 <= kLocalMaxBins / 2), its
+    // scatter goes to its own position, its slot (KEEP) is that position, so read_rows, write_slots and the composition of two
+    // passes' slots find there what the lane itself put there.
+    uint32_t live, inside;
 };
-template <int K>
+// SKIP_PADDING false: every row and lane takes part, as if the bucket filled its rows (the segmented sort's kernels: with the two
+// words more they spill -- 88 B of scratch per lane without payloads, a wave per SIMD less with: tools/isa_diff.py --resources,
+// recorded in profiles/half_hop/compare.txt; tests/test_kernel_resources.py fails on both if sort_segment asks for true)
+template <int K, bool SKIP_PADDING = true>
 __device__ __forceinline__ LocalGroup<K> local_group(uint32_t size)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -64,8 +80,19 @@ __device__ __forceinline__ LocalGroup<K> local_group(uint32_t size)
     g.size = size;
     g.rows = (size + (uint32_t)kLocalThreads - 1u) / (uint32_t)kLocalThreads;
     g.wbase = g.wave * g.rows * 64u + g.lane;
+    g.live = g.rows;
+    g.inside = 0xFFFFFFFFu;
+    if (SKIP_PADDING) {
+        const uint32_t wfirst = (uint32_t)__builtin_amdgcn_readfirstlane((int)(g.wave * g.rows * 64u));
+        const uint32_t left = size > wfirst ? (size - wfirst + 63u) / 64u : 0u;
+        g.live = left < g.rows ? left : g.rows;
+        g.inside = size > g.wbase ? size - g.wbase : 0u;
+    }
     return g;
 }
+// does lane l's position in row i hold a key?  (one compare against a constant: all of a row but in the partial one)
+template <int K>
+__device__ __forceinline__ bool holds_key(const LocalGroup<K>& g, int i) { return (uint32_t)i * 64u < g.inside; }
 
 __device__ __forceinline__ void raise_fault(uint32_t* fault, uint32_t bit)
 {
@@ -85,20 +112,22 @@ __device__ __forceinline__ void load_rows(const LocalGroup<K>& g, const uint32_t
         }
     }
 }
-// LDS -> registers in position order; registers -> LDS at slot[i]; LDS -> global memory, linear (x: the key transform to undo)
+// LDS -> registers in position order; registers -> LDS at slot[i]; LDS -> global memory, linear (x: the key transform to undo).
+// The live rows only: the registers of the others keep what the load gave them (0xFFFFFFFF), and a padding lane of the partial
+// row finds in its own position what scatter_keys parked there (its own register again); its slot[i] is that position.
 template <int K>
 __device__ __forceinline__ void read_rows(const LocalGroup<K>& g, uint32_t (&r)[K])
 {
 #pragma unroll
     for (int i = 0; i < K; i++)
-        if ((uint32_t)i < g.rows) r[i] = g.s_keys[g.wbase + (uint32_t)i * 64u];
+        if ((uint32_t)i < g.live) r[i] = g.s_keys[g.wbase + (uint32_t)i * 64u];
 }
 template <int K>
 __device__ __forceinline__ void write_slots(const LocalGroup<K>& g, const uint32_t (&slot)[K], const uint32_t (&r)[K])
 {
 #pragma unroll
     for (int i = 0; i < K; i++)
-        if ((uint32_t)i < g.rows) g.s_keys[slot[i]] = r[i];
+        if ((uint32_t)i < g.live) g.s_keys[slot[i]] = r[i];
 }
 template <int K>
 __device__ __forceinline__ void store_linear(const LocalGroup<K>& g, uint32_t* dst, const KeyTransform* x = nullptr)
@@ -118,11 +147,14 @@ __device__ __forceinline__ void count_and_rank(const LocalGroup<K>& g, const uin
     for (int j = 0; j < HW / kWave; j++) g.s_cnt[g.wave * HW + j * kWave + g.lane] = 0;
 #pragma unroll
     for (int i = 0; i < K; i++) {
-        if ((uint32_t)i < g.rows) {
+        if ((uint32_t)i < g.live) {
+            // a padding lane of the partial row adds nothing, to a word of its own (no exec mask: the adds of all rows stay in
+            // one chain of uniform branches, issued back to back)
+            const bool on = holds_key(g, i);
             const uint32_t d = (key[i] >> shift) & mask;
             const uint32_t sh = (d & 1u) * 16u;
-            const uint32_t old = __hip_atomic_fetch_add((lds_u32*)&g.s_cnt[g.wave * HW + (d >> 1)], 1u << sh, __ATOMIC_RELAXED,
-                                                        __HIP_MEMORY_SCOPE_WAVEFRONT);
+            const uint32_t old = __hip_atomic_fetch_add((lds_u32*)&g.s_cnt[g.wave * HW + (on ? d >> 1 : g.lane)], on ? 1u << sh : 0u,
+                                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             rank[i] = (old >> sh) & 0xFFFFu;
         }
     }
@@ -156,19 +188,20 @@ __device__ __forceinline__ void scatter_keys(const LocalGroup<K>& g, const uint3
                                              uint32_t mask)
 {
     // two rows per uniform branch: both base reads are in flight before the first write waits for its own (0.590 -> 0.584 ms per
-    // 2^28 keys).  A row past the bucket's last reads a counter it never uses -- its key register holds whatever it holds,
-    // masked into the table.
+    // 2^28 keys).  A row past the wave's last live one reads a counter it never uses -- its key register holds whatever it holds,
+    // masked into the table.  A padding lane of the partial row parks its register (0xFFFFFFFF) at its own position: past the
+    // bucket's end, where no key goes and nothing is stored from.
     static_assert(K % 2 == 0, "rows are scattered in pairs");
 #pragma unroll
     for (int i = 0; i < K; i += 2) {
-        if ((uint32_t)i < g.rows) {
+        if ((uint32_t)i < g.live) {
             const uint32_t b0 = g.s_cnt16[g.wave * kLocalMaxBins + ((key[i] >> shift) & mask)];
             const uint32_t b1 = g.s_cnt16[g.wave * kLocalMaxBins + ((key[i + 1] >> shift) & mask)];
-            const uint32_t pos0 = b0 + rank[i];
+            const uint32_t pos0 = holds_key(g, i) ? b0 + rank[i] : g.wbase + (uint32_t)i * 64u;
             if (KEEP) rank[i] = pos0;
             g.s_keys[pos0] = key[i];
-            if ((uint32_t)(i + 1) < g.rows) {
-                const uint32_t pos1 = b1 + rank[i + 1];
+            if ((uint32_t)(i + 1) < g.live) {
+                const uint32_t pos1 = holds_key(g, i + 1) ? b1 + rank[i + 1] : g.wbase + (uint32_t)(i + 1) * 64u;
                 if (KEEP) rank[i + 1] = pos1;
                 g.s_keys[pos1] = key[i + 1];
             }
@@ -322,11 +355,11 @@ __device__ __forceinline__ void sort_bucket_multi(const LocalSortParams& p, cons
         __syncthreads();   // the keys have left the LDS: it now holds the second pass's slots by position ...
 #pragma unroll
         for (int i = 0; i < K; i++)
-            if ((uint32_t)i < g.rows) g.s_keys[g.wbase + (uint32_t)i * 64u] = slot[i];
+            if ((uint32_t)i < g.live) g.s_keys[g.wbase + (uint32_t)i * 64u] = slot[i];
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < K; i++)   // ... and the element that started at position wbase + 64 i ends in slot2[slot1]
-            if ((uint32_t)i < g.rows) slot[i] = g.s_keys[first_slot[i]];
+            if ((uint32_t)i < g.live) slot[i] = g.s_keys[first_slot[i]];   // (a padding lane: its own position both times)
     }
     for (uint32_t e = 0; e < p.num_payloads; e++) {
         uint32_t* const pay = (e == 0 ? p.vals : p.more[e - 1]) + lo;
@@ -477,7 +510,7 @@ __device__ __forceinline__ void sort_segment(const SegSortParams& p, const uint3
     if (s >= p.num_segments) return raise_fault(p.fault, 128u);   // never listed: say so, touch nothing
     const uint32_t lo = p.offsets[s], hi = p.offsets[s + 1];
     if (hi < lo || hi > p.n || hi - lo > (uint32_t)(kLocalThreads * K)) return raise_fault(p.fault, 128u);
-    const LocalGroup<K> g = local_group<K>(hi - lo);
+    const LocalGroup<K> g = local_group<K, false>(hi - lo);
     uint32_t* const seg = p.keys + lo;
     uint32_t* const seg_vals = PAIRS ? p.vals + lo : nullptr;
 

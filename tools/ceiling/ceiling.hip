@@ -11,10 +11,12 @@
 //                 addresses a pass on perfectly uniform digits would use -- no LDS, no ranking, no chain:
 //                 the memory-system floor of a pass.  Tiles are dealt to XCDs in chunks of C consecutive
 //                 tiles (C = 0: round-robin), tile sizes 8192..65536 keys.
-// Build: hipcc --offload-arch=gfx950 -O3 -o ceiling ceiling.hip      Run: ./ceiling [log2_n]
+//   tile_scatter_half: the same with 16-bit scattered stores (`./ceiling 28 half` runs only this pair: profiles/half_hop/ceiling.txt)
+// Build: hipcc --offload-arch=gfx950 -O3 -o ceiling ceiling.hip      Run: ./ceiling [log2_n [half]]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 #include <algorithm>
 #include <functional>
@@ -130,6 +132,38 @@ __global__ void __launch_bounds__(T) tile_scatter_kernel(const uint32_t* __restr
     }
 }
 
+// The same shape with the scattered stores 16 bits wide: the key is still read as 4 B/lane, its low half goes to a uint16_t
+// destination at the same index (256-B runs at 1024 x 32).  What a pass would cost that writes only the low halves of its keys
+// (6 B/key instead of 8), run beside the 32-bit form by `ceiling <log2_n> half`.
+template <int T, int K>
+__global__ void __launch_bounds__(T) tile_scatter_half_kernel(const uint32_t* __restrict__ in, uint16_t* __restrict__ out,
+                                                              uint32_t n, uint32_t num_tiles, uint32_t chunk)
+{
+    constexpr uint32_t TILE = T * K;
+    constexpr uint32_t RUN = TILE / 256;
+    uint32_t tile = blockIdx.x;
+    if (chunk) {
+        const uint32_t group = 8u * chunk;
+        const uint32_t g0 = (tile / group) * group;
+        if (g0 + group <= num_tiles) {
+            const uint32_t k = tile - g0;
+            tile = g0 + (k % 8u) * chunk + (k / 8u);
+        }
+    }
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t* src = in + (size_t)tile * TILE + wave * (64 * K) + lane;
+    uint32_t key[K];
+#pragma unroll
+    for (int i = 0; i < K; i++) key[i] = src[i * 64];
+    const uint32_t per_digit = n / 256;
+#pragma unroll
+    for (int s = 0; s < K; s++) {
+        const uint32_t q = s * T + threadIdx.x;
+        const uint32_t d = q / RUN;
+        out[(size_t)d * per_digit + (size_t)tile * RUN + (q % RUN)] = (uint16_t)key[s];
+    }
+}
+
 // Same through LDS: keys are written to LDS at a permuted position and read back linearly, then stored as above
 // (adds the LDS round trip a real pass makes, still no ranking atomics and no chain).
 template <int T, int K>
@@ -168,7 +202,7 @@ __global__ void __launch_bounds__(T) tile_scatter_lds_kernel(const uint32_t* __r
     }
 }
 
-static float time_ms(hipEvent_t a, hipEvent_t b, int reps, const std::function<void()>& fn)
+static float time_ms(hipEvent_t a, hipEvent_t b, int reps, const std::function<void()>& fn, float* lo = nullptr, float* hi = nullptr)
 {
     std::vector<float> ts;
     for (int i = 0; i < reps + 2; i++) {
@@ -181,7 +215,26 @@ static float time_ms(hipEvent_t a, hipEvent_t b, int reps, const std::function<v
         if (i >= 2) ts.push_back(ms);
     }
     std::sort(ts.begin(), ts.end());
+    if (lo) *lo = ts.front();
+    if (hi) *hi = ts.back();
     return ts[ts.size() / 2];
+}
+
+// `ceiling <log2_n> half`: the work-free pass shape (1024 x 32 tile) with 32-bit and with 16-bit scattered stores, alternating, so
+// that both see the same box in the same minute: median, min and max of nine runs each, round-robin and 16 tiles per XCD.
+static void half_probe(const uint32_t* in, uint32_t* out, size_t n, hipEvent_t a, hipEvent_t b)
+{
+    const uint32_t tiles = (uint32_t)(n / 32768);
+    for (int round = 0; round < 3; round++) {
+        for (uint32_t chunk : {0u, 16u}) {
+            float lo, hi;
+            float ms = time_ms(a, b, 9, [&] { hipLaunchKernelGGL((tile_scatter_kernel<1024, 32>), dim3(tiles), dim3(1024), 0, 0, in, out, (uint32_t)n, tiles, chunk); }, &lo, &hi);
+            printf("round %d tile_scatter      1024x32 C=%-2u  8 B/key  median %.4f ms  min %.4f  max %.4f  spread %.4f\n", round, chunk, ms, lo, hi, hi - lo);
+            ms = time_ms(a, b, 9, [&] { hipLaunchKernelGGL((tile_scatter_half_kernel<1024, 32>), dim3(tiles), dim3(1024), 0, 0, in, (uint16_t*)out, (uint32_t)n, tiles, chunk); }, &lo, &hi);
+            printf("round %d tile_scatter_half 1024x32 C=%-2u  6 B/key  median %.4f ms  min %.4f  max %.4f  spread %.4f\n", round, chunk, ms, lo, hi, hi - lo);
+            fflush(stdout);
+        }
+    }
 }
 
 int main(int argc, char** argv)
@@ -198,6 +251,11 @@ int main(int argc, char** argv)
     hipEvent_t a, b;
     CHECK(hipEventCreate(&a));
     CHECK(hipEventCreate(&b));
+    if (argc > 2 && std::string(argv[2]) == "half") {
+        half_probe(in, out, n, a, b);
+        CHECK(hipDeviceSynchronize());
+        return 0;
+    }
     const int reps = 9;
     auto report = [&](const char* name, int grid, float ms, double moved) {
         printf("%-34s grid=%7d  %.4f ms  %.2f TB/s\n", name, grid, ms, moved / ms / 1e9);
