@@ -540,6 +540,45 @@ LSDSORT_API int lsdsort_topk16_filter_device(const void* d_keys, size_t rows, si
                                              void* d_out /* [rows][cols] 16-bit; may be d_keys itself */, void* d_workspace,
                                              size_t workspace_bytes, void* hip_stream);
 
+/* Top-p (nucleus) FILTER for float16 / bfloat16 rows with a p of its own for every row, read from device memory
+ * (lsdradixsort_amd/csrc/topp16.hip): "keep the smallest set of best logits whose softmax mass reaches p_r, set the rest to -inf",
+ * without a sort.  key_type is LSDSORT_KEY16_F16 or LSDSORT_KEY16_BF16; the order is always "largest is best" in the library's total
+ * order: -0.0 below +0.0, +NaN above +inf, -NaN below -inf.
+ * d_p is a DEVICE array of `rows` float32 (4-byte aligned); let p = d_p[r].  If !(p < 1) -- p >= 1 or a NaN -- the filter is OFF for
+ * the row: row r of d_out is row r of d_keys (left alone in place).  Otherwise, in exact arithmetic: m is the largest non-NaN key of
+ * the row by value; w(x) is 0 for a NaN, 1 where x == m (which also defines rows whose maximum is an infinity) and exp(x - m)
+ * elsewhere; Z is the sum of w over the row; A(x) the sum of w over the keys strictly better than x in the library's order.  Key x
+ * is KEPT iff A(x) < p * Z or x is the best value of the row.  So p <= 0 keeps the best value and its duplicates alone, a row always
+ * keeps at least one key, every duplicate of a kept value is kept.  Kept keys are copied bit for bit, the others become fill_bits.
+ * The kept set is "every key at least as good as a threshold value T_r".  The device works in float32 and truncated fixed point
+ * (w by v_exp_f32, masses floor(w * 2^32) summed as 64-bit integers), so T_r is specified to a mass tolerance: it is consistent with
+ * p_r +- 2^-12 for |logit| <= 64 and cols <= 2^17; given T_r the output is exact.  The result is DETERMINISTIC: integer sums do not
+ * depend on the order of the adds, so the same row and p give the same bits on every call, whatever the other rows and `rows`.
+ * Composition: w(-inf) = 0, so lsdsort_topk16_filter_device(fill_bits = -inf) followed by this entry, both in place, is "top-k,
+ * then top-p over the renormalised survivors".
+ * d_out may be d_keys itself (in place); any other overlap is the caller's error and is not checked.  d_keys and d_out need 2-byte
+ * alignment only, their alignments may differ from each other, and cols may be odd.  There is no bad-argument flag: every value of
+ * d_p means something.  The host never reads d_p and no value in it sizes a launch: capturable after lsdsort_prepare_device, and d_p
+ * is read again on every replay, so a captured decode graph follows a changed top_p.
+ * Kernels: rows of up to 1024 keys (one wavefront) and up to 16384 (one workgroup) are loaded into registers once, the threshold is
+ * found there by a 16-step bisection over the masses, and the same registers are compared and stored: one read and one write of the
+ * row (4 B/key by byte accounting).  Longer rows: the best key, a 2048-bin mass histogram and a 32-bin count histogram (three
+ * reads), then one kernel reads every tile again, compares and stores: 10 B/key.  Rows whose filter is off skip the select.
+ * Stream-ordered, no host synchronisation, nothing allocated; phases are ordered by kernel boundaries; every store stays within its
+ * row.  The fault word is the first word of the workspace: bit 1024 where nothing was selected for a row (never expected; nothing
+ * is stored for the row).  The result does not depend on lsdsort_set_rank_method.
+ * Checks, in order, each before a device is touched: key_type other than float16 / bfloat16 (INVALID_ARG), rows or rows * cols above
+ * LSDSORT_MAX_KEYS (TOO_LARGE), rows == 0 or cols == 0 (OK, nothing launched), a NULL or odd d_keys or d_out, a NULL d_p or one that
+ * is not 4-byte aligned (INVALID_ARG), the workspace (WORKSPACE: NULL, not 256-byte aligned, or below
+ * lsdsort_topp16_filter_workspace_bytes), the device (NO_DEVICE).
+ * lsdsort_topp16_filter_workspace_bytes is a multiple of 256, monotonic in each argument, 0 above the limits, independent of d_p,
+ * and O(rows): lsdsort_topk16_filter_workspace_bytes, and for rows above 16384 keys 16 KiB of mass bins per row on top of it. */
+LSDSORT_API size_t lsdsort_topp16_filter_workspace_bytes(size_t rows, size_t cols);
+LSDSORT_API int lsdsort_topp16_filter_device(const void* d_keys, size_t rows, size_t cols, const float* d_p /* DEVICE, [rows] */,
+                                             int key_type /* float16 or bfloat16 */, uint16_t fill_bits,
+                                             void* d_out /* [rows][cols] 16-bit; may be d_keys itself */, void* d_workspace,
+                                             size_t workspace_bytes, void* hip_stream);
+
 /* After the stream has drained: LSDSORT_OK, or LSDSORT_ERR_DEVICE_FAULT if a kernel of the
  * last sort on this workspace gave up a bounded spin or refused destinations outside the output
  * (never expected; the output is then undefined).  Synchronises hip_stream.  With LSDSORT_REPROBE=1

@@ -113,6 +113,9 @@ SIGNATURES = {
     "lsdsort_topk16_filter_workspace_bytes": (c_size, [c_size, c_size]),
     "lsdsort_topk16_filter_device": (c_int, [ctypes.c_void_p, c_size, c_size, c_u32p, c_int, c_int, ctypes.c_uint16, ctypes.c_void_p,
                                              ctypes.c_void_p, c_size, ctypes.c_void_p]),
+    "lsdsort_topp16_filter_workspace_bytes": (c_size, [c_size, c_size]),
+    "lsdsort_topp16_filter_device": (c_int, [ctypes.c_void_p, c_size, c_size, ctypes.c_void_p, c_int, ctypes.c_uint16, ctypes.c_void_p,
+                                             ctypes.c_void_p, c_size, ctypes.c_void_p]),
     "lsdsort_u32_device_timed": (c_int, [c_u32p, c_u32p, ctypes.c_void_p, c_size, c_size, c_int, c_int,
                                          ctypes.c_void_p, ctypes.POINTER(LsdsortTiming)]),
     "lsdsort_tile_keys": (c_size, [c_int]),

@@ -29,6 +29,7 @@ __all__ = [
     "GPUKth16", "kth16_workspace_bytes", "kthvalue16_rows", "median16_rows",
     "GPUKth16Multi", "kth16_multi_workspace_bytes", "quantile16_rows",
     "GPUKth16PerRow", "kth16_perrow_workspace_bytes", "GPUTopK16Filter", "topk16_filter_workspace_bytes", "topk16_filter_rows",
+    "GPUTopP16Filter", "topp16_filter_workspace_bytes", "topp16_filter_rows",
     "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
     "MSBPartition", "SplitterPartition", "ThresholdPartition", "sharded_thresholds",
 ]
@@ -1067,6 +1068,104 @@ def topk16_filter_rows(x, k, largest: bool = True, fill=None, inplace: bool = Fa
         flat = (x if inplace else x.contiguous()).view(-1, cols)
         out = GPUTopK16Filter(flat, d_k, key_type=str(x.dtype).replace("torch.", ""), largest=largest, fill=bits,
                               out=flat if inplace else None, stream=stream)
+        return x if inplace else out.view(x.shape)
+
+
+def topp16_filter_workspace_bytes(rows: int, cols: int) -> int:
+    """Bytes of device workspace ``GPUTopP16Filter`` needs for ``rows`` rows of ``cols`` 16-bit keys (whatever the p's)."""
+    return int(lib().lsdsort_topp16_filter_workspace_bytes(rows, cols))
+
+
+def _p_per_row(p, rows: int, device):
+    """``p`` of ``topp16_filter_rows`` as the float32 vector the library reads, one entry per row, on ``device``: a float (every
+    row), a sequence of floats, or a float32 / float64 tensor.  A float32 tensor on ``device`` is used as it is."""
+    torch = _torch()
+    what = "p: a float, a sequence of floats, or a float32 / float64 tensor"
+    if isinstance(p, torch.Tensor):
+        if p.dtype not in (torch.float32, torch.float64):
+            raise TypeError(what)
+        if p.numel() != rows:
+            raise ValueError(f"p: one entry per row ({rows}), got {p.numel()}")
+        return p.to(torch.float32).to(device).contiguous().view(-1)
+    if isinstance(p, (bool, str, bytes)) or p is None:
+        raise TypeError(what)
+    if isinstance(p, (int, float)):
+        return torch.full((rows,), float(p), dtype=torch.float32, device=device)
+    try:
+        values = [float(v) for v in p]
+    except (TypeError, ValueError):
+        raise TypeError(what) from None
+    if len(values) != rows:
+        raise ValueError(f"p: one entry per row ({rows}), got {len(values)}")
+    return torch.tensor(values, dtype=torch.float32).to(device)
+
+
+def GPUTopP16Filter(d_keys, d_p, key_type: str = "bfloat16", fill: int | None = None, out=None, workspace=None, stream=None,
+                    check_fault: bool = False):
+    """The top-p (nucleus) filter of every row with a p of its own per row, read on the device (``lsdsort_topp16_filter_device``):
+    ``d_keys`` a contiguous 1-D or 2-D float16 / bfloat16 CUDA tensor of logits, ``d_p`` a contiguous float32 CUDA tensor with one
+    entry per row.  Row ``r`` of the result is row ``r`` of ``d_keys`` where ``d_p[r]`` is not below 1 (a NaN included): the filter
+    is off.  Otherwise the smallest set of the row's best keys whose softmax mass reaches ``d_p[r]`` is kept bit for bit -- a key
+    stays iff the mass of the strictly better keys is below ``d_p[r]``, or it is the row's best value; every duplicate of a kept
+    value stays -- and the others become the 16-bit word ``fill`` (an int in 0 .. 0xFFFF; ``None``: -inf).  The order is the
+    library's total order: -0.0 below +0.0, NaNs by sign at the two ends, and a NaN has no mass.  The threshold is found without a
+    sort, in float32 and 64-bit fixed point: it is consistent with ``d_p[r]`` to 2^-12 of the row's mass, and the result is the same
+    bits on every call, whatever the other rows.  Returns the result: ``out`` where one is given (``out=d_keys`` runs in place),
+    else a new tensor.  The host never reads ``d_p``: a captured graph follows its contents.  Stream-ordered; short rows are read
+    once and written once, rows above 16384 keys read four times and written once."""
+    torch = _torch()
+    _dev(d_keys, "d_keys", (torch.float16, torch.bfloat16), dims=(1, 2))
+    if key_type not in ("float16", "bfloat16"):
+        raise ValueError(f'key_type: "float16" or "bfloat16", got {key_type!r}')
+    code, rows, cols = _keys16(d_keys, key_type, "is filtered")
+    _dev(d_p, "d_p", (torch.float32,))
+    if d_p.numel() != rows:
+        raise ValueError(f"d_p: one entry per row ({rows}), got {d_p.numel()}")
+    if fill is None:
+        fill = _worst_bits16(key_type, True)
+    if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 0xFFFF:
+        raise ValueError("fill: a 16-bit word, an int within 0 .. 0xFFFF")
+    if out is not None:
+        _dev(out, "out", (d_keys.dtype,), dims=(d_keys.dim(),))
+        if out.shape != d_keys.shape:
+            raise ValueError("out: the shape of d_keys")
+    with _on_stream(stream):   # the output, like a temporary workspace, belongs to the stream the kernels run on
+        result = out if out is not None else torch.empty_like(d_keys)
+    if workspace is None:
+        nbytes = topp16_filter_workspace_bytes(rows, cols)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_topp16_filter_workspace_bytes", "too many keys or rows")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    check(lib().lsdsort_topp16_filter_device(d_keys.data_ptr(), rows, cols, d_p.data_ptr(), code, fill, result.data_ptr(),
+                                             workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_topp16_filter_device")
+    if check_fault and rows and cols:
+        _check_fault(workspace, stream)
+    return result
+
+
+def topp16_filter_rows(x, p, fill=None, inplace: bool = False, stream=None):
+    """The top-p (nucleus) filter of a sampling step for a float16 / bfloat16 CUDA tensor of logits of one or more dimensions: per
+    row of the last dimension what sort descending, softmax, ``cumsum - probs >= p`` masked and scattered back gives, without the
+    sort: the best logits stay until their softmax mass reaches ``p_r``, ties of a kept value included, and the others become
+    ``fill``.  ``p`` is a float for every row, or one entry per row as a sequence or a float32 / float64 tensor; ``p_r >= 1`` or a
+    NaN leaves the row as it is, ``p_r <= 0`` keeps the best value alone.  A host value becomes a device tensor here; a float32 CUDA
+    tensor is used as it is, so a captured caller pays no conversion and may change its contents between replays.  ``fill``: a value
+    of ``x``'s dtype; ``None`` is -inf.  ``inplace`` filters ``x`` itself (contiguous) and returns it.  The order is the library's
+    total order, not torch's: -0.0 ranks below +0.0 and NaNs sort by sign at the two ends."""
+    torch = _torch()
+    _dev(x, "x", (torch.float16, torch.bfloat16), contiguous=bool(inplace))
+    if x.dim() == 0:
+        raise TypeError("x: at least one dimension")
+    cols = x.shape[-1]
+    rows = int(np.prod(x.shape[:-1], dtype=np.int64))
+    bits = _fill_bits16(x.dtype, fill, True)
+    with _on_stream(stream):
+        d_p = _p_per_row(p, rows, x.device)
+        if rows == 0 or cols == 0:
+            return x if inplace else x.clone()
+        flat = (x if inplace else x.contiguous()).view(-1, cols)
+        out = GPUTopP16Filter(flat, d_p, key_type=str(x.dtype).replace("torch.", ""), fill=bits, out=flat if inplace else None,
+                              stream=stream)
         return x if inplace else out.view(x.shape)
 
 
