@@ -6,8 +6,8 @@
 // applied where a key is read, and the raw key is what is stored.
 //
 // A radix SELECT by counting only, as in topk.hip, and a LOCATE instead of top-k's compact + sort.  The select's skeleton is
-// radix_select.hpp's, shared with topk.hip and topk16.hip, with the stop rule StopKth; this unit adds the loads (Row<uint32_t> with
-// a validity mask), locate_tile and the count, pick and locate kernels.
+// radix_select.hpp's, shared with topk.hip and topk16.hip, with the stop rule StopKth; the loads (Row<uint32_t> with a validity
+// mask) and locate_tile are select_tiles32.hpp's, shared with kth_multi.hip; this unit adds the count, pick and locate kernels.
 //   select   most significant digit first, count the digit of the keys that still match the prefix found so far, walk the counts
 //            from the best end to the bin that holds the wanted key: that bin's digit joins the prefix and `need` (which of the
 //            prefix's keys, in sorted order, is wanted; 1-based) shrinks by the number of keys in better bins.  Unlike top-k it
@@ -17,15 +17,7 @@
 //            `need`-th of them in POSITION order: per-lane counts, a wave scan, per-wave counts through LDS (and per-chunk counts
 //            through memory for long rows).  One lane stores the key, un-mapped, and its position.  No atomic-arrival order shows.
 //
-// Key reads.  A row starts 4 r cols bytes past d_keys, at any multiple of 4 within a 16-byte line.  Every kernel therefore splits
-// EACH ROW by address (Row, as topk16.hip does for 2-byte keys): `head` keys in front of the row's first 16-byte line (0..3), read
-// one by one, and the `body` from that line on, read as 16-byte groups of four keys; the last group of a row (or chunk) that is
-// not whole is read one by one too.  A lane holds four groups of its wave's tile: register 4 j + e is body position
-// q0 + 4 (64 j + lane) + e.
-// A key that does not exist.  Every 32-bit pattern is a real key, so no padding value can stand for "no key" (the 16-bit select's
-// 0xFFFFFFFF does not carry over).  Instead every tile comes with a per-lane VALIDITY MASK (bit i: register i holds a key of the
-// row; bit 16: the head register does), made from the positions alone where the tile is loaded, and every count and every match
-// is the AND of that bit with the comparison: a register without a key matches no (prefix, shift) whatever it holds.
+// Key reads and the validity mask that stands for "no key": select_tiles32.hpp.
 // Size classes (those of topk.hip, by cols):
 //   cols <= kWaveSegCap (1024)      one wavefront per row, eight rows per workgroup, no workgroup barrier: the row in its registers,
 //                                   8-bit digits counted in its own LDS slice.  4 B/key read, 8 B/row written.
@@ -45,118 +37,21 @@
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
 #include "radix_select.hpp"
+#include "select_tiles32.hpp"
 
 namespace lsd {
 namespace {
 
 constexpr uint32_t kKthFaultCount = 1024u;    // fault word: the digit counts of a row do not reach the rank (never expected)
 constexpr uint32_t kKthFaultLocate = 2048u;   // fault word: no key was located for a row (never expected; nothing stored)
-constexpr uint32_t kGroup = 4;                // keys of one 16-byte load
-constexpr uint32_t kHeadBit = 1u << kRegs;    // validity mask: the head register
-constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
-using Row32 = Row<uint32_t>;   // a lane holds four 16-byte groups of four keys of its wave's tile
-
-// The wave's tile from body position q0 (a multiple of four) on, valid below `end`: a whole group by one 16-byte load, the others
-// key by key.  Returns the validity mask of the sixteen registers; a register without a key holds zero and its bit is clear.
-__device__ __forceinline__ uint32_t load_tile(const Row32& r, uint32_t q0, uint32_t end, uint32_t lane, const KeyTransform& xf,
-                                              uint32_t (&t)[kRegs])
-{
-    uint32_t vm = 0u;
-#pragma unroll
-    for (int j = 0; j < kRegs / 4; j++) {
-        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroup;
-        if (q < end && end - q >= kGroup) {
-            const uint4 v = *reinterpret_cast<const uint4*>(r.keys + r.head + q);
-            t[4 * j] = to_sortable(v.x, xf);
-            t[4 * j + 1] = to_sortable(v.y, xf);
-            t[4 * j + 2] = to_sortable(v.z, xf);
-            t[4 * j + 3] = to_sortable(v.w, xf);
-            vm |= 0xFu << (4 * j);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                t[4 * j + e] = 0u;
-                if (q < end && q + (uint32_t)e < end) {
-                    t[4 * j + e] = to_sortable(r.keys[r.head + q + (uint32_t)e], xf);
-                    vm |= 1u << (4 * j + e);
-                }
-            }
-        }
-    }
-    return vm;
-}
-// head key `lane` of the row, for the one wave that owns the head: its validity bit, and the key into h
-__device__ __forceinline__ uint32_t load_head(const Row32& r, uint32_t lane, const KeyTransform& xf, uint32_t& h)
-{
-    h = 0u;
-    if (lane >= r.head) return 0u;
-    h = to_sortable(r.keys[lane], xf);
-    return kHeadBit;
-}
 
 struct Outputs {
     uint32_t* keys;       // [rows], raw keys
     uint32_t* idx;        // [rows] positions, may be null
     uint32_t rows;
     uint32_t* fault;
+    __device__ __forceinline__ size_t at(uint32_t row, uint32_t) const { return row; }   // locate_tile's store: one slot per row
 };
-
-// Locate within one tile held in registers (load_tile at q0, validity mask vm; with kHeadBit in vm of some lanes: the head keys h
-// in front of it).  `base`: the keys under the prefix before this tile in the row; it moves on past the tile.  If the `need`-th
-// (1-based) such key of the row lies in this tile, the lane that holds it stores it.  Returns whether it did (uniform over the
-// group).  s_wc: WAVES words.
-template <int WAVES>
-__device__ __forceinline__ bool locate_tile(const uint32_t (&t)[kRegs], uint32_t h, uint32_t vm, uint32_t q0, const Row32& r, uint32_t prefix,
-                                            uint32_t shift, uint32_t need, uint32_t& base, volatile lds_u32* s_wc, uint32_t wave,
-                                            uint32_t lane, uint32_t row, const Outputs& o, const KeyTransform& xf)
-{
-    uint32_t em = ((vm & kHeadBit) != 0u && (h >> shift) == prefix) ? kHeadBit : 0u;   // the keys under the prefix
-#pragma unroll
-    for (int i = 0; i < kRegs; i++) em |= (((vm >> i) & 1u) != 0u && (t[i] >> shift) == prefix) ? 1u << i : 0u;
-    const uint32_t mine = wave_sum((uint32_t)__builtin_popcount(em));
-    uint32_t before = base, all = mine;
-    if (WAVES > 1) {
-        if (lane == 0u) s_wc[wave] = mine;
-        __syncthreads();
-        all = 0u;
-        for (uint32_t w = 0; w < (uint32_t)WAVES; w++) {
-            const uint32_t c = s_wc[w];
-            if (w < wave) before += c;
-            all += c;
-        }
-        __syncthreads();   // the next tile writes s_wc again
-    }
-    const bool here = base < need && need - base <= all;   // uniform
-    if (here) {
-        auto store = [&](uint32_t key, uint32_t pos) {
-            if (row < o.rows) {
-                o.keys[row] = from_sortable(key, xf);
-                if (o.idx) o.idx[row] = pos;
-            }
-        };
-        // position order: the head keys by lane, then group j of lane 0, 1, .. 63, j = 0 .. 3
-        const uint32_t ch = em >> kRegs;
-        const uint32_t hi = wave_inclusive_scan(ch);
-        if (ch != 0u && before + hi == need) store(h, lane);
-        before += (uint32_t)__builtin_amdgcn_readlane((int)hi, 63);
-#pragma unroll
-        for (int j = 0; j < kRegs / 4; j++) {
-            const uint32_t g = (em >> (4 * j)) & 0xFu, c = (uint32_t)__builtin_popcount(g);
-            const uint32_t incl = wave_inclusive_scan(c), lo = before + incl - c;
-            if (lo < need && need - lo <= c) {
-                uint32_t left = need - lo;   // 1 .. c: which of this group's matching keys
-                const uint32_t pos = r.head + q0 + ((uint32_t)j * 64u + lane) * kGroup;
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    if (((g >> e) & 1u) != 0u && --left == 0u) store(t[4 * j + e], pos + (uint32_t)e);
-                }
-            }
-            before += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-    }
-    base += all;
-    return here;
-}
 
 // ---- short rows: one wavefront (WAVES = 1, eight rows per workgroup) or one workgroup (WAVES = 16) per row ----------------------
 struct ShortParams {
@@ -196,7 +91,7 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) kth_short_kernel(cons
         };
         const Selected sel = select_short<WAVES, 4, StopKth>(s_cnt, s_found, wave, lane, p.rank + 1u, p.out.fault, kKthFaultCount, count);
         uint32_t base = 0u;
-        const bool found = locate_tile<WAVES>(t, h, vm, q0, r, sel.prefix, sel.shift, sel.need, base, s_wc, wave, lane, row, p.out, p.xf);
+        const bool found = locate_tile<WAVES>(t, h, vm, q0, r, sel.prefix, sel.shift, sel.need, base, s_wc, wave, lane, row, 0u, p.out, p.xf);
         if (!found && sel.need != 0u && wave == 0u && lane == 0u) atomicOr(p.out.fault, kKthFaultLocate);
         group_sync<WAVES>();
     }
@@ -353,7 +248,7 @@ __global__ void __launch_bounds__(kLongThreads) kth_locate_kernel(const LongPara
         uint32_t t[kRegs], h = 0u;
         uint32_t vm = load_tile(r, q0, g.hi, lane, p.xf, t);
         if (st.w == 0u && tile == g.lo && wave == 0u) vm |= load_head(r, lane, p.xf, h);   // uniform
-        found = locate_tile<(int)kLongWaves>(t, h, vm, q0, r, st.x, st.y, st.z, base, s_wc, wave, lane, row, p.out, p.xf);
+        found = locate_tile<(int)kLongWaves>(t, h, vm, q0, r, st.x, st.y, st.z, base, s_wc, wave, lane, row, 0u, p.out, p.xf);
     }
     if (!found && tid == 0u) atomicOr(p.out.fault, kKthFaultLocate);
 }

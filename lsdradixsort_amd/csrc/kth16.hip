@@ -16,11 +16,8 @@
 //            StopNever16 (no early stop) and kth16_value_kernel stores from_sortable16(prefix) per row -- two reads of the row, six
 //            launches, no count, pick or locate.
 //
-// Key reads are topk16.hip's (Row<uint16_t>): `head` keys in front of the row's first 16-byte line (0..7) one by one, the `body` in
-// 16-byte groups of eight, two groups per lane per tile (register 8 j + e is body position q0 + 8 (64 j + lane) + e), the last group
-// that is not whole one by one.  A register without a key holds kNoKey = 0xFFFFFFFF: a sortable value is below 65536, so no
-// (prefix, shift) of a select matches it and kth.hip's validity mask is not needed.  The two loaders below are this unit's own copy
-// of topk16.hip's (one header once an ISA diff proves the move).
+// Key reads, the loaders and locate_tile are select_tiles16.hpp's, shared with every 16-bit row select: a register without a key
+// holds kNoKey, which no (prefix, shift) matches, so kth.hip's validity mask is not needed.
 // Size classes (those of every select here, by cols):
 //   cols <= kWaveSegCap (1024)      one wavefront per row, eight rows per workgroup, no workgroup barrier.  2 B/key read.
 //   cols <= kLocalSortCap (16384)   one workgroup of 16 wavefronts per row: the same
@@ -39,113 +36,21 @@
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
 #include "radix_select.hpp"
+#include "select_tiles16.hpp"
 
 namespace lsd {
 namespace {
 
 constexpr uint32_t kKth16FaultCount = 1024u;    // fault word: the digit counts of a row do not reach the rank (never expected)
 constexpr uint32_t kKth16FaultLocate = 2048u;   // fault word: no key was located for a row (never expected; nothing stored)
-constexpr uint32_t kNoKey = 0xFFFFFFFFu;        // a sortable value is below 65536
-constexpr uint32_t kHeadBit = 1u << kRegs;      // match mask: the head register
-constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
-using Row16 = Row<uint16_t>;   // a lane holds two 16-byte groups of eight keys of its wave's tile
-
-// the values-only select of long rows: both levels always run, so that the prefix is the whole value
-struct StopNever16 {
-    static __device__ __forceinline__ bool stops(uint32_t, uint32_t) { return false; }
-};
-
-// The wave's tile from body position q0 on, valid below `end`: a whole group by one 16-byte load, the others key by key.
-__device__ __forceinline__ void load_tile(const Row16& r, uint32_t q0, uint32_t end, uint32_t lane, const Key16Map& m, uint32_t (&t)[kRegs])
-{
-#pragma unroll
-    for (int j = 0; j < kRegs / 8; j++) {
-        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
-        if (q < end && end - q >= kGroupKeys) {
-            const uint4 v = *reinterpret_cast<const uint4*>(r.keys + r.head + q);
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                t[8 * j + 2 * i] = to_sortable16(w[i] & 0xFFFFu, m);
-                t[8 * j + 2 * i + 1] = to_sortable16(w[i] >> 16, m);
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                t[8 * j + e] = kNoKey;
-                if (q + (uint32_t)e < end) t[8 * j + e] = to_sortable16(r.keys[r.head + q + (uint32_t)e], m);
-            }
-        }
-    }
-}
-// head key `lane` of the row, for the one wave that owns the head
-__device__ __forceinline__ uint32_t load_head(const Row16& r, uint32_t lane, const Key16Map& m)
-{
-    return lane < r.head ? to_sortable16(r.keys[lane], m) : kNoKey;
-}
 
 struct Outputs {
     uint16_t* keys;       // [rows], the caller's 16-bit words
     uint32_t* idx;        // [rows] positions, may be null
     uint32_t rows;
     uint32_t* fault;
+    __device__ __forceinline__ size_t at(uint32_t row, uint32_t) const { return row; }   // locate_tile's store: one slot per row
 };
-
-// Locate within one tile held in registers (load_tile at q0; h: the head keys in front of it, kNoKey where there is none).  `base`:
-// the keys under the prefix before this tile in the row; it moves on past the tile.  If the `need`-th (1-based) such key of the row
-// lies in this tile, the lane that holds it stores it.  Returns whether it did (uniform over the group).  s_wc: WAVES words.
-template <int WAVES>
-__device__ __forceinline__ bool locate_tile(const uint32_t (&t)[kRegs], uint32_t h, uint32_t q0, const Row16& r, uint32_t prefix,
-                                            uint32_t shift, uint32_t need, uint32_t& base, volatile lds_u32* s_wc, uint32_t wave,
-                                            uint32_t lane, uint32_t row, const Outputs& o, const Key16Map& m)
-{
-    uint32_t em = (h >> shift) == prefix ? kHeadBit : 0u;   // the keys under the prefix (kNoKey never is)
-#pragma unroll
-    for (int i = 0; i < kRegs; i++) em |= (t[i] >> shift) == prefix ? 1u << i : 0u;
-    const uint32_t mine = wave_sum((uint32_t)__builtin_popcount(em));
-    uint32_t before = base, all = mine;
-    if (WAVES > 1) {
-        if (lane == 0u) s_wc[wave] = mine;
-        __syncthreads();
-        all = 0u;
-        for (uint32_t w = 0; w < (uint32_t)WAVES; w++) {
-            const uint32_t c = s_wc[w];
-            if (w < wave) before += c;
-            all += c;
-        }
-        __syncthreads();   // the next tile writes s_wc again
-    }
-    const bool here = base < need && need - base <= all;   // uniform
-    if (here) {
-        auto store = [&](uint32_t key, uint32_t pos) {
-            if (row < o.rows) {
-                o.keys[row] = (uint16_t)from_sortable16(key, m);
-                if (o.idx) o.idx[row] = pos;
-            }
-        };
-        // position order: the head keys by lane, then group j of lane 0, 1, .. 63, j = 0, 1
-        const uint32_t ch = em >> kRegs;
-        const uint32_t hi = wave_inclusive_scan(ch);
-        if (ch != 0u && before + hi == need) store(h, lane);
-        before += (uint32_t)__builtin_amdgcn_readlane((int)hi, 63);
-#pragma unroll
-        for (int j = 0; j < kRegs / 8; j++) {
-            const uint32_t g = (em >> (8 * j)) & 0xFFu, c = (uint32_t)__builtin_popcount(g);
-            const uint32_t incl = wave_inclusive_scan(c), lo = before + incl - c;
-            if (lo < need && need - lo <= c) {
-                uint32_t left = need - lo;   // 1 .. c: which of this group's matching keys
-                const uint32_t pos = r.head + q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    if (((g >> e) & 1u) != 0u && --left == 0u) store(t[8 * j + e], pos + (uint32_t)e);
-                }
-            }
-            before += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-    }
-    base += all;
-    return here;
-}
 
 // ---- short rows: one wavefront (WAVES = 1, eight rows per workgroup) or one workgroup (WAVES = 16) per row ----------------------
 struct ShortParams {
@@ -184,7 +89,7 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) kth16_short_kernel(co
         };
         const Selected sel = select_short<WAVES, 2, StopKth>(s_cnt, s_found, wave, lane, p.rank + 1u, p.out.fault, kKth16FaultCount, count);
         uint32_t base = 0u;
-        const bool found = locate_tile<WAVES>(t, h, q0, r, sel.prefix, sel.shift, sel.need, base, s_wc, wave, lane, row, p.out, p.map);
+        const bool found = locate_tile<WAVES>(t, h, q0, r, sel.prefix, sel.shift, sel.need, base, s_wc, wave, lane, row, 0u, p.out, p.map);
         if (!found && sel.need != 0u && wave == 0u && lane == 0u) atomicOr(p.out.fault, kKth16FaultLocate);
         group_sync<WAVES>();
     }
@@ -213,27 +118,12 @@ __global__ void __launch_bounds__(256) kth16_clear_kernel(uint32_t* ctl, uint32_
     clear_select(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, ctl, hist, hist_words, state, rows, need, Levels16::kNoLevel);
 }
 
-// One chunk of one row per workgroup: the digit of every key under the row's prefix, counted in LDS.  LEVEL 0: the top 11 bits
-// of every key; LEVEL 1: the low 5 bits of the keys whose top 11 are the prefix.
+// one chunk of one row per workgroup: the digit of every key under the row's prefix, counted in LDS (hist_level16)
 template <int LEVEL>
 __global__ void __launch_bounds__(kLongThreads) kth16_hist_kernel(const LongParams p)
 {
     __shared__ uint32_t s_hist[kBins];
-    hist_level(p, s_hist, [&](uint32_t row, uint32_t c, const uint4& st, uint32_t lane, uint32_t wave) __attribute__((always_inline)) {
-        const Row16 r = row_of(p.keys, row, p.cols);
-        const ChunkRange g = chunk_of(r, p.chunk, c);
-        auto count = [&](uint32_t key) __attribute__((always_inline)) {
-            const bool match = LEVEL == 0 ? key != kNoKey : (key >> Levels16::shift(0)) == st.x;
-            count_digit(s_hist, match, (key >> Levels16::shift(LEVEL)) & ((1u << Levels16::bits(LEVEL)) - 1u), lane);
-        };
-        if (c == 0u && wave == 0u) count(load_head(r, lane, p.map));   // uniform
-        for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
-            uint32_t t[kRegs];
-            load_tile(r, tile + wave * kWaveTile, g.hi, lane, p.map, t);
-#pragma unroll
-            for (int i = 0; i < kRegs; i++) count(t[i]);
-        }
-    });
+    hist_level16<LEVEL>(p, s_hist);
 }
 
 // One workgroup per row: walk the bins from the best end to the one that holds the wanted key; the counters go back to zero.
@@ -334,7 +224,7 @@ __global__ void __launch_bounds__(kLongThreads) kth16_locate_kernel(const LongPa
         uint32_t t[kRegs];
         load_tile(r, q0, g.hi, lane, p.map, t);
         const uint32_t h = (st.w == 0u && tile == g.lo && wave == 0u) ? load_head(r, lane, p.map) : kNoKey;   // uniform
-        found = locate_tile<(int)kLongWaves>(t, h, q0, r, st.x, st.y, st.z, base, s_wc, wave, lane, row, p.out, p.map);
+        found = locate_tile<(int)kLongWaves>(t, h, q0, r, st.x, st.y, st.z, base, s_wc, wave, lane, row, 0u, p.out, p.map);
     }
     if (!found && tid == 0u) atomicOr(p.out.fault, kKth16FaultLocate);
 }
@@ -343,11 +233,7 @@ __global__ void __launch_bounds__(kLongThreads) kth16_locate_kernel(const LongPa
 // counts fell short (its fault bit is set) or one no scan has visited -- never: nothing is stored for it.
 __global__ void __launch_bounds__(256) kth16_value_kernel(const LongParams p)
 {
-    for (uint32_t row = blockIdx.x * blockDim.x + threadIdx.x; row < p.out.rows; row += gridDim.x * blockDim.x) {
-        const uint4 st = p.state[row];
-        if (st.y == 0u && st.z != 0u) p.out.keys[row] = (uint16_t)from_sortable16(st.x & 0xFFFFu, p.map);
-        else atomicOr(p.out.fault, kKth16FaultLocate);
-    }
+    store_values16<0u>(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, p, kKth16FaultLocate, 0u);
 }
 
 // Workspace: control | row states (16 B per row) | counters [rows][2048] | chunk counts (4 B per chunk) -- the last two for rows

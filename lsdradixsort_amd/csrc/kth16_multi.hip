@@ -32,8 +32,8 @@
 // do not reach a rank, or a locate that finds no key, raise a fault bit instead -- never expected.  Nothing here ranks with the
 // returning add: the result does not depend on lsdsort_set_rank_method.
 //
-// load_tile, load_head and locate_tile are the 16-bit forms of kth16.hip (themselves topk16.hip's loaders), kept here as kth16.hip
-// and kth_multi.hip keep their own (one header once an ISA diff proves the move).
+// load_tile, load_head and locate_tile are select_tiles16.hpp's, shared with the other 16-bit row selects; Outputs::at gives
+// locate_tile the slot's place in the outputs.
 #define LSDSORT_BUILD 1
 #include "../../include/lsdsort.h"
 
@@ -41,23 +41,15 @@
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
 #include "radix_select.hpp"
+#include "select_tiles16.hpp"
 
 namespace lsd {
 namespace {
 
 constexpr uint32_t kKth16FaultCount = 1024u;    // fault word: the digit counts of a row do not reach a rank (never expected)
 constexpr uint32_t kKth16FaultLocate = 2048u;   // fault word: nothing located for a slot, or a values-only state is no whole value
-constexpr uint32_t kNoKey = 0xFFFFFFFFu;        // a sortable value is below 65536
-constexpr uint32_t kHeadBit = 1u << kRegs;      // match mask: the head register
-constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
 constexpr int kMaxSlots = LSDSORT_KTH_MAX_RANKS;
 constexpr uint32_t kBins1 = 1u << Levels16::bits(1);   // level 1: 32 counters per leader
-using Row16 = Row<uint16_t>;   // a lane holds two 16-byte groups of eight keys of its wave's tile
-
-// the values-only select of long rows: both levels always run, so that the prefix is the whole value
-struct StopNever16 {
-    static __device__ __forceinline__ bool stops(uint32_t, uint32_t) { return false; }
-};
 
 // need[j] = ranks[j] + 1: which key of the row slot j wants, 1-based.  A kernel argument; need_of() reads it by a chain of selects, so
 // that no kernel indexes its arguments by a run-time value.
@@ -72,99 +64,13 @@ __device__ __forceinline__ uint32_t need_of(const Needs& n, uint32_t j)
     return v;
 }
 
-// The wave's tile from body position q0 on, valid below `end`: a whole group by one 16-byte load, the others key by key.
-__device__ __forceinline__ void load_tile(const Row16& r, uint32_t q0, uint32_t end, uint32_t lane, const Key16Map& m, uint32_t (&t)[kRegs])
-{
-#pragma unroll
-    for (int j = 0; j < kRegs / 8; j++) {
-        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
-        if (q < end && end - q >= kGroupKeys) {
-            const uint4 v = *reinterpret_cast<const uint4*>(r.keys + r.head + q);
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                t[8 * j + 2 * i] = to_sortable16(w[i] & 0xFFFFu, m);
-                t[8 * j + 2 * i + 1] = to_sortable16(w[i] >> 16, m);
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                t[8 * j + e] = kNoKey;
-                if (q + (uint32_t)e < end) t[8 * j + e] = to_sortable16(r.keys[r.head + q + (uint32_t)e], m);
-            }
-        }
-    }
-}
-// head key `lane` of the row, for the one wave that owns the head
-__device__ __forceinline__ uint32_t load_head(const Row16& r, uint32_t lane, const Key16Map& m)
-{
-    return lane < r.head ? to_sortable16(r.keys[lane], m) : kNoKey;
-}
-
 struct Outputs {
     uint16_t* keys;       // [rows][slots], the caller's 16-bit words
     uint32_t* idx;        // [rows][slots] positions, may be null
     uint32_t rows, slots;
     uint32_t* fault;
+    __device__ __forceinline__ size_t at(uint32_t row, uint32_t slot) const { return (size_t)row * slots + slot; }   // locate_tile's store
 };
-
-// Locate within one tile held in registers (load_tile at q0; h: the head keys in front of it, kNoKey where there is none).  `base`:
-// the keys under the prefix before this tile in the row; it moves on past the tile.  If the `need`-th (1-based) such key of the row
-// lies in this tile, the lane that holds it stores it into slot `slot` of the row.  Returns whether it did (uniform over the group).
-// s_wc: WAVES words.
-template <int WAVES>
-__device__ __forceinline__ bool locate_tile(const uint32_t (&t)[kRegs], uint32_t h, uint32_t q0, const Row16& r, uint32_t prefix,
-                                            uint32_t shift, uint32_t need, uint32_t& base, volatile lds_u32* s_wc, uint32_t wave,
-                                            uint32_t lane, uint32_t row, uint32_t slot, const Outputs& o, const Key16Map& m)
-{
-    uint32_t em = (h >> shift) == prefix ? kHeadBit : 0u;   // the keys under the prefix (kNoKey never is)
-#pragma unroll
-    for (int i = 0; i < kRegs; i++) em |= (t[i] >> shift) == prefix ? 1u << i : 0u;
-    const uint32_t mine = wave_sum((uint32_t)__builtin_popcount(em));
-    uint32_t before = base, all = mine;
-    if (WAVES > 1) {
-        if (lane == 0u) s_wc[wave] = mine;
-        __syncthreads();
-        all = 0u;
-        for (uint32_t w = 0; w < (uint32_t)WAVES; w++) {
-            const uint32_t c = s_wc[w];
-            if (w < wave) before += c;
-            all += c;
-        }
-        __syncthreads();   // the next tile writes s_wc again
-    }
-    const bool here = base < need && need - base <= all;   // uniform
-    if (here) {
-        auto store = [&](uint32_t key, uint32_t pos) {
-            if (row < o.rows) {
-                const size_t at = (size_t)row * o.slots + slot;
-                o.keys[at] = (uint16_t)from_sortable16(key, m);
-                if (o.idx) o.idx[at] = pos;
-            }
-        };
-        // position order: the head keys by lane, then group j of lane 0, 1, .. 63, j = 0, 1
-        const uint32_t ch = em >> kRegs;
-        const uint32_t hi = wave_inclusive_scan(ch);
-        if (ch != 0u && before + hi == need) store(h, lane);
-        before += (uint32_t)__builtin_amdgcn_readlane((int)hi, 63);
-#pragma unroll
-        for (int j = 0; j < kRegs / 8; j++) {
-            const uint32_t g = (em >> (8 * j)) & 0xFFu, c = (uint32_t)__builtin_popcount(g);
-            const uint32_t incl = wave_inclusive_scan(c), lo = before + incl - c;
-            if (lo < need && need - lo <= c) {
-                uint32_t left = need - lo;   // 1 .. c: which of this group's matching keys
-                const uint32_t pos = r.head + q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    if (((g >> e) & 1u) != 0u && --left == 0u) store(t[8 * j + e], pos + (uint32_t)e);
-                }
-            }
-            before += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-    }
-    base += all;
-    return here;
-}
 
 // ---- short rows: one wavefront (WAVES = 1, eight rows per workgroup) or one workgroup (WAVES = 16) per row ----------------------
 struct ShortParams {

@@ -9,9 +9,9 @@
 // with Levels16, in kth16.hip's three size classes:
 //   cols <= kWaveSegCap (1024)      one wavefront per row, eight rows per workgroup; `need` is loaded once per row, uniformly
 //   cols <= kLocalSortCap (16384)   one workgroup of 16 wavefronts per row: the same
-//   longer                          many workgroups per row.  This unit's clear kernel writes the row states from the device array
-//                                   (select_long takes one `need` for all rows), then the two levels run.  Per-row rank: count,
-//                                   pick and locate, or without an index buffer both levels and the value kernel, as in kth16.hip.
+//   longer                          many workgroups per row.  select_long launches this unit's clear kernel, which writes the row
+//                                   states from the device array, then the two levels.  Per-row rank: count, pick and locate, or
+//                                   without an index buffer both levels and the value kernel, as in kth16.hip.
 //                                   Filter: both levels (the state then holds the whole threshold), then ONE apply kernel over the
 //                                   same chunks reads a tile, compares and stores.
 // The filter's short kernels compare and store the registers the select ran on: one read and one write of the row (4 B/key by byte
@@ -26,10 +26,12 @@
 // (pick, or the value kernel) reports kRowkFaultRank instead.  The filter has no such rank: k_r == 0 or k_r >= cols is "filter
 // off" (state w = kOffRow), the row is copied, or left alone in place.
 //
-// load_tile, load_head and locate_tile are this unit's copy of kth16.hip's, count / pick / locate / value follow kth16.hip's line by
-// line (one header once an ISA diff proves the move).  Every launch is sized from (rows, cols) and from whether
-// an index buffer was given; phases are ordered by kernel boundaries; every store into the outputs is guarded by row < rows and
-// stays within the row.  Nothing here ranks with the returning add: the result does not depend on lsdsort_set_rank_method.
+// The loaders, locate_tile, the filter's stores, the hist-level body and the value kernel's body are select_tiles16.hpp's, shared
+// with the other 16-bit row selects.  The count, pick and locate kernels still follow kth16.hip's line by line, pick with the
+// bad-rank branch in front: as shared bodies they compile to other code.  Every launch is sized from (rows,
+// cols) and from whether an index buffer was given; phases are ordered by kernel boundaries; every store into the outputs is guarded
+// by row < rows and stays within the row.  Nothing here ranks with the returning add: the result does not depend on
+// lsdsort_set_rank_method.
 #define LSDSORT_BUILD 1
 #include "../../include/lsdsort.h"
 
@@ -37,6 +39,7 @@
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
 #include "radix_select.hpp"
+#include "select_tiles16.hpp"
 
 namespace lsd {
 namespace {
@@ -44,139 +47,15 @@ namespace {
 constexpr uint32_t kRowkFaultCount = 1024u;    // fault word: the digit counts of a row do not reach the rank (never expected)
 constexpr uint32_t kRowkFaultLocate = 2048u;   // fault word: no key was located for a row (never expected; nothing stored)
 constexpr uint32_t kRowkFaultRank = 4096u;     // fault word: d_ranks[r] >= cols for some row (the caller's error; nothing stored for it)
-constexpr uint32_t kNoKey = 0xFFFFFFFFu;       // a sortable value is below 65536
-constexpr uint32_t kHeadBit = 1u << kRegs;     // match mask: the head register
-constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
 constexpr uint32_t kBadRow = 2u, kOffRow = 3u; // row state w: done from the start (1: the select stopped or fell short)
-using Row16 = Row<uint16_t>;   // a lane holds two 16-byte groups of eight keys of its wave's tile
-
-// the values-only select of long rows and the filter's: both levels always run, so that the prefix is the whole value
-struct StopNever16 {
-    static __device__ __forceinline__ bool stops(uint32_t, uint32_t) { return false; }
-};
-
-// The wave's tile from body position q0 on, valid below `end`: a whole group by one 16-byte load, the others key by key.
-__device__ __forceinline__ void load_tile(const Row16& r, uint32_t q0, uint32_t end, uint32_t lane, const Key16Map& m, uint32_t (&t)[kRegs])
-{
-#pragma unroll
-    for (int j = 0; j < kRegs / 8; j++) {
-        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
-        if (q < end && end - q >= kGroupKeys) {
-            const uint4 v = *reinterpret_cast<const uint4*>(r.keys + r.head + q);
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                t[8 * j + 2 * i] = to_sortable16(w[i] & 0xFFFFu, m);
-                t[8 * j + 2 * i + 1] = to_sortable16(w[i] >> 16, m);
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                t[8 * j + e] = kNoKey;
-                if (q + (uint32_t)e < end) t[8 * j + e] = to_sortable16(r.keys[r.head + q + (uint32_t)e], m);
-            }
-        }
-    }
-}
-// head key `lane` of the row, for the one wave that owns the head
-__device__ __forceinline__ uint32_t load_head(const Row16& r, uint32_t lane, const Key16Map& m)
-{
-    return lane < r.head ? to_sortable16(r.keys[lane], m) : kNoKey;
-}
 
 struct Outputs {
     uint16_t* keys;       // [rows], the caller's 16-bit words
     uint32_t* idx;        // [rows] positions, may be null
     uint32_t rows;
     uint32_t* fault;
+    __device__ __forceinline__ size_t at(uint32_t row, uint32_t) const { return row; }   // locate_tile's store: one slot per row
 };
-
-// Locate within one tile held in registers (load_tile at q0; h: the head keys in front of it, kNoKey where there is none).  `base`:
-// the keys under the prefix before this tile in the row; it moves on past the tile.  If the `need`-th (1-based) such key of the row
-// lies in this tile, the lane that holds it stores it.  Returns whether it did (uniform over the group).  s_wc: WAVES words.
-template <int WAVES>
-__device__ __forceinline__ bool locate_tile(const uint32_t (&t)[kRegs], uint32_t h, uint32_t q0, const Row16& r, uint32_t prefix,
-                                            uint32_t shift, uint32_t need, uint32_t& base, volatile lds_u32* s_wc, uint32_t wave,
-                                            uint32_t lane, uint32_t row, const Outputs& o, const Key16Map& m)
-{
-    uint32_t em = (h >> shift) == prefix ? kHeadBit : 0u;   // the keys under the prefix (kNoKey never is)
-#pragma unroll
-    for (int i = 0; i < kRegs; i++) em |= (t[i] >> shift) == prefix ? 1u << i : 0u;
-    const uint32_t mine = wave_sum((uint32_t)__builtin_popcount(em));
-    uint32_t before = base, all = mine;
-    if (WAVES > 1) {
-        if (lane == 0u) s_wc[wave] = mine;
-        __syncthreads();
-        all = 0u;
-        for (uint32_t w = 0; w < (uint32_t)WAVES; w++) {
-            const uint32_t c = s_wc[w];
-            if (w < wave) before += c;
-            all += c;
-        }
-        __syncthreads();   // the next tile writes s_wc again
-    }
-    const bool here = base < need && need - base <= all;   // uniform
-    if (here) {
-        auto store = [&](uint32_t key, uint32_t pos) {
-            if (row < o.rows) {
-                o.keys[row] = (uint16_t)from_sortable16(key, m);
-                if (o.idx) o.idx[row] = pos;
-            }
-        };
-        // position order: the head keys by lane, then group j of lane 0, 1, .. 63, j = 0, 1
-        const uint32_t ch = em >> kRegs;
-        const uint32_t hi = wave_inclusive_scan(ch);
-        if (ch != 0u && before + hi == need) store(h, lane);
-        before += (uint32_t)__builtin_amdgcn_readlane((int)hi, 63);
-#pragma unroll
-        for (int j = 0; j < kRegs / 8; j++) {
-            const uint32_t g = (em >> (8 * j)) & 0xFFu, c = (uint32_t)__builtin_popcount(g);
-            const uint32_t incl = wave_inclusive_scan(c), lo = before + incl - c;
-            if (lo < need && need - lo <= c) {
-                uint32_t left = need - lo;   // 1 .. c: which of this group's matching keys
-                const uint32_t pos = r.head + q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    if (((g >> e) & 1u) != 0u && --left == 0u) store(t[8 * j + e], pos + (uint32_t)e);
-                }
-            }
-            before += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-    }
-    base += all;
-    return here;
-}
-
-// The filter's store of one tile held in registers (load_tile at q0, valid below `end`) into the destination row `orow`: a key is
-// kept where (key >> shift) <= prefix and becomes `fill` elsewhere.  `vec`: the destination row has the source row's 16-byte phase,
-// so a whole group is one 16-byte store at the address the load had; otherwise, and behind the last whole group, key by key.
-// Every store is below `end`, that is inside the row.
-__device__ __forceinline__ void store_tile(uint16_t* orow, bool vec, const Row16& r, uint32_t q0, uint32_t end, uint32_t lane,
-                                           const uint32_t (&t)[kRegs], uint32_t prefix, uint32_t shift, uint32_t fill, const Key16Map& m)
-{
-#pragma unroll
-    for (int j = 0; j < kRegs / 8; j++) {
-        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
-        if (q >= end) continue;
-        uint32_t w[8];
-#pragma unroll
-        for (int e = 0; e < 8; e++) w[e] = (t[8 * j + e] >> shift) <= prefix ? from_sortable16(t[8 * j + e], m) & 0xFFFFu : fill;
-        if (vec && end - q >= kGroupKeys) {
-            *reinterpret_cast<uint4*>(orow + r.head + q) = make_uint4(w[0] | (w[1] << 16), w[2] | (w[3] << 16), w[4] | (w[5] << 16), w[6] | (w[7] << 16));
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; e++)
-                if (q + (uint32_t)e < end) orow[r.head + q + (uint32_t)e] = (uint16_t)w[e];
-        }
-    }
-}
-// the head keys of the row, by the one wave that owns them
-__device__ __forceinline__ void store_head(uint16_t* orow, const Row16& r, uint32_t lane, uint32_t h, uint32_t prefix, uint32_t shift,
-                                           uint32_t fill, const Key16Map& m)
-{
-    if (lane < r.head) orow[lane] = (uint16_t)((h >> shift) <= prefix ? from_sortable16(h, m) : fill);
-}
-__device__ __forceinline__ bool same_phase(const void* a, const void* b) { return (((uintptr_t)a ^ (uintptr_t)b) & 15u) == 0u; }
 
 // ---- short rows: one wavefront (WAVES = 1, eight rows per workgroup) or one workgroup (WAVES = 16) per row ----------------------
 struct ShortParams {
@@ -224,7 +103,7 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) kth16r_short_kernel(c
         };
         const Selected sel = select_short<WAVES, 2, StopKth>(s_cnt, s_found, wave, lane, rank + 1u, p.out.fault, kRowkFaultCount, count);
         uint32_t base = 0u;
-        const bool found = locate_tile<WAVES>(t, h, q0, r, sel.prefix, sel.shift, sel.need, base, s_wc, wave, lane, row, p.out, p.map);
+        const bool found = locate_tile<WAVES>(t, h, q0, r, sel.prefix, sel.shift, sel.need, base, s_wc, wave, lane, row, 0u, p.out, p.map);
         if (!found && sel.need != 0u && wave == 0u && lane == 0u) atomicOr(p.out.fault, kRowkFaultLocate);
         group_sync<WAVES>();
     }
@@ -313,27 +192,12 @@ __global__ void __launch_bounds__(256) kth16r_clear_kernel(uint32_t* ctl, uint32
     }
 }
 
-// One chunk of one row per workgroup: the digit of every key under the row's prefix, counted in LDS.  LEVEL 0: the top 11 bits
-// of every key; LEVEL 1: the low 5 bits of the keys whose top 11 are the prefix.  A done row returns at once.
+// one chunk of one row per workgroup: the digit of every key under the row's prefix, counted in LDS (hist_level16); a done row returns at once
 template <int LEVEL>
 __global__ void __launch_bounds__(kLongThreads) kth16r_hist_kernel(const LongParams p)
 {
     __shared__ uint32_t s_hist[kBins];
-    hist_level(p, s_hist, [&](uint32_t row, uint32_t c, const uint4& st, uint32_t lane, uint32_t wave) __attribute__((always_inline)) {
-        const Row16 r = row_of(p.keys, row, p.cols);
-        const ChunkRange g = chunk_of(r, p.chunk, c);
-        auto count = [&](uint32_t key) __attribute__((always_inline)) {
-            const bool match = LEVEL == 0 ? key != kNoKey : (key >> Levels16::shift(0)) == st.x;
-            count_digit(s_hist, match, (key >> Levels16::shift(LEVEL)) & ((1u << Levels16::bits(LEVEL)) - 1u), lane);
-        };
-        if (c == 0u && wave == 0u) count(load_head(r, lane, p.map));   // uniform
-        for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
-            uint32_t t[kRegs];
-            load_tile(r, tile + wave * kWaveTile, g.hi, lane, p.map, t);
-#pragma unroll
-            for (int i = 0; i < kRegs; i++) count(t[i]);
-        }
-    });
+    hist_level16<LEVEL>(p, s_hist);
 }
 
 // One workgroup per row: walk the bins from the best end to the one that holds the wanted key; the counters go back to zero.
@@ -441,7 +305,7 @@ __global__ void __launch_bounds__(kLongThreads) kth16r_locate_kernel(const LongP
         uint32_t t[kRegs];
         load_tile(r, q0, g.hi, lane, p.map, t);
         const uint32_t h = (st.w == 0u && tile == g.lo && wave == 0u) ? load_head(r, lane, p.map) : kNoKey;   // uniform
-        found = locate_tile<(int)kLongWaves>(t, h, q0, r, st.x, st.y, st.z, base, s_wc, wave, lane, row, p.out, p.map);
+        found = locate_tile<(int)kLongWaves>(t, h, q0, r, st.x, st.y, st.z, base, s_wc, wave, lane, row, 0u, p.out, p.map);
     }
     if (!found && tid == 0u) atomicOr(p.out.fault, kRowkFaultLocate);
 }
@@ -451,11 +315,7 @@ __global__ void __launch_bounds__(kLongThreads) kth16r_locate_kernel(const LongP
 // for either.
 __global__ void __launch_bounds__(256) kth16r_value_kernel(const LongParams p)
 {
-    for (uint32_t row = blockIdx.x * blockDim.x + threadIdx.x; row < p.out.rows; row += gridDim.x * blockDim.x) {
-        const uint4 st = p.state[row];
-        if (st.y == 0u && st.z != 0u) p.out.keys[row] = (uint16_t)from_sortable16(st.x & 0xFFFFu, p.map);
-        else atomicOr(p.out.fault, (st.y == Levels16::kNoLevel && st.w == kBadRow) ? kRowkFaultRank : kRowkFaultLocate);
-    }
+    store_values16<kBadRow>(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, p, kRowkFaultLocate, kRowkFaultRank);
 }
 
 // The filter over one chunk of one row per workgroup, the chunks of the select: after both levels the state holds the row's whole
@@ -489,31 +349,19 @@ using RowkLayout = SelectLayout;
 RowkLayout perrow_layout(size_t rows, size_t cols) { return select_layout(rows, cols, false, 4); }
 RowkLayout filter_layout(size_t rows, size_t cols) { return select_layout(rows, cols, false, 0); }
 
-// The long rows' select with the needs from the device array: radix_select.hpp's select_long with this unit's clear kernel.
-template <bool FILTER, class Stop0>
-int select_long_rowk(LongParams& lp, const uint16_t* keys, size_t rows, size_t cols, const uint32_t* ranks, char* ws, const RowkLayout& L,
-                     hipStream_t stream)
+// select_long's clear launch with the needs from the device array, and the two level sequences: the select that stops at one key,
+// and the one that runs both levels whatever it finds (values only, and the filter: the state then holds the whole value).
+template <bool FILTER>
+auto clear_from(const uint32_t* ranks, size_t cols, hipStream_t stream)
 {
-    const Chunks ch = chunks_for(rows, cols);
-    lp.keys = keys;
-    lp.cols = (uint32_t)cols;
-    lp.chunk = ch.chunk;
-    lp.chunks = ch.per_row;
-    lp.chunk_cap = (uint32_t)chunk_cap_for(cols);
-    lp.state = reinterpret_cast<uint4*>(ws + L.state);
-    lp.hist = reinterpret_cast<uint32_t*>(ws + L.hist);
-    lp.counts = reinterpret_cast<uint32_t*>(ws + L.counts);
-    if (lp.chunks > lp.chunk_cap) return LSDSORT_ERR_INVALID_ARG;   // never: chunks are at least kMinChunk keys
-    const uint32_t grid = (uint32_t)(rows * lp.chunks), row_grid = (uint32_t)rows;
-    hipLaunchKernelGGL(kth16r_clear_kernel<FILTER>, dim3(grid_for(rows * kBins, 1024, 4096)), dim3(256), 0, stream,
-                       reinterpret_cast<uint32_t*>(ws), lp.hist, (uint32_t)(rows * kBins), lp.state, (uint32_t)rows, ranks, (uint32_t)cols);
-    hipLaunchKernelGGL(kth16r_hist_kernel<0>, dim3(grid), dim3(kLongThreads), 0, stream, lp);
-    hipLaunchKernelGGL((kth16r_scan_kernel<0, Stop0>), dim3(row_grid), dim3(256), 0, stream, lp);
-    hipLaunchKernelGGL(kth16r_hist_kernel<1>, dim3(grid), dim3(kLongThreads), 0, stream, lp);
-    hipLaunchKernelGGL((kth16r_scan_kernel<1, StopKth>), dim3(row_grid), dim3(256), 0, stream, lp);
-    LSD_HIP(hipGetLastError());
-    return LSDSORT_OK;
+    return [=](dim3 grid, dim3 block, uint32_t* ctl, uint32_t* hist, uint32_t hist_words, uint4* state, uint32_t rows) {
+        hipLaunchKernelGGL(kth16r_clear_kernel<FILTER>, grid, block, 0, stream, ctl, hist, hist_words, state, rows, ranks, (uint32_t)cols);
+    };
 }
+const LevelKernels<LongParams> kLevelsKth[] = {{kth16r_hist_kernel<0>, kth16r_scan_kernel<0, StopKth>},
+                                               {kth16r_hist_kernel<1>, kth16r_scan_kernel<1, StopKth>}};
+const LevelKernels<LongParams> kLevelsWhole[] = {{kth16r_hist_kernel<0>, kth16r_scan_kernel<0, StopNever16>},
+                                                 {kth16r_hist_kernel<1>, kth16r_scan_kernel<1, StopKth>}};
 
 int run_perrow(const uint16_t* keys, size_t rows, size_t cols, const uint32_t* ranks, const Key16Map& map, uint16_t* out_keys,
                uint32_t* out_idx, char* ws, const RowkLayout& L, hipStream_t stream)
@@ -535,12 +383,12 @@ int run_perrow(const uint16_t* keys, size_t rows, size_t cols, const uint32_t* r
     lp.map = map;
     lp.out = out;
     if (!out_idx) {   // values only: both levels, then the prefix is the value
-        LSD_TRY((select_long_rowk<false, StopNever16>(lp, keys, rows, cols, ranks, ws, L, stream)));
+        LSD_TRY(select_long(lp, keys, rows, cols, ws, L, clear_from<false>(ranks, cols, stream), kLevelsWhole, stream));
         hipLaunchKernelGGL(kth16r_value_kernel, dim3(grid_for(rows, 256, 1024)), dim3(256), 0, stream, lp);
         LSD_HIP(hipGetLastError());
         return LSDSORT_OK;
     }
-    LSD_TRY((select_long_rowk<false, StopKth>(lp, keys, rows, cols, ranks, ws, L, stream)));
+    LSD_TRY(select_long(lp, keys, rows, cols, ws, L, clear_from<false>(ranks, cols, stream), kLevelsKth, stream));
     const uint32_t grid = (uint32_t)(rows * lp.chunks), row_grid = (uint32_t)rows;
     hipLaunchKernelGGL(kth16r_count_kernel, dim3(grid), dim3(kLongThreads), 0, stream, lp);
     hipLaunchKernelGGL(kth16r_pick_kernel, dim3(row_grid), dim3(256), 0, stream, lp);
@@ -570,7 +418,7 @@ int run_filter(const uint16_t* keys, size_t rows, size_t cols, const uint32_t* k
     lp.out = out;
     lp.dst = dst;
     lp.fill = fill;
-    LSD_TRY((select_long_rowk<true, StopNever16>(lp, keys, rows, cols, k, ws, L, stream)));
+    LSD_TRY(select_long(lp, keys, rows, cols, ws, L, clear_from<true>(k, cols, stream), kLevelsWhole, stream));
     hipLaunchKernelGGL(topk16f_apply_kernel, dim3((uint32_t)(rows * lp.chunks)), dim3(kLongThreads), 0, stream, lp);
     LSD_HIP(hipGetLastError());
     return LSDSORT_OK;

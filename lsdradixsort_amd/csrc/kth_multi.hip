@@ -27,24 +27,22 @@
 // by row < rows; positions come from position-ordered scans.  Counts that do not reach a rank, or a locate that finds no key, raise
 // a fault bit instead -- never expected.  Nothing here needs the returning-add rank form.
 //
-// load_tile, load_head and locate_tile are the 32-bit forms of kth.hip, kept here as kth16.hip keeps its own.
+// load_tile, load_head and locate_tile are select_tiles32.hpp's, shared with kth.hip; Outputs::at gives locate_tile the slot's place
+// in the outputs.
 #define LSDSORT_BUILD 1
 #include "../../include/lsdsort.h"
 
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
 #include "radix_select.hpp"
+#include "select_tiles32.hpp"
 
 namespace lsd {
 namespace {
 
 constexpr uint32_t kKthFaultCount = 1024u;    // fault word: the digit counts of a row do not reach a rank (never expected)
 constexpr uint32_t kKthFaultLocate = 2048u;   // fault word: no key was located for a slot (never expected; nothing stored)
-constexpr uint32_t kGroup = 4;                // keys of one 16-byte load
-constexpr uint32_t kHeadBit = 1u << kRegs;    // validity mask: the head register
-constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
 constexpr int kMaxSlots = LSDSORT_KTH_MAX_RANKS;
-using Row32 = Row<uint32_t>;   // a lane holds four 16-byte groups of four keys of its wave's tile
 
 // need[j] = ranks[j] + 1: which key of the row slot j wants, 1-based.  A kernel argument; need_of() reads it by a chain of selects, so
 // that no kernel indexes its arguments by a run-time value.
@@ -59,108 +57,13 @@ __device__ __forceinline__ uint32_t need_of(const Needs& n, uint32_t j)
     return v;
 }
 
-// The wave's tile from body position q0 (a multiple of four) on, valid below `end`: a whole group by one 16-byte load, the others
-// key by key.  Returns the validity mask of the sixteen registers; a register without a key holds zero and its bit is clear.
-__device__ __forceinline__ uint32_t load_tile(const Row32& r, uint32_t q0, uint32_t end, uint32_t lane, const KeyTransform& xf,
-                                              uint32_t (&t)[kRegs])
-{
-    uint32_t vm = 0u;
-#pragma unroll
-    for (int j = 0; j < kRegs / 4; j++) {
-        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroup;
-        if (q < end && end - q >= kGroup) {
-            const uint4 v = *reinterpret_cast<const uint4*>(r.keys + r.head + q);
-            t[4 * j] = to_sortable(v.x, xf);
-            t[4 * j + 1] = to_sortable(v.y, xf);
-            t[4 * j + 2] = to_sortable(v.z, xf);
-            t[4 * j + 3] = to_sortable(v.w, xf);
-            vm |= 0xFu << (4 * j);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                t[4 * j + e] = 0u;
-                if (q < end && q + (uint32_t)e < end) {
-                    t[4 * j + e] = to_sortable(r.keys[r.head + q + (uint32_t)e], xf);
-                    vm |= 1u << (4 * j + e);
-                }
-            }
-        }
-    }
-    return vm;
-}
-// head key `lane` of the row, for the one wave that owns the head: its validity bit, and the key into h
-__device__ __forceinline__ uint32_t load_head(const Row32& r, uint32_t lane, const KeyTransform& xf, uint32_t& h)
-{
-    h = 0u;
-    if (lane >= r.head) return 0u;
-    h = to_sortable(r.keys[lane], xf);
-    return kHeadBit;
-}
-
 struct Outputs {
     uint32_t* keys;       // [rows][slots], raw keys
     uint32_t* idx;        // [rows][slots] positions, may be null
     uint32_t rows, slots;
     uint32_t* fault;
+    __device__ __forceinline__ size_t at(uint32_t row, uint32_t slot) const { return (size_t)row * slots + slot; }   // locate_tile's store
 };
-
-// Locate within one tile held in registers (load_tile at q0, validity mask vm; with kHeadBit in vm of some lanes: the head keys h
-// in front of it).  `base`: the keys under the prefix before this tile in the row; it moves on past the tile.  If the `need`-th
-// (1-based) such key of the row lies in this tile, the lane that holds it stores it into slot `slot` of the row.  Returns whether it
-// did (uniform over the group).  s_wc: WAVES words.
-template <int WAVES>
-__device__ __forceinline__ bool locate_tile(const uint32_t (&t)[kRegs], uint32_t h, uint32_t vm, uint32_t q0, const Row32& r, uint32_t prefix,
-                                            uint32_t shift, uint32_t need, uint32_t& base, volatile lds_u32* s_wc, uint32_t wave,
-                                            uint32_t lane, uint32_t row, uint32_t slot, const Outputs& o, const KeyTransform& xf)
-{
-    uint32_t em = ((vm & kHeadBit) != 0u && (h >> shift) == prefix) ? kHeadBit : 0u;   // the keys under the prefix
-#pragma unroll
-    for (int i = 0; i < kRegs; i++) em |= (((vm >> i) & 1u) != 0u && (t[i] >> shift) == prefix) ? 1u << i : 0u;
-    const uint32_t mine = wave_sum((uint32_t)__builtin_popcount(em));
-    uint32_t before = base, all = mine;
-    if (WAVES > 1) {
-        if (lane == 0u) s_wc[wave] = mine;
-        __syncthreads();
-        all = 0u;
-        for (uint32_t w = 0; w < (uint32_t)WAVES; w++) {
-            const uint32_t c = s_wc[w];
-            if (w < wave) before += c;
-            all += c;
-        }
-        __syncthreads();   // the next tile writes s_wc again
-    }
-    const bool here = base < need && need - base <= all;   // uniform
-    if (here) {
-        auto store = [&](uint32_t key, uint32_t pos) {
-            if (row < o.rows) {
-                const size_t at = (size_t)row * o.slots + slot;
-                o.keys[at] = from_sortable(key, xf);
-                if (o.idx) o.idx[at] = pos;
-            }
-        };
-        // position order: the head keys by lane, then group j of lane 0, 1, .. 63, j = 0 .. 3
-        const uint32_t ch = em >> kRegs;
-        const uint32_t hi = wave_inclusive_scan(ch);
-        if (ch != 0u && before + hi == need) store(h, lane);
-        before += (uint32_t)__builtin_amdgcn_readlane((int)hi, 63);
-#pragma unroll
-        for (int j = 0; j < kRegs / 4; j++) {
-            const uint32_t g = (em >> (4 * j)) & 0xFu, c = (uint32_t)__builtin_popcount(g);
-            const uint32_t incl = wave_inclusive_scan(c), lo = before + incl - c;
-            if (lo < need && need - lo <= c) {
-                uint32_t left = need - lo;   // 1 .. c: which of this group's matching keys
-                const uint32_t pos = r.head + q0 + ((uint32_t)j * 64u + lane) * kGroup;
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    if (((g >> e) & 1u) != 0u && --left == 0u) store(t[4 * j + e], pos + (uint32_t)e);
-                }
-            }
-            before += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-    }
-    base += all;
-    return here;
-}
 
 // ---- short rows: one wavefront (WAVES = 1, eight rows per workgroup) or one workgroup (WAVES = 16) per row ----------------------
 struct ShortParams {

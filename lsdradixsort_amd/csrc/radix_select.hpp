@@ -5,8 +5,9 @@
 // stop where the stop rule says the rest is decided.  Three size classes (those of segmented.hip, by cols): one wavefront per row
 // and one workgroup per row (select_short: the row in registers, 8-bit digits in 256 LDS counters), and many chunks per row
 // (clear_select, hist_level, scan_level: wider digits, kBins counters per row in the workspace, one launch per level and step).
-// A unit brings how a tile is loaded and what marks a missing key (the counting functors), what it does with (prefix, shift,
-// need) afterwards, its __global__ wrappers and its entries.  Internal linkage: every unit's kernels keep their own symbols.
+// A unit brings how a tile is loaded and what marks a missing key (the counting functors; the loaders themselves are
+// select_tiles16.hpp's and select_tiles32.hpp's), what it does with (prefix, shift, need) afterwards, its __global__ wrappers and
+// its entries.  Internal linkage: every unit's kernels keep their own symbols.
 #pragma once
 
 #include <stddef.h>
@@ -295,15 +296,15 @@ SortRouteLayout sort_route_layout(size_t rows, size_t sort_keys)
 
 // The long rows' select: the fields every unit's LongParams has (keys, cols, chunk, chunks, chunk_cap, state, hist, counts) are
 // filled from the layout, then the unit's clear kernel and, per level, its hist and scan kernels run.  Afterwards the row states
-// hold (prefix, shift, need) and lp serves the unit's own kernels.
-using ClearKernel = void (*)(uint32_t*, uint32_t*, uint32_t, uint4*, uint32_t, uint32_t);
+// hold (prefix, shift, need) and lp serves the unit's own kernels.  `clear(grid, block, ctl, hist, hist_words, state, rows)`
+// launches the unit's clear kernel: the control block, the counters, and the row states at no level with the rows' needs.
 template <class LP>
 struct LevelKernels {
     void (*hist)(const LP);
     void (*scan)(const LP);
 };
-template <class LP, class Key, size_t LEVELS>
-int select_long(LP& lp, const Key* keys, size_t rows, size_t cols, uint32_t need, char* ws, const SelectLayout& L, ClearKernel clear,
+template <class LP, class Key, size_t LEVELS, class Clear>
+int select_long(LP& lp, const Key* keys, size_t rows, size_t cols, char* ws, const SelectLayout& L, Clear clear,
                 const LevelKernels<LP> (&levels)[LEVELS], hipStream_t stream)
 {
     const Chunks ch = chunks_for(rows, cols);
@@ -316,14 +317,25 @@ int select_long(LP& lp, const Key* keys, size_t rows, size_t cols, uint32_t need
     lp.hist = reinterpret_cast<uint32_t*>(ws + L.hist);
     lp.counts = reinterpret_cast<decltype(lp.counts)>(ws + L.counts);
     if (lp.chunks > lp.chunk_cap) return LSDSORT_ERR_INVALID_ARG;   // never: chunks are at least kMinChunk keys
-    hipLaunchKernelGGL(clear, dim3(grid_for(rows * kBins, 1024, 4096)), dim3(256), 0, stream, reinterpret_cast<uint32_t*>(ws), lp.hist,
-                       (uint32_t)(rows * kBins), lp.state, (uint32_t)rows, need);
+    clear(dim3(grid_for(rows * kBins, 1024, 4096)), dim3(256), reinterpret_cast<uint32_t*>(ws), lp.hist, (uint32_t)(rows * kBins), lp.state,
+          (uint32_t)rows);
     for (const LevelKernels<LP>& level : levels) {
         hipLaunchKernelGGL(level.hist, dim3((uint32_t)(rows * lp.chunks)), dim3(kLongThreads), 0, stream, lp);
         hipLaunchKernelGGL(level.scan, dim3((uint32_t)rows), dim3(256), 0, stream, lp);
     }
     LSD_HIP(hipGetLastError());
     return LSDSORT_OK;
+}
+// one `need` for all rows, as a kernel argument: the clear kernel of topk.hip, topk16.hip, kth.hip and kth16.hip
+using ClearKernel = void (*)(uint32_t*, uint32_t*, uint32_t, uint4*, uint32_t, uint32_t);
+template <class LP, class Key, size_t LEVELS>
+int select_long(LP& lp, const Key* keys, size_t rows, size_t cols, uint32_t need, char* ws, const SelectLayout& L, ClearKernel clear,
+                const LevelKernels<LP> (&levels)[LEVELS], hipStream_t stream)
+{
+    auto launch = [&](dim3 grid, dim3 block, uint32_t* ctl, uint32_t* hist, uint32_t hist_words, uint4* state, uint32_t nrows) {
+        hipLaunchKernelGGL(clear, grid, block, 0, stream, ctl, hist, hist_words, state, nrows, need);
+    };
+    return select_long(lp, keys, rows, cols, ws, L, launch, levels, stream);
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
 // topk16.hip -- the k best 16-bit keys of every row of a [rows x cols] array, with their positions (lsdsort_topk16_device;
 // DESIGN.md section 6.6).  The 16-bit sibling of topk.hip: same contract, same three steps, same size classes, and the same select
-// skeleton, radix_select.hpp's (two rounds, or the levels of 11 and 5 bits).  This unit adds the loads (Row<uint16_t>, kNoKey for a
-// key that does not exist), compact_tile into the workspace, the count and write kernels, and the widen and finish kernels.
+// skeleton, radix_select.hpp's (two rounds, or the levels of 11 and 5 bits).  The loads are select_tiles16.hpp's (Row<uint16_t>,
+// kNoKey for a key that does not exist), shared with every 16-bit row select; this unit adds compact_tile into the workspace, the
+// count and write kernels, and the widen and finish kernels.
 //
 // No counterpart in the reference (it sorts one whole array of uint32, LSDRadixSort.cu:839-910).  Row r's result is the first k
 // items of the stable sort of the row in the requested order.  "Best" is always "smallest sortable value": the map of
@@ -15,11 +16,7 @@
 //            stable, and its tiers of up to 16384 keys skip the two dead high digits on their own.  k = 1 needs no sort.
 //   finish   one small kernel un-maps, narrows into d_out_keys and copies the positions into d_out_idx.
 //
-// Key reads.  A row starts 2 r cols bytes past d_keys, at any even offset within a 16-byte line.  Every kernel therefore splits
-// EACH ROW by address (Row): `head` keys in front of the row's first 16-byte line (0..7), read one by one, and the `body` from that
-// line on, read as 16-byte groups of eight keys; the last group of a row (or chunk) that is not whole is read one by one too.
-// A lane holds two groups of a tile of its wave: register 8 j + e is body position q0 + 8 (64 j + lane) + e.  A key that does not
-// exist is kNoKey, which no (prefix, shift) of a select matches.
+// Key reads: select_tiles16.hpp (head keys one by one, the body in 16-byte groups of eight, two groups per lane and tile).
 // Size classes (those of topk.hip, by cols):
 //   cols <= kWaveSegCap (1024)      one wavefront per row: the row in its registers, two rounds of 8-bit digits in its LDS slice
 //   cols <= kLocalSortCap (16384)   one workgroup per row: the same with 16 wavefronts
@@ -39,42 +36,12 @@
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
 #include "radix_select.hpp"
+#include "select_tiles16.hpp"
 
 namespace lsd {
 namespace {
 
-constexpr uint32_t kNoKey = 0xFFFFFFFFu;      // a sortable value is below 65536
 constexpr int kPlainThreads = 256;
-using Row16 = Row<uint16_t>;   // a lane holds two 16-byte groups of eight keys of its wave's tile
-
-// The wave's tile from body position q0 on, valid below `end`: a whole group by one 16-byte load, the others key by key.
-__device__ __forceinline__ void load_tile(const Row16& r, uint32_t q0, uint32_t end, uint32_t lane, const Key16Map& m, uint32_t (&t)[kRegs])
-{
-#pragma unroll
-    for (int j = 0; j < kRegs / 8; j++) {
-        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
-        if (q < end && end - q >= kGroupKeys) {
-            const uint4 v = *reinterpret_cast<const uint4*>(r.keys + r.head + q);
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                t[8 * j + 2 * i] = to_sortable16(w[i] & 0xFFFFu, m);
-                t[8 * j + 2 * i + 1] = to_sortable16(w[i] >> 16, m);
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                t[8 * j + e] = kNoKey;
-                if (q + (uint32_t)e < end) t[8 * j + e] = to_sortable16(r.keys[r.head + q + (uint32_t)e], m);
-            }
-        }
-    }
-}
-// head key `lane` of the row, for the one wave that owns the head
-__device__ __forceinline__ uint32_t load_head(const Row16& r, uint32_t lane, const Key16Map& m)
-{
-    return lane < r.head ? to_sortable16(r.keys[lane], m) : kNoKey;
-}
 
 struct Winners {
     uint32_t* keys;       // [rows][k] in the workspace: sortable values as uint32
@@ -232,27 +199,12 @@ __global__ void __launch_bounds__(kPlainThreads) topk16_clear_kernel(uint32_t* c
     clear_select(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, ctl, hist, hist_words, state, rows, k, Levels16::kNoLevel);
 }
 
-// One chunk of one row per workgroup: the digit of every key under the row's prefix, counted in LDS.  LEVEL 0: the top 11 bits
-// of every key; LEVEL 1: the low 5 bits of the keys whose top 11 are the prefix.
+// one chunk of one row per workgroup: the digit of every key under the row's prefix, counted in LDS (hist_level16)
 template <int LEVEL>
 __global__ void __launch_bounds__(kLongThreads) topk16_hist_kernel(const LongParams p)
 {
     __shared__ uint32_t s_hist[kBins];
-    hist_level(p, s_hist, [&](uint32_t row, uint32_t c, const uint4& st, uint32_t lane, uint32_t wave) __attribute__((always_inline)) {
-        const Row16 r = row_of(p.keys, row, p.cols);
-        const ChunkRange g = chunk_of(r, p.chunk, c);
-        auto count = [&](uint32_t key) __attribute__((always_inline)) {
-            const bool match = LEVEL == 0 ? key != kNoKey : (key >> Levels16::shift(0)) == st.x;
-            count_digit(s_hist, match, (key >> Levels16::shift(LEVEL)) & ((1u << Levels16::bits(LEVEL)) - 1u), lane);
-        };
-        if (c == 0u && wave == 0u) count(load_head(r, lane, p.map));   // uniform
-        for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
-            uint32_t t[kRegs];
-            load_tile(r, tile + wave * kWaveTile, g.hi, lane, p.map, t);
-#pragma unroll
-            for (int i = 0; i < kRegs; i++) count(t[i]);
-        }
-    });
+    hist_level16<LEVEL>(p, s_hist);
 }
 
 // One workgroup per row: walk the bins from the best end to the one that holds the k-th key; the counters go back to zero.

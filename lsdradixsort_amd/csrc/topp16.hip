@@ -28,10 +28,10 @@
 // Short rows: one read and one write of the row (4 B/key by byte accounting); long rows three reads for the select, then one read and
 // one write: 10 B/key.  Rows with !(p < 1) are off: copied, or left alone in place.
 //
-// load_tile / load_head / store_tile / store_head are this unit's copy of kth16_rowk.hip's, where they are file-local (DESIGN.md
-// section 8: one header once an ISA diff proves the move); no existing unit or header changes.  Every launch is sized from (rows,
-// cols); phases are ordered by kernel boundaries; every store into d_out is guarded by row < rows and stays within the row.  Nothing
-// here ranks with the returning add: the result does not depend on lsdsort_set_rank_method.
+// load_tile / load_head / store_tile / store_head are select_tiles16.hpp's, shared with kth16_rowk.hip's top-k filter: the stores
+// keep (key >> shift) <= prefix, here the whole threshold with shift 0.  Every launch is sized from (rows, cols); phases are ordered
+// by kernel boundaries; every store into d_out is guarded by row < rows and stays within the row.  Nothing here ranks with the
+// returning add: the result does not depend on lsdsort_set_rank_method.
 #define LSDSORT_BUILD 1
 #include "../../include/lsdsort.h"
 
@@ -39,15 +39,14 @@
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
 #include "radix_select.hpp"
+#include "select_tiles16.hpp"
 
 namespace lsd {
 namespace {
 
 constexpr uint32_t kToppFaultSelect = 1024u;   // fault word: no threshold was selected for a row (never expected; nothing stored)
-constexpr uint32_t kNoKey = 0xFFFFFFFFu;       // a sortable value is below 65536
 constexpr uint32_t kFailedRow = 2u, kOffRow = 3u;   // row state w: 0 in the select, 1 the threshold is in x, these two from the start or on a fault
 constexpr int kMassShift = 32;                 // q = floor(w * 2^32)
-using Row16 = Row<uint16_t>;   // a lane holds two 16-byte groups of eight keys of its wave's tile
 
 // The value side of a key type: where the NaNs lie among the sortable values, and the float32 of a key.
 struct Values16 {
@@ -84,66 +83,6 @@ __device__ __forceinline__ uint64_t wave_sum64(uint64_t v)
     return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)hi, 63) << 22) + (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)lo, 63);
 }
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return b < a ? b : a; }); }
-
-// The wave's tile from body position q0 on, valid below `end`: a whole group by one 16-byte load, the others key by key.
-__device__ __forceinline__ void load_tile(const Row16& r, uint32_t q0, uint32_t end, uint32_t lane, const Key16Map& m, uint32_t (&t)[kRegs])
-{
-#pragma unroll
-    for (int j = 0; j < kRegs / 8; j++) {
-        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
-        if (q < end && end - q >= kGroupKeys) {
-            const uint4 v = *reinterpret_cast<const uint4*>(r.keys + r.head + q);
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                t[8 * j + 2 * i] = to_sortable16(w[i] & 0xFFFFu, m);
-                t[8 * j + 2 * i + 1] = to_sortable16(w[i] >> 16, m);
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                t[8 * j + e] = kNoKey;
-                if (q + (uint32_t)e < end) t[8 * j + e] = to_sortable16(r.keys[r.head + q + (uint32_t)e], m);
-            }
-        }
-    }
-}
-// head key `lane` of the row, for the one wave that owns the head
-__device__ __forceinline__ uint32_t load_head(const Row16& r, uint32_t lane, const Key16Map& m)
-{
-    return lane < r.head ? to_sortable16(r.keys[lane], m) : kNoKey;
-}
-
-// The store of one tile held in registers (load_tile at q0, valid below `end`) into the destination row `orow`: a key is kept where
-// key <= thr and becomes `fill` elsewhere.  `vec`: the destination row has the source row's 16-byte phase, so a whole group is one
-// 16-byte store at the address the load had; otherwise, and behind the last whole group, key by key.  Every store is below `end`,
-// that is inside the row.
-__device__ __forceinline__ void store_tile(uint16_t* orow, bool vec, const Row16& r, uint32_t q0, uint32_t end, uint32_t lane,
-                                           const uint32_t (&t)[kRegs], uint32_t thr, uint32_t fill, const Key16Map& m)
-{
-#pragma unroll
-    for (int j = 0; j < kRegs / 8; j++) {
-        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
-        if (q >= end) continue;
-        uint32_t w[8];
-#pragma unroll
-        for (int e = 0; e < 8; e++) w[e] = t[8 * j + e] <= thr ? from_sortable16(t[8 * j + e], m) & 0xFFFFu : fill;
-        if (vec && end - q >= kGroupKeys) {
-            *reinterpret_cast<uint4*>(orow + r.head + q) = make_uint4(w[0] | (w[1] << 16), w[2] | (w[3] << 16), w[4] | (w[5] << 16), w[6] | (w[7] << 16));
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; e++)
-                if (q + (uint32_t)e < end) orow[r.head + q + (uint32_t)e] = (uint16_t)w[e];
-        }
-    }
-}
-// the head keys of the row, by the one wave that owns them
-__device__ __forceinline__ void store_head(uint16_t* orow, const Row16& r, uint32_t lane, uint32_t h, uint32_t thr, uint32_t fill,
-                                           const Key16Map& m)
-{
-    if (lane < r.head) orow[lane] = (uint16_t)(h <= thr ? from_sortable16(h, m) : fill);
-}
-__device__ __forceinline__ bool same_phase(const void* a, const void* b) { return (((uintptr_t)a ^ (uintptr_t)b) & 15u) == 0u; }
 
 // ---- short rows: one wavefront (WAVES = 1, eight rows per workgroup) or one workgroup (WAVES = 16) per row ----------------------
 struct ShortParams {
@@ -256,8 +195,8 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) topp16_short_kernel(c
         }
         if (selected) {
             uint16_t* const orow = p.dst + (size_t)row * p.cols;
-            store_tile(orow, same_phase(orow, r.keys), r, q0, r.body, lane, t, thr, p.fill, p.map);
-            if (wave == 0u) store_head(orow, r, lane, h, thr, p.fill, p.map);
+            store_tile(orow, same_phase(orow, r.keys), r, q0, r.body, lane, t, thr, 0u, p.fill, p.map);
+            if (wave == 0u) store_head(orow, r, lane, h, thr, 0u, p.fill, p.map);
         }
         group_sync<WAVES>();   // the next row writes s_min and s_sum again
     }
@@ -499,12 +438,12 @@ __global__ void __launch_bounds__(kLongThreads) topp16_apply_kernel(const LongPa
     const ChunkRange g = chunk_of(r, p.chunk, c);
     uint16_t* const orow = p.dst + (size_t)row * p.cols;
     const bool vec = same_phase(orow, r.keys);
-    if (c == 0u && wave == 0u) store_head(orow, r, lane, load_head(r, lane, p.map), thr, p.fill, p.map);   // uniform
+    if (c == 0u && wave == 0u) store_head(orow, r, lane, load_head(r, lane, p.map), thr, 0u, p.fill, p.map);   // uniform
     for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
         const uint32_t q0 = tile + wave * kWaveTile;
         uint32_t t[kRegs];
         load_tile(r, q0, g.hi, lane, p.map, t);
-        store_tile(orow, vec, r, q0, g.hi, lane, t, thr, p.fill, p.map);
+        store_tile(orow, vec, r, q0, g.hi, lane, t, thr, 0u, p.fill, p.map);
     }
 }
 

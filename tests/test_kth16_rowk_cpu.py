@@ -447,8 +447,8 @@ def test_short_kernels_launch_lines_and_second_round_shapes(kernel, per, cap, sh
 
 
 def test_the_unit_includes_the_shared_headers_only_and_has_no_inline_assembly():
-    """kth16_rowk.hip brings its own copies of kth16.hip's loaders: it includes the shared headers and none of the sibling units"""
+    """kth16_rowk.hip takes its tile helpers from select_tiles16.hpp: it includes the shared headers and none of the sibling units"""
     text = open(os.path.join(ROOT, "lsdradixsort_amd", "csrc", "kth16_rowk.hip")).read()
     assert set(re.findall(r'#include "([^"]+)"', text)) == {"../../include/lsdsort.h", "keys16_map.hpp", "lsd_device.hpp", "lsd_host.hpp",
-                                                             "radix_select.hpp"}
+                                                             "radix_select.hpp", "select_tiles16.hpp"}
     assert "asm" not in re.sub(r"//.*", "", text)                                          # no inline assembly
