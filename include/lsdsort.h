@@ -579,6 +579,49 @@ LSDSORT_API int lsdsort_topp16_filter_device(const void* d_keys, size_t rows, si
                                              void* d_out /* [rows][cols] 16-bit; may be d_keys itself */, void* d_workspace,
                                              size_t workspace_bytes, void* hip_stream);
 
+/* The DRAW of a sampling step for float16 / bfloat16 rows, one token per row, with a uniform u of its own for every row read from
+ * device memory (lsdradixsort_amd/csrc/sample16.hip): the inverse CDF of the row's softmax in POSITION order, without a select, a
+ * sort or a float32 copy of the row.  key_type is LSDSORT_KEY16_F16 or LSDSORT_KEY16_BF16.
+ * Weights, those of lsdsort_topp16_filter_device: m is the largest non-NaN key of the row by value; w(x) is 0 for a NaN, 1 where
+ * x == m (which also defines rows whose maximum is an infinity) and exp(x - m) elsewhere; Z is the sum of w over the row; C_i the sum
+ * of w over the positions j < i.  d_u is a DEVICE array of `rows` float32 (4-byte aligned); with u = d_u[r], row r stores into
+ * d_index[r] the position i with C_i <= u * Z < C_i + w_i.  A key of zero mass is never drawn: a NaN, and a -inf under a finite
+ * maximum -- what the filters write.  Composition: lsdsort_topk16_filter_device and lsdsort_topp16_filter_device (fill_bits = -inf,
+ * in place) followed by this entry are "top-k, top-p, sample over the renormalised survivors" with no further code.  A row of -inf
+ * alone draws uniformly from its keys (x == m).  A row that holds no number (Z == 0) stores index -1 and logprob NaN and raises no
+ * flag: that is data, not a fault.
+ * Arithmetic actually used: q(x) = floor(w(x) * 2^32) as uint64 with w in float32 by v_exp_f32 -- the SAME device functions as the
+ * top-p filter, so a value has one mass in the filter and in the draw --, Z and C integer sums of q (Z < 2^62).  G = 0 where
+ * !(u > 0) (zero, a negative u, a NaN), else G = min(Z - 1, (uint64)floor((double)u * (double)Z)), so u >= 1 draws the last key of
+ * non-zero q; the result is the i with C_i <= G < C_i + q_i.  Tolerance, for |logit| <= 64 and cols <= 2^17: the drawn index is
+ * consistent with u +- 2^-12 of the row's mass (the top-p filter's budget: the masses are the same and the float64 product adds
+ * nothing visible).  The result is DETERMINISTIC: integer sums do not depend on the chunking, on the order of the atomics or on the
+ * other rows, so the same (row, u) gives the same index on every call, in any batch, at any `rows`, in every size class.
+ * d_logprob (optional, NULL: none) receives (x_i - m) - ln(Z * 2^-32) in float32, the log-probability of the drawn key under the
+ * row's softmax -- only this entry knows Z --, within 2^-11 absolute of float64 under the conditions above.
+ * The host never reads d_u and no value in it sizes a launch: capturable after lsdsort_prepare_device, and d_u and the keys are read
+ * again on every replay, so a captured decode graph follows changed u and changed keys.
+ * d_keys is READ ONLY, needs 2-byte alignment only, and cols may be odd.  Stores go to d_index[r] and d_logprob[r], r < rows, only.
+ * Kernels: rows of up to 1024 keys (one wavefront) and up to 16384 (one workgroup) are loaded into registers once: the maximum by an
+ * integer reduction, q per register, a 64-bit exclusive scan in position order, and the one lane whose range holds G stores: one read
+ * of the row (2 B/key by byte accounting).  Longer rows: the best number per chunk (integer atomicMin), the sum of q per chunk (one
+ * plain 64-bit store per chunk, every chunk on every call), Z, G and the chunk that holds G per row, then one workgroup per row reads
+ * that one chunk up to the crossing: two reads plus one chunk, about 4 B/key.
+ * Stream-ordered, no host synchronisation, nothing allocated; phases are ordered by kernel boundaries.  The fault word is the first
+ * word of the workspace: bit 1024 where no key was located for a row that has mass (never expected; nothing is stored for the row).
+ * The result does not depend on lsdsort_set_rank_method.
+ * Checks, in order, each before a device is touched: key_type other than float16 / bfloat16 (INVALID_ARG), rows or rows * cols above
+ * LSDSORT_MAX_KEYS (TOO_LARGE), rows == 0 or cols == 0 (OK, nothing launched), a NULL or odd d_keys (INVALID_ARG), a NULL d_u or
+ * d_index or one that is not 4-byte aligned (INVALID_ARG), a non-NULL d_logprob that is not 4-byte aligned (INVALID_ARG), the
+ * workspace (WORKSPACE: NULL, not 256-byte aligned, or below lsdsort_sample16_workspace_bytes), the device (NO_DEVICE).
+ * lsdsort_sample16_workspace_bytes is a multiple of 256, monotonic in each argument, 0 above the limits, independent of d_u and
+ * d_logprob, and O(rows): the control block, 16 B per row, and for rows above 16384 keys 8 B per 16384 keys of a row. */
+LSDSORT_API size_t lsdsort_sample16_workspace_bytes(size_t rows, size_t cols);
+LSDSORT_API int lsdsort_sample16_device(const void* d_keys, size_t rows, size_t cols, const float* d_u /* DEVICE, [rows] */,
+                                        int key_type /* float16 or bfloat16 */, int32_t* d_index /* [rows] */,
+                                        float* d_logprob /* [rows], or NULL */, void* d_workspace, size_t workspace_bytes,
+                                        void* hip_stream);
+
 /* After the stream has drained: LSDSORT_OK, or LSDSORT_ERR_DEVICE_FAULT if a kernel of the
  * last sort on this workspace gave up a bounded spin or refused destinations outside the output
  * (never expected; the output is then undefined).  Synchronises hip_stream.  With LSDSORT_REPROBE=1

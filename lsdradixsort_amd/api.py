@@ -30,6 +30,7 @@ __all__ = [
     "GPUKth16Multi", "kth16_multi_workspace_bytes", "quantile16_rows",
     "GPUKth16PerRow", "kth16_perrow_workspace_bytes", "GPUTopK16Filter", "topk16_filter_workspace_bytes", "topk16_filter_rows",
     "GPUTopP16Filter", "topp16_filter_workspace_bytes", "topp16_filter_rows",
+    "GPUSample16", "sample16_workspace_bytes", "sample16_rows",
     "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
     "MSBPartition", "SplitterPartition", "ThresholdPartition", "sharded_thresholds",
 ]
@@ -1076,16 +1077,17 @@ def topp16_filter_workspace_bytes(rows: int, cols: int) -> int:
     return int(lib().lsdsort_topp16_filter_workspace_bytes(rows, cols))
 
 
-def _p_per_row(p, rows: int, device):
-    """``p`` of ``topp16_filter_rows`` as the float32 vector the library reads, one entry per row, on ``device``: a float (every
-    row), a sequence of floats, or a float32 / float64 tensor.  A float32 tensor on ``device`` is used as it is."""
+def _p_per_row(p, rows: int, device, name: str = "p"):
+    """A per-row float argument (``p`` of ``topp16_filter_rows``, ``u`` of ``sample16_rows``) as the float32 vector the library
+    reads, one entry per row, on ``device``: a float (every row), a sequence of floats, or a float32 / float64 tensor.  A float32
+    tensor on ``device`` is used as it is.  ``name``: what the messages call it."""
     torch = _torch()
-    what = "p: a float, a sequence of floats, or a float32 / float64 tensor"
+    what = f"{name}: a float, a sequence of floats, or a float32 / float64 tensor"
     if isinstance(p, torch.Tensor):
         if p.dtype not in (torch.float32, torch.float64):
             raise TypeError(what)
         if p.numel() != rows:
-            raise ValueError(f"p: one entry per row ({rows}), got {p.numel()}")
+            raise ValueError(f"{name}: one entry per row ({rows}), got {p.numel()}")
         return p.to(torch.float32).to(device).contiguous().view(-1)
     if isinstance(p, (bool, str, bytes)) or p is None:
         raise TypeError(what)
@@ -1096,7 +1098,7 @@ def _p_per_row(p, rows: int, device):
     except (TypeError, ValueError):
         raise TypeError(what) from None
     if len(values) != rows:
-        raise ValueError(f"p: one entry per row ({rows}), got {len(values)}")
+        raise ValueError(f"{name}: one entry per row ({rows}), got {len(values)}")
     return torch.tensor(values, dtype=torch.float32).to(device)
 
 
@@ -1167,6 +1169,103 @@ def topp16_filter_rows(x, p, fill=None, inplace: bool = False, stream=None):
         out = GPUTopP16Filter(flat, d_p, key_type=str(x.dtype).replace("torch.", ""), fill=bits, out=flat if inplace else None,
                               stream=stream)
         return x if inplace else out.view(x.shape)
+
+
+def sample16_workspace_bytes(rows: int, cols: int) -> int:
+    """Bytes of device workspace ``GPUSample16`` needs for ``rows`` rows of ``cols`` 16-bit keys (whatever the u's, with or without
+    logprobs)."""
+    return int(lib().lsdsort_sample16_workspace_bytes(rows, cols))
+
+
+def GPUSample16(d_keys, d_u, key_type: str = "bfloat16", out=None, logprobs=False, workspace=None, stream=None,
+                check_fault: bool = False):
+    """The draw of a sampling step, one token per row, with a uniform ``u`` of its own per row read on the device
+    (``lsdsort_sample16_device``): ``d_keys`` a contiguous 1-D or 2-D float16 / bfloat16 CUDA tensor of logits, ``d_u`` a contiguous
+    float32 CUDA tensor with one entry per row.  Row ``r`` of the result is the position ``i`` whose softmax mass interval, in position
+    order, holds ``d_u[r]``: ``C_i <= u Z < C_i + w_i`` with the top-p filter's weights (0 for a NaN, 1 at the row's largest number,
+    ``exp(x - m)`` elsewhere) -- what ``searchsorted(cumsum(softmax(row)), u, right=True)`` gives.  A key without mass (a NaN, a -inf
+    under a finite maximum: what the filters fill with) is never drawn; ``u <= 0`` or a NaN draws the first key that has mass,
+    ``u >= 1`` the last; a row that holds no number gives -1 (and a NaN logprob).  Integer fixed-point masses: the index is
+    consistent with ``d_u[r]`` to 2^-12 of the row's mass and is the same on every call, whatever the other rows.  Returns the int32
+    index tensor ``[rows]`` (``out`` where one is given); with ``logprobs`` -- ``True``, or a contiguous float32 CUDA tensor
+    ``[rows]`` to fill -- ``(index, logprob)``, the drawn key's log-probability under the row's softmax in float32.  The host never
+    reads ``d_u``: a captured graph follows its contents and the keys'.  Stream-ordered; ``d_keys`` is only read: rows of up to
+    16384 keys once, longer ones twice plus one chunk."""
+    torch = _torch()
+    _dev(d_keys, "d_keys", (torch.float16, torch.bfloat16), dims=(1, 2))
+    if key_type not in ("float16", "bfloat16"):
+        raise ValueError(f'key_type: "float16" or "bfloat16", got {key_type!r}')
+    code, rows, cols = _keys16(d_keys, key_type, "is sampled")
+    _dev(d_u, "d_u", (torch.float32,))
+    if d_u.numel() != rows:
+        raise ValueError(f"d_u: one entry per row ({rows}), got {d_u.numel()}")
+    if out is not None:
+        _dev(out, "out", (torch.int32,), dims=(1,))
+        if out.numel() != rows:
+            raise ValueError(f"out: one entry per row ({rows}), got {out.numel()}")
+    own_logprob = isinstance(logprobs, torch.Tensor)
+    if own_logprob:
+        _dev(logprobs, "logprobs", (torch.float32,), dims=(1,))
+        if logprobs.numel() != rows:
+            raise ValueError(f"logprobs: one entry per row ({rows}), got {logprobs.numel()}")
+    elif not isinstance(logprobs, bool):
+        raise TypeError("logprobs: a bool, or a contiguous 1-D float32 CUDA tensor")
+    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
+        index = out if out is not None else torch.empty((rows,), dtype=torch.int32, device=d_keys.device)
+        logprob = logprobs if own_logprob else (torch.empty((rows,), dtype=torch.float32, device=d_keys.device) if logprobs else None)
+    if workspace is None:
+        nbytes = sample16_workspace_bytes(rows, cols)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_sample16_workspace_bytes", "too many keys or rows")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    check(lib().lsdsort_sample16_device(d_keys.data_ptr(), rows, cols, d_u.data_ptr(), code, index.data_ptr(),
+                                        logprob.data_ptr() if logprob is not None else None, workspace.data_ptr(), workspace.numel(),
+                                        _stream(stream)), "lsdsort_sample16_device")
+    if check_fault and rows and cols:
+        _check_fault(workspace, stream)
+    return (index, logprob) if logprob is not None else index
+
+
+def sample16_rows(x, u=None, top_k=None, top_p=None, generator=None, return_logprobs: bool = False, stream=None):
+    """One token per row of a float16 / bfloat16 CUDA tensor of logits of one or more dimensions, drawn from the softmax of the row of
+    the last dimension: what ``torch.multinomial(torch.softmax(x.float(), -1), 1)`` draws, as the inverse CDF
+    ``searchsorted(cumsum(softmax(row)), u_r, right=True)`` of a uniform ``u_r``, without the float32 passes.  ``u`` is a float for
+    every row, or one entry per row as a sequence or a float32 / float64 tensor; a float32 CUDA tensor is used as it is, so a captured
+    caller pays no conversion and changes its contents between replays; ``None`` draws ``torch.rand(rows, generator=generator)`` on
+    ``x``'s device.  With ``top_k`` (the forms of ``topk16_filter_rows``) or ``top_p`` (those of ``topp16_filter_rows``) the filters
+    run first, in place on ONE copy of ``x``, top-k before top-p, and the draw is over the renormalised survivors.  Returns int64
+    indices of shape ``x.shape[:-1]``, with ``return_logprobs`` ``(indices, logprobs)``, the float32 log-probability of each drawn
+    key (after the filters).  A row without a number gives -1.  A float32 ``u`` resolves 2^-24: a token whose probability is below
+    that, late in a row, may be out of reach -- as with any float32 uniform."""
+    torch = _torch()
+    _dev(x, "x", (torch.float16, torch.bfloat16), contiguous=False)
+    if x.dim() == 0:
+        raise TypeError("x: at least one dimension")
+    cols = x.shape[-1]
+    rows = int(np.prod(x.shape[:-1], dtype=np.int64))
+    key_type = str(x.dtype).replace("torch.", "")
+    with _on_stream(stream):
+        if u is None:
+            d_u = torch.rand((rows,), dtype=torch.float32, device=x.device, generator=generator)
+        else:
+            d_u = _p_per_row(u, rows, x.device, "u")
+        d_k = _k_per_row(top_k, rows, x.device) if top_k is not None else None
+        d_p = _p_per_row(top_p, rows, x.device, "top_p") if top_p is not None else None
+        if rows == 0 or cols == 0:
+            index = torch.full(x.shape[:-1], -1, dtype=torch.int64, device=x.device)
+            logprob = torch.full(x.shape[:-1], float("nan"), dtype=torch.float32, device=x.device)
+            return (index, logprob) if return_logprobs else index
+        flat = x.contiguous().view(-1, cols)
+        if d_k is not None or d_p is not None:
+            flat = flat.clone() if flat.data_ptr() == x.data_ptr() else flat   # the one copy the filters write
+            if d_k is not None:
+                GPUTopK16Filter(flat, d_k, key_type=key_type, largest=True, out=flat, stream=stream)
+            if d_p is not None:
+                GPUTopP16Filter(flat, d_p, key_type=key_type, out=flat, stream=stream)
+        got = GPUSample16(flat, d_u, key_type=key_type, logprobs=bool(return_logprobs), stream=stream)
+        if return_logprobs:
+            return got[0].to(torch.int64).view(x.shape[:-1]), got[1].view(x.shape[:-1])
+        return got.to(torch.int64).view(x.shape[:-1])
 
 
 def rows16_workspace_bytes(rows: int, cols: int) -> int:

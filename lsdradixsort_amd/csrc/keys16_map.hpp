@@ -1,6 +1,7 @@
 // keys16_map.hpp -- what the two translation units for 16-bit keys share (keys16.hip: the sort; topk16.hip: the select): the map
 // from the caller's key type and order to the sortable 16-bit value, and the split of an array of 2-byte keys into the keys in
-// front of its first 16-byte line, whole groups of eight from there on, and the keys behind the last whole group.
+// front of its first 16-byte line, whole groups of eight from there on, and the keys behind the last whole group.  And the value
+// side of a float16 / bfloat16 key: its float32 and its softmax mass, one definition for topp16.hip's filter and sample16.hip's draw.
 //
 // Everything here has internal linkage (an unnamed namespace, as when it lived in keys16.hip): every unit compiles its own copy
 // into its own kernels, and the kernels of keys16.hip keep their symbols.
@@ -59,5 +60,32 @@ inline Span span_of(const void* keys, size_t n)
 }
 __device__ __forceinline__ const uint4* body_of(const uint16_t* keys, const Span& sp) { return reinterpret_cast<const uint4*>(keys + sp.head); }
 __device__ __forceinline__ uint32_t first_tail_key(const Span& sp) { return sp.head + sp.groups * kGroupKeys; }
+
+// ---- the value side of a float16 / bfloat16 key: softmax masses (topp16.hip: the filter; sample16.hip: the draw) -------------------
+// One definition, so that a value has ONE mass in every kernel of both units (DESIGN.md sections 6.13 and 6.15).
+constexpr int kMassShift = 32;                 // q = floor(w * 2^32)
+
+// The value side of a key type: where the NaNs lie among the sortable values, and the float32 of a key.
+struct Values16 {
+    uint32_t nan_lo;    // sortable(+inf): the +NaNs lie below it, the -NaNs above 0xFFFF - nan_lo = sortable(-inf)
+    uint32_t bf16;      // bfloat16 (else float16)
+};
+__device__ __forceinline__ bool is_number(uint32_t s, const Values16& v) { return s - v.nan_lo <= 0xFFFFu - 2u * v.nan_lo; }   // kNoKey: never
+__device__ __forceinline__ float value_of(uint32_t s, const Key16Map& m, const Values16& v)
+{
+    const uint32_t bits = from_sortable16(s, m) & 0xFFFFu;
+    return v.bf16 ? __uint_as_float(bits << 16) : (float)__builtin_bit_cast(_Float16, (uint16_t)bits);
+}
+// q of a key that is a number; `best`: value_of(m).  The == also defines rows whose best number is an infinity (inf - inf).
+__device__ __forceinline__ uint64_t mass_of(float x, float best)
+{
+    if (x == best) return 1ull << kMassShift;
+    const float w = __builtin_amdgcn_exp2f((x - best) * 1.44269504088896341f);   // x < best: w <= 1
+    return w >= 1.0f ? 1ull << kMassShift : (uint64_t)(uint32_t)(w * 4294967296.0f);
+}
+__device__ __forceinline__ uint64_t mass_of_key(uint32_t s, float best, const Key16Map& m, const Values16& v)
+{
+    return is_number(s, v) ? mass_of(value_of(s, m, v), best) : 0ull;
+}
 
 }  // namespace

@@ -4,7 +4,8 @@
 // Softmax weight is a function of the value, so the kept set is "every key at least as good as a threshold T_r" -- what the top-k
 // filter (kth16_rowk.hip) stores.  New is the select: it walks MASSES instead of counts.
 //
-// Arithmetic (the same device functions in every kernel, so that every kernel gives a value the same mass):
+// Arithmetic (the same device functions in every kernel, so that every kernel gives a value the same mass; is_number, value_of, mass_of
+// and mass_of_key live in keys16_map.hpp, where sample16.hip's draw takes them from too):
 //   s      the sortable value of a key under the 16-bit map with largest: SMALLER is better; +NaN above +inf, -NaN below -inf
 //   m      the best key of the row that is no NaN (an integer minimum of s)
 //   w(x)   float32: 0 for a NaN, 1 where value(x) == value(m), else v_exp_f32((x - m) * log2 e)
@@ -46,30 +47,6 @@ namespace {
 
 constexpr uint32_t kToppFaultSelect = 1024u;   // fault word: no threshold was selected for a row (never expected; nothing stored)
 constexpr uint32_t kFailedRow = 2u, kOffRow = 3u;   // row state w: 0 in the select, 1 the threshold is in x, these two from the start or on a fault
-constexpr int kMassShift = 32;                 // q = floor(w * 2^32)
-
-// The value side of a key type: where the NaNs lie among the sortable values, and the float32 of a key.
-struct Values16 {
-    uint32_t nan_lo;    // sortable(+inf): the +NaNs lie below it, the -NaNs above 0xFFFF - nan_lo = sortable(-inf)
-    uint32_t bf16;      // bfloat16 (else float16)
-};
-__device__ __forceinline__ bool is_number(uint32_t s, const Values16& v) { return s - v.nan_lo <= 0xFFFFu - 2u * v.nan_lo; }   // kNoKey: never
-__device__ __forceinline__ float value_of(uint32_t s, const Key16Map& m, const Values16& v)
-{
-    const uint32_t bits = from_sortable16(s, m) & 0xFFFFu;
-    return v.bf16 ? __uint_as_float(bits << 16) : (float)__builtin_bit_cast(_Float16, (uint16_t)bits);
-}
-// q of a key that is a number; `best`: value_of(m).  The == also defines rows whose best number is an infinity (inf - inf).
-__device__ __forceinline__ uint64_t mass_of(float x, float best)
-{
-    if (x == best) return 1ull << kMassShift;
-    const float w = __builtin_amdgcn_exp2f((x - best) * 1.44269504088896341f);   // x < best: w <= 1
-    return w >= 1.0f ? 1ull << kMassShift : (uint64_t)(uint32_t)(w * 4294967296.0f);
-}
-__device__ __forceinline__ uint64_t mass_of_key(uint32_t s, float best, const Key16Map& m, const Values16& v)
-{
-    return is_number(s, v) ? mass_of(value_of(s, m, v), best) : 0ull;
-}
 // T: an integer F is below p * Z iff it is below ceil(p * Z).  p < 1, Z < 2^62.
 __device__ __forceinline__ uint64_t mass_target(float p, uint64_t z)
 {
@@ -526,7 +503,7 @@ int lsdsort_topp16_filter_device(const void* d_keys, size_t rows, size_t cols, c
     if (key_type != LSDSORT_KEY16_F16 && key_type != LSDSORT_KEY16_BF16) return LSDSORT_ERR_INVALID_ARG;
     Key16Map map;
     LSD_TRY(key16_map(key_type, 1, &map));
-    const lsd::Values16 val{key_type == LSDSORT_KEY16_BF16 ? 0x007Fu : 0x03FFu, key_type == LSDSORT_KEY16_BF16 ? 1u : 0u};
+    const Values16 val{key_type == LSDSORT_KEY16_BF16 ? 0x007Fu : 0x03FFu, key_type == LSDSORT_KEY16_BF16 ? 1u : 0u};
     if (!lsd::sizes_ok(rows, cols)) return LSDSORT_ERR_TOO_LARGE;
     if (rows == 0 || cols == 0) return LSDSORT_OK;
     if (!d_keys || !d_out || (((uintptr_t)d_keys | (uintptr_t)d_out) & 1)) return LSDSORT_ERR_INVALID_ARG;
