@@ -14,6 +14,7 @@ x - m in float32 is off by at most 7.6e-6, ln Z with Z off by at most 6e-5 relat
 below 1.2e-5; together below 8e-5."""
 import numpy as np
 
+import _long_plan as lp
 import _topp16 as tp
 
 M = tp.M
@@ -126,9 +127,8 @@ def cycle_u(rows, shift=0):
 
 def chunk_len(rows, cols):
     """the chunk length the library's plan gives rows above 16384 keys: about 2048 chunks over the array, at least 16384 keys, a
-    multiple of the 4096-key tile"""
-    chunk = max(16384, -(-rows * cols // 2048))
-    return -(-chunk // 4096) * 4096
+    multiple of the 4096-key tile (_long_plan.py restates the plan)"""
+    return lp.chunks_for(rows, cols)[0]
 
 
 def placement_positions(cols, chunk):

@@ -123,7 +123,7 @@ def test_long_tier(shape, key_type):
 
 @pytest.mark.parametrize("key_type", list(KEY_TYPES))
 def test_one_long_row_of_many_chunks(key_type):
-    """[1 x (2^20 + 13)]: 64 chunks, so the pick of the chunk and the remainder of `need` matter"""
+    """[1 x (2^20 + 13)]: 65 chunks, so the pick of the chunk and the remainder of `need` matter"""
     check_shape(1, (1 << 20) + 13, key_type)
 
 

@@ -153,7 +153,7 @@ def test_long_tier(shape, key_type):
 
 
 def test_one_long_row_of_many_chunks():
-    """[1 x (2^20 + 13)]: 64 chunks, so the slots pick different chunks and the remainder of each `need` matters"""
+    """[1 x (2^20 + 13)]: 65 chunks, so the slots pick different chunks and the remainder of each `need` matters"""
     check_shape(1, (1 << 20) + 13, "float32")
 
 
