@@ -579,6 +579,38 @@ LSDSORT_API int lsdsort_topp16_filter_device(const void* d_keys, size_t rows, si
                                              void* d_out /* [rows][cols] 16-bit; may be d_keys itself */, void* d_workspace,
                                              size_t workspace_bytes, void* hip_stream);
 
+/* The top-p filter with a TEMPERATURE and a MIN-P of its own for every row (the same kernels of topp16.hip; DESIGN.md section
+ * 6.16).  d_p, d_min_p and d_temperature are DEVICE arrays of `rows` float32 (4-byte aligned) and each of them may be NULL.
+ * Temperature T = d_temperature[r]; NULL: 1 for every row.  The weights of lsdsort_topp16_filter_device become w(x) = 0 for a NaN, 1
+ * where x == m, exp((x - m) / T) elsewhere: the device takes exp2((x - m) * c) with c = log2(e) / T computed in float64 and rounded
+ * to float32.  T above 2^64 (+inf) acts as 2^64, so a -inf under a finite maximum has no mass at ANY temperature.  !(T > 0) -- zero,
+ * a negative T, a NaN -- and a T so small that c overflows mean GREEDY: the maximum's duplicates alone have mass, and a select that
+ * is on (p < 1) keeps the best value alone.  T = 1 gives the literal log2(e) of the entry above: a NULL d_temperature, an array of
+ * ones and lsdsort_topp16_filter_device give the SAME BITS.  Every value of T means something.
+ * Top-p, p = d_p[r] as above under these weights; a NULL d_p, like !(p < 1), is OFF.
+ * Min-p, mp = d_min_p[r]: NULL or !(mp > 0) -- zero, a negative mp, a NaN -- is OFF.  Otherwise theta = value(m) + T ln(mp), for a
+ * greedy row theta = value(m), and the min-p threshold is the worst value of the library's order that is a number with
+ * value >= theta, never worse than m: "keep the keys whose probability is at least mp times the best key's".  So mp >= 1 keeps the
+ * best number's duplicates (and the +NaNs above them: as in the top-p filter every key at least as good as the threshold is kept),
+ * -0.0 is kept when theta == 0, and a row without a number keeps its best key value alone.  theta is float32: logf, then one fused
+ * multiply-add, within B = 2^-22 * (|value(m)| + |T ln mp|) of the exact value; given theta the output is exact.
+ * A key is KEPT iff it is at least as good as the STRICTER of the two thresholds.  The ratio to the maximum does not change under
+ * renormalisation, so this is "top-p, then min-p over the survivors" and equally the other order.  A row where both are off is
+ * copied (left alone in place); a row with top-p off and min-p on skips the mass select and needs its best number only.
+ * Tolerance of the top-p threshold: the mass tolerance 2^-12 above, for |logit| <= 64, cols <= 2^17 and T greedy or >= 2^-10.
+ * Alignment, in place, capture, determinism, the fault word and the kernels are those of lsdsort_topp16_filter_device: the host
+ * reads none of the three arrays, no launch is sized from them, and all three are read again on every replay of a captured graph.
+ * Long rows without d_p: the kernel that clears the row states reads 4 * rows bytes of d_keys in d_p's place and ignores them.
+ * Checks, in order, each before a device is touched: key_type (INVALID_ARG), rows or rows * cols above LSDSORT_MAX_KEYS (TOO_LARGE),
+ * rows == 0 or cols == 0 (OK, nothing launched), a NULL or odd d_keys or d_out, then a d_p, d_min_p or d_temperature that is not
+ * 4-byte aligned (INVALID_ARG), the workspace (WORKSPACE; lsdsort_topp16_filter_workspace_bytes), the device (NO_DEVICE). */
+LSDSORT_API int lsdsort_topp16_filter_ex_device(const void* d_keys, size_t rows, size_t cols, const float* d_p /* DEVICE, [rows], or NULL: off */,
+                                                const float* d_min_p /* DEVICE, [rows], or NULL: off */,
+                                                const float* d_temperature /* DEVICE, [rows], or NULL: 1 */,
+                                                int key_type /* float16 or bfloat16 */, uint16_t fill_bits,
+                                                void* d_out /* [rows][cols] 16-bit; may be d_keys itself */, void* d_workspace,
+                                                size_t workspace_bytes, void* hip_stream);
+
 /* The DRAW of a sampling step for float16 / bfloat16 rows, one token per row, with a uniform u of its own for every row read from
  * device memory (lsdradixsort_amd/csrc/sample16.hip): the inverse CDF of the row's softmax in POSITION order, without a select, a
  * sort or a float32 copy of the row.  key_type is LSDSORT_KEY16_F16 or LSDSORT_KEY16_BF16.
@@ -621,6 +653,24 @@ LSDSORT_API int lsdsort_sample16_device(const void* d_keys, size_t rows, size_t 
                                         int key_type /* float16 or bfloat16 */, int32_t* d_index /* [rows] */,
                                         float* d_logprob /* [rows], or NULL */, void* d_workspace, size_t workspace_bytes,
                                         void* hip_stream);
+
+/* The draw with a TEMPERATURE of its own for every row (the same kernels of sample16.hip): d_temperature is
+ * a DEVICE array of `rows` float32 (4-byte aligned), or NULL for T = 1 in every row, with the meaning and the arithmetic of
+ * lsdsort_topp16_filter_ex_device -- the same device function gives a key its mass in the filter and in the draw.  A greedy row --
+ * !(T > 0), or a T so small that log2(e) / T overflows -- draws the argmax, uniformly over its duplicates by u: the j-th of `ties`
+ * duplicates in position order with j = floor(u * ties).  A -inf under a finite maximum has no mass at any T, so what the filters
+ * write is never drawn.  d_logprob receives the log-probability under the TEMPERED softmax, (x_i - m) * c * ln 2 - ln(Z * 2^-32)
+ * with 0 for the first term where x_i == m, within 2^-11 + 2^-22 * |(x_i - m) / T| of float64; for T = 1 the factor c * ln 2 is taken
+ * as 1.  A NULL d_temperature, an array of ones and lsdsort_sample16_device give the SAME BITS in d_index and d_logprob.  Index
+ * tolerance: 2^-12 of the row's mass for |logit| <= 64, cols <= 2^17 and T greedy or >= 2^-10.  Everything else -- u, alignment,
+ * capture (d_temperature is read again on every replay), determinism, kernels, the fault word, the workspace figure -- is
+ * lsdsort_sample16_device's.  Checks, in order: those of lsdsort_sample16_device, a d_temperature that is not 4-byte aligned
+ * (INVALID_ARG) together with d_logprob's. */
+LSDSORT_API int lsdsort_sample16_ex_device(const void* d_keys, size_t rows, size_t cols, const float* d_u /* DEVICE, [rows] */,
+                                           const float* d_temperature /* DEVICE, [rows], or NULL: 1 */,
+                                           int key_type /* float16 or bfloat16 */, int32_t* d_index /* [rows] */,
+                                           float* d_logprob /* [rows], or NULL */, void* d_workspace, size_t workspace_bytes,
+                                           void* hip_stream);
 
 /* After the stream has drained: LSDSORT_OK, or LSDSORT_ERR_DEVICE_FAULT if a kernel of the
  * last sort on this workspace gave up a bounded spin or refused destinations outside the output

@@ -1102,8 +1102,18 @@ def _p_per_row(p, rows: int, device, name: str = "p"):
     return torch.tensor(values, dtype=torch.float32).to(device)
 
 
+def _row_array(t, name: str, rows: int):
+    """An optional per-row device argument: ``None``, or a contiguous float32 CUDA tensor with one entry per row."""
+    if t is None:
+        return None
+    _dev(t, name, (_torch().float32,))
+    if t.numel() != rows:
+        raise ValueError(f"{name}: one entry per row ({rows}), got {t.numel()}")
+    return t
+
+
 def GPUTopP16Filter(d_keys, d_p, key_type: str = "bfloat16", fill: int | None = None, out=None, workspace=None, stream=None,
-                    check_fault: bool = False):
+                    check_fault: bool = False, d_min_p=None, d_temperature=None):
     """The top-p (nucleus) filter of every row with a p of its own per row, read on the device (``lsdsort_topp16_filter_device``):
     ``d_keys`` a contiguous 1-D or 2-D float16 / bfloat16 CUDA tensor of logits, ``d_p`` a contiguous float32 CUDA tensor with one
     entry per row.  Row ``r`` of the result is row ``r`` of ``d_keys`` where ``d_p[r]`` is not below 1 (a NaN included): the filter
@@ -1114,15 +1124,24 @@ def GPUTopP16Filter(d_keys, d_p, key_type: str = "bfloat16", fill: int | None = 
     sort, in float32 and 64-bit fixed point: it is consistent with ``d_p[r]`` to 2^-12 of the row's mass, and the result is the same
     bits on every call, whatever the other rows.  Returns the result: ``out`` where one is given (``out=d_keys`` runs in place),
     else a new tensor.  The host never reads ``d_p``: a captured graph follows its contents.  Stream-ordered; short rows are read
-    once and written once, rows above 16384 keys read four times and written once."""
+    once and written once, rows above 16384 keys read four times and written once.
+
+    ``d_min_p`` and ``d_temperature`` (``lsdsort_topp16_filter_ex_device``; without them the entry above is called as before) are
+    contiguous float32 CUDA tensors with one entry per row, read on the device like ``d_p``.  The masses become
+    ``exp((x - m) / T_r)``; ``T_r`` not above 0 (a NaN included) is greedy: the maximum alone has mass.  With ``d_min_p`` a key also
+    has to reach ``min_p_r`` times the best key's probability, ``value >= m + T_r ln(min_p_r)``; ``min_p_r`` not above 0 is off.  A
+    key stays iff it passes both filters.  ``d_p`` may be ``None`` (top-p off in every row) when ``d_min_p`` is given."""
     torch = _torch()
     _dev(d_keys, "d_keys", (torch.float16, torch.bfloat16), dims=(1, 2))
     if key_type not in ("float16", "bfloat16"):
         raise ValueError(f'key_type: "float16" or "bfloat16", got {key_type!r}')
     code, rows, cols = _keys16(d_keys, key_type, "is filtered")
-    _dev(d_p, "d_p", (torch.float32,))
-    if d_p.numel() != rows:
-        raise ValueError(f"d_p: one entry per row ({rows}), got {d_p.numel()}")
+    if d_p is not None or d_min_p is None:
+        _dev(d_p, "d_p", (torch.float32,))
+        if d_p.numel() != rows:
+            raise ValueError(f"d_p: one entry per row ({rows}), got {d_p.numel()}")
+    _row_array(d_min_p, "d_min_p", rows)
+    _row_array(d_temperature, "d_temperature", rows)
     if fill is None:
         fill = _worst_bits16(key_type, True)
     if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 0xFFFF:
@@ -1138,14 +1157,20 @@ def GPUTopP16Filter(d_keys, d_p, key_type: str = "bfloat16", fill: int | None = 
         if nbytes == 0:
             raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_topp16_filter_workspace_bytes", "too many keys or rows")
         workspace = _temp_workspace(nbytes, d_keys.device, stream)
-    check(lib().lsdsort_topp16_filter_device(d_keys.data_ptr(), rows, cols, d_p.data_ptr(), code, fill, result.data_ptr(),
-                                             workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_topp16_filter_device")
+    if d_min_p is None and d_temperature is None:
+        check(lib().lsdsort_topp16_filter_device(d_keys.data_ptr(), rows, cols, d_p.data_ptr(), code, fill, result.data_ptr(),
+                                                 workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_topp16_filter_device")
+    else:
+        ptr = [t.data_ptr() if t is not None else None for t in (d_p, d_min_p, d_temperature)]
+        check(lib().lsdsort_topp16_filter_ex_device(d_keys.data_ptr(), rows, cols, ptr[0], ptr[1], ptr[2], code, fill, result.data_ptr(),
+                                                    workspace.data_ptr(), workspace.numel(), _stream(stream)),
+              "lsdsort_topp16_filter_ex_device")
     if check_fault and rows and cols:
         _check_fault(workspace, stream)
     return result
 
 
-def topp16_filter_rows(x, p, fill=None, inplace: bool = False, stream=None):
+def topp16_filter_rows(x, p, fill=None, inplace: bool = False, stream=None, min_p=None, temperature=None):
     """The top-p (nucleus) filter of a sampling step for a float16 / bfloat16 CUDA tensor of logits of one or more dimensions: per
     row of the last dimension what sort descending, softmax, ``cumsum - probs >= p`` masked and scattered back gives, without the
     sort: the best logits stay until their softmax mass reaches ``p_r``, ties of a kept value included, and the others become
@@ -1153,7 +1178,10 @@ def topp16_filter_rows(x, p, fill=None, inplace: bool = False, stream=None):
     NaN leaves the row as it is, ``p_r <= 0`` keeps the best value alone.  A host value becomes a device tensor here; a float32 CUDA
     tensor is used as it is, so a captured caller pays no conversion and may change its contents between replays.  ``fill``: a value
     of ``x``'s dtype; ``None`` is -inf.  ``inplace`` filters ``x`` itself (contiguous) and returns it.  The order is the library's
-    total order, not torch's: -0.0 ranks below +0.0 and NaNs sort by sign at the two ends."""
+    total order, not torch's: -0.0 ranks below +0.0 and NaNs sort by sign at the two ends.  ``min_p`` and ``temperature`` take the
+    forms of ``p``: with a temperature the softmax is that of ``x / T_r`` (``T_r <= 0``: greedy) without rounding ``x / T_r`` to 16
+    bits, and with ``min_p`` a kept key also has at least ``min_p_r`` times the best key's probability (``min_p_r <= 0``: off); a
+    row keeps what passes both.  ``p`` may be ``None`` (top-p off) when ``min_p`` is given."""
     torch = _torch()
     _dev(x, "x", (torch.float16, torch.bfloat16), contiguous=bool(inplace))
     if x.dim() == 0:
@@ -1162,12 +1190,14 @@ def topp16_filter_rows(x, p, fill=None, inplace: bool = False, stream=None):
     rows = int(np.prod(x.shape[:-1], dtype=np.int64))
     bits = _fill_bits16(x.dtype, fill, True)
     with _on_stream(stream):
-        d_p = _p_per_row(p, rows, x.device)
+        d_p = _p_per_row(p, rows, x.device) if p is not None or min_p is None else None
+        d_min_p = _p_per_row(min_p, rows, x.device, "min_p") if min_p is not None else None
+        d_t = _p_per_row(temperature, rows, x.device, "temperature") if temperature is not None else None
         if rows == 0 or cols == 0:
             return x if inplace else x.clone()
         flat = (x if inplace else x.contiguous()).view(-1, cols)
         out = GPUTopP16Filter(flat, d_p, key_type=str(x.dtype).replace("torch.", ""), fill=bits, out=flat if inplace else None,
-                              stream=stream)
+                              stream=stream, d_min_p=d_min_p, d_temperature=d_t)
         return x if inplace else out.view(x.shape)
 
 
@@ -1178,7 +1208,7 @@ def sample16_workspace_bytes(rows: int, cols: int) -> int:
 
 
 def GPUSample16(d_keys, d_u, key_type: str = "bfloat16", out=None, logprobs=False, workspace=None, stream=None,
-                check_fault: bool = False):
+                check_fault: bool = False, d_temperature=None):
     """The draw of a sampling step, one token per row, with a uniform ``u`` of its own per row read on the device
     (``lsdsort_sample16_device``): ``d_keys`` a contiguous 1-D or 2-D float16 / bfloat16 CUDA tensor of logits, ``d_u`` a contiguous
     float32 CUDA tensor with one entry per row.  Row ``r`` of the result is the position ``i`` whose softmax mass interval, in position
@@ -1190,7 +1220,11 @@ def GPUSample16(d_keys, d_u, key_type: str = "bfloat16", out=None, logprobs=Fals
     index tensor ``[rows]`` (``out`` where one is given); with ``logprobs`` -- ``True``, or a contiguous float32 CUDA tensor
     ``[rows]`` to fill -- ``(index, logprob)``, the drawn key's log-probability under the row's softmax in float32.  The host never
     reads ``d_u``: a captured graph follows its contents and the keys'.  Stream-ordered; ``d_keys`` is only read: rows of up to
-    16384 keys once, longer ones twice plus one chunk."""
+    16384 keys once, longer ones twice plus one chunk.
+
+    ``d_temperature`` (``lsdsort_sample16_ex_device``; without it the entry above is called as before): a contiguous float32 CUDA
+    tensor with one entry per row, read on the device.  The weights become ``exp((x - m) / T_r)`` and the logprob is that of the
+    tempered softmax; ``T_r`` not above 0 (a NaN included) is greedy: the argmax, uniform over its duplicates by ``u``."""
     torch = _torch()
     _dev(d_keys, "d_keys", (torch.float16, torch.bfloat16), dims=(1, 2))
     if key_type not in ("float16", "bfloat16"):
@@ -1199,6 +1233,7 @@ def GPUSample16(d_keys, d_u, key_type: str = "bfloat16", out=None, logprobs=Fals
     _dev(d_u, "d_u", (torch.float32,))
     if d_u.numel() != rows:
         raise ValueError(f"d_u: one entry per row ({rows}), got {d_u.numel()}")
+    _row_array(d_temperature, "d_temperature", rows)
     if out is not None:
         _dev(out, "out", (torch.int32,), dims=(1,))
         if out.numel() != rows:
@@ -1218,15 +1253,21 @@ def GPUSample16(d_keys, d_u, key_type: str = "bfloat16", out=None, logprobs=Fals
         if nbytes == 0:
             raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_sample16_workspace_bytes", "too many keys or rows")
         workspace = _temp_workspace(nbytes, d_keys.device, stream)
-    check(lib().lsdsort_sample16_device(d_keys.data_ptr(), rows, cols, d_u.data_ptr(), code, index.data_ptr(),
-                                        logprob.data_ptr() if logprob is not None else None, workspace.data_ptr(), workspace.numel(),
-                                        _stream(stream)), "lsdsort_sample16_device")
+    if d_temperature is None:
+        check(lib().lsdsort_sample16_device(d_keys.data_ptr(), rows, cols, d_u.data_ptr(), code, index.data_ptr(),
+                                            logprob.data_ptr() if logprob is not None else None, workspace.data_ptr(), workspace.numel(),
+                                            _stream(stream)), "lsdsort_sample16_device")
+    else:
+        check(lib().lsdsort_sample16_ex_device(d_keys.data_ptr(), rows, cols, d_u.data_ptr(), d_temperature.data_ptr(), code,
+                                               index.data_ptr(), logprob.data_ptr() if logprob is not None else None,
+                                               workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_sample16_ex_device")
     if check_fault and rows and cols:
         _check_fault(workspace, stream)
     return (index, logprob) if logprob is not None else index
 
 
-def sample16_rows(x, u=None, top_k=None, top_p=None, generator=None, return_logprobs: bool = False, stream=None):
+def sample16_rows(x, u=None, top_k=None, top_p=None, generator=None, return_logprobs: bool = False, stream=None, min_p=None,
+                  temperature=None):
     """One token per row of a float16 / bfloat16 CUDA tensor of logits of one or more dimensions, drawn from the softmax of the row of
     the last dimension: what ``torch.multinomial(torch.softmax(x.float(), -1), 1)`` draws, as the inverse CDF
     ``searchsorted(cumsum(softmax(row)), u_r, right=True)`` of a uniform ``u_r``, without the float32 passes.  ``u`` is a float for
@@ -1236,7 +1277,9 @@ def sample16_rows(x, u=None, top_k=None, top_p=None, generator=None, return_logp
     run first, in place on ONE copy of ``x``, top-k before top-p, and the draw is over the renormalised survivors.  Returns int64
     indices of shape ``x.shape[:-1]``, with ``return_logprobs`` ``(indices, logprobs)``, the float32 log-probability of each drawn
     key (after the filters).  A row without a number gives -1.  A float32 ``u`` resolves 2^-24: a token whose probability is below
-    that, late in a row, may be out of reach -- as with any float32 uniform."""
+    that, late in a row, may be out of reach -- as with any float32 uniform.  ``temperature`` and ``min_p`` take the forms of
+    ``top_p``: the softmax is that of ``x / T_r`` in the filters and in the draw (``T_r <= 0``: greedy, the argmax), and ``min_p``
+    joins ``top_p`` in ONE filter call between top-k and the draw."""
     torch = _torch()
     _dev(x, "x", (torch.float16, torch.bfloat16), contiguous=False)
     if x.dim() == 0:
@@ -1251,18 +1294,20 @@ def sample16_rows(x, u=None, top_k=None, top_p=None, generator=None, return_logp
             d_u = _p_per_row(u, rows, x.device, "u")
         d_k = _k_per_row(top_k, rows, x.device) if top_k is not None else None
         d_p = _p_per_row(top_p, rows, x.device, "top_p") if top_p is not None else None
+        d_min_p = _p_per_row(min_p, rows, x.device, "min_p") if min_p is not None else None
+        d_t = _p_per_row(temperature, rows, x.device, "temperature") if temperature is not None else None
         if rows == 0 or cols == 0:
             index = torch.full(x.shape[:-1], -1, dtype=torch.int64, device=x.device)
             logprob = torch.full(x.shape[:-1], float("nan"), dtype=torch.float32, device=x.device)
             return (index, logprob) if return_logprobs else index
         flat = x.contiguous().view(-1, cols)
-        if d_k is not None or d_p is not None:
+        if d_k is not None or d_p is not None or d_min_p is not None:
             flat = flat.clone() if flat.data_ptr() == x.data_ptr() else flat   # the one copy the filters write
             if d_k is not None:
                 GPUTopK16Filter(flat, d_k, key_type=key_type, largest=True, out=flat, stream=stream)
-            if d_p is not None:
-                GPUTopP16Filter(flat, d_p, key_type=key_type, out=flat, stream=stream)
-        got = GPUSample16(flat, d_u, key_type=key_type, logprobs=bool(return_logprobs), stream=stream)
+            if d_p is not None or d_min_p is not None:
+                GPUTopP16Filter(flat, d_p, key_type=key_type, out=flat, stream=stream, d_min_p=d_min_p, d_temperature=d_t)
+        got = GPUSample16(flat, d_u, key_type=key_type, logprobs=bool(return_logprobs), stream=stream, d_temperature=d_t)
         if return_logprobs:
             return got[0].to(torch.int64).view(x.shape[:-1]), got[1].view(x.shape[:-1])
         return got.to(torch.int64).view(x.shape[:-1])

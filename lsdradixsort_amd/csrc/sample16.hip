@@ -1,16 +1,20 @@
 // sample16.hip -- the draw of a sampling step for float16 / bfloat16 rows:
 //   lsdsort_sample16_device   row r stores the position i whose softmax mass interval holds u_r * Z_r, u_r read from DEVICE memory,
 //                             and optionally that key's log-probability
+//   lsdsort_sample16_ex_device   the same under a temperature T_r per row from DEVICE memory; the entry above
+//                             is this one with NULL
 // The inverse CDF in POSITION order: no select, no sort -- one maximum, one prefix sum, one crossing.  It follows the filters
 // (kth16_rowk.hip, topp16.hip) in place: what they fill with -inf has no mass and is never drawn.
 //
 // Arithmetic (keys16_map.hpp's device functions, the ones topp16.hip uses, so that a value has ONE mass in the filter and the draw):
 //   m      the best key of the row that is no NaN (an integer minimum of the sortable value under the 16-bit map with largest)
-//   q(x)   floor(w(x) * 2^32) as uint64: w = 0 for a NaN, 1 where value(x) == value(m), else v_exp_f32((x - m) * log2 e)
+//   c      the row's scale log2(e) / T (keys16_map.hpp: scale_of; kLog2e without a temperature, +inf for a greedy row), one SGPR
+//   q(x)   floor(w(x) * 2^32) as uint64: w = 0 for a NaN, 1 where value(x) == value(m), else v_exp_f32((x - m) * c)
 //   Z      the sum of q over the row (< 2^62); C_i the sum of q over the positions in front of i
 //   G      0 where !(u > 0); Z - 1 where u >= 1; else min(Z - 1, floor((double)u * (double)Z))
 //   i      the position with C_i <= G < C_i + q_i: a key of zero mass is never drawn; Z == 0 (no number in the row) gives -1
-//   logprob (x_i - m) - ln(Z * 2^-32) in float32, x_i - m taken as 0 where x_i == m (a row whose best number is an infinity)
+//   logprob (x_i - m) * (c ln 2) - ln(Z * 2^-32) in float32, the factor taken as 1 for c == kLog2e and x_i - m as 0 where x_i == m (a
+//          row whose best number is an infinity)
 // Integer adds commute: C, Z and G do not depend on the chunks, on the waves or on the other rows.  The same (row, u) gives the same
 // index on every call, in any batch, at any `rows`.
 //
@@ -121,10 +125,10 @@ struct Masses {
     uint64_t at_h, at_g[kRegs / 8], sum_g[kRegs / 8];   // exclusive prefixes within the wave, and the lane's group sums
     uint64_t total;
 };
-__device__ __forceinline__ void scan_masses(const uint32_t (&t)[kRegs], uint32_t h, float best, bool has1, const Key16Map& m, const Values16& v,
-                                            Masses& s)
+__device__ __forceinline__ void scan_masses(const uint32_t (&t)[kRegs], uint32_t h, float best, float scale, bool has1, const Key16Map& m,
+                                            const Values16& v, Masses& s)
 {
-    s.qh = mass_of_key(h, best, m, v);
+    s.qh = mass_of_key(h, best, scale, m, v);
     const uint64_t incl_h = wave_scan64(s.qh);
     s.at_h = incl_h - s.qh;
     uint64_t run = of_lane63(incl_h);
@@ -135,7 +139,7 @@ __device__ __forceinline__ void scan_masses(const uint32_t (&t)[kRegs], uint32_t
         if (j == 0 || has1) {   // uniform
 #pragma unroll
             for (int e = 0; e < 8; e++) {
-                s.q[8 * j + e] = mass_of_key(t[8 * j + e], best, m, v);
+                s.q[8 * j + e] = mass_of_key(t[8 * j + e], best, scale, m, v);
                 s.sum_g[j] += s.q[8 * j + e];
             }
             const uint64_t incl = wave_scan64(s.sum_g[j]);
@@ -155,10 +159,11 @@ struct DrawOut {
     uint32_t rows;
 };
 // The wave whose range [before, before + s.total) holds g: the one lane whose key's interval holds g stores the key's position and its
-// log-probability.  Returns whether a lane did (uniform over the wave).  `pos0`: the row position of body position q0.
+// log-probability.  Returns whether a lane did (uniform over the wave).  `pos0`: the row position of body position q0; `factor`:
+// log_factor of the row's scale.
 __device__ __forceinline__ bool draw_in_wave(const uint32_t (&t)[kRegs], uint32_t h, const Masses& s, uint64_t before, uint64_t g, uint32_t pos0,
-                                             uint32_t lane, uint32_t row, float best, float log_z, const DrawOut& o, const Key16Map& m,
-                                             const Values16& v)
+                                             uint32_t lane, uint32_t row, float best, float factor, float log_z, const DrawOut& o,
+                                             const Key16Map& m, const Values16& v)
 {
     bool mine = false;
     auto store = [&](uint32_t key, uint32_t pos) {
@@ -167,7 +172,7 @@ __device__ __forceinline__ bool draw_in_wave(const uint32_t (&t)[kRegs], uint32_
             o.index[row] = (int32_t)pos;
             if (o.logprob) {
                 const float x = value_of(key & 0xFFFFu, m, v);
-                o.logprob[row] = (x == best ? 0.0f : x - best) - log_z;
+                o.logprob[row] = (x == best ? 0.0f : (x - best) * factor) - log_z;
             }
         }
     };
@@ -197,6 +202,8 @@ __device__ __forceinline__ bool draw_in_wave(const uint32_t (&t)[kRegs], uint32_
 struct ShortParams {
     const uint16_t* keys;
     const float* u;          // [rows], device
+    const float* temperature;   // [rows], device, ALWAYS readable: without has_temperature (1 for every row) the host puts the
+    uint32_t has_temperature;   // workspace's row-state area here, 16 B per row the short tiers do not use, and the value is dropped
     uint32_t cols, rows;
     Key16Map map;
     Values16 val;
@@ -215,13 +222,15 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) sample16_short_kernel
     const uint32_t group = WAVES == 1 ? wave_of_block : 0u, wave = WAVES == 1 ? 0u : wave_of_block;
     // `row` is the same for every thread of a group (a wave, or the whole workgroup): its barriers are reached together
     for (uint32_t row = blockIdx.x * (WAVES == 1 ? 8u : 1u) + group; row < p.rows; row += gridDim.x * (WAVES == 1 ? 8u : 1u)) {
-        const float u_load = p.u[row];   // issued in front of the row's loads and used behind them: no wait of its own
+        // the row's scalars: two unconditional loads issued in front of the row's loads and used behind them, no wait of their own
+        const float u_load = p.u[row], t_load = p.temperature[row];
         const RowKeys r = row_of(p.keys, row, p.cols);
         const uint32_t q0 = wave * kWaveTile;
         uint32_t t[kRegs];
         read_body(r, q0, r.body, lane, p.map, t);
         const uint32_t h = wave == 0u ? read_front(r, lane, p.map) : kAbsent;
-        const float u = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(u_load)));   // one value per row
+        const float u = uniform_f32(u_load);   // one value per row
+        const float scale = p.has_temperature ? uniform_f32(scale_of(t_load)) : kLog2e;   // and one scale
         uint32_t lo_num = best_number(h, kAbsent, p.val);
 #pragma unroll
         for (int i = 0; i < kRegs; i++) lo_num = best_number(t[i], lo_num, p.val);
@@ -237,7 +246,7 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) sample16_short_kernel
         }
         const float best = value_of(lo_num & 0xFFFFu, p.map, p.val);   // a row of NaNs: every q is 0
         Masses s;
-        scan_masses(t, h, best, q0 + 64u * kGroupKeys < r.body, p.map, p.val, s);
+        scan_masses(t, h, best, scale, q0 + 64u * kGroupKeys < r.body, p.map, p.val, s);
         uint64_t before = 0ull, z = s.total;
         if (WAVES > 1) {
             if (lane == 0u) s_sum[wave] = s.total;
@@ -259,7 +268,7 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) sample16_short_kernel
         }
         const uint64_t g = mass_point(u, z);
         if (g < before || g - before >= s.total) continue;   // (uniform over the wave) another wave's range holds g
-        if (!draw_in_wave(t, h, s, before, g, r.head + q0, lane, row, best, log_total(z), p.out, p.map, p.val) && lane == 0u)
+        if (!draw_in_wave(t, h, s, before, g, r.head + q0, lane, row, best, log_factor(scale), log_total(z), p.out, p.map, p.val) && lane == 0u)
             atomicOr(p.fault, kSampleFaultLocate);
     }
 }
@@ -271,6 +280,7 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) sample16_short_kernel
 struct LongParams {
     const uint16_t* keys;
     const float* u;               // [rows], device
+    const float* temperature;     // [rows], device; null: 1 for every row
     uint32_t cols, rows;
     uint32_t chunk, chunks;       // body positions per chunk (a multiple of kLongTile), chunks per row
     uint4* state;
@@ -323,14 +333,15 @@ __global__ void __launch_bounds__(kLongThreads) sample16_sum_kernel(const LongPa
     if (row >= p.rows) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const float best = value_of(p.state[row].x & 0xFFFFu, p.map, p.val);   // a row of NaNs: every q is 0
+    const float scale = row_scale(p.temperature, row);
     const RowKeys r = row_of(p.keys, row, p.cols);
     const ChunkRange g = chunk_of(r, p.chunk, c);
-    uint64_t sum = mass_of_key((c == 0u && wave == 0u) ? read_front(r, lane, p.map) : kAbsent, best, p.map, p.val);   // uniform
+    uint64_t sum = mass_of_key((c == 0u && wave == 0u) ? read_front(r, lane, p.map) : kAbsent, best, scale, p.map, p.val);   // uniform
     for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
         uint32_t t[kRegs];
         read_body(r, tile + wave * kWaveTile, g.hi, lane, p.map, t);
 #pragma unroll
-        for (int i = 0; i < kRegs; i++) sum += mass_of_key(t[i], best, p.map, p.val);
+        for (int i = 0; i < kRegs; i++) sum += mass_of_key(t[i], best, scale, p.map, p.val);
     }
     sum = wave_add64(sum);
     if (lane == 0u) s_part[wave] = sum;
@@ -402,6 +413,7 @@ __global__ void __launch_bounds__(kLongThreads) sample16_locate_kernel(const Lon
     if (c >= p.chunks) return;   // (uniform) kNoPick: Z == 0, or a fault already raised
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const float best = value_of(st.x & 0xFFFFu, p.map, p.val);
+    const float scale = row_scale(p.temperature, row);
     const uint64_t left = (uint64_t)st.z | ((uint64_t)st.w << 32);
     const RowKeys r = row_of(p.keys, row, p.cols);
     const ChunkRange g = chunk_of(r, p.chunk, c);
@@ -414,7 +426,7 @@ __global__ void __launch_bounds__(kLongThreads) sample16_locate_kernel(const Lon
         read_body(r, q0, g.hi, lane, p.map, t);
         const uint32_t h = (c == 0u && tile == 0u && wave == 0u) ? read_front(r, lane, p.map) : kAbsent;   // uniform
         Masses s;
-        scan_masses(t, h, best, q0 + 64u * kGroupKeys < g.hi, p.map, p.val, s);
+        scan_masses(t, h, best, scale, q0 + 64u * kGroupKeys < g.hi, p.map, p.val, s);
         if (lane == 0u) s_part[turn + wave] = s.total;
         __syncthreads();
         uint64_t before = base, all = 0ull;
@@ -426,7 +438,8 @@ __global__ void __launch_bounds__(kLongThreads) sample16_locate_kernel(const Lon
         }
         here = base <= left && left - base < all;   // uniform over the workgroup
         if (here && before <= left && left - before < s.total &&
-            !draw_in_wave(t, h, s, before, left, r.head + q0, lane, row, best, __uint_as_float(st.y), p.out, p.map, p.val) && lane == 0u)
+            !draw_in_wave(t, h, s, before, left, r.head + q0, lane, row, best, log_factor(scale), __uint_as_float(st.y), p.out, p.map, p.val) &&
+            lane == 0u)
             atomicOr(p.fault, kSampleFaultLocate);
         base += all;
     }
@@ -446,12 +459,13 @@ SampleLayout sample_layout(size_t rows, size_t cols)
     return L;
 }
 
-int run_sample(const uint16_t* keys, size_t rows, size_t cols, const float* d_u, const Key16Map& map, const Values16& val, const DrawOut& out,
-               char* ws, const SampleLayout& L, hipStream_t stream)
+int run_sample(const uint16_t* keys, size_t rows, size_t cols, const float* d_u, const float* d_temperature, const Key16Map& map,
+               const Values16& val, const DrawOut& out, char* ws, const SampleLayout& L, hipStream_t stream)
 {
     uint32_t* const ctl = reinterpret_cast<uint32_t*>(ws);
     if (cols <= (size_t)kLocalSortCap) {
-        const ShortParams sp{keys, d_u, (uint32_t)cols, (uint32_t)rows, map, val, ctl, out};
+        const float* const unused = reinterpret_cast<const float*>(ws + L.state);
+        const ShortParams sp{keys, d_u, d_temperature ? d_temperature : unused, d_temperature ? 1u : 0u, (uint32_t)cols, (uint32_t)rows, map, val, ctl, out};
         hipLaunchKernelGGL(sample16_clear_kernel, dim3(1), dim3(256), 0, stream, ctl, (uint4*)nullptr, 0u);
         if (cols <= (size_t)kWaveSegCap)
             hipLaunchKernelGGL(sample16_short_kernel<1>, dim3(grid_for(rows, 8, 16384)), dim3(512), 0, stream, sp);
@@ -464,6 +478,7 @@ int run_sample(const uint16_t* keys, size_t rows, size_t cols, const float* d_u,
     LongParams lp{};
     lp.keys = keys;
     lp.u = d_u;
+    lp.temperature = d_temperature;
     lp.cols = (uint32_t)cols;
     lp.rows = (uint32_t)rows;
     lp.chunk = ch.chunk;
@@ -498,8 +513,8 @@ size_t lsdsort_sample16_workspace_bytes(size_t rows, size_t cols)
     return lsd::sample_layout(rows, cols).end;
 }
 
-int lsdsort_sample16_device(const void* d_keys, size_t rows, size_t cols, const float* d_u, int key_type, int32_t* d_index, float* d_logprob,
-                            void* d_workspace, size_t workspace_bytes, void* hip_stream)
+int lsdsort_sample16_ex_device(const void* d_keys, size_t rows, size_t cols, const float* d_u, const float* d_temperature, int key_type,
+                               int32_t* d_index, float* d_logprob, void* d_workspace, size_t workspace_bytes, void* hip_stream)
 {
     if (key_type != LSDSORT_KEY16_F16 && key_type != LSDSORT_KEY16_BF16) return LSDSORT_ERR_INVALID_ARG;
     Key16Map map;
@@ -509,14 +524,20 @@ int lsdsort_sample16_device(const void* d_keys, size_t rows, size_t cols, const 
     if (rows == 0 || cols == 0) return LSDSORT_OK;
     if (!d_keys || ((uintptr_t)d_keys & 1)) return LSDSORT_ERR_INVALID_ARG;
     if (!d_u || !d_index || (((uintptr_t)d_u | (uintptr_t)d_index) & 3)) return LSDSORT_ERR_INVALID_ARG;   // u's values are the device's to read
-    if ((uintptr_t)d_logprob & 3) return LSDSORT_ERR_INVALID_ARG;                                          // NULL: no logprob
+    if (((uintptr_t)d_logprob | (uintptr_t)d_temperature) & 3) return LSDSORT_ERR_INVALID_ARG;             // NULL: no logprob; T = 1
     const lsd::SampleLayout L = lsd::sample_layout(rows, cols);
     if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.end)) return LSDSORT_ERR_WORKSPACE;
     int rank_method = 0;   // asked for the device set-up alone: nothing here ranks with the returning add
     LSD_TRY(lsd::device_rank_method(8, &rank_method));
     const lsd::DrawOut out{d_index, d_logprob, (uint32_t)rows};
-    return lsd::run_sample(static_cast<const uint16_t*>(d_keys), rows, cols, d_u, map, val, out, static_cast<char*>(d_workspace), L,
-                           static_cast<hipStream_t>(hip_stream));
+    return lsd::run_sample(static_cast<const uint16_t*>(d_keys), rows, cols, d_u, d_temperature, map, val, out, static_cast<char*>(d_workspace),
+                           L, static_cast<hipStream_t>(hip_stream));
+}
+
+int lsdsort_sample16_device(const void* d_keys, size_t rows, size_t cols, const float* d_u, int key_type, int32_t* d_index, float* d_logprob,
+                            void* d_workspace, size_t workspace_bytes, void* hip_stream)
+{
+    return lsdsort_sample16_ex_device(d_keys, rows, cols, d_u, nullptr, key_type, d_index, d_logprob, d_workspace, workspace_bytes, hip_stream);
 }
 
 }  // extern "C"

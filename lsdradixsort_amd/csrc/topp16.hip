@@ -1,6 +1,10 @@
 // topp16.hip -- the top-p (nucleus) filter of a sampling step for float16 / bfloat16 rows, without a sort:
 //   lsdsort_topp16_filter_device   row r keeps the smallest set of its best keys whose softmax mass reaches d_p[r], every duplicate of
 //                                  a kept value included; the others become `fill_bits`
+//   lsdsort_topp16_filter_ex_device   the same with a temperature T_r and a min-p mp_r per row, each array or NULL (DESIGN.md section
+//                                  6.16): masses under T_r, and a second threshold -- the worst number with value >= m + T ln mp --
+//                                  of which the stricter one goes into the store; a row whose select is off and whose min-p is
+//                                  on needs its best number only
 // Softmax weight is a function of the value, so the kept set is "every key at least as good as a threshold T_r" -- what the top-k
 // filter (kth16_rowk.hip) stores.  New is the select: it walks MASSES instead of counts.
 //
@@ -8,7 +12,8 @@
 // and mass_of_key live in keys16_map.hpp, where sample16.hip's draw takes them from too):
 //   s      the sortable value of a key under the 16-bit map with largest: SMALLER is better; +NaN above +inf, -NaN below -inf
 //   m      the best key of the row that is no NaN (an integer minimum of s)
-//   w(x)   float32: 0 for a NaN, 1 where value(x) == value(m), else v_exp_f32((x - m) * log2 e)
+//   c      the row's scale log2(e) / T (keys16_map.hpp: scale_of; kLog2e without a temperature, +inf for a greedy row), one SGPR
+//   w(x)   float32: 0 for a NaN, 1 where value(x) == value(m), else v_exp_f32((x - m) * c)
 //   q(x)   floor(w(x) * 2^32) as uint64 (kMassShift): a row of LSDSORT_MAX_KEYS < 2^30 copies of the maximum sums to < 2^62
 //   Z      the sum of q over the row; F(t) the sum of q over the keys with s < t (the mass strictly better than the value t)
 //   T      ceil(p * Z) in float64 for p > 0, 0 for p <= 0: for an integer F, F < p * Z is F < T
@@ -64,7 +69,14 @@ __device__ __forceinline__ uint32_t wave_min(uint32_t v) { return wave_reduce(v,
 // ---- short rows: one wavefront (WAVES = 1, eight rows per workgroup) or one workgroup (WAVES = 16) per row ----------------------
 struct ShortParams {
     const uint16_t* keys;
-    const float* p;          // [rows], device
+    // The three per-row arrays, [rows] float32 on the device.  All three pointers can ALWAYS be read: where the caller gave none,
+    // the host puts the row-state area of the workspace there (16 B per row, which the short tiers do not use) and leaves the
+    // array's bit out of `given`, and the value loaded is replaced by the default behind the load.  So the loads are unconditional
+    // and stand in front of the row's key loads with no branch and no wait of their own.
+    const float* p;          // kGivenP; not given: the select is off for every row
+    const float* min_p;      // kGivenMinP; not given: min-p is off for every row
+    const float* temperature;   // kGivenT; not given: 1 for every row
+    uint32_t given;
     uint32_t cols, rows;
     Key16Map map;
     Values16 val;
@@ -72,6 +84,7 @@ struct ShortParams {
     uint16_t* dst;           // [rows][cols], may be `keys`
     uint32_t fill;
 };
+constexpr uint32_t kGivenP = 1u, kGivenMinP = 2u, kGivenT = 4u;
 
 // The sum of one value per thread over the group.  WAVES > 1: through s_sum[WAVES] and ONE barrier; the caller alternates between
 // two such arrays from call to call, so that a wave two calls on writes only what every wave has read.
@@ -82,9 +95,18 @@ __device__ __forceinline__ uint64_t group_sum64(uint64_t v, volatile lds_u64* s_
     if (WAVES == 1) return v;
     if (lane == 0u) s_sum[wave] = v;
     __syncthreads();
+    // Eight reads in flight, then their adds: left to itself hipcc may issue the 16 reads of the bisection's loop one by one, each
+    // behind a full wait for the one before (16 LDS round trips per step: 14 % of the filter at [2^14 x 2^14] when it did).
     uint64_t all = 0ull;
 #pragma unroll
-    for (int w = 0; w < WAVES; w++) all += s_sum[w];
+    for (int w0 = 0; w0 < WAVES; w0 += 8) {
+        uint64_t o[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) o[i] = s_sum[w0 + i];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 8; i++) all += o[i];
+    }
     return all;
 }
 template <int WAVES>
@@ -116,18 +138,22 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) topp16_short_kernel(c
     const bool in_place = p.dst == p.keys;
     // `row` is the same for every thread of a group (a wave, or the whole workgroup): its barriers are reached together
     for (uint32_t row = blockIdx.x * (WAVES == 1 ? 8u : 1u) + group; row < p.rows; row += gridDim.x * (WAVES == 1 ? 8u : 1u)) {
-        const float p_load = p.p[row];   // issued in front of the row's loads and used behind them: no wait of its own
+        // the row's scalars: three unconditional loads issued in front of the row's loads and used behind them, no wait of their own
+        const float p_load = p.p[row], mp_load = p.min_p[row], t_load = p.temperature[row];
         const Row16 r = row_of(p.keys, row, p.cols);
         const uint32_t q0 = wave * kWaveTile;
         uint32_t t[kRegs];
         load_tile(r, q0, r.body, lane, p.map, t);
         const uint32_t h = wave == 0u ? load_head(r, lane, p.map) : kNoKey;
-        const float pr = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(p_load)));   // one value per row
-        const bool off = !(pr < 1.0f);   // (uniform) p >= 1 or NaN: the row is copied
-        if (off && in_place) continue;
+        // one value each per row; the default where the array was not given (what was loaded in its place means nothing)
+        const float pr = (p.given & kGivenP) ? uniform_f32(p_load) : 1.0f, mp = (p.given & kGivenMinP) ? uniform_f32(mp_load) : 0.0f;
+        const float tr = (p.given & kGivenT) ? uniform_f32(t_load) : 1.0f;
+        const bool off = !(pr < 1.0f);   // (uniform) p >= 1 or NaN: no select
+        const bool mp_on = mp > 0.0f;    // (uniform) else min-p is off; both off: the row is copied
+        if (off && !mp_on && in_place) continue;
         uint32_t thr = 0xFFFFu;   // every key there is
         bool selected = true;
-        if (!off) {
+        if (!off || mp_on) {
             uint32_t lo_key = h, lo_num = is_number(h, p.val) ? h : kNoKey;
 #pragma unroll
             for (int i = 0; i < kRegs; i++) {
@@ -138,35 +164,45 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) topp16_short_kernel(c
             lo_key = group_min<WAVES>(lo_key, s_min, wave, lane);
             lo_num = group_min<WAVES>(lo_num, s_min + kWords, wave, lane);
             const float best = value_of(lo_num & 0xFFFFu, p.map, p.val);   // a row of NaNs: every q is 0
-            uint64_t q[kRegs], part = 0ull;
+            const float c = (p.given & kGivenT) ? uniform_f32(scale_of(tr)) : kLog2e;
+            // The min-p threshold FIRST, one uniform word: best, lo_num, mp and T then end here, and the select's loop below keeps the
+            // registers it had before there was a min-p (with them live across it hipcc serialised the loop's 16 LDS reads).
+            // A row without a number keeps its best key value alone.
+            uint32_t thr_mp = 0xFFFFu;
+            if (mp_on) thr_mp = lo_num == kNoKey ? lo_key : minp_threshold(lo_num, minp_theta(best, tr, c, mp), p.map, p.val);
+            thr_mp = (uint32_t)__builtin_amdgcn_readfirstlane((int)thr_mp);
+            if (!off) {
+                uint64_t q[kRegs], part = 0ull;
 #pragma unroll
-            for (int i = 0; i < kRegs; i++) {
-                q[i] = mass_of_key(t[i], best, p.map, p.val);
-                part += q[i];
-            }
-            const uint64_t qh = mass_of_key(h, best, p.map, p.val);
-            const uint64_t z = group_sum64<WAVES>(part + qh, s_sum, wave, lane);
-            const uint64_t target = mass_target(pr, z);
-            thr = 0u;
-            // (uniform over the wave) whether any lane's first / second group of eight registers holds a key: a short row, or
-            // the last waves of a workgroup, skip the registers that are all kNoKey
-            const bool has0 = q0 < r.body, has1 = q0 + 64u * kGroupKeys < r.body;
+                for (int i = 0; i < kRegs; i++) {
+                    q[i] = mass_of_key(t[i], best, c, p.map, p.val);
+                    part += q[i];
+                }
+                const uint64_t qh = mass_of_key(h, best, c, p.map, p.val);
+                const uint64_t z = group_sum64<WAVES>(part + qh, s_sum, wave, lane);
+                const uint64_t target = mass_target(pr, z);
+                thr = 0u;
+                // (uniform over the wave) whether any lane's first / second group of eight registers holds a key: a short row, or
+                // the last waves of a workgroup, skip the registers that are all kNoKey
+                const bool has0 = q0 < r.body, has1 = q0 + 64u * kGroupKeys < r.body;
 #pragma unroll 1
-            for (int bit = 15; bit >= 0 && target != 0ull; bit--) {   // uniform
-                const uint32_t cand = thr | (1u << bit);
-                uint64_t f = h < cand ? qh : 0ull;
-                if (has0) {
+                for (int bit = 15; bit >= 0 && target != 0ull; bit--) {   // uniform
+                    const uint32_t cand = thr | (1u << bit);
+                    uint64_t f = h < cand ? qh : 0ull;
+                    if (has0) {
 #pragma unroll
-                    for (int i = 0; i < kRegs / 2; i++) f += t[i] < cand ? q[i] : 0ull;
-                }
-                if (has1) {
+                        for (int i = 0; i < kRegs / 2; i++) f += t[i] < cand ? q[i] : 0ull;
+                    }
+                    if (has1) {
 #pragma unroll
-                    for (int i = kRegs / 2; i < kRegs; i++) f += t[i] < cand ? q[i] : 0ull;
+                        for (int i = kRegs / 2; i < kRegs; i++) f += t[i] < cand ? q[i] : 0ull;
+                    }
+                    f = group_sum64<WAVES>(f, s_sum + ((bit & 1) ? kWords : 0), wave, lane);   // z went through the array bit 15 does not take
+                    if (f < target) thr = cand;
                 }
-                f = group_sum64<WAVES>(f, s_sum + ((bit & 1) ? kWords : 0), wave, lane);   // z went through the array bit 15 does not take
-                if (f < target) thr = cand;
+                if (target == 0ull) thr = lo_key;   // p <= 0, or a row of NaNs: the best value alone
             }
-            if (target == 0ull) thr = lo_key;   // p <= 0, or a row of NaNs: the best value alone
+            thr = thr_mp < thr ? thr_mp : thr;   // the stricter of the two thresholds
             selected = thr >= lo_key && lo_key != kNoKey;   // else nothing was selected (never): nothing is stored
             if (!selected && wave == 0u && lane == 0u) atomicOr(p.fault, kToppFaultSelect);
         }
@@ -197,9 +233,21 @@ struct LongParams {
     uint32_t* fault;
     uint16_t* dst;                // [rows][cols], may be `keys`
     uint32_t fill;
+    const float* min_p;           // [rows], device; null: min-p is off for every row
+    const float* temperature;     // [rows], device; null: 1 for every row
+    uint32_t p_null;              // there is no d_p: the select is off for every row, whatever the clear kernel made of the words it read
 };
 
+// What the kernels do with a row.  The clear kernel knows d_p alone: a row is "select off" with the state kOffRow, or in a call
+// without d_p.  Such a row is LIVE through min-p where min_p[row] > 0: the best kernel finds its best number and scan 1 turns that
+// into its threshold; the mass, scan 0 and count kernels skip it.  Scan 1 leaves every row with kOffRow, a threshold or kFailedRow.
+__device__ __forceinline__ bool select_off(const LongParams& p, uint32_t w) { return p.p_null != 0u || w == kOffRow; }
+__device__ __forceinline__ bool in_select(const LongParams& p, uint32_t w) { return p.p_null == 0u && w == 0u; }
+__device__ __forceinline__ bool minp_on(const LongParams& p, uint32_t row) { return p.min_p && p.min_p[row] > 0.0f; }
+
 // Control block, mass bins, row words and row states of a call, the states from the device array: !(p < 1) gives the "off" state.
+// In a call without d_p (LongParams::p_null) `p` is the start of the KEYS and the states made of it mean nothing: every kernel that
+// reads a state's w goes through select_off() / in_select(), and scan 1 rewrites every state.
 // With state == nullptr (short rows) it is the control block alone.
 __global__ void __launch_bounds__(256) topp16_clear_kernel(uint32_t* ctl, uint64_t* mass, uint32_t* cnt, uint4* state, uint32_t rows, const float* p)
 {
@@ -223,7 +271,8 @@ __global__ void __launch_bounds__(kLongThreads) topp16_best_kernel(const LongPar
     __shared__ uint32_t s_part[2 * kLongWaves];
     const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
     if (row >= p.rows) return;
-    if (p.state[row].w != 0u) return;   // uniform
+    const uint32_t w = p.state[row].w;
+    if (select_off(p, w) ? !minp_on(p, row) : w != 0u) return;   // uniform
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const Row16 r = row_of(p.keys, row, p.cols);
     const ChunkRange g = chunk_of(r, p.chunk, c);
@@ -263,15 +312,16 @@ __global__ void __launch_bounds__(kLongThreads) topp16_mass_kernel(const LongPar
     __shared__ unsigned long long s_mass[kBins];
     const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
     if (row >= p.rows) return;
-    if (p.state[row].w != 0u) return;   // uniform
+    if (!in_select(p, p.state[row].w)) return;   // uniform
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     for (uint32_t b = tid; b < kBins; b += kLongThreads) s_mass[b] = 0ull;
     __syncthreads();
     const float best = value_of(p.cnt[(size_t)row * kBins + kWordBestNum] & 0xFFFFu, p.map, p.val);   // a row of NaNs: every q is 0
+    const float scale = row_scale(p.temperature, row);
     const Row16 r = row_of(p.keys, row, p.cols);
     const ChunkRange g = chunk_of(r, p.chunk, c);
     auto add = [&](uint32_t key) __attribute__((always_inline)) {
-        const uint64_t q = mass_of_key(key, best, p.map, p.val);
+        const uint64_t q = mass_of_key(key, best, scale, p.map, p.val);
         if (q != 0ull) atomicAdd(&s_mass[key >> 5], (unsigned long long)q);
     };
     if (c == 0u && wave == 0u) add(load_head(r, lane, p.map));   // uniform
@@ -298,7 +348,7 @@ __global__ void __launch_bounds__(256) topp16_scan0_kernel(const LongParams p)
     const uint32_t row = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     if (row >= p.rows) return;
     const uint4 st = p.state[row];
-    if (st.w != 0u) return;   // uniform
+    if (!in_select(p, st.w)) return;   // uniform
     const uint64_t* const bins = p.mass + (size_t)row * kBins;
     constexpr uint32_t E = kBins / 256u;
     uint64_t c[E], sum = 0ull;
@@ -358,7 +408,7 @@ __global__ void __launch_bounds__(kLongThreads) topp16_count_kernel(const LongPa
     const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
     if (row >= p.rows) return;
     const uint4 st = p.state[row];
-    if (st.w != 0u) return;   // uniform
+    if (!in_select(p, st.w)) return;   // uniform
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     if (tid < 32u) s_hist[tid] = 0u;
     __syncthreads();
@@ -380,21 +430,42 @@ __global__ void __launch_bounds__(kLongThreads) topp16_count_kernel(const LongPa
 }
 
 // Scan 1, one thread per row: F moves on through the bin's 32 values by count * q; the threshold is the last value F stays below T at.
+// Then the min-p threshold where min-p is on, and the stricter of the two; for a row whose select is off it is the threshold.  A row
+// scan 0 ended (T == 0: the best key alone) stays: no min-p threshold is better than the best number.
 __global__ void __launch_bounds__(256) topp16_scan1_kernel(const LongParams p)
 {
     for (uint32_t row = blockIdx.x * blockDim.x + threadIdx.x; row < p.rows; row += gridDim.x * blockDim.x) {
         const uint4 st = p.state[row];
-        if (st.w != 0u) continue;
+        const bool no_select = select_off(p, st.w), mp_on = minp_on(p, row);
+        if (no_select && !mp_on) {
+            if (p.p_null) p.state[row] = make_uint4(0u, 16u, 0u, kOffRow);   // whatever the clear kernel read
+            continue;
+        }
+        if (!no_select && st.w != 0u) continue;
         const uint32_t* const words = p.cnt + (size_t)row * kBins;
-        const float best = value_of(words[kWordBestNum] & 0xFFFFu, p.map, p.val);
-        const uint64_t target = (uint64_t)words[kWordTarget] | ((uint64_t)words[kWordTarget + 1] << 32);
-        uint64_t f = (uint64_t)words[kWordBefore] | ((uint64_t)words[kWordBefore + 1] << 32);   // F(32 bin) < T
-        uint32_t thr = st.x << 5;
+        const uint32_t best_num = words[kWordBestNum], best_key = words[kWordBestKey];
+        const float best = value_of(best_num & 0xFFFFu, p.map, p.val);
+        const float t = p.temperature ? p.temperature[row] : 1.0f, scale = p.temperature ? scale_of(t) : kLog2e;
+        uint32_t thr = 0xFFFFu;
+        if (!no_select) {
+            const uint64_t target = (uint64_t)words[kWordTarget] | ((uint64_t)words[kWordTarget + 1] << 32);
+            uint64_t f = (uint64_t)words[kWordBefore] | ((uint64_t)words[kWordBefore + 1] << 32);   // F(32 bin) < T
+            thr = st.x << 5;
 #pragma unroll 1
-        for (uint32_t d = 0; d < 31u; d++) {
-            f += (uint64_t)words[d] * mass_of_key((st.x << 5) + d, best, p.map, p.val);   // F(32 bin + d + 1)
-            if (f >= target) break;
-            thr = (st.x << 5) + d + 1u;
+            for (uint32_t d = 0; d < 31u; d++) {
+                f += (uint64_t)words[d] * mass_of_key((st.x << 5) + d, best, scale, p.map, p.val);   // F(32 bin + d + 1)
+                if (f >= target) break;
+                thr = (st.x << 5) + d + 1u;
+            }
+        }
+        if (mp_on) {   // a row without a number keeps its best key value alone
+            const uint32_t thr_mp = best_num == kNoKey ? best_key : minp_threshold(best_num, minp_theta(best, t, scale, p.min_p[row]), p.map, p.val);
+            thr = thr_mp < thr ? thr_mp : thr;
+        }
+        if (thr > 0xFFFFu) {   // a row without keys (never): nothing is stored
+            atomicOr(p.fault, kToppFaultSelect);
+            p.state[row] = make_uint4(0u, 0u, st.z, kFailedRow);
+            continue;
         }
         p.state[row] = make_uint4(thr, 0u, st.z, 1u);
     }
@@ -440,12 +511,22 @@ ToppLayout topp_layout(size_t rows, size_t cols)
     return L;
 }
 
-int run_topp(const uint16_t* keys, size_t rows, size_t cols, const float* d_p, const Key16Map& map, const Values16& val, uint32_t fill,
+// The per-row arrays of a call, each of them null where the caller gave none.
+struct RowScalars {
+    const float* p;
+    const float* min_p;
+    const float* temperature;
+};
+
+int run_topp(const uint16_t* keys, size_t rows, size_t cols, const RowScalars& rs, const Key16Map& map, const Values16& val, uint32_t fill,
              uint16_t* dst, char* ws, const ToppLayout& L, hipStream_t stream)
 {
     uint32_t* const ctl = reinterpret_cast<uint32_t*>(ws);
     if (cols <= (size_t)kLocalSortCap) {
-        const ShortParams sp{keys, d_p, (uint32_t)cols, (uint32_t)rows, map, val, ctl, dst, fill};
+        const float* const unused = reinterpret_cast<const float*>(ws + L.state);   // 16 B per row: readable, and no short tier's
+        const uint32_t given = (rs.p ? kGivenP : 0u) | (rs.min_p ? kGivenMinP : 0u) | (rs.temperature ? kGivenT : 0u);
+        const ShortParams sp{keys, rs.p ? rs.p : unused, rs.min_p ? rs.min_p : unused, rs.temperature ? rs.temperature : unused, given,
+                             (uint32_t)cols, (uint32_t)rows, map, val, ctl, dst, fill};
         hipLaunchKernelGGL(topp16_clear_kernel, dim3(1), dim3(256), 0, stream, ctl, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint4*)nullptr, 0u,
                            (const float*)nullptr);
         if (cols <= (size_t)kWaveSegCap)
@@ -470,10 +551,17 @@ int run_topp(const uint16_t* keys, size_t rows, size_t cols, const float* d_p, c
     lp.fault = ctl;
     lp.dst = dst;
     lp.fill = fill;
+    lp.min_p = rs.min_p;
+    lp.temperature = rs.temperature;
+    lp.p_null = rs.p ? 0u : 1u;
+    // The clear kernel takes the row states from an array of `rows` float32 that exists.  Without d_p it reads the first 4 * rows
+    // bytes of the keys from their first 4-byte boundary on (rows of more than 16384 keys: they are there), and p_null tells every
+    // kernel that those states mean nothing.
+    const float* const clear_p = rs.p ? rs.p : reinterpret_cast<const float*>(((uintptr_t)keys + 3) & ~(uintptr_t)3);
     if (lp.chunks > chunk_cap_for(cols)) return LSDSORT_ERR_INVALID_ARG;   // never: chunks are at least kMinChunk keys
     const uint32_t grid = (uint32_t)(rows * lp.chunks), row_grid = (uint32_t)rows;
     hipLaunchKernelGGL(topp16_clear_kernel, dim3(grid_for(rows * kBins, 1024, 4096)), dim3(256), 0, stream, ctl, lp.mass, lp.cnt, lp.state,
-                       (uint32_t)rows, d_p);
+                       (uint32_t)rows, clear_p);
     hipLaunchKernelGGL(topp16_best_kernel, dim3(grid), dim3(kLongThreads), 0, stream, lp);
     hipLaunchKernelGGL(topp16_mass_kernel, dim3(grid), dim3(kLongThreads), 0, stream, lp);
     hipLaunchKernelGGL(topp16_scan0_kernel, dim3(row_grid), dim3(256), 0, stream, lp);
@@ -485,6 +573,27 @@ int run_topp(const uint16_t* keys, size_t rows, size_t cols, const float* d_p, c
 }
 
 bool sizes_ok(size_t rows, size_t cols) { return rows <= LSDSORT_MAX_KEYS && (rows == 0 || cols <= LSDSORT_MAX_KEYS / rows); }
+
+// Both entries.  need_p: the entry without min-p has no defined answer for a NULL d_p.
+int filter_call(const void* d_keys, size_t rows, size_t cols, const RowScalars& rs, bool need_p, int key_type, uint16_t fill_bits, void* d_out,
+                void* d_workspace, size_t workspace_bytes, void* hip_stream)
+{
+    if (key_type != LSDSORT_KEY16_F16 && key_type != LSDSORT_KEY16_BF16) return LSDSORT_ERR_INVALID_ARG;
+    Key16Map map;
+    LSD_TRY(key16_map(key_type, 1, &map));
+    const Values16 val{key_type == LSDSORT_KEY16_BF16 ? 0x007Fu : 0x03FFu, key_type == LSDSORT_KEY16_BF16 ? 1u : 0u};
+    if (!lsd::sizes_ok(rows, cols)) return LSDSORT_ERR_TOO_LARGE;
+    if (rows == 0 || cols == 0) return LSDSORT_OK;
+    if (!d_keys || !d_out || (((uintptr_t)d_keys | (uintptr_t)d_out) & 1)) return LSDSORT_ERR_INVALID_ARG;
+    if ((need_p && !rs.p) || ((uintptr_t)rs.p & 3)) return LSDSORT_ERR_INVALID_ARG;   // their values are the device's to read
+    if ((((uintptr_t)rs.min_p | (uintptr_t)rs.temperature) & 3)) return LSDSORT_ERR_INVALID_ARG;
+    const lsd::ToppLayout L = lsd::topp_layout(rows, cols);
+    if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.end)) return LSDSORT_ERR_WORKSPACE;
+    int rank_method = 0;   // asked for the device set-up alone: nothing here ranks with the returning add
+    LSD_TRY(lsd::device_rank_method(8, &rank_method));
+    return lsd::run_topp(static_cast<const uint16_t*>(d_keys), rows, cols, rs, map, val, (uint32_t)fill_bits, static_cast<uint16_t*>(d_out),
+                         static_cast<char*>(d_workspace), L, static_cast<hipStream_t>(hip_stream));
+}
 
 }  // namespace
 }  // namespace lsd
@@ -500,20 +609,16 @@ size_t lsdsort_topp16_filter_workspace_bytes(size_t rows, size_t cols)
 int lsdsort_topp16_filter_device(const void* d_keys, size_t rows, size_t cols, const float* d_p, int key_type, uint16_t fill_bits, void* d_out,
                                  void* d_workspace, size_t workspace_bytes, void* hip_stream)
 {
-    if (key_type != LSDSORT_KEY16_F16 && key_type != LSDSORT_KEY16_BF16) return LSDSORT_ERR_INVALID_ARG;
-    Key16Map map;
-    LSD_TRY(key16_map(key_type, 1, &map));
-    const Values16 val{key_type == LSDSORT_KEY16_BF16 ? 0x007Fu : 0x03FFu, key_type == LSDSORT_KEY16_BF16 ? 1u : 0u};
-    if (!lsd::sizes_ok(rows, cols)) return LSDSORT_ERR_TOO_LARGE;
-    if (rows == 0 || cols == 0) return LSDSORT_OK;
-    if (!d_keys || !d_out || (((uintptr_t)d_keys | (uintptr_t)d_out) & 1)) return LSDSORT_ERR_INVALID_ARG;
-    if (!d_p || ((uintptr_t)d_p & 3)) return LSDSORT_ERR_INVALID_ARG;   // their values are the device's to read
-    const lsd::ToppLayout L = lsd::topp_layout(rows, cols);
-    if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.end)) return LSDSORT_ERR_WORKSPACE;
-    int rank_method = 0;   // asked for the device set-up alone: nothing here ranks with the returning add
-    LSD_TRY(lsd::device_rank_method(8, &rank_method));
-    return lsd::run_topp(static_cast<const uint16_t*>(d_keys), rows, cols, d_p, map, val, (uint32_t)fill_bits, static_cast<uint16_t*>(d_out),
-                         static_cast<char*>(d_workspace), L, static_cast<hipStream_t>(hip_stream));
+    return lsd::filter_call(d_keys, rows, cols, lsd::RowScalars{d_p, nullptr, nullptr}, true, key_type, fill_bits, d_out, d_workspace,
+                            workspace_bytes, hip_stream);
+}
+
+int lsdsort_topp16_filter_ex_device(const void* d_keys, size_t rows, size_t cols, const float* d_p, const float* d_min_p,
+                                    const float* d_temperature, int key_type, uint16_t fill_bits, void* d_out, void* d_workspace,
+                                    size_t workspace_bytes, void* hip_stream)
+{
+    return lsd::filter_call(d_keys, rows, cols, lsd::RowScalars{d_p, d_min_p, d_temperature}, false, key_type, fill_bits, d_out, d_workspace,
+                            workspace_bytes, hip_stream);
 }
 
 }  // extern "C"
