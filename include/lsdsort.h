@@ -672,6 +672,54 @@ LSDSORT_API int lsdsort_sample16_ex_device(const void* d_keys, size_t rows, size
                                            float* d_logprob /* [rows], or NULL */, void* d_workspace, size_t workspace_bytes,
                                            void* hip_stream);
 
+/* LOG-PROBABILITIES and RANKS of GIVEN tokens of float16 / bfloat16 logit rows (lsdradixsort_amd/csrc/logprob16.hip; DESIGN.md
+ * section 6.17): what a server returns next to the token -- `logprobs` / `top_logprobs`, the rank of the sampled token, prompt
+ * log-probabilities, the forward of a cross-entropy loss -- without a float32 copy of the row.  d_ids is a DEVICE array of
+ * rows * slots int32 (4-byte aligned), 1 <= slots <= LSDSORT_LOGPROB_MAX_SLOTS; slot s of row r asks for key i = d_ids[r * slots + s]
+ * of row r, with value x.  key_type is LSDSORT_KEY16_F16 or LSDSORT_KEY16_BF16.
+ * Masses: m, c = log2(e) / T_r, w, q = floor(w * 2^32) and the integer sum Z are exactly those of lsdsort_sample16_ex_device, from the
+ * same device functions; d_temperature as there (NULL: 1 in every row; !(T > 0) or a T so small that c overflows: GREEDY).
+ * d_logprob[r * slots + s] = (x == m ? 0 : (x - m) * c * ln 2) - ln(Z * 2^-32) in float32, the factor taken as 1 for T = 1: the
+ * expression the draw stores, in its order.  Called on the index the draw returned, with the same keys and temperature, this entry
+ * gives THE BITS of the draw's d_logprob, in every size class.  A -inf under a finite maximum gives exactly -inf; a greedy row gives
+ * -ln(ties) on the maximum's duplicates and -inf elsewhere; a NaN key gives NaN; a row without a number (Z == 0) gives NaN in every
+ * slot.  Tolerance, for |logit| <= 64, cols <= 2^17 and T greedy or >= 2^-10: within 2^-11 + 2^-22 * |(x - m) / T| of float64.
+ * d_rank (optional, NULL: none): d_rank[r * slots + s] is the number of keys of row r that are numbers and strictly greater than x BY
+ * VALUE, (row.float() > x).sum(): NaNs count for nothing, -0.0 and +0.0 are equal, the maximum and all its ties have rank 0.  -1 where
+ * x is a NaN.  Exact, and independent of the temperature.
+ * d_lse (optional, NULL: none): d_lse[r] = value(m) * c * ln 2 + ln(Z * 2^-32), the log-sum-exp of the tempered row, within
+ * 2^-11 + 2^-22 * |m / T| of float64 under the conditions above; NaN for a greedy row and for a row without a number, +inf / -inf
+ * where m is an infinity.
+ * An id below 0 or at or above cols is PADDING: its slot stores logprob NaN and rank -1 and raises no flag -- data, not a fault; a
+ * ragged top-n is padded with -1.  Every word of the three outputs is written on every call.  This entry sets no fault bit: it clears
+ * the control block, so lsdsort_check_device answers OK.
+ * The host reads neither d_ids nor d_temperature and no launch is sized from them: capturable after lsdsort_prepare_device, and ids,
+ * temperatures and keys are read again on every replay of a captured graph.  d_keys is READ ONLY, needs 2-byte alignment only, and
+ * cols may be odd.  Stores go to the three outputs under r < rows only.  The result is DETERMINISTIC: integer sums and counts do not depend on the chunking, on
+ * the order of the atomics or on the other rows; the same row, ids and T give the same bits in any batch and any size class.
+ * Kernels: rows of up to 1024 keys (one wavefront) and up to 16384 (one workgroup) are loaded into registers once, behind the loads of
+ * the row's ids and of the keys they name: the maximum by an integer reduction, Z by an integer sum, per slot the queried key broadcast
+ * and the better keys counted by ballot and popcount; lane s stores slot s: one read of the row (2 B/key by byte accounting).  Longer
+ * rows, launches sized from (rows, cols, slots, whether d_rank was given): the best number per chunk (integer atomicMin), the sum of q
+ * per chunk (one plain 64-bit store per chunk, every chunk on every call) with the per-slot counts (integer atomicAdd), and one
+ * wavefront per row that finishes: two reads, 4 B/key.  Stream-ordered, no host synchronisation, nothing allocated; phases are ordered
+ * by kernel boundaries.  The result does not depend on lsdsort_set_rank_method.
+ * Checks, in order, each before a device is touched: key_type other than float16 / bfloat16 (INVALID_ARG), slots 0 or above
+ * LSDSORT_LOGPROB_MAX_SLOTS (INVALID_ARG), rows or rows * cols above LSDSORT_MAX_KEYS (TOO_LARGE), rows == 0 or cols == 0 (OK, nothing
+ * launched), a NULL or odd d_keys (INVALID_ARG), a NULL d_ids or d_logprob or one that is not 4-byte aligned (INVALID_ARG), a non-NULL
+ * d_rank, d_lse or d_temperature that is not 4-byte aligned (INVALID_ARG), the workspace (WORKSPACE: NULL, not 256-byte aligned, or
+ * below lsdsort_logprob16_workspace_bytes), the device (NO_DEVICE).
+ * lsdsort_logprob16_workspace_bytes is a multiple of 256, monotonic in each argument, 0 above the limits and for a bad `slots`,
+ * independent of which optional outputs are given, and O(rows * slots): the control block, 4 B per row, and for rows above 16384 keys
+ * 8 B per 16384 keys of a row and 4 B per slot. */
+#define LSDSORT_LOGPROB_MAX_SLOTS 32
+LSDSORT_API size_t lsdsort_logprob16_workspace_bytes(size_t rows, size_t cols, size_t slots);
+LSDSORT_API int lsdsort_logprob16_device(const void* d_keys, size_t rows, size_t cols, const int32_t* d_ids /* DEVICE, [rows][slots] */,
+                                         size_t slots, const float* d_temperature /* DEVICE, [rows], or NULL: 1 */,
+                                         int key_type /* float16 or bfloat16 */, float* d_logprob /* [rows][slots] */,
+                                         int32_t* d_rank /* [rows][slots], or NULL */, float* d_lse /* [rows], or NULL */,
+                                         void* d_workspace, size_t workspace_bytes, void* hip_stream);
+
 /* After the stream has drained: LSDSORT_OK, or LSDSORT_ERR_DEVICE_FAULT if a kernel of the
  * last sort on this workspace gave up a bounded spin or refused destinations outside the output
  * (never expected; the output is then undefined).  Synchronises hip_stream.  With LSDSORT_REPROBE=1

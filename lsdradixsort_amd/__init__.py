@@ -21,6 +21,7 @@ from .api import (  # noqa: F401  (api.__all__, name for name)
     GPUKth16PerRow, kth16_perrow_workspace_bytes, GPUTopK16Filter, topk16_filter_workspace_bytes, topk16_filter_rows,
     GPUTopP16Filter, topp16_filter_workspace_bytes, topp16_filter_rows,
     GPUSample16, sample16_workspace_bytes, sample16_rows,
+    GPULogprob16, logprob16_workspace_bytes, logprobs16_rows, top_logprobs16_rows,
     BuildHistograms, BuildOffsets, RankScatter, DigitHistograms,
     MSBPartition, SplitterPartition, ThresholdPartition, sharded_thresholds,
 )

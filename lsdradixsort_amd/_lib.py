@@ -123,6 +123,9 @@ SIGNATURES = {
                                         ctypes.c_void_p, c_size, ctypes.c_void_p]),
     "lsdsort_sample16_ex_device": (c_int, [ctypes.c_void_p, c_size, c_size, ctypes.c_void_p, ctypes.c_void_p, c_int, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, c_size, ctypes.c_void_p]),
+    "lsdsort_logprob16_workspace_bytes": (c_size, [c_size, c_size, c_size]),
+    "lsdsort_logprob16_device": (c_int, [ctypes.c_void_p, c_size, c_size, ctypes.c_void_p, c_size, ctypes.c_void_p, c_int, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_size, ctypes.c_void_p]),
     "lsdsort_u32_device_timed": (c_int, [c_u32p, c_u32p, ctypes.c_void_p, c_size, c_size, c_int, c_int,
                                          ctypes.c_void_p, ctypes.POINTER(LsdsortTiming)]),
     "lsdsort_tile_keys": (c_size, [c_int]),

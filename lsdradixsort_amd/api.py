@@ -31,6 +31,7 @@ __all__ = [
     "GPUKth16PerRow", "kth16_perrow_workspace_bytes", "GPUTopK16Filter", "topk16_filter_workspace_bytes", "topk16_filter_rows",
     "GPUTopP16Filter", "topp16_filter_workspace_bytes", "topp16_filter_rows",
     "GPUSample16", "sample16_workspace_bytes", "sample16_rows",
+    "GPULogprob16", "logprob16_workspace_bytes", "logprobs16_rows", "top_logprobs16_rows",
     "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
     "MSBPartition", "SplitterPartition", "ThresholdPartition", "sharded_thresholds",
 ]
@@ -1311,6 +1312,138 @@ def sample16_rows(x, u=None, top_k=None, top_p=None, generator=None, return_logp
         if return_logprobs:
             return got[0].to(torch.int64).view(x.shape[:-1]), got[1].view(x.shape[:-1])
         return got.to(torch.int64).view(x.shape[:-1])
+
+
+def logprob16_workspace_bytes(rows: int, cols: int, slots: int) -> int:
+    """Bytes of device workspace ``GPULogprob16`` needs for ``slots`` ids in each of ``rows`` rows of ``cols`` 16-bit keys (whatever the
+    ids, with or without ranks and the log-sum-exp); 0 for a ``slots`` outside 1 .. ``LSDSORT_LOGPROB_MAX_SLOTS``."""
+    return int(lib().lsdsort_logprob16_workspace_bytes(rows, cols, slots))
+
+
+def _optional_out(arg, name: str, dtype, shape, device):
+    """An optional output asked for as ``False`` (none), ``True`` (a new tensor) or a contiguous CUDA tensor of ``dtype`` with
+    ``shape``'s element count to fill."""
+    torch = _torch()
+    if isinstance(arg, torch.Tensor):
+        _dev(arg, name, (dtype,))
+        if arg.numel() != int(np.prod(shape, dtype=np.int64)):
+            raise ValueError(f"{name}: {int(np.prod(shape, dtype=np.int64))} entries, got {arg.numel()}")
+        return arg
+    if not isinstance(arg, bool):
+        raise TypeError(f"{name}: a bool, or a contiguous {str(dtype).replace('torch.', '')} CUDA tensor")
+    return torch.empty(shape, dtype=dtype, device=device) if arg else None
+
+
+def GPULogprob16(d_keys, d_ids, key_type: str = "bfloat16", ranks=False, lse=False, d_temperature=None, out=None, workspace=None,
+                 stream=None, check_fault: bool = False):
+    """The log-probabilities of given tokens of every row (``lsdsort_logprob16_device``): ``d_keys`` a contiguous 1-D or 2-D float16 /
+    bfloat16 CUDA tensor of logits, ``d_ids`` a contiguous int32 CUDA tensor ``[rows, slots]`` or ``[rows]`` (one slot), read on the
+    device, with at most ``LSDSORT_LOGPROB_MAX_SLOTS`` slots.  Entry ``(r, s)`` of the result is the float32 log-probability of key
+    ``d_ids[r, s]`` of row ``r`` under the row's softmax -- ``torch.log_softmax(row.float() / T_r, -1)[id]`` without the float32 row --
+    from the masses and the integer sum of ``GPUSample16``: called on the index the draw returned it gives the bits of the draw's
+    logprob.  A NaN key, an id below 0 or at or above the row length (padding) and a row without a number give NaN; a -inf under a
+    finite maximum gives -inf.  ``ranks`` -- ``True``, or a contiguous int32 CUDA tensor of the ids' shape to fill -- adds the number of
+    keys of the row that are numbers and strictly greater by value (``(row.float() > x).sum()``; -1 for a NaN key and for padding);
+    ``lse`` -- ``True``, or a float32 CUDA tensor ``[rows]`` -- adds the log-sum-exp of the tempered row (NaN for a greedy row and a row
+    without a number).  ``d_temperature``: a contiguous float32 CUDA tensor with one entry per row, as in ``GPUSample16`` (``T_r`` not
+    above 0: greedy).  Returns the logprob tensor (``out`` where one is given), or with ``ranks`` / ``lse`` the tuple
+    ``(logprob[, rank][, lse])``.  The host reads none of the arrays: a captured graph follows their contents.  Stream-ordered;
+    ``d_keys`` is only read: rows of up to 16384 keys once, longer ones twice."""
+    torch = _torch()
+    _dev(d_keys, "d_keys", (torch.float16, torch.bfloat16), dims=(1, 2))
+    if key_type not in ("float16", "bfloat16"):
+        raise ValueError(f'key_type: "float16" or "bfloat16", got {key_type!r}')
+    code, rows, cols = _keys16(d_keys, key_type, "is scored")
+    _dev(d_ids, "d_ids", (torch.int32,), dims=(1, 2))
+    if d_ids.shape[0] != rows:
+        raise ValueError(f"d_ids: one row of ids per row ({rows}), got {d_ids.shape[0]}")
+    slots = 1 if d_ids.dim() == 1 else d_ids.shape[1]
+    if not 1 <= slots <= errors.LSDSORT_LOGPROB_MAX_SLOTS:
+        raise ValueError(f"d_ids: 1 .. {errors.LSDSORT_LOGPROB_MAX_SLOTS} ids per row, got {slots}")
+    _row_array(d_temperature, "d_temperature", rows)
+    if out is not None:
+        _dev(out, "out", (torch.float32,))
+        if out.numel() != rows * slots:
+            raise ValueError(f"out: one entry per id ({rows * slots}), got {out.numel()}")
+    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
+        logprob = out if out is not None else torch.empty(d_ids.shape, dtype=torch.float32, device=d_keys.device)
+        rank = _optional_out(ranks, "ranks", torch.int32, d_ids.shape, d_keys.device)
+        total = _optional_out(lse, "lse", torch.float32, (rows,), d_keys.device)
+    if workspace is None:
+        nbytes = logprob16_workspace_bytes(rows, cols, slots)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_logprob16_workspace_bytes", "too many keys or rows")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    ptr = [t.data_ptr() if t is not None else None for t in (d_temperature, rank, total)]
+    check(lib().lsdsort_logprob16_device(d_keys.data_ptr(), rows, cols, d_ids.data_ptr(), slots, ptr[0], code, logprob.data_ptr(), ptr[1],
+                                         ptr[2], workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_logprob16_device")
+    if check_fault and rows and cols:
+        _check_fault(workspace, stream)
+    got = (logprob,) + tuple(t for t in (rank, total) if t is not None)
+    return got if len(got) > 1 else logprob
+
+
+def logprobs16_rows(x, ids, temperature=None, return_ranks: bool = False, return_lse: bool = False, stream=None):
+    """``torch.log_softmax(x.float() / T, -1).gather(-1, ids)`` for a float16 / bfloat16 CUDA tensor of logits of one or more
+    dimensions, without the float32 passes over the rows: ``ids`` is an int32 / int64 CUDA tensor of shape ``x.shape[:-1]`` (one id per
+    row: the sampled token, the next prompt token, a cross-entropy target) or ``x.shape[:-1] + (n,)``; the result has its shape.  An id
+    below 0 or at or above the row length is padding and gives NaN, as does a NaN logit.  More than ``LSDSORT_LOGPROB_MAX_SLOTS`` ids
+    per row take several calls.  ``temperature`` takes the forms of ``sample16_rows`` (``T_r <= 0``: greedy).  With ``return_ranks``
+    also the int64 ranks ``(x.float() > x.gather(-1, ids)).sum(-1)`` (-1 for padding and NaN logits), with ``return_lse`` the float32
+    log-sum-exp of every tempered row, of shape ``x.shape[:-1]``: ``(logprobs[, ranks][, lse])``."""
+    torch = _torch()
+    _dev(x, "x", (torch.float16, torch.bfloat16), contiguous=False)
+    if x.dim() == 0:
+        raise TypeError("x: at least one dimension")
+    _dev(ids, "ids", (torch.int32, torch.int64), contiguous=False)
+    lead = tuple(x.shape[:-1])
+    if tuple(ids.shape) != lead and tuple(ids.shape[:-1]) != lead:
+        raise ValueError(f"ids: the shape of x without its last dimension {lead}, or that with a last dimension of ids per row; got {tuple(ids.shape)}")
+    cols = x.shape[-1]
+    rows = int(np.prod(lead, dtype=np.int64))
+    n = 1 if tuple(ids.shape) == lead else ids.shape[-1]
+    step = errors.LSDSORT_LOGPROB_MAX_SLOTS
+    with _on_stream(stream):
+        d_t = _p_per_row(temperature, rows, x.device, "temperature") if temperature is not None else None
+        if rows == 0 or cols == 0 or n == 0:
+            got = (torch.full(ids.shape, float("nan"), dtype=torch.float32, device=x.device),)
+            got += (torch.full(ids.shape, -1, dtype=torch.int64, device=x.device),) if return_ranks else ()
+            got += (torch.full(lead, float("nan"), dtype=torch.float32, device=x.device),) if return_lse else ()
+            return got if len(got) > 1 else got[0]
+        flat = x.contiguous().view(rows, cols)
+        wide = ids.reshape(rows, n)
+        if wide.dtype != torch.int32:   # what does not fit 32 bits names no key
+            wide = torch.where((wide < 0) | (wide >= cols), torch.full_like(wide, -1), wide).to(torch.int32)
+        logprob = torch.empty((rows, n), dtype=torch.float32, device=x.device)
+        rank = torch.empty((rows, n), dtype=torch.int32, device=x.device) if return_ranks else None
+        total = None
+        for a in range(0, n, step):
+            part = wide[:, a:a + step].contiguous()
+            got = GPULogprob16(flat, part, key_type=str(x.dtype).replace("torch.", ""), ranks=bool(return_ranks),
+                               lse=bool(return_lse) and a == 0, d_temperature=d_t, stream=stream)
+            got = got if isinstance(got, tuple) else (got,)
+            logprob[:, a:a + step] = got[0]
+            if return_ranks:
+                rank[:, a:a + step] = got[1]
+            if return_lse and a == 0:
+                total = got[-1]
+        out = (logprob.view(ids.shape),)
+        out += (rank.view(ids.shape).to(torch.int64),) if return_ranks else ()
+        out += (total.view(lead),) if return_lse else ()
+        return out if len(out) > 1 else out[0]
+
+
+def top_logprobs16_rows(x, n: int, temperature=None, stream=None):
+    """The ``top_logprobs=n`` of a request in two calls and without a float32 row: ``topk16_rows(x, n)`` and the log-probabilities of
+    its positions under the softmax of ``x / T`` -> ``(logprobs, indices)``, float32 and int64 of shape ``x.shape[:-1] + (n,)``, best
+    first.  The order is ``topk16_rows``'s: +NaN logits come in front of +inf (their logprob is NaN), among equal logits the lower
+    position first.  ``n`` may exceed ``LSDSORT_LOGPROB_MAX_SLOTS``."""
+    torch = _torch()
+    _dev(x, "x", (torch.float16, torch.bfloat16), contiguous=False)
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError("n: a positive int")
+    _, indices = topk16_rows(x, n, largest=True, stream=stream)
+    return logprobs16_rows(x, indices, temperature=temperature, stream=stream), indices
 
 
 def rows16_workspace_bytes(rows: int, cols: int) -> int:

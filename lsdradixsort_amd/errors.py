@@ -20,6 +20,7 @@ LSDSORT_MAX_KEYS = 0x3FFFFFFF
 LSDSORT_MAX_PASSES = 32
 LSDSORT_ROWS16_NATIVE_MAX_COLS = 262144   # lsdsort_rows16_device: longer rows take the widen route
 LSDSORT_KTH_MAX_RANKS = 8                 # lsdsort_kth_multi_device: ranks per call
+LSDSORT_LOGPROB_MAX_SLOTS = 32            # lsdsort_logprob16_device: ids per row and call
 
 LSDSORT_KEY_U32, LSDSORT_KEY_I32, LSDSORT_KEY_F32 = 0, 1, 2
 LSDSORT_KEY_U64, LSDSORT_KEY_I64, LSDSORT_KEY_F64 = 3, 4, 5
