@@ -106,6 +106,14 @@ LSDSORT_API int lsdsort_pairs_u32(uint32_t* keys, uint32_t* vals, size_t n);
  * made for n serves every smaller sort with the same (radix_bits, pairs, algorithm). */
 LSDSORT_API size_t lsdsort_workspace_bytes(size_t n, int radix_bits, int pairs);
 LSDSORT_API size_t lsdsort_workspace_bytes_ex(size_t n, int radix_bits, int pairs, int algorithm);
+/* The workspace of a keys-only sort (default algorithm) with room for the hybrid form's HALF variant (lsdsort_set_half_hop):
+ * lsdsort_workspace_bytes(n, radix_bits, 0), and where the variant can be attempted -- 8-bit digits, about 1.58e8 .. 3.3e8 keys
+ * (the sizes sorted in 2^15 buckets), the default tile -- behind it 2 n bytes for the low halves of the keys (256-byte aligned),
+ * 65536 words for the counts and 32768 words of bucket splits.  Everywhere else it equals lsdsort_workspace_bytes(n,
+ * radix_bits, 0).  A sort given at least this much runs the variant where the device takes it; given less (the plain size
+ * included) it runs exactly what it ran without.  The entries that take keys of other types, payloads, or a shard
+ * (lsdsort_u32_device_prefixed) never run it. */
+LSDSORT_API size_t lsdsort_workspace_bytes_roomy(size_t n, int radix_bits);
 
 /* Replaces GPULSDRadixSort(a, b, h, block_sums, d, grid, block, ...), .cu:839-910: device
  * pointers, result in d_keys (the reference's `a`; the pass count is even), stream-ordered
@@ -786,6 +794,17 @@ LSDSORT_API int lsdsort_rank_scatter_u32_device(const uint32_t* d_in, uint32_t* 
  * out).  Needs the returning-LDS-add rank form (LSDSORT_ERR_UNSUPPORTED where the device probe failed). */
 LSDSORT_API int lsdsort_local_sort_u32_device(uint32_t* d_keys, uint32_t* d_vals, const uint32_t* d_bases, size_t num_buckets,
                                               int low_bits, void* hip_stream);
+/* The same stage reading HALVES, as the hybrid form's half variant runs it (lsdsort_set_half_hop): position q of bucket b is read
+ * as the 16-bit word d_halves[d_bases[b] + q] and rebuilt as
+ *     key = high | ((2 b + (q >= d_first[b])) >> t) << 16 | half
+ * with the three device words d_words = { t (0 .. 7), high (the t top bits every key shares, in place; 0 for t = 0), low_bits
+ * (17 - t in a whole sort) }; the bucket is sorted by its keys' low `low_bits` bits (nine bits, then the rest; a digit that is
+ * the same for every key of a bucket is no pass) and the full keys are stored to d_keys_out[d_bases[b] ..], which is never
+ * read.  d_first: num_buckets words.  The 10240-key kernel: a larger bucket raises bit 3 of *d_fault (may be NULL) and its range
+ * of d_keys_out is left as it was.  num_buckets at most 65536.  UNSUPPORTED where the device probe failed. */
+LSDSORT_API int lsdsort_local_sort_halves_u32_device(uint32_t* d_keys_out, const uint16_t* d_halves, const uint32_t* d_bases,
+                                                     const uint32_t* d_first, size_t num_buckets, const uint32_t* d_words,
+                                                     uint32_t* d_fault, void* hip_stream);
 
 /* One read of all keys -> all 32/radix_bits digit histograms, d_hist[g][d] (uint32). */
 LSDSORT_API int lsdsort_digit_histograms_u32_device(const uint32_t* d_keys, size_t n, int radix_bits,
@@ -960,6 +979,14 @@ LSDSORT_API int lsdsort_set_pass_skipping(int on);
  * 10 % for the attempt, 1 % where a 65536-key sample already shows it).  Same result either way.  On by default; 0 = always
  * the ordinary passes, the reference's structure. */
 LSDSORT_API int lsdsort_set_hybrid(int on);
+/* The hybrid form's HALF variant (lsdradixsort_amd/csrc/half_hop.hip): after the second global pass the array is sorted by the 16
+ * bits below the key prefix, so those bits of a key follow from its position and the exact counts of the 2^16 groups of equal
+ * such bits.  The second pass then writes, and the local stage reads, only the low 16 bits of every key: 4 + 8 + 6 + 6 = 24
+ * bytes per key instead of 28.  Attempted for uint32 keys without payloads at 8-bit digits in 2^15 buckets, in a workspace of
+ * at least lsdsort_workspace_bytes_roomy(n, 8); the device runs it iff it runs the hybrid form and every bucket fits the
+ * 10240-key local kernel, otherwise the full-key launches run, as without it.  Same result either way.  On by default
+ * (LSDSORT_HALF_HOP=0 in the environment starts it off); 0 = never attempted. */
+LSDSORT_API int lsdsort_set_half_hop(int on);
 /* Sorts of up to 16384 keys or pairs (uint32, default algorithm and rank form) are ONE launch: one workgroup sorts them inside
  * its LDS in four 8-bit digit passes (lsdradixsort_amd/csrc/local_sort.hip) instead of clear + stage 1 + stage 2 + 32 / r passes,
  * whose own latencies are all there is at this size (12 us instead of 39).  Same result.  On by default; 0 = the chained form at
@@ -968,6 +995,9 @@ LSDSORT_API int lsdsort_set_small_sort(int on);
 /* Which form the last sort queued on `hip_stream` in this workspace ran: *hybrid = 1 the hybrid form, 0 the ordinary passes (also
  * where the hybrid form was not tried).  Reads the device's verdict back: synchronises the stream. */
 LSDSORT_API int lsdsort_workspace_form(const void* d_workspace, void* hip_stream, int* hybrid);
+/* ... and whether it ran the half variant of it: *half = 1 if so (lsdsort_workspace_form then says 1 as well), else 0.
+ * Synchronises the stream. */
+LSDSORT_API int lsdsort_workspace_half(const void* d_workspace, void* hip_stream, int* half);
 /* lsdsort_u32_device for a SHARD of a range-partitioned array: every key is expected to agree with the others on its top
  * `common_prefix_bits` bits (0 .. 8) -- what a rank holds after the MSB-bucket exchange of the multi-GPU sort (north_star;
  * csrc/sharded.hip calls this).  The hybrid form takes its buckets BELOW a key prefix (with the prefix inside them a shard's 2^15

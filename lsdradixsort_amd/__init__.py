@@ -8,8 +8,8 @@ library, or without a gfx950 device, every entry raises.
 from .errors import (LSDSORT_ALGO_ONESWEEP, LSDSORT_ALGO_STAGED, LSDSORT_MAX_KEYS, LsdsortError)  # noqa: F401
 from ._lib import LIB_PATH, lib  # noqa: F401
 from .api import (  # noqa: F401  (api.__all__, name for name)
-    sort, sort_pairs, to_device, to_host, workspace_bytes, alloc_workspace, workspace_form, tile_keys,
-    set_tile_config, set_xcd_chunk, set_hybrid, set_small_sort, set_pass_skipping, set_rank_method, rank_method,
+    sort, sort_pairs, to_device, to_host, workspace_bytes, alloc_workspace, workspace_form, workspace_half, tile_keys,
+    set_tile_config, set_xcd_chunk, set_hybrid, set_half_hop, set_small_sort, set_pass_skipping, set_rank_method, rank_method,
     GPULSDRadixSort, GPULSDRadixSortTimed, GPUSortMulti, GPUSortTyped, GPUSortWide, sort64,
     GPUSort16, keys16_workspace_bytes, set_keys16_route, sort16, GPUTopK16, topk16_workspace_bytes, topk16_rows,
     GPUSortRows16, rows16_workspace_bytes, set_rows16_route, sort_rows16,

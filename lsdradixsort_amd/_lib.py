@@ -65,6 +65,7 @@ SIGNATURES = {
     "lsdsort_release_host_cache": (c_int, []),
     "lsdsort_workspace_bytes": (c_size, [c_size, c_int, c_int]),
     "lsdsort_workspace_bytes_ex": (c_size, [c_size, c_int, c_int, c_int]),
+    "lsdsort_workspace_bytes_roomy": (c_size, [c_size, c_int]),
     "lsdsort_u32_device": (c_int, [c_u32p, ctypes.c_void_p, c_size, c_size, c_int, ctypes.c_void_p]),
     "lsdsort_pairs_u32_device": (c_int, [c_u32p, c_u32p, ctypes.c_void_p, c_size, c_size, c_int, ctypes.c_void_p]),
     "lsdsort_u32_device_ex": (c_int, [c_u32p, c_u32p, ctypes.c_void_p, c_size, c_size, c_int, c_int, ctypes.c_void_p]),
@@ -135,6 +136,7 @@ SIGNATURES = {
     "lsdsort_rank_scatter_u32_device": (c_int, [c_u32p, c_u32p, c_u32p, c_u32p, c_u32p, c_size, c_int, c_int,
                                                 ctypes.c_void_p]),
     "lsdsort_local_sort_u32_device": (c_int, [c_u32p, c_u32p, c_u32p, c_size, c_int, ctypes.c_void_p]),
+    "lsdsort_local_sort_halves_u32_device": (c_int, [c_u32p, ctypes.c_void_p, c_u32p, c_u32p, c_size, c_u32p, c_u32p, ctypes.c_void_p]),
     "lsdsort_digit_histograms_u32_device": (c_int, [c_u32p, c_size, c_int, c_u32p, ctypes.c_void_p]),
     "lsdsort_msb_partition_workspace_bytes": (c_size, [c_size, c_int]),
     "lsdsort_msb_partition_u32_device": (c_int, [c_u32p, c_u32p, c_size, c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -177,8 +179,10 @@ SIGNATURES = {
     "lsdsort_set_xcd_chunk": (c_int, [c_int]),
     "lsdsort_set_pass_skipping": (c_int, [c_int]),
     "lsdsort_set_hybrid": (c_int, [c_int]),
+    "lsdsort_set_half_hop": (c_int, [c_int]),
     "lsdsort_set_small_sort": (c_int, [c_int]),
     "lsdsort_workspace_form": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(c_int)]),
+    "lsdsort_workspace_half": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(c_int)]),
     "lsdsort_u32_device_prefixed": (c_int, [c_u32p, ctypes.c_void_p, c_size, c_size, c_int, c_int, ctypes.c_void_p]),
     "lsdsort_set_rank_method": (c_int, [c_int]),
     "lsdsort_rank_method": (c_int, [c_int]),

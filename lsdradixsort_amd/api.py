@@ -18,8 +18,8 @@ from .errors import KEY_TYPES_16, KEY_TYPES_32, KEY_TYPES_64, LSDSORT_ALGO_ONESW
 
 # exactly what __init__.py re-exports from here (tests/test_python_face_cpu.py)
 __all__ = [
-    "sort", "sort_pairs", "to_device", "to_host", "workspace_bytes", "alloc_workspace", "workspace_form", "tile_keys",
-    "set_tile_config", "set_xcd_chunk", "set_hybrid", "set_small_sort", "set_pass_skipping", "set_rank_method", "rank_method",
+    "sort", "sort_pairs", "to_device", "to_host", "workspace_bytes", "alloc_workspace", "workspace_form", "workspace_half", "tile_keys",
+    "set_tile_config", "set_xcd_chunk", "set_hybrid", "set_half_hop", "set_small_sort", "set_pass_skipping", "set_rank_method", "rank_method",
     "GPULSDRadixSort", "GPULSDRadixSortTimed", "GPUSortMulti", "GPUSortTyped", "GPUSortWide", "sort64",
     "GPUSort16", "keys16_workspace_bytes", "set_keys16_route", "sort16", "GPUTopK16", "topk16_workspace_bytes", "topk16_rows",
     "GPUSortRows16", "rows16_workspace_bytes", "set_rows16_route", "sort_rows16",
@@ -143,7 +143,11 @@ def _check_fault(workspace, stream, entry: str = "lsdsort_check_device", *shape,
 
 
 def workspace_bytes(n: int, radix_bits: int = 8, pairs: int = False, algorithm: int = LSDSORT_ALGO_ONESWEEP) -> int:
-    """Bytes of device workspace for a sort of up to ``n`` keys; ``pairs``: the number of payload arrays (False / True / 2 / 3)."""
+    """Bytes of device workspace for a sort of up to ``n`` keys; ``pairs``: the number of payload arrays (False / True / 2 / 3).
+    Keys only, default algorithm: the roomy size (``lsdsort_workspace_bytes_roomy``), which lets the hybrid form's half variant
+    run at the sizes it exists for and is the plain size everywhere else."""
+    if int(pairs) == 0 and algorithm == LSDSORT_ALGO_ONESWEEP:
+        return int(lib().lsdsort_workspace_bytes_roomy(n, radix_bits))
     return int(lib().lsdsort_workspace_bytes_ex(n, radix_bits, int(pairs), algorithm))
 
 
@@ -176,6 +180,12 @@ def set_hybrid(on: bool) -> None:
     check(lib().lsdsort_set_hybrid(1 if on else 0), "lsdsort_set_hybrid")
 
 
+def set_half_hop(on: bool) -> None:
+    """The hybrid form's half variant (``lsdsort_set_half_hop``): the second global pass writes and the local stage reads 16-bit
+    halves, 24 B/key instead of 28, where the workspace has the roomy size.  Default on; off = never attempted."""
+    check(lib().lsdsort_set_half_hop(1 if on else 0), "lsdsort_set_half_hop")
+
+
 def set_small_sort(on: bool) -> None:
     """Sorts of up to 16384 items in one launch (``lsdsort_set_small_sort``).  Default on; off = the chained form at every size."""
     check(lib().lsdsort_set_small_sort(1 if on else 0), "lsdsort_set_small_sort")
@@ -185,6 +195,13 @@ def workspace_form(workspace, stream=None) -> int:
     """1 if the last sort queued in ``workspace`` ran the hybrid form, 0 if the ordinary passes (``lsdsort_workspace_form``)."""
     out = ctypes.c_int(0)
     check(lib().lsdsort_workspace_form(workspace.data_ptr(), _stream(stream), ctypes.byref(out)), "lsdsort_workspace_form")
+    return out.value
+
+
+def workspace_half(workspace, stream=None) -> int:
+    """1 if the last sort queued in ``workspace`` ran the hybrid form's half variant (``lsdsort_workspace_half``)."""
+    out = ctypes.c_int(0)
+    check(lib().lsdsort_workspace_half(workspace.data_ptr(), _stream(stream), ctypes.byref(out)), "lsdsort_workspace_half")
     return out.value
 
 

@@ -99,6 +99,9 @@ __global__ void __launch_bounds__(kHybridHistThreads) hybrid_histograms_kernel(c
     // key; the planner sums it to pass A's [digit][region] and pass B's [digit][A's digit].
     constexpr int T = kHybridHistThreads, CA = R == 8 ? kHybridCopiesA : 1, VPT = kHybridVpt;
     constexpr uint32_t FA = R == 8 ? 2048 : 4096;
+    // B16: the launcher's bucket_shift may carry kHybridPackedFlush (the counts leave packed, see the flush below)
+    const bool packed_flush = B16 && (bucket_shift & kHybridPackedFlush) != 0u;   // uniform
+    if (B16) bucket_shift &= kHybridPackedFlush - 1u;
     const uint32_t NB = 1u << (32u - bucket_shift);   // at most kHybridBuckets (the LDS is sized for that)
     extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];
     uint32_t* const s_a = s_mem;                 // [region][digit][CA], region-major: a wave's lanes share the region
@@ -266,6 +269,13 @@ __global__ void __launch_bounds__(kHybridHistThreads) hybrid_histograms_kernel(c
         }
         if (cnt) atomicAdd(&field_a[j], cnt);
     }
+    if (packed_flush) {   // two counts to a word, as they lie: bucket[j] += counts of 2 j (low half) and 2 j + 1 (high half)
+        for (uint32_t j = tid; j < NB / 2u; j += T) {
+            const uint32_t two = s_b[j];
+            if (two) atomicAdd(&bucket[j], two);
+        }
+        return;
+    }
     for (uint32_t j = tid; j < NB; j += T) {
         const uint32_t cnt = B16 ? (s_b[j >> 1] >> ((j & 1u) << 4)) & 0xFFFFu : s_b[j];
         if (cnt) atomicAdd(&bucket[j], cnt);
@@ -302,12 +312,13 @@ static hipError_t launch_hybrid_hist_radix(bool typed, bool b16, const HybridHis
 }
 
 hipError_t launch_hybrid_histograms(int radix_bits, const uint32_t* keys, uint32_t n, uint32_t region0_keys, uint32_t* field_a, uint32_t* bucket,
-                                    int bucket_bits, uint32_t* words, hipStream_t stream, const KeyTransform& xf)
+                                    int bucket_bits, uint32_t* words, hipStream_t stream, const KeyTransform& xf, bool packed16)
 {
+    if (packed16 && bucket_bits != 16) return hipErrorInvalidValue;
     if (!words) return hipErrorInvalidValue;
     if (bucket_bits < 11 || (1 << bucket_bits) > kHybridBuckets) return hipErrorInvalidValue;
     if (region0_keys == 0 || region0_keys % (kHybridHistThreads * 4) != 0) return hipErrorInvalidValue;
-    const HybridHistArgs a{keys, n, region0_keys, field_a, bucket, 32u - (uint32_t)bucket_bits, words, xf};
+    const HybridHistArgs a{keys, n, region0_keys, field_a, bucket, (32u - (uint32_t)bucket_bits) | (packed16 ? kHybridPackedFlush : 0u), words, xf};
     const bool typed = xf.on != 0, b16 = bucket_bits == 16;
     switch (radix_bits) {
         case 8: return launch_hybrid_hist_radix<8>(typed, b16, a, stream);

@@ -271,15 +271,44 @@ __device__ __forceinline__ void sort_bucket(const LocalSortParams& p, const uint
     uint32_t* const bucket = p.keys + lo;
     uint32_t* const bucket_vals = PAIRS ? p.vals + lo : nullptr;
     uint32_t key[K], rank[K], val[K];   // val: PAIRS only
-    // keys and payloads in one loop, written out here: through load_rows, or one array after the other, the pairs kernels take ten
-    // registers more (K = 16 spills, the K = 32 list kernel loses a wave per SIMD)
+    // The half form (LocalSortParams::halves; this one kernel only, every other instantiation keeps its code): the bucket arrives
+    // as 16-bit halves and each key is rebuilt from its position -- the bits above the half are those of group 2 b for the first
+    // first[b] positions and of group 2 b + 1 behind them, below the prefix every key shares.  For a prefix t >= 1 the group's
+    // lowest t bits lie inside the half and the two words are equal.  `bucket` is then only written.
+    constexpr bool kMayReadHalves = K == 20 && !PAIRS && !XOUT && !WHOLE;
+    bool from_halves = false;   // uniform
+    uint32_t ref = 0u;          // the key at position 0: the dead-digit test's reference
+    if constexpr (kMayReadHalves) from_halves = p.halves != nullptr && (!p.half_on || *p.half_on != 0u);
+    if (from_halves) {
+        if constexpr (kMayReadHalves) {
+            const uint16_t* const half = p.halves + lo;
+            const uint32_t t = *p.prefix_word, high = *p.high_word, first = p.first[b];
+            const uint32_t upper0 = high | (((2u * b) >> t) << 16), upper1 = high | (((2u * b + 1u) >> t) << 16);
+            ref = (first ? upper0 : upper1) | half[0];
+            // the loads first, all of them in flight, and the upper bits in a loop of its own: ORed in where the half is loaded,
+            // each row's region ends waiting for its own load -- twenty round trips in a row (local stage 0.55 -> 0.86 ms)
 #pragma unroll
-    for (int i = 0; i < K; i++) {
-        key[i] = 0xFFFFFFFFu;   // rows past the bucket's last are never ranked or stored; the paired scatter looks at one
-        if ((uint32_t)i < g.rows) {
-            const uint32_t pos = g.wbase + (uint32_t)i * 64u;
-            if (pos < size) key[i] = bucket[pos];
-            if (PAIRS) val[i] = pos < size ? bucket_vals[pos] : 0u;
+            for (int i = 0; i < K; i++) {
+                key[i] = 0xFFFFFFFFu;
+                if ((uint32_t)i < g.rows) {
+                    const uint32_t pos = g.wbase + (uint32_t)i * 64u;
+                    if (pos < size) key[i] = half[pos];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < K; i++) key[i] |= g.wbase + (uint32_t)i * 64u < first ? upper0 : upper1;   // padding stays 0xFFFFFFFF
+        }
+    } else {
+        // keys and payloads in one loop, written out here: through load_rows, or one array after the other, the pairs kernels take ten
+        // registers more (K = 16 spills, the K = 32 list kernel loses a wave per SIMD)
+#pragma unroll
+        for (int i = 0; i < K; i++) {
+            key[i] = 0xFFFFFFFFu;   // rows past the bucket's last are never ranked or stored; the paired scatter looks at one
+            if ((uint32_t)i < g.rows) {
+                const uint32_t pos = g.wbase + (uint32_t)i * 64u;
+                if (pos < size) key[i] = bucket[pos];
+                if (PAIRS) val[i] = pos < size ? bucket_vals[pos] : 0u;
+            }
         }
     }
     auto pass = [&](uint32_t shift, uint32_t width, bool last) {
@@ -301,7 +330,7 @@ __device__ __forceinline__ void sort_bucket(const LocalSortParams& p, const uint
         // multiples of 512 -- is no pass at all, and as a pass it is the worst one: every lane on one counter, which the LDS
         // serves a lane per clock (2.47 instead of 1.85 ms per 2^28 such keys).  One OR over the bucket says so: key ^ first key,
         // per thread, per wave, then across the waves through LDS.  One of the two passes always runs.
-        const uint32_t ref = bucket[0];
+        if (!from_halves) ref = bucket[0];   // (the half form: bucket[0] is a stale word; ref is the rebuilt key)
         uint32_t diff = 0;
 #pragma unroll
         for (int i = 0; i < K; i++)
@@ -481,6 +510,9 @@ hipError_t launch_local_sort(const LocalSortParams& p, hipStream_t stream)
     if ((p.list == nullptr) != (p.list_count == nullptr)) return hipErrorInvalidValue;
     if (p.small_variant && p.list) return hipErrorInvalidValue;   // the list is the large variant's
     if (p.num_payloads > 3 || (p.num_payloads > 0 && !p.vals)) return hipErrorInvalidValue;
+    // halves are read by the 10240-key keys-only kernel alone, in its device-planned form
+    if (p.halves && (p.small_variant != 1 || p.vals || p.xout.on || p.list || !p.low_bits_word || !p.first || !p.high_word || !p.prefix_word))
+        return hipErrorInvalidValue;
     if (p.num_payloads > 1) {   // records: several payload arrays
         if (p.width[2] || p.xout.on || !p.more[0] || (p.num_payloads > 2 && !p.more[1])) return hipErrorInvalidValue;
         return p.small_variant ? launch_local_multi<16>(p, stream) : launch_local_multi<32>(p, stream);

@@ -177,6 +177,9 @@ struct PassParams {
     uint32_t splitters[7];
     KeyTransform xin;    // first pass: applied to every key as it is loaded
     KeyTransform xout;   // last pass: undone on every key as it is stored
+    // The half-writing pass B of the hybrid form (launch_rank_scatter_half only): every key leaves as its low 16 bits, to
+    // half_out[the index its 32 bits would have gone to in the output].
+    uint16_t* half_out;
 };
 
 // How stage 3 ranks a key among the same-digit keys of its wave (rank_scatter.hpp).
@@ -190,6 +193,13 @@ enum RankMethod : int {
 // rank_method: kRankLdsAdd, or any other value for the mask form suited to the digit width.
 hipError_t launch_rank_scatter(int radix_bits, const TileShape& shape, int rank_method, bool chained,
                                const PassParams& p, hipStream_t stream);
+
+// Pass B of the hybrid form writing HALVES: the chained keys-only kernel of 8-bit digits, shape kHalfShapeR8
+// (1024 x 32, one LDS round) and the returning-add rank, with one difference -- the read-back stores (uint16_t)key to
+// p.half_out[destination] instead of the key to the output buffer.  Ticket, look-back, destination guard, give-up path and the
+// clearing of the next pass's status rows are the sibling's.
+constexpr int kHalfShapeR8 = 4;
+hipError_t launch_rank_scatter_half(const PassParams& p, hipStream_t stream);
 
 // Device probe of the property kRankLdsAdd relies on: returns hipSuccess and sets *ok.
 hipError_t probe_lds_add_lane_order(bool* ok, hipStream_t stream);
@@ -268,6 +278,17 @@ struct LocalSortParams {
     KeyTransform xout;           // typed sorts: the stage's store turns the sortable keys back (from_sortable)
     const uint32_t* list;        // null: bucket = workgroup index.  Else the buckets to sort, *list_count of them, walked by a
     const uint32_t* list_count;  // grid of 512 workgroups
+    // The half form (small_variant 1, keys only, untyped, with low_bits_word).  halves not null: position q of
+    // bucket b is read as the 16-bit word halves[bases[b] + q] and rebuilt with t = *prefix_word as
+    //     *high_word | ((2 b + (q >= first[b])) >> t) << 16 | half
+    // -- the array is sorted by the 16 bits below the prefix, of which the bucket's first[b] keys have the lower value --
+    // and `keys` is only written (the full keys, in order).
+    const uint16_t* halves;
+    const uint32_t* half_on;     // not null: halves are read only if *half_on != 0, else `keys` as ever -- ONE launch serves both
+                                 // forms of a sort (a second launch of 32768 workgroups that all leave costs 15 us)
+    const uint32_t* first;       // [num_buckets]: the keys of bucket b whose bit below the bucket's own is 0
+    const uint32_t* high_word;   // the t prefix bits every key shares, in place (0 for t = 0)
+    const uint32_t* prefix_word; // t
 };
 hipError_t launch_local_sort(const LocalSortParams& p, hipStream_t stream);
 // A whole sort of up to kLocalSortCap items in ONE launch: one workgroup loads keys (and vals, may be null), sorts all 32 bits
@@ -332,6 +353,12 @@ constexpr int kHybridWordPrefix = 15;     // t = the prefix the form was planned
 constexpr int kHybridWordShift = 16;      // [4]: PassParams::shift of the g-th global pass = 16 - t + g x radix_bits
 constexpr int kHybridWordLowBits = 20;    // the local stage's bits: 32 - t - bucket_bits
 constexpr int kHybridWords = 21;
+// ... and behind them the half form's (half_hop.hip, written by half_decide_kernel where the form is attempted)
+constexpr int kHalfWordOk = 21;          // 1: pass B writes halves and the local stage rebuilds the keys
+constexpr int kHalfWordHigh = 22;        // the prefix bits every key shares, in place: keys[0] & ~(2^(32 - t) - 1), 0 for t = 0
+constexpr int kHalfWordPlan = 23;        // [2]: PassParams::plan of the half-writing pass B (2 = leave at once | 0, then 1: it reads the alternate)
+constexpr int kHalfWords = 25;
+constexpr int kHalfGroups = 1 << 16;     // the groups of equal 16 bits below the prefix: two to a bucket of the 2^15
 // A prefix of eight bits or more is a constant top byte: the ordinary form then skips a pass and moves as few bytes as the hybrid
 // form would, so the form is only planned for 0 .. 7 shared bits.
 constexpr uint32_t kHybridMaxPrefix = 7;
@@ -356,14 +383,29 @@ hipError_t launch_hybrid_sample(const uint32_t* keys, uint32_t n, int bucket_bit
 // joint field); and bucket[key >> (32 - bucket_bits)] += counts (all zero on entry) -- bits counted below the prefix.
 // Nothing if words[Hopeless] or the sampled prefix is eight bits or more.  xf: the keys are counted as to_sortable(key, xf)
 // (typed sorts: what the first global pass will store).
+// packed16 (bucket_bits 16 only; the half form): the 2^16 counts leave as they are kept in LDS, two 16-bit counts to a word, added
+// to the 2^15 words bucket[0 .. 2^15) -- half the global atomics of the flush, which are 20 us of this kernel at 2^16 counters.
+// A count of 65536 or more carries into or out of its neighbour, and every such event takes 65535 or 65536 from the sum of all
+// counts, as an overflow in LDS does: the planner's sum check refuses.
 hipError_t launch_hybrid_histograms(int radix_bits, const uint32_t* keys, uint32_t n, uint32_t region0_keys, uint32_t* field, uint32_t* bucket,
-                                    int bucket_bits, uint32_t* words, hipStream_t stream, const KeyTransform& xf = KeyTransform{});
+                                    int bucket_bits, uint32_t* words, hipStream_t stream, const KeyTransform& xf = KeyTransform{},
+                                    bool packed16 = false);
+constexpr uint32_t kHybridPackedFlush = 0x100u;   // in the kernel's bucket_shift argument, above the shift itself
 // verdict, bucket bases (2^bucket_bits + 1 words), plan words and the count fields the upfront read has not written: 8-bit digits
 // fields_out = the second pass's field B [256][8] (joint unused); 4-bit digits fields_out = all four passes' [4][16][16], from
 // joint and the buckets
 // ... and large_list[0 .. words[kHybridWordLargeCount]): the buckets of more than small_cap keys (up to 2^bucket_bits words)
 hipError_t launch_hybrid_plan(int radix_bits, const uint32_t* bucket, uint32_t n, int bucket_bits, uint32_t* bases, uint32_t* fields_out,
                               const uint32_t* joint, uint32_t* words, uint32_t* large_list, uint32_t small_cap, hipStream_t stream);
+
+// ---- the half form's two small kernels (half_hop.hip) -----------------------------------------------------------------------
+// packed[j] = the counts of groups 2 j (low 16 bits) and 2 j + 1 (high), as the upfront read leaves them with `packed16`:
+// bucket15[j] = their sum and first[j] = the lower group's, j < 2^15 -- the planner's bucket counts from the group counts
+hipError_t launch_half_fold(const uint32_t* packed, uint32_t* bucket15, uint32_t* first, hipStream_t stream);
+// Behind the planner, one thread: the half form runs iff the planner chose the hybrid form and listed no bucket for the large
+// variant.  Writes words[kHalfWord*]; where it runs also words[kHybridWordPlan + 2] = 2 (the full pass B leaves at once).
+// keys: the caller's buffer, still holding the input.
+hipError_t launch_half_decide(const uint32_t* keys, uint32_t* words, hipStream_t stream);
 
 // counts64[b] = hist32[b], b < bins (multi-GPU bucket sizes as uint64).
 hipError_t launch_widen_counts(const uint32_t* hist32, uint64_t* counts64, int bins, hipStream_t stream);

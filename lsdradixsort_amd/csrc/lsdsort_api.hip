@@ -28,7 +28,8 @@ thread_local hipError_t g_last_hip = hipSuccess;
 constexpr size_t kControlBytes = 512;            // u32[128]: [0] fault word, [16 .. 16 + kPlanWords) the pass plan, then the hybrid form's words
 constexpr size_t kPlanOffsetWords = 16;
 constexpr size_t kHybridOffsetWords = kPlanOffsetWords + lsd::kPlanWords + 1;   // the hybrid form's plan words (hybrid.hip)
-static_assert(kHybridOffsetWords + lsd::kHybridWords <= kControlBytes / sizeof(uint32_t), "the plans live in the control block");
+static_assert(kHybridOffsetWords + lsd::kHalfWords <= kControlBytes / sizeof(uint32_t) && lsd::kHalfWords >= lsd::kHybridWords,
+              "the plans live in the control block");
 // what the bucket rule gives BASELINE's sizes: 2^28 keys 2^15 buckets of 8192, 2^27 keys 2^14 of 8192, 2^27 pairs 2^15 of 4096
 static_assert(lsd::hybrid_bucket_bits((size_t)1 << 28, false) == 15 && lsd::hybrid_bucket_bits((size_t)1 << 27, false) == 14 &&
               lsd::hybrid_bucket_bits((size_t)1 << 27, true) == 15 && lsd::hybrid_bucket_bits((size_t)1 << 26, true) == 14, "bucket rule");
@@ -59,6 +60,7 @@ int hybrid_small_cap(size_t n, bool pairs)
     if (mean + 1.5 * std::sqrt(mean) > (double)small) return lsd::kLocalSortCap;
     return small;
 }
+std::atomic<int> g_half_hop{env_flag("LSDSORT_HALF_HOP", true)};        // lsdsort_set_half_hop; LSDSORT_HALF_HOP=0 starts it off
 std::atomic<int> g_small_sort{env_flag("LSDSORT_SMALL_SORT", true)};                  // lsdsort_set_small_sort; LSDSORT_SMALL_SORT=0 starts it off
 std::atomic<int> g_skip_dead_passes{env_flag("LSDSORT_PASS_SKIPPING", true)};         // lsdsort_set_pass_skipping; LSDSORT_PASS_SKIPPING=0 starts it off
 constexpr uint32_t kMaxXcdChunk = 64;
@@ -206,6 +208,33 @@ Layout make_layout(size_t n, int radix_bits, int payloads, int algorithm, const 
     return L;
 }
 
+// The half variant of the hybrid form (half_hop.hip) keeps three arrays BEHIND the plain workspace of a sort,
+// which is why it needs the roomy size (lsdsort_workspace_bytes_roomy) and why every plain size stays what it was: the halves
+// pass B writes, an array of 65536 words for counts (the 2^15 folded bucket counts the planner reads lie there; the packed group
+// counts themselves go into the sort's own bucket array), and each bucket's count of its lower group.
+struct HalfLayout {
+    size_t halves = 0, c16 = 0, first = 0, total = 0;   // total: the roomy size
+};
+// Can a keys-only uint32 sort of n keys run the variant at all?  8-bit digits, 2^15 buckets (about 1.58e8 .. 3.3e8 keys), the
+// default 1024 x 32 tile of the chained form (the one HALF instantiation of the pass kernel).
+bool half_form_fits(size_t n, int radix_bits)
+{
+    if (radix_bits != 8 || n < hybrid_min_items(8, false) || n > kHybridMaxKeys) return false;
+    if (lsd::hybrid_bucket_bits(n, false) != 15 || (n >> 15) > lsd::kHybridMaxMeanBucket) return false;
+    const TileShape* shapes = nullptr;
+    const int count = lsd::tile_shapes(8, &shapes);
+    return count > lsd::kHalfShapeR8 && current_shape(8, n, LSDSORT_ALGO_ONESWEEP) == &shapes[lsd::kHalfShapeR8];
+}
+HalfLayout make_half_layout(size_t n, size_t plain_bytes)
+{
+    HalfLayout H;
+    H.halves = align_up(plain_bytes);
+    H.c16 = align_up(H.halves + n * sizeof(uint16_t));
+    H.first = align_up(H.c16 + (size_t)lsd::kHalfGroups * sizeof(uint32_t));
+    H.total = align_up(H.first + (size_t)(lsd::kHalfGroups / 2) * sizeof(uint32_t));
+    return H;
+}
+
 // Per-device facts learned once: is it gfx950, and does it serve colliding LDS atomics of one
 // wave instruction in lane order (needed by kRankLdsAdd)?  The probe allocates and synchronises,
 // so it runs once per device, on first use or from lsdsort_prepare_device(), never per sort.
@@ -296,6 +325,7 @@ struct StageEvents {
     hipEvent_t ev[3 * LSDSORT_MAX_PASSES + 4];
     hipEvent_t kernel_ev[2 * LSDSORT_MAX_PASSES];   // begin/end of each pass's rank-and-scatter kernel
     int kernel_count = 0;
+    bool half_tried = false;   // the hybrid form's pass B was launched twice (full, then halves): one more pair of kernel events
     int count = 0;
     hipStream_t stream = nullptr;
     int arm_kernel_events()   // the next rank-and-scatter launch of this thread reports into a fresh pair
@@ -356,6 +386,7 @@ struct SortRequest {
     hipStream_t stream = nullptr;
     lsd::KeyTransform xf{};                // typed sorts
     const HostFeed* feed = nullptr;        // the host-pointer entries
+    bool half_allowed = true;              // the hybrid form's half variant may run where the workspace has the roomy size
     StageEvents* ev = nullptr;             // lsdsort_u32_device_timed
     lsdsort_timing* timing = nullptr;
     SortRequest(uint32_t* d_keys, uint32_t* d_vals, void* d_ws, size_t bytes, size_t count, int radix, void* hip_stream)
@@ -391,6 +422,10 @@ struct SortPlan {
     uint32_t* bucket = nullptr;       // [32768] bucket counts
     uint32_t* bases = nullptr;        // [32769] bucket bases, then the list of large buckets
     int bucket_bits = 0, small_cap = 0;   // small_cap: capacity of the local stage's launch over all buckets
+    // the half variant (attempted iff halves is set: then the upfront read counts the 2^16 groups, two to a word of `bucket`, and
+    // half_hop.hip's kernels fold them into bucket15 -- the counts the planner then reads -- and decide)
+    uint16_t* halves = nullptr;       // [n] the low 16 bits of every key, as pass B leaves them
+    uint32_t *bucket15 = nullptr, *first = nullptr;   // [32768] bucket counts (in the array sized for 65536 group counts); [32768] each bucket's count of its lower group
     uint32_t *tile_hist = nullptr, *tile_global = nullptr, *scratch = nullptr;   // staged form
 };
 
@@ -481,6 +516,17 @@ int make_plan(const SortRequest& rq, SortPlan* out)
         sp.bucket = sp.joint + lsd::hybrid_joint_words(radix_bits);
         sp.bases = at(L.hyb_bases);
         sp.small_cap = hybrid_small_cap(n, pairs);
+        // the half variant: plain uint32 keys without payloads, and a workspace of the roomy size (the arrays lie behind the
+        // plain size this n is given by the query, wherever the caller's larger workspace ends)
+        if (!pairs && !rq.xf.on && rq.half_allowed && g_half_hop.load(std::memory_order_relaxed) && half_form_fits(n, radix_bits) &&
+            sp.bucket_bits == 15 && sp.small_cap == lsd::kLocalSortCapSmall) {
+            const HalfLayout H = make_half_layout(n, lsdsort_workspace_bytes_ex(n, radix_bits, 0, LSDSORT_ALGO_ONESWEEP));
+            if (rq.ws_bytes >= H.total) {
+                sp.halves = reinterpret_cast<uint16_t*>(at(H.halves));
+                sp.bucket15 = at(H.c16);
+                sp.first = at(H.first);
+            }
+        }
     }
     return LSDSORT_OK;
 }
@@ -566,9 +612,17 @@ int hybrid_upfront(const SortRequest& rq, const SortPlan& sp)
     const int radix_bits = rq.radix_bits;
     const uint32_t n = (uint32_t)rq.n;
     LSD_HIP(lsd::launch_hybrid_sample(rq.keys, n, sp.bucket_bits, sp.hyb, rq.stream));
-    LSD_HIP(lsd::launch_hybrid_histograms(radix_bits, rq.keys, n, sp.L.region0, radix_bits == 8 ? sp.fields : sp.joint, sp.bucket,
-                                          sp.bucket_bits, sp.hyb, rq.stream, rq.xf));
-    LSD_HIP(lsd::launch_hybrid_plan(radix_bits, sp.bucket, n, sp.bucket_bits, sp.bases, radix_bits == 8 ? sp.fields + 2048 : sp.fields,
+    if (sp.halves) {
+        // the half variant: the same read counts the 2^16 groups (its 16-bit-counter form; a counter that overflows loses keys
+        // from the sum, which the planner refuses), two to a word of the sort's own bucket array -- zero since the opening memset --
+        // and the fold gives the planner its 2^15 buckets
+        LSD_HIP(lsd::launch_hybrid_histograms(radix_bits, rq.keys, n, sp.L.region0, sp.fields, sp.bucket, 16, sp.hyb, rq.stream, rq.xf, true));
+        LSD_HIP(lsd::launch_half_fold(sp.bucket, sp.bucket15, sp.first, rq.stream));
+    } else {
+        LSD_HIP(lsd::launch_hybrid_histograms(radix_bits, rq.keys, n, sp.L.region0, radix_bits == 8 ? sp.fields : sp.joint, sp.bucket,
+                                              sp.bucket_bits, sp.hyb, rq.stream, rq.xf));
+    }
+    LSD_HIP(lsd::launch_hybrid_plan(radix_bits, sp.halves ? sp.bucket15 : sp.bucket, n, sp.bucket_bits, sp.bases, radix_bits == 8 ? sp.fields + 2048 : sp.fields,
                                     sp.joint, sp.hyb, sp.bases + lsd::kHybridBuckets + 1, (uint32_t)sp.small_cap, rq.stream));
     LSD_TRY(inject_count_fault(rq, sp, true));
     // the global passes' region tables: the first one's regions are by position (like any first pass), the others' by the
@@ -576,6 +630,7 @@ int hybrid_upfront(const SortRequest& rq, const SortPlan& sp)
     // (no fault word: where the sample or the planner has said no these counts are partial or absent, and nobody uses the tables)
     LSD_HIP(lsd::launch_scan_regions(radix_bits, lsd::hybrid_global_passes(radix_bits), sp.L.regions, sp.fields, n, (uint32_t)sp.shape->tile(),
                                      sp.L.region0, sp.chain.tables + (size_t)sp.passes * sp.chain.table_words, rq.stream, nullptr, nullptr));
+    if (sp.halves) LSD_HIP(lsd::launch_half_decide(rq.keys, sp.hyb, rq.stream));   // the caller's buffer still holds the input
     return LSDSORT_OK;
 }
 
@@ -629,7 +684,17 @@ int hybrid_passes(const SortRequest& rq, const SortPlan& sp)
         p.shift_word = sp.hyb + lsd::kHybridWordShift + g;   // ... less the key prefix the device found: bits [16 - t, 32 - t)
         p.plan = sp.hyb + lsd::kHybridWordPlan + 2 * g;
         if (rq.xf.on && g == 0) p.xin = rq.xf;   // typed sorts: sortable keys from the first store on; the local stage's store turns them back
+        const bool twice = sp.halves && g + 1 == hyb_passes;   // the half variant: pass B in both forms, the device has told one of them 2
+        if (twice) p.plan_first = 1u;
         LSD_TRY(launch_sort_pass(rq, sp, p));
+        if (twice) {
+            p.plan = sp.hyb + lsd::kHalfWordPlan;
+            p.half_out = sp.halves;
+            if (rq.ev) LSD_TRY(rq.ev->arm_kernel_events());
+            const hipError_t launched = lsd::launch_rank_scatter_half(p, rq.stream);
+            StageEvents::disarm_kernel_events();
+            LSD_HIP(launched);
+        }
     }
     lsd::LocalSortParams lp{};
     lp.keys = rq.keys;
@@ -647,7 +712,15 @@ int hybrid_passes(const SortRequest& rq, const SortPlan& sp)
     // stay under 5120 a bucket, four
     lp.small_variant = sp.small_cap == lsd::kLocalSortCapTiny ? 2u : sp.small_cap == lsd::kLocalSortCap ? 0u : 1u;
     lp.larger_elsewhere = 1;
+    if (sp.halves) {   // the half variant: this one launch reads halves where the device chose it, keys where it did not
+        lp.halves = sp.halves;
+        lp.half_on = sp.hyb + lsd::kHalfWordOk;
+        lp.first = sp.first;
+        lp.high_word = sp.hyb + lsd::kHalfWordHigh;
+        lp.prefix_word = sp.hyb + lsd::kHybridWordPrefix;
+    }
     LSD_HIP(lsd::launch_local_sort(lp, rq.stream));
+    lp.halves = nullptr;
     lp.small_variant = 0;     // the planner's list of larger ones (up to 16384 keys): two per CU, a grid of 512 walks the list
     lp.larger_elsewhere = 0;
     lp.list = lp.bases + lsd::kHybridBuckets + 1;
@@ -736,6 +809,7 @@ int run_sort(const SortRequest& rq)
         rq.timing->hybrid = sp.hyb ? -1 : 0;   // -1: tried; lsdsort_u32_device_timed reads the device's verdict back
     }
     if (sp.small) return small_sort(rq, sp);
+    if (rq.ev) rq.ev->half_tried = sp.halves != nullptr;
     LSD_TRY(mark(rq, StageEvents::kStart));
     LSD_HIP(hipMemsetAsync(rq.ws, 0, sp.L.zero_bytes, rq.stream));
     LSD_TRY(mark(rq, StageEvents::kCleared));
@@ -948,6 +1022,26 @@ int lsdsort_workspace_form(const void* d_workspace, void* hip_stream, int* hybri
     return LSDSORT_OK;
 }
 
+int lsdsort_set_half_hop(int on)
+{
+    g_half_hop.store(on ? 1 : 0, std::memory_order_relaxed);
+    return LSDSORT_OK;
+}
+
+int lsdsort_workspace_half(const void* d_workspace, void* hip_stream, int* half)
+{
+    if (!d_workspace || !half) return LSDSORT_ERR_INVALID_ARG;
+    // both words are cleared by the opening memset of every sort; the second is written only where the variant was attempted
+    uint32_t words[2] = {0, 0};
+    const uint32_t* hyb = static_cast<const uint32_t*>(d_workspace) + kHybridOffsetWords;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    LSD_HIP(hipMemcpyAsync(&words[0], hyb + lsd::kHybridWordOk, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    LSD_HIP(hipMemcpyAsync(&words[1], hyb + lsd::kHalfWordOk, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    LSD_HIP(hipStreamSynchronize(stream));
+    *half = (words[0] && words[1]) ? 1 : 0;
+    return LSDSORT_OK;
+}
+
 int lsdsort_set_small_sort(int on)
 {
     g_small_sort.store(on ? 1 : 0, std::memory_order_relaxed);
@@ -1069,6 +1163,13 @@ size_t lsdsort_workspace_bytes_ex(size_t n, int radix_bits, int pairs, int algor
     return need > stage ? need : stage;
 }
 
+size_t lsdsort_workspace_bytes_roomy(size_t n, int radix_bits)
+{
+    const size_t plain = lsdsort_workspace_bytes_ex(n, radix_bits, 0, LSDSORT_ALGO_ONESWEEP);
+    if (plain == 0 || !half_form_fits(n, radix_bits)) return plain;
+    return make_half_layout(n, plain).total;
+}
+
 size_t lsdsort_workspace_bytes(size_t n, int radix_bits, int pairs)
 {
     return lsdsort_workspace_bytes_ex(n, radix_bits, pairs, LSDSORT_ALGO_ONESWEEP);
@@ -1094,7 +1195,11 @@ int lsdsort_u32_device_prefixed(uint32_t* d_keys, void* d_workspace, size_t work
 {
     // the argument is checked, not needed: the device finds the key prefix itself
     if (common_prefix_bits < 0 || common_prefix_bits > 8) return LSDSORT_ERR_INVALID_ARG;
-    return run_sort(SortRequest(d_keys, nullptr, d_workspace, workspace_bytes, n, radix_bits, hip_stream));
+    // (the sharded step's entry: its workspace is sized for the rank's capacity, not for this sort -- the half variant, which is
+    // chosen by workspace size, stays out)
+    SortRequest rq(d_keys, nullptr, d_workspace, workspace_bytes, n, radix_bits, hip_stream);
+    rq.half_allowed = false;
+    return run_sort(rq);
 }
 
 int lsdsort_pairs_u32_device(uint32_t* d_keys, uint32_t* d_vals, void* d_workspace, size_t workspace_bytes, size_t n,
@@ -1181,20 +1286,29 @@ int lsdsort_u32_device_timed(uint32_t* d_keys, uint32_t* d_vals, void* d_workspa
                 // per pass: the kernel's own events.  Where the hybrid form was tried its global passes come first (event pairs 0, 1
                 // and at 4-bit digits 2, 3).
                 int first_pair = 0;
+                uint32_t half_ok = 0;   // the hybrid form ran with pass B writing halves: its time is that launch's
                 if (out->hybrid == -1) {
                     uint32_t ok = 0;
                     LSD_HIP(hipMemcpy(&ok, static_cast<const uint32_t*>(d_workspace) + kHybridOffsetWords + lsd::kHybridWordOk, sizeof(ok),
                                       hipMemcpyDeviceToHost));
                     out->hybrid = ok ? 1 : 0;
-                    first_pair = ok ? 0 : lsd::hybrid_global_passes(radix_bits);
+                    // (the half variant launched pass B twice: pairs 0 = A, 1 = B, 2 = B writing halves)
+                    first_pair = ok ? 0 : lsd::hybrid_global_passes(radix_bits) + (ev.half_tried ? 1 : 0);
+                    if (ok && ev.half_tried) {
+                        LSD_HIP(hipMemcpy(&half_ok, static_cast<const uint32_t*>(d_workspace) + kHybridOffsetWords + lsd::kHalfWordOk,
+                                          sizeof(half_ok), hipMemcpyDeviceToHost));
+                    }
                     if (ok) {
                         out->passes = lsd::hybrid_global_passes(radix_bits);
                         if (ev.count > StageEvents::kLocalEnd)
                             LSD_HIP(hipEventElapsedTime(&out->local_ms, ev.ev[StageEvents::kLocalBegin], ev.ev[StageEvents::kLocalEnd]));
                     }
                 }
-                for (int p = 0; p < out->passes && p < LSDSORT_MAX_PASSES && 2 * (p + first_pair) + 1 < ev.kernel_count; p++)
-                    LSD_HIP(hipEventElapsedTime(&out->scatter_ms[p], ev.kernel_ev[2 * (p + first_pair)], ev.kernel_ev[2 * (p + first_pair) + 1]));
+                for (int p = 0; p < out->passes && p < LSDSORT_MAX_PASSES; p++) {
+                    const int pair = p + first_pair + (half_ok && p == 1 ? 1 : 0);
+                    if (2 * pair + 1 >= ev.kernel_count) break;
+                    LSD_HIP(hipEventElapsedTime(&out->scatter_ms[p], ev.kernel_ev[2 * pair], ev.kernel_ev[2 * pair + 1]));
+                }
             } else {
                 out->histogram_ms = 0.f;
                 out->scan_ms = 0.f;
@@ -1317,6 +1431,30 @@ int lsdsort_local_sort_u32_device(uint32_t* d_keys, uint32_t* d_vals, const uint
         p.width[i] = (uint32_t)width;
         shift += width;
     }
+    LSD_HIP(lsd::launch_local_sort(p, static_cast<hipStream_t>(hip_stream)));
+    return LSDSORT_OK;
+}
+
+int lsdsort_local_sort_halves_u32_device(uint32_t* d_keys_out, const uint16_t* d_halves, const uint32_t* d_bases, const uint32_t* d_first,
+                                         size_t num_buckets, const uint32_t* d_words, uint32_t* d_fault, void* hip_stream)
+{
+    if (num_buckets > (size_t)lsd::kHybridBuckets) return LSDSORT_ERR_INVALID_ARG;
+    if (num_buckets == 0) return LSDSORT_OK;
+    if (!d_keys_out || !d_halves || !d_bases || !d_first || !d_words) return LSDSORT_ERR_INVALID_ARG;
+    int dev = 0;
+    LSD_TRY(check_device_ready(&dev));
+    if (!g_device[dev].lds_add_in_lane_order) return LSDSORT_ERR_UNSUPPORTED;
+    lsd::LocalSortParams p{};
+    p.keys = d_keys_out;
+    p.bases = d_bases;
+    p.num_buckets = (uint32_t)num_buckets;
+    p.small_variant = 1;   // the kernel a whole sort runs in this form: buckets of up to 10240 keys, above that fault bit 3
+    p.halves = d_halves;
+    p.first = d_first;
+    p.prefix_word = d_words;
+    p.high_word = d_words + 1;
+    p.low_bits_word = d_words + 2;
+    p.fault = d_fault;
     LSD_HIP(lsd::launch_local_sort(p, static_cast<hipStream_t>(hip_stream)));
     return LSDSORT_OK;
 }

@@ -168,9 +168,12 @@ __device__ __forceinline__ bool row_is_heavy(uint32_t d)
 
 // XF: this launch may carry a key transform (PassParams::xin on a sort's first pass, ::xout on its last);
 // plain uint32 sorts use the XF = false instantiations, which contain none of it.
-template <int R, int T, int K, int CAP, int RANK, bool PAIRS, bool CHAINED, bool XF = false>
+// HALF: the hybrid form's pass B writing halves (keys only): the read-back stores (uint16_t)key to p.half_out at the index the key
+// would have gone to; nothing else differs (one instantiation, launch_rank_scatter_half).
+template <int R, int T, int K, int CAP, int RANK, bool PAIRS, bool CHAINED, bool XF = false, bool HALF = false>
 __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_kernel(const PassParams p)
 {
+    static_assert(!HALF || (!PAIRS && !XF && CHAINED), "halves: untyped keys without payloads, chained form");
     if (CHAINED && p.plan_first && p.plan[0] == 2u) return;   // uniform (PassParams::plan_first)
     LSD_STATS_BEGIN(st, p, threadIdx.x);
     using S = ScatterShape<R, T, K, CAP, RANK>;
@@ -809,7 +812,10 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
                         const uint32_t q = round * CAP + slot;
                         const uint32_t k = s_keys[slot];
                         const uint32_t d = digit_of(k);
-                        if (decltype(all_valid)::value || q < valid) out_keys[s_gdelta[d] + q] = leaving(k);
+                        if (decltype(all_valid)::value || q < valid) {
+                            if constexpr (HALF) p.half_out[s_gdelta[d] + q] = (uint16_t)k;
+                            else out_keys[s_gdelta[d] + q] = leaving(k);
+                        }
                     }
                 }
             };
@@ -854,11 +860,11 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
 }
 
 // Launch one instantiation.  LDS above 64 KiB needs the attribute raised once per function.
-template <int R, int T, int K, int CAP, int RANK, bool PAIRS, bool CHAINED, bool XF = false>
+template <int R, int T, int K, int CAP, int RANK, bool PAIRS, bool CHAINED, bool XF = false, bool HALF = false>
 hipError_t launch_rank_scatter_inst(const PassParams& p, hipStream_t stream)
 {
     constexpr size_t lds_bytes = (size_t)rank_scatter_lds_words<R, T, K, CAP, RANK>() * sizeof(uint32_t);
-    constexpr auto kernel = rank_scatter_kernel<R, T, K, CAP, RANK, PAIRS, CHAINED, XF>;
+    constexpr auto kernel = rank_scatter_kernel<R, T, K, CAP, RANK, PAIRS, CHAINED, XF, HALF>;
     if (lds_bytes > 64 * 1024) {
         const hipError_t attr = allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds_bytes, dynamic_lds_told<kernel>);
         if (attr != hipSuccess) return attr;
