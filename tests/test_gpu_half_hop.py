@@ -63,7 +63,7 @@ def _run_halves(gpu, keys, bases, first, t, high, num_buckets, sentinel=0xDEADBE
     return gpu.to_host(d_out), int(gpu.to_host(d_fault)[0])
 
 
-@pytest.mark.parametrize("t", [0, 1, 7])
+@pytest.mark.parametrize("t", [0, 1, 2, 3, 4, 5, 6, 7])
 def test_local_stage_reads_halves(gpu, t):
     """Bucket sizes 0, 1, around a row of 512 and at the 10240-key capacity; first[b] = 0, size and size / 2; dead first and
     second digits; 0xFFFF halves at a tail -- at bucket numbers spread over all 2^15, so that the rebuilt upper bits differ."""
