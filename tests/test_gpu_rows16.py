@@ -239,6 +239,33 @@ def test_every_route_gives_the_same_words(shape):
     assert_intact16(keys=whole)
 
 
+def test_widen_route_past_the_segmented_sorts_item_cap():
+    """1027 rows of 16387 keys on the widen route: 1027 large segments with positions as payloads, three more than one round of
+    the segmented sort's tile-table kernel takes (tests/_seg_plan.py, ITEMS), and 16.8 M items, past the 8192 x 1024 items one
+    round of the widen and narrow kernels covers.  Against numpy, and word for word against the native route."""
+    rows, cols = 1027, 16387
+    assert rows > 1024 and cols > 16384 and rows * cols > 8192 * 1024
+    keys = make_keys(rows, cols, "bfloat16", seed=rows)
+    ek, ei = expected_np(keys, "bfloat16", True)
+    whole, view = guarded16(keys, 2, torch.bfloat16)
+    lsd.set_rows16_route(0)
+    try:
+        widen = Call(view, rows, cols, "bfloat16", True).result()
+    finally:
+        lsd.set_rows16_route(-1)
+    assert_equal(widen[0], ek, "widen route: values")
+    assert_equal(widen[1], ei, "widen route: positions")
+    lsd.set_rows16_route(1)
+    try:
+        native = Call(view, rows, cols, "bfloat16", True).result()
+    finally:
+        lsd.set_rows16_route(-1)
+    assert_equal(native[0], widen[0], "native route against widen route: values")
+    assert_equal(native[1], widen[1], "native route against widen route: positions")
+    assert_equal(bits_of(view), keys.reshape(-1), "input unchanged")
+    assert_intact16(keys=whole)
+
+
 # ---- streams and replay ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", CLASSES[:3], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_two_streams_two_workspaces(shape):

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import lsdradixsort_amd as lsd
+from _seg_plan import expected_dev   # the large shapes' reference: shared with test_gpu_segmented_plan.py
 
 pytestmark = pytest.mark.gpu
 
@@ -37,27 +38,6 @@ def expected(keys, offsets, vals=None, key_type="uint32", descending=False):
     if vals is not None:
         out_v[lo:hi] = vals[order]
     return out_k, out_v
-
-
-def expected_dev(d_keys, offsets_np, key_type="uint32", descending=False):
-    """the same on the device (large shapes): stable torch.sort of segment id << 32 | sortable key; returns (keys, source index)"""
-    u = d_keys.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-    if key_type == "int32":
-        u = u ^ 0x80000000
-    elif key_type == "float32":
-        u = u ^ (((u >> 31) * 0x7FFFFFFF) | 0x80000000)
-    if descending:
-        u = u ^ 0xFFFFFFFF
-    lo, hi = int(offsets_np[0]), int(offsets_np[-1])
-    sizes = torch.from_numpy(np.diff(offsets_np.astype(np.int64))).to(d_keys.device)
-    seg = torch.repeat_interleave(torch.arange(sizes.numel(), device=d_keys.device), sizes)
-    comp = (seg << 32) | u[lo:hi]
-    _, idx = torch.sort(comp, stable=True)
-    del comp, seg, u
-    idx = idx + lo
-    out = d_keys.clone()
-    out[lo:hi] = d_keys[idx]
-    return out, idx
 
 
 def run(keys, offsets, vals=None, key_type="uint32", descending=False, check=True):

@@ -167,6 +167,23 @@ def test_values_against_torch_topk(shape, key_type):
             check_case_dev(dk, key_type, largest, k, ek, ei, f"{rows}x{cols} {key_type} largest={largest}", witness=True)
 
 
+@pytest.mark.parametrize("largest", [True, False])
+def test_sort_route_past_the_segmented_sorts_item_cap(largest):
+    """1027 rows of 16387 keys with k above 3/4 of cols: the sort route hands the segmented sort 1027 large segments with
+    positions as payloads, three more than one round of its tile-table kernel takes (tests/_seg_plan.py, ITEMS).  int32 with
+    ties, where torch's stable sort is the library's order."""
+    rows, cols = 1027, 16387
+    assert rows > 1024 and cols > 16384
+    g = torch.Generator(device="cuda").manual_seed(1027)
+    dk = torch.randint(-(1 << 31), 1 << 31, (rows, cols), generator=g, device="cuda", dtype=torch.int64).to(torch.int32)
+    dk[:, ::5] >>= 20   # ties within every row
+    before = dk.clone()
+    ek, ei = torch.sort(dk, dim=-1, descending=largest, stable=True)
+    for k in (cols, 3 * cols // 4 + 1):
+        check_case_dev(dk, "int32", largest, k, ek, ei, f"{rows}x{cols} int32 largest={largest}")
+    assert torch.equal(dk, before), "input unchanged"
+
+
 def test_one_row_of_2_26():
     cols = 1 << 26
     g = torch.Generator(device="cuda").manual_seed(26)

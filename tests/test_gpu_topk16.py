@@ -207,6 +207,24 @@ def test_ties_and_shared_prefixes_by_position(shape, key_type):
         assert_intact16(keys=whole)
 
 
+# ---- the sort route at the segmented sort's item cap ----------------------------------------------------------------------------
+@pytest.mark.parametrize("largest", [True, False])
+def test_sort_route_past_the_segmented_sorts_item_cap(largest):
+    """1027 rows of 16387 keys with k above 3/4 of cols: the sort route hands the segmented sort 1027 large segments with
+    positions as payloads, three more than one round of its tile-table kernel takes (tests/_seg_plan.py, ITEMS).  int16 (ties in
+    every row: 16387 keys of 65536 values), where torch's stable sort is the library's order."""
+    rows, cols = 1027, 16387
+    assert rows > 1024 and cols > 16384
+    keys = make_keys(rows, cols, "int16", seed=1027)
+    whole, view = guarded16(keys, 2, torch.int16)
+    tk, ti = torch.sort(view.view(rows, cols), dim=-1, descending=largest, stable=True)
+    ek, ei = bits_of(tk.contiguous()).reshape(rows, cols), ti.to(torch.int32).cpu().numpy().view(np.uint32)
+    for k in (cols, 3 * cols // 4 + 1):
+        check_case(view, (rows, cols), "int16", largest, k, ek, ei, f"{rows}x{cols} int16 largest={largest}")
+    assert_equal(bits_of(view), keys.reshape(-1), "input unchanged")
+    assert_intact16(keys=whole)
+
+
 # ---- guards ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape,k", [((9, 700), 33), ((9, 700), 1), ((5, 9000), 1500), ((3, 300007), 1000), ((3, 300007), 1),
                                      ((3, 300007), 299000)], ids=lambda v: str(v))
