@@ -2,7 +2,7 @@
 // from the caller's key type and order to the sortable 16-bit value, and the split of an array of 2-byte keys into the keys in
 // front of its first 16-byte line, whole groups of eight from there on, and the keys behind the last whole group.  And the value
 // side of a float16 / bfloat16 key: its float32, its softmax mass under the row's temperature and the min-p threshold, one definition
-// for topp16.hip's filter and sample16.hip's draw.
+// for topp16.hip's filter, sample16.hip's draw and logprob16.hip (their row helpers: mass_rows16.hpp).
 //
 // Everything here has internal linkage (an unnamed namespace, as when it lived in keys16.hip): every unit compiles its own copy
 // into its own kernels, and the kernels of keys16.hip keep their symbols.
@@ -71,6 +71,13 @@ struct Values16 {
     uint32_t nan_lo;    // sortable(+inf): the +NaNs lie below it, the -NaNs above 0xFFFF - nan_lo = sortable(-inf)
     uint32_t bf16;      // bfloat16 (else float16)
 };
+// The map (largest first) and the value side of a float key type, for the entries that weigh keys: float16 or bfloat16 only.
+inline int float16_values(int key_type, Key16Map* m, Values16* v)
+{
+    if (key_type != LSDSORT_KEY16_F16 && key_type != LSDSORT_KEY16_BF16) return LSDSORT_ERR_INVALID_ARG;
+    *v = Values16{key_type == LSDSORT_KEY16_BF16 ? 0x007Fu : 0x03FFu, key_type == LSDSORT_KEY16_BF16 ? 1u : 0u};
+    return key16_map(key_type, 1, m);
+}
 __device__ __forceinline__ bool is_number(uint32_t s, const Values16& v) { return s - v.nan_lo <= 0xFFFFu - 2u * v.nan_lo; }   // kNoKey: never
 __device__ __forceinline__ float value_of(uint32_t s, const Key16Map& m, const Values16& v)
 {

@@ -424,8 +424,6 @@ int run_filter(const uint16_t* keys, size_t rows, size_t cols, const uint32_t* k
     return LSDSORT_OK;
 }
 
-bool sizes_ok(size_t rows, size_t cols) { return rows <= LSDSORT_MAX_KEYS && (rows == 0 || cols <= LSDSORT_MAX_KEYS / rows); }
-
 }  // namespace
 }  // namespace lsd
 

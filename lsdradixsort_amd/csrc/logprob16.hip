@@ -26,8 +26,9 @@
 //                                   and the chunk's counts (integer atomicAdd), finish (one wavefront per row: Z, ln Z, the slots)
 // Short rows: one read of the row (2 B/key by byte accounting); long rows two: 4 B/key.
 //
-// The row read is this unit's own (read_body / read_front, restated from sample16.hip, which is pinned):
-// select_tiles16.hpp belongs to the seven selecting units.  Register 8 j + e of a lane is body position q0 + 8 (64 j + lane) + e.
+// The row read (read_body / read_front), the best number of a row or chunk, wave_add64 and log_total are mass_rows16.hpp's, the ones
+// sample16.hip's draw uses; select_tiles16.hpp belongs to the seven selecting units.  Register 8 j + e of a lane is body position
+// q0 + 8 (64 j + lane) + e.
 // Keys are only read; every store goes to d_logprob / d_rank [row][slot] and d_lse[row] under row < rows.  This unit raises no fault
 // bit: the clear kernel zeroes the control block and lsdsort_check_device answers OK.
 #define LSDSORT_BUILD 1
@@ -36,62 +37,15 @@
 #include "keys16_map.hpp"
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
+#include "mass_rows16.hpp"
 #include "radix_select.hpp"
 
 namespace lsd {
 namespace {
 
-constexpr uint32_t kAbsent = 0xFFFFFFFFu;   // a register without a key: a sortable value is below 65536, and it is no number
 constexpr uint32_t kSlots = LSDSORT_LOGPROB_MAX_SLOTS;
 constexpr uint32_t kNaN = 0x7FC00000u;
 static_assert(kSlots <= 64u, "lane s owns slot s");
-using RowKeys = Row<uint16_t>;
-
-// ---- the row read (sample16.hip's) --------------------------------------------------------------------------------------------------
-// The wave's tile from body position q0 on, valid below `end`: a whole group by one 16-byte load, the others key by key.
-__device__ __forceinline__ void read_body(const RowKeys& r, uint32_t q0, uint32_t end, uint32_t lane, const Key16Map& m, uint32_t (&t)[kRegs])
-{
-#pragma unroll
-    for (int j = 0; j < kRegs / 8; j++) {
-        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
-        if (q < end && end - q >= kGroupKeys) {
-            const uint4 v = *reinterpret_cast<const uint4*>(r.keys + r.head + q);
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                t[8 * j + 2 * i] = to_sortable16(w[i] & 0xFFFFu, m);
-                t[8 * j + 2 * i + 1] = to_sortable16(w[i] >> 16, m);
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                t[8 * j + e] = kAbsent;
-                if (q < end && end - q > (uint32_t)e) t[8 * j + e] = to_sortable16(r.keys[r.head + q + (uint32_t)e], m);
-            }
-        }
-    }
-}
-// key `lane` of the keys in front of the row's first 16-byte line, for the one wave that owns them
-__device__ __forceinline__ uint32_t read_front(const RowKeys& r, uint32_t lane, const Key16Map& m)
-{
-    return lane < r.head ? to_sortable16(r.keys[lane], m) : kAbsent;
-}
-
-// ---- wave arithmetic (sample16.hip's) -----------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t wave_least(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return b < a ? b : a; }); }
-__device__ __forceinline__ uint32_t best_number(uint32_t s, uint32_t lo, const Values16& v)
-{
-    const uint32_t n = is_number(s, v) ? s : kAbsent;
-    return n < lo ? n : lo;
-}
-__device__ __forceinline__ uint64_t wave_add64(uint64_t v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, off, kWave);
-    return v;
-}
-// ln(Z * 2^-32): the conversion rounds Z to 24 bits, the scaling is exact; -inf for Z == 0
-__device__ __forceinline__ float log_total(uint64_t z) { return logf((float)z * 2.3283064365386963e-10f); }
 
 // ---- the slots ----------------------------------------------------------------------------------------------------------------------
 struct Outputs {
@@ -190,19 +144,7 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) logprob16_short_kerne
         const uint32_t h = wave == 0u ? read_front(r, lane, p.map) : kAbsent;
         const Query q = read_query(id, r.keys, p.cols, p.map);
         const float scale = p.has_temperature ? uniform_f32(scale_of(t_load)) : kLog2e;   // one scale per row
-        uint32_t lo_num = best_number(h, kAbsent, p.val);
-#pragma unroll
-        for (int i = 0; i < kRegs; i++) lo_num = best_number(t[i], lo_num, p.val);
-        lo_num = wave_least(lo_num);
-        if (WAVES > 1) {
-            if (lane == 0u) s_min[wave] = lo_num;
-            __syncthreads();
-#pragma unroll
-            for (int w = 0; w < WAVES; w++) {
-                const uint32_t o = s_min[w];
-                lo_num = o < lo_num ? o : lo_num;
-            }
-        }
+        const uint32_t lo_num = row_best_number<WAVES>(t, h, s_min, wave, lane, p.val);
         const float best = value_of(lo_num & 0xFFFFu, p.map, p.val);   // a row of NaNs: every q is 0
         uint64_t z = mass_of_key(h, best, scale, p.map, p.val);
 #pragma unroll
@@ -267,22 +209,7 @@ __global__ void __launch_bounds__(kLongThreads) logprob16_best_kernel(const Long
     __shared__ uint32_t s_part[kLongWaves];
     const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
     if (row >= p.rows) return;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const RowKeys r = row_of(p.keys, row, p.cols);
-    const ChunkRange g = chunk_of(r, p.chunk, c);
-    uint32_t lo_num = best_number((c == 0u && wave == 0u) ? read_front(r, lane, p.map) : kAbsent, kAbsent, p.val);   // uniform
-    for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
-        uint32_t t[kRegs];
-        read_body(r, tile + wave * kWaveTile, g.hi, lane, p.map, t);
-#pragma unroll
-        for (int i = 0; i < kRegs; i++) lo_num = best_number(t[i], lo_num, p.val);
-    }
-    lo_num = wave_least(lo_num);
-    if (lane == 0u) s_part[wave] = lo_num;
-    __syncthreads();
-    if (tid != 0u) return;
-    for (uint32_t w = 1; w < kLongWaves; w++) lo_num = s_part[w] < lo_num ? s_part[w] : lo_num;
-    if (lo_num != kAbsent) atomicMin(p.state + row, lo_num);
+    chunk_best_number(p, row, c, s_part, p.state + row);
 }
 
 // One chunk of one row per workgroup: the sum of q over the chunk, chunk 0 with the head keys, by ONE plain 64-bit store -- an empty
@@ -416,7 +343,6 @@ int run_logprob(const uint16_t* keys, size_t rows, size_t cols, const int32_t* d
     return LSDSORT_OK;
 }
 
-bool sizes_ok(size_t rows, size_t cols) { return rows <= LSDSORT_MAX_KEYS && (rows == 0 || cols <= LSDSORT_MAX_KEYS / rows); }
 bool slots_ok(size_t slots) { return slots >= 1 && slots <= LSDSORT_LOGPROB_MAX_SLOTS; }
 
 }  // namespace
@@ -434,10 +360,9 @@ int lsdsort_logprob16_device(const void* d_keys, size_t rows, size_t cols, const
                              int key_type, float* d_logprob, int32_t* d_rank, float* d_lse, void* d_workspace, size_t workspace_bytes,
                              void* hip_stream)
 {
-    if (key_type != LSDSORT_KEY16_F16 && key_type != LSDSORT_KEY16_BF16) return LSDSORT_ERR_INVALID_ARG;
     Key16Map map;
-    LSD_TRY(key16_map(key_type, 1, &map));
-    const Values16 val{key_type == LSDSORT_KEY16_BF16 ? 0x007Fu : 0x03FFu, key_type == LSDSORT_KEY16_BF16 ? 1u : 0u};
+    Values16 val;
+    LSD_TRY(float16_values(key_type, &map, &val));
     if (!lsd::slots_ok(slots)) return LSDSORT_ERR_INVALID_ARG;
     if (!lsd::sizes_ok(rows, cols)) return LSDSORT_ERR_TOO_LARGE;
     if (rows == 0 || cols == 0) return LSDSORT_OK;

@@ -243,6 +243,8 @@ Chunks chunks_for(size_t rows, size_t cols)
     return Chunks{(uint32_t)chunk, (uint32_t)((cols + chunk - 1) / chunk)};
 }
 size_t chunk_cap_for(size_t cols) { return min_sz(kMaxChunks, (cols + kMinChunk - 1) / kMinChunk); }
+// a [rows][cols] array a row entry takes: no more than LSDSORT_MAX_KEYS rows, and no more keys in all (no product that can overflow)
+bool sizes_ok(size_t rows, size_t cols) { return rows <= LSDSORT_MAX_KEYS && (rows == 0 || cols <= LSDSORT_MAX_KEYS / rows); }
 
 // The select's part of a workspace: control | row states | [offsets of rows + 1 segments] | counters [rows][kBins] | chunk counts
 // of `count_bytes` each -- the last two for rows above kLocalSortCap keys only.  A unit's own arrays follow from `end`.

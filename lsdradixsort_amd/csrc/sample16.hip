@@ -29,63 +29,27 @@
 //                                   G and the remainder), locate (one workgroup per row reads that ONE chunk up to the crossing)
 // Short rows: one read of the row (2 B/key by byte accounting); long rows two reads plus one chunk: about 4 B/key.
 //
-// The row read is this unit's own (read_front / read_body): select_tiles16.hpp belongs to the seven selecting units.  A lane holds two
-// 16-byte groups of its wave's tile: register 8 j + e is body position q0 + 8 (64 j + lane) + e, so position order is "head keys by
-// lane, then group j = 0, 1: lane by lane, key by key".  Keys are only read; every store goes to d_index[row] / d_logprob[row] under
-// row < rows.  Every launch is sized from (rows, cols); phases are ordered by kernel boundaries.
+// The row read (read_front / read_body), the best number of a row or chunk and the small wave helpers are mass_rows16.hpp's, shared
+// with logprob16.hip and topp16.hip; select_tiles16.hpp belongs to the seven selecting units.  A lane holds two 16-byte groups of its
+// wave's tile: register 8 j + e is body position q0 + 8 (64 j + lane) + e, so position order is "head keys by lane, then group
+// j = 0, 1: lane by lane, key by key".  Keys are only read; every store goes to d_index[row] / d_logprob[row] under row < rows.  Every
+// launch is sized from (rows, cols); phases are ordered by kernel boundaries.
 #define LSDSORT_BUILD 1
 #include "../../include/lsdsort.h"
 
 #include "keys16_map.hpp"
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
+#include "mass_rows16.hpp"
 #include "radix_select.hpp"
 
 namespace lsd {
 namespace {
 
 constexpr uint32_t kSampleFaultLocate = 1024u;   // fault word: no key was located for a row that has mass (never expected; nothing stored)
-constexpr uint32_t kAbsent = 0xFFFFFFFFu;        // a register without a key: a sortable value is below 65536, and it is no number
 constexpr uint32_t kNoPick = 0xFFFFu;            // row state of the long rows: no chunk was picked (Z == 0, or a fault)
-using RowKeys = Row<uint16_t>;
 
-// ---- the row read -------------------------------------------------------------------------------------------------------------------
-// The wave's tile from body position q0 on, valid below `end`: a whole group by one 16-byte load, the others key by key.
-__device__ __forceinline__ void read_body(const RowKeys& r, uint32_t q0, uint32_t end, uint32_t lane, const Key16Map& m, uint32_t (&t)[kRegs])
-{
-#pragma unroll
-    for (int j = 0; j < kRegs / 8; j++) {
-        const uint32_t q = q0 + ((uint32_t)j * 64u + lane) * kGroupKeys;
-        if (q < end && end - q >= kGroupKeys) {
-            const uint4 v = *reinterpret_cast<const uint4*>(r.keys + r.head + q);
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                t[8 * j + 2 * i] = to_sortable16(w[i] & 0xFFFFu, m);
-                t[8 * j + 2 * i + 1] = to_sortable16(w[i] >> 16, m);
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                t[8 * j + e] = kAbsent;
-                if (q < end && end - q > (uint32_t)e) t[8 * j + e] = to_sortable16(r.keys[r.head + q + (uint32_t)e], m);
-            }
-        }
-    }
-}
-// key `lane` of the keys in front of the row's first 16-byte line, for the one wave that owns them
-__device__ __forceinline__ uint32_t read_front(const RowKeys& r, uint32_t lane, const Key16Map& m)
-{
-    return lane < r.head ? to_sortable16(r.keys[lane], m) : kAbsent;
-}
-
-// ---- wave arithmetic ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t wave_least(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return b < a ? b : a; }); }
-__device__ __forceinline__ uint32_t best_number(uint32_t s, uint32_t lo, const Values16& v)
-{
-    const uint32_t n = is_number(s, v) ? s : kAbsent;
-    return n < lo ? n : lo;
-}
+// ---- wave arithmetic (wave_least, best_number, wave_add64 and log_total: mass_rows16.hpp) -------------------------------------------
 // The inclusive scan over the wave of one value below 2^42 per lane (eight masses of at most 2^32): two limbs of 22 and 20 bits, each
 // scanned on the DPP network.  All 64 lanes must be active.
 __device__ __forceinline__ uint64_t wave_scan64(uint64_t v)
@@ -98,13 +62,6 @@ __device__ __forceinline__ uint64_t of_lane63(uint64_t v)
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
     return ((uint64_t)hi << 32) | lo;
 }
-// the sum over the wave of any 64-bit value per lane (the chunk sums of the long rows): every lane ends with it
-__device__ __forceinline__ uint64_t wave_add64(uint64_t v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, off, kWave);
-    return v;
-}
 
 // G of a row with Z != 0
 __device__ __forceinline__ uint64_t mass_point(float u, uint64_t z)
@@ -114,8 +71,6 @@ __device__ __forceinline__ uint64_t mass_point(float u, uint64_t z)
     const uint64_t g = (uint64_t)floor((double)u * (double)z);   // below 2^62
     return g < z - 1ull ? g : z - 1ull;
 }
-// ln(Z * 2^-32), Z != 0: the conversion rounds Z to 24 bits, the scaling is exact
-__device__ __forceinline__ float log_total(uint64_t z) { return logf((float)z * 2.3283064365386963e-10f); }
 
 // One wave's tile in registers (read_body at q0; h the head keys in front of it, kAbsent where there is none) with its masses, scanned
 // in position order: per lane the mass in front of its head key and in front of each of its two groups, within the wave, and the wave's
@@ -231,19 +186,7 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) sample16_short_kernel
         const uint32_t h = wave == 0u ? read_front(r, lane, p.map) : kAbsent;
         const float u = uniform_f32(u_load);   // one value per row
         const float scale = p.has_temperature ? uniform_f32(scale_of(t_load)) : kLog2e;   // and one scale
-        uint32_t lo_num = best_number(h, kAbsent, p.val);
-#pragma unroll
-        for (int i = 0; i < kRegs; i++) lo_num = best_number(t[i], lo_num, p.val);
-        lo_num = wave_least(lo_num);
-        if (WAVES > 1) {
-            if (lane == 0u) s_min[wave] = lo_num;
-            __syncthreads();
-#pragma unroll
-            for (int w = 0; w < WAVES; w++) {
-                const uint32_t o = s_min[w];
-                lo_num = o < lo_num ? o : lo_num;
-            }
-        }
+        const uint32_t lo_num = row_best_number<WAVES>(t, h, s_min, wave, lane, p.val);
         const float best = value_of(lo_num & 0xFFFFu, p.map, p.val);   // a row of NaNs: every q is 0
         Masses s;
         scan_masses(t, h, best, scale, q0 + 64u * kGroupKeys < r.body, p.map, p.val, s);
@@ -306,22 +249,7 @@ __global__ void __launch_bounds__(kLongThreads) sample16_best_kernel(const LongP
     __shared__ uint32_t s_part[kLongWaves];
     const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
     if (row >= p.rows) return;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const RowKeys r = row_of(p.keys, row, p.cols);
-    const ChunkRange g = chunk_of(r, p.chunk, c);
-    uint32_t lo_num = best_number((c == 0u && wave == 0u) ? read_front(r, lane, p.map) : kAbsent, kAbsent, p.val);   // uniform
-    for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
-        uint32_t t[kRegs];
-        read_body(r, tile + wave * kWaveTile, g.hi, lane, p.map, t);
-#pragma unroll
-        for (int i = 0; i < kRegs; i++) lo_num = best_number(t[i], lo_num, p.val);
-    }
-    lo_num = wave_least(lo_num);
-    if (lane == 0u) s_part[wave] = lo_num;
-    __syncthreads();
-    if (tid != 0u) return;
-    for (uint32_t w = 1; w < kLongWaves; w++) lo_num = s_part[w] < lo_num ? s_part[w] : lo_num;
-    if (lo_num != kAbsent) atomicMin(reinterpret_cast<uint32_t*>(p.state + row), lo_num);   // the state's x
+    chunk_best_number(p, row, c, s_part, reinterpret_cast<uint32_t*>(p.state + row));   // the state's x
 }
 
 // One chunk of one row per workgroup: the sum of q over the chunk, chunk 0 with the head keys, by ONE plain 64-bit store.  An empty
@@ -500,8 +428,6 @@ int run_sample(const uint16_t* keys, size_t rows, size_t cols, const float* d_u,
     return LSDSORT_OK;
 }
 
-bool sizes_ok(size_t rows, size_t cols) { return rows <= LSDSORT_MAX_KEYS && (rows == 0 || cols <= LSDSORT_MAX_KEYS / rows); }
-
 }  // namespace
 }  // namespace lsd
 
@@ -516,10 +442,9 @@ size_t lsdsort_sample16_workspace_bytes(size_t rows, size_t cols)
 int lsdsort_sample16_ex_device(const void* d_keys, size_t rows, size_t cols, const float* d_u, const float* d_temperature, int key_type,
                                int32_t* d_index, float* d_logprob, void* d_workspace, size_t workspace_bytes, void* hip_stream)
 {
-    if (key_type != LSDSORT_KEY16_F16 && key_type != LSDSORT_KEY16_BF16) return LSDSORT_ERR_INVALID_ARG;
     Key16Map map;
-    LSD_TRY(key16_map(key_type, 1, &map));
-    const Values16 val{key_type == LSDSORT_KEY16_BF16 ? 0x007Fu : 0x03FFu, key_type == LSDSORT_KEY16_BF16 ? 1u : 0u};
+    Values16 val;
+    LSD_TRY(float16_values(key_type, &map, &val));
     if (!lsd::sizes_ok(rows, cols)) return LSDSORT_ERR_TOO_LARGE;
     if (rows == 0 || cols == 0) return LSDSORT_OK;
     if (!d_keys || ((uintptr_t)d_keys & 1)) return LSDSORT_ERR_INVALID_ARG;

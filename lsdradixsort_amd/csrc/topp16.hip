@@ -35,15 +35,17 @@
 // one write: 10 B/key.  Rows with !(p < 1) are off: copied, or left alone in place.
 //
 // load_tile / load_head / store_tile / store_head are select_tiles16.hpp's, shared with kth16_rowk.hip's top-k filter: the stores
-// keep (key >> shift) <= prefix, here the whole threshold with shift 0.  Every launch is sized from (rows, cols); phases are ordered
-// by kernel boundaries; every store into d_out is guarded by row < rows and stays within the row.  Nothing here ranks with the
-// returning add: the result does not depend on lsdsort_set_rank_method.
+// keep (key >> shift) <= prefix, here the whole threshold with shift 0.  wave_least is mass_rows16.hpp's, shared with the draw and
+// the log-probabilities.  Every launch is sized from (rows, cols); phases are ordered by kernel boundaries; every store into d_out
+// is guarded by row < rows and stays within the row.  Nothing here ranks with the returning add: the result does not depend on
+// lsdsort_set_rank_method.
 #define LSDSORT_BUILD 1
 #include "../../include/lsdsort.h"
 
 #include "keys16_map.hpp"
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
+#include "mass_rows16.hpp"
 #include "radix_select.hpp"
 #include "select_tiles16.hpp"
 
@@ -64,7 +66,6 @@ __device__ __forceinline__ uint64_t wave_sum64(uint64_t v)
     const uint32_t lo = wave_inclusive_scan((uint32_t)v & 0x3FFFFFu), hi = wave_inclusive_scan((uint32_t)(v >> 22));
     return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)hi, 63) << 22) + (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)lo, 63);
 }
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return b < a ? b : a; }); }
 
 // ---- short rows: one wavefront (WAVES = 1, eight rows per workgroup) or one workgroup (WAVES = 16) per row ----------------------
 struct ShortParams {
@@ -112,7 +113,7 @@ __device__ __forceinline__ uint64_t group_sum64(uint64_t v, volatile lds_u64* s_
 template <int WAVES>
 __device__ __forceinline__ uint32_t group_min(uint32_t v, volatile lds_u32* s_min, uint32_t wave, uint32_t lane)
 {
-    v = wave_min(v);
+    v = wave_least(v);
     if (WAVES == 1) return v;
     if (lane == 0u) s_min[wave] = v;
     __syncthreads();
@@ -288,8 +289,8 @@ __global__ void __launch_bounds__(kLongThreads) topp16_best_kernel(const LongPar
             lo_num = n < lo_num ? n : lo_num;
         }
     }
-    lo_key = wave_min(lo_key);
-    lo_num = wave_min(lo_num);
+    lo_key = wave_least(lo_key);
+    lo_num = wave_least(lo_num);
     if (lane == 0u) {
         s_part[wave] = lo_key;
         s_part[kLongWaves + wave] = lo_num;
@@ -572,16 +573,13 @@ int run_topp(const uint16_t* keys, size_t rows, size_t cols, const RowScalars& r
     return LSDSORT_OK;
 }
 
-bool sizes_ok(size_t rows, size_t cols) { return rows <= LSDSORT_MAX_KEYS && (rows == 0 || cols <= LSDSORT_MAX_KEYS / rows); }
-
 // Both entries.  need_p: the entry without min-p has no defined answer for a NULL d_p.
 int filter_call(const void* d_keys, size_t rows, size_t cols, const RowScalars& rs, bool need_p, int key_type, uint16_t fill_bits, void* d_out,
                 void* d_workspace, size_t workspace_bytes, void* hip_stream)
 {
-    if (key_type != LSDSORT_KEY16_F16 && key_type != LSDSORT_KEY16_BF16) return LSDSORT_ERR_INVALID_ARG;
     Key16Map map;
-    LSD_TRY(key16_map(key_type, 1, &map));
-    const Values16 val{key_type == LSDSORT_KEY16_BF16 ? 0x007Fu : 0x03FFu, key_type == LSDSORT_KEY16_BF16 ? 1u : 0u};
+    Values16 val;
+    LSD_TRY(float16_values(key_type, &map, &val));
     if (!lsd::sizes_ok(rows, cols)) return LSDSORT_ERR_TOO_LARGE;
     if (rows == 0 || cols == 0) return LSDSORT_OK;
     if (!d_keys || !d_out || (((uintptr_t)d_keys | (uintptr_t)d_out) & 1)) return LSDSORT_ERR_INVALID_ARG;

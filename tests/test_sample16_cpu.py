@@ -380,7 +380,7 @@ def test_the_unit_includes_the_shared_headers_only_and_has_no_inline_assembly():
     csrc = os.path.join(ROOT, "lsdradixsort_amd", "csrc")
     text = open(os.path.join(csrc, "sample16.hip")).read()
     assert set(re.findall(r'#include "([^"]+)"', text)) == {"../../include/lsdsort.h", "keys16_map.hpp", "lsd_device.hpp", "lsd_host.hpp",
-                                                             "radix_select.hpp"}
+                                                             "mass_rows16.hpp", "radix_select.hpp"}
     code = re.sub(r"//.*", "", text)
     assert "asm" not in code
     for name in ("load_tile", "load_head", "locate_tile", "store_tile", "store_head", "same_phase"):   # select_tiles16.hpp's, not this unit's

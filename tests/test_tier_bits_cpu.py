@@ -31,8 +31,10 @@ def test_tier_and_tile_constants_of_the_sources():
     for unit in UNITS:   # the units choose their size class by these two constants
         text = source(unit + ".hip")
         assert re.search(r"cols <= \(size_t\)kWaveSegCap\b", text) and re.search(r"cols <= \(size_t\)kLocalSortCap\b", text), f"{unit}.hip: {UPDATE}"
-    text = source("sample16.hip")   # the lane layout the offsets aim at: register 8 j + e is body position q0 + 8 (64 j + lane) + e
-    assert "q0 + ((uint32_t)j * 64u + lane) * kGroupKeys" in text, UPDATE
+    text = source("mass_rows16.hpp")   # the lane layout the offsets aim at: register 8 j + e is body position q0 + 8 (64 j + lane) + e
+    assert "q0 + ((uint32_t)j * 64u + lane) * kGroupKeys" in text, UPDATE   # read_body, the draw's and the log-probabilities' row read
+    for unit in ("sample16", "logprob16"):
+        assert '#include "mass_rows16.hpp"' in source(unit + ".hip") and "read_body(" in source(unit + ".hip"), UPDATE
 
 
 def test_widths_reach_every_size_class_and_offsets_every_boundary():

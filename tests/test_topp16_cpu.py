@@ -355,7 +355,7 @@ def test_kernels_no_scratch_no_spill_and_recorded_resources():
 def test_the_unit_includes_the_shared_headers_only_and_has_no_inline_assembly():
     text = open(os.path.join(ROOT, "lsdradixsort_amd", "csrc", "topp16.hip")).read()
     assert set(re.findall(r'#include "([^"]+)"', text)) == {"../../include/lsdsort.h", "keys16_map.hpp", "lsd_device.hpp", "lsd_host.hpp",
-                                                             "radix_select.hpp", "select_tiles16.hpp"}
+                                                             "mass_rows16.hpp", "radix_select.hpp", "select_tiles16.hpp"}
     assert "asm" not in re.sub(r"//.*", "", text)
     # the launches the GPU suite runs past their grid caps
     launch = re.compile(r"(\w+_kernel(?:<[^<>]*>)?)[>,(\s]*dim3\(grid_for\(([^,()]+),\s*(\w+)\s*,\s*(\w+)\s*\)\)")
