@@ -732,12 +732,9 @@ LSDSORT_API int lsdsort_logprob16_device(const void* d_keys, size_t rows, size_t
  * section 6.18): the distinct keys of an array and how often each occurs -- torch.unique_consecutive, torch.unique(sorted=True),
  * np.unique(return_index / return_inverse / return_counts), group-by, deduplication of ids.  Both entries are device-resident and
  * stream-ordered, allocate nothing and never synchronise with the host; EVERY LAUNCH IS SIZED FROM n ALONE -- the number of runs is
- * known on the device only and sizes nothing.  GRAPH CAPTURE: lsdsort_rle_device, which launches kernels only and rewrites every word
- * of state on every call, can be captured after lsdsort_prepare_device and replayed any number of times on changed keys.
- * lsdsort_unique_device is NOT promised to be replayable: a captured call was right on its first replay on changed keys, and on a
- * SECOND replay in the same workspace the sort inside left the keys unsorted and lsdsort_unique_check_device answered
- * LSDSORT_ERR_DEVICE_FAULT (cause not found).  Call it eagerly, or check lsdsort_unique_check_device behind
- * every replay.  No workgroup waits for another: the phases are ordered by kernel boundaries.
+ * known on the device only and sizes nothing.  GRAPH CAPTURE: both entries launch kernels only and clear or rewrite every word of
+ * state they read on every call; either can be captured after lsdsort_prepare_device and replayed any number of times on changed
+ * keys, in the same workspace.  No workgroup of the run-length phases waits for another: they are ordered by kernel boundaries.
  * EQUALITY IS EQUALITY OF BIT PATTERNS, which matches the sorts' total order: -0.0 and +0.0 are two values and every NaN payload is a
  * value of its own.  torch.unique and torch.unique_consecutive compare floats by value (they merge -0.0 with +0.0 and keep every NaN
  * apart); on integer keys, and on floats that hold no -0.0 next to a +0.0 and no NaN, the results are the same.

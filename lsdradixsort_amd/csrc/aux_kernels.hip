@@ -27,6 +27,39 @@ hipError_t launch_keep_fault(uint32_t* sticky, const uint32_t* fault, hipStream_
     return hipGetLastError();
 }
 
+// The opening clear of a sort, a partition or a caller's table: 16-byte stores, the grid walking the range.
+constexpr int kClearThreads = 256;
+constexpr uint32_t kClearMaxGrid = 2048;   // eight workgroups per CU: 8 MiB (a 2^28-key sort's counts and status rows) is 1 KiB a thread
+
+__global__ void __launch_bounds__(kClearThreads) clear_kernel(uint4* __restrict__ quads, uint32_t count)
+{
+    for (uint32_t i = blockIdx.x * kClearThreads + threadIdx.x; i < count; i += gridDim.x * kClearThreads) quads[i] = make_uint4(0, 0, 0, 0);
+}
+
+// the same by single words, for a caller's array that is promised 4-byte alignment only
+__global__ void __launch_bounds__(kClearThreads) clear_words_kernel(uint32_t* __restrict__ words, uint32_t count)
+{
+    for (uint32_t i = blockIdx.x * kClearThreads + threadIdx.x; i < count; i += gridDim.x * kClearThreads) words[i] = 0u;
+}
+
+hipError_t launch_clear(void* at, size_t bytes, hipStream_t stream)
+{
+    if (!at || ((uintptr_t)at & 3u) || (bytes & 3u) || bytes / 4 > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (bytes == 0) return hipSuccess;
+    if ((((uintptr_t)at | bytes) & 15u) == 0) {
+        const size_t quads = bytes / 16;
+        const uint32_t grid = (uint32_t)((quads + kClearThreads - 1) / kClearThreads);
+        hipLaunchKernelGGL(clear_kernel, dim3(grid < kClearMaxGrid ? grid : kClearMaxGrid), dim3(kClearThreads), 0, stream, static_cast<uint4*>(at),
+                           (uint32_t)quads);
+    } else {
+        const size_t words = bytes / 4;
+        const uint32_t grid = (uint32_t)((words + kClearThreads - 1) / kClearThreads);
+        hipLaunchKernelGGL(clear_words_kernel, dim3(grid < kClearMaxGrid ? grid : kClearMaxGrid), dim3(kClearThreads), 0, stream,
+                           static_cast<uint32_t*>(at), (uint32_t)words);
+    }
+    return hipGetLastError();
+}
+
 __global__ void store_u64_kernel(uint64_t* out, uint64_t value) { *out = value; }
 
 hipError_t launch_store_u64(uint64_t* out, uint64_t value, hipStream_t stream)

@@ -20,7 +20,7 @@ typedef __attribute__((address_space(3))) uint64_t lds_u64;
 // publishes it and a single relaxed agent-scope load observes it (no fences: the data is the
 // flag).  State = the low two bits:  0 = stale (not written in this pass), 1 = tile aggregate,
 // 2 = inclusive prefix.  A sort keeps TWO status arrays: a pass works in one while its workgroups
-// zero the other for the pass after it (rank_scatter.hpp, clear_next; the sort's opening memset
+// zero the other for the pass after it (rank_scatter.hpp, clear_next; the sort's opening clear
 // covers the first), so every word a pass reads is either zero or was written by THAT pass -- no
 // word outlives its pass (a single never-cleared, parity-coded array is
 // what let round 1's prototype read an old prefix as a current one).  The codes still take a

@@ -411,8 +411,12 @@ hipError_t launch_half_decide(const uint32_t* keys, uint32_t* words, hipStream_t
 hipError_t launch_widen_counts(const uint32_t* hist32, uint64_t* counts64, int bins, hipStream_t stream);
 
 // *sticky |= *fault (stream-ordered): callers that run several sorts in ONE workspace keep each sort's fault word this way --
-// the next sort's opening memset clears the workspace's own word (wide.hip, sharded.hip).
+// the next sort's opening clear takes the workspace's own word (wide.hip, sharded.hip).
 hipError_t launch_keep_fault(uint32_t* sticky, const uint32_t* fault, hipStream_t stream);
+
+// [at, at + bytes) = 0 by a kernel (stream-ordered; both multiples of 4: 16-byte stores where both are multiples of 16, single words
+// otherwise).  Every clear on a path a caller may capture goes through here, not through hipMemsetAsync: DESIGN.md section 6.18.
+hipError_t launch_clear(void* at, size_t bytes, hipStream_t stream);
 
 // *out = value (stream-ordered).
 hipError_t launch_store_u64(uint64_t* out, uint64_t value, hipStream_t stream);

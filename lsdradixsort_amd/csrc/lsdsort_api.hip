@@ -566,7 +566,7 @@ PassParams chained_pass(const Chain& c, const uint32_t* in, uint32_t* out, size_
     // parity-coded reuse of lsd_device.hpp (every word rewritten every pass) does not apply.
     // Two status arrays instead: a pass works in one and its workgroups clear the other, one
     // row each (the grid has exactly `rows` workgroups), for the pass after it -- 1 KiB of plain
-    // stores per 64 KiB tile and no launch between the passes.  The sort's opening memset
+    // stores per 64 KiB tile and no launch between the passes.  The sort's opening clear
     // covers the even array.
     p.status = c.status[step & 1];
     p.status_clear = last ? nullptr : c.status[(step + 1) & 1];
@@ -614,7 +614,7 @@ int hybrid_upfront(const SortRequest& rq, const SortPlan& sp)
     LSD_HIP(lsd::launch_hybrid_sample(rq.keys, n, sp.bucket_bits, sp.hyb, rq.stream));
     if (sp.halves) {
         // the half variant: the same read counts the 2^16 groups (its 16-bit-counter form; a counter that overflows loses keys
-        // from the sum, which the planner refuses), two to a word of the sort's own bucket array -- zero since the opening memset --
+        // from the sum, which the planner refuses), two to a word of the sort's own bucket array -- zero since the opening clear --
         // and the fold gives the planner its 2^15 buckets
         LSD_HIP(lsd::launch_hybrid_histograms(radix_bits, rq.keys, n, sp.L.region0, sp.fields, sp.bucket, 16, sp.hyb, rq.stream, rq.xf, true));
         LSD_HIP(lsd::launch_half_fold(sp.bucket, sp.bucket15, sp.first, rq.stream));
@@ -811,7 +811,7 @@ int run_sort(const SortRequest& rq)
     if (sp.small) return small_sort(rq, sp);
     if (rq.ev) rq.ev->half_tried = sp.halves != nullptr;
     LSD_TRY(mark(rq, StageEvents::kStart));
-    LSD_HIP(hipMemsetAsync(rq.ws, 0, sp.L.zero_bytes, rq.stream));
+    LSD_HIP(lsd::launch_clear(rq.ws, sp.L.zero_bytes, rq.stream));   // a kernel, not a memset node: DESIGN.md section 6.18
     LSD_TRY(mark(rq, StageEvents::kCleared));
     if (rq.algorithm == LSDSORT_ALGO_STAGED) return staged_passes(rq, sp);
     if (sp.hyb) LSD_TRY(hybrid_upfront(rq, sp));
@@ -1013,7 +1013,7 @@ int lsdsort_set_xcd_chunk(int chunk)
 int lsdsort_workspace_form(const void* d_workspace, void* hip_stream, int* hybrid)
 {
     if (!d_workspace || !hybrid) return LSDSORT_ERR_INVALID_ARG;
-    // the opening memset of every sort clears the word; only the hybrid planner sets it
+    // the opening clear of every sort takes the word; only the hybrid planner sets it
     uint32_t ok = 0;
     LSD_HIP(hipMemcpyAsync(&ok, static_cast<const uint32_t*>(d_workspace) + kHybridOffsetWords + lsd::kHybridWordOk, sizeof(ok),
                            hipMemcpyDeviceToHost, static_cast<hipStream_t>(hip_stream)));
@@ -1031,7 +1031,7 @@ int lsdsort_set_half_hop(int on)
 int lsdsort_workspace_half(const void* d_workspace, void* hip_stream, int* half)
 {
     if (!d_workspace || !half) return LSDSORT_ERR_INVALID_ARG;
-    // both words are cleared by the opening memset of every sort; the second is written only where the variant was attempted
+    // both words are cleared by the opening clear of every sort; the second is written only where the variant was attempted
     uint32_t words[2] = {0, 0};
     const uint32_t* hyb = static_cast<const uint32_t*>(d_workspace) + kHybridOffsetWords;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
@@ -1468,7 +1468,7 @@ int lsdsort_digit_histograms_u32_device(const uint32_t* d_keys, size_t n, int ra
     LSD_TRY(check_device_ready());
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const int groups = 32 / radix_bits;
-    LSD_HIP(hipMemsetAsync(d_hist, 0, (size_t)groups * ((size_t)1 << radix_bits) * sizeof(uint32_t), stream));
+    LSD_HIP(lsd::launch_clear(d_hist, (size_t)groups * ((size_t)1 << radix_bits) * sizeof(uint32_t), stream));
     if (n == 0) return LSDSORT_OK;
     LSD_HIP(lsd::launch_digit_histograms(radix_bits, groups, 0, d_keys, (uint32_t)n, d_hist, stream));
     return LSDSORT_OK;
@@ -1510,7 +1510,7 @@ static int partition_impl(const uint32_t* d_in, uint32_t* d_out, size_t n, int m
     chain.status[0] = reinterpret_cast<uint32_t*>(ws + L.status);
     uint32_t* hist = reinterpret_cast<uint32_t*>(ws + L.counts);
     const int bins = 1 << msb_bits;
-    LSD_HIP(hipMemsetAsync(ws, 0, L.zero_bytes, stream));
+    LSD_HIP(lsd::launch_clear(ws, L.zero_bytes, stream));
     if (msb_bits == 0) {
         // one bucket: the shard itself
         LSD_HIP(lsd::launch_store_u64(d_counts, (uint64_t)n, stream));

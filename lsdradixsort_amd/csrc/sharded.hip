@@ -109,7 +109,7 @@ constexpr int kMaxBuckets = 16;   // world x sub-buckets: the partition pass tak
 
 struct ShardedLayout {
     size_t sticky = 0;     // u32: fault words of the step's local sorts, ORed together (they share one workspace, and every
-                           // sort's opening memset clears that workspace's own word)
+                           // sort's opening clear takes that workspace's own word)
     size_t vec = 0;        // u64[B + 1]: this rank's bucket counts, then its output capacity   (B <= kMaxBuckets)
     size_t all = 0;        // u64[W][B + 1]: everybody's
     size_t part_ws = 0;    // workspace of the partition pass
@@ -636,7 +636,7 @@ static int sharded_step(lsdsort_comm* c, const uint32_t* d_keys_in, size_t n_loc
     uint32_t* d_send = reinterpret_cast<uint32_t*>(ws + L.send);
     uint32_t* sticky = reinterpret_cast<uint32_t*>(ws + L.sticky);
     Transport& T = *c->transport;
-    LSD_HIP(hipMemsetAsync(sticky, 0, sizeof(uint32_t), stream));
+    LSD_HIP(lsd::launch_clear(sticky, sizeof(uint32_t), stream));
 
     // 0.  splitter rule only: a regular sample of every shard to every rank (one more host wait, ahead of the partition);
     //     each rank then cuts the sorted (key, source rank) sample into B equal parts and derives ITS thresholds
@@ -715,7 +715,7 @@ static int sharded_step(lsdsort_comm* c, const uint32_t* d_keys_in, size_t n_loc
             LSD_HIP(hipEventRecord(c->arrived[j], stream));
             LSD_HIP(hipStreamWaitEvent(c->sorter, c->arrived[j], 0));
         }
-        if (sub_size[j] == 0) LSD_HIP(hipMemsetAsync(ws + L.sort_ws, 0, sizeof(uint32_t), sort_on));   // an empty sort never touches its fault word
+        if (sub_size[j] == 0) LSD_HIP(lsd::launch_clear(ws + L.sort_ws, sizeof(uint32_t), sort_on));   // an empty sort never touches its fault word
         // under the MSB partition the keys of sub-bucket j of rank r all carry the top `bits` bits (r, j): the hybrid form plans
         // its buckets below such a prefix (hybrid.hip; the device finds it itself -- the argument says what this caller knows)
         LSD_TRY(lsdsort_u32_device_prefixed(d_out + sub_begin, ws + L.sort_ws, L.sort_ws_bytes, (size_t)sub_size[j], radix_bits,

@@ -135,7 +135,7 @@ int key64_transform(int key_type, int descending, Key64Transform* xf)
 
 struct WideLayout {
     size_t sticky = 0;              // u32: fault words of every sort inside the call, ORed together (each sort's opening
-                                    // memset clears the shared sort workspace's own word, so the first sort's would be lost)
+                                    // clear takes the shared sort workspace's own word, so the first sort's would be lost)
     size_t a = 0, b = 0;            // uint32[n]: low / high key words (64-bit keys)
     size_t c = 0, d = 0;            // uint32[n]: low / high payload words (64-bit payloads)
     size_t sort_ws = 0;             // workspace of the sorts inside
@@ -208,7 +208,7 @@ static int sort_wide(void* d_keys, void* d_vals, int key_bits, int val_bits, voi
     const uint32_t g = grid_for(n);
     uint32_t* sticky = reinterpret_cast<uint32_t*>(ws + L.sticky);
     const uint32_t* fault = reinterpret_cast<const uint32_t*>(ws + L.sort_ws);   // the sorts' fault word: first word of their workspace
-    LSD_HIP(hipMemsetAsync(sticky, 0, sizeof(uint32_t), s));
+    LSD_HIP(lsd::launch_clear(sticky, sizeof(uint32_t), s));
     // the words of the records as arrays of their own: 32-bit members are used where they lie
     uint32_t* klo = key_bits == 64 ? reinterpret_cast<uint32_t*>(ws + L.a) : static_cast<uint32_t*>(d_keys);
     uint32_t* khi = key_bits == 64 ? reinterpret_cast<uint32_t*>(ws + L.b) : nullptr;
@@ -238,7 +238,7 @@ static int sort_wide(void* d_keys, void* d_vals, int key_bits, int val_bits, voi
         if (vlo) pay[np++] = vlo;
         if (vhi) pay[np++] = vhi;
         LSD_TRY(lsdsort_multi_u32_device(klo, pay, np, ws + L.sort_ws, L.sort_ws_bytes, n, radix_bits, s));
-        LSD_HIP(lsd::launch_keep_fault(sticky, fault, s));   // the next sort's memset clears that word
+        LSD_HIP(lsd::launch_keep_fault(sticky, fault, s));   // the next sort's opening clear takes that word
     }
     if (khi) {
         uint32_t* pay[3];

@@ -226,10 +226,11 @@ def _runs_of(length, n, w, seed):
 
 
 @functools.lru_cache(maxsize=None)
-def families(n, w):
+def families(n, w, seed=0):
     """{name: words} -- the run-length inputs at size n and width w; runs of TILE, TILE - 1 and TILE + 1 put run edges on, before
-    and after tile edges; `recurring` is unsorted: runs of three values come back again and again."""
-    rng = np.random.default_rng(1000 * w + n)
+    and after tile edges; `recurring` is unsorted: runs of three values come back again and again.  Another `seed` draws `random8`
+    and `recurring` anew from the same values (tests/_replay.py)."""
+    rng = np.random.default_rng(1000 * w + n + 7919 * seed)
     eight = _values(8, w, 3)
     three = _values(3, w, 4)
     lengths = rng.integers(1, 6, size=n)

@@ -306,9 +306,9 @@ def test_rle_graph_replays_follow_changed_keys(gpu, w):
 
 @pytest.mark.parametrize("key_type", ["int32", "float64"])
 def test_graph_replay_follows_changed_keys(gpu, key_type):
-    """lsdsort_unique_device captured once and replayed ONCE on changed keys: count and outputs follow.  That is all the header
-    promises for this entry: a SECOND replay in the same workspace was seen to leave the keys unsorted with the fault word of the sort
-    inside set (include/lsdsort.h) -- its cause is not found, and that case is not run here again."""
+    """lsdsort_unique_device captured once and replayed four times, each time on other keys -- eight values, a run per key, one run,
+    eight values drawn anew: count and every output follow.  (A second replay used to come back unsorted: the sort inside opened with
+    a captured memset; tests/test_gpu_replay.py holds every entry that opened with one.)"""
     import torch
 
     L = gpu.lib()
@@ -339,8 +339,9 @@ def test_graph_replay_follows_changed_keys(gpu, key_type):
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         call()
-    for name in ("random8",):   # captured on two distinct values, replayed on eight: the count and every output follow the keys
-        bits = un.shuffled(n, w, name)
+    # captured on two distinct values; the last replay is another draw of the eight values of the first
+    replays = [(name, un.shuffled(n, w, name)) for name in ("random8", "all_distinct", "all_equal")] + [("random8 again", un.families(n, w, 1)["random8"])]
+    for name, bits in replays:
         want = un.oracle_unique(bits, key_type, True)
         m = want["keys"].size
         dk.copy_(torch.from_numpy(bits.view(signed).copy()))
