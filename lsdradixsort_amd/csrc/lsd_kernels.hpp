@@ -160,8 +160,13 @@ struct PassParams {
     uint32_t* status_clear;      // the next pass's status array: workgroup b zeroes row b; may be null
     uint32_t* tickets;           // [kMaxRegions] arrival ticket dispensers for this pass (zeroed)
     uint32_t parity;             // pass parity for the status codes
-    // staged form
-    const uint32_t* global_off;  // [num_tiles][2^R] digit-major exclusive scan, block-major
+    union {
+        // staged form
+        const uint32_t* global_off;  // [num_tiles][2^R] digit-major exclusive scan, block-major
+        // chained form, launch_rank_scatter_half only: see half_out below (the struct keeps its size: every other
+        // instantiation's kernel arguments are what they were)
+        const uint32_t* half_on;
+    };
     uint32_t* fault;             // workspace fault word
     uint32_t spin_limit;         // empty look-back polls a tile sits out before it gives up (lsd_device.hpp kSpinLimit)
     uint32_t mute_row;           // diagnostic builds only (LSD_FAULT_INJECT): status row + 1 that never publishes; 0 = none
@@ -178,7 +183,8 @@ struct PassParams {
     KeyTransform xin;    // first pass: applied to every key as it is loaded
     KeyTransform xout;   // last pass: undone on every key as it is stored
     // The half-writing pass B of the hybrid form (launch_rank_scatter_half only): every key leaves as its low 16 bits, to
-    // half_out[the index its 32 bits would have gone to in the output].
+    // half_out[the index its 32 bits would have gone to in the output] -- where *half_on != 0; where it is 0 the launch is pass B
+    // as ever and stores the keys to the output (uniform: ONE launch serves both, the device having decided in between).
     uint16_t* half_out;
 };
 
@@ -195,9 +201,9 @@ hipError_t launch_rank_scatter(int radix_bits, const TileShape& shape, int rank_
                                const PassParams& p, hipStream_t stream);
 
 // Pass B of the hybrid form writing HALVES: the chained keys-only kernel of 8-bit digits, shape kHalfShapeR8
-// (1024 x 32, one LDS round) and the returning-add rank, with one difference -- the read-back stores (uint16_t)key to
-// p.half_out[destination] instead of the key to the output buffer.  Ticket, look-back, destination guard, give-up path and the
-// clearing of the next pass's status rows are the sibling's.
+// (1024 x 32, one LDS round) and the returning-add rank, with one difference -- where *p.half_on is set the read-back stores
+// (uint16_t)key to p.half_out[destination] instead of the key to the output buffer.  Ticket, look-back, destination guard,
+// give-up path and the clearing of the next pass's status rows are the sibling's.  A sort launches pass B ONCE, through here.
 constexpr int kHalfShapeR8 = 4;
 hipError_t launch_rank_scatter_half(const PassParams& p, hipStream_t stream);
 
@@ -228,8 +234,9 @@ hipError_t launch_joint_histograms(int radix_bits, const uint32_t* keys, uint32_
 // from plain digit histograms (`regions` = 1; passes may then be 1 for the multi-GPU partition).
 // counts: [passes][2^R][regions]; tables: [passes][region_table_words(R)].
 // `fault` (may be null): the workspace fault word, raised (bit 2) if a pass's counts do not sum to n.
-// `hybrid_ok` (may be null): *hybrid_ok != 0 = the hybrid form runs instead: the plan then says "skip, and leave the status rows
-// alone" (2) for every pass and nothing else is written.
+// `hybrid_ok` (may be null): *hybrid_ok != 0 = the hybrid form runs instead: the plan then gives the first hybrid_global_passes
+// launches, which serve either form, the hybrid form's pairs (run; an odd pass reads the alternate), says "skip, and leave the
+// status rows alone" (2) for every other pass, and nothing else is written.
 // `skip_dead_passes` = false: the plan never marks a pass as the identity (typed sorts: their first and last pass carry the key
 // transform), it only says which way round each pass runs.
 hipError_t launch_scan_regions(int radix_bits, int passes, int regions, const uint32_t* counts, uint32_t n,
@@ -356,8 +363,12 @@ constexpr int kHybridWords = 21;
 // ... and behind them the half form's (half_hop.hip, written by half_decide_kernel where the form is attempted)
 constexpr int kHalfWordOk = 21;          // 1: pass B writes halves and the local stage rebuilds the keys
 constexpr int kHalfWordHigh = 22;        // the prefix bits every key shares, in place: keys[0] & ~(2^(32 - t) - 1), 0 for t = 0
-constexpr int kHalfWordPlan = 23;        // [2]: PassParams::plan of the half-writing pass B (2 = leave at once | 0, then 1: it reads the alternate)
+constexpr int kHalfWordPlan = 23;        // [2]: the decision as a plan pair (2 = no halves | 0, then 1); no launch reads it since pass B is one launch
 constexpr int kHalfWords = 25;
+// ... and behind those the words of the pass launches that serve either form, written by the planner
+constexpr int kSlotWordShift = 25;       // [4]: PassParams::shift of the g-th shared launch: 16 - t + g x radix_bits where the hybrid form
+                                         // runs (= kHybridWordShift), g x radix_bits where the ordinary form does
+constexpr int kSlotWords = 29;
 constexpr int kHalfGroups = 1 << 16;     // the groups of equal 16 bits below the prefix: two to a bucket of the 2^15
 // A prefix of eight bits or more is a constant top byte: the ordinary form then skips a pass and moves as few bytes as the hybrid
 // form would, so the form is only planned for 0 .. 7 shared bits.
@@ -406,6 +417,10 @@ hipError_t launch_half_fold(const uint32_t* packed, uint32_t* bucket15, uint32_t
 // variant.  Writes words[kHalfWord*]; where it runs also words[kHybridWordPlan + 2] = 2 (the full pass B leaves at once).
 // keys: the caller's buffer, still holding the input.
 hipError_t launch_half_decide(const uint32_t* keys, uint32_t* words, hipStream_t stream);
+// The three in one launch, as a sort issues them: launch_half_fold, launch_hybrid_plan (8-bit digits, 2^15 buckets, on the folded
+// counts) and launch_half_decide -- the same words, arrays and list.
+hipError_t launch_half_plan(const uint32_t* packed, uint32_t* bucket15, uint32_t* first, uint32_t n, uint32_t* bases, uint32_t* fields_out,
+                            uint32_t* words, uint32_t* large_list, uint32_t small_cap, const uint32_t* keys, hipStream_t stream);
 
 // counts64[b] = hist32[b], b < bins (multi-GPU bucket sizes as uint64).
 hipError_t launch_widen_counts(const uint32_t* hist32, uint64_t* counts64, int bins, hipStream_t stream);

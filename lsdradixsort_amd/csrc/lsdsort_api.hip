@@ -30,6 +30,8 @@ constexpr size_t kPlanOffsetWords = 16;
 constexpr size_t kHybridOffsetWords = kPlanOffsetWords + lsd::kPlanWords + 1;   // the hybrid form's plan words (hybrid.hip)
 static_assert(kHybridOffsetWords + lsd::kHalfWords <= kControlBytes / sizeof(uint32_t) && lsd::kHalfWords >= lsd::kHybridWords,
               "the plans live in the control block");
+static_assert(kHybridOffsetWords + lsd::kSlotWords <= kControlBytes / sizeof(uint32_t) && lsd::kSlotWordShift >= lsd::kHalfWords,
+              "so do the shared launches' words, behind the half form's");
 // what the bucket rule gives BASELINE's sizes: 2^28 keys 2^15 buckets of 8192, 2^27 keys 2^14 of 8192, 2^27 pairs 2^15 of 4096
 static_assert(lsd::hybrid_bucket_bits((size_t)1 << 28, false) == 15 && lsd::hybrid_bucket_bits((size_t)1 << 27, false) == 14 &&
               lsd::hybrid_bucket_bits((size_t)1 << 27, true) == 15 && lsd::hybrid_bucket_bits((size_t)1 << 26, true) == 14, "bucket rule");
@@ -325,7 +327,6 @@ struct StageEvents {
     hipEvent_t ev[3 * LSDSORT_MAX_PASSES + 4];
     hipEvent_t kernel_ev[2 * LSDSORT_MAX_PASSES];   // begin/end of each pass's rank-and-scatter kernel
     int kernel_count = 0;
-    bool half_tried = false;   // the hybrid form's pass B was launched twice (full, then halves): one more pair of kernel events
     int count = 0;
     hipStream_t stream = nullptr;
     int arm_kernel_events()   // the next rank-and-scatter launch of this thread reports into a fresh pair
@@ -615,22 +616,25 @@ int hybrid_upfront(const SortRequest& rq, const SortPlan& sp)
     if (sp.halves) {
         // the half variant: the same read counts the 2^16 groups (its 16-bit-counter form; a counter that overflows loses keys
         // from the sum, which the planner refuses), two to a word of the sort's own bucket array -- zero since the opening clear --
-        // and the fold gives the planner its 2^15 buckets
+        // and ONE launch folds them into the planner's 2^15 buckets, plans, and decides whether the variant runs (the caller's
+        // buffer still holds the input: the decision takes the key prefix's bits from its first key)
         LSD_HIP(lsd::launch_hybrid_histograms(radix_bits, rq.keys, n, sp.L.region0, sp.fields, sp.bucket, 16, sp.hyb, rq.stream, rq.xf, true));
-        LSD_HIP(lsd::launch_half_fold(sp.bucket, sp.bucket15, sp.first, rq.stream));
+        LSD_HIP(lsd::launch_half_plan(sp.bucket, sp.bucket15, sp.first, n, sp.bases, sp.fields + 2048, sp.hyb, sp.bases + lsd::kHybridBuckets + 1,
+                                      (uint32_t)sp.small_cap, rq.keys, rq.stream));
     } else {
         LSD_HIP(lsd::launch_hybrid_histograms(radix_bits, rq.keys, n, sp.L.region0, radix_bits == 8 ? sp.fields : sp.joint, sp.bucket,
                                               sp.bucket_bits, sp.hyb, rq.stream, rq.xf));
+        LSD_HIP(lsd::launch_hybrid_plan(radix_bits, sp.bucket, n, sp.bucket_bits, sp.bases, radix_bits == 8 ? sp.fields + 2048 : sp.fields, sp.joint,
+                                        sp.hyb, sp.bases + lsd::kHybridBuckets + 1, (uint32_t)sp.small_cap, rq.stream));
     }
-    LSD_HIP(lsd::launch_hybrid_plan(radix_bits, sp.halves ? sp.bucket15 : sp.bucket, n, sp.bucket_bits, sp.bases, radix_bits == 8 ? sp.fields + 2048 : sp.fields,
-                                    sp.joint, sp.hyb, sp.bases + lsd::kHybridBuckets + 1, (uint32_t)sp.small_cap, rq.stream));
     LSD_TRY(inject_count_fault(rq, sp, true));
     // the global passes' region tables: the first one's regions are by position (like any first pass), the others' by the
     // top bits of the digit before -- exactly what stage 2 builds for consecutive passes
     // (no fault word: where the sample or the planner has said no these counts are partial or absent, and nobody uses the tables)
+    // They go into the table slots of the sort's first passes, whose launches serve either form (shared_passes): stage 2 runs
+    // behind this and rewrites every slot where the ordinary form runs, and leaves them alone where the hybrid form does.
     LSD_HIP(lsd::launch_scan_regions(radix_bits, lsd::hybrid_global_passes(radix_bits), sp.L.regions, sp.fields, n, (uint32_t)sp.shape->tile(),
-                                     sp.L.region0, sp.chain.tables + (size_t)sp.passes * sp.chain.table_words, rq.stream, nullptr, nullptr));
-    if (sp.halves) LSD_HIP(lsd::launch_half_decide(rq.keys, sp.hyb, rq.stream));   // the caller's buffer still holds the input
+                                     sp.L.region0, sp.chain.tables, rq.stream, nullptr, nullptr));
     return LSDSORT_OK;
 }
 
@@ -673,28 +677,34 @@ int stage2(const SortRequest& rq, const SortPlan& sp)
     return LSDSORT_OK;
 }
 
-int hybrid_passes(const SortRequest& rq, const SortPlan& sp)
+// The first hybrid_global_passes launches of a sort that tries the hybrid form serve EITHER form: the hybrid form's global passes
+// (bits 16-31 less the key prefix, lowest digit first: caller's buffer -> alternate and back) or the ordinary form's first passes
+// (bits 0-15).  Both roles take the same launch -- table and ticket slot g, status step g, the same arrays -- and what differs is
+// read from device words: the shift from the planner's (kSlotWordShift), the plan pair from stage 2's (scan_regions_kernel writes
+// the hybrid form's pairs there where that form runs, the ordinary plan -- skipped identity passes, swapped roles -- where it
+// does not).  No shared launch is the last of a run: pass g + 1's status array is cleared whichever form runs (where the hybrid
+// form runs the last of them clears an array nobody reads: a row per workgroup).  Then the hybrid form's local stage.
+int shared_passes(const SortRequest& rq, const SortPlan& sp)
 {
-    // the hybrid form's global passes and its local stage (all return at once where the device chose the ordinary form):
-    // bits 16-31, lowest digit first: caller's buffer -> alternate and back (an even number of passes); then the buckets in place
     const int hyb_passes = lsd::hybrid_global_passes(rq.radix_bits);
     for (int g = 0; g < hyb_passes; g++) {
-        // the plan word says which way round (for the keys and every payload array)
-        PassParams p = sort_pass(rq, sp, (uint32_t)(16 + rq.radix_bits * g), sp.passes + g, g, g + 1 == hyb_passes, false);
-        p.shift_word = sp.hyb + lsd::kHybridWordShift + g;   // ... less the key prefix the device found: bits [16 - t, 32 - t)
-        p.plan = sp.hyb + lsd::kHybridWordPlan + 2 * g;
-        if (rq.xf.on && g == 0) p.xin = rq.xf;   // typed sorts: sortable keys from the first store on; the local stage's store turns them back
-        const bool twice = sp.halves && g + 1 == hyb_passes;   // the half variant: pass B in both forms, the device has told one of them 2
-        if (twice) p.plan_first = 1u;
-        LSD_TRY(launch_sort_pass(rq, sp, p));
-        if (twice) {
-            p.plan = sp.hyb + lsd::kHalfWordPlan;
+        PassParams p = sort_pass(rq, sp, (uint32_t)(rq.radix_bits * g), g, g, false, false);
+        p.mute_row = sp.mute_row;
+        p.shift_word = sp.hyb + lsd::kSlotWordShift + g;
+        p.plan = sp.plan + 2 * g;   // plan_first stays 0: both roles work here, neither is to wait for its plan word
+        if (rq.xf.on && g == 0) p.xin = rq.xf;   // typed sorts: sortable keys from the first store on, in either form
+        if (sp.halves && g + 1 == hyb_passes) {
+            // the half variant: this launch is the half-capable instantiation, which stores halves or keys as the device has
+            // decided (words[kHalfWordOk]: 0 wherever the variant does not run, the ordinary form's second pass included)
             p.half_out = sp.halves;
+            p.half_on = sp.hyb + lsd::kHalfWordOk;
             if (rq.ev) LSD_TRY(rq.ev->arm_kernel_events());
             const hipError_t launched = lsd::launch_rank_scatter_half(p, rq.stream);
             StageEvents::disarm_kernel_events();
             LSD_HIP(launched);
+            continue;
         }
+        LSD_TRY(launch_sort_pass(rq, sp, p));
     }
     lsd::LocalSortParams lp{};
     lp.keys = rq.keys;
@@ -731,7 +741,8 @@ int hybrid_passes(const SortRequest& rq, const SortPlan& sp)
 
 int chained_passes(const SortRequest& rq, const SortPlan& sp)
 {
-    for (int pass = 0; pass < sp.passes; pass++) {
+    // (a sort that tried the hybrid form has launched its first passes already: shared_passes)
+    for (int pass = sp.hyb ? lsd::hybrid_global_passes(rq.radix_bits) : 0; pass < sp.passes; pass++) {
         // every array ping-pongs alike: even passes read the caller's, odd passes the alternates -- or, under a plan, the same pair
         // for every pass: the plan says which way round (and whether at all)
         PassParams p = sort_pass(rq, sp, (uint32_t)(pass * rq.radix_bits), pass, pass, pass + 1 == sp.passes, (pass & 1) && !sp.plan);
@@ -809,7 +820,6 @@ int run_sort(const SortRequest& rq)
         rq.timing->hybrid = sp.hyb ? -1 : 0;   // -1: tried; lsdsort_u32_device_timed reads the device's verdict back
     }
     if (sp.small) return small_sort(rq, sp);
-    if (rq.ev) rq.ev->half_tried = sp.halves != nullptr;
     LSD_TRY(mark(rq, StageEvents::kStart));
     LSD_HIP(lsd::launch_clear(rq.ws, sp.L.zero_bytes, rq.stream));   // a kernel, not a memset node: DESIGN.md section 6.18
     LSD_TRY(mark(rq, StageEvents::kCleared));
@@ -820,7 +830,7 @@ int run_sort(const SortRequest& rq)
     LSD_TRY(inject_count_fault(rq, sp, false));
     LSD_TRY(stage2(rq, sp));
     LSD_TRY(mark(rq, StageEvents::kScanned));
-    if (sp.hyb) LSD_TRY(hybrid_passes(rq, sp));
+    if (sp.hyb) LSD_TRY(shared_passes(rq, sp));
     LSD_TRY(chained_passes(rq, sp));
     return finish(rq, sp);
 }
@@ -1283,21 +1293,13 @@ int lsdsort_u32_device_timed(uint32_t* d_keys, uint32_t* d_vals, void* d_workspa
             LSD_HIP(hipEventElapsedTime(&out->histogram_ms, ev.ev[StageEvents::kCleared], ev.ev[StageEvents::kCounted]));
             LSD_HIP(hipEventElapsedTime(&out->scan_ms, ev.ev[StageEvents::kCounted], ev.ev[StageEvents::kScanned]));
             if (algorithm == LSDSORT_ALGO_ONESWEEP) {
-                // per pass: the kernel's own events.  Where the hybrid form was tried its global passes come first (event pairs 0, 1
-                // and at 4-bit digits 2, 3).
-                int first_pair = 0;
-                uint32_t half_ok = 0;   // the hybrid form ran with pass B writing halves: its time is that launch's
+                // per pass: the kernel's own events, one pair per launch in launch order.  Where the hybrid form was tried the first
+                // two launches (four at 4-bit digits) are its global passes or the ordinary form's first ones, as the device chose.
                 if (out->hybrid == -1) {
                     uint32_t ok = 0;
                     LSD_HIP(hipMemcpy(&ok, static_cast<const uint32_t*>(d_workspace) + kHybridOffsetWords + lsd::kHybridWordOk, sizeof(ok),
                                       hipMemcpyDeviceToHost));
                     out->hybrid = ok ? 1 : 0;
-                    // (the half variant launched pass B twice: pairs 0 = A, 1 = B, 2 = B writing halves)
-                    first_pair = ok ? 0 : lsd::hybrid_global_passes(radix_bits) + (ev.half_tried ? 1 : 0);
-                    if (ok && ev.half_tried) {
-                        LSD_HIP(hipMemcpy(&half_ok, static_cast<const uint32_t*>(d_workspace) + kHybridOffsetWords + lsd::kHalfWordOk,
-                                          sizeof(half_ok), hipMemcpyDeviceToHost));
-                    }
                     if (ok) {
                         out->passes = lsd::hybrid_global_passes(radix_bits);
                         if (ev.count > StageEvents::kLocalEnd)
@@ -1305,7 +1307,7 @@ int lsdsort_u32_device_timed(uint32_t* d_keys, uint32_t* d_vals, void* d_workspa
                     }
                 }
                 for (int p = 0; p < out->passes && p < LSDSORT_MAX_PASSES; p++) {
-                    const int pair = p + first_pair + (half_ok && p == 1 ? 1 : 0);
+                    const int pair = p;
                     if (2 * pair + 1 >= ev.kernel_count) break;
                     LSD_HIP(hipEventElapsedTime(&out->scatter_ms[p], ev.kernel_ev[2 * pair], ev.kernel_ev[2 * pair + 1]));
                 }

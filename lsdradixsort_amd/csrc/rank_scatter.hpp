@@ -168,8 +168,9 @@ __device__ __forceinline__ bool row_is_heavy(uint32_t d)
 
 // XF: this launch may carry a key transform (PassParams::xin on a sort's first pass, ::xout on its last);
 // plain uint32 sorts use the XF = false instantiations, which contain none of it.
-// HALF: the hybrid form's pass B writing halves (keys only): the read-back stores (uint16_t)key to p.half_out at the index the key
-// would have gone to; nothing else differs (one instantiation, launch_rank_scatter_half).
+// HALF: the hybrid form's pass B where halves may be written (keys only): if *p.half_on is set the read-back stores (uint16_t)key to
+// p.half_out at the index the key would have gone to, else the key to the output as ever; nothing else differs (one instantiation,
+// launch_rank_scatter_half).
 template <int R, int T, int K, int CAP, int RANK, bool PAIRS, bool CHAINED, bool XF = false, bool HALF = false>
 __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_kernel(const PassParams p)
 {
@@ -233,6 +234,10 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
         plan_skip = p.plan[0];
         plan_swapped = p.plan[1];
     }
+
+    // HALF: halves or keys? -- requested with the plan (a scalar load: nothing has been stored yet), first looked at by the read-back
+    [[maybe_unused]] uint32_t half_on = 0;   // uniform
+    if constexpr (HALF) half_on = *p.half_on;
 
     // wave-private tables start at zero
 #pragma unroll
@@ -819,8 +824,32 @@ __global__ void __launch_bounds__(T, (min_waves_per_simd<T, K>())) rank_scatter_
                     }
                 }
             };
-            if (full) key_slots(std::true_type{});
-            else key_slots(std::false_type{});
+            if constexpr (HALF) {
+                // The device's choice is tested once, outside the slot loops, like `full`.  The key-storing loop is a lambda of
+                // this branch alone: a second parameter on key_slots changed three sibling instantiations (tools/isa_diff.py).
+                if (half_on == 0u) {
+                    auto full_key_slots = [&](auto all_valid) {
+#pragma unroll 1
+                        for (int s0 = 0; s0 < SLOTS; s0 += STEP) {
+#pragma unroll
+                            for (int u = 0; u < STEP; u++) {
+                                const uint32_t slot = (s0 + u) * T + tid;
+                                const uint32_t q = round * CAP + slot;
+                                const uint32_t k = s_keys[slot];
+                                if (decltype(all_valid)::value || q < valid) out_keys[s_gdelta[digit_of(k)] + q] = k;
+                            }
+                        }
+                    };
+                    if (full) full_key_slots(std::true_type{});
+                    else full_key_slots(std::false_type{});
+                } else {
+                    if (full) key_slots(std::true_type{});
+                    else key_slots(std::false_type{});
+                }
+            } else {
+                if (full) key_slots(std::true_type{});
+                else key_slots(std::false_type{});
+            }
         }
 
         // ---- 6. payloads follow their keys through the same slots -----------------------------

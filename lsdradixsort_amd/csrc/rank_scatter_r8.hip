@@ -21,7 +21,7 @@ hipError_t launch_rank_scatter_r8(int shape_id, int rank_method, bool chained, c
 static_assert(kHalfShapeR8 == 4, "the HALF instantiation is shape 4's: 1024 x 32, one LDS round of 32768 keys");
 hipError_t launch_rank_scatter_half(const PassParams& p, hipStream_t stream)
 {
-    if (!p.half_out || p.vals_in || p.xin.on || p.xout.on || !p.plan) return hipErrorInvalidValue;
+    if (!p.half_out || !p.half_on || p.vals_in || p.xin.on || p.xout.on || !p.plan) return hipErrorInvalidValue;
     if (p.num_tiles == 0) return hipSuccess;
     return launch_rank_scatter_inst<8, 1024, 32, 32768, kRankLdsAdd, false, true, false, true>(p, stream);
 }

@@ -54,10 +54,13 @@ __global__ void __launch_bounds__(256) scan_regions_kernel(const uint32_t* __res
     __shared__ uint32_t s_const[kPlanWords];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const int pass = blockIdx.x;
-    if (hybrid_ok && *hybrid_ok != 0u) {   // uniform: the hybrid form runs; these passes leave at once and touch nothing (2)
+    if (hybrid_ok && *hybrid_ok != 0u) {
+        // uniform: the hybrid form runs.  The first launches serve either form: theirs are the hybrid form's pairs -- run; an odd pass
+        // reads what the one before it wrote.  The other passes leave at once and touch nothing (2).
         if (plan && tid == 0) {
-            plan[2 * pass] = 2u;
-            plan[2 * pass + 1] = 0u;
+            const bool shared = pass < hybrid_global_passes(bins == 256 ? 8 : 4);
+            plan[2 * pass] = shared ? 0u : 2u;
+            plan[2 * pass + 1] = shared ? (uint32_t)(pass & 1) : 0u;
             if (pass + 1 == passes) plan[2 * passes] = 0u;   // the local stage leaves the keys in the caller's buffer
         }
         return;
