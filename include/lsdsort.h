@@ -785,6 +785,69 @@ LSDSORT_API int lsdsort_unique_device(const void* d_keys, size_t n, int key_type
                                       void* hip_stream);
 LSDSORT_API int lsdsort_unique_check_device(void* d_workspace, size_t n, int key_type, int with_positions, void* hip_stream);
 
+/* Reduce by key: the sum, minimum or maximum of a 32-bit value array per run and per distinct key, for 32- and 64-bit keys (no reference
+ * counterpart, .cu:62; lsdradixsort_amd/csrc/reduce_by_key.hip) -- thrust::reduce_by_key, segment sums of
+ * gradients per embedding id, the best score per document id; what index_add_ / scatter_reduce_ on unique's inverse map do with
+ * atomics.  Both entries are device-resident and stream-ordered, allocate nothing and never synchronise with the host; EVERY LAUNCH IS
+ * SIZED FROM n ALONE.  GRAPH CAPTURE: both entries launch kernels only (no memset) and clear or rewrite every word of state they read
+ * on every call; either can be captured after lsdsort_prepare_device and replayed any number of times on changed keys and values, in
+ * the same workspace.  No workgroup of the three phases waits for another: they are ordered by kernel boundaries.  Keys are equal
+ * where their BIT PATTERNS are, as in lsdsort_rle_device.
+ *
+ * VALUES AND OPERATIONS.  val_type says how the 32-bit value words are read (lsdsort_val_type), op what is taken over a run
+ * (lsdsort_reduce_op).  SUM of U32 / I32 is arithmetic mod 2^32.  MIN / MAX of U32 / I32 are unsigned / signed.  MIN / MAX of F32 are
+ * taken in the library's float TOTAL ORDER, the map lsdsort_keys_device sorts float32 by: -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf
+ * < +NaN; the result is always the bits of one of the run's values, and equals amin / amax wherever the run holds no NaN.  SUM of F32
+ * is IEEE float32 addition in an order FIXED BY THE POSITIONS ALONE: the same input gives the same bits on every call, eager or
+ * replayed.  A run of one element returns that element's bits, -0.0 and NaN payloads included: no identity element is ever added to a
+ * value.  The order is not the sequential one -- a run is summed as a tree over (16-byte group, wavefront, lane, word) of its tiles of
+ * 4096 keys, tile after tile -- so the result differs from a left-to-right sum by rounding: for a run of L values
+ * |result - exact| <= g * sum|v| with g = (L-1)u / (1 - (L-1)u), u = 2^-24, the bound of every summation order.
+ *
+ * lsdsort_reduce_runs_device: the runs of d_keys AS IT LIES, sorted or not (torch.unique_consecutive plus a segment reduce).  Run j is
+ * a maximal stretch of equal adjacent words of key_bits (32 | 64); d_out_keys[j] is its word, d_out_vals[j] the aggregate of its
+ * values, d_out_counts[j] (may be NULL) its length, *d_num_runs (a DEVICE word) the number of runs.  Words at index >= *d_num_runs of
+ * every output are NOT WRITTEN.  d_keys and d_vals are READ ONLY and need the alignment of their word only (16-byte loads where an
+ * array starts on a 16-byte line).  d_out_keys == d_keys or d_out_vals == d_vals is INVALID_ARG: the inputs are read while the runs
+ * are stored; any other overlap is the caller's error.  Kernels: every tile of 4096 keys counts its run heads and folds its values
+ * from its last head on | one workgroup scans the tile counts and carries the open run's aggregate and head from tile to tile, and
+ * stores the last run's aggregate and length | every tile ranks its heads and folds its values in position order; every head stores
+ * the aggregate and the length of the run before it.  Two reads of keys and values.  The fault word, the first word of the workspace
+ * (lsdsort_check_device), is set where the scanned total or last head is 0 or above n -- never expected; nothing is stored then.
+ *
+ * lsdsort_reduce_by_key_device: the same per DISTINCT key of unsorted input, in the library's order for key_type (all six of
+ * lsdsort_key_type: ascending, or the largest first with descending != 0); *d_num_groups (a DEVICE word) their number.  The entry
+ * copies keys and values into the workspace -- after that copy the inputs are no longer read, so d_out_keys MAY BE d_keys and
+ * d_out_vals MAY BE d_vals -- sorts the copies with lsdsort_keys_device / lsdsort_keys64_device (8-bit digits, the value bits as the
+ * 32-bit payload) inside a sub-range of its workspace, and runs the three phases over the sorted copies.  The sort is stable, so the
+ * values of a group meet the reduction IN INPUT ORDER.  Workspace: control block (fault word first) | key copy | value copy | the
+ * sort's workspace | per-tile head counts | per-tile open-run heads | per-tile open-run aggregates, each 256-byte aligned.
+ * lsdsort_reduce_by_key_check_device synchronises the stream and answers LSDSORT_ERR_DEVICE_FAULT where the unit's own word is set or
+ * the check of the sort inside (lsdsort_check_device / lsdsort_wide_check_device on its sub-range) reports one.
+ *
+ * Checks of both entries, in order, each before a device is touched: key_bits / key_type, val_type, op (INVALID_ARG), n above
+ * LSDSORT_MAX_KEYS (TOO_LARGE), n == 0 (OK: *d_num_* receives 0 by one stream-ordered 4-byte store where the pointer is given, and
+ * nothing else happens), a NULL d_keys, d_vals, d_out_keys, d_out_vals or d_num_*, an array not aligned to its word (INVALID_ARG), the
+ * forbidden aliases of the runs entry (INVALID_ARG), the workspace (WORKSPACE: NULL, not 256-byte aligned, or below the figure), the
+ * device (NO_DEVICE).  The workspace functions return a multiple of 256, are monotonic in n and return 0 above the limit or for a bad
+ * key_bits / key_type. */
+typedef enum lsdsort_reduce_op { LSDSORT_REDUCE_SUM = 0, LSDSORT_REDUCE_MIN = 1, LSDSORT_REDUCE_MAX = 2 } lsdsort_reduce_op;
+typedef enum lsdsort_val_type { LSDSORT_VAL_U32 = 0, LSDSORT_VAL_I32 = 1, LSDSORT_VAL_F32 = 2 } lsdsort_val_type;
+LSDSORT_API size_t lsdsort_reduce_runs_workspace_bytes(size_t n, int key_bits);
+LSDSORT_API int lsdsort_reduce_runs_device(const void* d_keys, const void* d_vals /* [n], 32-bit */, size_t n, int key_bits /* 32 | 64 */,
+                                           int val_type /* lsdsort_val_type */, int op /* lsdsort_reduce_op */,
+                                           void* d_out_keys /* [n] words of key_bits */, void* d_out_vals /* [n], 32-bit */,
+                                           uint32_t* d_out_counts /* [n] or NULL */, uint32_t* d_num_runs /* DEVICE, one word */,
+                                           void* d_workspace, size_t workspace_bytes, void* hip_stream);
+LSDSORT_API size_t lsdsort_reduce_by_key_workspace_bytes(size_t n, int key_type);
+LSDSORT_API int lsdsort_reduce_by_key_device(const void* d_keys, const void* d_vals /* [n], 32-bit */, size_t n,
+                                             int key_type /* lsdsort_key_type, all six */, int descending, int val_type, int op,
+                                             void* d_out_keys /* [n], caller's type; may be d_keys itself */,
+                                             void* d_out_vals /* [n], 32-bit; may be d_vals itself */,
+                                             uint32_t* d_out_counts /* [n] or NULL */, uint32_t* d_num_groups /* DEVICE, one word */,
+                                             void* d_workspace, size_t workspace_bytes, void* hip_stream);
+LSDSORT_API int lsdsort_reduce_by_key_check_device(void* d_workspace, size_t n, int key_type, void* hip_stream);
+
 /* After the stream has drained: LSDSORT_OK, or LSDSORT_ERR_DEVICE_FAULT if a kernel of the
  * last sort on this workspace gave up a bounded spin or refused destinations outside the output
  * (never expected; the output is then undefined).  Synchronises hip_stream.  With LSDSORT_REPROBE=1

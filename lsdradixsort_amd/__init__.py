@@ -23,6 +23,7 @@ from .api import (  # noqa: F401  (api.__all__, name for name)
     GPUSample16, sample16_workspace_bytes, sample16_rows,
     GPULogprob16, logprob16_workspace_bytes, logprobs16_rows, top_logprobs16_rows,
     GPURunLength, GPUUnique, rle_workspace_bytes, unique_workspace_bytes, unique, unique_consecutive,
+    GPUReduceRuns, GPUReduceByKey, reduce_runs_workspace_bytes, reduce_by_key_workspace_bytes, reduce_by_key, reduce_consecutive,
     BuildHistograms, BuildOffsets, RankScatter, DigitHistograms,
     MSBPartition, SplitterPartition, ThresholdPartition, sharded_thresholds,
 )

@@ -134,6 +134,13 @@ SIGNATURES = {
     "lsdsort_unique_device": (c_int, [ctypes.c_void_p, c_size, c_int, c_int, ctypes.c_void_p, c_u32p, c_u32p, c_u32p, c_u32p,
                                       ctypes.c_void_p, c_size, ctypes.c_void_p]),
     "lsdsort_unique_check_device": (c_int, [ctypes.c_void_p, c_size, c_int, c_int, ctypes.c_void_p]),
+    "lsdsort_reduce_runs_workspace_bytes": (c_size, [c_size, c_int]),
+    "lsdsort_reduce_runs_device": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_size, c_int, c_int, c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                           c_u32p, c_u32p, ctypes.c_void_p, c_size, ctypes.c_void_p]),
+    "lsdsort_reduce_by_key_workspace_bytes": (c_size, [c_size, c_int]),
+    "lsdsort_reduce_by_key_device": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_size, c_int, c_int, c_int, c_int, ctypes.c_void_p,
+                                             ctypes.c_void_p, c_u32p, c_u32p, ctypes.c_void_p, c_size, ctypes.c_void_p]),
+    "lsdsort_reduce_by_key_check_device": (c_int, [ctypes.c_void_p, c_size, c_int, ctypes.c_void_p]),
     "lsdsort_u32_device_timed": (c_int, [c_u32p, c_u32p, ctypes.c_void_p, c_size, c_size, c_int, c_int,
                                          ctypes.c_void_p, ctypes.POINTER(LsdsortTiming)]),
     "lsdsort_tile_keys": (c_size, [c_int]),

@@ -33,6 +33,7 @@ __all__ = [
     "GPUSample16", "sample16_workspace_bytes", "sample16_rows",
     "GPULogprob16", "logprob16_workspace_bytes", "logprobs16_rows", "top_logprobs16_rows",
     "GPURunLength", "GPUUnique", "rle_workspace_bytes", "unique_workspace_bytes", "unique", "unique_consecutive",
+    "GPUReduceRuns", "GPUReduceByKey", "reduce_runs_workspace_bytes", "reduce_by_key_workspace_bytes", "reduce_by_key", "reduce_consecutive",
     "BuildHistograms", "BuildOffsets", "RankScatter", "DigitHistograms",
     "MSBPartition", "SplitterPartition", "ThresholdPartition", "sharded_thresholds",
 ]
@@ -1676,6 +1677,159 @@ def unique_consecutive(x, return_counts: bool = False):
     if return_counts:
         return got[0][:m], got[1][:m].to(torch.int64)
     return got[0][:m]
+
+
+# ------------------------------------------------------------------------------ reduce by key
+def reduce_runs_workspace_bytes(n: int, key_bits: int = 32) -> int:
+    """Bytes of device workspace ``GPUReduceRuns`` needs for up to ``n`` keys of ``key_bits`` (32 | 64), whatever the values, the
+    operation and the outputs; 0 above the limit or for another width."""
+    return int(lib().lsdsort_reduce_runs_workspace_bytes(n, key_bits))
+
+
+def reduce_by_key_workspace_bytes(n: int, key_type: str = "int32") -> int:
+    """Bytes of device workspace ``GPUReduceByKey`` needs for up to ``n`` keys of ``key_type`` (any of the six 32- and 64-bit names);
+    0 above the limit."""
+    return int(lib().lsdsort_reduce_by_key_workspace_bytes(n, _key_type(key_type, {**KEY_TYPES_32, **KEY_TYPES_64})))
+
+
+def _reduce_values(d_vals, n: int, op: str):
+    """The value check of the reduce wrappers: a contiguous 1-D int32 / float32 CUDA tensor (uint32 where torch has it) as long as
+    the keys, and one of the three operations.  Returns the header's codes ``(val_type, op)``; the value type follows the dtype."""
+    torch = _torch()
+    own = {torch.int32: "int32", torch.float32: "float32"}
+    if hasattr(torch, "uint32"):
+        own[torch.uint32] = "uint32"
+    _dev(d_vals, "d_vals", tuple(own), dims=(1,))
+    if d_vals.numel() != n:
+        raise ValueError("keys and values differ in length")
+    if op not in errors.REDUCE_OPS:
+        raise ValueError("op: " + " or ".join(f'"{name}"' for name in errors.REDUCE_OPS) + f", got {op!r}")
+    return errors.VAL_TYPES[own[d_vals.dtype]], errors.REDUCE_OPS[op]
+
+
+def _out_values(out_vals, d_vals, may_alias: bool):
+    """``out_vals`` of the two wrappers: a contiguous CUDA tensor of the values' dtype and length."""
+    if out_vals is None:
+        return None
+    _dev(out_vals, "out_vals", (d_vals.dtype,), dims=(1,))
+    if out_vals.numel() != d_vals.numel():
+        raise ValueError(f"out_vals: as long as the values ({d_vals.numel()}), got {out_vals.numel()}")
+    if not may_alias and out_vals.numel() and out_vals.data_ptr() == d_vals.data_ptr():
+        raise ValueError("out_vals: the values themselves cannot take the aggregates (they are read while the runs are stored)")
+    return out_vals
+
+
+def GPUReduceRuns(d_keys, d_vals, op: str = "sum", counts=False, out_keys=None, out_vals=None, workspace=None, stream=None,
+                  check_fault: bool = False):
+    """``op`` ("sum" | "min" | "max") of ``d_vals`` over every run of equal adjacent keys of ``d_keys`` as it lies, sorted or not
+    (``lsdsort_reduce_runs_device``): ``torch.unique_consecutive`` plus a segment reduce, on the device and without atomics.
+    ``d_keys``: as for ``GPURunLength`` (keys are equal where their BITS are); ``d_vals``: a contiguous 1-D int32 / float32 CUDA
+    tensor (uint32 where torch has it) of the same length, whose dtype says how the values are read.  Integer sums wrap; float min /
+    max follow the library's total order (-NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN) and return the bits of one of the run's
+    values; float sums are IEEE additions in an order fixed by the positions, the same bits on every call, and a run of one element
+    keeps its bits.  Returns ``(keys, aggregates[, counts], num_runs)``: FULL-LENGTH tensors whose first ``num_runs`` entries are
+    written, and the one-word int32 count -- no host synchronisation.  ``counts``: ``True``, or a contiguous int32 CUDA tensor of the
+    keys' length to fill; ``out_keys`` / ``out_vals``: where keys and aggregates go (not the inputs themselves)."""
+    torch = _torch()
+    _word_keys(d_keys, "d_keys")
+    n = d_keys.numel()
+    bits = 8 * d_keys.element_size()
+    val_type, code = _reduce_values(d_vals, n, op)
+    _out_keys(out_keys, d_keys, may_alias=False)
+    _out_values(out_vals, d_vals, may_alias=False)
+    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
+        keys = out_keys if out_keys is not None else torch.empty_like(d_keys)
+        vals = out_vals if out_vals is not None else torch.empty_like(d_vals)
+        lengths = _optional_out(counts, "counts", torch.int32, (n,), d_keys.device)
+        num = torch.empty(1, dtype=torch.int32, device=d_keys.device)
+    if workspace is None:
+        nbytes = reduce_runs_workspace_bytes(n, bits)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_reduce_runs_workspace_bytes", "too many keys")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    check(lib().lsdsort_reduce_runs_device(d_keys.data_ptr() if n else None, d_vals.data_ptr() if n else None, n, bits, val_type, code,
+                                           keys.data_ptr() if n else None, vals.data_ptr() if n else None,
+                                           lengths.data_ptr() if lengths is not None and n else None, num.data_ptr(),
+                                           workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_reduce_runs_device")
+    if check_fault and n:
+        _check_fault(workspace, stream)
+    return (keys, vals) + ((lengths,) if lengths is not None else ()) + (num,)
+
+
+def GPUReduceByKey(d_keys, d_vals, op: str = "sum", key_type=None, descending: bool = False, counts=False, out_keys=None, out_vals=None,
+                   workspace=None, stream=None, check_fault: bool = False):
+    """``op`` of ``d_vals`` per DISTINCT key of the unsorted ``d_keys``, the keys in sorted order (``lsdsort_reduce_by_key_device``):
+    the library's stable pair sort on copies inside the workspace, then the kernels of ``GPUReduceRuns`` -- what
+    ``index_add_`` / ``scatter_reduce_`` on ``unique``'s inverse map do with atomics, here in a fixed order: the values of a group
+    meet in input order and the same input gives the same bits on every call.  ``key_type`` and ``descending``: as for ``GPUUnique``;
+    values, operations and their float rules (-0.0, NaN, the total order of min / max): as for ``GPUReduceRuns``.  Returns
+    ``(keys, aggregates[, counts], num_groups)``: full-length tensors and the one-word int32 count, no host synchronisation.
+    ``out_keys`` / ``out_vals`` may be ``d_keys`` / ``d_vals`` themselves."""
+    torch = _torch()
+    key_type = _word_keys(d_keys, "d_keys", key_type)
+    key_code = _key_type(key_type, {**KEY_TYPES_32, **KEY_TYPES_64})
+    n = d_keys.numel()
+    val_type, code = _reduce_values(d_vals, n, op)
+    _out_keys(out_keys, d_keys, may_alias=True)
+    _out_values(out_vals, d_vals, may_alias=True)
+    with _on_stream(stream):
+        keys = out_keys if out_keys is not None else torch.empty_like(d_keys)
+        vals = out_vals if out_vals is not None else torch.empty_like(d_vals)
+        lengths = _optional_out(counts, "counts", torch.int32, (n,), d_keys.device)
+        num = torch.empty(1, dtype=torch.int32, device=d_keys.device)
+    if workspace is None:
+        nbytes = reduce_by_key_workspace_bytes(n, key_type)
+        if nbytes == 0:
+            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_reduce_by_key_workspace_bytes", "too many keys")
+        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    check(lib().lsdsort_reduce_by_key_device(d_keys.data_ptr() if n else None, d_vals.data_ptr() if n else None, n, key_code,
+                                             int(bool(descending)), val_type, code, keys.data_ptr() if n else None,
+                                             vals.data_ptr() if n else None, lengths.data_ptr() if lengths is not None and n else None,
+                                             num.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(stream)),
+          "lsdsort_reduce_by_key_device")
+    if check_fault and n:
+        _check_fault(workspace, stream, "lsdsort_reduce_by_key_check_device", n, key_code)
+    return (keys, vals) + ((lengths,) if lengths is not None else ()) + (num,)
+
+
+def _contiguous_values(values, n: int, op: str):
+    """The values of the two slicing wrappers: a strided 1-D CUDA tensor is copied, everything else goes to the shared check as it is."""
+    torch = _torch()
+    if isinstance(values, torch.Tensor) and values.is_cuda and values.dim() == 1 and not values.is_contiguous():
+        values = values.contiguous()
+    _reduce_values(values, n, op)
+    return values
+
+
+def reduce_by_key(keys, values, op: str = "sum", descending: bool = False, return_counts: bool = False):
+    """``(distinct keys, op of the values that carry each[, counts])`` for 1-D CUDA tensors of equal length: ``keys`` of the types
+    ``unique`` takes, ``values`` int32 / float32 (uint32 where torch has it), reinterpreted, never converted; ``op``: "sum", "min" or
+    "max".  Equals ``torch.unique(return_inverse=True)`` followed by ``index_add_`` / ``scatter_reduce_(include_self=False)`` on
+    integers and on NaN-free floats whose sums are exact; float sums are deterministic (``GPUReduceByKey``) and differ from a
+    sequential sum by rounding.  -0.0 and +0.0 are two keys, every NaN payload is one.  Reads the count once (one synchronisation)
+    and slices; ``return_counts`` adds the int64 group sizes."""
+    torch = _torch()
+    _word_keys(keys, "keys", contiguous=False)
+    n = keys.numel()
+    got = GPUReduceByKey(keys.contiguous(), _contiguous_values(values, n, op), op=op, descending=descending, counts=bool(return_counts))
+    m = int(got[-1].item())
+    if return_counts:
+        return got[0][:m], got[1][:m], got[2][:m].to(torch.int64)
+    return got[0][:m], got[1][:m]
+
+
+def reduce_consecutive(keys, values, op: str = "sum", return_counts: bool = False):
+    """``(the first key of every run of equal adjacent keys, op of the run's values[, counts])``: ``torch.unique_consecutive`` plus a
+    segment reduce, for the tensors ``reduce_by_key`` takes.  One synchronisation (the count).  Keys are equal where their bits are:
+    -0.0 and +0.0 end a run, NaN payloads that agree do not."""
+    torch = _torch()
+    _word_keys(keys, "keys", contiguous=False)
+    n = keys.numel()
+    got = GPUReduceRuns(keys.contiguous(), _contiguous_values(values, n, op), op=op, counts=bool(return_counts))
+    m = int(got[-1].item())
+    if return_counts:
+        return got[0][:m], got[1][:m], got[2][:m].to(torch.int64)
+    return got[0][:m], got[1][:m]
 
 
 def GPULSDRadixSortTimed(d_keys, r: int = 8, d_vals=None, algorithm: int = LSDSORT_ALGO_ONESWEEP, workspace=None,

@@ -30,6 +30,12 @@ KEY_TYPES_64 = {"uint64": LSDSORT_KEY_U64, "int64": LSDSORT_KEY_I64, "float64": 
 LSDSORT_KEY16_U16, LSDSORT_KEY16_I16, LSDSORT_KEY16_F16, LSDSORT_KEY16_BF16 = 0, 1, 2, 3
 KEY_TYPES_16 = {"uint16": LSDSORT_KEY16_U16, "int16": LSDSORT_KEY16_I16, "float16": LSDSORT_KEY16_F16, "bfloat16": LSDSORT_KEY16_BF16}
 
+# lsdsort_reduce_op and lsdsort_val_type (lsdsort_reduce_runs_device, lsdsort_reduce_by_key_device)
+LSDSORT_REDUCE_SUM, LSDSORT_REDUCE_MIN, LSDSORT_REDUCE_MAX = 0, 1, 2
+REDUCE_OPS = {"sum": LSDSORT_REDUCE_SUM, "min": LSDSORT_REDUCE_MIN, "max": LSDSORT_REDUCE_MAX}
+LSDSORT_VAL_U32, LSDSORT_VAL_I32, LSDSORT_VAL_F32 = 0, 1, 2
+VAL_TYPES = {"uint32": LSDSORT_VAL_U32, "int32": LSDSORT_VAL_I32, "float32": LSDSORT_VAL_F32}
+
 LSDSORT_PARTITION_MSB = 0
 LSDSORT_PARTITION_SPLITTERS = 1
 PARTITIONS = {"msb": LSDSORT_PARTITION_MSB, "splitters": LSDSORT_PARTITION_SPLITTERS}
