@@ -23,25 +23,18 @@
 //
 // Stream-ordered, nothing allocated, never synchronises, every launch sized from n alone; for graph capture see include/lsdsort.h.
 // Keys and values need the alignment of their word only: 16-byte loads are used where an array starts on a 16-byte line, single
-// words otherwise and in the last, partial group.  The loaders restate unique.hip's: that unit is pinned byte
-// for byte by its tests.
+// words otherwise and in the last, partial group.  The tile, its loaders and head flags, the workspace carve-up and the sort of the
+// copies are run_tiles.hpp's, shared with unique.hip.
 #define LSDSORT_BUILD 1
 #include "../../include/lsdsort.h"
 
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
+#include "run_tiles.hpp"
 
 namespace {
 
-constexpr int kRbkThreads = 256;
-constexpr int kRbkWaves = kRbkThreads / lsd::kWave;
-constexpr uint32_t kRbkThreadKeys = 16;
-constexpr uint32_t kRbkTile = kRbkThreads * kRbkThreadKeys;   // keys of a workgroup: 4096
-constexpr int kRbkScanThreads = 1024;
-constexpr int kRbkScanWaves = kRbkScanThreads / lsd::kWave;
-constexpr uint32_t kRbkScanRound = 4 * kRbkScanThreads;       // tiles the scan takes per round: 4096
-constexpr uint32_t kRbkMaxGrid = 2048;                        // workgroups of the grid-stride copy kernel
-constexpr uint32_t kRbkFault = 1u;                            // the scanned total or the last head is 0 or above n: never expected
+using namespace lsd;   // run_tiles.hpp: the tile constants, Groups, the loaders, the head flags, the host plumbing
 
 // ---- values and their three operations ----------------------------------------------------------------------------------------
 // to_domain(x) = x ^ ((sign(x) ? a : 0) | b) ^ c, where the operation runs; from_domain is its inverse.  Sums: a = b = c = 0.
@@ -112,86 +105,6 @@ __device__ __forceinline__ Part part_below(Part x, uint32_t lane)
     return up;
 }
 
-// ---- a tile in registers --------------------------------------------------------------------------------------------------------
-// A thread holds its 16 keys as J groups of G words, one 16-byte load each; group j of thread t is the G keys from
-// tile * kRbkTile + (j * 256 + t) * G, so that the lanes of a wave read consecutive 16-byte lines.  A tile's keys in position order
-// are indexed (group, wave, lane, word).
-template <class Word>
-struct Groups {
-    static constexpr uint32_t G = 16 / sizeof(Word);        // 4 | 2
-    static constexpr uint32_t J = kRbkThreadKeys / G;       // 4 | 8
-};
-
-template <class Word>
-__device__ __forceinline__ uint32_t group_start(uint32_t tile, uint32_t j, uint32_t tid)
-{
-    return tile * kRbkTile + (j * kRbkThreads + tid) * Groups<Word>::G;   // below 2^30 + 4096
-}
-
-// The G words from i0 (a multiple of G); words at or behind n read as 0.  vec: the array starts on a 16-byte line.
-template <class Word>
-__device__ __forceinline__ void load_group(const Word* __restrict__ keys, uint32_t i0, uint32_t n, bool vec, Word (&k)[Groups<Word>::G])
-{
-    constexpr uint32_t G = Groups<Word>::G;
-    if (vec && i0 + G <= n) {
-        const uint4 v = *reinterpret_cast<const uint4*>(keys + i0);
-        if constexpr (sizeof(Word) == 4) {
-            k[0] = v.x; k[1] = v.y; k[2] = v.z; k[3] = v.w;
-        } else {
-            k[0] = (Word)v.x | (Word)v.y << 32;
-            k[1] = (Word)v.z | (Word)v.w << 32;
-        }
-    } else {
-#pragma unroll
-        for (uint32_t e = 0; e < G; e++) k[e] = i0 + e < n ? keys[i0 + e] : (Word)0;
-    }
-}
-
-// The values beside the keys: the same groups of a uint32 array.  vec: it starts on a 16-byte line.
-template <class Word>
-__device__ __forceinline__ void load_values(const uint32_t* __restrict__ vals, uint32_t i0, uint32_t n, bool vec, uint32_t (&v)[Groups<Word>::G])
-{
-    constexpr uint32_t G = Groups<Word>::G;
-    if (vec && i0 + G <= n) {
-        if constexpr (G == 4) {
-            const uint4 q = *reinterpret_cast<const uint4*>(vals + i0);
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-        } else {
-            const uint2 q = *reinterpret_cast<const uint2*>(vals + i0);
-            v[0] = q.x; v[1] = q.y;
-        }
-    } else {
-#pragma unroll
-        for (uint32_t e = 0; e < G; e++) v[e] = i0 + e < n ? vals[i0 + e] : 0u;
-    }
-}
-
-// This thread's keys of `tile` and their head flags: bit j * G + e is set where key (j, e) lies below n and is position 0 or
-// differs from the key in front of it.  That key is the one before it in the group, for a group's first key the last key of the
-// lane below, and for lane 0 one more global load.  All 64 lanes of every wave must be active.
-template <class Word>
-__device__ __forceinline__ uint32_t tile_keys_and_heads(const Word* __restrict__ keys, uint32_t n, bool vec, uint32_t tile, uint32_t tid,
-                                                        uint32_t lane, Word (&k)[Groups<Word>::J][Groups<Word>::G])
-{
-    constexpr uint32_t G = Groups<Word>::G, J = Groups<Word>::J;
-#pragma unroll
-    for (uint32_t j = 0; j < J; j++) load_group<Word>(keys, group_start<Word>(tile, j, tid), n, vec, k[j]);
-    uint32_t flags = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < J; j++) {
-        const uint32_t i0 = group_start<Word>(tile, j, tid);
-        Word before = __shfl_up(k[j][G - 1], 1u, lsd::kWave);
-        if (lane == 0 && i0 > 0 && i0 < n) before = keys[i0 - 1];
-#pragma unroll
-        for (uint32_t e = 0; e < G; e++) {
-            const uint32_t i = i0 + e;
-            const bool head = i < n && (i == 0 || k[j][e] != (e ? k[j][e - 1] : before));
-            flags |= (head ? 1u : 0u) << (j * G + e);
-        }
-    }
-    return flags;
-}
-
 // This thread's values of `tile`, in the domain of the operation.
 template <class Word>
 __device__ __forceinline__ void tile_values(const uint32_t* __restrict__ vals, uint32_t n, bool vec, uint32_t tile, uint32_t tid, ValueMap map,
@@ -200,7 +113,7 @@ __device__ __forceinline__ void tile_values(const uint32_t* __restrict__ vals, u
     constexpr uint32_t G = Groups<Word>::G, J = Groups<Word>::J;
 #pragma unroll
     for (uint32_t j = 0; j < J; j++) {
-        load_values<Word>(vals, group_start<Word>(tile, j, tid), n, vec, v[j]);
+        load_words32<Word>(vals, group_start<Word>(tile, j, tid), n, vec, v[j]);
 #pragma unroll
         for (uint32_t e = 0; e < G; e++) v[j][e] = to_domain(v[j][e], map);
     }
@@ -230,15 +143,15 @@ __device__ __forceinline__ Part group_part(uint32_t i0, uint32_t n, uint32_t fla
 // last head (0: none) and the aggregate of its values from that head on -- three plain stores per workgroup, every tile word on
 // every call.  The first workgroup clears the unit's fault word, which the scan (behind this kernel's end) may set.
 template <class Word, class Op>
-__global__ void __launch_bounds__(kRbkThreads) rbk_count_kernel(const Word* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t n,
+__global__ void __launch_bounds__(kRunThreads) rbk_count_kernel(const Word* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t n,
                                                                uint32_t vec, uint32_t vec_vals, ValueMap map, uint32_t* __restrict__ tile_heads,
                                                                uint32_t* __restrict__ tile_state, uint32_t* __restrict__ tile_value,
                                                                uint32_t* __restrict__ fault)
 {
     constexpr uint32_t G = Groups<Word>::G, J = Groups<Word>::J;
-    __shared__ uint32_t part_heads[kRbkWaves];
-    __shared__ uint32_t part_s[J * kRbkWaves];
-    __shared__ uint32_t part_v[J * kRbkWaves];
+    __shared__ uint32_t part_heads[kRunWaves];
+    __shared__ uint32_t part_s[J * kRunWaves];
+    __shared__ uint32_t part_v[J * kRunWaves];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, tile = blockIdx.x;
     Word k[J][G];
     const uint32_t flags = tile_keys_and_heads<Word>(keys, n, vec != 0, tile, tid, lane, k);
@@ -246,11 +159,11 @@ __global__ void __launch_bounds__(kRbkThreads) rbk_count_kernel(const Word* __re
     tile_values<Word>(vals, n, vec_vals != 0, tile, tid, map, v);
 #pragma unroll
     for (uint32_t j = 0; j < J; j++) {
-        const Part mine = group_part<Word, Op>(group_start<Word>(tile, j, tid), n, (flags >> (j * G)) & ((1u << G) - 1u), v[j]);
+        const Part mine = group_part<Word, Op>(group_start<Word>(tile, j, tid), n, group_flags<Word>(flags, j), v[j]);
         const Part upto = wave_join_scan<Op>(mine, lane);
         if (lane == 63u) {
-            part_s[j * kRbkWaves + wave] = upto.s;
-            part_v[j * kRbkWaves + wave] = upto.v;
+            part_s[j * kRunWaves + wave] = upto.s;
+            part_v[j * kRunWaves + wave] = upto.v;
         }
     }
     const uint32_t heads = lsd::wave_sum((uint32_t)__builtin_popcount(flags));
@@ -259,10 +172,10 @@ __global__ void __launch_bounds__(kRbkThreads) rbk_count_kernel(const Word* __re
     if (tid == 0) {
         uint32_t all = 0;
 #pragma unroll
-        for (int w = 0; w < kRbkWaves; w++) all += part_heads[w];
+        for (int w = 0; w < kRunWaves; w++) all += part_heads[w];
         Part whole{0u, 0u};   // groups follow each other in the tile as (j, wave)
 #pragma unroll
-        for (uint32_t x = 0; x < J * (uint32_t)kRbkWaves; x++) whole = join<Op>(whole, Part{part_s[x], part_v[x]});
+        for (uint32_t x = 0; x < J * (uint32_t)kRunWaves; x++) whole = join<Op>(whole, Part{part_s[x], part_v[x]});
         tile_heads[tile] = all;
         tile_state[tile] = whole.s;
         tile_value[tile] = whole.v;
@@ -278,21 +191,21 @@ __global__ void __launch_bounds__(kRbkThreads) rbk_count_kernel(const Word* __re
 // written whole; its words behind `tiles` count as nothing.  All tiles as one part are the last run: its aggregate and its length
 // -- from the last head of all to n -- are stored here; every other run's are stored by the head BEHIND it (emit).
 template <class Op>
-__global__ void __launch_bounds__(kRbkScanThreads) rbk_scan_kernel(uint32_t* __restrict__ tile_heads, uint32_t* __restrict__ tile_state,
+__global__ void __launch_bounds__(kRunScanThreads) rbk_scan_kernel(uint32_t* __restrict__ tile_heads, uint32_t* __restrict__ tile_state,
                                                                   uint32_t* __restrict__ tile_value, uint32_t tiles, uint32_t n, ValueMap map,
                                                                   uint32_t* __restrict__ num_runs, uint32_t* __restrict__ out_vals,
                                                                   uint32_t* __restrict__ counts, uint32_t* __restrict__ fault)
 {
-    __shared__ uint32_t part[kRbkScanWaves];
-    __shared__ uint32_t part_s[kRbkScanWaves];
-    __shared__ uint32_t part_v[kRbkScanWaves];
+    __shared__ uint32_t part[kRunScanWaves];
+    __shared__ uint32_t part_s[kRunScanWaves];
+    __shared__ uint32_t part_v[kRunScanWaves];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     uint4* heads4 = reinterpret_cast<uint4*>(tile_heads);
     uint4* state4 = reinterpret_cast<uint4*>(tile_state);
     uint4* value4 = reinterpret_cast<uint4*>(tile_value);
     uint32_t carry = 0;
     Part carried{0u, 0u};
-    for (uint32_t first = 0; first < tiles; first += kRbkScanRound) {
+    for (uint32_t first = 0; first < tiles; first += kRunScanRound) {
         const uint32_t t = first + 4 * tid;
         uint4 h = make_uint4(0, 0, 0, 0), s = make_uint4(0, 0, 0, 0), v = make_uint4(0, 0, 0, 0);
         if (t < tiles) {
@@ -312,10 +225,10 @@ __global__ void __launch_bounds__(kRbkScanThreads) rbk_scan_kernel(uint32_t* __r
             part_v[wave] = upto.v;
         }
         uint32_t all = 0;
-        const uint32_t excl = carry + lsd::group_exclusive_scan<kRbkScanWaves>(h.x + h.y + h.z + h.w, lane, wave, part, &all);   // a barrier inside
+        const uint32_t excl = carry + lsd::group_exclusive_scan<kRunScanWaves>(h.x + h.y + h.z + h.w, lane, wave, part, &all);   // a barrier inside
         Part running = carried, front = carried;   // the waves of this round in order, behind what the rounds before left
 #pragma unroll
-        for (uint32_t w = 0; w < (uint32_t)kRbkScanWaves; w++) {
+        for (uint32_t w = 0; w < (uint32_t)kRunScanWaves; w++) {
             if (w == wave) front = running;
             running = join<Op>(running, Part{part_s[w], part_v[w]});
         }
@@ -333,7 +246,7 @@ __global__ void __launch_bounds__(kRbkScanThreads) rbk_scan_kernel(uint32_t* __r
         *num_runs = carry;
         const uint32_t last = carried.s >> 1;   // 1 + the position of the last head of all
         if (carry == 0 || carry > n || !(carried.s & 1u) || last == 0 || last > n) {
-            atomicOr(fault, kRbkFault);
+            atomicOr(fault, kRunFault);
         } else {
             out_vals[carry - 1] = from_domain(carried.v, map);
             if (counts) counts[carry - 1] = n - (last - 1u);
@@ -351,7 +264,7 @@ __global__ void __launch_bounds__(kRbkScanThreads) rbk_scan_kernel(uint32_t* __r
 // tiles it began in -- and counts[r - 1] = i - (its last head).  counts may be null.  Every store is guarded by its rank and by
 // i < n; nothing is stored where the scan set the fault word.
 template <class Word, class Op>
-__global__ void __launch_bounds__(kRbkThreads) rbk_emit_kernel(const Word* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t n,
+__global__ void __launch_bounds__(kRunThreads) rbk_emit_kernel(const Word* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t n,
                                                               uint32_t vec, uint32_t vec_vals, ValueMap map,
                                                               const uint32_t* __restrict__ tile_heads, const uint32_t* __restrict__ tile_state,
                                                               const uint32_t* __restrict__ tile_value, const uint32_t* __restrict__ fault,
@@ -359,9 +272,9 @@ __global__ void __launch_bounds__(kRbkThreads) rbk_emit_kernel(const Word* __res
                                                               uint32_t* __restrict__ counts)
 {
     constexpr uint32_t G = Groups<Word>::G, J = Groups<Word>::J;
-    __shared__ uint32_t part[J * kRbkWaves];
-    __shared__ uint32_t part_s[J * kRbkWaves];
-    __shared__ uint32_t part_v[J * kRbkWaves];
+    __shared__ uint32_t part[J * kRunWaves];
+    __shared__ uint32_t part_s[J * kRunWaves];
+    __shared__ uint32_t part_v[J * kRunWaves];
     if (*fault != 0u) return;   // uniform
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, tile = blockIdx.x;
     Word k[J][G];
@@ -372,15 +285,15 @@ __global__ void __launch_bounds__(kRbkThreads) rbk_emit_kernel(const Word* __res
     Part below[J];   // the lanes below this one in group j, as one part
 #pragma unroll
     for (uint32_t j = 0; j < J; j++) {
-        count[j] = (uint32_t)__builtin_popcount((flags >> (j * G)) & ((1u << G) - 1u));
+        count[j] = (uint32_t)__builtin_popcount(group_flags<Word>(flags, j));
         incl[j] = lsd::wave_inclusive_scan(count[j]);
-        const Part mine = group_part<Word, Op>(group_start<Word>(tile, j, tid), n, (flags >> (j * G)) & ((1u << G) - 1u), v[j]);
+        const Part mine = group_part<Word, Op>(group_start<Word>(tile, j, tid), n, group_flags<Word>(flags, j), v[j]);
         const Part upto = wave_join_scan<Op>(mine, lane);
         below[j] = part_below(upto, lane);
         if (lane == 63u) {
-            part[j * kRbkWaves + wave] = incl[j];
-            part_s[j * kRbkWaves + wave] = upto.s;
-            part_v[j * kRbkWaves + wave] = upto.v;
+            part[j * kRunWaves + wave] = incl[j];
+            part_s[j * kRunWaves + wave] = upto.s;
+            part_v[j * kRunWaves + wave] = upto.v;
         }
     }
     __syncthreads();
@@ -392,12 +305,12 @@ __global__ void __launch_bounds__(kRbkThreads) rbk_emit_kernel(const Word* __res
         uint32_t mine = 0, all = 0;
         Part front = running;
 #pragma unroll
-        for (uint32_t w = 0; w < (uint32_t)kRbkWaves; w++) {
-            const uint32_t t = part[j * kRbkWaves + w];
+        for (uint32_t w = 0; w < (uint32_t)kRunWaves; w++) {
+            const uint32_t t = part[j * kRunWaves + w];
             mine += w < wave ? t : 0u;
             all += t;
             if (w == wave) front = running;
-            running = join<Op>(running, Part{part_s[j * kRbkWaves + w], part_v[j * kRbkWaves + w]});
+            running = join<Op>(running, Part{part_s[j * kRunWaves + w], part_v[j * kRunWaves + w]});
         }
         uint32_t q = heads_below + mine + incl[j] - count[j];   // heads of the tile in front of this thread's group j
         heads_below += all;
@@ -422,37 +335,26 @@ __global__ void __launch_bounds__(kRbkThreads) rbk_emit_kernel(const Word* __res
     }
 }
 
-// one word: the count of an empty call
-__global__ void __launch_bounds__(lsd::kWave) rbk_store_kernel(uint32_t* __restrict__ word, uint32_t value)
-{
-    if (threadIdx.x == 0) *word = value;
-}
-
 // ------------------------------------------------------------------------------------------------ reduce by key: copy
 // key_copy[i] = keys[i], val_copy[i] = vals[i].  One 16-byte group of keys, and the values beside it, per thread and round; the copies
 // are 256-byte aligned, the caller's arrays need not be (vec, vec_vals).
 template <class Word>
-__global__ void __launch_bounds__(kRbkThreads) rbk_copy_kernel(const Word* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t n,
+__global__ void __launch_bounds__(kRunThreads) rbk_copy_kernel(const Word* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t n,
                                                               uint32_t vec, uint32_t vec_vals, Word* __restrict__ key_copy,
                                                               uint32_t* __restrict__ val_copy)
 {
     constexpr uint32_t G = Groups<Word>::G;
     const uint32_t groups = (n + G - 1) / G;
-    for (uint32_t g = blockIdx.x * kRbkThreads + threadIdx.x; g < groups; g += gridDim.x * kRbkThreads) {
+    for (uint32_t g = blockIdx.x * kRunThreads + threadIdx.x; g < groups; g += gridDim.x * kRunThreads) {
         const uint32_t i0 = g * G;
         Word k[G];
         uint32_t v[G];
         load_group<Word>(keys, i0, n, vec != 0, k);
-        load_values<Word>(vals, i0, n, vec_vals != 0, v);
+        load_words32<Word>(vals, i0, n, vec_vals != 0, v);
         if (i0 + G <= n) {
-            if constexpr (G == 4) {
-                *reinterpret_cast<uint4*>(key_copy + i0) = make_uint4(k[0], k[1], k[2], k[3]);
-                *reinterpret_cast<uint4*>(val_copy + i0) = make_uint4(v[0], v[1], v[2], v[3]);
-            } else {
-                *reinterpret_cast<uint4*>(key_copy + i0) =
-                    make_uint4((uint32_t)k[0], (uint32_t)(k[0] >> 32), (uint32_t)k[1], (uint32_t)(k[1] >> 32));
-                *reinterpret_cast<uint2*>(val_copy + i0) = make_uint2(v[0], v[1]);
-            }
+            store_group<Word>(key_copy, i0, k);
+            if constexpr (G == 4) *reinterpret_cast<uint4*>(val_copy + i0) = make_uint4(v[0], v[1], v[2], v[3]);
+            else *reinterpret_cast<uint2*>(val_copy + i0) = make_uint2(v[0], v[1]);
         } else {
 #pragma unroll
             for (uint32_t e = 0; e < G; e++) {
@@ -466,61 +368,9 @@ __global__ void __launch_bounds__(kRbkThreads) rbk_copy_kernel(const Word* __res
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-// The arrays of the three phases, behind whatever the entry keeps in front of them.
-struct RunArrays {
-    uint32_t tiles = 1;
-    size_t tile_heads = 0;   // uint32[tiles], padded: the scan reads and writes whole quads
-    size_t tile_state = 0;   // uint32[tiles], padded alike: a part's s, per tile and then in front of each tile
-    size_t tile_value = 0;   // uint32[tiles], padded alike: its v
-    size_t end = 0;
-};
-
-RunArrays make_run_arrays(size_t n, size_t off)
-{
-    RunArrays A;
-    A.tiles = lsd::grid_for(n, kRbkTile, (size_t)1 << 31);
-    A.tile_heads = off; off += lsd::align_up(A.tiles * sizeof(uint32_t));
-    A.tile_state = off; off += lsd::align_up(A.tiles * sizeof(uint32_t));
-    A.tile_value = off; off += lsd::align_up(A.tiles * sizeof(uint32_t));
-    A.end = off;
-    return A;
-}
-
-// By key: control block (fault word first) | key copy | value copy | the sort's workspace | the arrays of the phases.
-struct ByKeyLayout {
-    size_t control = 0;
-    size_t key_copy = 0;
-    size_t val_copy = 0;
-    size_t sort_ws = 0;
-    size_t sort_ws_bytes = 0;
-    RunArrays runs;
-    size_t total = 0;
-};
-
-// 32 | 64, or 0 for what is no lsdsort_key_type
-int key_bits_of(int key_type)
-{
-    if (key_type >= LSDSORT_KEY_U32 && key_type <= LSDSORT_KEY_F32) return 32;
-    if (key_type >= LSDSORT_KEY_U64 && key_type <= LSDSORT_KEY_F64) return 64;
-    return 0;
-}
-
-ByKeyLayout make_by_key_layout(size_t n, int key_bits)
-{
-    ByKeyLayout L;
-    size_t off = 0;
-    L.control = off; off += lsd::kCtlBytes;
-    L.key_copy = off; off += lsd::align_up(n * (size_t)(key_bits / 8));
-    L.val_copy = off; off += lsd::align_up(n * sizeof(uint32_t));
-    L.sort_ws = off;
-    L.sort_ws_bytes = key_bits == 32 ? lsdsort_workspace_bytes(n, 8, 1) : lsdsort_wide_workspace_bytes(n, 8, 64, 32);
-    off += lsd::align_up(L.sort_ws_bytes);
-    L.runs = make_run_arrays(n, off);
-    L.total = L.runs.end;
-    return L;
-}
-
-bool aligned_to(const void* p, size_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
+// The tile arrays of the three phases (TileArrays::at): [0] tile_heads, [1] tile_state and [2] tile_value -- a part's s and v, per tile
+// and then in front of each tile.  By key the companion of the key copy (RunLayout) is the value copy: always there.
+constexpr int kTileArrays = 3;
 
 enum OpKind { kAddWords, kAddFloats, kLeastWord };
 
@@ -544,19 +394,19 @@ bool plan_values(int val_type, int op, OpKind* kind, ValueMap* map)
 // count | scan | emit over keys[0 .. n) and vals[0 .. n), n >= 1
 template <class Word, class Op>
 int run_phases(const Word* keys, const uint32_t* vals, size_t n, ValueMap map, Word* out_keys, uint32_t* out_vals, uint32_t* counts,
-               uint32_t* num_runs, uint32_t* fault, char* ws, const RunArrays& A, hipStream_t s)
+               uint32_t* num_runs, uint32_t* fault, char* ws, const TileArrays& A, hipStream_t s)
 {
     const uint32_t vec = aligned_to(keys, 16) ? 1u : 0u, vec_vals = aligned_to(vals, 16) ? 1u : 0u;
-    uint32_t* tile_heads = reinterpret_cast<uint32_t*>(ws + A.tile_heads);
-    uint32_t* tile_state = reinterpret_cast<uint32_t*>(ws + A.tile_state);
-    uint32_t* tile_value = reinterpret_cast<uint32_t*>(ws + A.tile_value);
-    hipLaunchKernelGGL((rbk_count_kernel<Word, Op>), dim3(A.tiles), dim3(kRbkThreads), 0, s, keys, vals, (uint32_t)n, vec, vec_vals, map,
+    uint32_t* tile_heads = reinterpret_cast<uint32_t*>(ws + A.at[0]);
+    uint32_t* tile_state = reinterpret_cast<uint32_t*>(ws + A.at[1]);
+    uint32_t* tile_value = reinterpret_cast<uint32_t*>(ws + A.at[2]);
+    hipLaunchKernelGGL((rbk_count_kernel<Word, Op>), dim3(A.tiles), dim3(kRunThreads), 0, s, keys, vals, (uint32_t)n, vec, vec_vals, map,
                        tile_heads, tile_state, tile_value, fault);
     LSD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rbk_scan_kernel<Op>, dim3(1), dim3(kRbkScanThreads), 0, s, tile_heads, tile_state, tile_value, A.tiles, (uint32_t)n, map,
+    hipLaunchKernelGGL(rbk_scan_kernel<Op>, dim3(1), dim3(kRunScanThreads), 0, s, tile_heads, tile_state, tile_value, A.tiles, (uint32_t)n, map,
                        num_runs, out_vals, counts, fault);
     LSD_HIP(hipGetLastError());
-    hipLaunchKernelGGL((rbk_emit_kernel<Word, Op>), dim3(A.tiles), dim3(kRbkThreads), 0, s, keys, vals, (uint32_t)n, vec, vec_vals, map,
+    hipLaunchKernelGGL((rbk_emit_kernel<Word, Op>), dim3(A.tiles), dim3(kRunThreads), 0, s, keys, vals, (uint32_t)n, vec, vec_vals, map,
                        static_cast<const uint32_t*>(tile_heads), static_cast<const uint32_t*>(tile_state),
                        static_cast<const uint32_t*>(tile_value), static_cast<const uint32_t*>(fault), out_keys, out_vals, counts);
     LSD_HIP(hipGetLastError());
@@ -565,7 +415,7 @@ int run_phases(const Word* keys, const uint32_t* vals, size_t n, ValueMap map, W
 
 template <class Word>
 int run_phases_of(OpKind kind, const void* keys, const void* vals, size_t n, ValueMap map, void* out_keys, void* out_vals, uint32_t* counts,
-                  uint32_t* num_runs, uint32_t* fault, char* ws, const RunArrays& A, hipStream_t s)
+                  uint32_t* num_runs, uint32_t* fault, char* ws, const TileArrays& A, hipStream_t s)
 {
     const Word* k = static_cast<const Word*>(keys);
     const uint32_t* v = static_cast<const uint32_t*>(vals);
@@ -578,22 +428,11 @@ int run_phases_of(OpKind kind, const void* keys, const void* vals, size_t n, Val
     }
 }
 
-// the count of an empty call: one stream-ordered 4-byte store, where the caller gave the word
-int store_zero_runs(uint32_t* d_num, void* hip_stream)
-{
-    if (!d_num) return LSDSORT_OK;
-    if (!aligned_to(d_num, 4)) return LSDSORT_ERR_INVALID_ARG;
-    LSD_TRY(lsdsort_prepare_device());
-    hipLaunchKernelGGL(rbk_store_kernel, dim3(1), dim3(lsd::kWave), 0, static_cast<hipStream_t>(hip_stream), d_num, 0u);
-    LSD_HIP(hipGetLastError());
-    return LSDSORT_OK;
-}
-
 template <class Word>
 hipError_t launch_copy(const void* keys, const void* vals, size_t n, void* key_copy, void* val_copy, hipStream_t s)
 {
     const size_t groups = (n + Groups<Word>::G - 1) / Groups<Word>::G;
-    hipLaunchKernelGGL(rbk_copy_kernel<Word>, dim3(lsd::grid_for(groups, kRbkThreads, kRbkMaxGrid)), dim3(kRbkThreads), 0, s,
+    hipLaunchKernelGGL(rbk_copy_kernel<Word>, dim3(lsd::grid_for(groups, kRunThreads, kRunMaxGrid)), dim3(kRunThreads), 0, s,
                        static_cast<const Word*>(keys), static_cast<const uint32_t*>(vals), (uint32_t)n, aligned_to(keys, 16) ? 1u : 0u,
                        aligned_to(vals, 16) ? 1u : 0u, static_cast<Word*>(key_copy), static_cast<uint32_t*>(val_copy));
     return hipGetLastError();
@@ -606,7 +445,7 @@ extern "C" {
 size_t lsdsort_reduce_runs_workspace_bytes(size_t n, int key_bits)
 {
     if ((key_bits != 32 && key_bits != 64) || n > LSDSORT_MAX_KEYS) return 0;
-    return make_run_arrays(n, lsd::kCtlBytes).end;
+    return make_tile_arrays(n, kTileArrays, lsd::kCtlBytes).end;
 }
 
 int lsdsort_reduce_runs_device(const void* d_keys, const void* d_vals, size_t n, int key_bits, int val_type, int op, void* d_out_keys,
@@ -624,7 +463,7 @@ int lsdsort_reduce_runs_device(const void* d_keys, const void* d_vals, size_t n,
         !aligned_to(d_out_counts, 4) || !aligned_to(d_num_runs, 4))
         return LSDSORT_ERR_INVALID_ARG;
     if (d_out_keys == d_keys || d_out_vals == d_vals) return LSDSORT_ERR_INVALID_ARG;   // read while the runs are stored
-    const RunArrays A = make_run_arrays(n, lsd::kCtlBytes);
+    const TileArrays A = make_tile_arrays(n, kTileArrays, lsd::kCtlBytes);
     if (!lsd::workspace_ok(d_workspace, workspace_bytes, A.end)) return LSDSORT_ERR_WORKSPACE;
     LSD_TRY(lsdsort_prepare_device());
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
@@ -638,7 +477,7 @@ size_t lsdsort_reduce_by_key_workspace_bytes(size_t n, int key_type)
 {
     const int key_bits = key_bits_of(key_type);
     if (!key_bits || n > LSDSORT_MAX_KEYS) return 0;
-    return make_by_key_layout(n, key_bits).total;
+    return make_run_layout(n, key_bits, true, kTileArrays).total;
 }
 
 int lsdsort_reduce_by_key_device(const void* d_keys, const void* d_vals, size_t n, int key_type, int descending, int val_type, int op,
@@ -656,23 +495,20 @@ int lsdsort_reduce_by_key_device(const void* d_keys, const void* d_vals, size_t 
     if (!aligned_to(d_keys, word) || !aligned_to(d_vals, 4) || !aligned_to(d_out_keys, word) || !aligned_to(d_out_vals, 4) ||
         !aligned_to(d_out_counts, 4) || !aligned_to(d_num_groups, 4))
         return LSDSORT_ERR_INVALID_ARG;
-    const ByKeyLayout L = make_by_key_layout(n, key_bits);
+    const RunLayout L = make_run_layout(n, key_bits, true, kTileArrays);
     if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.total)) return LSDSORT_ERR_WORKSPACE;
     LSD_TRY(lsdsort_prepare_device());
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     char* ws = static_cast<char*>(d_workspace);
     uint32_t* fault = reinterpret_cast<uint32_t*>(ws + L.control);
-    void* key_copy = ws + L.key_copy;
-    uint32_t* val_copy = reinterpret_cast<uint32_t*>(ws + L.val_copy);
+    void* key_copy = ws + L.copy;
+    uint32_t* val_copy = reinterpret_cast<uint32_t*>(ws + L.companion);
     // after this copy d_keys and d_vals are no longer read: the outputs may be the inputs themselves
     LSD_HIP(key_bits == 32 ? launch_copy<uint32_t>(d_keys, d_vals, n, key_copy, val_copy, s) : launch_copy<uint64_t>(d_keys, d_vals, n, key_copy, val_copy, s));
     // the sorts are stable in either direction: the values of a group stay in input order
-    if (key_bits == 32) {
-        LSD_TRY(lsdsort_keys_device(key_copy, val_copy, ws + L.sort_ws, L.sort_ws_bytes, n, 8, key_type, descending, hip_stream));
-        return run_phases_of<uint32_t>(kind, key_copy, val_copy, n, map, d_out_keys, d_out_vals, d_out_counts, d_num_groups, fault, ws, L.runs, s);
-    }
-    LSD_TRY(lsdsort_keys64_device(key_copy, val_copy, 32, ws + L.sort_ws, L.sort_ws_bytes, n, 8, key_type, descending, hip_stream));
-    return run_phases_of<uint64_t>(kind, key_copy, val_copy, n, map, d_out_keys, d_out_vals, d_out_counts, d_num_groups, fault, ws, L.runs, s);
+    LSD_TRY(sort_copies(ws, L, n, key_type, descending, hip_stream));
+    if (key_bits == 32) return run_phases_of<uint32_t>(kind, key_copy, val_copy, n, map, d_out_keys, d_out_vals, d_out_counts, d_num_groups, fault, ws, L.arrays, s);
+    return run_phases_of<uint64_t>(kind, key_copy, val_copy, n, map, d_out_keys, d_out_vals, d_out_counts, d_num_groups, fault, ws, L.arrays, s);
 }
 
 int lsdsort_reduce_by_key_check_device(void* d_workspace, size_t n, int key_type, void* hip_stream)
@@ -682,11 +518,7 @@ int lsdsort_reduce_by_key_check_device(void* d_workspace, size_t n, int key_type
     if (!key_bits) return LSDSORT_ERR_INVALID_ARG;
     if (n > LSDSORT_MAX_KEYS) return LSDSORT_ERR_TOO_LARGE;
     if (n == 0) return LSDSORT_OK;   // an empty call touches no workspace
-    const ByKeyLayout L = make_by_key_layout(n, key_bits);
-    char* ws = static_cast<char*>(d_workspace);
-    LSD_TRY(lsdsort_check_device(ws + L.control, hip_stream));   // the unit's own word; synchronises the stream
-    if (key_bits == 32) return lsdsort_check_device(ws + L.sort_ws, hip_stream);
-    return lsdsort_wide_check_device(ws + L.sort_ws, n, 8, 64, 32, hip_stream);
+    return check_copies(static_cast<char*>(d_workspace), make_run_layout(n, key_bits, true, kTileArrays), n, hip_stream);
 }
 
 }  // extern "C"

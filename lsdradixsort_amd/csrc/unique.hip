@@ -23,130 +23,45 @@
 
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
+#include "run_tiles.hpp"
 
 namespace {
 
-constexpr int kRleThreads = 256;
-constexpr int kRleWaves = kRleThreads / lsd::kWave;
-constexpr uint32_t kRleThreadKeys = 16;
-constexpr uint32_t kRleTile = kRleThreads * kRleThreadKeys;   // keys of a workgroup: 4096
-constexpr int kRleScanThreads = 1024;
-constexpr int kRleScanWaves = kRleScanThreads / lsd::kWave;
-constexpr uint32_t kRleScanRound = 4 * kRleScanThreads;       // tile counts the scan takes per round: 4096
-constexpr uint32_t kRleMaxGrid = 2048;                        // workgroups of the grid-stride copy kernel
-constexpr uint32_t kRleFault = 1u;                            // the scanned total is 0 or above n: never expected
-
-// A thread holds its 16 keys as J groups of G words, one 16-byte load each; group j of thread t is the G keys from
-// tile * kRleTile + (j * 256 + t) * G, so that the lanes of a wave read consecutive 16-byte lines.
-template <class Word>
-struct Groups {
-    static constexpr uint32_t G = 16 / sizeof(Word);        // 4 | 2
-    static constexpr uint32_t J = kRleThreadKeys / G;       // 4 | 8
-};
-
-template <class Word>
-__device__ __forceinline__ uint32_t group_start(uint32_t tile, uint32_t j, uint32_t tid)
-{
-    return tile * kRleTile + (j * kRleThreads + tid) * Groups<Word>::G;   // below 2^30 + 4096
-}
-
-// The G words from i0 (a multiple of G); words at or behind n read as 0.  vec: the array starts on a 16-byte line.
-template <class Word>
-__device__ __forceinline__ void load_group(const Word* __restrict__ keys, uint32_t i0, uint32_t n, bool vec, Word (&k)[Groups<Word>::G])
-{
-    constexpr uint32_t G = Groups<Word>::G;
-    if (vec && i0 + G <= n) {
-        const uint4 v = *reinterpret_cast<const uint4*>(keys + i0);
-        if constexpr (sizeof(Word) == 4) {
-            k[0] = v.x; k[1] = v.y; k[2] = v.z; k[3] = v.w;
-        } else {
-            k[0] = (Word)v.x | (Word)v.y << 32;
-            k[1] = (Word)v.z | (Word)v.w << 32;
-        }
-    } else {
-#pragma unroll
-        for (uint32_t e = 0; e < G; e++) k[e] = i0 + e < n ? keys[i0 + e] : (Word)0;
-    }
-}
-
-// The positions beside the keys: the same groups of a 256-byte aligned uint32 array.
-template <class Word>
-__device__ __forceinline__ void load_positions(const uint32_t* __restrict__ pos, uint32_t i0, uint32_t n, uint32_t (&p)[Groups<Word>::G])
-{
-    constexpr uint32_t G = Groups<Word>::G;
-    if (i0 + G <= n) {
-        if constexpr (G == 4) {
-            const uint4 v = *reinterpret_cast<const uint4*>(pos + i0);
-            p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
-        } else {
-            const uint2 v = *reinterpret_cast<const uint2*>(pos + i0);
-            p[0] = v.x; p[1] = v.y;
-        }
-    } else {
-#pragma unroll
-        for (uint32_t e = 0; e < G; e++) p[e] = i0 + e < n ? pos[i0 + e] : 0u;
-    }
-}
-
-// This thread's keys of `tile` and their head flags: bit j * G + e is set where key (j, e) lies below n and is position 0 or
-// differs from the key in front of it.  That key is the one before it in the group, for a group's first key the last key of the
-// lane below, and for lane 0 one more global load.  All 64 lanes of every wave must be active.
-template <class Word>
-__device__ __forceinline__ uint32_t load_tile_heads(const Word* __restrict__ keys, uint32_t n, bool vec, uint32_t tile, uint32_t tid,
-                                                    uint32_t lane, Word (&k)[Groups<Word>::J][Groups<Word>::G])
-{
-    constexpr uint32_t G = Groups<Word>::G, J = Groups<Word>::J;
-#pragma unroll
-    for (uint32_t j = 0; j < J; j++) load_group<Word>(keys, group_start<Word>(tile, j, tid), n, vec, k[j]);
-    uint32_t flags = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < J; j++) {
-        const uint32_t i0 = group_start<Word>(tile, j, tid);
-        Word before = __shfl_up(k[j][G - 1], 1u, lsd::kWave);
-        if (lane == 0 && i0 > 0 && i0 < n) before = keys[i0 - 1];
-#pragma unroll
-        for (uint32_t e = 0; e < G; e++) {
-            const uint32_t i = i0 + e;
-            const bool head = i < n && (i == 0 || k[j][e] != (e ? k[j][e - 1] : before));
-            flags |= (head ? 1u : 0u) << (j * G + e);
-        }
-    }
-    return flags;
-}
+using namespace lsd;   // run_tiles.hpp: the tile constants, Groups, the loaders, the head flags, the host plumbing
 
 // ------------------------------------------------------------------------------------------------ count
 // tile_heads[tile] = number of run heads in the tile, tile_last[tile] = 1 + the position of its last head (0: the tile has none): two
 // plain stores per workgroup, every tile word on every call.  The first workgroup clears the unit's fault word, which the scan
 // (behind this kernel's end) may set.
 template <class Word>
-__global__ void __launch_bounds__(kRleThreads) rle_count_kernel(const Word* __restrict__ keys, uint32_t n, uint32_t vec,
+__global__ void __launch_bounds__(kRunThreads) rle_count_kernel(const Word* __restrict__ keys, uint32_t n, uint32_t vec,
                                                                uint32_t* __restrict__ tile_heads, uint32_t* __restrict__ tile_last,
                                                                uint32_t* __restrict__ fault)
 {
     constexpr uint32_t G = Groups<Word>::G, J = Groups<Word>::J;
-    __shared__ uint32_t part[2 * kRleWaves];
+    __shared__ uint32_t part[2 * kRunWaves];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     Word k[J][G];
-    const uint32_t flags = load_tile_heads<Word>(keys, n, vec != 0, blockIdx.x, tid, lane, k);
+    const uint32_t flags = tile_keys_and_heads<Word>(keys, n, vec != 0, blockIdx.x, tid, lane, k);
     uint32_t last = 0;   // this thread's groups lie in ascending position order
 #pragma unroll
     for (uint32_t j = 0; j < J; j++) {
-        const uint32_t f = (flags >> (j * G)) & ((1u << G) - 1u);
+        const uint32_t f = group_flags<Word>(flags, j);
         if (f) last = group_start<Word>(blockIdx.x, j, tid) + (31u - (uint32_t)__builtin_clz(f)) + 1u;
     }
     const uint32_t heads = lsd::wave_sum((uint32_t)__builtin_popcount(flags));
     last = lsd::wave_max(last);
     if (lane == 0) {
         part[wave] = heads;
-        part[kRleWaves + wave] = last;
+        part[kRunWaves + wave] = last;
     }
     __syncthreads();
     if (tid == 0) {
         uint32_t all = 0, top = 0;
 #pragma unroll
-        for (int w = 0; w < kRleWaves; w++) {
+        for (int w = 0; w < kRunWaves; w++) {
             all += part[w];
-            top = part[kRleWaves + w] > top ? part[kRleWaves + w] : top;
+            top = part[kRunWaves + w] > top ? part[kRunWaves + w] : top;
         }
         tile_heads[blockIdx.x] = all;
         tile_last[blockIdx.x] = top;
@@ -160,17 +75,17 @@ __global__ void __launch_bounds__(kRleThreads) rle_count_kernel(const Word* __re
 // need, the running total and the running last head carried from round to round.  The arrays are 256-byte aligned and padded, so the
 // last quad is read and written whole; its words behind `tiles` count as 0.  Where the caller wants counts, the last run's -- from
 // the last head of all to n -- is stored here: every other run's count is stored by the head BEHIND it (emit).
-__global__ void __launch_bounds__(kRleScanThreads) rle_scan_kernel(uint32_t* __restrict__ tile_heads, uint32_t* __restrict__ tile_last,
+__global__ void __launch_bounds__(kRunScanThreads) rle_scan_kernel(uint32_t* __restrict__ tile_heads, uint32_t* __restrict__ tile_last,
                                                                   uint32_t tiles, uint32_t n, uint32_t* __restrict__ num_runs,
                                                                   uint32_t* __restrict__ counts, uint32_t* __restrict__ fault)
 {
-    __shared__ uint32_t part[kRleScanWaves];
-    __shared__ uint32_t part_last[kRleScanWaves];
+    __shared__ uint32_t part[kRunScanWaves];
+    __shared__ uint32_t part_last[kRunScanWaves];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     uint4* heads4 = reinterpret_cast<uint4*>(tile_heads);
     uint4* last4 = reinterpret_cast<uint4*>(tile_last);
     uint32_t carry = 0, carry_last = 0;
-    for (uint32_t first = 0; first < tiles; first += kRleScanRound) {
+    for (uint32_t first = 0; first < tiles; first += kRunScanRound) {
         const uint32_t t = first + 4 * tid;
         uint4 v = make_uint4(0, 0, 0, 0), l = make_uint4(0, 0, 0, 0);
         if (t < tiles) {
@@ -192,11 +107,11 @@ __global__ void __launch_bounds__(kRleScanThreads) rle_scan_kernel(uint32_t* __r
         if (lane == 0) before_last = 0;
         if (lane == 63u) part_last[wave] = incl_last;
         uint32_t all = 0;
-        const uint32_t excl = carry + lsd::group_exclusive_scan<kRleScanWaves>(v.x + v.y + v.z + v.w, lane, wave, part, &all);   // a barrier inside
+        const uint32_t excl = carry + lsd::group_exclusive_scan<kRunScanWaves>(v.x + v.y + v.z + v.w, lane, wave, part, &all);   // a barrier inside
         uint32_t all_last = carry_last;
         before_last = before_last > carry_last ? before_last : carry_last;
 #pragma unroll
-        for (uint32_t w = 0; w < (uint32_t)kRleScanWaves; w++) {
+        for (uint32_t w = 0; w < (uint32_t)kRunScanWaves; w++) {
             const uint32_t x = part_last[w];
             if (w < wave) before_last = x > before_last ? x : before_last;
             all_last = x > all_last ? x : all_last;
@@ -212,7 +127,7 @@ __global__ void __launch_bounds__(kRleScanThreads) rle_scan_kernel(uint32_t* __r
     }
     if (tid == 0) {
         *num_runs = carry;
-        if (carry == 0 || carry > n || carry_last == 0 || carry_last > n) atomicOr(fault, kRleFault);
+        if (carry == 0 || carry > n || carry_last == 0 || carry_last > n) atomicOr(fault, kRunFault);
         else if (counts) counts[carry - 1] = n - (carry_last - 1u);
     }
 }
@@ -227,7 +142,7 @@ __global__ void __launch_bounds__(kRleScanThreads) rle_scan_kernel(uint32_t* __r
 // from tile_last[tile] (scanned).  No array of starts is written and read again for the counts.  counts, starts, first and inverse
 // may each be null.  Nothing is stored where the scan set the fault word.
 template <class Word, bool POSITIONS>
-__global__ void __launch_bounds__(kRleThreads) rle_emit_kernel(const Word* __restrict__ keys, const uint32_t* __restrict__ pos, uint32_t n,
+__global__ void __launch_bounds__(kRunThreads) rle_emit_kernel(const Word* __restrict__ keys, const uint32_t* __restrict__ pos, uint32_t n,
                                                               uint32_t vec, const uint32_t* __restrict__ tile_heads,
                                                               const uint32_t* __restrict__ tile_last, const uint32_t* __restrict__ fault,
                                                               Word* __restrict__ out_keys, uint32_t* __restrict__ counts,
@@ -235,23 +150,23 @@ __global__ void __launch_bounds__(kRleThreads) rle_emit_kernel(const Word* __res
                                                               uint32_t* __restrict__ inverse)
 {
     constexpr uint32_t G = Groups<Word>::G, J = Groups<Word>::J;
-    __shared__ uint32_t part[J * kRleWaves];
-    __shared__ uint32_t head_at[kRleTile];   // position of the tile's q-th head
+    __shared__ uint32_t part[J * kRunWaves];
+    __shared__ uint32_t head_at[kRunTile];   // position of the tile's q-th head
     if (*fault != 0u) return;   // uniform
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, tile = blockIdx.x;
     Word k[J][G];
-    const uint32_t flags = load_tile_heads<Word>(keys, n, vec != 0, tile, tid, lane, k);
+    const uint32_t flags = tile_keys_and_heads<Word>(keys, n, vec != 0, tile, tid, lane, k);
     uint32_t p[J][G];
     if constexpr (POSITIONS) {
 #pragma unroll
-        for (uint32_t j = 0; j < J; j++) load_positions<Word>(pos, group_start<Word>(tile, j, tid), n, p[j]);
+        for (uint32_t j = 0; j < J; j++) load_words32<Word>(pos, group_start<Word>(tile, j, tid), n, true, p[j]);
     }
     uint32_t count[J], incl[J];
 #pragma unroll
     for (uint32_t j = 0; j < J; j++) {
-        count[j] = (uint32_t)__builtin_popcount((flags >> (j * G)) & ((1u << G) - 1u));
+        count[j] = (uint32_t)__builtin_popcount(group_flags<Word>(flags, j));
         incl[j] = lsd::wave_inclusive_scan(count[j]);
-        if (lane == 63u) part[j * kRleWaves + wave] = incl[j];
+        if (lane == 63u) part[j * kRunWaves + wave] = incl[j];
     }
     __syncthreads();
     const uint32_t base = tile_heads[tile];   // heads in front of the tile
@@ -261,8 +176,8 @@ __global__ void __launch_bounds__(kRleThreads) rle_emit_kernel(const Word* __res
     for (uint32_t j = 0; j < J; j++) {
         uint32_t mine = 0, all = 0;
 #pragma unroll
-        for (uint32_t w = 0; w < (uint32_t)kRleWaves; w++) {
-            const uint32_t t = part[j * kRleWaves + w];
+        for (uint32_t w = 0; w < (uint32_t)kRunWaves; w++) {
+            const uint32_t t = part[j * kRunWaves + w];
             mine += w < wave ? t : 0u;
             all += t;
         }
@@ -282,7 +197,7 @@ __global__ void __launch_bounds__(kRleThreads) rle_emit_kernel(const Word* __res
                         if (first) first[r] = p[j][e];
                     }
                 }
-                if (counts && q < kRleTile) head_at[q] = i;
+                if (counts && q < kRunTile) head_at[q] = i;
                 q++;
             }
             if constexpr (POSITIONS) {   // base + q = heads at positions <= i, at least 1: position 0 is one
@@ -309,33 +224,24 @@ __global__ void __launch_bounds__(kRleThreads) rle_emit_kernel(const Word* __res
     }
 }
 
-// one word: the count of an empty call
-__global__ void __launch_bounds__(lsd::kWave) rle_store_kernel(uint32_t* __restrict__ word, uint32_t value)
-{
-    if (threadIdx.x == 0) *word = value;
-}
-
 // ------------------------------------------------------------------------------------------------ unique: copy
 // copy[i] = keys[i], and with positions pos[i] = i.  One 16-byte group of keys per thread and round; copy and pos are 256-byte
 // aligned, the caller's keys need not be (vec).
 template <class Word, bool POSITIONS>
-__global__ void __launch_bounds__(kRleThreads) unique_copy_kernel(const Word* __restrict__ keys, uint32_t n, uint32_t vec,
+__global__ void __launch_bounds__(kRunThreads) unique_copy_kernel(const Word* __restrict__ keys, uint32_t n, uint32_t vec,
                                                                  Word* __restrict__ copy, uint32_t* __restrict__ pos)
 {
     constexpr uint32_t G = Groups<Word>::G;
     const uint32_t groups = (n + G - 1) / G;
-    for (uint32_t g = blockIdx.x * kRleThreads + threadIdx.x; g < groups; g += gridDim.x * kRleThreads) {
+    for (uint32_t g = blockIdx.x * kRunThreads + threadIdx.x; g < groups; g += gridDim.x * kRunThreads) {
         const uint32_t i0 = g * G;
         Word k[G];
         load_group<Word>(keys, i0, n, vec != 0, k);
         if (i0 + G <= n) {
-            if constexpr (G == 4) {
-                *reinterpret_cast<uint4*>(copy + i0) = make_uint4(k[0], k[1], k[2], k[3]);
-                if constexpr (POSITIONS) *reinterpret_cast<uint4*>(pos + i0) = make_uint4(i0, i0 + 1, i0 + 2, i0 + 3);
-            } else {
-                *reinterpret_cast<uint4*>(copy + i0) =
-                    make_uint4((uint32_t)k[0], (uint32_t)(k[0] >> 32), (uint32_t)k[1], (uint32_t)(k[1] >> 32));
-                if constexpr (POSITIONS) *reinterpret_cast<uint2*>(pos + i0) = make_uint2(i0, i0 + 1);
+            store_group<Word>(copy, i0, k);
+            if constexpr (POSITIONS) {
+                if constexpr (G == 4) *reinterpret_cast<uint4*>(pos + i0) = make_uint4(i0, i0 + 1, i0 + 2, i0 + 3);
+                else *reinterpret_cast<uint2*>(pos + i0) = make_uint2(i0, i0 + 1);
             }
         } else {
 #pragma unroll
@@ -350,92 +256,32 @@ __global__ void __launch_bounds__(kRleThreads) unique_copy_kernel(const Word* __
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-// The arrays of the run-length phases, behind whatever the entry keeps in front of them.
-struct RleArrays {
-    uint32_t tiles = 1;
-    size_t tile_heads = 0;   // uint32[tiles], padded: the scan reads and writes whole quads
-    size_t tile_last = 0;    // uint32[tiles], padded alike: 1 + the position of the last head, per tile and then in front of each tile
-    size_t end = 0;
-};
-
-RleArrays make_rle_arrays(size_t n, size_t off)
-{
-    RleArrays A;
-    A.tiles = lsd::grid_for(n, kRleTile, (size_t)1 << 31);
-    A.tile_heads = off; off += lsd::align_up(A.tiles * sizeof(uint32_t));
-    A.tile_last = off; off += lsd::align_up(A.tiles * sizeof(uint32_t));
-    A.end = off;
-    return A;
-}
-
-// Unique's carve-up: control block (fault word first) | key copy | positions | the sort's workspace | the run-length arrays.
-struct UniqueLayout {
-    size_t control = 0;
-    size_t copy = 0;
-    size_t pos = 0;
-    size_t sort_ws = 0;
-    size_t sort_ws_bytes = 0;
-    RleArrays rle;
-    size_t total = 0;
-};
-
-// 32 | 64, or 0 for what is no lsdsort_key_type
-int key_bits_of(int key_type)
-{
-    if (key_type >= LSDSORT_KEY_U32 && key_type <= LSDSORT_KEY_F32) return 32;
-    if (key_type >= LSDSORT_KEY_U64 && key_type <= LSDSORT_KEY_F64) return 64;
-    return 0;
-}
-
-UniqueLayout make_unique_layout(size_t n, int key_bits, int with_positions)
-{
-    UniqueLayout L;
-    size_t off = 0;
-    L.control = off; off += lsd::kCtlBytes;
-    L.copy = off; off += lsd::align_up(n * (size_t)(key_bits / 8));
-    L.pos = off; off += with_positions ? lsd::align_up(n * sizeof(uint32_t)) : 0;
-    L.sort_ws = off;
-    L.sort_ws_bytes = key_bits == 32 ? lsdsort_workspace_bytes(n, 8, with_positions ? 1 : 0)
-                                     : lsdsort_wide_workspace_bytes(n, 8, 64, with_positions ? 32 : 0);
-    off += lsd::align_up(L.sort_ws_bytes);
-    L.rle = make_rle_arrays(n, off);
-    L.total = L.rle.end;
-    return L;
-}
-
-bool aligned_to(const void* p, size_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
+// The tile arrays of the run-length phases (TileArrays::at): [0] tile_heads, [1] tile_last -- 1 + the position of the last head, per
+// tile and then in front of each tile.
+constexpr int kTileArrays = 2;
 
 // count | scan | emit over keys[0 .. n), n >= 1.  pos: the positions beside the keys, or null (then first and inverse are null too).
 template <class Word>
-int run_rle(const Word* keys, const uint32_t* pos, size_t n, Word* out_keys, uint32_t* counts, uint32_t* starts, uint32_t* first,
-            uint32_t* inverse, uint32_t* num_runs, uint32_t* fault, char* ws, const RleArrays& A, hipStream_t s)
+int run_rle(const void* keys_in, const uint32_t* pos, size_t n, void* out, uint32_t* counts, uint32_t* starts, uint32_t* first,
+            uint32_t* inverse, uint32_t* num_runs, uint32_t* fault, char* ws, const TileArrays& A, hipStream_t s)
 {
+    const Word* keys = static_cast<const Word*>(keys_in);
+    Word* out_keys = static_cast<Word*>(out);
     const uint32_t vec = aligned_to(keys, 16) ? 1u : 0u;
-    uint32_t* tile_heads = reinterpret_cast<uint32_t*>(ws + A.tile_heads);
-    uint32_t* tile_last = reinterpret_cast<uint32_t*>(ws + A.tile_last);
-    hipLaunchKernelGGL(rle_count_kernel<Word>, dim3(A.tiles), dim3(kRleThreads), 0, s, keys, (uint32_t)n, vec, tile_heads, tile_last, fault);
+    uint32_t* tile_heads = reinterpret_cast<uint32_t*>(ws + A.at[0]);
+    uint32_t* tile_last = reinterpret_cast<uint32_t*>(ws + A.at[1]);
+    hipLaunchKernelGGL(rle_count_kernel<Word>, dim3(A.tiles), dim3(kRunThreads), 0, s, keys, (uint32_t)n, vec, tile_heads, tile_last, fault);
     LSD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rle_scan_kernel, dim3(1), dim3(kRleScanThreads), 0, s, tile_heads, tile_last, A.tiles, (uint32_t)n, num_runs, counts, fault);
+    hipLaunchKernelGGL(rle_scan_kernel, dim3(1), dim3(kRunScanThreads), 0, s, tile_heads, tile_last, A.tiles, (uint32_t)n, num_runs, counts, fault);
     LSD_HIP(hipGetLastError());
     if (pos)
-        hipLaunchKernelGGL((rle_emit_kernel<Word, true>), dim3(A.tiles), dim3(kRleThreads), 0, s, keys, pos, (uint32_t)n, vec,
+        hipLaunchKernelGGL((rle_emit_kernel<Word, true>), dim3(A.tiles), dim3(kRunThreads), 0, s, keys, pos, (uint32_t)n, vec,
                            static_cast<const uint32_t*>(tile_heads), static_cast<const uint32_t*>(tile_last),
                            static_cast<const uint32_t*>(fault), out_keys, counts, starts, first, inverse);
     else
-        hipLaunchKernelGGL((rle_emit_kernel<Word, false>), dim3(A.tiles), dim3(kRleThreads), 0, s, keys, pos, (uint32_t)n, vec,
+        hipLaunchKernelGGL((rle_emit_kernel<Word, false>), dim3(A.tiles), dim3(kRunThreads), 0, s, keys, pos, (uint32_t)n, vec,
                            static_cast<const uint32_t*>(tile_heads), static_cast<const uint32_t*>(tile_last),
                            static_cast<const uint32_t*>(fault), out_keys, counts, starts, first, inverse);
-    LSD_HIP(hipGetLastError());
-    return LSDSORT_OK;
-}
-
-// the count of an empty call: one stream-ordered 4-byte store, where the caller gave the word
-int store_zero_runs(uint32_t* d_num, void* hip_stream)
-{
-    if (!d_num) return LSDSORT_OK;
-    if (!aligned_to(d_num, 4)) return LSDSORT_ERR_INVALID_ARG;
-    LSD_TRY(lsdsort_prepare_device());
-    hipLaunchKernelGGL(rle_store_kernel, dim3(1), dim3(lsd::kWave), 0, static_cast<hipStream_t>(hip_stream), d_num, 0u);
     LSD_HIP(hipGetLastError());
     return LSDSORT_OK;
 }
@@ -444,7 +290,7 @@ template <class Word, bool POSITIONS>
 hipError_t launch_copy(const void* keys, size_t n, void* copy, uint32_t* pos, hipStream_t s)
 {
     const size_t groups = (n + Groups<Word>::G - 1) / Groups<Word>::G;
-    hipLaunchKernelGGL((unique_copy_kernel<Word, POSITIONS>), dim3(lsd::grid_for(groups, kRleThreads, kRleMaxGrid)), dim3(kRleThreads), 0, s,
+    hipLaunchKernelGGL((unique_copy_kernel<Word, POSITIONS>), dim3(lsd::grid_for(groups, kRunThreads, kRunMaxGrid)), dim3(kRunThreads), 0, s,
                        static_cast<const Word*>(keys), (uint32_t)n, aligned_to(keys, 16) ? 1u : 0u, static_cast<Word*>(copy), pos);
     return hipGetLastError();
 }
@@ -456,7 +302,7 @@ extern "C" {
 size_t lsdsort_rle_workspace_bytes(size_t n, int key_bits)
 {
     if ((key_bits != 32 && key_bits != 64) || n > LSDSORT_MAX_KEYS) return 0;
-    return make_rle_arrays(n, lsd::kCtlBytes).end;
+    return make_tile_arrays(n, kTileArrays, lsd::kCtlBytes).end;
 }
 
 int lsdsort_rle_device(const void* d_keys, size_t n, int key_bits, void* d_out_keys, uint32_t* d_out_counts, uint32_t* d_out_starts,
@@ -470,24 +316,21 @@ int lsdsort_rle_device(const void* d_keys, size_t n, int key_bits, void* d_out_k
     if (!aligned_to(d_keys, word) || !aligned_to(d_out_keys, word) || !aligned_to(d_out_counts, 4) || !aligned_to(d_out_starts, 4) ||
         !aligned_to(d_num_runs, 4))
         return LSDSORT_ERR_INVALID_ARG;
-    const RleArrays A = make_rle_arrays(n, lsd::kCtlBytes);
+    const TileArrays A = make_tile_arrays(n, kTileArrays, lsd::kCtlBytes);
     if (!lsd::workspace_ok(d_workspace, workspace_bytes, A.end)) return LSDSORT_ERR_WORKSPACE;
     LSD_TRY(lsdsort_prepare_device());
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     char* ws = static_cast<char*>(d_workspace);
     uint32_t* fault = reinterpret_cast<uint32_t*>(ws);
-    if (key_bits == 32)
-        return run_rle<uint32_t>(static_cast<const uint32_t*>(d_keys), nullptr, n, static_cast<uint32_t*>(d_out_keys), d_out_counts,
-                                 d_out_starts, nullptr, nullptr, d_num_runs, fault, ws, A, s);
-    return run_rle<uint64_t>(static_cast<const uint64_t*>(d_keys), nullptr, n, static_cast<uint64_t*>(d_out_keys), d_out_counts, d_out_starts,
-                             nullptr, nullptr, d_num_runs, fault, ws, A, s);
+    if (key_bits == 32) return run_rle<uint32_t>(d_keys, nullptr, n, d_out_keys, d_out_counts, d_out_starts, nullptr, nullptr, d_num_runs, fault, ws, A, s);
+    return run_rle<uint64_t>(d_keys, nullptr, n, d_out_keys, d_out_counts, d_out_starts, nullptr, nullptr, d_num_runs, fault, ws, A, s);
 }
 
 size_t lsdsort_unique_workspace_bytes(size_t n, int key_type, int with_positions)
 {
     const int key_bits = key_bits_of(key_type);
     if (!key_bits || n > LSDSORT_MAX_KEYS) return 0;
-    return make_unique_layout(n, key_bits, with_positions != 0).total;
+    return make_run_layout(n, key_bits, with_positions != 0, kTileArrays).total;
 }
 
 int lsdsort_unique_device(const void* d_keys, size_t n, int key_type, int descending, void* d_out_keys, uint32_t* d_out_counts,
@@ -504,26 +347,21 @@ int lsdsort_unique_device(const void* d_keys, size_t n, int key_type, int descen
         !aligned_to(d_out_inverse, 4) || !aligned_to(d_num_unique, 4))
         return LSDSORT_ERR_INVALID_ARG;
     const bool positions = d_out_first || d_out_inverse;
-    const UniqueLayout L = make_unique_layout(n, key_bits, positions);
+    const RunLayout L = make_run_layout(n, key_bits, positions, kTileArrays);   // the companion of the key copy: the positions
     if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.total)) return LSDSORT_ERR_WORKSPACE;
     LSD_TRY(lsdsort_prepare_device());
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     char* ws = static_cast<char*>(d_workspace);
     uint32_t* fault = reinterpret_cast<uint32_t*>(ws + L.control);
     void* copy = ws + L.copy;
-    uint32_t* pos = positions ? reinterpret_cast<uint32_t*>(ws + L.pos) : nullptr;
+    uint32_t* pos = positions ? reinterpret_cast<uint32_t*>(ws + L.companion) : nullptr;
     // after this copy d_keys is no longer read: d_out_keys may be d_keys itself
     if (key_bits == 32) LSD_HIP(positions ? (launch_copy<uint32_t, true>(d_keys, n, copy, pos, s)) : (launch_copy<uint32_t, false>(d_keys, n, copy, pos, s)));
     else LSD_HIP(positions ? (launch_copy<uint64_t, true>(d_keys, n, copy, pos, s)) : (launch_copy<uint64_t, false>(d_keys, n, copy, pos, s)));
     // the sorts are stable in either direction: the head of every run carries the lowest input position
-    if (key_bits == 32) {
-        LSD_TRY(lsdsort_keys_device(copy, pos, ws + L.sort_ws, L.sort_ws_bytes, n, 8, key_type, descending, hip_stream));
-        return run_rle<uint32_t>(static_cast<const uint32_t*>(copy), pos, n, static_cast<uint32_t*>(d_out_keys), d_out_counts, nullptr,
-                                 d_out_first, d_out_inverse, d_num_unique, fault, ws, L.rle, s);
-    }
-    LSD_TRY(lsdsort_keys64_device(copy, pos, positions ? 32 : 0, ws + L.sort_ws, L.sort_ws_bytes, n, 8, key_type, descending, hip_stream));
-    return run_rle<uint64_t>(static_cast<const uint64_t*>(copy), pos, n, static_cast<uint64_t*>(d_out_keys), d_out_counts, nullptr, d_out_first,
-                             d_out_inverse, d_num_unique, fault, ws, L.rle, s);
+    LSD_TRY(sort_copies(ws, L, n, key_type, descending, hip_stream));
+    if (key_bits == 32) return run_rle<uint32_t>(copy, pos, n, d_out_keys, d_out_counts, nullptr, d_out_first, d_out_inverse, d_num_unique, fault, ws, L.arrays, s);
+    return run_rle<uint64_t>(copy, pos, n, d_out_keys, d_out_counts, nullptr, d_out_first, d_out_inverse, d_num_unique, fault, ws, L.arrays, s);
 }
 
 int lsdsort_unique_check_device(void* d_workspace, size_t n, int key_type, int with_positions, void* hip_stream)
@@ -533,11 +371,9 @@ int lsdsort_unique_check_device(void* d_workspace, size_t n, int key_type, int w
     if (!key_bits) return LSDSORT_ERR_INVALID_ARG;
     if (n > LSDSORT_MAX_KEYS) return LSDSORT_ERR_TOO_LARGE;
     if (n == 0) return LSDSORT_OK;   // an empty call touches no workspace
-    const UniqueLayout L = make_unique_layout(n, key_bits, with_positions != 0);
-    char* ws = static_cast<char*>(d_workspace);
-    LSD_TRY(lsdsort_check_device(ws + L.control, hip_stream));   // the unit's own word; synchronises the stream
-    if (key_bits == 32) return lsdsort_check_device(ws + L.sort_ws, hip_stream);
-    return lsdsort_wide_check_device(ws + L.sort_ws, n, 8, 64, with_positions ? 32 : 0, hip_stream);
+    return check_copies(static_cast<char*>(d_workspace), make_run_layout(n, key_bits, with_positions != 0, kTileArrays), n, hip_stream);
 }
 
 }  // extern "C"
+
+

@@ -5,7 +5,7 @@
     oracle_unique(bits, key_type, descending)     distinct words in the library's order: keys, counts, first, inverse
     model_rle(bits, pos=None)                     the unit's own phases -- count | scan | emit -- tile by tile, wave by wave
     families(n, bits_per_key)                     the inputs of the tests, by name
-    TILE, SCAN_ROUND, MAX_GRID, ...               the unit's constants, restated; unit_constants() reads them out of the source
+    TILE, SCAN_ROUND, MAX_GRID, ...               csrc/run_tiles.hpp's constants, restated; unit_constants() reads them out of the source
 
 Keys are handled as uint32 / uint64 bit patterns throughout; equality is equality of bits."""
 import functools
@@ -16,16 +16,17 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 UNIT = os.path.join(ROOT, "lsdradixsort_amd", "csrc", "unique.hip")
+HEADER = os.path.join(ROOT, "lsdradixsort_amd", "csrc", "run_tiles.hpp")   # what the unit shares with reduce_by_key.hip
 
-# ---- the unit's constants, restated (tests/test_unique_cpu.py holds them to the source) ---------------------------------------
-THREADS = 256                      # kRleThreads
-THREAD_KEYS = 16                   # kRleThreadKeys
-TILE = THREADS * THREAD_KEYS       # kRleTile: keys of a workgroup
+# ---- the constants of csrc/run_tiles.hpp, restated (tests/test_unique_cpu.py holds them to the source) ------------------------
+THREADS = 256                      # kRunThreads
+THREAD_KEYS = 16                   # kRunThreadKeys
+TILE = THREADS * THREAD_KEYS       # kRunTile: keys of a workgroup
 WAVE = 64
 WAVES = THREADS // WAVE
-SCAN_THREADS = 1024                # kRleScanThreads
-SCAN_ROUND = 4 * SCAN_THREADS      # kRleScanRound: tile counts the one-workgroup scan takes per round
-MAX_GRID = 2048                    # kRleMaxGrid: workgroups of the grid-stride copy kernel
+SCAN_THREADS = 1024                # kRunScanThreads
+SCAN_ROUND = 4 * SCAN_THREADS      # kRunScanRound: tile counts the one-workgroup scan takes per round
+MAX_GRID = 2048                    # kRunMaxGrid: workgroups of the grid-stride copy kernel
 
 SIZES = (1, 2, 3, TILE - 1, TILE, TILE + 1, 2 * TILE + 1, 5 * TILE + 7)
 # One size past every loop's first round: the scan's second round starts at SCAN_ROUND tiles; the copy kernel's at
@@ -44,8 +45,9 @@ SENT = {32: 0x7E7E7E7E, 64: 0x7E7E7E7E7E7E7E7E}   # tests/_guarded.py: what the 
 
 
 def unit_constants():
-    """{name: value} of the constexpr integers of unique.hip that are written as plain numbers."""
-    text = open(UNIT).read()
+    """{name: value} of the constexpr integers of run_tiles.hpp (the tile of unique.hip and reduce_by_key.hip) that are written as plain
+    numbers."""
+    text = open(HEADER).read()
     return {name: int(value) for name, value in re.findall(r"constexpr (?:int|uint32_t) (k\w+) = (\d+)u?;", text)}
 
 

@@ -395,7 +395,7 @@ def test_kernels_no_scratch_no_spill_and_recorded_resources():
     res = kernel_resources("reduce_by_key.hip")
     names = list(res)
     # the exact kernel set: count and emit per word and operation, one scan per operation, copy per word, one store
-    sets = {"rbk_count_kernel": 6, "rbk_scan_kernel": 3, "rbk_emit_kernel": 6, "rbk_copy_kernel": 2, "rbk_store_kernel": 1}
+    sets = {"rbk_count_kernel": 6, "rbk_scan_kernel": 3, "rbk_emit_kernel": 6, "rbk_copy_kernel": 2, "run_store_kernel": 1}
     for must, times in sets.items():
         assert sum(must in name for name in names) == times, (must, names)
     assert len(names) == sum(sets.values()), names
@@ -410,19 +410,27 @@ def test_kernels_no_scratch_no_spill_and_recorded_resources():
         assert res[name]["lds_bytes"] == w["lds_bytes"], f"{name}: {res[name]['lds_bytes']} B of static LDS, recorded {w['lds_bytes']}"
 
 
-def test_the_unit_includes_three_files_only_and_has_no_inline_assembly():
+def test_the_unit_includes_four_files_only_and_has_no_inline_assembly():
     text = open(UNIT).read()
-    assert re.findall(r"#include\s+(\S+)", text) == ['"../../include/lsdsort.h"', '"lsd_device.hpp"', '"lsd_host.hpp"']
-    code = re.sub(r"//.*", "", text)
+    assert re.findall(r"#include\s+(\S+)", text) == ['"../../include/lsdsort.h"', '"lsd_device.hpp"', '"lsd_host.hpp"', '"run_tiles.hpp"']
+    unit = re.sub(r"//.*", "", text)
+    header = open(un.HEADER).read()
+    shared = re.sub(r"//.*", "", header)
+    code = unit + shared   # what the unit compiles beside the three files it always had
     assert "asm" not in code
-    # it reaches the sorts through their public device entries, waits for no other workgroup, and clears with kernels only
+    # it reaches the sorts through their public device entries -- each call stands once, in the shared header -- waits for no other
+    # workgroup, and clears with kernels only
     for call in ("lsdsort_keys_device(", "lsdsort_keys64_device(", "lsdsort_check_device(", "lsdsort_wide_check_device("):
-        assert call in code, call
+        assert shared.count(call) == 1 and call not in unit, call
     for word in ("load_status", "store_status", "__hip_atomic", "hipMalloc", "hipMemset", "hipStreamSynchronize", "hipDeviceSynchronize",
                  "atomicAdd", "atomicMin", "atomicMax"):
         assert word not in code, word
-    # the tile of unique.hip, restated: tests/_unique.py's sizes are this unit's edges too
-    k = {name: int(value) for name, value in re.findall(r"constexpr (?:int|uint32_t) (k\w+) = (\d+)u?;", text)}
-    assert (k["kRbkThreads"], k["kRbkThreadKeys"], k["kRbkScanThreads"], k["kRbkMaxGrid"]) == (un.THREADS, un.THREAD_KEYS, un.SCAN_THREADS,
+    # the tile is unique.hip's, out of the header both include: tests/_unique.py's sizes are this unit's edges too
+    k = {name: int(value) for name, value in re.findall(r"constexpr (?:int|uint32_t) (k\w+) = (\d+)u?;", header)}
+    assert (k["kRunThreads"], k["kRunThreadKeys"], k["kRunScanThreads"], k["kRunMaxGrid"]) == (un.THREADS, un.THREAD_KEYS, un.SCAN_THREADS,
                                                                                                un.MAX_GRID)
-    assert "kRbkTile = kRbkThreads * kRbkThreadKeys;" in text and "kRbkScanRound = 4 * kRbkScanThreads;" in text
+    assert "kRunTile = kRunThreads * kRunThreadKeys;" in header and "kRunScanRound = 4 * kRunScanThreads;" in header
+    assert not re.findall(r"constexpr[^;\n]*\bkRun\w+\s*=", text)                  # the unit defines none of them itself
+    # the grid cap the unit has: the grid-stride copy kernel's, and none on the per-tile kernels
+    caps = re.findall(r"grid_for\(([^,()]+),\s*(\w+)\s*,\s*([^()]+?)\)\)", text)
+    assert [cap for _, _, cap in caps] == ["kRunMaxGrid"], caps

@@ -52,13 +52,16 @@ def test_header_ctypes_table_makefile_and_faces_have_the_entries():
 
 def test_the_restated_constants_are_the_units():
     k = un.unit_constants()
-    assert (k["kRleThreads"], k["kRleThreadKeys"], k["kRleScanThreads"], k["kRleMaxGrid"]) == (un.THREADS, un.THREAD_KEYS, un.SCAN_THREADS,
+    assert (k["kRunThreads"], k["kRunThreadKeys"], k["kRunScanThreads"], k["kRunMaxGrid"]) == (un.THREADS, un.THREAD_KEYS, un.SCAN_THREADS,
                                                                                                un.MAX_GRID)
+    header = open(un.HEADER).read()
+    assert "kRunTile = kRunThreads * kRunThreadKeys;" in header and "kRunScanRound = 4 * kRunScanThreads;" in header
+    # the constants are csrc/run_tiles.hpp's: the unit defines none of them itself
     text = open(un.UNIT).read()
-    assert "kRleTile = kRleThreads * kRleThreadKeys;" in text and "kRleScanRound = 4 * kRleScanThreads;" in text
+    assert not re.findall(r"constexpr[^;\n]*\bkRun\w+\s*=", text)
     # the grid cap the unit has: the grid-stride copy kernel's, and none on the per-tile kernels
     caps = re.findall(r"grid_for\(([^,()]+),\s*(\w+)\s*,\s*([^()]+?)\)\)", text)
-    assert [cap for _, _, cap in caps] == ["kRleMaxGrid"], caps                     # the copy kernel's
+    assert [cap for _, _, cap in caps] == ["kRunMaxGrid"], caps                     # the copy kernel's
     assert un.SIZES == (1, 2, 3, 4095, 4096, 4097, 8193, 20487)
 
 
@@ -389,7 +392,7 @@ def test_kernels_no_scratch_no_spill_and_recorded_resources():
     res = kernel_resources("unique.hip")
     names = list(res)
     # the exact kernel set: count and emit per word, emit and copy with and without positions, one scan, one store
-    sets = {"rle_count_kernel": 2, "rle_scan_kernel": 1, "rle_emit_kernel": 4, "rle_store_kernel": 1, "unique_copy_kernel": 4}
+    sets = {"rle_count_kernel": 2, "rle_scan_kernel": 1, "rle_emit_kernel": 4, "run_store_kernel": 1, "unique_copy_kernel": 4}
     for must, times in sets.items():
         assert sum(must in name for name in names) == times, (must, names)
     assert len(names) == sum(sets.values()), names
@@ -402,13 +405,16 @@ def test_kernels_no_scratch_no_spill_and_recorded_resources():
         assert res[name]["lds_bytes"] == w["lds_bytes"], f"{name}: {res[name]['lds_bytes']} B of static LDS, recorded {w['lds_bytes']}"
 
 
-def test_the_unit_includes_three_files_only_and_has_no_inline_assembly():
+def test_the_unit_includes_four_files_only_and_has_no_inline_assembly():
     text = open(un.UNIT).read()
-    assert re.findall(r"#include\s+(\S+)", text) == ['"../../include/lsdsort.h"', '"lsd_device.hpp"', '"lsd_host.hpp"']
-    code = re.sub(r"//.*", "", text)
+    assert re.findall(r"#include\s+(\S+)", text) == ['"../../include/lsdsort.h"', '"lsd_device.hpp"', '"lsd_host.hpp"', '"run_tiles.hpp"']
+    unit = re.sub(r"//.*", "", text)
+    shared = re.sub(r"//.*", "", open(un.HEADER).read())
+    code = unit + shared   # what the unit compiles beside the three files it always had
     assert "asm" not in code
-    # it reaches the sorts through their public device entries, and waits for no other workgroup
+    # it reaches the sorts through their public device entries -- each call stands once, in the shared header -- and waits for no
+    # other workgroup
     for call in ("lsdsort_keys_device(", "lsdsort_keys64_device(", "lsdsort_check_device(", "lsdsort_wide_check_device("):
-        assert call in code, call
+        assert shared.count(call) == 1 and call not in unit, call
     for word in ("load_status", "store_status", "__hip_atomic", "hipMalloc", "hipStreamSynchronize", "hipDeviceSynchronize"):
         assert word not in code, word
