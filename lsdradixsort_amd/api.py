@@ -1,10 +1,30 @@
-"""Host-side mirror of the reference's sort path over the C-ABI (include/lsdsort.h).
+"""The Python face of ``liblsdsort.so`` over the C-ABI (include/lsdsort.h).
 
-Names follow the reference's own (``LSDRadixSort/LSDRadixSort.cu``): ``GPULSDRadixSort``
-(.cu:839), ``BuildHistograms`` (.cu:660), ``LSDRadixSortKernel`` -> ``rank_scatter`` (.cu:795).
-PyTorch is plumbing only: device memory (``torch.int32`` tensors holding the uint32 bit
-patterns) and the current HIP stream.  All computation happens in ``liblsdsort.so``; nothing
-here falls back to PyTorch or the CPU.
+PyTorch is plumbing only: device memory and the current HIP stream.  All computation happens in the library; nothing here
+falls back to PyTorch or the CPU.  The sort path keeps the reference's names (``LSDRadixSort/LSDRadixSort.cu``):
+``GPULSDRadixSort`` (.cu:839), ``BuildHistograms`` (.cu:660), ``LSDRadixSortKernel`` -> ``RankScatter`` (.cu:795).
+
+A map of the file, in its order:
+
+- host-pointer entries (``sort``, ``sort_pairs``);
+- the shared plumbing: ``_dev`` (the tensor check), ``_key_type``, ``_stream`` / ``_on_stream``, ``_workspace`` (the one
+  workspace path, over ``_temp_workspace``), ``_check_fault``, ``_ptr``; then the library's switches;
+- the 32-bit sorts: plain, multi, typed, segmented (``sort_rows``);
+- the 32-bit row selects (``_keys32``, ``_select_code32``, ``_select_outputs``, ``_ranks``): top-k, k-th value, multi-rank,
+  and ``_Rows``, the flatten / restore helper of every torch-shaped ``*_rows`` wrapper; quantiles;
+- the wide sorts (``sort64``) and the 16-bit sort (``sort16``), which share ``_sort_1d``;
+- the 16-bit rows (``_keys16``, ``_logits16``, ``_per_row``, ``_row_out``, ``_fill16``): selects, per-row ranks, the two
+  filters, the draw, the log-probabilities, the row sort;
+- the run units (``_word_keys``, ``_run_outputs``, ``_run_result``, ``_slice_by_count``): run-length, unique, the two reduces;
+- the timed sort, the stage entries and the partitions.
+
+Every device wrapper has the same five steps, in this order:
+
+1. check the arguments (nothing below is reached with a bad one, the library least of all);
+2. allocate the outputs under ``_on_stream(stream)``;
+3. take the workspace from ``_workspace``;
+4. call the entry, through ``check``;
+5. ``_check_fault`` where ``check_fault`` is set and kernels ran at all.
 """
 from __future__ import annotations
 
@@ -84,6 +104,11 @@ def to_host(t) -> np.ndarray:
     return t.detach().cpu().numpy().view(np.uint32)
 
 
+def _dtype_name(dtype) -> str:
+    """``torch.bfloat16`` -> "bfloat16": what the messages call a dtype, and the key-type name of a tensor sorted as what it is."""
+    return str(dtype).replace("torch.", "")
+
+
 def _dev(t, name: str, dtypes=None, dims=None, contiguous: bool = True):
     """The tensor check of every wrapper: ``t`` is a CUDA tensor of one of ``dtypes`` (default: int32, holding uint32 bit
     patterns), with one of ``dims`` dimensions where that is given, and contiguous -- except where the wrapper sorts a copy it
@@ -93,7 +118,7 @@ def _dev(t, name: str, dtypes=None, dims=None, contiguous: bool = True):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in dtypes and (t.is_contiguous() or not contiguous)
             and (dims is None or t.dim() in dims)):
         shape = "" if dims is None else " or ".join(f"{d}-D" for d in dims) + " "
-        kinds = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+        kinds = " or ".join(_dtype_name(d) for d in dtypes)
         raise TypeError(f"{name}: a {'contiguous ' if contiguous else ''}{shape}{kinds} CUDA tensor")
     return t
 
@@ -126,13 +151,33 @@ def _on_stream(stream):
 
 
 def _temp_workspace(nbytes: int, device, stream):
-    """The one place a workspace tensor is made.  A wrapper returns while its kernels are still running, so a temporary
-    workspace must belong to THEIR stream: allocated under ``stream`` (where that is not torch's current stream, ``None``), the
-    caching allocator orders the block's reuse after the sort's kernels instead of after whatever the current stream is doing."""
+    """The one place a workspace tensor is made; ``_workspace`` and ``alloc_workspace`` are its only callers.  A wrapper returns
+    while its kernels are still running, so a temporary workspace must belong to THEIR stream: allocated under ``stream`` (where
+    that is not torch's current stream, ``None``), the caching allocator orders the block's reuse after the sort's kernels instead
+    of after whatever the current stream is doing."""
     torch = _torch()
     with _on_stream(stream):
         # torch's caching allocator returns 512-byte aligned blocks; the ABI needs 256.
         return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+
+
+def _workspace(workspace, entry: str, args, device, stream, tail: str = "too many keys or rows", zero_ok: bool = False,
+               always: bool = False, status: int = errors.LSDSORT_ERR_TOO_LARGE):
+    """The workspace step of every wrapper: the caller's ``workspace`` where one is given, else a temporary one of the size the
+    unit's own ``entry`` (a ``*_workspace_bytes`` name) gives for ``args``, on ``device`` and under ``stream``.  A figure of 0 says
+    that the library refuses the shape: ``LsdsortError(status, entry, tail)``, unless ``zero_ok`` (nothing will run).  ``always``:
+    the figure is asked for, and checked, even when a workspace is given (the wide sorts)."""
+    if workspace is not None and not always:
+        return workspace
+    nbytes = int(getattr(lib(), entry)(*args))
+    if nbytes == 0 and not zero_ok:
+        raise errors.LsdsortError(status, entry, tail)
+    return workspace if workspace is not None else _temp_workspace(nbytes, device, stream)
+
+
+def _ptr(t, live=True):
+    """The pointer argument of an optional tensor: ``None`` (NULL) without one -- or, for the run units, without keys."""
+    return t.data_ptr() if t is not None and live else None
 
 
 def _check_fault(workspace, stream, entry: str = "lsdsort_check_device", *shape, quiet: bool = False) -> int:
@@ -312,11 +357,8 @@ def GPUSortSegmented(d_keys, d_offsets, d_vals=None, key_type: str = "uint32", d
     if pairs:
         _payload(d_vals, n)
     code = _key_type(key_type, KEY_TYPES_32)
-    if workspace is None:
-        nbytes = segmented_workspace_bytes(n, segs, pairs)
-        if nbytes == 0 and n > 0 and segs > 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_segmented_workspace_bytes", "too many keys or segments")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    workspace = _workspace(workspace, "lsdsort_segmented_workspace_bytes", (n, segs, int(pairs)), d_keys.device, stream,
+                           "too many keys or segments", zero_ok=not (n > 0 and segs > 0))
     check(lib().lsdsort_segmented_device(d_keys.data_ptr(), d_vals.data_ptr() if pairs else None, d_offsets.data_ptr(), segs, n,
                                          code, int(bool(descending)), workspace.data_ptr(), workspace.numel(), _stream(stream)),
           "lsdsort_segmented_device")
@@ -343,6 +385,78 @@ def sort_rows(x, descending: bool = False, return_indices: bool = False, stream=
     return out
 
 
+# ------------------------------------------------------------------------------ row selects, and what every row wrapper shares
+def _rows_cols(d_keys):
+    """(rows, cols) of a row entry's keys: a 1-D tensor is one row."""
+    return (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
+
+
+def _keys32(d_keys):
+    """The tensor check of the 32-bit row selects -> (rows, cols).  The key-type code is ``_select_code32``'s, a step of its
+    own, because the three wrappers check k, the rank or the ranks between the two."""
+    torch = _torch()
+    _dev(d_keys, "d_keys", (torch.int32, torch.float32), dims=(1, 2))
+    return _rows_cols(d_keys)
+
+
+def _select_code32(d_keys, key_type: str, own_type_only: bool) -> int:
+    """The key-type code of the 32-bit row selects.  ``own_type_only``: ``GPUKth`` and ``GPUKthMulti`` refuse a float32 tensor
+    with another ``key_type``; ``GPUTopK`` takes it and compares the bits as it is told.  The difference is as old as the three
+    entries and callers may rely on either side of it: it is kept here, not settled."""
+    code = _key_type(key_type, KEY_TYPES_32)
+    if own_type_only and d_keys.dtype == _torch().float32 and key_type != "float32":
+        raise TypeError('a float32 tensor selects with key_type="float32" only (an int32 tensor holds any of the three bit patterns)')
+    return code
+
+
+def _select_outputs(d_keys, rows: int, tail: tuple, return_indices: bool, stream):
+    """``(values, indices)`` of a row select: ``tail`` entries per row -- ``[rows] + tail``, for 1-D keys ``tail`` alone --, values
+    in the keys' dtype, int32 positions or ``None``.  The outputs, like a temporary workspace, belong to the stream the kernels
+    run on."""
+    torch = _torch()
+    shape = tail if d_keys.dim() == 1 else (rows,) + tail
+    with _on_stream(stream):
+        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
+        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
+    return values, indices
+
+
+def _ranks(ranks, cols: int) -> list:
+    """The ranks of a multi-rank select: a sequence of 1 .. ``LSDSORT_KTH_MAX_RANKS`` ints, each within the row."""
+    try:
+        ranks = [int(r) for r in ranks]
+    except TypeError:
+        raise ValueError("ranks: a sequence of ints") from None
+    if not 1 <= len(ranks) <= errors.LSDSORT_KTH_MAX_RANKS:
+        raise ValueError(f"ranks: 1 .. {errors.LSDSORT_KTH_MAX_RANKS} of them, got {len(ranks)}")
+    if not all(0 <= r < cols for r in ranks):
+        raise ValueError("every rank must be within 0 .. the row length - 1")
+    return ranks
+
+
+class _Rows:
+    """What every torch-shaped ``*_rows`` wrapper does with ``x``: the tensor check (one of ``dtypes``, any strides unless
+    ``contiguous``), at least one dimension, and the rows of the last one -- ``cols``, the leading shape ``lead``, and the dtype's
+    name as ``key_type``.  ``flat()`` is the ``[rows, cols]`` tensor a ``GPU*`` wrapper takes -- a copy where ``x`` is strided:
+    call it under the stream --, ``restore`` gives a ``[rows, ...]`` result the leading shape back."""
+
+    def __init__(self, x, dtypes, contiguous: bool = False):
+        _dev(x, "x", dtypes, contiguous=contiguous)
+        if x.dim() == 0:
+            raise TypeError("x: at least one dimension")
+        self.x, self.cols, self.lead, self.key_type = x, x.shape[-1], tuple(x.shape[:-1]), _dtype_name(x.dtype)
+
+    @property
+    def rows(self) -> int:
+        return int(np.prod(self.lead, dtype=np.int64))
+
+    def flat(self, copy: bool = True):
+        return (self.x.contiguous() if copy else self.x).view(-1, self.cols)
+
+    def restore(self, t, *tail):
+        return t.view(self.lead + tail)
+
+
 def topk_workspace_bytes(rows: int, cols: int, k: int) -> int:
     """Bytes of device workspace ``GPUTopK`` needs for the ``k`` best of each of ``rows`` rows of ``cols`` keys."""
     return int(lib().lsdsort_topk_workspace_bytes(rows, cols, k))
@@ -355,28 +469,37 @@ def GPUTopK(d_keys, k: int, key_type: str = "uint32", largest: bool = True, retu
     ``(values, indices)`` -- ``[rows, k]`` (``[k]`` for 1-D input), best first, ``indices`` the int32 positions within the row,
     or ``None`` without ``return_indices`` -- exactly the first ``k`` columns of the rows' stable sort: equal keys in position
     order.  ``d_keys`` is only read.  Stream-ordered; the rows are not sorted (a radix select, then a sort of the winners)."""
-    torch = _torch()
-    _dev(d_keys, "d_keys", (torch.int32, torch.float32), dims=(1, 2))
-    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
+    rows, cols = _keys32(d_keys)
     k = int(k)
     if not 0 <= k <= cols:
         raise ValueError("k must be within 0 .. the row length")
-    code = _key_type(key_type, KEY_TYPES_32)
-    shape = (k,) if d_keys.dim() == 1 else (rows, k)
-    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
-        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
-        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
-    if workspace is None:
-        nbytes = topk_workspace_bytes(rows, cols, k)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_topk_workspace_bytes", "too many keys or rows")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
-    check(lib().lsdsort_topk_device(d_keys.data_ptr(), rows, cols, k, code, int(bool(largest)), values.data_ptr(),
-                                    indices.data_ptr() if return_indices else None, workspace.data_ptr(), workspace.numel(),
-                                    _stream(stream)), "lsdsort_topk_device")
+    code = _select_code32(d_keys, key_type, own_type_only=False)
+    values, indices = _select_outputs(d_keys, rows, (k,), return_indices, stream)
+    workspace = _workspace(workspace, "lsdsort_topk_workspace_bytes", (rows, cols, k), d_keys.device, stream)
+    check(lib().lsdsort_topk_device(d_keys.data_ptr(), rows, cols, k, code, int(bool(largest)), values.data_ptr(), _ptr(indices),
+                                    workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_topk_device")
     if check_fault and rows and cols and k:
         _check_fault(workspace, stream)
     return values, indices
+
+
+def _topk_rows(x, k, largest, stream, dtypes, select):
+    """The body of ``topk_rows`` and ``topk16_rows``; ``select``: ``GPUTopK`` or ``GPUTopK16``."""
+    r = _Rows(x, dtypes)
+    with _on_stream(stream):
+        values, indices = select(r.flat(), k, key_type=r.key_type, largest=largest, stream=stream)
+        return r.restore(values, k), r.restore(indices, k).to(_torch().int64)
+
+
+def _kthvalue_rows(x, k, stream, dtypes, select):
+    """The body of ``kthvalue_rows`` and ``kthvalue16_rows``; ``select``: ``GPUKth`` or ``GPUKth16``."""
+    r = _Rows(x, dtypes)
+    k = int(k)
+    if not 1 <= k <= r.cols:
+        raise ValueError("k must be within 1 .. the row length")
+    with _on_stream(stream):
+        values, indices = select(r.flat(), k - 1, key_type=r.key_type, stream=stream)
+        return r.restore(values), r.restore(indices).to(_torch().int64)
 
 
 def topk_rows(x, k: int, largest: bool = True, stream=None):
@@ -384,15 +507,7 @@ def topk_rows(x, k: int, largest: bool = True, stream=None):
     dimensions: ``(values, int64 indices)``.  float32 follows IEEE total order, not torch's: NaNs by sign at the two ends
     (+NaN above +inf, -NaN below -inf) and -0.0 below +0.0.  Among equal keys the lower position comes first, always."""
     torch = _torch()
-    _dev(x, "x", (torch.int32, torch.float32), contiguous=False)
-    if x.dim() == 0:
-        raise TypeError("x: at least one dimension")
-    cols = x.shape[-1]
-    with _on_stream(stream):
-        flat = x.contiguous().view(-1, cols)
-        values, indices = GPUTopK(flat, k, key_type="int32" if x.dtype == torch.int32 else "float32", largest=largest, stream=stream)
-        lead = tuple(x.shape[:-1])
-        return values.view(lead + (k,)), indices.view(lead + (k,)).to(torch.int64)
+    return _topk_rows(x, k, largest, stream, (torch.int32, torch.float32), GPUTopK)
 
 
 def kth_workspace_bytes(rows: int, cols: int) -> int:
@@ -409,27 +524,15 @@ def GPUKth(d_keys, rank: int, key_type: str = "uint32", largest: bool = False, r
     ``rank`` of ``GPUTopK(d_keys, rank + 1, ...)``: among equal keys the stable sort's position, on every run.  ``d_keys`` is only
     read.  A float32 tensor goes with ``key_type="float32"`` only; an int32 tensor holds the bit patterns of any of the three.
     Stream-ordered; the rows are not sorted and no winner is written (a radix select, then a locate)."""
-    torch = _torch()
-    _dev(d_keys, "d_keys", (torch.int32, torch.float32), dims=(1, 2))
-    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
+    rows, cols = _keys32(d_keys)
     rank = int(rank)
     if not 0 <= rank < cols:
         raise ValueError("rank must be within 0 .. the row length - 1")
-    code = _key_type(key_type, KEY_TYPES_32)
-    if d_keys.dtype == torch.float32 and key_type != "float32":
-        raise TypeError('a float32 tensor selects with key_type="float32" only (an int32 tensor holds any of the three bit patterns)')
-    shape = () if d_keys.dim() == 1 else (rows,)
-    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
-        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
-        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
-    if workspace is None:
-        nbytes = kth_workspace_bytes(rows, cols)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_kth_workspace_bytes", "too many keys or rows")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
-    check(lib().lsdsort_kth_device(d_keys.data_ptr(), rows, cols, rank, code, int(bool(largest)), values.data_ptr(),
-                                   indices.data_ptr() if return_indices else None, workspace.data_ptr(), workspace.numel(),
-                                   _stream(stream)), "lsdsort_kth_device")
+    code = _select_code32(d_keys, key_type, own_type_only=True)
+    values, indices = _select_outputs(d_keys, rows, (), return_indices, stream)
+    workspace = _workspace(workspace, "lsdsort_kth_workspace_bytes", (rows, cols), d_keys.device, stream)
+    check(lib().lsdsort_kth_device(d_keys.data_ptr(), rows, cols, rank, code, int(bool(largest)), values.data_ptr(), _ptr(indices),
+                                   workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_kth_device")
     if check_fault and rows and cols:
         _check_fault(workspace, stream)
     return values, indices
@@ -442,18 +545,7 @@ def kthvalue_rows(x, k: int, stream=None):
     ends (+NaN above +inf, -NaN below -inf), and -0.0 below +0.0.  The index is the stable sort's (among equal keys the one the
     stable sort puts at that rank), where torch leaves it unspecified among ties."""
     torch = _torch()
-    _dev(x, "x", (torch.int32, torch.float32), contiguous=False)
-    if x.dim() == 0:
-        raise TypeError("x: at least one dimension")
-    cols = x.shape[-1]
-    k = int(k)
-    if not 1 <= k <= cols:
-        raise ValueError("k must be within 1 .. the row length")
-    with _on_stream(stream):
-        flat = x.contiguous().view(-1, cols)
-        values, indices = GPUKth(flat, k - 1, key_type="int32" if x.dtype == torch.int32 else "float32", stream=stream)
-        lead = tuple(x.shape[:-1])
-        return values.view(lead), indices.view(lead).to(torch.int64)
+    return _kthvalue_rows(x, k, stream, (torch.int32, torch.float32), GPUKth)
 
 
 def median_rows(x, stream=None):
@@ -482,33 +574,15 @@ def GPUKthMulti(d_keys, ranks, key_type: str = "uint32", largest: bool = False, 
     exactly ``GPUKth(d_keys, ranks[j], ...)``, values and int32 positions bit for bit; ``indices`` is ``None`` without
     ``return_indices``.  ``d_keys`` is only read, and read once for all ranks where ``GPUKth`` reads it once per rank.  The ranks
     are host values: they are fixed in a captured graph."""
-    torch = _torch()
-    _dev(d_keys, "d_keys", (torch.int32, torch.float32), dims=(1, 2))
-    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
-    try:
-        ranks = [int(r) for r in ranks]
-    except TypeError:
-        raise ValueError("ranks: a sequence of ints") from None
-    if not 1 <= len(ranks) <= errors.LSDSORT_KTH_MAX_RANKS:
-        raise ValueError(f"ranks: 1 .. {errors.LSDSORT_KTH_MAX_RANKS} of them, got {len(ranks)}")
-    if not all(0 <= r < cols for r in ranks):
-        raise ValueError("every rank must be within 0 .. the row length - 1")
-    code = _key_type(key_type, KEY_TYPES_32)
-    if d_keys.dtype == torch.float32 and key_type != "float32":
-        raise TypeError('a float32 tensor selects with key_type="float32" only (an int32 tensor holds any of the three bit patterns)')
+    rows, cols = _keys32(d_keys)
+    ranks = _ranks(ranks, cols)
+    code = _select_code32(d_keys, key_type, own_type_only=True)
     m = len(ranks)
-    shape = (m,) if d_keys.dim() == 1 else (rows, m)
-    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
-        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
-        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
-    if workspace is None:
-        nbytes = kth_multi_workspace_bytes(rows, cols, m)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_kth_multi_workspace_bytes", "too many keys or rows")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    values, indices = _select_outputs(d_keys, rows, (m,), return_indices, stream)
+    workspace = _workspace(workspace, "lsdsort_kth_multi_workspace_bytes", (rows, cols, m), d_keys.device, stream)
     check(lib().lsdsort_kth_multi_device(d_keys.data_ptr(), rows, cols, (ctypes.c_size_t * m)(*ranks), m, code, int(bool(largest)),
-                                         values.data_ptr(), indices.data_ptr() if return_indices else None, workspace.data_ptr(),
-                                         workspace.numel(), _stream(stream)), "lsdsort_kth_multi_device")
+                                         values.data_ptr(), _ptr(indices), workspace.data_ptr(), workspace.numel(), _stream(stream)),
+          "lsdsort_kth_multi_device")
     if check_fault and rows and cols:
         _check_fault(workspace, stream)
     return values, indices
@@ -565,29 +639,23 @@ def quantile_rows(x, q, interpolation: str = "linear", stream=None):
     mean more than one read of ``x``.
     float32 follows IEEE total order, not torch's: a row with NaNs does NOT propagate NaN as ``torch.quantile`` does -- NaNs sort
     by sign at the two ends (+NaN above +inf, -NaN below -inf), and -0.0 below +0.0."""
-    torch = _torch()
-    _dev(x, "x", (torch.float32,), contiguous=False)
-
     def select(flat, ranks):
         return GPUKthMulti(flat, ranks, key_type="float32", return_indices=False, stream=stream)[0]
 
-    return _quantile_of(x, q, interpolation, stream, select)
+    return _quantile_of(x, (_torch().float32,), q, interpolation, stream, select)
 
 
-def _quantile_of(x, q, interpolation, stream, select):
+def _quantile_of(x, dtypes, q, interpolation, stream, select):
     """What ``quantile_rows`` and ``quantile16_rows`` share: ``select(flat, ranks)`` -> the float32 ``[rows, len(ranks)]`` order
     statistics of at most ``LSDSORT_KTH_MAX_RANKS`` distinct ranks; the rest is ``quantile_ranks`` and torch's own arithmetic."""
     torch = _torch()
-    if x.dim() == 0:
-        raise TypeError("x: at least one dimension")
-    cols = x.shape[-1]
-    below, above, weights, scalar = quantile_ranks(q, cols, interpolation)
+    r = _Rows(x, dtypes)
+    below, above, weights, scalar = quantile_ranks(q, r.cols, interpolation)
     distinct = sorted(set(below) | set(above or ()))
     slot = {rank: i for i, rank in enumerate(distinct)}
     group = errors.LSDSORT_KTH_MAX_RANKS
-    lead = tuple(x.shape[:-1])
     with _on_stream(stream):
-        flat = x.contiguous().view(-1, cols)
+        flat = r.flat()
         parts = [select(flat, distinct[at:at + group]) for at in range(0, len(distinct), group)]
         stats = torch.cat(parts, dim=1) if parts else flat.new_empty((flat.shape[0], 0), dtype=torch.float32)   # [rows, distinct ranks]
 
@@ -597,7 +665,7 @@ def _quantile_of(x, q, interpolation, stream, select):
         values = take(below)
         if above is not None:
             values = torch.lerp(values, take(above), weights.to(x.device, non_blocking=True))
-        values = values.view(lead + (len(below),)).movedim(-1, 0)
+        values = r.restore(values, len(below)).movedim(-1, 0)
         return values[0] if scalar else values
 
 
@@ -623,11 +691,8 @@ def GPUSortWide(d_keys, d_vals=None, r: int = 8, workspace=None, stream=None, ch
     if kb == 32 and (key_type != "uint64" or descending):
         raise ValueError("32-bit keys with 64-bit payloads sort as uint32, ascending, only")
     n = d_keys.numel()
-    need = int(lib().lsdsort_wide_workspace_bytes(n, r, kb, vb))
-    if need == 0:
-        raise errors.LsdsortError(errors.LSDSORT_ERR_INVALID_ARG, "lsdsort_wide_workspace_bytes", "bad (n, radix_bits)")
-    if workspace is None:
-        workspace = _temp_workspace(need, d_keys.device, stream)
+    workspace = _workspace(workspace, "lsdsort_wide_workspace_bytes", (n, r, kb, vb), d_keys.device, stream, "bad (n, radix_bits)",
+                           always=True, status=errors.LSDSORT_ERR_INVALID_ARG)
     if kb == 64:
         st = lib().lsdsort_keys64_device(d_keys.data_ptr(), d_vals.data_ptr() if vb else None, vb, workspace.data_ptr(),
                                          workspace.numel(), n, r, code, int(bool(descending)), _stream(stream))
@@ -647,15 +712,77 @@ def sort64(x, descending: bool = False, return_indices: bool = False, stream=Non
     positions as payload, so equal keys keep their input order in either direction).  float64 follows IEEE total order, not
     torch's: NaNs by sign at the two ends (+NaN above +inf, -NaN below -inf) and -0.0 below +0.0."""
     torch = _torch()
-    _dev(x, "x", (torch.int64, torch.float64), dims=(1,), contiguous=False)
-    key_type = "int64" if x.dtype == torch.int64 else "float64"
+    return _sort_1d(x, (torch.int64, torch.float64), return_indices, stream,
+                    lambda out, idx, key_type: GPUSortWide(out, idx, key_type=key_type, descending=descending, stream=stream))
+
+
+def _sort_1d(x, dtypes, return_indices: bool, stream, sort):
+    """The body of ``sort64`` and ``sort16``: ``sort(out, idx, key_type)`` sorts the contiguous copy ``out`` of ``x`` in place as
+    the dtype's own key type, with the int32 positions ``idx`` (or ``None``) as its payload."""
+    torch = _torch()
+    _dev(x, "x", dtypes, dims=(1,), contiguous=False)
     with _on_stream(stream):
         out = x.clone(memory_format=torch.contiguous_format)
         idx = torch.arange(x.numel(), dtype=torch.int32, device=x.device) if return_indices else None
-        GPUSortWide(out, idx, key_type=key_type, descending=descending, stream=stream)
+        sort(out, idx, _dtype_name(x.dtype))
         if return_indices:
             return out, idx.to(torch.int64)
     return out
+
+
+# ------------------------------------------------------------------------------ 16-bit keys
+_FITS16 = {"int16": ("uint16", "int16"), "float16": ("float16",), "bfloat16": ("bfloat16",)}   # dtype -> the key types it pairs with
+
+
+def _keys16(d_keys, key_type: str, verb: str = "selects", dims=(1, 2)):
+    """The tensor and key-type checks of every 16-bit entry -> (code, rows, cols); ``verb``: what the message says the tensor
+    does with its key type; ``dims``: the dimensions the entry takes (the plain sort: one)."""
+    torch = _torch()
+    _dev(d_keys, "d_keys", (torch.int16, torch.float16, torch.bfloat16), dims=dims)
+    code = _key_type(key_type, KEY_TYPES_16)
+    fits = _FITS16[_dtype_name(d_keys.dtype)]
+    if key_type not in fits:
+        raise TypeError(f"a {_dtype_name(d_keys.dtype)} tensor {verb} with key_type " + " or ".join(f'"{k}"' for k in fits))
+    rows, cols = _rows_cols(d_keys)
+    return code, rows, cols
+
+
+def _logits16(d_keys, key_type: str, verb: str):
+    """``_keys16`` for the units that weigh logits (the top-p filter, the draw, the log-probabilities): the float types only."""
+    torch = _torch()
+    _dev(d_keys, "d_keys", (torch.float16, torch.bfloat16), dims=(1, 2))
+    if key_type not in ("float16", "bfloat16"):
+        raise ValueError(f'key_type: "float16" or "bfloat16", got {key_type!r}')
+    return _keys16(d_keys, key_type, verb)
+
+
+def _per_row(t, name: str, rows: int, dtype, dims=None, optional: bool = False):
+    """A per-row device argument or output: a contiguous CUDA tensor of ``dtype`` with one entry per row (``dims``: of that many
+    dimensions); ``optional``: or ``None``."""
+    if t is None and optional:
+        return None
+    _dev(t, name, (dtype,), dims=dims)
+    if t.numel() != rows:
+        raise ValueError(f"{name}: one entry per row ({rows}), got {t.numel()}")
+    return t
+
+
+def _row_out(out, d_keys):
+    """``out`` of the entries that write rows like their keys': ``None``, or a contiguous CUDA tensor of the keys' dtype and shape."""
+    if out is not None:
+        _dev(out, "out", (d_keys.dtype,), dims=(d_keys.dim(),))
+        if out.shape != d_keys.shape:
+            raise ValueError("out: the shape of d_keys")
+    return out
+
+
+def _fill16(fill, key_type: str, largest: bool) -> int:
+    """``fill`` of the two filters: a 16-bit word; ``None``: the value that ranks last in the requested order."""
+    if fill is None:
+        fill = _worst_bits16(key_type, largest)
+    if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 0xFFFF:
+        raise ValueError("fill: a 16-bit word, an int within 0 .. 0xFFFF")
+    return fill
 
 
 def keys16_workspace_bytes(n: int, pairs: bool = False) -> int:
@@ -676,23 +803,13 @@ def GPUSort16(d_keys, key_type: str = "int16", descending: bool = False, d_vals=
     bfloat16 CUDA tensor whose 16 bits compare as ``key_type``: "uint16" / "int16" for an int16 tensor ("uint16" sorts its bit
     patterns), "float16" / "bfloat16" for the tensor of that dtype (IEEE total order: NaNs by sign at the two ends, -0.0 below
     +0.0).  ``d_vals``: optional int32 payloads permuted with the keys, stable in either direction."""
-    torch = _torch()
-    _dev(d_keys, "d_keys", (torch.int16, torch.float16, torch.bfloat16), dims=(1,))
-    code = _key_type(key_type, KEY_TYPES_16)
-    fits = {torch.int16: ("uint16", "int16"), torch.float16: ("float16",), torch.bfloat16: ("bfloat16",)}[d_keys.dtype]
-    if key_type not in fits:
-        raise TypeError(f"a {str(d_keys.dtype).replace('torch.', '')} tensor sorts with key_type " + " or ".join(f'"{k}"' for k in fits))
-    n = d_keys.numel()
+    code, _, n = _keys16(d_keys, key_type, "sorts", dims=(1,))
     pairs = d_vals is not None
     if pairs:
         _payload(d_vals, n)
-    if workspace is None:
-        nbytes = keys16_workspace_bytes(n, pairs)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_keys16_workspace_bytes", "too many keys")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
-    check(lib().lsdsort_keys16_device(d_keys.data_ptr(), d_vals.data_ptr() if pairs else None, workspace.data_ptr(),
-                                      workspace.numel(), n, code, int(bool(descending)), _stream(stream)), "lsdsort_keys16_device")
+    workspace = _workspace(workspace, "lsdsort_keys16_workspace_bytes", (n, int(pairs)), d_keys.device, stream, "too many keys")
+    check(lib().lsdsort_keys16_device(d_keys.data_ptr(), _ptr(d_vals), workspace.data_ptr(), workspace.numel(), n, code,
+                                      int(bool(descending)), _stream(stream)), "lsdsort_keys16_device")
     if check_fault and n:
         _check_fault(workspace, stream, "lsdsort_keys16_check_device", n, int(pairs))
     return d_keys if not pairs else (d_keys, d_vals)
@@ -704,15 +821,8 @@ def sort16(x, descending: bool = False, return_indices: bool = False, stream=Non
     ``return_indices`` also the int64 positions (the positions ride as payloads, so equal keys keep their input order in either
     direction).  The float types follow IEEE total order, not torch's: NaNs by sign at the two ends and -0.0 below +0.0."""
     torch = _torch()
-    _dev(x, "x", (torch.int16, torch.float16, torch.bfloat16), dims=(1,), contiguous=False)
-    key_type = str(x.dtype).replace("torch.", "")
-    with _on_stream(stream):
-        out = x.clone(memory_format=torch.contiguous_format)
-        idx = torch.arange(x.numel(), dtype=torch.int32, device=x.device) if return_indices else None
-        GPUSort16(out, key_type=key_type, descending=descending, d_vals=idx, stream=stream)
-        if return_indices:
-            return out, idx.to(torch.int64)
-    return out
+    return _sort_1d(x, (torch.int16, torch.float16, torch.bfloat16), return_indices, stream,
+                    lambda out, idx, key_type: GPUSort16(out, key_type=key_type, descending=descending, d_vals=idx, stream=stream))
 
 
 def topk16_workspace_bytes(rows: int, cols: int, k: int) -> int:
@@ -729,28 +839,14 @@ def GPUTopK16(d_keys, k: int, key_type: str = "int16", largest: bool = True, ret
     row, or ``None`` without ``return_indices`` -- exactly the first ``k`` columns of the rows' stable sort: equal keys in position
     order.  ``d_keys`` is only read.  Stream-ordered; the rows are not sorted (a radix select of at most two digit levels, then a
     sort of the winners)."""
-    torch = _torch()
-    _dev(d_keys, "d_keys", (torch.int16, torch.float16, torch.bfloat16), dims=(1, 2))
-    code = _key_type(key_type, KEY_TYPES_16)
-    fits = {torch.int16: ("uint16", "int16"), torch.float16: ("float16",), torch.bfloat16: ("bfloat16",)}[d_keys.dtype]
-    if key_type not in fits:
-        raise TypeError(f"a {str(d_keys.dtype).replace('torch.', '')} tensor selects with key_type " + " or ".join(f'"{k}"' for k in fits))
-    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
+    code, rows, cols = _keys16(d_keys, key_type)
     k = int(k)
     if not 0 <= k <= cols:
         raise ValueError("k must be within 0 .. the row length")
-    shape = (k,) if d_keys.dim() == 1 else (rows, k)
-    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
-        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
-        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
-    if workspace is None:
-        nbytes = topk16_workspace_bytes(rows, cols, k)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_topk16_workspace_bytes", "too many keys or rows")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
-    check(lib().lsdsort_topk16_device(d_keys.data_ptr(), rows, cols, k, code, int(bool(largest)), values.data_ptr(),
-                                      indices.data_ptr() if return_indices else None, workspace.data_ptr(), workspace.numel(),
-                                      _stream(stream)), "lsdsort_topk16_device")
+    values, indices = _select_outputs(d_keys, rows, (k,), return_indices, stream)
+    workspace = _workspace(workspace, "lsdsort_topk16_workspace_bytes", (rows, cols, k), d_keys.device, stream)
+    check(lib().lsdsort_topk16_device(d_keys.data_ptr(), rows, cols, k, code, int(bool(largest)), values.data_ptr(), _ptr(indices),
+                                      workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_topk16_device")
     if check_fault and rows and cols and k:
         _check_fault(workspace, stream)
     return values, indices
@@ -762,15 +858,7 @@ def topk16_rows(x, k: int, largest: bool = True, stream=None):
     order, not torch's: NaNs by sign at the two ends (+NaN above +inf, -NaN below -inf) and -0.0 below +0.0.  Among equal keys the
     lower position comes first, always."""
     torch = _torch()
-    _dev(x, "x", (torch.int16, torch.float16, torch.bfloat16), contiguous=False)
-    if x.dim() == 0:
-        raise TypeError("x: at least one dimension")
-    cols = x.shape[-1]
-    with _on_stream(stream):
-        flat = x.contiguous().view(-1, cols)
-        values, indices = GPUTopK16(flat, k, key_type=str(x.dtype).replace("torch.", ""), largest=largest, stream=stream)
-        lead = tuple(x.shape[:-1])
-        return values.view(lead + (k,)), indices.view(lead + (k,)).to(torch.int64)
+    return _topk_rows(x, k, largest, stream, (torch.int16, torch.float16, torch.bfloat16), GPUTopK16)
 
 
 def kth16_workspace_bytes(rows: int, cols: int) -> int:
@@ -789,28 +877,14 @@ def GPUKth16(d_keys, rank: int, key_type: str = "int16", largest: bool = False, 
     exactly column ``rank`` of ``GPUTopK16(d_keys, rank + 1, ...)``: among equal keys the stable sort's position, on every run.
     ``d_keys`` is only read and never widened.  Stream-ordered; the rows are not sorted and no winner is written (a radix select of
     at most two digit levels, then a locate; without indices a row above 16384 keys needs no locate)."""
-    torch = _torch()
-    _dev(d_keys, "d_keys", (torch.int16, torch.float16, torch.bfloat16), dims=(1, 2))
-    code = _key_type(key_type, KEY_TYPES_16)
-    fits = {torch.int16: ("uint16", "int16"), torch.float16: ("float16",), torch.bfloat16: ("bfloat16",)}[d_keys.dtype]
-    if key_type not in fits:
-        raise TypeError(f"a {str(d_keys.dtype).replace('torch.', '')} tensor selects with key_type " + " or ".join(f'"{k}"' for k in fits))
-    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
+    code, rows, cols = _keys16(d_keys, key_type)
     rank = int(rank)
     if not 0 <= rank < cols:
         raise ValueError("rank must be within 0 .. the row length - 1")
-    shape = () if d_keys.dim() == 1 else (rows,)
-    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
-        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
-        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
-    if workspace is None:
-        nbytes = kth16_workspace_bytes(rows, cols)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_kth16_workspace_bytes", "too many keys or rows")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
-    check(lib().lsdsort_kth16_device(d_keys.data_ptr(), rows, cols, rank, code, int(bool(largest)), values.data_ptr(),
-                                     indices.data_ptr() if return_indices else None, workspace.data_ptr(), workspace.numel(),
-                                     _stream(stream)), "lsdsort_kth16_device")
+    values, indices = _select_outputs(d_keys, rows, (), return_indices, stream)
+    workspace = _workspace(workspace, "lsdsort_kth16_workspace_bytes", (rows, cols), d_keys.device, stream)
+    check(lib().lsdsort_kth16_device(d_keys.data_ptr(), rows, cols, rank, code, int(bool(largest)), values.data_ptr(), _ptr(indices),
+                                     workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_kth16_device")
     if check_fault and rows and cols:
         _check_fault(workspace, stream)
     return values, indices
@@ -823,18 +897,7 @@ def kthvalue16_rows(x, k: int, stream=None):
     ``torch.median`` do -- NaNs sort by sign at the two ends (+NaN above +inf, -NaN below -inf), and -0.0 below +0.0.  The index is
     the stable sort's (among equal keys the one the stable sort puts at that rank), where torch leaves it unspecified among ties."""
     torch = _torch()
-    _dev(x, "x", (torch.int16, torch.float16, torch.bfloat16), contiguous=False)
-    if x.dim() == 0:
-        raise TypeError("x: at least one dimension")
-    cols = x.shape[-1]
-    k = int(k)
-    if not 1 <= k <= cols:
-        raise ValueError("k must be within 1 .. the row length")
-    with _on_stream(stream):
-        flat = x.contiguous().view(-1, cols)
-        values, indices = GPUKth16(flat, k - 1, key_type=str(x.dtype).replace("torch.", ""), stream=stream)
-        lead = tuple(x.shape[:-1])
-        return values.view(lead), indices.view(lead).to(torch.int64)
+    return _kthvalue_rows(x, k, stream, (torch.int16, torch.float16, torch.bfloat16), GPUKth16)
 
 
 def median16_rows(x, stream=None):
@@ -864,34 +927,14 @@ def GPUKth16Multi(d_keys, ranks, key_type: str = "int16", largest: bool = False,
     values in the input's dtype and int32 positions bit for bit; ``indices`` is ``None`` without ``return_indices``.  ``d_keys`` is
     only read and never widened, and read once for all ranks where ``GPUKth16`` reads it once per rank; without indices a row above
     16384 keys is read twice, whatever the number of ranks.  The ranks are host values: they are fixed in a captured graph."""
-    torch = _torch()
-    _dev(d_keys, "d_keys", (torch.int16, torch.float16, torch.bfloat16), dims=(1, 2))
-    code = _key_type(key_type, KEY_TYPES_16)
-    fits = {torch.int16: ("uint16", "int16"), torch.float16: ("float16",), torch.bfloat16: ("bfloat16",)}[d_keys.dtype]
-    if key_type not in fits:
-        raise TypeError(f"a {str(d_keys.dtype).replace('torch.', '')} tensor selects with key_type " + " or ".join(f'"{k}"' for k in fits))
-    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
-    try:
-        ranks = [int(r) for r in ranks]
-    except TypeError:
-        raise ValueError("ranks: a sequence of ints") from None
-    if not 1 <= len(ranks) <= errors.LSDSORT_KTH_MAX_RANKS:
-        raise ValueError(f"ranks: 1 .. {errors.LSDSORT_KTH_MAX_RANKS} of them, got {len(ranks)}")
-    if not all(0 <= r < cols for r in ranks):
-        raise ValueError("every rank must be within 0 .. the row length - 1")
+    code, rows, cols = _keys16(d_keys, key_type)
+    ranks = _ranks(ranks, cols)
     m = len(ranks)
-    shape = (m,) if d_keys.dim() == 1 else (rows, m)
-    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
-        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
-        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
-    if workspace is None:
-        nbytes = kth16_multi_workspace_bytes(rows, cols, m)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_kth16_multi_workspace_bytes", "too many keys or rows")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    values, indices = _select_outputs(d_keys, rows, (m,), return_indices, stream)
+    workspace = _workspace(workspace, "lsdsort_kth16_multi_workspace_bytes", (rows, cols, m), d_keys.device, stream)
     check(lib().lsdsort_kth16_multi_device(d_keys.data_ptr(), rows, cols, (ctypes.c_size_t * m)(*ranks), m, code, int(bool(largest)),
-                                           values.data_ptr(), indices.data_ptr() if return_indices else None, workspace.data_ptr(),
-                                           workspace.numel(), _stream(stream)), "lsdsort_kth16_multi_device")
+                                           values.data_ptr(), _ptr(indices), workspace.data_ptr(), workspace.numel(), _stream(stream)),
+          "lsdsort_kth16_multi_device")
     if check_fault and rows and cols:
         _check_fault(workspace, stream)
     return values, indices
@@ -907,34 +950,11 @@ def quantile16_rows(x, q, interpolation: str = "linear", stream=None):
     As in ``kthvalue16_rows`` the float types follow IEEE total order, not torch's: a row with NaNs does NOT propagate NaN as
     ``torch.quantile`` does -- NaNs sort by sign at the two ends (+NaN above +inf, -NaN below -inf), and -0.0 below +0.0."""
     torch = _torch()
-    _dev(x, "x", (torch.float16, torch.bfloat16), contiguous=False)
-    key_type = str(x.dtype).replace("torch.", "")
 
     def select(flat, ranks):
-        return GPUKth16Multi(flat, ranks, key_type=key_type, return_indices=False, stream=stream)[0].float()
+        return GPUKth16Multi(flat, ranks, key_type=_dtype_name(flat.dtype), return_indices=False, stream=stream)[0].float()
 
-    return _quantile_of(x, q, interpolation, stream, select)
-
-
-def _keys16(d_keys, key_type: str, verb: str = "selects"):
-    """The tensor and key-type checks of the 16-bit row entries -> (code, rows, cols)."""
-    torch = _torch()
-    _dev(d_keys, "d_keys", (torch.int16, torch.float16, torch.bfloat16), dims=(1, 2))
-    code = _key_type(key_type, KEY_TYPES_16)
-    fits = {torch.int16: ("uint16", "int16"), torch.float16: ("float16",), torch.bfloat16: ("bfloat16",)}[d_keys.dtype]
-    if key_type not in fits:
-        raise TypeError(f"a {str(d_keys.dtype).replace('torch.', '')} tensor {verb} with key_type " + " or ".join(f'"{k}"' for k in fits))
-    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
-    return code, rows, cols
-
-
-def _per_row_i32(t, name: str, rows: int):
-    """A per-row device array: a contiguous int32 CUDA tensor with one entry per row (its 32 bits are read as uint32)."""
-    torch = _torch()
-    _dev(t, name, (torch.int32,))
-    if t.numel() != rows:
-        raise ValueError(f"{name}: one entry per row ({rows}), got {t.numel()}")
-    return t
+    return _quantile_of(x, (torch.float16, torch.bfloat16), q, interpolation, stream, select)
 
 
 def kth16_perrow_workspace_bytes(rows: int, cols: int) -> int:
@@ -952,21 +972,13 @@ def GPUKth16PerRow(d_keys, d_ranks, key_type: str = "int16", largest: bool = Fal
     is outside ``0 .. cols - 1`` (as uint32) has nothing stored for it -- its slots of the returned tensors are uninitialised --, the
     other rows are right, and ``check_fault=True`` raises ``LsdsortError`` (``LSDSORT_ERR_DEVICE_FAULT``: bit 4096 of the workspace's
     first word)."""
-    torch = _torch()
     code, rows, cols = _keys16(d_keys, key_type)
-    _per_row_i32(d_ranks, "d_ranks", rows)
-    shape = () if d_keys.dim() == 1 else (rows,)
-    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
-        values = torch.empty(shape, dtype=d_keys.dtype, device=d_keys.device)
-        indices = torch.empty(shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
-    if workspace is None:
-        nbytes = kth16_perrow_workspace_bytes(rows, cols)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_kth16_perrow_workspace_bytes", "too many keys or rows")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    _per_row(d_ranks, "d_ranks", rows, _torch().int32)
+    values, indices = _select_outputs(d_keys, rows, (), return_indices, stream)
+    workspace = _workspace(workspace, "lsdsort_kth16_perrow_workspace_bytes", (rows, cols), d_keys.device, stream)
     check(lib().lsdsort_kth16_perrow_device(d_keys.data_ptr(), rows, cols, d_ranks.data_ptr(), code, int(bool(largest)),
-                                            values.data_ptr(), indices.data_ptr() if return_indices else None, workspace.data_ptr(),
-                                            workspace.numel(), _stream(stream)), "lsdsort_kth16_perrow_device")
+                                            values.data_ptr(), _ptr(indices), workspace.data_ptr(), workspace.numel(), _stream(stream)),
+          "lsdsort_kth16_perrow_device")
     if check_fault and rows and cols:
         _check_fault(workspace, stream)
     return values, indices
@@ -989,9 +1001,8 @@ def _fill_bits16(dtype, fill, largest: bool) -> int:
     """The 16-bit word ``topk16_filter_rows`` fills with: ``fill`` as a value of ``dtype`` (``None``: the worst value in the
     requested order)."""
     torch = _torch()
-    key_type = str(dtype).replace("torch.", "")
     if fill is None:
-        return _worst_bits16(key_type, largest)
+        return _worst_bits16(_dtype_name(dtype), largest)
     if dtype == torch.int16:
         if isinstance(fill, float) and not fill.is_integer():
             raise ValueError("fill: an integer for an int16 tensor")
@@ -1041,22 +1052,12 @@ def GPUTopK16Filter(d_keys, d_k, key_type: str = "int16", largest: bool = True, 
     once and written once, rows above 16384 keys read three times and written once."""
     torch = _torch()
     code, rows, cols = _keys16(d_keys, key_type, "is filtered")
-    _per_row_i32(d_k, "d_k", rows)
-    if fill is None:
-        fill = _worst_bits16(key_type, bool(largest))
-    if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 0xFFFF:
-        raise ValueError("fill: a 16-bit word, an int within 0 .. 0xFFFF")
-    if out is not None:
-        _dev(out, "out", (d_keys.dtype,), dims=(d_keys.dim(),))
-        if out.shape != d_keys.shape:
-            raise ValueError("out: the shape of d_keys")
+    _per_row(d_k, "d_k", rows, torch.int32)
+    fill = _fill16(fill, key_type, bool(largest))
+    _row_out(out, d_keys)
     with _on_stream(stream):   # the output, like a temporary workspace, belongs to the stream the kernels run on
         result = out if out is not None else torch.empty_like(d_keys)
-    if workspace is None:
-        nbytes = topk16_filter_workspace_bytes(rows, cols)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_topk16_filter_workspace_bytes", "too many keys or rows")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    workspace = _workspace(workspace, "lsdsort_topk16_filter_workspace_bytes", (rows, cols), d_keys.device, stream)
     check(lib().lsdsort_topk16_filter_device(d_keys.data_ptr(), rows, cols, d_k.data_ptr(), code, int(bool(largest)), fill,
                                              result.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(stream)),
           "lsdsort_topk16_filter_device")
@@ -1076,19 +1077,15 @@ def topk16_filter_rows(x, k, largest: bool = True, fill=None, inplace: bool = Fa
     (contiguous) and returns it.  The order is the library's total order, not torch's: -0.0 ranks below +0.0 and NaNs sort by sign
     at the two ends."""
     torch = _torch()
-    _dev(x, "x", (torch.int16, torch.float16, torch.bfloat16), contiguous=bool(inplace))
-    if x.dim() == 0:
-        raise TypeError("x: at least one dimension")
-    cols = x.shape[-1]
-    rows = int(np.prod(x.shape[:-1], dtype=np.int64))
+    r = _Rows(x, (torch.int16, torch.float16, torch.bfloat16), contiguous=bool(inplace))
+    rows = r.rows
     bits = _fill_bits16(x.dtype, fill, bool(largest))
     with _on_stream(stream):
         d_k = _k_per_row(k, rows, x.device)
-        if rows == 0 or cols == 0:
+        if rows == 0 or r.cols == 0:
             return x if inplace else x.clone()
-        flat = (x if inplace else x.contiguous()).view(-1, cols)
-        out = GPUTopK16Filter(flat, d_k, key_type=str(x.dtype).replace("torch.", ""), largest=largest, fill=bits,
-                              out=flat if inplace else None, stream=stream)
+        flat = r.flat(copy=not inplace)
+        out = GPUTopK16Filter(flat, d_k, key_type=r.key_type, largest=largest, fill=bits, out=flat if inplace else None, stream=stream)
         return x if inplace else out.view(x.shape)
 
 
@@ -1122,16 +1119,6 @@ def _p_per_row(p, rows: int, device, name: str = "p"):
     return torch.tensor(values, dtype=torch.float32).to(device)
 
 
-def _row_array(t, name: str, rows: int):
-    """An optional per-row device argument: ``None``, or a contiguous float32 CUDA tensor with one entry per row."""
-    if t is None:
-        return None
-    _dev(t, name, (_torch().float32,))
-    if t.numel() != rows:
-        raise ValueError(f"{name}: one entry per row ({rows}), got {t.numel()}")
-    return t
-
-
 def GPUTopP16Filter(d_keys, d_p, key_type: str = "bfloat16", fill: int | None = None, out=None, workspace=None, stream=None,
                     check_fault: bool = False, d_min_p=None, d_temperature=None):
     """The top-p (nucleus) filter of every row with a p of its own per row, read on the device (``lsdsort_topp16_filter_device``):
@@ -1152,38 +1139,21 @@ def GPUTopP16Filter(d_keys, d_p, key_type: str = "bfloat16", fill: int | None = 
     has to reach ``min_p_r`` times the best key's probability, ``value >= m + T_r ln(min_p_r)``; ``min_p_r`` not above 0 is off.  A
     key stays iff it passes both filters.  ``d_p`` may be ``None`` (top-p off in every row) when ``d_min_p`` is given."""
     torch = _torch()
-    _dev(d_keys, "d_keys", (torch.float16, torch.bfloat16), dims=(1, 2))
-    if key_type not in ("float16", "bfloat16"):
-        raise ValueError(f'key_type: "float16" or "bfloat16", got {key_type!r}')
-    code, rows, cols = _keys16(d_keys, key_type, "is filtered")
-    if d_p is not None or d_min_p is None:
-        _dev(d_p, "d_p", (torch.float32,))
-        if d_p.numel() != rows:
-            raise ValueError(f"d_p: one entry per row ({rows}), got {d_p.numel()}")
-    _row_array(d_min_p, "d_min_p", rows)
-    _row_array(d_temperature, "d_temperature", rows)
-    if fill is None:
-        fill = _worst_bits16(key_type, True)
-    if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 0xFFFF:
-        raise ValueError("fill: a 16-bit word, an int within 0 .. 0xFFFF")
-    if out is not None:
-        _dev(out, "out", (d_keys.dtype,), dims=(d_keys.dim(),))
-        if out.shape != d_keys.shape:
-            raise ValueError("out: the shape of d_keys")
+    code, rows, cols = _logits16(d_keys, key_type, "is filtered")
+    _per_row(d_p, "d_p", rows, torch.float32, optional=d_min_p is not None)
+    _per_row(d_min_p, "d_min_p", rows, torch.float32, optional=True)
+    _per_row(d_temperature, "d_temperature", rows, torch.float32, optional=True)
+    fill = _fill16(fill, key_type, True)
+    _row_out(out, d_keys)
     with _on_stream(stream):   # the output, like a temporary workspace, belongs to the stream the kernels run on
         result = out if out is not None else torch.empty_like(d_keys)
-    if workspace is None:
-        nbytes = topp16_filter_workspace_bytes(rows, cols)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_topp16_filter_workspace_bytes", "too many keys or rows")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    workspace = _workspace(workspace, "lsdsort_topp16_filter_workspace_bytes", (rows, cols), d_keys.device, stream)
     if d_min_p is None and d_temperature is None:
         check(lib().lsdsort_topp16_filter_device(d_keys.data_ptr(), rows, cols, d_p.data_ptr(), code, fill, result.data_ptr(),
                                                  workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_topp16_filter_device")
     else:
-        ptr = [t.data_ptr() if t is not None else None for t in (d_p, d_min_p, d_temperature)]
-        check(lib().lsdsort_topp16_filter_ex_device(d_keys.data_ptr(), rows, cols, ptr[0], ptr[1], ptr[2], code, fill, result.data_ptr(),
-                                                    workspace.data_ptr(), workspace.numel(), _stream(stream)),
+        check(lib().lsdsort_topp16_filter_ex_device(d_keys.data_ptr(), rows, cols, _ptr(d_p), _ptr(d_min_p), _ptr(d_temperature), code,
+                                                    fill, result.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(stream)),
               "lsdsort_topp16_filter_ex_device")
     if check_fault and rows and cols:
         _check_fault(workspace, stream)
@@ -1203,21 +1173,18 @@ def topp16_filter_rows(x, p, fill=None, inplace: bool = False, stream=None, min_
     bits, and with ``min_p`` a kept key also has at least ``min_p_r`` times the best key's probability (``min_p_r <= 0``: off); a
     row keeps what passes both.  ``p`` may be ``None`` (top-p off) when ``min_p`` is given."""
     torch = _torch()
-    _dev(x, "x", (torch.float16, torch.bfloat16), contiguous=bool(inplace))
-    if x.dim() == 0:
-        raise TypeError("x: at least one dimension")
-    cols = x.shape[-1]
-    rows = int(np.prod(x.shape[:-1], dtype=np.int64))
+    r = _Rows(x, (torch.float16, torch.bfloat16), contiguous=bool(inplace))
+    rows = r.rows
     bits = _fill_bits16(x.dtype, fill, True)
     with _on_stream(stream):
         d_p = _p_per_row(p, rows, x.device) if p is not None or min_p is None else None
         d_min_p = _p_per_row(min_p, rows, x.device, "min_p") if min_p is not None else None
         d_t = _p_per_row(temperature, rows, x.device, "temperature") if temperature is not None else None
-        if rows == 0 or cols == 0:
+        if rows == 0 or r.cols == 0:
             return x if inplace else x.clone()
-        flat = (x if inplace else x.contiguous()).view(-1, cols)
-        out = GPUTopP16Filter(flat, d_p, key_type=str(x.dtype).replace("torch.", ""), fill=bits, out=flat if inplace else None,
-                              stream=stream, d_min_p=d_min_p, d_temperature=d_t)
+        flat = r.flat(copy=not inplace)
+        out = GPUTopP16Filter(flat, d_p, key_type=r.key_type, fill=bits, out=flat if inplace else None, stream=stream,
+                              d_min_p=d_min_p, d_temperature=d_t)
         return x if inplace else out.view(x.shape)
 
 
@@ -1246,41 +1213,26 @@ def GPUSample16(d_keys, d_u, key_type: str = "bfloat16", out=None, logprobs=Fals
     tensor with one entry per row, read on the device.  The weights become ``exp((x - m) / T_r)`` and the logprob is that of the
     tempered softmax; ``T_r`` not above 0 (a NaN included) is greedy: the argmax, uniform over its duplicates by ``u``."""
     torch = _torch()
-    _dev(d_keys, "d_keys", (torch.float16, torch.bfloat16), dims=(1, 2))
-    if key_type not in ("float16", "bfloat16"):
-        raise ValueError(f'key_type: "float16" or "bfloat16", got {key_type!r}')
-    code, rows, cols = _keys16(d_keys, key_type, "is sampled")
-    _dev(d_u, "d_u", (torch.float32,))
-    if d_u.numel() != rows:
-        raise ValueError(f"d_u: one entry per row ({rows}), got {d_u.numel()}")
-    _row_array(d_temperature, "d_temperature", rows)
-    if out is not None:
-        _dev(out, "out", (torch.int32,), dims=(1,))
-        if out.numel() != rows:
-            raise ValueError(f"out: one entry per row ({rows}), got {out.numel()}")
+    code, rows, cols = _logits16(d_keys, key_type, "is sampled")
+    _per_row(d_u, "d_u", rows, torch.float32)
+    _per_row(d_temperature, "d_temperature", rows, torch.float32, optional=True)
+    _per_row(out, "out", rows, torch.int32, dims=(1,), optional=True)
     own_logprob = isinstance(logprobs, torch.Tensor)
     if own_logprob:
-        _dev(logprobs, "logprobs", (torch.float32,), dims=(1,))
-        if logprobs.numel() != rows:
-            raise ValueError(f"logprobs: one entry per row ({rows}), got {logprobs.numel()}")
+        _per_row(logprobs, "logprobs", rows, torch.float32, dims=(1,))
     elif not isinstance(logprobs, bool):
         raise TypeError("logprobs: a bool, or a contiguous 1-D float32 CUDA tensor")
     with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
         index = out if out is not None else torch.empty((rows,), dtype=torch.int32, device=d_keys.device)
         logprob = logprobs if own_logprob else (torch.empty((rows,), dtype=torch.float32, device=d_keys.device) if logprobs else None)
-    if workspace is None:
-        nbytes = sample16_workspace_bytes(rows, cols)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_sample16_workspace_bytes", "too many keys or rows")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
+    workspace = _workspace(workspace, "lsdsort_sample16_workspace_bytes", (rows, cols), d_keys.device, stream)
     if d_temperature is None:
-        check(lib().lsdsort_sample16_device(d_keys.data_ptr(), rows, cols, d_u.data_ptr(), code, index.data_ptr(),
-                                            logprob.data_ptr() if logprob is not None else None, workspace.data_ptr(), workspace.numel(),
-                                            _stream(stream)), "lsdsort_sample16_device")
+        check(lib().lsdsort_sample16_device(d_keys.data_ptr(), rows, cols, d_u.data_ptr(), code, index.data_ptr(), _ptr(logprob),
+                                            workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_sample16_device")
     else:
         check(lib().lsdsort_sample16_ex_device(d_keys.data_ptr(), rows, cols, d_u.data_ptr(), d_temperature.data_ptr(), code,
-                                               index.data_ptr(), logprob.data_ptr() if logprob is not None else None,
-                                               workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_sample16_ex_device")
+                                               index.data_ptr(), _ptr(logprob), workspace.data_ptr(), workspace.numel(), _stream(stream)),
+              "lsdsort_sample16_ex_device")
     if check_fault and rows and cols:
         _check_fault(workspace, stream)
     return (index, logprob) if logprob is not None else index
@@ -1301,12 +1253,8 @@ def sample16_rows(x, u=None, top_k=None, top_p=None, generator=None, return_logp
     ``top_p``: the softmax is that of ``x / T_r`` in the filters and in the draw (``T_r <= 0``: greedy, the argmax), and ``min_p``
     joins ``top_p`` in ONE filter call between top-k and the draw."""
     torch = _torch()
-    _dev(x, "x", (torch.float16, torch.bfloat16), contiguous=False)
-    if x.dim() == 0:
-        raise TypeError("x: at least one dimension")
-    cols = x.shape[-1]
-    rows = int(np.prod(x.shape[:-1], dtype=np.int64))
-    key_type = str(x.dtype).replace("torch.", "")
+    r = _Rows(x, (torch.float16, torch.bfloat16))
+    rows, cols, key_type = r.rows, r.cols, r.key_type
     with _on_stream(stream):
         if u is None:
             d_u = torch.rand((rows,), dtype=torch.float32, device=x.device, generator=generator)
@@ -1320,7 +1268,7 @@ def sample16_rows(x, u=None, top_k=None, top_p=None, generator=None, return_logp
             index = torch.full(x.shape[:-1], -1, dtype=torch.int64, device=x.device)
             logprob = torch.full(x.shape[:-1], float("nan"), dtype=torch.float32, device=x.device)
             return (index, logprob) if return_logprobs else index
-        flat = x.contiguous().view(-1, cols)
+        flat = r.flat()
         if d_k is not None or d_p is not None or d_min_p is not None:
             flat = flat.clone() if flat.data_ptr() == x.data_ptr() else flat   # the one copy the filters write
             if d_k is not None:
@@ -1329,8 +1277,8 @@ def sample16_rows(x, u=None, top_k=None, top_p=None, generator=None, return_logp
                 GPUTopP16Filter(flat, d_p, key_type=key_type, out=flat, stream=stream, d_min_p=d_min_p, d_temperature=d_t)
         got = GPUSample16(flat, d_u, key_type=key_type, logprobs=bool(return_logprobs), stream=stream, d_temperature=d_t)
         if return_logprobs:
-            return got[0].to(torch.int64).view(x.shape[:-1]), got[1].view(x.shape[:-1])
-        return got.to(torch.int64).view(x.shape[:-1])
+            return r.restore(got[0].to(torch.int64)), r.restore(got[1])
+        return r.restore(got.to(torch.int64))
 
 
 def logprob16_workspace_bytes(rows: int, cols: int, slots: int) -> int:
@@ -1349,7 +1297,7 @@ def _optional_out(arg, name: str, dtype, shape, device):
             raise ValueError(f"{name}: {int(np.prod(shape, dtype=np.int64))} entries, got {arg.numel()}")
         return arg
     if not isinstance(arg, bool):
-        raise TypeError(f"{name}: a bool, or a contiguous {str(dtype).replace('torch.', '')} CUDA tensor")
+        raise TypeError(f"{name}: a bool, or a contiguous {_dtype_name(dtype)} CUDA tensor")
     return torch.empty(shape, dtype=dtype, device=device) if arg else None
 
 
@@ -1369,17 +1317,14 @@ def GPULogprob16(d_keys, d_ids, key_type: str = "bfloat16", ranks=False, lse=Fal
     ``(logprob[, rank][, lse])``.  The host reads none of the arrays: a captured graph follows their contents.  Stream-ordered;
     ``d_keys`` is only read: rows of up to 16384 keys once, longer ones twice."""
     torch = _torch()
-    _dev(d_keys, "d_keys", (torch.float16, torch.bfloat16), dims=(1, 2))
-    if key_type not in ("float16", "bfloat16"):
-        raise ValueError(f'key_type: "float16" or "bfloat16", got {key_type!r}')
-    code, rows, cols = _keys16(d_keys, key_type, "is scored")
+    code, rows, cols = _logits16(d_keys, key_type, "is scored")
     _dev(d_ids, "d_ids", (torch.int32,), dims=(1, 2))
     if d_ids.shape[0] != rows:
         raise ValueError(f"d_ids: one row of ids per row ({rows}), got {d_ids.shape[0]}")
     slots = 1 if d_ids.dim() == 1 else d_ids.shape[1]
     if not 1 <= slots <= errors.LSDSORT_LOGPROB_MAX_SLOTS:
         raise ValueError(f"d_ids: 1 .. {errors.LSDSORT_LOGPROB_MAX_SLOTS} ids per row, got {slots}")
-    _row_array(d_temperature, "d_temperature", rows)
+    _per_row(d_temperature, "d_temperature", rows, torch.float32, optional=True)
     if out is not None:
         _dev(out, "out", (torch.float32,))
         if out.numel() != rows * slots:
@@ -1388,14 +1333,10 @@ def GPULogprob16(d_keys, d_ids, key_type: str = "bfloat16", ranks=False, lse=Fal
         logprob = out if out is not None else torch.empty(d_ids.shape, dtype=torch.float32, device=d_keys.device)
         rank = _optional_out(ranks, "ranks", torch.int32, d_ids.shape, d_keys.device)
         total = _optional_out(lse, "lse", torch.float32, (rows,), d_keys.device)
-    if workspace is None:
-        nbytes = logprob16_workspace_bytes(rows, cols, slots)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_logprob16_workspace_bytes", "too many keys or rows")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
-    ptr = [t.data_ptr() if t is not None else None for t in (d_temperature, rank, total)]
-    check(lib().lsdsort_logprob16_device(d_keys.data_ptr(), rows, cols, d_ids.data_ptr(), slots, ptr[0], code, logprob.data_ptr(), ptr[1],
-                                         ptr[2], workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_logprob16_device")
+    workspace = _workspace(workspace, "lsdsort_logprob16_workspace_bytes", (rows, cols, slots), d_keys.device, stream)
+    check(lib().lsdsort_logprob16_device(d_keys.data_ptr(), rows, cols, d_ids.data_ptr(), slots, _ptr(d_temperature), code,
+                                         logprob.data_ptr(), _ptr(rank), _ptr(total), workspace.data_ptr(), workspace.numel(),
+                                         _stream(stream)), "lsdsort_logprob16_device")
     if check_fault and rows and cols:
         _check_fault(workspace, stream)
     got = (logprob,) + tuple(t for t in (rank, total) if t is not None)
@@ -1411,15 +1352,12 @@ def logprobs16_rows(x, ids, temperature=None, return_ranks: bool = False, return
     also the int64 ranks ``(x.float() > x.gather(-1, ids)).sum(-1)`` (-1 for padding and NaN logits), with ``return_lse`` the float32
     log-sum-exp of every tempered row, of shape ``x.shape[:-1]``: ``(logprobs[, ranks][, lse])``."""
     torch = _torch()
-    _dev(x, "x", (torch.float16, torch.bfloat16), contiguous=False)
-    if x.dim() == 0:
-        raise TypeError("x: at least one dimension")
+    r = _Rows(x, (torch.float16, torch.bfloat16))
     _dev(ids, "ids", (torch.int32, torch.int64), contiguous=False)
-    lead = tuple(x.shape[:-1])
+    lead = r.lead
     if tuple(ids.shape) != lead and tuple(ids.shape[:-1]) != lead:
         raise ValueError(f"ids: the shape of x without its last dimension {lead}, or that with a last dimension of ids per row; got {tuple(ids.shape)}")
-    cols = x.shape[-1]
-    rows = int(np.prod(lead, dtype=np.int64))
+    rows, cols = r.rows, r.cols
     n = 1 if tuple(ids.shape) == lead else ids.shape[-1]
     step = errors.LSDSORT_LOGPROB_MAX_SLOTS
     with _on_stream(stream):
@@ -1429,7 +1367,7 @@ def logprobs16_rows(x, ids, temperature=None, return_ranks: bool = False, return
             got += (torch.full(ids.shape, -1, dtype=torch.int64, device=x.device),) if return_ranks else ()
             got += (torch.full(lead, float("nan"), dtype=torch.float32, device=x.device),) if return_lse else ()
             return got if len(got) > 1 else got[0]
-        flat = x.contiguous().view(rows, cols)
+        flat = r.flat()
         wide = ids.reshape(rows, n)
         if wide.dtype != torch.int32:   # what does not fit 32 bits names no key
             wide = torch.where((wide < 0) | (wide >= cols), torch.full_like(wide, -1), wide).to(torch.int32)
@@ -1438,7 +1376,7 @@ def logprobs16_rows(x, ids, temperature=None, return_ranks: bool = False, return
         total = None
         for a in range(0, n, step):
             part = wide[:, a:a + step].contiguous()
-            got = GPULogprob16(flat, part, key_type=str(x.dtype).replace("torch.", ""), ranks=bool(return_ranks),
+            got = GPULogprob16(flat, part, key_type=r.key_type, ranks=bool(return_ranks),
                                lse=bool(return_lse) and a == 0, d_temperature=d_t, stream=stream)
             got = got if isinstance(got, tuple) else (got,)
             logprob[:, a:a + step] = got[0]
@@ -1485,28 +1423,14 @@ def GPUSortRows16(d_keys, key_type: str = "int16", descending: bool = False, ret
     within the row, or ``None`` without ``return_indices``.  Equal keys come out in position order in either direction.
     Stream-ordered; ``d_keys`` is only read unless it is ``out``."""
     torch = _torch()
-    kinds = (torch.int16, torch.float16, torch.bfloat16)
-    _dev(d_keys, "d_keys", kinds, dims=(1, 2))
-    code = _key_type(key_type, KEY_TYPES_16)
-    fits = {torch.int16: ("uint16", "int16"), torch.float16: ("float16",), torch.bfloat16: ("bfloat16",)}[d_keys.dtype]
-    if key_type not in fits:
-        raise TypeError(f"a {str(d_keys.dtype).replace('torch.', '')} tensor sorts with key_type " + " or ".join(f'"{k}"' for k in fits))
-    if out is not None:
-        _dev(out, "out", (d_keys.dtype,), dims=(d_keys.dim(),))
-        if out.shape != d_keys.shape:
-            raise ValueError("out: the shape of d_keys")
-    rows, cols = (1, d_keys.shape[0]) if d_keys.dim() == 1 else d_keys.shape
+    code, rows, cols = _keys16(d_keys, key_type, "sorts")
+    _row_out(out, d_keys)
     with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
         values = out if out is not None else torch.empty_like(d_keys)
         indices = torch.empty(d_keys.shape, dtype=torch.int32, device=d_keys.device) if return_indices else None
-    if workspace is None:
-        nbytes = rows16_workspace_bytes(rows, cols)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_rows16_workspace_bytes", "too many keys or rows")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
-    check(lib().lsdsort_rows16_device(d_keys.data_ptr(), rows, cols, code, int(bool(descending)), values.data_ptr(),
-                                      indices.data_ptr() if return_indices else None, workspace.data_ptr(), workspace.numel(),
-                                      _stream(stream)), "lsdsort_rows16_device")
+    workspace = _workspace(workspace, "lsdsort_rows16_workspace_bytes", (rows, cols), d_keys.device, stream)
+    check(lib().lsdsort_rows16_device(d_keys.data_ptr(), rows, cols, code, int(bool(descending)), values.data_ptr(), _ptr(indices),
+                                      workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_rows16_device")
     if check_fault and rows and cols:
         _check_fault(workspace, stream)
     return values, indices
@@ -1518,14 +1442,10 @@ def sort_rows16(x, descending: bool = False, return_indices: bool = False, strea
     positions within each row (equal keys keep their input order in either direction).  The float types follow IEEE total order,
     not torch's: NaNs by sign at the two ends and -0.0 below +0.0."""
     torch = _torch()
-    _dev(x, "x", (torch.int16, torch.float16, torch.bfloat16), contiguous=False)
-    if x.dim() == 0:
-        raise TypeError("x: at least one dimension")
-    cols = x.shape[-1]
+    r = _Rows(x, (torch.int16, torch.float16, torch.bfloat16))
     with _on_stream(stream):
-        flat = x.contiguous().view(-1, cols)
-        values, indices = GPUSortRows16(flat, key_type=str(x.dtype).replace("torch.", ""), descending=descending,
-                                        return_indices=return_indices, stream=stream)
+        values, indices = GPUSortRows16(r.flat(), key_type=r.key_type, descending=descending, return_indices=return_indices,
+                                        stream=stream)
         if return_indices:
             return values.view(x.shape), indices.view(x.shape).to(torch.int64)
     return values.view(x.shape)
@@ -1564,16 +1484,42 @@ def _word_keys(d_keys, name: str, key_type=None, contiguous: bool = True):
     return key_type
 
 
-def _out_keys(out, d_keys, may_alias: bool):
-    """``out`` of the two wrappers: a contiguous CUDA tensor of the keys' dtype and length."""
-    if out is None:
-        return None
-    _dev(out, "out", (d_keys.dtype,), dims=(1,))
-    if out.numel() != d_keys.numel():
-        raise ValueError(f"out: as long as the keys ({d_keys.numel()}), got {out.numel()}")
-    if not may_alias and out.numel() and out.data_ptr() == d_keys.data_ptr():
-        raise ValueError("out: the keys themselves cannot take the runs (they are read while the runs are stored)")
-    return out
+_RUN_OUTS = (("out", "keys", "runs"), ("out_vals", "values", "aggregates"))   # what the messages call the outputs and their inputs
+
+
+def _run_outputs(d_keys, outs, optional, may_alias: bool, stream):
+    """The outputs of the four run units -> (mandatory ones, optional ones, num).  ``outs``: ``(out, input)`` for the keys, and
+    for the reduces the values: ``out`` is ``None`` (a new tensor like the input) or a contiguous CUDA tensor of the input's dtype
+    and length -- the input itself only where ``may_alias``.  ``optional``: ``(argument, name)`` of every int32 array of the keys'
+    length that ``_optional_out`` makes, fills or leaves out.  ``num``: the one-word int32 count.  All under the stream: the
+    outputs, like a temporary workspace, belong to the stream the kernels run on."""
+    torch = _torch()
+    for (out, src), (name, what, takes) in zip(outs, _RUN_OUTS):
+        if out is None:
+            continue
+        _dev(out, name, (src.dtype,), dims=(1,))
+        if out.numel() != src.numel():
+            raise ValueError(f"{name}: as long as the {what} ({src.numel()}), got {out.numel()}")
+        if not may_alias and out.numel() and out.data_ptr() == src.data_ptr():
+            raise ValueError(f"{name}: the {what} themselves cannot take the {takes} (they are read while the runs are stored)")
+    n = d_keys.numel()
+    with _on_stream(stream):
+        fixed = [out if out is not None else torch.empty_like(src) for out, src in outs]
+        extra = [_optional_out(arg, name, torch.int32, (n,), d_keys.device) for arg, name in optional]
+        num = torch.empty(1, dtype=torch.int32, device=d_keys.device)
+    return fixed, extra, num
+
+
+def _run_result(fixed, extra, num) -> tuple:
+    """What the four run units return: the mandatory outputs, the optional ones that were asked for, the count."""
+    return tuple(fixed) + tuple(t for t in extra if t is not None) + (num,)
+
+
+def _slice_by_count(got) -> list:
+    """``(full-length tensors ..., count)`` of a run unit -> the tensors cut to the count, which is read here: the one
+    synchronisation of the slicing wrappers."""
+    m = int(got[-1].item())
+    return [t[:m] for t in got[:-1]]
 
 
 def GPURunLength(d_keys, counts=False, starts=False, out=None, workspace=None, stream=None, check_fault: bool = False):
@@ -1584,27 +1530,16 @@ def GPURunLength(d_keys, counts=False, starts=False, out=None, workspace=None, s
     FULL-LENGTH tensors whose first ``num_runs`` entries are the word, the length and the first position of every run (the rest is
     not written), and ``num_runs``, a one-word int32 CUDA tensor -- no host synchronisation; slice after reading it.  ``counts`` /
     ``starts``: ``True``, or a contiguous int32 CUDA tensor of the keys' length to fill; ``out``: where the keys go (not ``d_keys``)."""
-    torch = _torch()
     _word_keys(d_keys, "d_keys")
     n = d_keys.numel()
     bits = 8 * d_keys.element_size()
-    _out_keys(out, d_keys, may_alias=False)
-    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
-        keys = out if out is not None else torch.empty_like(d_keys)
-        optional = [_optional_out(counts, "counts", torch.int32, (n,), d_keys.device),
-                    _optional_out(starts, "starts", torch.int32, (n,), d_keys.device)]
-        num = torch.empty(1, dtype=torch.int32, device=d_keys.device)
-    if workspace is None:
-        nbytes = rle_workspace_bytes(n, bits)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_rle_workspace_bytes", "too many keys")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
-    ptr = [t.data_ptr() if t is not None and n else None for t in optional]
-    check(lib().lsdsort_rle_device(d_keys.data_ptr() if n else None, n, bits, keys.data_ptr() if n else None, ptr[0], ptr[1],
-                                   num.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_rle_device")
+    fixed, extra, num = _run_outputs(d_keys, [(out, d_keys)], [(counts, "counts"), (starts, "starts")], False, stream)
+    workspace = _workspace(workspace, "lsdsort_rle_workspace_bytes", (n, bits), d_keys.device, stream, "too many keys")
+    check(lib().lsdsort_rle_device(_ptr(d_keys, n), n, bits, _ptr(fixed[0], n), _ptr(extra[0], n), _ptr(extra[1], n), num.data_ptr(),
+                                   workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_rle_device")
     if check_fault and n:
         _check_fault(workspace, stream)
-    return (keys,) + tuple(t for t in optional if t is not None) + (num,)
+    return _run_result(fixed, extra, num)
 
 
 def GPUUnique(d_keys, key_type=None, descending: bool = False, counts=False, first=False, inverse=False, out=None, workspace=None,
@@ -1618,30 +1553,18 @@ def GPUUnique(d_keys, key_type=None, descending: bool = False, counts=False, fir
     ``counts[j]``: how often value ``j`` occurs; ``first[j]``: the lowest input position that holds it; ``inverse[i]``: the ``j`` with
     ``keys[j] == d_keys[i]`` (all ``n`` entries written).  Each of the three: ``True``, or a contiguous int32 CUDA tensor of the keys'
     length to fill.  ``out``: where the distinct keys go; it may be ``d_keys`` itself."""
-    torch = _torch()
     key_type = _word_keys(d_keys, "d_keys", key_type)
     code = _key_type(key_type, {**KEY_TYPES_32, **KEY_TYPES_64})
     n = d_keys.numel()
-    _out_keys(out, d_keys, may_alias=True)
-    with _on_stream(stream):
-        keys = out if out is not None else torch.empty_like(d_keys)
-        optional = [_optional_out(counts, "counts", torch.int32, (n,), d_keys.device),
-                    _optional_out(first, "first", torch.int32, (n,), d_keys.device),
-                    _optional_out(inverse, "inverse", torch.int32, (n,), d_keys.device)]
-        num = torch.empty(1, dtype=torch.int32, device=d_keys.device)
-    positions = optional[1] is not None or optional[2] is not None
-    if workspace is None:
-        nbytes = unique_workspace_bytes(n, key_type, positions)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_unique_workspace_bytes", "too many keys")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
-    ptr = [t.data_ptr() if t is not None and n else None for t in optional]
-    check(lib().lsdsort_unique_device(d_keys.data_ptr() if n else None, n, code, int(bool(descending)), keys.data_ptr() if n else None,
-                                      ptr[0], ptr[1], ptr[2], num.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(stream)),
-          "lsdsort_unique_device")
+    fixed, extra, num = _run_outputs(d_keys, [(out, d_keys)], [(counts, "counts"), (first, "first"), (inverse, "inverse")], True, stream)
+    positions = extra[1] is not None or extra[2] is not None
+    workspace = _workspace(workspace, "lsdsort_unique_workspace_bytes", (n, code, int(positions)), d_keys.device, stream, "too many keys")
+    check(lib().lsdsort_unique_device(_ptr(d_keys, n), n, code, int(bool(descending)), _ptr(fixed[0], n), _ptr(extra[0], n),
+                                      _ptr(extra[1], n), _ptr(extra[2], n), num.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                      _stream(stream)), "lsdsort_unique_device")
     if check_fault and n:
         _check_fault(workspace, stream, "lsdsort_unique_check_device", n, code, int(positions))
-    return (keys,) + tuple(t for t in optional if t is not None) + (num,)
+    return _run_result(fixed, extra, num)
 
 
 def unique(x, return_inverse: bool = False, return_counts: bool = False, return_index: bool = False, descending: bool = False):
@@ -1654,16 +1577,12 @@ def unique(x, return_inverse: bool = False, return_counts: bool = False, return_
     result equals torch's wherever the input holds no -0.0 next to a +0.0 and no NaN."""
     torch = _torch()
     _word_keys(x, "x", contiguous=False)
-    got = GPUUnique(x.contiguous(), descending=descending, counts=bool(return_counts), first=bool(return_index), inverse=bool(return_inverse))
-    m = int(got[-1].item())
-    arrays = list(got[1:-1])
-    result = [got[0][:m]]
-    counts = arrays.pop(0)[:m].to(torch.int64) if return_counts else None
-    index = arrays.pop(0)[:m].to(torch.int64) if return_index else None
-    if return_inverse:
-        result.append(arrays.pop(0).to(torch.int64))
-    result += [t for t in (counts, index) if t is not None]
-    return result[0] if len(result) == 1 else tuple(result)
+    got = list(GPUUnique(x.contiguous(), descending=descending, counts=bool(return_counts), first=bool(return_index),
+                         inverse=bool(return_inverse)))
+    inverse = [got.pop(-2)] if return_inverse else []   # all n entries: the one array that is not cut to the count
+    values, *arrays = _slice_by_count(got)              # then counts and first, each where asked for
+    result = (values,) + tuple(t.to(torch.int64) for t in inverse + arrays)
+    return values if len(result) == 1 else result
 
 
 def unique_consecutive(x, return_counts: bool = False):
@@ -1672,11 +1591,8 @@ def unique_consecutive(x, return_counts: bool = False):
     Equality is equality of bits: the result equals torch's wherever the input holds no -0.0 next to a +0.0 and no NaN."""
     torch = _torch()
     _word_keys(x, "x", contiguous=False)
-    got = GPURunLength(x.contiguous(), counts=bool(return_counts))
-    m = int(got[-1].item())
-    if return_counts:
-        return got[0][:m], got[1][:m].to(torch.int64)
-    return got[0][:m]
+    values, *counts = _slice_by_count(GPURunLength(x.contiguous(), counts=bool(return_counts)))
+    return (values, counts[0].to(torch.int64)) if return_counts else values
 
 
 # ------------------------------------------------------------------------------ reduce by key
@@ -1707,18 +1623,6 @@ def _reduce_values(d_vals, n: int, op: str):
     return errors.VAL_TYPES[own[d_vals.dtype]], errors.REDUCE_OPS[op]
 
 
-def _out_values(out_vals, d_vals, may_alias: bool):
-    """``out_vals`` of the two wrappers: a contiguous CUDA tensor of the values' dtype and length."""
-    if out_vals is None:
-        return None
-    _dev(out_vals, "out_vals", (d_vals.dtype,), dims=(1,))
-    if out_vals.numel() != d_vals.numel():
-        raise ValueError(f"out_vals: as long as the values ({d_vals.numel()}), got {out_vals.numel()}")
-    if not may_alias and out_vals.numel() and out_vals.data_ptr() == d_vals.data_ptr():
-        raise ValueError("out_vals: the values themselves cannot take the aggregates (they are read while the runs are stored)")
-    return out_vals
-
-
 def GPUReduceRuns(d_keys, d_vals, op: str = "sum", counts=False, out_keys=None, out_vals=None, workspace=None, stream=None,
                   check_fault: bool = False):
     """``op`` ("sum" | "min" | "max") of ``d_vals`` over every run of equal adjacent keys of ``d_keys`` as it lies, sorted or not
@@ -1730,30 +1634,18 @@ def GPUReduceRuns(d_keys, d_vals, op: str = "sum", counts=False, out_keys=None, 
     keeps its bits.  Returns ``(keys, aggregates[, counts], num_runs)``: FULL-LENGTH tensors whose first ``num_runs`` entries are
     written, and the one-word int32 count -- no host synchronisation.  ``counts``: ``True``, or a contiguous int32 CUDA tensor of the
     keys' length to fill; ``out_keys`` / ``out_vals``: where keys and aggregates go (not the inputs themselves)."""
-    torch = _torch()
     _word_keys(d_keys, "d_keys")
     n = d_keys.numel()
     bits = 8 * d_keys.element_size()
     val_type, code = _reduce_values(d_vals, n, op)
-    _out_keys(out_keys, d_keys, may_alias=False)
-    _out_values(out_vals, d_vals, may_alias=False)
-    with _on_stream(stream):   # the outputs, like a temporary workspace, belong to the stream the kernels run on
-        keys = out_keys if out_keys is not None else torch.empty_like(d_keys)
-        vals = out_vals if out_vals is not None else torch.empty_like(d_vals)
-        lengths = _optional_out(counts, "counts", torch.int32, (n,), d_keys.device)
-        num = torch.empty(1, dtype=torch.int32, device=d_keys.device)
-    if workspace is None:
-        nbytes = reduce_runs_workspace_bytes(n, bits)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_reduce_runs_workspace_bytes", "too many keys")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
-    check(lib().lsdsort_reduce_runs_device(d_keys.data_ptr() if n else None, d_vals.data_ptr() if n else None, n, bits, val_type, code,
-                                           keys.data_ptr() if n else None, vals.data_ptr() if n else None,
-                                           lengths.data_ptr() if lengths is not None and n else None, num.data_ptr(),
-                                           workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_reduce_runs_device")
+    fixed, extra, num = _run_outputs(d_keys, [(out_keys, d_keys), (out_vals, d_vals)], [(counts, "counts")], False, stream)
+    workspace = _workspace(workspace, "lsdsort_reduce_runs_workspace_bytes", (n, bits), d_keys.device, stream, "too many keys")
+    check(lib().lsdsort_reduce_runs_device(_ptr(d_keys, n), _ptr(d_vals, n), n, bits, val_type, code, _ptr(fixed[0], n), _ptr(fixed[1], n),
+                                           _ptr(extra[0], n), num.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(stream)),
+          "lsdsort_reduce_runs_device")
     if check_fault and n:
         _check_fault(workspace, stream)
-    return (keys, vals) + ((lengths,) if lengths is not None else ()) + (num,)
+    return _run_result(fixed, extra, num)
 
 
 def GPUReduceByKey(d_keys, d_vals, op: str = "sum", key_type=None, descending: bool = False, counts=False, out_keys=None, out_vals=None,
@@ -1765,40 +1657,30 @@ def GPUReduceByKey(d_keys, d_vals, op: str = "sum", key_type=None, descending: b
     values, operations and their float rules (-0.0, NaN, the total order of min / max): as for ``GPUReduceRuns``.  Returns
     ``(keys, aggregates[, counts], num_groups)``: full-length tensors and the one-word int32 count, no host synchronisation.
     ``out_keys`` / ``out_vals`` may be ``d_keys`` / ``d_vals`` themselves."""
-    torch = _torch()
     key_type = _word_keys(d_keys, "d_keys", key_type)
     key_code = _key_type(key_type, {**KEY_TYPES_32, **KEY_TYPES_64})
     n = d_keys.numel()
     val_type, code = _reduce_values(d_vals, n, op)
-    _out_keys(out_keys, d_keys, may_alias=True)
-    _out_values(out_vals, d_vals, may_alias=True)
-    with _on_stream(stream):
-        keys = out_keys if out_keys is not None else torch.empty_like(d_keys)
-        vals = out_vals if out_vals is not None else torch.empty_like(d_vals)
-        lengths = _optional_out(counts, "counts", torch.int32, (n,), d_keys.device)
-        num = torch.empty(1, dtype=torch.int32, device=d_keys.device)
-    if workspace is None:
-        nbytes = reduce_by_key_workspace_bytes(n, key_type)
-        if nbytes == 0:
-            raise errors.LsdsortError(errors.LSDSORT_ERR_TOO_LARGE, "lsdsort_reduce_by_key_workspace_bytes", "too many keys")
-        workspace = _temp_workspace(nbytes, d_keys.device, stream)
-    check(lib().lsdsort_reduce_by_key_device(d_keys.data_ptr() if n else None, d_vals.data_ptr() if n else None, n, key_code,
-                                             int(bool(descending)), val_type, code, keys.data_ptr() if n else None,
-                                             vals.data_ptr() if n else None, lengths.data_ptr() if lengths is not None and n else None,
-                                             num.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(stream)),
-          "lsdsort_reduce_by_key_device")
+    fixed, extra, num = _run_outputs(d_keys, [(out_keys, d_keys), (out_vals, d_vals)], [(counts, "counts")], True, stream)
+    workspace = _workspace(workspace, "lsdsort_reduce_by_key_workspace_bytes", (n, key_code), d_keys.device, stream, "too many keys")
+    check(lib().lsdsort_reduce_by_key_device(_ptr(d_keys, n), _ptr(d_vals, n), n, key_code, int(bool(descending)), val_type, code,
+                                             _ptr(fixed[0], n), _ptr(fixed[1], n), _ptr(extra[0], n), num.data_ptr(),
+                                             workspace.data_ptr(), workspace.numel(), _stream(stream)), "lsdsort_reduce_by_key_device")
     if check_fault and n:
         _check_fault(workspace, stream, "lsdsort_reduce_by_key_check_device", n, key_code)
-    return (keys, vals) + ((lengths,) if lengths is not None else ()) + (num,)
+    return _run_result(fixed, extra, num)
 
 
-def _contiguous_values(values, n: int, op: str):
-    """The values of the two slicing wrappers: a strided 1-D CUDA tensor is copied, everything else goes to the shared check as it is."""
+def _reduce_sliced(reduce, keys, values, op: str, return_counts: bool):
+    """The body of the two slicing wrappers; ``reduce(keys, values, counts)``: ``GPUReduceByKey`` or ``GPUReduceRuns``.  Strided
+    1-D CUDA tensors are copied; any other ``values`` go to the shared check as they are."""
     torch = _torch()
+    _word_keys(keys, "keys", contiguous=False)
     if isinstance(values, torch.Tensor) and values.is_cuda and values.dim() == 1 and not values.is_contiguous():
         values = values.contiguous()
-    _reduce_values(values, n, op)
-    return values
+    _reduce_values(values, keys.numel(), op)
+    got = _slice_by_count(reduce(keys.contiguous(), values, bool(return_counts)))
+    return tuple(got[:2]) + ((got[2].to(torch.int64),) if return_counts else ())
 
 
 def reduce_by_key(keys, values, op: str = "sum", descending: bool = False, return_counts: bool = False):
@@ -1808,28 +1690,15 @@ def reduce_by_key(keys, values, op: str = "sum", descending: bool = False, retur
     integers and on NaN-free floats whose sums are exact; float sums are deterministic (``GPUReduceByKey``) and differ from a
     sequential sum by rounding.  -0.0 and +0.0 are two keys, every NaN payload is one.  Reads the count once (one synchronisation)
     and slices; ``return_counts`` adds the int64 group sizes."""
-    torch = _torch()
-    _word_keys(keys, "keys", contiguous=False)
-    n = keys.numel()
-    got = GPUReduceByKey(keys.contiguous(), _contiguous_values(values, n, op), op=op, descending=descending, counts=bool(return_counts))
-    m = int(got[-1].item())
-    if return_counts:
-        return got[0][:m], got[1][:m], got[2][:m].to(torch.int64)
-    return got[0][:m], got[1][:m]
+    return _reduce_sliced(lambda k, v, counts: GPUReduceByKey(k, v, op=op, descending=descending, counts=counts), keys, values, op,
+                          return_counts)
 
 
 def reduce_consecutive(keys, values, op: str = "sum", return_counts: bool = False):
     """``(the first key of every run of equal adjacent keys, op of the run's values[, counts])``: ``torch.unique_consecutive`` plus a
     segment reduce, for the tensors ``reduce_by_key`` takes.  One synchronisation (the count).  Keys are equal where their bits are:
     -0.0 and +0.0 end a run, NaN payloads that agree do not."""
-    torch = _torch()
-    _word_keys(keys, "keys", contiguous=False)
-    n = keys.numel()
-    got = GPUReduceRuns(keys.contiguous(), _contiguous_values(values, n, op), op=op, counts=bool(return_counts))
-    m = int(got[-1].item())
-    if return_counts:
-        return got[0][:m], got[1][:m], got[2][:m].to(torch.int64)
-    return got[0][:m], got[1][:m]
+    return _reduce_sliced(lambda k, v, counts: GPUReduceRuns(k, v, op=op, counts=counts), keys, values, op, return_counts)
 
 
 def GPULSDRadixSortTimed(d_keys, r: int = 8, d_vals=None, algorithm: int = LSDSORT_ALGO_ONESWEEP, workspace=None,
@@ -1874,7 +1743,7 @@ def BuildOffsets(d_hist, r: int, stream=None):
     tiles = d_hist.shape[0]
     local = torch.empty_like(d_hist)
     glob = torch.empty_like(d_hist)
-    scratch = _temp_workspace(int(lib().lsdsort_tile_offsets_scratch_bytes(tiles, r)), d_hist.device, None)   # with the outputs
+    scratch = _workspace(None, "lsdsort_tile_offsets_scratch_bytes", (tiles, r), d_hist.device, None, zero_ok=True)   # with the outputs
     check(lib().lsdsort_tile_offsets_u32_device(d_hist.data_ptr(), local.data_ptr(), glob.data_ptr(), tiles, r,
                                                 scratch.data_ptr(), _stream(stream)),
           "lsdsort_tile_offsets_u32_device")
@@ -1914,7 +1783,7 @@ def _partition(entry: str, d_keys, bits: int, stream, *cuts):
     n = d_keys.numel()
     out = torch.empty_like(d_keys)
     counts = torch.zeros(1 << bits, dtype=torch.int64, device=d_keys.device)
-    ws = _temp_workspace(int(lib().lsdsort_msb_partition_workspace_bytes(n, bits)), d_keys.device, None)
+    ws = _workspace(None, "lsdsort_msb_partition_workspace_bytes", (n, bits), d_keys.device, None, zero_ok=True)
     check(getattr(lib(), entry)(d_keys.data_ptr(), out.data_ptr(), n, bits, *cuts, counts.data_ptr(), ws.data_ptr(), ws.numel(),
                                 _stream(stream)), entry)
     if n:
