@@ -16,8 +16,9 @@
 //                       position w * rows * 64 + i * 64 + l, rows = ceil(size / T); positions past the bucket hold 0xFFFFFFFF
 //                       (the highest digit in every pass and the highest positions: they would stay at the end and are never
 //                       stored) and are neither ranked nor scattered (LocalGroup::live, ::inside)
-//   per digit pass    : zero the wave's counters | rank = returning add | barrier | one thread per digit: wave bases + exclusive
-//                       scan over digits | barrier | keys -> LDS at (base + rank) | barrier | read back in position order
+//   per digit pass    : zero the wave's counters | rank = returning add | barrier | one thread per counter word (two digits): wave
+//                       bases + exclusive scan over digits | barrier | keys -> LDS at (base + rank) | barrier | read back in
+//                       position order
 //   store             : from LDS, linear.
 // Counters are 16 bits wide, two to a word (a wave holds at most 2048 keys): 8 waves x 512 digits in 8 KiB, so that two
 // workgroups share a CU (72 KiB each) and one's loads and barriers hide under the other's LDS work.
@@ -160,25 +161,54 @@ __device__ __forceinline__ void count_and_rank(const LocalGroup<K>& g, const uin
     }
     __syncthreads();
 }
-// Counts to bases, one thread per digit: the waves' counts become their bases inside the digit's range, the digits' totals an
-// exclusive scan.
+// Exclusive scan of v over the first `threads` threads of the workgroup (uniform, at most 256; v = 0 in the others).  The form of
+// group_exclusive_scan (lsd_device.hpp) for a scan that few waves take part in: one wave needs no partials and no barrier; with
+// more, only the waves that hold such threads write a partial or read them (four words: at most three waves precede one).
+template <int K>
+__device__ __forceinline__ uint32_t live_exclusive_scan(const LocalGroup<K>& g, uint32_t v, uint32_t threads)
+{
+    const uint32_t incl = wave_inclusive_scan(v);
+    uint32_t before = 0;
+    if (threads > (uint32_t)kWave) {   // uniform
+        const bool live_wave = g.tid - g.lane < threads;
+        if (live_wave && g.lane == 63u) g.s_misc[g.wave] = incl;
+        __syncthreads();
+        if (live_wave) {
+#pragma unroll
+            for (int w = 0; w < 4; w++) {   // a partial at or past this wave's own may be stale: never added
+                const uint32_t t = g.s_misc[w];
+                before += (uint32_t)w < g.wave ? t : 0u;
+            }
+        }
+    }
+    return before + incl - v;
+}
+// Counts to bases, one thread per counter WORD (digits 2j and 2j + 1; bins / 2 threads): the waves' counts become their bases inside
+// the digit's range, the digits' totals an exclusive scan.  The running sum over the waves stays packed, both halves in one add,
+// and so does what is written back: run + (off | (off + low) << 16), off = the keys of the digits below 2j.  Every half is a
+// number of keys of one bucket, at most kLocalSortCap = 16384, so no carry leaves a low half (tests/test_local_bases_cpu.py).
+// Half the LDS instructions of one thread per 16-bit counter, between two barriers where the workgroup's other waves wait.
 template <int K>
 __device__ __forceinline__ void counts_to_bases(const LocalGroup<K>& g, uint32_t bins)
 {
-    constexpr int W = kLocalWaves;
+    constexpr int W = kLocalWaves, HW = kLocalMaxBins / 2;
+    const uint32_t threads = bins >> 1;   // bins is even: a digit has at least one bit
+    const bool mine = g.tid < threads;
     uint32_t total = 0;
     uint32_t wave_excl[W];
-    if (g.tid < bins) {
+    if (mine) {
 #pragma unroll
         for (int w = 0; w < W; w++) {
             wave_excl[w] = total;
-            total += g.s_cnt16[w * kLocalMaxBins + g.tid];
+            total += g.s_cnt[w * HW + g.tid];
         }
     }
-    const uint32_t local_off = group_exclusive_scan<W>(total, g.lane, g.wave, g.s_misc);   // total = 0 past the last digit
-    if (g.tid < bins) {
+    const uint32_t low = total & 0xFFFFu;
+    const uint32_t off = live_exclusive_scan(g, low + (total >> 16), threads);   // total = 0 past the last word
+    if (mine) {
+        const uint32_t add = off | ((off + low) << 16);
 #pragma unroll
-        for (int w = 0; w < W; w++) g.s_cnt16[w * kLocalMaxBins + g.tid] = (uint16_t)(local_off + wave_excl[w]);
+        for (int w = 0; w < W; w++) g.s_cnt[w * HW + g.tid] = wave_excl[w] + add;
     }
     __syncthreads();
 }
