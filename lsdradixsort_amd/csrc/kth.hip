@@ -7,7 +7,8 @@
 //
 // A radix SELECT by counting only, as in topk.hip, and a LOCATE instead of top-k's compact + sort.  The select's skeleton is
 // radix_select.hpp's, shared with topk.hip and topk16.hip, with the stop rule StopKth; the loads (Row<uint32_t> with a validity
-// mask) and locate_tile are select_tiles32.hpp's, shared with kth_multi.hip; this unit adds the count, pick and locate kernels.
+// mask) and locate_tile are select_tiles32.hpp's, shared with kth_multi.hip; this unit adds the count and locate kernels, and
+// names its instantiation of the pick kernel, a template of radix_select.hpp that every single-rank k-th value unit shares.
 //   select   most significant digit first, count the digit of the keys that still match the prefix found so far, walk the counts
 //            from the best end to the bin that holds the wanted key: that bin's digit joins the prefix and `need` (which of the
 //            prefix's keys, in sorted order, is wanted; 1-based) shrinks by the number of keys in better bins.  Unlike top-k it
@@ -41,9 +42,6 @@
 
 namespace lsd {
 namespace {
-
-constexpr uint32_t kKthFaultCount = 1024u;    // fault word: the digit counts of a row do not reach the rank (never expected)
-constexpr uint32_t kKthFaultLocate = 2048u;   // fault word: no key was located for a row (never expected; nothing stored)
 
 struct Outputs {
     uint32_t* keys;       // [rows], raw keys
@@ -190,43 +188,14 @@ __global__ void __launch_bounds__(kLongThreads) kth_count_kernel(const LongParam
     }
 }
 
-// One workgroup per row: the chunk that holds the `need`-th key under the prefix, and which of that chunk's such keys it is.
-__global__ void __launch_bounds__(256) kth_pick_kernel(const LongParams p)
-{
-    __shared__ uint32_t s_part[4];
-    __shared__ uint32_t s_found[2];
-    const uint32_t row = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (row >= p.out.rows) return;
-    const uint4 st = p.state[row];
-    const uint32_t* const counts = p.counts + (size_t)row * p.chunk_cap;
-    constexpr uint32_t E = kMaxChunks / 256u;
-    uint32_t c[E], sum = 0u;
-#pragma unroll
-    for (uint32_t e = 0; e < E; e++) {
-        c[e] = tid * E + e < p.chunks ? counts[tid * E + e] : 0u;
-        sum += c[e];
-    }
-    if (tid == 0u) s_found[0] = kNoChunk;
-    uint32_t run = group_exclusive_scan<4>(sum, lane, wave, s_part);
-    const uint32_t need = st.y < Levels32::kNoLevel ? st.z : 0u;
-#pragma unroll
-    for (uint32_t e = 0; e < E; e++) {
-        if (run < need && need - run <= c[e]) {   // at most one chunk of the row
-            s_found[0] = tid * E + e;
-            s_found[1] = need - run;
-        }
-        run += c[e];
-    }
-    __syncthreads();
-    if (tid != 0u) return;
-    const uint32_t chunk = s_found[0];
-    if (chunk == kNoChunk) {   // the keys under the prefix are fewer than `need`: nothing is located
-        atomicOr(p.out.fault, kKthFaultLocate);
-        p.state[row] = make_uint4(0u, 0u, 0u, kNoChunk);
-        return;
-    }
-    p.state[row] = make_uint4(st.x, st.y, s_found[1], chunk);
-}
+// One workgroup per row: the chunk that holds the `need`-th key under the prefix, and which of that chunk's such keys it is --
+// radix_select.hpp's kernel template, under this unit's name.
+struct Kth {
+    using Levels = Levels32;
+    using Params = LongParams;
+    static constexpr uint32_t kBadW = 0u;   // no row is refused from the start
+};
+constexpr auto kth_pick_kernel = pick_rows_kernel<Kth>;
 
 // One workgroup per row reads the picked chunk, and only up to the tile that holds the key.
 __global__ void __launch_bounds__(kLongThreads) kth_locate_kernel(const LongParams p)

@@ -17,7 +17,8 @@
 //            launches, no count, pick or locate.
 //
 // Key reads, the loaders and locate_tile are select_tiles16.hpp's, shared with every 16-bit row select: a register without a key
-// holds kNoKey, which no (prefix, shift) matches, so kth.hip's validity mask is not needed.
+// holds kNoKey, which no (prefix, shift) matches, so kth.hip's validity mask is not needed.  The long rows' count and locate kernels
+// are that header's too, and the pick is radix_select.hpp's: kernel templates, shared with kth16_rowk.hip, that this unit names.
 // Size classes (those of every select here, by cols):
 //   cols <= kWaveSegCap (1024)      one wavefront per row, eight rows per workgroup, no workgroup barrier.  2 B/key read.
 //   cols <= kLocalSortCap (16384)   one workgroup of 16 wavefronts per row: the same
@@ -40,9 +41,6 @@
 
 namespace lsd {
 namespace {
-
-constexpr uint32_t kKth16FaultCount = 1024u;    // fault word: the digit counts of a row do not reach the rank (never expected)
-constexpr uint32_t kKth16FaultLocate = 2048u;   // fault word: no key was located for a row (never expected; nothing stored)
 
 struct Outputs {
     uint16_t* keys;       // [rows], the caller's 16-bit words
@@ -87,10 +85,10 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) kth16_short_kernel(co
             for (int i = 0; i < kRegs; i++) one(t[i]);
             one(h);
         };
-        const Selected sel = select_short<WAVES, 2, StopKth>(s_cnt, s_found, wave, lane, p.rank + 1u, p.out.fault, kKth16FaultCount, count);
+        const Selected sel = select_short<WAVES, 2, StopKth>(s_cnt, s_found, wave, lane, p.rank + 1u, p.out.fault, kKthFaultCount, count);
         uint32_t base = 0u;
         const bool found = locate_tile<WAVES>(t, h, q0, r, sel.prefix, sel.shift, sel.need, base, s_wc, wave, lane, row, 0u, p.out, p.map);
-        if (!found && sel.need != 0u && wave == 0u && lane == 0u) atomicOr(p.out.fault, kKth16FaultLocate);
+        if (!found && sel.need != 0u && wave == 0u && lane == 0u) atomicOr(p.out.fault, kKthFaultLocate);
         group_sync<WAVES>();
     }
 }
@@ -133,107 +131,25 @@ __global__ void __launch_bounds__(256) kth16_scan_kernel(const LongParams p)
 {
     __shared__ uint32_t s_part[4];
     __shared__ uint32_t s_found[3];
-    scan_level<Levels16, LEVEL, Stop>(p, s_part, s_found, kKth16FaultCount);
+    scan_level<Levels16, LEVEL, Stop>(p, s_part, s_found, kKthFaultCount);
 }
 
-// the keys under the prefix, per chunk
-__global__ void __launch_bounds__(kLongThreads) kth16_count_kernel(const LongParams p)
-{
-    __shared__ uint32_t s_part[kLongWaves];
-    const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
-    if (row >= p.out.rows) return;
-    const uint4 st = p.state[row];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const Row16 r = row_of(p.keys, row, p.cols);
-    const ChunkRange g = chunk_of(r, p.chunk, c);
-    uint32_t ne = 0u;
-    if (st.y < Levels16::kNoLevel && st.z != 0u) {   // (uniform) else: a row no scan has visited, or one whose counts fell short -- never
-        if (c == 0u && wave == 0u) ne += (load_head(r, lane, p.map) >> st.y) == st.x ? 1u : 0u;   // uniform
-        for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
-            uint32_t t[kRegs];
-            load_tile(r, tile + wave * kWaveTile, g.hi, lane, p.map, t);
-#pragma unroll
-            for (int i = 0; i < kRegs; i++) ne += (t[i] >> st.y) == st.x ? 1u : 0u;
-        }
-    }
-    ne = wave_sum(ne);
-    if (lane == 0u) s_part[wave] = ne;
-    __syncthreads();
-    if (tid == 0u) {
-        uint32_t e = 0u;
-        for (uint32_t w = 0; w < kLongWaves; w++) e += s_part[w];
-        p.counts[(size_t)row * p.chunk_cap + c] = e;
-    }
-}
-
-// One workgroup per row: the chunk that holds the `need`-th key under the prefix, and which of that chunk's such keys it is.
-__global__ void __launch_bounds__(256) kth16_pick_kernel(const LongParams p)
-{
-    __shared__ uint32_t s_part[4];
-    __shared__ uint32_t s_found[2];
-    const uint32_t row = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (row >= p.out.rows) return;
-    const uint4 st = p.state[row];
-    const uint32_t* const counts = p.counts + (size_t)row * p.chunk_cap;
-    constexpr uint32_t E = kMaxChunks / 256u;
-    uint32_t c[E], sum = 0u;
-#pragma unroll
-    for (uint32_t e = 0; e < E; e++) {
-        c[e] = tid * E + e < p.chunks ? counts[tid * E + e] : 0u;
-        sum += c[e];
-    }
-    if (tid == 0u) s_found[0] = kNoChunk;
-    uint32_t run = group_exclusive_scan<4>(sum, lane, wave, s_part);
-    const uint32_t need = st.y < Levels16::kNoLevel ? st.z : 0u;
-#pragma unroll
-    for (uint32_t e = 0; e < E; e++) {
-        if (run < need && need - run <= c[e]) {   // at most one chunk of the row
-            s_found[0] = tid * E + e;
-            s_found[1] = need - run;
-        }
-        run += c[e];
-    }
-    __syncthreads();
-    if (tid != 0u) return;
-    const uint32_t chunk = s_found[0];
-    if (chunk == kNoChunk) {   // the keys under the prefix are fewer than `need`: nothing is located
-        atomicOr(p.out.fault, kKth16FaultLocate);
-        p.state[row] = make_uint4(0u, 0u, 0u, kNoChunk);
-        return;
-    }
-    p.state[row] = make_uint4(st.x, st.y, s_found[1], chunk);
-}
-
-// One workgroup per row reads the picked chunk, and only up to the tile that holds the key.
-__global__ void __launch_bounds__(kLongThreads) kth16_locate_kernel(const LongParams p)
-{
-    __shared__ uint32_t s_wc_raw[kLongWaves];
-    const uint32_t row = blockIdx.x;
-    if (row >= p.out.rows) return;
-    const uint4 st = p.state[row];
-    if (st.z == 0u || st.w >= p.chunks) return;   // (uniform) nothing was picked: the fault bit is already set
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const Row16 r = row_of(p.keys, row, p.cols);
-    const ChunkRange g = chunk_of(r, p.chunk, st.w);
-    volatile lds_u32* const s_wc = (volatile lds_u32*)(lds_u32*)s_wc_raw;
-    uint32_t base = 0u;
-    bool found = false;
-    // chunk 0 has at least one tile (a long row's body is longer than its head), and its first tile carries the head
-    for (uint32_t tile = g.lo; tile < g.hi && !found; tile += kLongTile) {   // uniform
-        const uint32_t q0 = tile + wave * kWaveTile;
-        uint32_t t[kRegs];
-        load_tile(r, q0, g.hi, lane, p.map, t);
-        const uint32_t h = (st.w == 0u && tile == g.lo && wave == 0u) ? load_head(r, lane, p.map) : kNoKey;   // uniform
-        found = locate_tile<(int)kLongWaves>(t, h, q0, r, st.x, st.y, st.z, base, s_wc, wave, lane, row, 0u, p.out, p.map);
-    }
-    if (!found && tid == 0u) atomicOr(p.out.fault, kKth16FaultLocate);
-}
+// Count (the keys under the prefix, per chunk), pick (the chunk that holds the `need`-th of them) and locate (that ONE chunk, up to
+// the tile that holds the key): the kernel templates of select_tiles16.hpp and radix_select.hpp, under this unit's name.
+struct Kth16 {
+    using Levels = Levels16;
+    using Params = LongParams;
+    static constexpr uint32_t kBadW = 0u;   // no row is refused from the start
+};
+constexpr auto kth16_count_kernel = count_rows16_kernel<Kth16>;
+constexpr auto kth16_pick_kernel = pick_rows_kernel<Kth16>;
+constexpr auto kth16_locate_kernel = locate_rows16_kernel<Kth16>;
 
 // Values only: after both levels the prefix is the row's whole sortable value (shift 0, need not 0).  Anything else is a row whose
 // counts fell short (its fault bit is set) or one no scan has visited -- never: nothing is stored for it.
 __global__ void __launch_bounds__(256) kth16_value_kernel(const LongParams p)
 {
-    store_values16<0u>(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, p, kKth16FaultLocate, 0u);
+    store_values16<0u>(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, p, kKthFaultLocate, 0u);
 }
 
 // Workspace: control | row states (16 B per row) | counters [rows][2048] | chunk counts (4 B per chunk) -- the last two for rows

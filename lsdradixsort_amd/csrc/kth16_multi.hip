@@ -33,11 +33,13 @@
 // returning add: the result does not depend on lsdsort_set_rank_method.
 //
 // load_tile, load_head and locate_tile are select_tiles16.hpp's, shared with the other 16-bit row selects; Outputs::at gives
-// locate_tile the slot's place in the outputs.
+// locate_tile the slot's place in the outputs.  The slots themselves -- Needs, Outputs, SlotStates, leaders(), leader_of(), the pick
+// kernel, the entry's checks of the ranks and the short rows' launches -- are kth_slots.hpp's, shared with kth_multi.hip.
 #define LSDSORT_BUILD 1
 #include "../../include/lsdsort.h"
 
 #include "keys16_map.hpp"
+#include "kth_slots.hpp"
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
 #include "radix_select.hpp"
@@ -46,31 +48,7 @@
 namespace lsd {
 namespace {
 
-constexpr uint32_t kKth16FaultCount = 1024u;    // fault word: the digit counts of a row do not reach a rank (never expected)
-constexpr uint32_t kKth16FaultLocate = 2048u;   // fault word: nothing located for a slot, or a values-only state is no whole value
-constexpr int kMaxSlots = LSDSORT_KTH_MAX_RANKS;
 constexpr uint32_t kBins1 = 1u << Levels16::bits(1);   // level 1: 32 counters per leader
-
-// need[j] = ranks[j] + 1: which key of the row slot j wants, 1-based.  A kernel argument; need_of() reads it by a chain of selects, so
-// that no kernel indexes its arguments by a run-time value.
-struct Needs {
-    uint32_t v[kMaxSlots];
-};
-__device__ __forceinline__ uint32_t need_of(const Needs& n, uint32_t j)
-{
-    uint32_t v = n.v[0];
-#pragma unroll
-    for (int i = 1; i < kMaxSlots; i++) v = j == (uint32_t)i ? n.v[i] : v;
-    return v;
-}
-
-struct Outputs {
-    uint16_t* keys;       // [rows][slots], the caller's 16-bit words
-    uint32_t* idx;        // [rows][slots] positions, may be null
-    uint32_t rows, slots;
-    uint32_t* fault;
-    __device__ __forceinline__ size_t at(uint32_t row, uint32_t slot) const { return (size_t)row * slots + slot; }   // locate_tile's store
-};
 
 // ---- short rows: one wavefront (WAVES = 1, eight rows per workgroup) or one workgroup (WAVES = 16) per row ----------------------
 struct ShortParams {
@@ -78,7 +56,7 @@ struct ShortParams {
     uint32_t cols;
     Needs need;
     Key16Map map;
-    Outputs out;
+    Outputs<uint16_t> out;
 };
 
 // The slot loop keeps the row's registers live across the select AND the locate; as in kth_multi.hip the hint asks for that unit's
@@ -120,11 +98,11 @@ kth16m_short_kernel(const ShortParams p)
 #pragma unroll
             for (int i = 0; i < kRegs; i++) asm volatile("" : "+v"(t[i]));
             const Selected sel =
-                select_short<WAVES, 2, StopKth>(s_cnt, s_found, wave, lane, need_of(p.need, slot), p.out.fault, kKth16FaultCount, count);
+                select_short<WAVES, 2, StopKth>(s_cnt, s_found, wave, lane, need_of(p.need, slot), p.out.fault, kKthFaultCount, count);
             uint32_t base = 0u;
             const bool found =
                 locate_tile<WAVES>(t, h, q0, r, sel.prefix, sel.shift, sel.need, base, s_wc, wave, lane, row, slot, p.out, p.map);
-            if (!found && sel.need != 0u && wave == 0u && lane == 0u) atomicOr(p.out.fault, kKth16FaultLocate);
+            if (!found && sel.need != 0u && wave == 0u && lane == 0u) atomicOr(p.out.fault, kKthFaultLocate);
             group_sync<WAVES>();
         }
     }
@@ -144,41 +122,8 @@ struct LongParams {
     uint32_t* hist1;              // [rows][slots][kBins1]: the low 5 bits under a leader's prefix; zero on entry
     uint32_t* counts;             // [rows][slots][chunk_cap]: keys under the prefix, per chunk; only the final leaders' are written
     Key16Map map;
-    Outputs out;
+    Outputs<uint16_t> out;
 };
-
-// The states of a row's slots, for the kernels that test every key against all of them: kMaxSlots registers each, uniform over the
-// workgroup.  Slots from `slots` on are done and match nothing.
-struct SlotStates {
-    uint32_t prefix[kMaxSlots], shift[kMaxSlots];
-    bool live[kMaxSlots];   // the select goes on (w == 0)
-};
-__device__ __forceinline__ SlotStates slot_states(const LongParams& p, uint32_t row)
-{
-    SlotStates s;
-#pragma unroll
-    for (int l = 0; l < kMaxSlots; l++) {
-        uint4 st = make_uint4(0u, 0u, 0u, 1u);
-        if ((uint32_t)l < p.out.slots) st = p.state[(size_t)row * p.out.slots + l];   // uniform
-        s.prefix[l] = st.x;
-        s.shift[l] = st.y;
-        s.live[l] = st.w == 0u;
-    }
-    return s;
-}
-// Bit l: slot l is a leader -- it takes part (`in[l]`) and no lower slot that takes part has the same (prefix, shift).
-__device__ __forceinline__ uint32_t leaders(const SlotStates& s, const bool (&in)[kMaxSlots])
-{
-    uint32_t lead = 0u;
-#pragma unroll
-    for (int l = 0; l < kMaxSlots; l++) {
-        bool first = in[l];
-#pragma unroll
-        for (int i = 0; i < l; i++) first = first && !(in[i] && s.prefix[i] == s.prefix[l] && s.shift[i] == s.shift[l]);
-        lead |= first ? 1u << l : 0u;
-    }
-    return lead;
-}
 
 // control block, both histograms (one stretch of the workspace) and slot states of a call (a kernel rather than memsets: one kind of
 // node in a captured graph)
@@ -264,7 +209,7 @@ __global__ void __launch_bounds__(256) kth16m_scan0_kernel(const LongParams p)
     if (tid >= slots) return;
     const uint32_t bin = s_found[tid][0], before = s_found[tid][1], count = s_found[tid][2];
     if (bin >= kBins) {   // no bin of the walk: nothing is selected
-        atomicOr(p.out.fault, kKth16FaultCount);
+        atomicOr(p.out.fault, kKthFaultCount);
         state[tid] = make_uint4(0u, 0u, 0u, 1u);
         return;
     }
@@ -283,7 +228,7 @@ __global__ void __launch_bounds__(kLongThreads) kth16m_hist1_kernel(const LongPa
     __shared__ uint32_t s_hist[kMaxSlots * kBins1];
     const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
     if (row >= p.out.rows) return;
-    const SlotStates s = slot_states(p, row);
+    const SlotStates<kMaxSlots> s = slot_states<kMaxSlots>(p, row);
     bool in[kMaxSlots];
 #pragma unroll
     for (int l = 0; l < kMaxSlots; l++) in[l] = s.live[l] && s.shift[l] == kUp;
@@ -330,16 +275,6 @@ __global__ void __launch_bounds__(kLongThreads) kth16m_hist1_kernel(const LongPa
     if (v != 0u && l < p.out.slots) atomicAdd(p.hist1 + ((size_t)row * p.out.slots + l) * kBins1 + (tid % kBins1), v);
 }
 
-// the lowest live slot of the row with slot j's (prefix, shift): j itself, or the slot whose counters j's keys were counted into
-// (the histogram kernel's leaders() on the same states: there a live slot also has to carry level 0's shift, which every live slot
-// does -- one that did not would find its counters empty here and raise the count fault)
-__device__ __forceinline__ uint32_t leader_of(const uint4* st, uint32_t j)
-{
-    for (uint32_t i = 0; i < j; i++)
-        if (st[i].w == 0u && st[i].x == st[j].x && st[i].y == st[j].y) return i;
-    return j;
-}
-
 // Level 1, one wavefront per row: for every live slot, lane b holds bin b of its leader's 32 counters; the lane whose bin holds the
 // slot's key stores the state.  All states of the row are read before any is written.  The last level ends the select.
 __global__ void __launch_bounds__(64) kth16m_scan1_kernel(const LongParams p)
@@ -361,7 +296,7 @@ __global__ void __launch_bounds__(64) kth16m_scan1_kernel(const LongParams p)
         const bool hit = lane < kBins1 && run < need && need - run <= c;   // at most one bin of the walk
         if (hit) state[j] = make_uint4((st.x << Levels16::bits(1)) | lane, Levels16::shift(1), need - run, 1u);
         if (__ballot(hit) == 0ull && lane == 0u) {   // no bin of the walk: nothing is selected
-            atomicOr(p.out.fault, kKth16FaultCount);
+            atomicOr(p.out.fault, kKthFaultCount);
             state[j] = make_uint4(0u, 0u, 0u, 1u);
         }
     }
@@ -374,7 +309,7 @@ __global__ void __launch_bounds__(kLongThreads) kth16m_count_kernel(const LongPa
     __shared__ uint32_t s_part[kMaxSlots * kLongWaves];
     const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
     if (row >= p.out.rows) return;
-    const SlotStates s = slot_states(p, row);
+    const SlotStates<kMaxSlots> s = slot_states<kMaxSlots>(p, row);
     bool in[kMaxSlots];   // a slot no scan has visited (never) is not counted: its shift is no shift
 #pragma unroll
     for (int l = 0; l < kMaxSlots; l++) in[l] = (uint32_t)l < p.out.slots && s.shift[l] < Levels16::kNoLevel;
@@ -437,54 +372,12 @@ __global__ void __launch_bounds__(kLongThreads) kth16m_count_kernel(const LongPa
     }
 }
 
-// One workgroup per (row, slot): the chunk that holds the `need`-th key under the slot's prefix, and which of that chunk's such
-// keys it is.  The chunk counts are those of the lowest slot of the row with the same (prefix, shift).  The workgroups of a row read
-// one another's (prefix, shift) while they run, so a pick stores z and w ALONE: no word is read by one workgroup and written by
-// another.
-__global__ void __launch_bounds__(256) kth16m_pick_kernel(const LongParams p)
-{
-    __shared__ uint32_t s_part[4];
-    __shared__ uint32_t s_found[2];
-    const uint32_t slots = p.out.slots, row = blockIdx.x / slots, slot = blockIdx.x % slots;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (row >= p.out.rows) return;
-    uint4* const state = p.state + (size_t)row * slots;
-    const uint2 xy = *reinterpret_cast<const uint2*>(&state[slot].x);
-    uint32_t lead = slot;
-    for (uint32_t i = slot; i-- > 0u;) {   // uniform
-        const uint2 o = *reinterpret_cast<const uint2*>(&state[i].x);
-        if (o.x == xy.x && o.y == xy.y) lead = i;
-    }
-    const uint32_t* const counts = p.counts + ((size_t)row * slots + lead) * p.chunk_cap;
-    constexpr uint32_t E = kMaxChunks / 256u;
-    uint32_t c[E], sum = 0u;
-    const uint32_t need = xy.y < Levels16::kNoLevel ? state[slot].z : 0u;
-#pragma unroll
-    for (uint32_t e = 0; e < E; e++) {
-        c[e] = (need != 0u && tid * E + e < p.chunks) ? counts[tid * E + e] : 0u;
-        sum += c[e];
-    }
-    if (tid == 0u) s_found[0] = kNoChunk;
-    uint32_t run = group_exclusive_scan<4>(sum, lane, wave, s_part);
-#pragma unroll
-    for (uint32_t e = 0; e < E; e++) {
-        if (run < need && need - run <= c[e]) {   // at most one chunk of the row
-            s_found[0] = tid * E + e;
-            s_found[1] = need - run;
-        }
-        run += c[e];
-    }
-    __syncthreads();
-    if (tid != 0u) return;
-    const uint32_t chunk = s_found[0];
-    uint2* const zw = reinterpret_cast<uint2*>(&state[slot].z);
-    if (chunk == kNoChunk) {   // the keys under the prefix are fewer than `need`: nothing is located
-        atomicOr(p.out.fault, kKth16FaultLocate);
-        *zw = make_uint2(0u, kNoChunk);
-        return;
-    }
-    *zw = make_uint2(s_found[1], chunk);
-}
+// One workgroup per (row, slot): the chunk that holds the slot's key -- kth_slots.hpp's kernel template, under this unit's name.
+struct Kth16Multi {
+    using Levels = Levels16;
+    using Params = LongParams;
+};
+constexpr auto kth16m_pick_kernel = pick_slots_kernel<Kth16Multi>;
 
 // One workgroup per (row, slot) reads the picked chunk, and only up to the tile that holds the key.
 __global__ void __launch_bounds__(kLongThreads) kth16m_locate_kernel(const LongParams p)
@@ -508,7 +401,7 @@ __global__ void __launch_bounds__(kLongThreads) kth16m_locate_kernel(const LongP
         const uint32_t h = (st.w == 0u && tile == g.lo && wave == 0u) ? load_head(r, lane, p.map) : kNoKey;   // uniform
         found = locate_tile<(int)kLongWaves>(t, h, q0, r, st.x, st.y, st.z, base, s_wc, wave, lane, row, slot, p.out, p.map);
     }
-    if (!found && tid == 0u) atomicOr(p.out.fault, kKth16FaultLocate);
+    if (!found && tid == 0u) atomicOr(p.out.fault, kKthFaultLocate);
 }
 
 // Values only: after both levels the prefix is the slot's whole sortable value (shift 0, need not 0).  Anything else is a slot whose
@@ -519,7 +412,7 @@ __global__ void __launch_bounds__(256) kth16m_value_kernel(const LongParams p)
     for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
         const uint4 st = p.state[s];
         if (st.y == 0u && st.z != 0u) p.out.keys[s] = (uint16_t)from_sortable16(st.x & 0xFFFFu, p.map);
-        else atomicOr(p.out.fault, kKth16FaultLocate);
+        else atomicOr(p.out.fault, kKthFaultLocate);
     }
 }
 
@@ -546,16 +439,12 @@ int run_kth16_multi(const uint16_t* keys, size_t rows, size_t cols, const Needs&
                     uint16_t* out_keys, uint32_t* out_idx, char* ws, const Kth16mLayout& L, hipStream_t stream)
 {
     uint32_t* const ctl = reinterpret_cast<uint32_t*>(ws);
-    const Outputs out{out_keys, out_idx, (uint32_t)rows, (uint32_t)slots, ctl};
+    const Outputs<uint16_t> out{out_keys, out_idx, (uint32_t)rows, (uint32_t)slots, ctl};
     if (cols <= (size_t)kLocalSortCap) {
         const ShortParams sp{keys, (uint32_t)cols, need, map, out};
-        hipLaunchKernelGGL(kth16m_clear_kernel, dim3(1), dim3(256), 0, stream, ctl, (uint32_t*)nullptr, 0u, (uint4*)nullptr, 0u, 0u, need);
         if (cols <= (size_t)kWaveSegCap)
-            hipLaunchKernelGGL(kth16m_short_kernel<1>, dim3(grid_for(rows, 8, 16384)), dim3(512), 0, stream, sp);
-        else
-            hipLaunchKernelGGL(kth16m_short_kernel<16>, dim3(grid_for(rows, 1, 4096)), dim3(1024), 0, stream, sp);
-        LSD_HIP(hipGetLastError());
-        return LSDSORT_OK;
+            return launch_short_slots(kth16m_clear_kernel, ctl, kth16m_short_kernel<1>, dim3(grid_for(rows, 8, 16384)), dim3(512), sp, stream);
+        return launch_short_slots(kth16m_clear_kernel, ctl, kth16m_short_kernel<16>, dim3(grid_for(rows, 1, 4096)), dim3(1024), sp, stream);
     }
     const Chunks ch = chunks_for(rows, cols);
     LongParams lp{};
@@ -595,12 +484,6 @@ int run_kth16_multi(const uint16_t* keys, size_t rows, size_t cols, const Needs&
     return LSDSORT_OK;
 }
 
-bool kth16m_too_large(size_t rows, size_t cols, size_t slots)
-{
-    if (rows > LSDSORT_MAX_KEYS) return true;
-    return rows != 0 && (cols > LSDSORT_MAX_KEYS / rows || slots > LSDSORT_MAX_KEYS / rows);
-}
-
 }  // namespace
 }  // namespace lsd
 
@@ -608,7 +491,7 @@ extern "C" {
 
 size_t lsdsort_kth16_multi_workspace_bytes(size_t rows, size_t cols, size_t num_ranks)
 {
-    if (num_ranks > LSDSORT_KTH_MAX_RANKS || cols > LSDSORT_MAX_KEYS || lsd::kth16m_too_large(rows, cols, num_ranks)) return 0;
+    if (num_ranks > LSDSORT_KTH_MAX_RANKS || cols > LSDSORT_MAX_KEYS || lsd::multi_too_large(rows, cols, num_ranks)) return 0;
     return lsd::kth16m_layout(rows, cols, num_ranks).end;
 }
 
@@ -619,14 +502,10 @@ int lsdsort_kth16_multi_device(const void* d_keys, size_t rows, size_t cols, con
     Key16Map map;
     LSD_TRY(key16_map(key_type, largest, &map));
     if (num_ranks > LSDSORT_KTH_MAX_RANKS) return LSDSORT_ERR_INVALID_ARG;
-    if (lsd::kth16m_too_large(rows, cols, num_ranks)) return LSDSORT_ERR_TOO_LARGE;
+    if (lsd::multi_too_large(rows, cols, num_ranks)) return LSDSORT_ERR_TOO_LARGE;
     if (rows == 0 || cols == 0 || num_ranks == 0) return LSDSORT_OK;   // before the ranks: an empty row has no valid rank
-    if (!ranks) return LSDSORT_ERR_INVALID_ARG;
-    lsd::Needs need{};
-    for (size_t j = 0; j < num_ranks; j++) {
-        if (ranks[j] >= cols) return LSDSORT_ERR_INVALID_ARG;
-        need.v[j] = (uint32_t)ranks[j] + 1u;
-    }
+    lsd::Needs need;
+    LSD_TRY(lsd::needs_from_ranks(ranks, num_ranks, cols, &need));
     if (!d_keys || !d_out_keys || (((uintptr_t)d_keys | (uintptr_t)d_out_keys) & 1)) return LSDSORT_ERR_INVALID_ARG;
     const lsd::Kth16mLayout L = lsd::kth16m_layout(rows, cols, num_ranks);
     if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.end)) return LSDSORT_ERR_WORKSPACE;

@@ -27,8 +27,9 @@
 // off" (state w = kOffRow), the row is copied, or left alone in place.
 //
 // The loaders, locate_tile, the filter's stores, the hist-level body and the value kernel's body are select_tiles16.hpp's, shared
-// with the other 16-bit row selects.  The count, pick and locate kernels still follow kth16.hip's line by line, pick with the
-// bad-rank branch in front: as shared bodies they compile to other code.  Every launch is sized from (rows,
+// with the other 16-bit row selects.  The count, pick and locate kernels are kth16.hip's too: kernel templates (count_rows16_kernel
+// and locate_rows16_kernel there, pick_rows_kernel in radix_select.hpp), the pick with this unit's bad-rank branch in front, behind
+// `if constexpr` on the unit.  Every launch is sized from (rows,
 // cols) and from whether an index buffer was given; phases are ordered by kernel boundaries; every store into the outputs is guarded
 // by row < rows and stays within the row.  Nothing here ranks with the returning add: the result does not depend on
 // lsdsort_set_rank_method.
@@ -44,8 +45,6 @@
 namespace lsd {
 namespace {
 
-constexpr uint32_t kRowkFaultCount = 1024u;    // fault word: the digit counts of a row do not reach the rank (never expected)
-constexpr uint32_t kRowkFaultLocate = 2048u;   // fault word: no key was located for a row (never expected; nothing stored)
 constexpr uint32_t kRowkFaultRank = 4096u;     // fault word: d_ranks[r] >= cols for some row (the caller's error; nothing stored for it)
 constexpr uint32_t kBadRow = 2u, kOffRow = 3u; // row state w: done from the start (1: the select stopped or fell short)
 
@@ -101,10 +100,10 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) kth16r_short_kernel(c
             for (int i = 0; i < kRegs; i++) one(t[i]);
             one(h);
         };
-        const Selected sel = select_short<WAVES, 2, StopKth>(s_cnt, s_found, wave, lane, rank + 1u, p.out.fault, kRowkFaultCount, count);
+        const Selected sel = select_short<WAVES, 2, StopKth>(s_cnt, s_found, wave, lane, rank + 1u, p.out.fault, kKthFaultCount, count);
         uint32_t base = 0u;
         const bool found = locate_tile<WAVES>(t, h, q0, r, sel.prefix, sel.shift, sel.need, base, s_wc, wave, lane, row, 0u, p.out, p.map);
-        if (!found && sel.need != 0u && wave == 0u && lane == 0u) atomicOr(p.out.fault, kRowkFaultLocate);
+        if (!found && sel.need != 0u && wave == 0u && lane == 0u) atomicOr(p.out.fault, kKthFaultLocate);
         group_sync<WAVES>();
     }
 }
@@ -142,7 +141,7 @@ __global__ void __launch_bounds__(WAVES == 1 ? 512 : 1024) topk16f_short_kernel(
                 for (int i = 0; i < kRegs; i++) one(t[i]);
                 one(h);
             };
-            const Selected sel = select_short<WAVES, 2, StopKth>(s_cnt, s_found, wave, lane, k, p.out.fault, kRowkFaultCount, count);
+            const Selected sel = select_short<WAVES, 2, StopKth>(s_cnt, s_found, wave, lane, k, p.out.fault, kKthFaultCount, count);
             prefix = sel.prefix;
             shift = sel.shift;
             selected = sel.need != 0u;   // else the counts fell short (never; the fault bit is set): nothing is stored
@@ -206,116 +205,26 @@ __global__ void __launch_bounds__(256) kth16r_scan_kernel(const LongParams p)
 {
     __shared__ uint32_t s_part[4];
     __shared__ uint32_t s_found[3];
-    scan_level<Levels16, LEVEL, Stop>(p, s_part, s_found, kRowkFaultCount);
+    scan_level<Levels16, LEVEL, Stop>(p, s_part, s_found, kKthFaultCount);
 }
 
-// the keys under the prefix, per chunk
-__global__ void __launch_bounds__(kLongThreads) kth16r_count_kernel(const LongParams p)
-{
-    __shared__ uint32_t s_part[kLongWaves];
-    const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
-    if (row >= p.out.rows) return;
-    const uint4 st = p.state[row];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const Row16 r = row_of(p.keys, row, p.cols);
-    const ChunkRange g = chunk_of(r, p.chunk, c);
-    uint32_t ne = 0u;
-    if (st.y < Levels16::kNoLevel && st.z != 0u) {   // (uniform) else: a row with a rank outside it, or one whose counts fell short
-        if (c == 0u && wave == 0u) ne += (load_head(r, lane, p.map) >> st.y) == st.x ? 1u : 0u;   // uniform
-        for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
-            uint32_t t[kRegs];
-            load_tile(r, tile + wave * kWaveTile, g.hi, lane, p.map, t);
-#pragma unroll
-            for (int i = 0; i < kRegs; i++) ne += (t[i] >> st.y) == st.x ? 1u : 0u;
-        }
-    }
-    ne = wave_sum(ne);
-    if (lane == 0u) s_part[wave] = ne;
-    __syncthreads();
-    if (tid == 0u) {
-        uint32_t e = 0u;
-        for (uint32_t w = 0; w < kLongWaves; w++) e += s_part[w];
-        p.counts[(size_t)row * p.chunk_cap + c] = e;
-    }
-}
-
-// One workgroup per row: the chunk that holds the `need`-th key under the prefix, and which of that chunk's such keys it is.  A row
-// whose rank lies outside it is reported here, by its own bit, and has nothing picked.
-__global__ void __launch_bounds__(256) kth16r_pick_kernel(const LongParams p)
-{
-    __shared__ uint32_t s_part[4];
-    __shared__ uint32_t s_found[2];
-    const uint32_t row = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (row >= p.out.rows) return;
-    const uint4 st = p.state[row];
-    if (st.y == Levels16::kNoLevel && st.w == kBadRow) {   // uniform
-        if (tid == 0u) {
-            atomicOr(p.out.fault, kRowkFaultRank);
-            p.state[row] = make_uint4(0u, 0u, 0u, kNoChunk);
-        }
-        return;
-    }
-    const uint32_t* const counts = p.counts + (size_t)row * p.chunk_cap;
-    constexpr uint32_t E = kMaxChunks / 256u;
-    uint32_t c[E], sum = 0u;
-#pragma unroll
-    for (uint32_t e = 0; e < E; e++) {
-        c[e] = tid * E + e < p.chunks ? counts[tid * E + e] : 0u;
-        sum += c[e];
-    }
-    if (tid == 0u) s_found[0] = kNoChunk;
-    uint32_t run = group_exclusive_scan<4>(sum, lane, wave, s_part);
-    const uint32_t need = st.y < Levels16::kNoLevel ? st.z : 0u;
-#pragma unroll
-    for (uint32_t e = 0; e < E; e++) {
-        if (run < need && need - run <= c[e]) {   // at most one chunk of the row
-            s_found[0] = tid * E + e;
-            s_found[1] = need - run;
-        }
-        run += c[e];
-    }
-    __syncthreads();
-    if (tid != 0u) return;
-    const uint32_t chunk = s_found[0];
-    if (chunk == kNoChunk) {   // the keys under the prefix are fewer than `need`: nothing is located
-        atomicOr(p.out.fault, kRowkFaultLocate);
-        p.state[row] = make_uint4(0u, 0u, 0u, kNoChunk);
-        return;
-    }
-    p.state[row] = make_uint4(st.x, st.y, s_found[1], chunk);
-}
-
-// One workgroup per row reads the picked chunk, and only up to the tile that holds the key.
-__global__ void __launch_bounds__(kLongThreads) kth16r_locate_kernel(const LongParams p)
-{
-    __shared__ uint32_t s_wc_raw[kLongWaves];
-    const uint32_t row = blockIdx.x;
-    if (row >= p.out.rows) return;
-    const uint4 st = p.state[row];
-    if (st.z == 0u || st.w >= p.chunks) return;   // (uniform) nothing was picked: the pick has set the row's fault bit
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const Row16 r = row_of(p.keys, row, p.cols);
-    const ChunkRange g = chunk_of(r, p.chunk, st.w);
-    volatile lds_u32* const s_wc = (volatile lds_u32*)(lds_u32*)s_wc_raw;
-    uint32_t base = 0u;
-    bool found = false;
-    // chunk 0 has at least one tile (a long row's body is longer than its head), and its first tile carries the head
-    for (uint32_t tile = g.lo; tile < g.hi && !found; tile += kLongTile) {   // uniform
-        const uint32_t q0 = tile + wave * kWaveTile;
-        uint32_t t[kRegs];
-        load_tile(r, q0, g.hi, lane, p.map, t);
-        const uint32_t h = (st.w == 0u && tile == g.lo && wave == 0u) ? load_head(r, lane, p.map) : kNoKey;   // uniform
-        found = locate_tile<(int)kLongWaves>(t, h, q0, r, st.x, st.y, st.z, base, s_wc, wave, lane, row, 0u, p.out, p.map);
-    }
-    if (!found && tid == 0u) atomicOr(p.out.fault, kRowkFaultLocate);
-}
+// Count, pick and locate are kth16.hip's: the kernel templates of select_tiles16.hpp and radix_select.hpp, under this unit's name.
+// Count and locate pass a row whose rank lies outside it by; the pick reports it, by its own bit, and has nothing picked for it.
+struct Kth16Rowk {
+    using Levels = Levels16;
+    using Params = LongParams;
+    static constexpr uint32_t kBadW = kBadRow, kFaultBad = kRowkFaultRank;
+};
+constexpr auto kth16r_count_kernel = count_rows16_kernel<Kth16Rowk>;
+constexpr auto kth16r_pick_kernel = pick_rows_kernel<Kth16Rowk>;
+constexpr auto kth16r_locate_kernel = locate_rows16_kernel<Kth16Rowk>;
 
 // Values only: after both levels the prefix is the row's whole sortable value (shift 0, need not 0).  A row whose rank lies outside
 // it is reported by its own bit; anything else is a row whose counts fell short (its fault bit is set) -- never.  Nothing is stored
 // for either.
 __global__ void __launch_bounds__(256) kth16r_value_kernel(const LongParams p)
 {
-    store_values16<kBadRow>(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, p, kRowkFaultLocate, kRowkFaultRank);
+    store_values16<kBadRow>(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, p, kKthFaultLocate, kRowkFaultRank);
 }
 
 // The filter over one chunk of one row per workgroup, the chunks of the select: after both levels the state holds the row's whole

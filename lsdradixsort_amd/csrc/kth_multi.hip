@@ -28,10 +28,12 @@
 // a fault bit instead -- never expected.  Nothing here needs the returning-add rank form.
 //
 // load_tile, load_head and locate_tile are select_tiles32.hpp's, shared with kth.hip; Outputs::at gives locate_tile the slot's place
-// in the outputs.
+// in the outputs.  The slots themselves -- Needs, Outputs, SlotStates, leaders(), leader_of(), the pick kernel, the entry's checks of
+// the ranks and the short rows' launches -- are kth_slots.hpp's, shared with kth16_multi.hip.
 #define LSDSORT_BUILD 1
 #include "../../include/lsdsort.h"
 
+#include "kth_slots.hpp"
 #include "lsd_device.hpp"
 #include "lsd_host.hpp"
 #include "radix_select.hpp"
@@ -40,38 +42,13 @@
 namespace lsd {
 namespace {
 
-constexpr uint32_t kKthFaultCount = 1024u;    // fault word: the digit counts of a row do not reach a rank (never expected)
-constexpr uint32_t kKthFaultLocate = 2048u;   // fault word: no key was located for a slot (never expected; nothing stored)
-constexpr int kMaxSlots = LSDSORT_KTH_MAX_RANKS;
-
-// need[j] = ranks[j] + 1: which key of the row slot j wants, 1-based.  A kernel argument; need_of() reads it by a chain of selects, so
-// that no kernel indexes its arguments by a run-time value.
-struct Needs {
-    uint32_t v[kMaxSlots];
-};
-__device__ __forceinline__ uint32_t need_of(const Needs& n, uint32_t j)
-{
-    uint32_t v = n.v[0];
-#pragma unroll
-    for (int i = 1; i < kMaxSlots; i++) v = j == (uint32_t)i ? n.v[i] : v;
-    return v;
-}
-
-struct Outputs {
-    uint32_t* keys;       // [rows][slots], raw keys
-    uint32_t* idx;        // [rows][slots] positions, may be null
-    uint32_t rows, slots;
-    uint32_t* fault;
-    __device__ __forceinline__ size_t at(uint32_t row, uint32_t slot) const { return (size_t)row * slots + slot; }   // locate_tile's store
-};
-
 // ---- short rows: one wavefront (WAVES = 1, eight rows per workgroup) or one workgroup (WAVES = 16) per row ----------------------
 struct ShortParams {
     const uint32_t* keys;
     uint32_t cols;
     Needs need;
     KeyTransform xf;
-    Outputs out;
+    Outputs<uint32_t> out;
 };
 
 // The slot loop keeps the row's registers live across the select AND the locate, and left to itself the register allocator takes what
@@ -133,44 +110,8 @@ struct LongParams {
     uint32_t* hist;               // [rows][slots][kBins], zero on entry to every level; only a level's leaders are counted into
     uint32_t* counts;             // [rows][slots][chunk_cap]: keys under the prefix, per chunk; only the final leaders' are written
     KeyTransform xf;
-    Outputs out;
+    Outputs<uint32_t> out;
 };
-
-// The states of a row's slots, for the kernels that test every key against all of them: SLOTS registers each, uniform over the
-// workgroup.  Slots from `slots` on are done and match nothing.
-template <int SLOTS>
-struct SlotStates {
-    uint32_t prefix[SLOTS], shift[SLOTS];
-    bool live[SLOTS];   // the select goes on (w == 0)
-};
-template <int SLOTS>
-__device__ __forceinline__ SlotStates<SLOTS> slot_states(const LongParams& p, uint32_t row)
-{
-    SlotStates<SLOTS> s;
-#pragma unroll
-    for (int l = 0; l < SLOTS; l++) {
-        uint4 st = make_uint4(0u, 0u, 0u, 1u);
-        if ((uint32_t)l < p.out.slots) st = p.state[(size_t)row * p.out.slots + l];   // uniform
-        s.prefix[l] = st.x;
-        s.shift[l] = st.y;
-        s.live[l] = st.w == 0u;
-    }
-    return s;
-}
-// Bit l: slot l is a leader -- it takes part (`in[l]`) and no lower slot that takes part has the same (prefix, shift).
-template <int SLOTS>
-__device__ __forceinline__ uint32_t leaders(const SlotStates<SLOTS>& s, const bool (&in)[SLOTS])
-{
-    uint32_t lead = 0u;
-#pragma unroll
-    for (int l = 0; l < SLOTS; l++) {
-        bool first = in[l];
-#pragma unroll
-        for (int i = 0; i < l; i++) first = first && !(in[i] && s.prefix[i] == s.prefix[l] && s.shift[i] == s.shift[l]);
-        lead |= first ? 1u << l : 0u;
-    }
-    return lead;
-}
 
 // control block, counters and slot states of a call (a kernel rather than memsets: one kind of node in a captured graph)
 __global__ void __launch_bounds__(256) kthm_clear_kernel(uint32_t* ctl, uint32_t* hist, uint32_t hist_words, uint4* state, uint32_t rows,
@@ -296,16 +237,6 @@ __global__ void __launch_bounds__(hist_threads<SLOTS>()) kthm_hist_kernel(const 
             if (v != 0u) atomicAdd(out + b, v);
         }
     }
-}
-
-// the lowest live slot of the row with slot j's (prefix, shift): j itself, or the slot whose counters j's keys were counted into
-// (the histogram kernel's leaders() on the same states: there a live slot also has to carry the previous level's shift, which every
-// live slot does -- one that did not would find its counters empty here and raise the count fault)
-__device__ __forceinline__ uint32_t leader_of(const uint4* st, uint32_t j)
-{
-    for (uint32_t i = 0; i < j; i++)
-        if (st[i].w == 0u && st[i].x == st[j].x && st[i].y == st[j].y) return i;
-    return j;
 }
 
 // One workgroup per row: for every live slot, walk its leader's bins from the best end to the one that holds the slot's key.  All
@@ -445,54 +376,12 @@ __global__ void __launch_bounds__(kLongThreads) kthm_count_kernel(const LongPara
     }
 }
 
-// One workgroup per (row, slot): the chunk that holds the `need`-th key under the slot's prefix, and which of that chunk's such
-// keys it is.  The chunk counts are those of the lowest slot of the row with the same (prefix, shift).  The workgroups of a row read
-// one another's (prefix, shift) while they run, so a pick stores z and w ALONE: no word is read by one workgroup and written by
-// another.
-__global__ void __launch_bounds__(256) kthm_pick_kernel(const LongParams p)
-{
-    __shared__ uint32_t s_part[4];
-    __shared__ uint32_t s_found[2];
-    const uint32_t slots = p.out.slots, row = blockIdx.x / slots, slot = blockIdx.x % slots;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (row >= p.out.rows) return;
-    uint4* const state = p.state + (size_t)row * slots;
-    const uint2 xy = *reinterpret_cast<const uint2*>(&state[slot].x);
-    uint32_t lead = slot;
-    for (uint32_t i = slot; i-- > 0u;) {   // uniform
-        const uint2 o = *reinterpret_cast<const uint2*>(&state[i].x);
-        if (o.x == xy.x && o.y == xy.y) lead = i;
-    }
-    const uint32_t* const counts = p.counts + ((size_t)row * slots + lead) * p.chunk_cap;
-    constexpr uint32_t E = kMaxChunks / 256u;
-    uint32_t c[E], sum = 0u;
-    const uint32_t need = xy.y < Levels32::kNoLevel ? state[slot].z : 0u;
-#pragma unroll
-    for (uint32_t e = 0; e < E; e++) {
-        c[e] = (need != 0u && tid * E + e < p.chunks) ? counts[tid * E + e] : 0u;
-        sum += c[e];
-    }
-    if (tid == 0u) s_found[0] = kNoChunk;
-    uint32_t run = group_exclusive_scan<4>(sum, lane, wave, s_part);
-#pragma unroll
-    for (uint32_t e = 0; e < E; e++) {
-        if (run < need && need - run <= c[e]) {   // at most one chunk of the row
-            s_found[0] = tid * E + e;
-            s_found[1] = need - run;
-        }
-        run += c[e];
-    }
-    __syncthreads();
-    if (tid != 0u) return;
-    const uint32_t chunk = s_found[0];
-    uint2* const zw = reinterpret_cast<uint2*>(&state[slot].z);
-    if (chunk == kNoChunk) {   // the keys under the prefix are fewer than `need`: nothing is located
-        atomicOr(p.out.fault, kKthFaultLocate);
-        *zw = make_uint2(0u, kNoChunk);
-        return;
-    }
-    *zw = make_uint2(s_found[1], chunk);
-}
+// One workgroup per (row, slot): the chunk that holds the slot's key -- kth_slots.hpp's kernel template, under this unit's name.
+struct KthMulti {
+    using Levels = Levels32;
+    using Params = LongParams;
+};
+constexpr auto kthm_pick_kernel = pick_slots_kernel<KthMulti>;
 
 // One workgroup per (row, slot) reads the picked chunk, and only up to the tile that holds the key.
 __global__ void __launch_bounds__(kLongThreads) kthm_locate_kernel(const LongParams p)
@@ -538,16 +427,12 @@ int run_kth_multi(const uint32_t* keys, size_t rows, size_t cols, const Needs& n
                   uint32_t* out_keys, uint32_t* out_idx, char* ws, const KthmLayout& L, hipStream_t stream)
 {
     uint32_t* const ctl = reinterpret_cast<uint32_t*>(ws);
-    const Outputs out{out_keys, out_idx, (uint32_t)rows, (uint32_t)slots, ctl};
+    const Outputs<uint32_t> out{out_keys, out_idx, (uint32_t)rows, (uint32_t)slots, ctl};
     if (cols <= (size_t)kLocalSortCap) {
         const ShortParams sp{keys, (uint32_t)cols, need, xf, out};
-        hipLaunchKernelGGL(kthm_clear_kernel, dim3(1), dim3(256), 0, stream, ctl, (uint32_t*)nullptr, 0u, (uint4*)nullptr, 0u, 0u, need);
         if (cols <= (size_t)kWaveSegCap)
-            hipLaunchKernelGGL(kthm_short_kernel<1>, dim3(grid_for(rows, 8, 16384)), dim3(512), 0, stream, sp);
-        else
-            hipLaunchKernelGGL(kthm_short_kernel<16>, dim3(grid_for(rows, 1, 4096)), dim3(1024), 0, stream, sp);
-        LSD_HIP(hipGetLastError());
-        return LSDSORT_OK;
+            return launch_short_slots(kthm_clear_kernel, ctl, kthm_short_kernel<1>, dim3(grid_for(rows, 8, 16384)), dim3(512), sp, stream);
+        return launch_short_slots(kthm_clear_kernel, ctl, kthm_short_kernel<16>, dim3(grid_for(rows, 1, 4096)), dim3(1024), sp, stream);
     }
     const Chunks ch = chunks_for(rows, cols);
     LongParams lp{};
@@ -578,12 +463,6 @@ int run_kth_multi(const uint32_t* keys, size_t rows, size_t cols, const Needs& n
     return LSDSORT_OK;
 }
 
-bool kthm_too_large(size_t rows, size_t cols, size_t slots)
-{
-    if (rows > LSDSORT_MAX_KEYS) return true;
-    return rows != 0 && (cols > LSDSORT_MAX_KEYS / rows || slots > LSDSORT_MAX_KEYS / rows);
-}
-
 }  // namespace
 }  // namespace lsd
 
@@ -591,7 +470,7 @@ extern "C" {
 
 size_t lsdsort_kth_multi_workspace_bytes(size_t rows, size_t cols, size_t num_ranks)
 {
-    if (num_ranks > LSDSORT_KTH_MAX_RANKS || cols > LSDSORT_MAX_KEYS || lsd::kthm_too_large(rows, cols, num_ranks)) return 0;
+    if (num_ranks > LSDSORT_KTH_MAX_RANKS || cols > LSDSORT_MAX_KEYS || lsd::multi_too_large(rows, cols, num_ranks)) return 0;
     return lsd::kthm_layout(rows, cols, num_ranks).end;
 }
 
@@ -602,14 +481,10 @@ int lsdsort_kth_multi_device(const void* d_keys, size_t rows, size_t cols, const
     lsd::KeyTransform xf;
     LSD_TRY(lsd::key_transform(key_type, largest, &xf));
     if (num_ranks > LSDSORT_KTH_MAX_RANKS) return LSDSORT_ERR_INVALID_ARG;
-    if (lsd::kthm_too_large(rows, cols, num_ranks)) return LSDSORT_ERR_TOO_LARGE;
+    if (lsd::multi_too_large(rows, cols, num_ranks)) return LSDSORT_ERR_TOO_LARGE;
     if (rows == 0 || cols == 0 || num_ranks == 0) return LSDSORT_OK;   // before the ranks: an empty row has no valid rank
-    if (!ranks) return LSDSORT_ERR_INVALID_ARG;
-    lsd::Needs need{};
-    for (size_t j = 0; j < num_ranks; j++) {
-        if (ranks[j] >= cols) return LSDSORT_ERR_INVALID_ARG;
-        need.v[j] = (uint32_t)ranks[j] + 1u;
-    }
+    lsd::Needs need;
+    LSD_TRY(lsd::needs_from_ranks(ranks, num_ranks, cols, &need));
     if (!d_keys || !d_out_keys || (((uintptr_t)d_keys | (uintptr_t)d_out_keys) & 3)) return LSDSORT_ERR_INVALID_ARG;
     const lsd::KthmLayout L = lsd::kthm_layout(rows, cols, num_ranks);
     if (!lsd::workspace_ok(d_workspace, workspace_bytes, L.end)) return LSDSORT_ERR_WORKSPACE;

@@ -7,7 +7,8 @@
 // (clear_select, hist_level, scan_level: wider digits, kBins counters per row in the workspace, one launch per level and step).
 // A unit brings how a tile is loaded and what marks a missing key (the counting functors; the loaders themselves are
 // select_tiles16.hpp's and select_tiles32.hpp's), what it does with (prefix, shift, need) afterwards, its __global__ wrappers and
-// its entries.  Internal linkage: every unit's kernels keep their own symbols.
+// its entries.  Internal linkage: every unit's kernels keep their own symbols.  The k-th value units also share their fault bits
+// and the pick of their long rows, a kernel template that each of them instantiates under its own name (pick_rows_kernel).
 #pragma once
 
 #include <stddef.h>
@@ -222,6 +223,70 @@ __device__ __forceinline__ void scan_level(const LP& p, uint32_t* s_part, uint32
     const uint32_t prefix = LEVEL == 0 ? bin : ((st.x << L::bits(LEVEL)) | bin);
     const uint32_t left = need - before;
     p.state[row] = make_uint4(prefix, L::shift(LEVEL), left, (LEVEL == L::kLevels - 1 || Stop::stops(count, left)) ? 1u : 0u);
+}
+
+// ---- the k-th value units: the pick of the long rows ------------------------------------------------------------------------------
+constexpr uint32_t kKthFaultCount = 1024u;    // fault word: the digit counts of a row do not reach a rank (never expected)
+// fault word: no key was located for a row or slot, or a values-only state is no whole value (never expected; nothing stored)
+constexpr uint32_t kKthFaultLocate = 2048u;
+constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
+
+// The kernels behind the levels that do not depend on the unit are kernel TEMPLATES, here, in select_tiles16.hpp and in
+// kth_slots.hpp: a template is optimised once, as a kernel, so each instantiation is the code the unit's own kernel was (a shared
+// device function is not: DESIGN.md section 6.14).  A unit names itself to them by a struct U of its own -- it is what tells two
+// units' instantiations apart in a kernel trace, every LongParams being lsd::(anonymous)::LongParams:
+//   U::Levels   Levels32 or Levels16
+//   U::Params   the unit's LongParams
+//   U::kBadW    single-rank units: the state w of a row that was refused from the start, 0 where the unit has no such rows;
+//               U::kFaultBad (needed only where kBadW is not 0) is the bit such a row is reported by
+//
+// One workgroup per row: the chunk that holds the `need`-th key under the prefix, and which of that chunk's such keys it is.  A row
+// that was refused from the start (kth16_rowk.hip: a rank outside the row) is reported here, by its own bit, and has nothing picked.
+template <class U>
+__global__ void __launch_bounds__(256) pick_rows_kernel(const typename U::Params p)
+{
+    __shared__ uint32_t s_part[4];
+    __shared__ uint32_t s_found[2];
+    const uint32_t row = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    if constexpr (U::kBadW != 0u) {
+        if (st.y == U::Levels::kNoLevel && st.w == U::kBadW) {   // uniform
+            if (tid == 0u) {
+                atomicOr(p.out.fault, U::kFaultBad);
+                p.state[row] = make_uint4(0u, 0u, 0u, kNoChunk);
+            }
+            return;
+        }
+    }
+    const uint32_t* const counts = p.counts + (size_t)row * p.chunk_cap;
+    constexpr uint32_t E = kMaxChunks / 256u;
+    uint32_t c[E], sum = 0u;
+#pragma unroll
+    for (uint32_t e = 0; e < E; e++) {
+        c[e] = tid * E + e < p.chunks ? counts[tid * E + e] : 0u;
+        sum += c[e];
+    }
+    if (tid == 0u) s_found[0] = kNoChunk;
+    uint32_t run = group_exclusive_scan<4>(sum, lane, wave, s_part);
+    const uint32_t need = st.y < U::Levels::kNoLevel ? st.z : 0u;
+#pragma unroll
+    for (uint32_t e = 0; e < E; e++) {
+        if (run < need && need - run <= c[e]) {   // at most one chunk of the row
+            s_found[0] = tid * E + e;
+            s_found[1] = need - run;
+        }
+        run += c[e];
+    }
+    __syncthreads();
+    if (tid != 0u) return;
+    const uint32_t chunk = s_found[0];
+    if (chunk == kNoChunk) {   // the keys under the prefix are fewer than `need`: nothing is located
+        atomicOr(p.out.fault, kKthFaultLocate);
+        p.state[row] = make_uint4(0u, 0u, 0u, kNoChunk);
+        return;
+    }
+    p.state[row] = make_uint4(st.x, st.y, s_found[1], chunk);
 }
 
 // off[r] = r * stride, r <= rows: the rows as segments of the segmented sort

@@ -1,7 +1,8 @@
 // select_tiles16.hpp -- the tile helpers of the 16-bit row selects, once: what topk16.hip, kth16.hip, kth16_multi.hip,
 // kth16_rowk.hip and topp16.hip do with one wave's tile of a Row<uint16_t>.  Internal linkage, as
 // radix_select.hpp: every unit's kernels keep their own symbols, and a unit calls these helpers DIRECTLY from its kernels -- a
-// per-unit wrapper around one of them is one more inlining level and changes the register allocation of the kernel.
+// per-unit wrapper around one of them is one more inlining level and changes the register allocation of the kernel.  The count and
+// the locate kernel of the two single-rank k-th value units are kernel TEMPLATES here, instantiated under each unit's name.
 //
 // Key reads.  A row starts 2 r cols bytes past the keys, at any even offset within a 16-byte line.  Every kernel therefore splits
 // EACH ROW by address (Row): `head` keys in front of the row's first 16-byte line (0..7), read one by one, and the `body` from that
@@ -20,7 +21,6 @@ namespace {
 
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;     // a sortable value is below 65536
 constexpr uint32_t kHeadBit = 1u << kRegs;   // match mask: the head register
-constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
 using Row16 = Row<uint16_t>;   // a lane holds two 16-byte groups of eight keys of its wave's tile
 
 // a select whose levels always all run, so that the prefix is the whole value (values only, and the filters)
@@ -182,8 +182,6 @@ __device__ __forceinline__ void hist_level16(const LP& p, uint32_t* s_hist)
 // the row's whole sortable value (shift 0, need not 0).  Anything else is a row the unit's clear kernel refused from the start
 // (state w == BAD_W with no level run: reported by `fault_bad`; BAD_W 0: the unit has no such rows), a row whose counts fell short
 // (its fault bit is set) or one no scan has visited -- never: nothing is stored for it.
-// The count, pick and locate kernels of those two units stay in the units, twice: as shared bodies they compile to other code
-// (DESIGN.md section 6.14).
 template <uint32_t BAD_W, class LP>
 __device__ __forceinline__ void store_values16(uint32_t at, uint32_t step, const LP& p, uint32_t fault_locate, uint32_t fault_bad)
 {
@@ -192,6 +190,68 @@ __device__ __forceinline__ void store_values16(uint32_t at, uint32_t step, const
         if (st.y == 0u && st.z != 0u) p.out.keys[row] = (uint16_t)from_sortable16(st.x & 0xFFFFu, p.map);
         else atomicOr(p.out.fault, (BAD_W != 0u && st.y == Levels16::kNoLevel && st.w == BAD_W) ? fault_bad : fault_locate);
     }
+}
+
+// ---- long rows: the count and the locate of the single-rank units (kth16.hip, kth16_rowk.hip) -----------------------------------
+// Kernel templates, with radix_select.hpp's pick_rows_kernel between them; U is the unit's own struct (U::Params: its LongParams).
+// The 32-bit pair reads keys under a validity mask and is kth.hip's own.
+
+// the keys under the prefix, per chunk
+template <class U>
+__global__ void __launch_bounds__(kLongThreads) count_rows16_kernel(const typename U::Params p)
+{
+    __shared__ uint32_t s_part[kLongWaves];
+    const uint32_t row = blockIdx.x / p.chunks, c = blockIdx.x % p.chunks;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const Row16 r = row_of(p.keys, row, p.cols);
+    const ChunkRange g = chunk_of(r, p.chunk, c);
+    uint32_t ne = 0u;
+    // (uniform) else: a row no scan has visited or that was refused from the start, or one whose counts fell short
+    if (st.y < Levels16::kNoLevel && st.z != 0u) {
+        if (c == 0u && wave == 0u) ne += (load_head(r, lane, p.map) >> st.y) == st.x ? 1u : 0u;   // uniform
+        for (uint32_t tile = g.lo; tile < g.hi; tile += kLongTile) {   // uniform
+            uint32_t t[kRegs];
+            load_tile(r, tile + wave * kWaveTile, g.hi, lane, p.map, t);
+#pragma unroll
+            for (int i = 0; i < kRegs; i++) ne += (t[i] >> st.y) == st.x ? 1u : 0u;
+        }
+    }
+    ne = wave_sum(ne);
+    if (lane == 0u) s_part[wave] = ne;
+    __syncthreads();
+    if (tid == 0u) {
+        uint32_t e = 0u;
+        for (uint32_t w = 0; w < kLongWaves; w++) e += s_part[w];
+        p.counts[(size_t)row * p.chunk_cap + c] = e;
+    }
+}
+
+// One workgroup per row reads the picked chunk, and only up to the tile that holds the key.
+template <class U>
+__global__ void __launch_bounds__(kLongThreads) locate_rows16_kernel(const typename U::Params p)
+{
+    __shared__ uint32_t s_wc_raw[kLongWaves];
+    const uint32_t row = blockIdx.x;
+    if (row >= p.out.rows) return;
+    const uint4 st = p.state[row];
+    if (st.z == 0u || st.w >= p.chunks) return;   // (uniform) nothing was picked: the pick has set the row's fault bit
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const Row16 r = row_of(p.keys, row, p.cols);
+    const ChunkRange g = chunk_of(r, p.chunk, st.w);
+    volatile lds_u32* const s_wc = (volatile lds_u32*)(lds_u32*)s_wc_raw;
+    uint32_t base = 0u;
+    bool found = false;
+    // chunk 0 has at least one tile (a long row's body is longer than its head), and its first tile carries the head
+    for (uint32_t tile = g.lo; tile < g.hi && !found; tile += kLongTile) {   // uniform
+        const uint32_t q0 = tile + wave * kWaveTile;
+        uint32_t t[kRegs];
+        load_tile(r, q0, g.hi, lane, p.map, t);
+        const uint32_t h = (st.w == 0u && tile == g.lo && wave == 0u) ? load_head(r, lane, p.map) : kNoKey;   // uniform
+        found = locate_tile<(int)kLongWaves>(t, h, q0, r, st.x, st.y, st.z, base, s_wc, wave, lane, row, 0u, p.out, p.map);
+    }
+    if (!found && tid == 0u) atomicOr(p.out.fault, kKthFaultLocate);
 }
 
 }  // namespace

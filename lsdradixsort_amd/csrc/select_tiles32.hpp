@@ -21,7 +21,6 @@ namespace {
 
 constexpr uint32_t kGroup = 4;                // keys of one 16-byte load
 constexpr uint32_t kHeadBit = 1u << kRegs;    // validity mask: the head register
-constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
 using Row32 = Row<uint32_t>;   // a lane holds four 16-byte groups of four keys of its wave's tile
 
 // The wave's tile from body position q0 (a multiple of four) on, valid below `end`: a whole group by one 16-byte load, the others

@@ -255,11 +255,13 @@ def test_kth16_kernels_no_scratch_no_spill():
         pytest.skip("no hipcc on this machine")
     res = kernel_resources("kth16.hip")
     names = list(res)
-    for must in ("kth16_clear_kernel", "kth16_count_kernel", "kth16_pick_kernel", "kth16_locate_kernel", "kth16_value_kernel"):
+    # count, pick and locate: the kernel templates of select_tiles16.hpp and radix_select.hpp, as Kth16
+    for must in ("kth16_clear_kernel", "count_rows16_kernelINS0_5Kth16E", "pick_rows_kernelINS0_5Kth16E", "locate_rows16_kernelINS0_5Kth16E",
+                 "kth16_value_kernel"):
         assert sum(must in name for name in names) == 1, (must, names)
     assert sum("kth16_short_kernel" in name for name in names) == 2, names                # one wavefront, one workgroup
     assert sum("kth16_hist_kernel" in name for name in names) == 2, names                 # two digit levels
     assert 2 <= sum("kth16_scan_kernel" in name for name in names) <= 4, names            # two levels, two stop rules at the most
-    assert all("kth16_" in name for name in names), names
+    assert all("kth16_" in name or "_kernelINS0_5Kth16E" in name for name in names), names   # every kernel names its unit
     for name, r in res.items():
         assert r["scratch"] == 0 and r["vgpr_spill"] == 0, (name, r)

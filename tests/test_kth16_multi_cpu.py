@@ -286,13 +286,13 @@ def test_kernels_no_scratch_no_spill_and_recorded_resources():
     res = kernel_resources("kth16_multi.hip")
     names = list(res)
     once = ("kth16m_clear_kernel", "kth16m_hist0_kernel", "kth16m_hist1_kernel", "kth16m_scan1_kernel", "kth16m_count_kernel",
-            "kth16m_pick_kernel", "kth16m_locate_kernel", "kth16m_value_kernel")
+            "pick_slots_kernelINS0_10Kth16MultiE", "kth16m_locate_kernel", "kth16m_value_kernel")
     for must in once:
         assert sum(must in name for name in names) == 1, (must, names)
     assert sum("kth16m_short_kernel" in name for name in names) == 2, names               # one wavefront, one workgroup
     assert sum("kth16m_scan0_kernel" in name for name in names) == 2, names               # StopKth, and never-stop for values only
     assert len(names) == len(once) + 2 + 2, names
-    assert all("kth16m_" in name for name in names), names                                # one common prefix
+    assert all("kth16m_" in name or "_kernelINS0_10Kth16MultiE" in name for name in names), names   # every kernel names its unit
     for name, r in res.items():
         assert r["scratch"] == 0 and r["vgpr_spill"] == 0, (name, r)
     want = json.load(open(GOLDEN))["kth16_multi.hip"]

@@ -399,14 +399,16 @@ def test_kernels_no_scratch_no_spill_and_recorded_resources():
         pytest.skip("no hipcc on this machine")
     res = kernel_resources("kth16_rowk.hip")
     names = list(res)
-    once = ("kth16r_count_kernel", "kth16r_pick_kernel", "kth16r_locate_kernel", "kth16r_value_kernel", "topk16f_apply_kernel")
+    # count, pick and locate: the kernel templates of select_tiles16.hpp and radix_select.hpp, as Kth16Rowk
+    once = ("count_rows16_kernelINS0_9Kth16RowkE", "pick_rows_kernelINS0_9Kth16RowkE", "locate_rows16_kernelINS0_9Kth16RowkE",
+            "kth16r_value_kernel", "topk16f_apply_kernel")
     for must in once:
         assert sum(must in name for name in names) == 1, (must, names)
     for twice in ("kth16r_short_kernel", "topk16f_short_kernel", "kth16r_hist_kernel", "kth16r_clear_kernel"):
         assert sum(twice in name for name in names) == 2, (twice, names)              # wavefront / workgroup; two levels; rank / k
     assert sum("kth16r_scan_kernel" in name for name in names) == 3, names              # level 0 under two stop rules, level 1
     assert len(names) == len(once) + 4 * 2 + 3, names
-    assert all("kth16r_" in name or "topk16f_" in name for name in names), names
+    assert all("kth16r_" in name or "topk16f_" in name or "_kernelINS0_9Kth16RowkE" in name for name in names), names   # each names its unit
     for name, r in res.items():
         assert r["scratch"] == 0 and r["vgpr_spill"] == 0, (name, r)
     want = json.load(open(GOLDEN))["kth16_rowk.hip"]

@@ -1,6 +1,7 @@
 """CPU suite: the row selects' tile helpers live ONCE, in csrc/select_tiles16.hpp (16-bit keys) and csrc/select_tiles32.hpp (32-bit
-keys), and the units include them instead of carrying copies.  Source text, and hipcc for the one thing
-text cannot show: that each header stands on its own includes."""
+keys), the slots of the two multi-rank k-th value units in csrc/kth_slots.hpp, the k-th value units' pick kernel and fault bits in
+csrc/radix_select.hpp, and the units include them instead of carrying copies.  Source text, and hipcc for
+the one thing text cannot show: that each header stands on its own includes."""
 import os
 import re
 import subprocess
@@ -9,20 +10,25 @@ import pytest
 
 from _kernel_resources import CSRC, hipcc
 
-H16, H32 = "select_tiles16.hpp", "select_tiles32.hpp"
+H16, H32, SLOTS, SELECT = "select_tiles16.hpp", "select_tiles32.hpp", "kth_slots.hpp", "radix_select.hpp"
 UNITS = {"topk16.hip": H16, "kth16.hip": H16, "kth16_multi.hip": H16, "kth16_rowk.hip": H16, "topp16.hip": H16,
          "kth.hip": H32, "kth_multi.hip": H32}
+SLOT_UNITS = {"kth_multi.hip", "kth16_multi.hip"}
 # helper -> the files under csrc/ that define it, each exactly once.  topk.hip's load_tile is the one exception: another shape (a
 # plain pointer, one key per load, no validity mask), its own on purpose.
 FUNCTIONS = {"load_tile": {H16, H32, "topk.hip"}, "load_head": {H16, H32}, "locate_tile": {H16, H32},
-             "store_tile": {H16}, "store_head": {H16}, "same_phase": {H16}}
-STRUCTS = {"StopNever16": {H16}}
-CONSTANTS = {"kNoKey": {H16}, "kHeadBit": {H16, H32}, "kNoChunk": {H16, H32}}
-# Kernel bodies of kth16_rowk.hip that still repeat kth16.hip's line for line (pick: around its bad-rank branch).  Moved into a
-# shared device function they compile to other instructions than the measured ones -- the callee is optimised once on its own and
-# once more after inlining, which reorders the operands of their small unrolled sums -- so they stay double.
-# Sharing one of them later is a one-line change here.
-STILL_DOUBLE = {"count", "pick", "locate"}
+             "store_tile": {H16}, "store_head": {H16}, "same_phase": {H16},
+             "need_of": {SLOTS}, "slot_states": {SLOTS}, "leaders": {SLOTS}, "leader_of": {SLOTS}}
+STRUCTS = {"StopNever16": {H16}, "Needs": {SLOTS}, "SlotStates": {SLOTS}}
+CONSTANTS = {"kNoKey": {H16}, "kHeadBit": {H16, H32}, "kNoChunk": {SELECT}, "kMaxSlots": {SLOTS},
+             "kKthFaultCount": {SELECT}, "kKthFaultLocate": {SELECT}}
+# host functions and kernel templates -> the one header that defines each
+HOST = {"multi_too_large": SLOTS, "needs_from_ranks": SLOTS, "launch_short_slots": SLOTS}
+KERNEL_TEMPLATES = {"pick_rows_kernel": SELECT, "pick_slots_kernel": SLOTS, "count_rows16_kernel": H16, "locate_rows16_kernel": H16}
+# Kernel bodies of kth16_rowk.hip that repeat kth16.hip's line for line: none.  Count, pick and locate were the last three; they are
+# kernel templates now, instantiated by both units (DESIGN.md section 6.14 says why that form keeps the instructions where a shared
+# device function did not).
+STILL_DOUBLE = set()
 
 
 def sources():
@@ -41,7 +47,7 @@ def defined_in(pattern):
 
 def test_each_helper_is_defined_once_and_in_its_header():
     for name, where in FUNCTIONS.items():   # a definition: the line opens with the qualifiers, and a body follows the parameters
-        found = defined_in(r"^(?:template[^\n]*\n)?__device__ __forceinline__ [\w ]+\b" + name + r"\(")
+        found = defined_in(r"^(?:template[^\n]*\n)?__device__ __forceinline__ [\w <>]+\b" + name + r"\(")
         assert found == {f: 1 for f in where}, f"{name} is defined in {found}"
     for name, where in STRUCTS.items():
         found = defined_in(r"^\s*struct " + name + r"\b")
@@ -49,6 +55,15 @@ def test_each_helper_is_defined_once_and_in_its_header():
     for name, where in CONSTANTS.items():
         found = defined_in(r"^\s*constexpr[^;\n]*\b" + name + r"\s*=")
         assert found == {f: 1 for f in where}, f"{name} is defined in {found}"
+    for name, where in HOST.items():   # a host function: the line opens with its return type
+        found = defined_in(r"^(?:template[^\n]*\n)?(?:bool|int) " + name + r"\(")
+        assert found == {where: 1}, f"{name} is defined in {found}"
+    for name, where in KERNEL_TEMPLATES.items():
+        found = defined_in(r"^template <class U>\n__global__ void __launch_bounds__\(\w+\) " + name + r"\(const typename U::Params p\)\n\{")
+        assert found == {where: 1}, f"{name} is defined in {found}"
+    # the pick's walk over a row's chunk counts: once for rows, once for slots, and in no unit
+    found = defined_in(r"s_found\[0\] = kNoChunk;\n\s*uint32_t run = group_exclusive_scan<4>\(")
+    assert found == {SELECT: 1, SLOTS: 1}, f"the pick walk is written in {found}"
     assert FUNCTIONS["load_tile"] - {H16, H32} == {"topk.hip"}   # the only helper a unit defines itself
     for table in (FUNCTIONS, STRUCTS, CONSTANTS):
         for name, where in table.items():
@@ -63,12 +78,14 @@ def test_each_unit_includes_its_header_and_not_the_other():
     for name, text in texts.items():   # and nobody else does: the headers are those seven units'
         if name not in UNITS:
             assert not {H16, H32} & set(re.findall(r'#include "([^"]+)"', text)), name
+        # the slots' header is the two multi-rank units', whatever their key width
+        assert (SLOTS in re.findall(r'#include "([^"]+)"', text)) == (name in SLOT_UNITS), name
 
 
 def test_the_makefile_rebuilds_the_units_when_a_header_changes():
     makefile = open(os.path.join(CSRC, "Makefile")).read()
     headers = re.search(r"^HEADERS\s*:=(.*)$", makefile, flags=re.M).group(1).split()
-    assert H16 in headers and H32 in headers
+    assert H16 in headers and H32 in headers and SLOTS in headers and SELECT in headers
     assert re.search(r"^\$\(BUILD\)/%\.o: %\.hip \$\(HEADERS\)$", makefile, flags=re.M)
 
 
@@ -89,8 +106,10 @@ def kernel_bodies(text, prefix):
 def test_kernel_bodies_left_double_are_the_listed_ones():
     texts = sources()
     one = kernel_bodies(texts["kth16.hip"], "kth16")
-    per_row = kernel_bodies(texts["kth16_rowk.hip"].replace("kRowkFault", "kKth16Fault"), "kth16r")
+    per_row = kernel_bodies(texts["kth16_rowk.hip"], "kth16r")
     assert STILL_DOUBLE <= set(one) & set(per_row)
+    assert {"hist", "scan", "value"} <= set(one) & set(per_row)                # the kernels both units still write out are read ...
+    assert not {"count", "pick", "locate"} & (set(one) | set(per_row))         # ... and these three are written out in neither
 
     def repeats(kind):   # kth16.hip's body, more than a call or two, lies in kth16_rowk.hip's line for line and in order
         rest = iter(per_row[kind])
@@ -100,7 +119,7 @@ def test_kernel_bodies_left_double_are_the_listed_ones():
 
 
 @pytest.mark.skipif(hipcc() is None, reason="no hipcc")
-@pytest.mark.parametrize("header", [H16, H32])
+@pytest.mark.parametrize("header", [H16, H32, SLOTS, SELECT])
 def test_a_header_stands_on_its_own_includes(header, tmp_path):
     unit = tmp_path / "only.hip"
     unit.write_text(f'#include "{header}"\n')
