@@ -8,32 +8,15 @@
 Keys only: 2^12 .. 2^24 and 2^28 uniform bfloat16 bit patterns, 2^28 all-equal keys, 2^28 normal-distributed bfloat16 values.
 Pairs: 2^24 and 2^27 uniform patterns.  bytes_per_key_at_5p5TBs puts a time into the unit of DESIGN.md's byte accounting.
 Usage: python tools/keys16_perf.py [--reps 20] [--warmup 3] [--only NAME] [--no-baselines] [--out FILE]"""
-import argparse
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
-
-
-def timed(fn, fresh, reps, warmup):
-    """fresh() refills the inputs outside the timed region; fn() is timed by device events"""
-    ts = []
-    for i in range(warmup + reps):
-        fresh()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append(e0.elapsed_time(e1))
-    return float(np.median(ts)), float(np.min(ts))
+import perfkit
+from perfkit import timed
 
 
 def fill_uniform(x, g):
@@ -84,11 +67,11 @@ def run_shape(name, n, pairs, fill, reps, warmup, baselines=True):
     if not pairs:
         ms = timed_on_route(1, sort, fresh, reps, warmup)
         check()
-        out.update(count_ms=ms[0], count_min_ms=ms[1], count_bytes_per_key_at_5p5TBs=ms[0] * 1e-3 * 5.5e12 / n,
+        out.update(count_ms=ms[0], count_min_ms=ms[1], count_bytes_per_key_at_5p5TBs=perfkit.bytes_per_key(ms[0], n),
                    count_GBps_of_6B_per_key=6.0 * n / (ms[0] * 1e-3) / 1e9)
     ms = timed_on_route(0, sort, fresh, reps, warmup)
     check()
-    out.update(widen_ms=ms[0], widen_min_ms=ms[1], widen_bytes_per_key_at_5p5TBs=ms[0] * 1e-3 * 5.5e12 / n)
+    out.update(widen_ms=ms[0], widen_min_ms=ms[1], widen_bytes_per_key_at_5p5TBs=perfkit.bytes_per_key(ms[0], n))
     if not baselines:
         return out
     del ws
@@ -141,24 +124,16 @@ SHAPES = {
 }
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--only", default=None, help="comma-separated shape names")
+def parser():
+    ap = perfkit.parser(__doc__, only_help="comma-separated shape names")
     ap.add_argument("--no-baselines", action="store_true")
-    ap.add_argument("--out", default=None, help="append the rows to this file as well")
-    a = ap.parse_args()
-    only = a.only.split(",") if a.only else None
-    for name, (n, pairs, fill) in SHAPES.items():
-        if only and name not in only:
-            continue
-        row = json.dumps(run_shape(name, n, pairs, fill, a.reps, a.warmup, baselines=not a.no_baselines))
-        print(row, flush=True)
-        if a.out:
-            with open(a.out, "a") as f:
-                f.write(row + "\n")
-        torch.cuda.empty_cache()
+    return ap
+
+
+def main():
+    a = parser().parse_args()
+    perfkit.run_cases(a, SHAPES, lambda name, *shape: run_shape(name, *shape, a.reps, a.warmup, baselines=not a.no_baselines),
+                      match="list")
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Multi-rank k-th value timings for 16-bit keys (GPU box): one JSON line per case, the method of tools/kth_multi_perf.py.
+"""Multi-rank k-th value timings for 16-bit keys (GPU box): one JSON line per case, the method of tools/perfkit.py.
 bfloat16 normal-distributed rows, smallest; device events around the call alone; the median of --reps calls on fresh inputs after
 --warmup calls.  The sides ALTERNATE in one process, call by call, on the same rows:
   multi              lsdsort_kth16_multi_device with the case's ranks and an index buffer: ONE call
@@ -18,42 +18,19 @@ Rank sets: the adjacent pair around the median (m = 2), the quartiles (m = 3), a
 and 99.9 (m = 8).  Shapes: [128 x 128256], [4096 x 131072], [1 x 2^28] (long rows) and [2^14 x 2^14], [2^20 x 256] (short rows).
 The bytes-per-key figures divide a time by 5.5 TB/s: byte ACCOUNTING of a time, not a measured traffic.
 Usage: python tools/kth16_multi_perf.py [--reps 20] [--warmup 3] [--spread-repeats 5] [--only SHAPE] [--baseline-lib PATH] [--out FILE]"""
-import argparse
 import ctypes
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
+import perfkit
 
 BF16 = 3
-c_size, c_int, c_ptr = ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p
-
-
-def baseline_library(path):
-    """the three entries of the baseline legs, bound in the library at `path` (None: this tree's)"""
-    if path is None:
-        return lsd.lib()
-    L = ctypes.CDLL(os.path.abspath(path))
-    L.lsdsort_kth16_workspace_bytes.restype, L.lsdsort_kth16_workspace_bytes.argtypes = c_size, [c_size, c_size]
-    L.lsdsort_kth16_device.restype = c_int
-    L.lsdsort_kth16_device.argtypes = [c_ptr, c_size, c_size, c_size, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]
-    L.lsdsort_check_device.restype, L.lsdsort_check_device.argtypes = c_int, [c_ptr, c_ptr]
-    return L
-
-
-def one(fn):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
+BASELINES = ("baseline", "baseline_values")
+BASELINE_ENTRIES = ("lsdsort_kth16_workspace_bytes", "lsdsort_kth16_device", "lsdsort_check_device")
 
 
 def rank_sets(cols):
@@ -73,7 +50,7 @@ def run_case(shape, set_name, rows, cols, ranks, a, base):
     one_k, one_i = torch.empty((m, rows), dtype=torch.bfloat16, **dev), torch.empty((m, rows), dtype=torch.int32, **dev)
     one_v = torch.empty((m, rows), dtype=torch.bfloat16, **dev)
     L = lsd.lib()
-    c_ranks = (c_size * m)(*ranks)
+    c_ranks = (ctypes.c_size_t * m)(*ranks)
     ws = torch.empty(L.lsdsort_kth16_multi_workspace_bytes(rows, cols, m), dtype=torch.uint8, **dev)
     ws_b = torch.empty(base.lsdsort_kth16_workspace_bytes(rows, cols), dtype=torch.uint8, **dev)
     stream = int(torch.cuda.current_stream().cuda_stream)
@@ -101,20 +78,7 @@ def run_case(shape, set_name, rows, cols, ranks, a, base):
             assert st == 0, st
 
     sides = {"multi": multi, "multi_values": multi_values, "baseline": baseline, "baseline_values": baseline_values}
-    medians = {side: [] for side in sides}
-    for repeat in range(a.spread_repeats):
-        ts = {side: [] for side in sides}
-        for i in range(a.warmup + a.reps):
-            x.normal_(0.0, 1.0, generator=g)
-            for side, fn in sides.items():   # the sides alternate, call by call, on the same rows
-                if repeat > 0 and not side.startswith("baseline"):
-                    continue                  # the further repeats measure the baselines' spread
-                t = one(fn)
-                if i >= a.warmup:
-                    ts[side].append(t)
-        for side in sides:
-            if ts[side]:
-                medians[side].append(float(np.median(ts[side])))
+    medians = perfkit.measure(sides, BASELINES, a.spread_repeats, a.reps, a.warmup, fresh=lambda: x.normal_(0.0, 1.0, generator=g))
     assert L.lsdsort_check_device(ws.data_ptr(), None) == 0 and base.lsdsort_check_device(ws_b.data_ptr(), None) == 0
     # once more, untimed, on the same rows: the sides answer the same question, bit for bit
     for fn in sides.values():
@@ -127,8 +91,7 @@ def run_case(shape, set_name, rows, cols, ranks, a, base):
     assert torch.equal(bits(out_v), bits(out_k)) and torch.equal(bits(one_v), bits(one_k)), "values only and with positions disagree"
     b, bv = medians["baseline"], medians["baseline_values"]
     multi_ms, values_ms = medians["multi"][0], medians["multi_values"][0]
-    base_ms, spread = float(np.median(b)), max(b) - min(b)
-    base_v_ms, spread_v = float(np.median(bv)), max(bv) - min(bv)
+    (base_ms, spread), (base_v_ms, spread_v) = perfkit.spread_of(b), perfkit.spread_of(bv)
     which = " (parent commit's library)" if a.baseline_lib else " (this tree's library)"
     return {"shape": shape, "ranks": set_name, "rows": rows, "cols": cols, "num_ranks": m, "rank_values": ranks, "dtype": "bfloat16",
             "largest": False, "reps": a.reps, "warmup": a.warmup, "gated": cols > 16384,
@@ -139,8 +102,8 @@ def run_case(shape, set_name, rows, cols, ranks, a, base):
             "baseline_values_repeats_ms": bv, "baseline_values_spread_ms": spread_v,
             "speedup_vs_baseline": base_ms / multi_ms, "ahead": bool(base_ms - multi_ms > spread),
             "values_speedup_vs_baseline": base_v_ms / values_ms, "values_ahead": bool(base_v_ms - values_ms > spread_v),
-            "multi_bytes_per_key_at_5p5TBs": multi_ms * 1e-3 * 5.5e12 / n,
-            "multi_values_bytes_per_key_at_5p5TBs": values_ms * 1e-3 * 5.5e12 / n,
+            "multi_bytes_per_key_at_5p5TBs": perfkit.bytes_per_key(multi_ms, n),
+            "multi_values_bytes_per_key_at_5p5TBs": perfkit.bytes_per_key(values_ms, n),
             "workspace_bytes": ws.numel(), "baseline_workspace_bytes": ws_b.numel()}
 
 
@@ -153,27 +116,15 @@ SHAPES = {
 }
 
 
+def parser():
+    return perfkit.parser(__doc__, spread_repeats=5, lib_flag="--baseline-lib")
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--spread-repeats", type=int, default=5)
-    ap.add_argument("--only", default=None)
-    ap.add_argument("--baseline-lib", default=None)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    base = baseline_library(a.baseline_lib)
-    sink = open(a.out, "a") if a.out else None
-    for shape, (rows, cols) in SHAPES.items():
-        if a.only and a.only != shape:
-            continue
-        for set_name, ranks in rank_sets(cols).items():
-            line = json.dumps(run_case(shape, set_name, rows, cols, ranks, a, base))
-            print(line, flush=True)
-            if sink:
-                sink.write(line + "\n")
-                sink.flush()
-            torch.cuda.empty_cache()
+    a = parser().parse_args()
+    base = perfkit.bound_library(a.baseline_lib, BASELINE_ENTRIES)
+    perfkit.run_cases(a, SHAPES, lambda shape, rows, cols: (run_case(shape, set_name, rows, cols, ranks, a, base)
+                                                            for set_name, ranks in rank_sets(cols).items()))
 
 
 if __name__ == "__main__":

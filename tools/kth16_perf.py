@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""K-th value timings for 16-bit keys (GPU box): one JSON line per case, the method of tools/kth_perf.py.  bfloat16
+"""K-th value timings for 16-bit keys (GPU box): one JSON line per case, the method of tools/perfkit.py.  bfloat16
 normal-distributed rows, smallest; device events around the call alone; the median of --reps calls on fresh inputs after --warmup
 calls.  The sides ALTERNATE in one process, call by call, on the same rows:
   kth16              lsdsort_kth16_device at the given rank, with positions
@@ -20,9 +20,6 @@ After the timed calls every side runs once more on the same rows and the tool as
 Cases: the lower-median rank of [128 x 128256], [4096 x 131072], [1 x 2^28], [2^14 x 2^14], [2^20 x 256]; rank 1023 of [1 x 2^28].
 Usage: python tools/kth16_perf.py [--reps 20] [--warmup 3] [--spread-repeats 5] [--torch-reps 3] [--only NAME] [--baseline-lib PATH]
                                   [--out FILE]"""
-import argparse
-import ctypes
-import json
 import os
 import sys
 
@@ -31,33 +28,12 @@ import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
+import perfkit
 
 F32, BF16 = 2, 3
-c_size, c_int, c_ptr = ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p
-SELECT = [c_ptr, c_size, c_size, c_size, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]   # topk16's and kth's argument list
-
-
-def baseline_library(path):
-    """the five entries of the baseline legs, bound in the library at `path` (None: this tree's)"""
-    if path is None:
-        return lsd.lib()
-    L = ctypes.CDLL(os.path.abspath(path))
-    L.lsdsort_topk16_workspace_bytes.restype, L.lsdsort_topk16_workspace_bytes.argtypes = c_size, [c_size, c_size, c_size]
-    L.lsdsort_kth_workspace_bytes.restype, L.lsdsort_kth_workspace_bytes.argtypes = c_size, [c_size, c_size]
-    L.lsdsort_topk16_device.restype, L.lsdsort_topk16_device.argtypes = c_int, SELECT
-    L.lsdsort_kth_device.restype, L.lsdsort_kth_device.argtypes = c_int, SELECT
-    L.lsdsort_check_device.restype, L.lsdsort_check_device.argtypes = c_int, [c_ptr, c_ptr]
-    return L
-
-
-def one(fn):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
+BASELINES = ("baseline_topk16", "baseline_float32")
+BASELINE_ENTRIES = ("lsdsort_topk16_workspace_bytes", "lsdsort_kth_workspace_bytes", "lsdsort_topk16_device", "lsdsort_kth_device",
+                    "lsdsort_check_device")
 
 
 def run_case(name, rows, cols, rank, a, base):
@@ -99,20 +75,7 @@ def run_case(name, rows, cols, rank, a, base):
 
     sides = {"kth16": kth16, "kth16_values_only": kth16_values_only, "baseline_topk16": baseline_topk16,
              "baseline_float32": baseline_float32}
-    medians = {side: [] for side in sides}
-    for repeat in range(a.spread_repeats):
-        ts = {side: [] for side in sides}
-        for i in range(a.warmup + a.reps):
-            x.normal_(0.0, 1.0, generator=g)
-            for side, fn in sides.items():   # the sides alternate, call by call, on the same rows
-                if repeat > 0 and not side.startswith("baseline"):
-                    continue                  # the further repeats measure the baselines' spread
-                t = one(fn)
-                if i >= a.warmup:
-                    ts[side].append(t)
-        for side in sides:
-            if ts[side]:
-                medians[side].append(float(np.median(ts[side])))
+    medians = perfkit.measure(sides, BASELINES, a.spread_repeats, a.reps, a.warmup, fresh=lambda: x.normal_(0.0, 1.0, generator=g))
     assert L.lsdsort_check_device(ws.data_ptr(), None) == 0
     for w in (ws_a, ws_b):
         assert base.lsdsort_check_device(w.data_ptr(), None) == 0
@@ -132,7 +95,8 @@ def run_case(name, rows, cols, rank, a, base):
     for side, what in (("baseline_topk16", "lsdsort_topk16_device k=rank+1"), ("baseline_float32", "float32 copy + lsdsort_kth_device")):
         b = medians[side]
         out[side] = what
-        out[side + "_ms"], out[side + "_repeats_ms"], out[side + "_spread_ms"] = float(np.median(b)), b, max(b) - min(b)
+        ms, spread = perfkit.spread_of(b)
+        out[side + "_ms"], out[side + "_repeats_ms"], out[side + "_spread_ms"] = ms, b, spread
         if best is None or out[side + "_ms"] < out[best + "_ms"]:
             best = side
     base_ms, spread = out[best + "_ms"], out[best + "_spread_ms"]
@@ -141,8 +105,8 @@ def run_case(name, rows, cols, rank, a, base):
                 "values_only_speedup_vs_faster_baseline": base_ms / out["kth16_values_only_ms"],
                 "values_only_ahead": bool(base_ms - out["kth16_values_only_ms"] > spread),
                 "speedup_vs_float32": out["baseline_float32_ms"] / out["kth16_ms"],
-                "kth16_bytes_per_key_at_5p5TBs": out["kth16_ms"] * 1e-3 * 5.5e12 / n,
-                "kth16_values_only_bytes_per_key_at_5p5TBs": out["kth16_values_only_ms"] * 1e-3 * 5.5e12 / n,
+                "kth16_bytes_per_key_at_5p5TBs": perfkit.bytes_per_key(out["kth16_ms"], n),
+                "kth16_values_only_bytes_per_key_at_5p5TBs": perfkit.bytes_per_key(out["kth16_values_only_ms"], n),
                 "workspace_bytes": ws.numel(), "baseline_topk16_workspace_bytes": ws_a.numel(),
                 "baseline_float32_workspace_bytes": ws_b.numel() + 4 * n})
     del top_k, top_i, ws_a, ws_b, wide
@@ -152,7 +116,7 @@ def run_case(name, rows, cols, rank, a, base):
         try:
             for i in range(1 + a.torch_reps):
                 x.normal_(0.0, 1.0, generator=g)
-                t = one(lambda: torch.kthvalue(x, k, dim=-1))
+                t = perfkit.one(lambda: torch.kthvalue(x, k, dim=-1))
                 if i >= 1:
                     ts.append(t)
                 elif t > 2000.0:   # seconds per call: the warm-up call is the record
@@ -179,27 +143,16 @@ CASES = {
 }
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--spread-repeats", type=int, default=5)
+def parser():
+    ap = perfkit.parser(__doc__, spread_repeats=5, lib_flag="--baseline-lib")
     ap.add_argument("--torch-reps", type=int, default=3)
-    ap.add_argument("--only", default=None)
-    ap.add_argument("--baseline-lib", default=None)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    base = baseline_library(a.baseline_lib)
-    sink = open(a.out, "a") if a.out else None
-    for name, (rows, cols, rank) in CASES.items():
-        if a.only and a.only != name:
-            continue
-        line = json.dumps(run_case(name, rows, cols, rank, a, base))
-        print(line, flush=True)
-        if sink:
-            sink.write(line + "\n")
-            sink.flush()
-        torch.cuda.empty_cache()
+    return ap
+
+
+def main():
+    a = parser().parse_args()
+    base = perfkit.bound_library(a.baseline_lib, BASELINE_ENTRIES)
+    perfkit.run_cases(a, CASES, lambda name, rows, cols, rank: run_case(name, rows, cols, rank, a, base))
 
 
 if __name__ == "__main__":

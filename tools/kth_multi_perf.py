@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Multi-rank k-th value timings (GPU box): one JSON line per case, the method of tools/kth_perf.py.  float32 normal-distributed
+"""Multi-rank k-th value timings (GPU box): one JSON line per case, the method of tools/perfkit.py.  float32 normal-distributed
 rows, smallest, with positions; device events around the call alone; the median of --reps calls on fresh inputs after --warmup
 calls.  The sides ALTERNATE in one process, call by call, on the same rows:
   multi      lsdsort_kth_multi_device with the case's ranks: ONE call
@@ -13,42 +13,18 @@ the tool asserts that they agree bit for bit, values and positions.
 Rank sets: the adjacent pair around the median (m = 2), the quartiles (m = 3), and the eight percentiles 1, 5, 25, 50, 75, 95, 99
 and 99.9 (m = 8).  Shapes: [64 x 2^22], [4096 x 131072], [1 x 2^28] (long rows) and [2^14 x 2^14], [2^20 x 256] (short rows).
 Usage: python tools/kth_multi_perf.py [--reps 20] [--warmup 3] [--spread-repeats 5] [--only SHAPE] [--baseline-lib PATH] [--out FILE]"""
-import argparse
 import ctypes
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
+import perfkit
 
 F32 = 2
-c_size, c_int, c_ptr = ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p
-
-
-def baseline_library(path):
-    """the three entries of the baseline leg, bound in the library at `path` (None: this tree's)"""
-    if path is None:
-        return lsd.lib()
-    L = ctypes.CDLL(os.path.abspath(path))
-    L.lsdsort_kth_workspace_bytes.restype, L.lsdsort_kth_workspace_bytes.argtypes = c_size, [c_size, c_size]
-    L.lsdsort_kth_device.restype = c_int
-    L.lsdsort_kth_device.argtypes = [c_ptr, c_size, c_size, c_size, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]
-    L.lsdsort_check_device.restype, L.lsdsort_check_device.argtypes = c_int, [c_ptr, c_ptr]
-    return L
-
-
-def one(fn):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
+BASELINE_ENTRIES = ("lsdsort_kth_workspace_bytes", "lsdsort_kth_device", "lsdsort_check_device")
 
 
 def rank_sets(cols):
@@ -67,7 +43,7 @@ def run_case(shape, set_name, rows, cols, ranks, a, base):
     one_k = torch.empty((m, rows), dtype=torch.float32, device="cuda")
     one_i = torch.empty((m, rows), dtype=torch.int32, device="cuda")
     L = lsd.lib()
-    c_ranks = (c_size * m)(*ranks)
+    c_ranks = (ctypes.c_size_t * m)(*ranks)
     ws = torch.empty(L.lsdsort_kth_multi_workspace_bytes(rows, cols, m), dtype=torch.uint8, device="cuda")
     ws_b = torch.empty(base.lsdsort_kth_workspace_bytes(rows, cols), dtype=torch.uint8, device="cuda")
     stream = int(torch.cuda.current_stream().cuda_stream)
@@ -84,20 +60,7 @@ def run_case(shape, set_name, rows, cols, ranks, a, base):
             assert st == 0, st
 
     sides = {"multi": multi, "baseline": baseline}
-    medians = {side: [] for side in sides}
-    for repeat in range(a.spread_repeats):
-        ts = {side: [] for side in sides}
-        for i in range(a.warmup + a.reps):
-            x.normal_(0.0, 1.0, generator=g)
-            for side, fn in sides.items():   # the sides alternate, call by call, on the same rows
-                if repeat > 0 and side != "baseline":
-                    continue                  # the further repeats measure the baseline's spread
-                t = one(fn)
-                if i >= a.warmup:
-                    ts[side].append(t)
-        for side in sides:
-            if ts[side]:
-                medians[side].append(float(np.median(ts[side])))
+    medians = perfkit.measure(sides, {"baseline"}, a.spread_repeats, a.reps, a.warmup, fresh=lambda: x.normal_(0.0, 1.0, generator=g))
     assert L.lsdsort_check_device(ws.data_ptr(), None) == 0 and base.lsdsort_check_device(ws_b.data_ptr(), None) == 0
     # once more, untimed, on the same rows: the two sides answer the same question, bit for bit
     multi()
@@ -106,13 +69,13 @@ def run_case(shape, set_name, rows, cols, ranks, a, base):
     assert torch.equal(out_k.view(torch.int32), one_k.t().contiguous().view(torch.int32)), "multi and the baseline disagree in a value"
     assert torch.equal(out_i, one_i.t()), "multi and the baseline disagree in a position"
     b = medians["baseline"]
-    multi_ms, base_ms, spread = medians["multi"][0], float(np.median(b)), max(b) - min(b)
+    multi_ms, (base_ms, spread) = medians["multi"][0], perfkit.spread_of(b)
     return {"shape": shape, "ranks": set_name, "rows": rows, "cols": cols, "num_ranks": m, "rank_values": ranks, "dtype": "float32",
             "largest": False, "positions": True, "reps": a.reps, "warmup": a.warmup, "multi_ms": multi_ms,
             "baseline": f"{m} x lsdsort_kth_device" + (" (parent commit's library)" if a.baseline_lib else " (this tree's library)"),
             "baseline_ms": base_ms, "baseline_repeats_ms": b, "baseline_spread_ms": spread,
             "speedup_vs_baseline": base_ms / multi_ms, "ahead": bool(base_ms - multi_ms > spread),
-            "multi_TBs_at_4B_per_key": 4.0 * n / (multi_ms * 1e-3) / 1e12, "multi_bytes_per_key_at_5p5TBs": multi_ms * 1e-3 * 5.5e12 / n,
+            "multi_TBs_at_4B_per_key": 4.0 * n / (multi_ms * 1e-3) / 1e12, "multi_bytes_per_key_at_5p5TBs": perfkit.bytes_per_key(multi_ms, n),
             "workspace_bytes": ws.numel(), "baseline_workspace_bytes": ws_b.numel()}
 
 
@@ -125,27 +88,15 @@ SHAPES = {
 }
 
 
+def parser():
+    return perfkit.parser(__doc__, spread_repeats=5, lib_flag="--baseline-lib")
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--spread-repeats", type=int, default=5)
-    ap.add_argument("--only", default=None)
-    ap.add_argument("--baseline-lib", default=None)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    base = baseline_library(a.baseline_lib)
-    sink = open(a.out, "a") if a.out else None
-    for shape, (rows, cols) in SHAPES.items():
-        if a.only and a.only != shape:
-            continue
-        for set_name, ranks in rank_sets(cols).items():
-            line = json.dumps(run_case(shape, set_name, rows, cols, ranks, a, base))
-            print(line, flush=True)
-            if sink:
-                sink.write(line + "\n")
-                sink.flush()
-            torch.cuda.empty_cache()
+    a = parser().parse_args()
+    base = perfkit.bound_library(a.baseline_lib, BASELINE_ENTRIES)
+    perfkit.run_cases(a, SHAPES, lambda shape, rows, cols: (run_case(shape, set_name, rows, cols, ranks, a, base)
+                                                            for set_name, ranks in rank_sets(cols).items()))
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""K-th value timings (GPU box): one JSON line per case, the method of tools/topk16_perf.py and tools/rows16_perf.py.  float32
+"""K-th value timings (GPU box): one JSON line per case, the method of tools/perfkit.py.  float32
 normal-distributed rows, smallest, with positions; device events around the call alone; the median of --reps calls on fresh inputs
 after --warmup calls.  The sides ALTERNATE in one process, call by call, on the same rows:
   kth        lsdsort_kth_device at the given rank
@@ -14,9 +14,6 @@ is ahead of the baseline by more than that spread.
 Cases: the lower-median rank of [64 x 2^22], [4096 x 131072], [1 x 2^28], [2^14 x 2^14], [2^20 x 256]; rank 1023 of [1 x 2^28].
 Usage: python tools/kth_perf.py [--reps 20] [--warmup 3] [--spread-repeats 5] [--torch-reps 3] [--only NAME] [--baseline-lib PATH]
                                 [--out FILE]"""
-import argparse
-import ctypes
-import json
 import os
 import sys
 
@@ -25,31 +22,10 @@ import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
+import perfkit
 
 F32 = 2
-c_size, c_int, c_ptr = ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p
-
-
-def baseline_library(path):
-    """the three entries of the baseline leg, bound in the library at `path` (None: this tree's)"""
-    if path is None:
-        return lsd.lib()
-    L = ctypes.CDLL(os.path.abspath(path))
-    L.lsdsort_topk_workspace_bytes.restype, L.lsdsort_topk_workspace_bytes.argtypes = c_size, [c_size, c_size, c_size]
-    L.lsdsort_topk_device.restype = c_int
-    L.lsdsort_topk_device.argtypes = [c_ptr, c_size, c_size, c_size, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]
-    L.lsdsort_check_device.restype, L.lsdsort_check_device.argtypes = c_int, [c_ptr, c_ptr]
-    return L
-
-
-def one(fn):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
+BASELINE_ENTRIES = ("lsdsort_topk_workspace_bytes", "lsdsort_topk_device", "lsdsort_check_device")
 
 
 def run_case(name, rows, cols, rank, a, base):
@@ -77,20 +53,7 @@ def run_case(name, rows, cols, rank, a, base):
         assert st == 0, st
 
     sides = {"kth": kth, "baseline": baseline}
-    medians = {side: [] for side in sides}
-    for repeat in range(a.spread_repeats):
-        ts = {side: [] for side in sides}
-        for i in range(a.warmup + a.reps):
-            x.normal_(0.0, 1.0, generator=g)
-            for side, fn in sides.items():   # the sides alternate, call by call, on the same rows
-                if repeat > 0 and side != "baseline":
-                    continue                  # the further repeats measure the baseline's spread
-                t = one(fn)
-                if i >= a.warmup:
-                    ts[side].append(t)
-        for side in sides:
-            if ts[side]:
-                medians[side].append(float(np.median(ts[side])))
+    medians = perfkit.measure(sides, {"baseline"}, a.spread_repeats, a.reps, a.warmup, fresh=lambda: x.normal_(0.0, 1.0, generator=g))
     assert L.lsdsort_check_device(ws.data_ptr(), None) == 0 and base.lsdsort_check_device(ws_b.data_ptr(), None) == 0
     # once more, untimed, on the same rows: the two sides answer the same question
     kth()
@@ -98,13 +61,13 @@ def run_case(name, rows, cols, rank, a, base):
     torch.cuda.synchronize()
     assert torch.equal(out_k, top_k[:, -1]) and torch.equal(out_i, top_i[:, -1]), "kth and the baseline disagree"
     b = medians["baseline"]
-    kth_ms, base_ms, spread = medians["kth"][0], float(np.median(b)), max(b) - min(b)
+    kth_ms, (base_ms, spread) = medians["kth"][0], perfkit.spread_of(b)
     out = {"case": name, "rows": rows, "cols": cols, "rank": rank, "dtype": "float32", "largest": False, "positions": True,
            "reps": a.reps, "warmup": a.warmup, "kth_ms": kth_ms,
            "baseline": "lsdsort_topk_device k=rank+1" + (" (parent commit's library)" if a.baseline_lib else " (this tree's library)"),
            "baseline_ms": base_ms, "baseline_repeats_ms": b, "baseline_spread_ms": spread,
            "speedup_vs_baseline": base_ms / kth_ms, "ahead": bool(base_ms - kth_ms > spread),
-           "kth_bytes_per_key_at_5p5TBs": kth_ms * 1e-3 * 5.5e12 / n, "kth_TBs_at_4B_per_key": 4.0 * n / (kth_ms * 1e-3) / 1e12,
+           "kth_bytes_per_key_at_5p5TBs": perfkit.bytes_per_key(kth_ms, n), "kth_TBs_at_4B_per_key": 4.0 * n / (kth_ms * 1e-3) / 1e12,
            "workspace_bytes": ws.numel(), "baseline_workspace_bytes": ws_b.numel()}
     del top_k, top_i, ws_b
     torch.cuda.empty_cache()
@@ -112,7 +75,7 @@ def run_case(name, rows, cols, rank, a, base):
         ts = []
         for i in range(1 + a.torch_reps):
             x.normal_(0.0, 1.0, generator=g)
-            t = one(lambda: torch.kthvalue(x, k, dim=-1))
+            t = perfkit.one(lambda: torch.kthvalue(x, k, dim=-1))
             if i >= 1:
                 ts.append(t)
             elif t > 2000.0:   # seconds per call: the warm-up call is the record
@@ -137,27 +100,16 @@ CASES = {
 }
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--spread-repeats", type=int, default=5)
+def parser():
+    ap = perfkit.parser(__doc__, spread_repeats=5, lib_flag="--baseline-lib")
     ap.add_argument("--torch-reps", type=int, default=3)
-    ap.add_argument("--only", default=None)
-    ap.add_argument("--baseline-lib", default=None)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    base = baseline_library(a.baseline_lib)
-    sink = open(a.out, "a") if a.out else None
-    for name, (rows, cols, rank) in CASES.items():
-        if a.only and a.only != name:
-            continue
-        line = json.dumps(run_case(name, rows, cols, rank, a, base))
-        print(line, flush=True)
-        if sink:
-            sink.write(line + "\n")
-            sink.flush()
-        torch.cuda.empty_cache()
+    return ap
+
+
+def main():
+    a = parser().parse_args()
+    base = perfkit.bound_library(a.baseline_lib, BASELINE_ENTRIES)
+    perfkit.run_cases(a, CASES, lambda name, rows, cols, rank: run_case(name, rows, cols, rank, a, base))
 
 
 if __name__ == "__main__":

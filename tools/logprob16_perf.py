@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Timings of logprob16 -- log-probabilities and ranks of given tokens of 16-bit logit rows (GPU box): one JSON line per shape and
-case, the method of tools/sample16_perf.py.  bfloat16 normal logits scaled by 4, 16-byte aligned, a temperature per row in [0.5, 1.5],
+case, the method of tools/perfkit.py.  bfloat16 normal logits scaled by 4, 16-byte aligned, a temperature per row in [0.5, 1.5],
 ids uniform over the row; device events around the call alone; the median of --reps calls on fresh rows after --warmup calls.  The
 sides ALTERNATE in one process, call by call, on the same rows, ids and temperatures.
 Case a, slots = 1, no ranks:
@@ -22,53 +22,18 @@ go through float64: every logprob within 2^-11 + 2^-22 |(x - m) / T|, every rank
 Shapes: [128 x 128256], [4096 x 131072], [2^14 x 2^14], [2^20 x 256]; recorded without a gate: [8192 x 128256], case a.
 Usage: python tools/logprob16_perf.py [--reps 20] [--warmup 3] [--spread-repeats 5] [--only NAME] [--case a|b] [--check-rows 256]
                                       [--out profiles/logprob16_perf.jsonl]"""
-import argparse
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
+import perfkit
 
 BF16 = 3
 TOL = 2.0 ** -11
 BROADCAST_LIMIT = 24 << 30       # bytes of the broadcast form's boolean intermediate above which it is not attempted
-
-
-def one(fn):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def measure(sides, baselines, fresh, a):
-    """side -> the medians of its repeats (one for a side that is no baseline).  `sides` keeps its order within an iteration."""
-    medians = {side: [] for side in sides}
-    for repeat in range(a.spread_repeats):
-        ts = {side: [] for side in sides}
-        for i in range(a.warmup + a.reps):
-            fresh()
-            for side, fn in sides.items():   # the sides alternate, call by call, on the same rows
-                if repeat > 0 and side not in baselines:
-                    continue                  # the further repeats measure the baselines' spread
-                t = one(fn)
-                if i >= a.warmup:
-                    ts[side].append(t)
-        for side in sides:
-            if ts[side]:
-                medians[side].append(float(np.median(ts[side])))
-    return medians
-
-
-def verdict(side_ms, base_ms, spread):
-    return "ahead" if base_ms - side_ms > spread else ("behind" if side_ms - base_ms > spread else "within spread")
 
 
 def checked(x, ids, T, logprob, rank, lse):
@@ -149,8 +114,8 @@ def run(name, rows, cols, case, a):
         sides = {"logprob": lambda: entry(True), "baseline_loop": base_loop, "logprob_no_ranks": lambda: entry(False)}
         if n * slots <= BROADCAST_LIMIT:
             sides["baseline_broadcast"] = base_broadcast
-        baselines = tuple(s for s in sides if s.startswith("baseline"))
-    medians = measure(sides, baselines, fresh, a)
+        baselines = tuple(s for s in ("baseline_loop", "baseline_broadcast") if s in sides)
+    medians = perfkit.measure(sides, baselines, a.spread_repeats, a.reps, a.warmup, fresh=fresh)
     kept.clear()
     torch.cuda.empty_cache()
     # once more, untimed: the entry's three outputs through float64
@@ -165,15 +130,16 @@ def run(name, rows, cols, case, a):
            "warmup": a.warmup, "workspace_bytes": ws.numel(), "rows_checked": int(pick.numel()), "within_tolerance": list(agreed)}
     for side in baselines:
         b = medians[side]
-        out[side + "_ms"], out[side + "_repeats_ms"], out[side + "_spread_ms"] = float(np.median(b)), b, max(b) - min(b)
+        ms, spread = perfkit.spread_of(b)
+        out[side + "_ms"], out[side + "_repeats_ms"], out[side + "_spread_ms"] = ms, b, spread
     faster = min(baselines, key=lambda side: out[side + "_ms"])
     out["faster_baseline"] = faster
     for side in sides:
         if side not in baselines:
             out[side + "_ms"] = medians[side][0]
     out["speedup"] = out[faster + "_ms"] / out["logprob_ms"]
-    out["bytes_per_key_at_5p5TBs"] = out["logprob_ms"] * 1e-3 * 5.5e12 / n
-    out["verdict"] = verdict(out["logprob_ms"], out[faster + "_ms"], out[faster + "_spread_ms"])
+    out["bytes_per_key_at_5p5TBs"] = perfkit.bytes_per_key(out["logprob_ms"], n)
+    out["verdict"] = perfkit.verdict(out["logprob_ms"], out[faster + "_ms"], out[faster + "_spread_ms"])
     return out
 
 
@@ -186,29 +152,17 @@ CASES = {
 }
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--spread-repeats", type=int, default=5)
-    ap.add_argument("--only", default=None)
+def parser():
+    ap = perfkit.parser(__doc__, spread_repeats=5)
     ap.add_argument("--case", default=None, choices=("a", "b"))
     ap.add_argument("--check-rows", type=int, default=256)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    sink = open(a.out, "a") if a.out else None
-    for name, (rows, cols, cases) in CASES.items():
-        if a.only and a.only != name:
-            continue
-        for case in cases:
-            if a.case and a.case != case:
-                continue
-            line = json.dumps(run(name, rows, cols, case, a))
-            print(line, flush=True)
-            if sink:
-                sink.write(line + "\n")
-                sink.flush()
-            torch.cuda.empty_cache()
+    return ap
+
+
+def main():
+    a = parser().parse_args()
+    perfkit.run_cases(a, CASES, lambda name, rows, cols, cases: (run(name, rows, cols, case, a) for case in cases
+                                                                 if not a.case or a.case == case))
 
 
 if __name__ == "__main__":

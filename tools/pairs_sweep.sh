@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU parity suite, then bench.py --pairs over the tile configurations (two runs each).
-set -e
+set -eo pipefail   # a bench.py run that fails or runs out of time ends the script
 mkdir -p gpurun_out
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > gpurun_out/pytest_pairs.log 2>&1 || { tail -30 gpurun_out/pytest_pairs.log; exit 1; }
 tail -3 gpurun_out/pytest_pairs.log

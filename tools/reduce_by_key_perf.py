@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timings of reduce by key (GPU box): one JSON line per case and operation, the method of tools/unique_perf.py.
+"""Timings of reduce by key (GPU box): one JSON line per case and operation, the method of tools/perfkit.py.
 Device events around the call alone, on the same keys and values for every side; the sides ALTERNATE in one process, call by call,
 in --rounds rounds (six) of --warmup + --reps calls each.  A side's time is the median of its round medians, its spread the largest
 minus the smallest of them.
@@ -22,49 +22,18 @@ Byte accounting of the three phases as timed here (with counts), per key of widt
 and values, 2 (w + 4), and per group the word, the aggregate and the count, (w + 8) d / n.
 Usage: python tools/reduce_by_key_perf.py [--rounds 6] [--reps 5] [--warmup 2] [--only NAME] [--op f32_sum|i32_max]
                                           [--out profiles/reduce_by_key_perf.jsonl]"""
-import argparse
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
+import perfkit
 from lsdradixsort_amd import errors as E
 
 KEY_CODE = {"uint32": E.LSDSORT_KEY_U32, "int64": E.LSDSORT_KEY_I64}
 OPS = {"f32_sum": (torch.float32, E.LSDSORT_VAL_F32, E.LSDSORT_REDUCE_SUM), "i32_max": (torch.int32, E.LSDSORT_VAL_I32, E.LSDSORT_REDUCE_MAX)}
-
-
-def one(fn):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def measure(sides, a):
-    """side -> its round medians; the sides alternate call by call within every round"""
-    rounds = {side: [] for side in sides}
-    for _ in range(a.rounds):
-        ts = {side: [] for side in sides}
-        for i in range(a.warmup + a.reps):
-            for side, fn in sides.items():
-                t = one(fn)
-                if i >= a.warmup:
-                    ts[side].append(t)
-        for side in sides:
-            rounds[side].append(float(np.median(ts[side])))
-    return rounds
-
-
-def verdict(side_ms, base_ms, spread):
-    return "ahead" if base_ms - side_ms > spread else ("behind" if side_ms - base_ms > spread else "within spread")
 
 
 def make_keys(n, key_type, kind):
@@ -152,7 +121,7 @@ def run(name, n, key_type, kind, op, a):
 
     sides = {"reduce_by_key": reduce_by_key, "unique_scatter": unique_scatter, "sort_scatter": sort_scatter, "sort": sort, "runs": runs,
              "torch_runs": torch_runs, "copy": lambda: copy.copy_(x)}
-    rounds = measure(sides, a)
+    rounds = perfkit.measure(sides, None, a.rounds, a.reps, a.warmup)   # every side in every round
     # once more, untimed: the entry against baseline (a), and the runs entry against the entry
     runs()
     torch.cuda.synchronize()
@@ -170,13 +139,14 @@ def run(name, n, key_type, kind, op, a):
     res = {"case": name, "op": op, "n": n, "key_type": key_type, "kind": kind, "groups": m, "rounds": a.rounds, "reps": a.reps,
            "warmup": a.warmup, "workspace_bytes": ws.numel(), "agrees_with_baseline": bool(agreed)}
     for side, r in rounds.items():
-        res[side + "_ms"], res[side + "_rounds_ms"], res[side + "_spread_ms"] = float(np.median(r)), r, max(r) - min(r)
+        ms, spread = perfkit.spread_of(r)
+        res[side + "_ms"], res[side + "_rounds_ms"], res[side + "_spread_ms"] = ms, r, spread
     faster = min(("unique_scatter", "sort_scatter"), key=lambda side: res[side + "_ms"])
     res["faster_baseline"] = faster
     res["speedup"] = res[faster + "_ms"] / res["reduce_by_key_ms"]
     res["speedup_unique_scatter"] = res["unique_scatter_ms"] / res["reduce_by_key_ms"]
     res["speedup_sort_scatter"] = res["sort_scatter_ms"] / res["reduce_by_key_ms"]
-    res["verdict"] = verdict(res["reduce_by_key_ms"], res[faster + "_ms"], res[faster + "_spread_ms"])
+    res["verdict"] = perfkit.verdict(res["reduce_by_key_ms"], res[faster + "_ms"], res[faster + "_spread_ms"])
     res["gated"] = key_type == "uint32"
     res["sort_share"] = res["sort_ms"] / res["reduce_by_key_ms"]
     res["runs_speedup_torch"] = res["torch_runs_ms"] / res["runs_ms"]
@@ -195,28 +165,17 @@ def cases():
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=6)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--only", default=None)
+def parser():
+    ap = perfkit.parser(__doc__, reps=5, warmup=2, rounds=6, only_help="run the cases whose name contains this")
     ap.add_argument("--op", default=None, choices=tuple(OPS))
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    sink = open(a.out, "a") if a.out else None
-    for name, (n, key_type, kind) in cases().items():
-        if a.only and a.only not in name:
-            continue
-        for op in OPS:
-            if a.op and a.op != op:
-                continue
-            line = json.dumps(run(name, n, key_type, kind, op, a))
-            print(line, flush=True)
-            if sink:
-                sink.write(line + "\n")
-                sink.flush()
-            torch.cuda.empty_cache()
+    return ap
+
+
+def main():
+    a = parser().parse_args()
+    perfkit.run_cases(a, cases(), lambda name, n, key_type, kind: (run(name, n, key_type, kind, op, a)
+                                                                   for op in OPS if not a.op or a.op == op),
+                      match="substring")
 
 
 if __name__ == "__main__":

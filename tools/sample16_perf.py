@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timings of the draw for 16-bit logit rows (GPU box): one JSON line per shape, the method of tools/topp16_filter_perf.py.
+"""Timings of the draw for 16-bit logit rows (GPU box): one JSON line per shape, the method of tools/perfkit.py.
 bfloat16 normal logits scaled by 4, 16-byte aligned, u_r uniform per row; device events around the call alone; the median of --reps
 calls on fresh rows after --warmup calls.  The sides ALTERNATE in one process, call by call, on the same rows and the same u:
   sample            lsdsort_sample16_device without d_logprob
@@ -20,56 +20,19 @@ up to 16384 keys, about 4 B/key above).
 Shapes: [128 x 128256], [4096 x 131072], [2^14 x 2^14], [2^20 x 256].
 Usage: python tools/sample16_perf.py [--reps 20] [--warmup 3] [--spread-repeats 5] [--only NAME] [--check-rows 256]
                                      [--out profiles/sample16_perf.jsonl]"""
-import argparse
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
+import perfkit
 
 BF16 = 3
 NEG_INF_BITS = 0xFF80
 TOLERANCE = 2.0 ** -12
 BASELINES = ("multinomial", "cumsum")
-
-
-def one(fn, prepare=None):
-    if prepare:
-        prepare()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def measure(sides, prepare, fresh, a):
-    """side -> the medians of its repeats (one for a side that is no baseline).  `sides` keeps its order within an iteration."""
-    medians = {side: [] for side in sides}
-    for repeat in range(a.spread_repeats):
-        ts = {side: [] for side in sides}
-        for i in range(a.warmup + a.reps):
-            fresh()
-            for side, fn in sides.items():   # the sides alternate, call by call, on the same rows
-                if repeat > 0 and side not in BASELINES:
-                    continue                  # the further repeats measure the baselines' spread
-                t = one(fn, prepare.get(side))
-                if i >= a.warmup:
-                    ts[side].append(t)
-        for side in sides:
-            if ts[side]:
-                medians[side].append(float(np.median(ts[side])))
-    return medians
-
-
-def verdict(side_ms, base_ms, spread):
-    return "ahead" if base_ms - side_ms > spread else ("behind" if side_ms - base_ms > spread else "within spread")
 
 
 def accepted(x, index, u):
@@ -138,7 +101,8 @@ def run(name, rows, cols, a):
     sides = {"sample": lambda: draw(x, None), "sample_logprob": lambda: draw(x, logprob.data_ptr()), "multinomial": multinomial,
              "cumsum": cumsum, "chain": chain, "chain_multinomial": chain_multinomial}
     copy = lambda: y.copy_(x)
-    medians = measure(sides, {"chain": copy, "chain_multinomial": copy}, fresh, a)
+    medians = perfkit.measure(sides, BASELINES, a.spread_repeats, a.reps, a.warmup, fresh=fresh,
+                              prepare={"chain": copy, "chain_multinomial": copy})
     for w in (ws, ws_k, ws_p):
         assert L.lsdsort_check_device(w.data_ptr(), None) == 0
     # once more, untimed, on the same rows: this side and baseline (b) under the acceptance rule
@@ -160,15 +124,16 @@ def run(name, rows, cols, a):
            "chain": {"k": 50, "p": 0.9}}
     for side in BASELINES:
         b = medians[side]
-        out[side + "_ms"], out[side + "_repeats_ms"], out[side + "_spread_ms"] = float(np.median(b)), b, max(b) - min(b)
+        ms, spread = perfkit.spread_of(b)
+        out[side + "_ms"], out[side + "_repeats_ms"], out[side + "_spread_ms"] = ms, b, spread
     faster = min(BASELINES, key=lambda side: out[side + "_ms"])
     out["faster_baseline"] = faster
     for side in ("sample", "sample_logprob", "chain", "chain_multinomial"):
         out[side + "_ms"] = medians[side][0]
     for side in ("sample", "sample_logprob"):
         out[side + "_speedup"] = out[faster + "_ms"] / out[side + "_ms"]
-        out[side + "_bytes_per_key_at_5p5TBs"] = out[side + "_ms"] * 1e-3 * 5.5e12 / n
-    out["verdict"] = verdict(out["sample_ms"], out[faster + "_ms"], out[faster + "_spread_ms"])
+        out[side + "_bytes_per_key_at_5p5TBs"] = perfkit.bytes_per_key(out[side + "_ms"], n)
+    out["verdict"] = perfkit.verdict(out["sample_ms"], out[faster + "_ms"], out[faster + "_spread_ms"])
     out["chain_speedup"] = out["chain_multinomial_ms"] / out["chain_ms"]
     return out
 
@@ -181,26 +146,15 @@ CASES = {
 }
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--spread-repeats", type=int, default=5)
-    ap.add_argument("--only", default=None)
+def parser():
+    ap = perfkit.parser(__doc__, spread_repeats=5)
     ap.add_argument("--check-rows", type=int, default=256)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    sink = open(a.out, "a") if a.out else None
-    for name, (rows, cols) in CASES.items():
-        if a.only and a.only != name:
-            continue
-        result = run(name, rows, cols, a)
-        line = json.dumps(result)
-        print(line, flush=True)
-        if sink:
-            sink.write(line + "\n")
-            sink.flush()
-        torch.cuda.empty_cache()
+    return ap
+
+
+def main():
+    a = parser().parse_args()
+    perfkit.run_cases(a, CASES, lambda name, rows, cols: run(name, rows, cols, a))
 
 
 if __name__ == "__main__":

@@ -1,14 +1,12 @@
 #!/usr/bin/env python3
 """Segmented sort timings (GPU box): one JSON line per shape, device-event timing of the sort alone on a fresh copy of the
-keys each rep (warm-up first, median and min of the timed reps), next to what it is compared with:
+keys each rep (warm-up first, median and min of the timed reps: perfkit.timed), next to what it is compared with:
   [2^14 x 2^14]            workgroup tier   GPULSDRadixSort of the same 2^28 keys as one array; torch.sort(dim=-1)
   [2^20 x 256]             wave tier        torch.sort(dim=-1)
   1e6 lognormal segments   wave/workgroup   torch.sort(dim=-1) of a row-padded copy (rows of the largest segment)
   [64 x 2^22]              large tier       GPULSDRadixSort(algorithm=STAGED) of the 2^28 keys as one array; torch.sort(dim=-1)
   [32 x 131072] float32 descending + indices: large tier vs torch.sort(dim=-1, descending=True, stable=True)
 Usage: python tools/segmented_perf.py [--reps 20] [--warmup 3] [--only NAME]"""
-import argparse
-import json
 import os
 import sys
 
@@ -17,22 +15,8 @@ import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
-
-
-def timed(fn, fresh, reps, warmup):
-    """fresh() -> the call's inputs (copied outside the timed region); fn(*inputs) is timed by device events"""
-    ts = []
-    for i in range(warmup + reps):
-        args = fresh()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn(*args)
-        e1.record()
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append(e0.elapsed_time(e1))
-    return float(np.median(ts)), float(np.min(ts))
+import perfkit
+from perfkit import timed
 
 
 def shape_rows(name, rows, cols, reps, warmup, whole_algo=None, dtype=torch.int32, descending=False, indices=False):
@@ -53,18 +37,17 @@ def shape_rows(name, rows, cols, reps, warmup, whole_algo=None, dtype=torch.int3
         work.copy_(src)
         if indices:
             vals.copy_(iota)
-        return ()
 
     seg_ms = timed(lambda: lsd.GPUSortSegmented(work, off, d_vals=vals, key_type=key_type, descending=descending, workspace=ws),
                    fresh, reps, warmup)
     out = {"shape": name, "n": n, "segments": rows, "segmented_ms": seg_ms[0], "segmented_min_ms": seg_ms[1],
            "segmented_gkeys_s": n / seg_ms[0] / 1e6}
     ref = src.view(rows, cols) if dtype == torch.float32 else (src.to(torch.int64) & 0xFFFFFFFF).view(rows, cols)
-    t_ms = timed(lambda: torch.sort(ref, dim=-1, descending=descending, stable=True), lambda: (), reps, warmup)
+    t_ms = timed(lambda: torch.sort(ref, dim=-1, descending=descending, stable=True), None, reps, warmup)
     out["torch_sort_ms"] = t_ms[0]
     out["torch_sort_dtype"] = str(ref.dtype)
     if dtype == torch.int32:   # torch on the int32 bits too (signed order: the same work)
-        t32 = timed(lambda: torch.sort(src.view(rows, cols), dim=-1, stable=True), lambda: (), reps, warmup)
+        t32 = timed(lambda: torch.sort(src.view(rows, cols), dim=-1, stable=True), None, reps, warmup)
         out["torch_sort_int32_ms"] = t32[0]
     if whole_algo is not None:
         wws = lsd.alloc_workspace(n, 8, False, whole_algo)
@@ -86,7 +69,6 @@ def shape_lognormal(reps, warmup):
 
     def fresh():
         work.copy_(src)
-        return ()
 
     seg_ms = timed(lambda: lsd.GPUSortSegmented(work, off, workspace=ws), fresh, reps, warmup)
     classes = {"wave": int(((sizes >= 2) & (sizes <= 1024)).sum()), "workgroup": int(((sizes > 1024) & (sizes <= 16384)).sum()),
@@ -96,7 +78,7 @@ def shape_lognormal(reps, warmup):
     width = int(sizes.max())
     if sizes.size * width <= (1 << 29):
         padded = torch.full((sizes.size, width), 0x7FFFFFFF, dtype=torch.int32, device="cuda")
-        out["torch_sort_padded_ms"] = timed(lambda: torch.sort(padded, dim=-1, stable=True), lambda: (), reps, warmup)[0]
+        out["torch_sort_padded_ms"] = timed(lambda: torch.sort(padded, dim=-1, stable=True), None, reps, warmup)[0]
         out["torch_padded_shape"] = [int(sizes.size), width]
     else:
         out["torch_sort_padded_ms"] = None
@@ -104,12 +86,12 @@ def shape_lognormal(reps, warmup):
     return out
 
 
+def parser():
+    return perfkit.parser(__doc__, out=False)
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--only", default=None)
-    a = ap.parse_args()
+    a = parser().parse_args()
     shapes = {
         "rows_16384x16384": lambda: shape_rows("rows_16384x16384", 1 << 14, 1 << 14, a.reps, a.warmup, whole_algo=lsd.LSDSORT_ALGO_ONESWEEP),
         "rows_1048576x256": lambda: shape_rows("rows_1048576x256", 1 << 20, 256, a.reps, a.warmup),
@@ -118,11 +100,7 @@ def main():
         "rows_32x131072_f32_desc_idx": lambda: shape_rows("rows_32x131072_f32_desc_idx", 32, 131072, a.reps, a.warmup,
                                                           dtype=torch.float32, descending=True, indices=True),
     }
-    for name, fn in shapes.items():
-        if a.only and a.only != name:
-            continue
-        print(json.dumps(fn()), flush=True)
-        torch.cuda.empty_cache()
+    perfkit.run_cases(a, {name: () for name in shapes}, lambda name: shapes[name]())
 
 
 if __name__ == "__main__":

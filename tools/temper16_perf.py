@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Timings of the per-row temperature and min-p of the 16-bit sampling chain (GPU box): one JSON line per shape, the method of
-tools/sample16_perf.py.  bfloat16 normal logits scaled by 4, 16-byte aligned; u uniform per row, T from {0.5, 0.7, 1, 1.3} by row,
+tools/perfkit.py.  bfloat16 normal logits scaled by 4, 16-byte aligned; u uniform per row, T from {0.5, 0.7, 1, 1.3} by row,
 p = 0.9, mp = 0.05; device events around the call alone; the median of --reps calls on fresh rows after --warmup calls.  The sides
 ALTERNATE in one process, call by call, on the same rows.  Every baseline is measured --spread-repeats times over: its spread is the
 largest minus the smallest of those medians.
@@ -27,9 +27,6 @@ largest minus the smallest of those medians.
                                    torch.topk, the sort-based filter above and multinomial
 Usage: python tools/temper16_perf.py [--parent-lib PATH] [--gate1-rounds N] [--reps 20] [--warmup 3] [--spread-repeats 5] [--only NAME] [--check-rows 256]
                                      [--out profiles/temper16_perf.jsonl]"""
-import argparse
-import ctypes
-import json
 import os
 import sys
 
@@ -40,54 +37,13 @@ import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
-from lsdradixsort_amd import _lib as binding
+import perfkit
+from perfkit import spread_of, verdict
 
 BF16 = 3
 NEG_INF_BITS = 0xFF80
 BASELINES = ("parent_filter", "parent_draw", "multinomial_T", "cumsum_T", "sort_filter")
-
-
-def one(fn, prepare=None):
-    if prepare:
-        prepare()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def measure(sides, prepare, fresh, a):
-    medians = {side: [] for side in sides}
-    for repeat in range(a.spread_repeats):
-        ts = {side: [] for side in sides}
-        for i in range(a.warmup + a.reps):
-            fresh()
-            for side, fn in sides.items():   # the sides alternate, call by call, on the same rows
-                if repeat > 0 and side not in BASELINES:
-                    continue                  # the further repeats measure the baselines' spread
-                t = one(fn, prepare.get(side))
-                if i >= a.warmup:
-                    ts[side].append(t)
-        for side in sides:
-            if ts[side]:
-                medians[side].append(float(np.median(ts[side])))
-    return medians
-
-
-def verdict(side_ms, base_ms, spread):
-    return "ahead" if base_ms - side_ms > spread else ("behind" if side_ms - base_ms > spread else "within spread")
-
-
-def parent_library(path):
-    lib = ctypes.CDLL(path)
-    for name in ("lsdsort_topp16_filter_device", "lsdsort_sample16_device", "lsdsort_prepare_device"):
-        if name in binding.SIGNATURES:
-            getattr(lib, name).restype, getattr(lib, name).argtypes = binding.SIGNATURES[name]
-    assert lib.lsdsort_prepare_device() == 0
-    return lib
+PARENT_ENTRIES = ("lsdsort_topp16_filter_device", "lsdsort_sample16_device", "lsdsort_prepare_device")
 
 
 def run(name, rows, cols, a, parent):
@@ -164,24 +120,15 @@ def run(name, rows, cols, a, parent):
         sides.update({"parent_filter": lambda: old_filter(parent), "parent_draw": lambda: old_draw(parent)})
     if a.gate1_rounds:
         assert parent is not None, "--gate1-rounds needs --parent-lib"
-        rounds = {side: [] for side in sides}
-        for n in range(a.gate1_rounds):
-            order = list(sides) if n % 2 == 0 else ["parent_filter", "parent_draw", "old_filter", "old_draw"]
-            ts = {side: [] for side in sides}
-            for i in range(a.warmup + a.reps):
-                fresh()
-                for side in order:
-                    t = one(sides[side])
-                    if i >= a.warmup:
-                        ts[side].append(t)
-            for side in sides:
-                rounds[side].append(float(np.median(ts[side])))
+        swapped = ["parent_filter", "parent_draw", "old_filter", "old_draw"]
+        rounds = perfkit.measure(sides, None, a.gate1_rounds, a.reps, a.warmup, fresh=fresh,
+                                 order=lambda n: list(sides) if n % 2 == 0 else swapped)
         for w in (ws_d, ws_p):
             assert L.lsdsort_check_device(w.data_ptr(), None) == 0
         res = {"case": name, "rows": rows, "cols": cols, "dtype": "bfloat16", "sigma": 4.0, "reps": a.reps, "warmup": a.warmup, "p": 0.9,
                "gate1_rounds": a.gate1_rounds}
         for side, m in rounds.items():
-            res[side + "_rounds_ms"], res[side + "_ms"], res[side + "_spread_ms"] = m, float(np.median(m)), max(m) - min(m)
+            res[side + "_rounds_ms"], (res[side + "_ms"], res[side + "_spread_ms"]) = m, spread_of(m)
         for mine, base in (("old_filter", "parent_filter"), ("old_draw", "parent_draw")):
             res[mine + "_verdict"] = verdict(res[mine + "_ms"], res[base + "_ms"], res[base + "_spread_ms"])
         return res
@@ -193,7 +140,8 @@ def run(name, rows, cols, a, parent):
         "minp_alone": lambda: ex_filter(x, out, None, d_mp.data_ptr(), d_t.data_ptr()), "minp_torch": minp_torch, "lossy_draw": lossy_draw,
         "chain": chain, "chain_torch": chain_torch})
     copy = lambda: y.copy_(x)
-    medians = measure(sides, {"ex_filter_inplace": copy, "chain": copy, "chain_torch": copy}, fresh, a)
+    medians = perfkit.measure(sides, BASELINES, a.spread_repeats, a.reps, a.warmup, fresh=fresh,
+                              prepare={"ex_filter_inplace": copy, "chain": copy, "chain_torch": copy})
     for w in (ws_d, ws_p, ws_k):
         assert L.lsdsort_check_device(w.data_ptr(), None) == 0
     # once more, untimed, on the same rows: both sides of the two gates under the float64 acceptance rule of the tests
@@ -226,9 +174,9 @@ def run(name, rows, cols, a, parent):
     res = {"case": name, "rows": rows, "cols": cols, "dtype": "bfloat16", "sigma": 4.0, "reps": a.reps, "warmup": a.warmup,
            "T": [0.5, 0.7, 1.0, 1.3], "p": 0.9, "mp": 0.05, "k": 50, "accepted": agreed, "rows_checked": int(pick.size)}
     for side, m in medians.items():
-        res[side + "_ms"] = float(np.median(m))
+        res[side + "_ms"], spread = spread_of(m)
         if side in BASELINES:
-            res[side + "_repeats_ms"], res[side + "_spread_ms"] = m, max(m) - min(m)
+            res[side + "_repeats_ms"], res[side + "_spread_ms"] = m, spread
     if parent is not None:
         for mine, base in (("old_filter", "parent_filter"), ("old_draw", "parent_draw")):
             res[mine + "_verdict"] = verdict(res[mine + "_ms"], res[base + "_ms"], res[base + "_spread_ms"])
@@ -250,29 +198,18 @@ CASES = {
 }
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--parent-lib", default=None)
+def parser():
+    ap = perfkit.parser(__doc__, spread_repeats=5, lib_flag="--parent-lib")
     ap.add_argument("--gate1-rounds", type=int, default=0)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--spread-repeats", type=int, default=5)
-    ap.add_argument("--only", default=None)
     ap.add_argument("--check-rows", type=int, default=256)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    parent = parent_library(a.parent_lib) if a.parent_lib else None
-    sink = open(a.out, "a") if a.out else None
-    for name, (rows, cols) in CASES.items():
-        if a.only and a.only != name:
-            continue
-        result = run(name, rows, cols, a, parent)
-        line = json.dumps(result)
-        print(line, flush=True)
-        if sink:
-            sink.write(line + "\n")
-            sink.flush()
-        torch.cuda.empty_cache()
+    return ap
+
+
+def main():
+    a = parser().parse_args()
+    parent = perfkit.bound_library(a.parent_lib, PARENT_ENTRIES) if a.parent_lib else None
+    assert parent is None or parent.lsdsort_prepare_device() == 0
+    perfkit.run_cases(a, CASES, lambda name, rows, cols: run(name, rows, cols, a, parent))
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timings of the per-row-k entries for 16-bit keys (GPU box): one JSON line per case and mode, the method of tools/kth16_perf.py.
+"""Timings of the per-row-k entries for 16-bit keys (GPU box): one JSON line per case and mode, the method of tools/perfkit.py.
 bfloat16 normal-distributed rows, largest, 16-byte aligned; device events around the call alone; the median of --reps calls on fresh
 inputs after --warmup calls.  The sides ALTERNATE in one process, call by call, on the same rows.  Three modes per shape:
   perrow_k (the gate)   k_r drawn per row from {1, 20, 50, 100, 1000}, capped at cols - 1.
@@ -21,80 +21,35 @@ the tool asserts that they agree, bit for bit.
 Shapes: [128 x 128256], [4096 x 131072], [1 x 2^28], [2^14 x 2^14], [2^20 x 256].
 Usage: python tools/topk16_filter_perf.py [--reps 20] [--warmup 3] [--spread-repeats 5] [--only NAME] [--modes a,b] [--baseline-lib PATH]
                                           [--out profiles/topk16_filter_perf.jsonl]"""
-import argparse
-import ctypes
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
+import perfkit
 
 BF16 = 3
 NEG_INF_BITS = 0xFF80
-c_size, c_int, c_ptr = ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p
-SELECT = [c_ptr, c_size, c_size, c_size, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]   # topk16's and kth16's argument list
+BASELINE_ENTRIES = ("lsdsort_topk16_workspace_bytes", "lsdsort_kth16_workspace_bytes", "lsdsort_topk16_device", "lsdsort_kth16_device",
+                    "lsdsort_check_device")
 
 
-def baseline_library(path):
-    """the entries of the baseline legs, bound in the library at `path` (None: this tree's)"""
-    if path is None:
-        return lsd.lib()
-    L = ctypes.CDLL(os.path.abspath(path))
-    L.lsdsort_topk16_workspace_bytes.restype, L.lsdsort_topk16_workspace_bytes.argtypes = c_size, [c_size, c_size, c_size]
-    L.lsdsort_kth16_workspace_bytes.restype, L.lsdsort_kth16_workspace_bytes.argtypes = c_size, [c_size, c_size]
-    L.lsdsort_topk16_device.restype, L.lsdsort_topk16_device.argtypes = c_int, SELECT
-    L.lsdsort_kth16_device.restype, L.lsdsort_kth16_device.argtypes = c_int, SELECT
-    L.lsdsort_check_device.restype, L.lsdsort_check_device.argtypes = c_int, [c_ptr, c_ptr]
-    return L
-
-
-def one(fn):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def measure(sides, x, g, a):
-    """side -> the medians of its repeats (one for a side that is no baseline).  `sides` keeps its order within an iteration."""
-    medians = {side: [] for side in sides}
-    for repeat in range(a.spread_repeats):
-        ts = {side: [] for side in sides}
-        for i in range(a.warmup + a.reps):
-            x.normal_(0.0, 1.0, generator=g)
-            for side, fn in sides.items():   # the sides alternate, call by call, on the same rows
-                if repeat > 0 and not side.startswith("baseline"):
-                    continue                  # the further repeats measure the baselines' spread
-                t = one(fn)
-                if i >= a.warmup:
-                    ts[side].append(t)
-        for side in sides:
-            if ts[side]:
-                medians[side].append(float(np.median(ts[side])))
-    return medians
-
-
-def verdict(side_ms, base_ms, spread):
-    return "ahead" if base_ms - side_ms > spread else ("behind" if side_ms - base_ms > spread else "within spread")
+def measured(sides, baselines, x, g, a):
+    return perfkit.measure(sides, baselines, a.spread_repeats, a.reps, a.warmup, fresh=lambda: x.normal_(0.0, 1.0, generator=g))
 
 
 def report(out, medians, pairs, n):
     for side, baseline in pairs:
         b = medians[baseline]
-        base_ms, spread = float(np.median(b)), max(b) - min(b)
+        base_ms, spread = perfkit.spread_of(b)
         out[baseline + "_ms"], out[baseline + "_repeats_ms"], out[baseline + "_spread_ms"] = base_ms, b, spread
         ms = medians[side][0]
         out[side + "_ms"] = ms
         out[side + "_speedup"] = base_ms / ms
-        out[side + "_verdict"] = verdict(ms, base_ms, spread)
-        out[side + "_bytes_per_key_at_5p5TBs"] = ms * 1e-3 * 5.5e12 / n
+        out[side + "_verdict"] = perfkit.verdict(ms, base_ms, spread)
+        out[side + "_bytes_per_key_at_5p5TBs"] = perfkit.bytes_per_key(ms, n)
     return out
 
 
@@ -149,7 +104,7 @@ def run_filter(name, mode, rows, cols, a, base):
             torch.where(x < thr.unsqueeze(1), neg_inf, x, out=out_b)
 
     sides = {"filter": filter_, "baseline": baseline, "filter_in_place": filter_in_place}   # in place last: it changes the rows
-    medians = measure(sides, x, g, a)
+    medians = measured(sides, {"baseline"}, x, g, a)
     assert L.lsdsort_check_device(ws.data_ptr(), None) == 0 and base.lsdsort_check_device(ws_b.data_ptr(), None) == 0
     # once more, untimed, on the same rows: every side answers the same question
     x.normal_(0.0, 1.0, generator=g)
@@ -200,7 +155,7 @@ def run_rank(name, rows, cols, a, base):
 
     sides = {"perrow": perrow("perrow", True), "baseline": single("baseline", True),
              "perrow_values_only": perrow("perrow_values_only", False), "baseline_values_only": single("baseline_values_only", False)}
-    medians = measure(sides, x, g, a)
+    medians = measured(sides, {"baseline", "baseline_values_only"}, x, g, a)
     for fn in sides.values():
         fn()
     torch.cuda.synchronize()
@@ -225,31 +180,23 @@ CASES = {
 MODES = ("perrow_k", "uniform_k", "perrow_rank")
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--spread-repeats", type=int, default=5)
-    ap.add_argument("--only", default=None)
+def parser():
+    ap = perfkit.parser(__doc__, spread_repeats=5, lib_flag="--baseline-lib")
     ap.add_argument("--modes", default=",".join(MODES))
-    ap.add_argument("--baseline-lib", default=None)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    return ap
+
+
+def main():
+    a = parser().parse_args()
     modes = a.modes.split(",")
     assert all(m in MODES for m in modes), modes
-    base = baseline_library(a.baseline_lib)
-    sink = open(a.out, "a") if a.out else None
-    for name, (rows, cols) in CASES.items():
-        if a.only and a.only != name:
-            continue
+    base = perfkit.bound_library(a.baseline_lib, BASELINE_ENTRIES)
+
+    def run(name, rows, cols):
         for mode in modes:
-            result = run_rank(name, rows, cols, a, base) if mode == "perrow_rank" else run_filter(name, mode, rows, cols, a, base)
-            line = json.dumps(result)
-            print(line, flush=True)
-            if sink:
-                sink.write(line + "\n")
-                sink.flush()
-            torch.cuda.empty_cache()
+            yield run_rank(name, rows, cols, a, base) if mode == "perrow_rank" else run_filter(name, mode, rows, cols, a, base)
+
+    perfkit.run_cases(a, CASES, run)
 
 
 if __name__ == "__main__":

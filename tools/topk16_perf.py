@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""16-bit top-k timings (GPU box): one JSON line per shape, the method of tools/topk_perf.py.  Device-event timing of the call
+"""16-bit top-k timings (GPU box): one JSON line per shape, the method of tools/perfkit.py.  Device-event timing of the call
 alone on fresh inputs each rep (warm-up first, median and min of the timed reps), next to the two things it is compared with,
 timed in the same process on the same bfloat16 rows, largest first, with indices:
   float32 path   what a caller did before the entry: x.float() followed by GPUTopK(..., "float32") -- the conversion IS in the time
@@ -7,32 +7,15 @@ timed in the same process on the same bfloat16 rows, largest first, with indices
 Shapes (all normal-distributed bfloat16 "logits"): [128 x 128256] k=50; [4096 x 131072] k=50; [1 x 2^28] k=1024;
 [2^14 x 2^14] k=32; [2^20 x 256] k=8.
 Usage: python tools/topk16_perf.py [--reps 20] [--warmup 3] [--only NAME] [--no-baselines]"""
-import argparse
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
-
-
-def timed(fn, fresh, reps, warmup):
-    """fresh() refills the inputs outside the timed region; fn() is timed by device events"""
-    ts = []
-    for i in range(warmup + reps):
-        fresh()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append(e0.elapsed_time(e1))
-    return float(np.median(ts)), float(np.min(ts))
+import perfkit
+from perfkit import timed
 
 
 def run_shape(name, rows, cols, k, reps, warmup, baselines=True):
@@ -47,7 +30,7 @@ def run_shape(name, rows, cols, k, reps, warmup, baselines=True):
     ms = timed(lambda: lsd.GPUTopK16(x, k, key_type="bfloat16", largest=True, workspace=ws), fresh, reps, warmup)
     assert lsd.lib().lsdsort_check_device(ws.data_ptr(), None) == 0
     out = {"shape": name, "rows": rows, "cols": cols, "k": k, "dtype": "bfloat16", "topk16_ms": ms[0], "topk16_min_ms": ms[1],
-           "topk16_bytes_per_key_at_5p5TBs": ms[0] * 1e-3 * 5.5e12 / n, "workspace_bytes": ws.numel()}
+           "topk16_bytes_per_key_at_5p5TBs": perfkit.bytes_per_key(ms[0], n), "workspace_bytes": ws.numel()}
     if not baselines:
         return out
     del ws
@@ -73,18 +56,15 @@ SHAPES = {
 }
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--only", default=None)
+def parser():
+    ap = perfkit.parser(__doc__, out=False)
     ap.add_argument("--no-baselines", action="store_true")
-    a = ap.parse_args()
-    for name, (rows, cols, k) in SHAPES.items():
-        if a.only and a.only != name:
-            continue
-        print(json.dumps(run_shape(name, rows, cols, k, a.reps, a.warmup, baselines=not a.no_baselines)), flush=True)
-        torch.cuda.empty_cache()
+    return ap
+
+
+def main():
+    a = parser().parse_args()
+    perfkit.run_cases(a, SHAPES, lambda name, *shape: run_shape(name, *shape, a.reps, a.warmup, baselines=not a.no_baselines))
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timings of the top-p filter for 16-bit rows (GPU box): one JSON line per shape, the method of tools/topk16_filter_perf.py.
+"""Timings of the top-p filter for 16-bit rows (GPU box): one JSON line per shape, the method of tools/perfkit.py.
 bfloat16 normal logits scaled by 4, 16-byte aligned, p_r drawn per row from {0.5, 0.8, 0.9, 0.95, 0.99}; device events around the
 call alone; the median of --reps calls on fresh rows after --warmup calls.  The sides ALTERNATE in one process, call by call, on the
 same rows:
@@ -19,71 +19,23 @@ T they keep some and drop others: for them the rule leaves the duplicates of T o
 Shapes: [128 x 128256], [4096 x 131072], [2^14 x 2^14], [2^20 x 256].
 Usage: python tools/topp16_filter_perf.py [--reps 20] [--warmup 3] [--spread-repeats 5] [--only NAME] [--baseline-lib PATH]
                                           [--check-rows 256] [--out profiles/topp16_filter_perf.jsonl]"""
-import argparse
-import ctypes
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
+import perfkit
 
 BF16 = 3
 NEG_INF_BITS = 0xFF80
 TOLERANCE = 2.0 ** -12
-c_size, c_int, c_ptr = ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p
-
-
-def baseline_library(path):
-    """the entries of the baseline leg, bound in the library at `path` (None: this tree's)"""
-    if path is None:
-        return lsd.lib()
-    L = ctypes.CDLL(os.path.abspath(path))
-    L.lsdsort_rows16_workspace_bytes.restype, L.lsdsort_rows16_workspace_bytes.argtypes = c_size, [c_size, c_size]
-    L.lsdsort_rows16_device.restype = c_int
-    L.lsdsort_rows16_device.argtypes = [c_ptr, c_size, c_size, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]
-    L.lsdsort_check_device.restype, L.lsdsort_check_device.argtypes = c_int, [c_ptr, c_ptr]
-    return L
-
-
-def one(fn):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
+BASELINE_ENTRIES = ("lsdsort_rows16_workspace_bytes", "lsdsort_rows16_device", "lsdsort_check_device")
 
 
 def fresh(x, g):
     x.normal_(0.0, 4.0, generator=g)
-
-
-def measure(sides, x, g, a):
-    """side -> the medians of its repeats (one for a side that is no baseline).  `sides` keeps its order within an iteration."""
-    medians = {side: [] for side in sides}
-    for repeat in range(a.spread_repeats):
-        ts = {side: [] for side in sides}
-        for i in range(a.warmup + a.reps):
-            fresh(x, g)
-            for side, fn in sides.items():   # the sides alternate, call by call, on the same rows
-                if repeat > 0 and side != "baseline":
-                    continue                  # the further repeats measure the baseline's spread
-                t = one(fn)
-                if i >= a.warmup:
-                    ts[side].append(t)
-        for side in sides:
-            if ts[side]:
-                medians[side].append(float(np.median(ts[side])))
-    return medians
-
-
-def verdict(side_ms, base_ms, spread):
-    return "ahead" if base_ms - side_ms > spread else ("behind" if side_ms - base_ms > spread else "within spread")
 
 
 def sortable(t):
@@ -159,7 +111,7 @@ def run(name, rows, cols, a, base):
         mask_and_scatter(keys, index, out_t)
 
     sides = {"filter": filter_, "baseline": baseline, "torch": torch_, "filter_in_place": filter_in_place}   # in place last
-    medians = measure(sides, x, g, a)
+    medians = perfkit.measure(sides, {"baseline"}, a.spread_repeats, a.reps, a.warmup, fresh=lambda: fresh(x, g))
     assert L.lsdsort_check_device(ws.data_ptr(), None) == 0 and base.lsdsort_check_device(ws_b.data_ptr(), None) == 0
     # once more, untimed, on the same rows: every side answers the same question, under the acceptance rule
     fresh(x, g)
@@ -175,7 +127,7 @@ def run(name, rows, cols, a, base):
     assert agreed["filter"], "the filter's output is not accepted"
     same = float((out_f.view(torch.int16) == out_b.view(torch.int16)).all(dim=1).float().mean())
     b = medians["baseline"]
-    base_ms, spread = float(np.median(b)), max(b) - min(b)
+    base_ms, spread = perfkit.spread_of(b)
     out = {"case": name, "rows": rows, "cols": cols, "dtype": "bfloat16", "sigma": 4.0, "p": choice.tolist(), "reps": a.reps, "warmup": a.warmup,
            "baseline": "lsdsort_rows16_device descending with positions + float32 softmax, cumsum, mask, scatter",
            "baseline_library": "parent commit's" if a.baseline_lib else "this tree's", "workspace_bytes": ws.numel(),
@@ -186,8 +138,8 @@ def run(name, rows, cols, a, base):
         ms = medians[side][0]
         out[side + "_ms"] = ms
         out[side + "_speedup"] = base_ms / ms
-        out[side + "_verdict"] = verdict(ms, base_ms, spread)
-        out[side + "_bytes_per_key_at_5p5TBs"] = ms * 1e-3 * 5.5e12 / n
+        out[side + "_verdict"] = perfkit.verdict(ms, base_ms, spread)
+        out[side + "_bytes_per_key_at_5p5TBs"] = perfkit.bytes_per_key(ms, n)
     return out
 
 
@@ -199,28 +151,16 @@ CASES = {
 }
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--spread-repeats", type=int, default=5)
-    ap.add_argument("--only", default=None)
-    ap.add_argument("--baseline-lib", default=None)
+def parser():
+    ap = perfkit.parser(__doc__, spread_repeats=5, lib_flag="--baseline-lib")
     ap.add_argument("--check-rows", type=int, default=256)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    base = baseline_library(a.baseline_lib)
-    sink = open(a.out, "a") if a.out else None
-    for name, (rows, cols) in CASES.items():
-        if a.only and a.only != name:
-            continue
-        result = run(name, rows, cols, a, base)
-        line = json.dumps(result)
-        print(line, flush=True)
-        if sink:
-            sink.write(line + "\n")
-            sink.flush()
-        torch.cuda.empty_cache()
+    return ap
+
+
+def main():
+    a = parser().parse_args()
+    base = perfkit.bound_library(a.baseline_lib, BASELINE_ENTRIES)
+    perfkit.run_cases(a, CASES, lambda name, rows, cols: run(name, rows, cols, a, base))
 
 
 if __name__ == "__main__":

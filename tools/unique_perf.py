@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timings of unique and run-length encode (GPU box): one JSON line per case and variant, the method of tools/logprob16_perf.py.
+"""Timings of unique and run-length encode (GPU box): one JSON line per case and variant, the method of tools/perfkit.py.
 Device events around the call alone, on the same keys for every side; the sides ALTERNATE in one process, call by call, in --rounds
 rounds (six) of --warmup + --reps calls each.  A side's time is the median of its round medians, its spread the largest minus the
 smallest of them.
@@ -22,47 +22,16 @@ Byte accounting of the run-length phases as timed here (counts, no starts), per 
 n: two reads of the keys (2 w) and per run the word and the count, (w + 4) d / n.
 Usage: python tools/unique_perf.py [--rounds 6] [--reps 5] [--warmup 2] [--only NAME] [--variant counts|inverse]
                                    [--out profiles/unique_perf.jsonl]"""
-import argparse
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
 import lsdradixsort_amd as lsd
+import perfkit
 
 KEY_CODE = {"uint32": 0, "int64": 4}
-
-
-def one(fn):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def measure(sides, a):
-    """side -> its round medians; the sides alternate call by call within every round"""
-    rounds = {side: [] for side in sides}
-    for _ in range(a.rounds):
-        ts = {side: [] for side in sides}
-        for i in range(a.warmup + a.reps):
-            for side, fn in sides.items():
-                t = one(fn)
-                if i >= a.warmup:
-                    ts[side].append(t)
-        for side in sides:
-            rounds[side].append(float(np.median(ts[side])))
-    return rounds
-
-
-def verdict(side_ms, base_ms, spread):
-    return "ahead" if base_ms - side_ms > spread else ("behind" if side_ms - base_ms > spread else "within spread")
 
 
 def make_keys(n, key_type, kind):
@@ -135,7 +104,7 @@ def run(name, n, key_type, kind, variant, a):
 
     sides = {"unique": unique, "torch_unique": torch_unique, "sort_rle": sort_rle, "sort": sort, "rle": rle, "torch_rle": torch_rle,
              "copy": lambda: copy.copy_(x)}
-    rounds = measure(sides, a)
+    rounds = perfkit.measure(sides, None, a.rounds, a.reps, a.warmup)   # every side in every round
     # once more, untimed: the entry against torch.unique
     unique()
     torch.cuda.synchronize()
@@ -149,13 +118,14 @@ def run(name, n, key_type, kind, variant, a):
     res = {"case": name, "variant": variant, "n": n, "key_type": key_type, "kind": kind, "distinct": m, "rounds": a.rounds, "reps": a.reps,
            "warmup": a.warmup, "workspace_bytes": ws.numel(), "agrees_with_torch": bool(agreed)}
     for side, r in rounds.items():
-        res[side + "_ms"], res[side + "_rounds_ms"], res[side + "_spread_ms"] = float(np.median(r)), r, max(r) - min(r)
+        ms, spread = perfkit.spread_of(r)
+        res[side + "_ms"], res[side + "_rounds_ms"], res[side + "_spread_ms"] = ms, r, spread
     faster = min(("torch_unique", "sort_rle"), key=lambda side: res[side + "_ms"])
     res["faster_baseline"] = faster
     res["speedup"] = res[faster + "_ms"] / res["unique_ms"]
     res["speedup_torch_unique"] = res["torch_unique_ms"] / res["unique_ms"]
     res["speedup_sort_rle"] = res["sort_rle_ms"] / res["unique_ms"]
-    res["verdict"] = verdict(res["unique_ms"], res[faster + "_ms"], res[faster + "_spread_ms"])
+    res["verdict"] = perfkit.verdict(res["unique_ms"], res[faster + "_ms"], res[faster + "_spread_ms"])
     res["gated"] = key_type == "uint32" and variant == "counts"
     res["sort_share"] = res["sort_ms"] / res["unique_ms"]
     res["rle_speedup_torch"] = res["torch_rle_ms"] / res["rle_ms"]
@@ -174,28 +144,17 @@ def cases():
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=6)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--only", default=None)
+def parser():
+    ap = perfkit.parser(__doc__, reps=5, warmup=2, rounds=6, only_help="run the cases whose name contains this")
     ap.add_argument("--variant", default=None, choices=("counts", "inverse"))
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    sink = open(a.out, "a") if a.out else None
-    for name, (n, key_type, kind) in cases().items():
-        if a.only and a.only not in name:
-            continue
-        for variant in ("counts", "inverse"):
-            if a.variant and a.variant != variant:
-                continue
-            line = json.dumps(run(name, n, key_type, kind, variant, a))
-            print(line, flush=True)
-            if sink:
-                sink.write(line + "\n")
-                sink.flush()
-            torch.cuda.empty_cache()
+    return ap
+
+
+def main():
+    a = parser().parse_args()
+    perfkit.run_cases(a, cases(), lambda name, n, key_type, kind: (run(name, n, key_type, kind, variant, a)
+                                                                   for variant in ("counts", "inverse") if not a.variant or a.variant == variant),
+                      match="substring")
 
 
 if __name__ == "__main__":
