@@ -1,5 +1,6 @@
 """hipcc's own resource remarks for one translation unit of lsdradixsort_amd/csrc, compiled for gfx950 (device code only):
-what tests/test_kernel_resources.py and tests/test_segmented_cpu.py assert on."""
+what tests/test_kernel_resources.py and tests/test_segmented_cpu.py assert on; and the text of csrc/ for the header-discipline suites
+(test_mass_rows_cpu.py, test_run_tiles_cpu.py, test_tile_headers_cpu.py): sources, code, defined_in, includes."""
 import functools
 import os
 import re
@@ -11,6 +12,26 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lsdradixsort_amd", "csrc")
 FIELDS = {"scratch": "ScratchSize [bytes/lane]", "vgpr_spill": "VGPRs Spill", "occupancy": "Occupancy [waves/SIMD]",
           "lds_bytes": "LDS Size [bytes/block]"}
+
+
+def sources():
+    """{file name: text} of every .hip and .hpp under csrc/"""
+    return {name: open(os.path.join(CSRC, name)).read() for name in sorted(os.listdir(CSRC)) if name.endswith((".hip", ".hpp"))}
+
+
+def code(text):
+    """the text without its // comments"""
+    return re.sub(r"//.*", "", text)
+
+
+def defined_in(pattern):
+    """{file: number of definitions} over csrc/, comments aside"""
+    found = {name: len(re.findall(pattern, code(text), flags=re.M)) for name, text in sources().items()}
+    return {name: n for name, n in found.items() if n}
+
+
+def includes(text):
+    return set(re.findall(r'#include "([^"]+)"', text))
 
 
 def hipcc():

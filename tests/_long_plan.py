@@ -24,6 +24,7 @@ import numpy as np
 
 import _rowk16 as rk
 import _topp16 as tp
+from _key_oracle import SPECIALS32
 
 MIN_CHUNK, MAX_CHUNKS, LONG_TILE, LOCAL_SORT_CAP = 16384, 2048, 4096, 16384
 
@@ -66,8 +67,6 @@ SKIP = {2: 6, 4: 12}           # the first row lies 3 elements into its buffer: 
 FAMILIES = ("uniform bits", "four values", "all equal")
 FOUR = {2: np.array([5, 0x0100, 0x7FFF, 0xFFF0], dtype=np.uint16), 4: np.array([5, 0x00010000, 0x7FFFFFFF, 0xFFFFFFF0], dtype=np.uint32)}
 EQUAL = {2: 0x9E37, 4: 0x9E3779B9}
-SPECIALS32 = np.array([0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x00000001, 0x80000001, 0x007FFFFF, 0x807FFFFF,
-                       0x7FC00000, 0xFFC00000, 0x7F800001, 0xFFFFFFFF, 0x7FFFFFFF, 0x3F800000, 0xBF800000], dtype=np.uint32)
 TOPK = {"FIVE_TILES": 4099, "WHOLE_ROW": 70, "AT_CAP": 4099}   # topk16's k: the winners of a uniform row come from every chunk
 
 

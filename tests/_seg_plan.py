@@ -13,6 +13,8 @@ first round.
 import numpy as np
 import torch
 
+from _key_oracle import SPECIALS32 as SPECIALS
+
 SEG_TILE = 4096        # kSegTile: keys per large-tier tile
 SCAN_BLOCK = 4096      # kScanBlock: entries per block of the flat scan
 WAVE_CAP = 1024        # kWaveSegCap
@@ -136,9 +138,6 @@ def plan_of(name):
 
 
 # ---- inputs ---------------------------------------------------------------------------------------------------------------------
-# +-0, +-inf, denormals, NaNs of either sign, +-1: the list of test_gpu_segmented.test_typed_keys_with_specials
-SPECIALS = (0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x00000001, 0x80000001, 0x007FFFFF, 0x807FFFFF, 0x7FC00000, 0xFFC00000,
-            0x7F800001, 0xFFFFFFFF, 0x7FFFFFFF, 0x3F800000, 0xBF800000)
 KINDS = ("uniform", "half zeros", "one live byte", "four values", "all equal", "float specials")
 
 
@@ -157,7 +156,7 @@ def make_keys(off, n, key_type, seed, device="cuda", shift=0):
     """n int32 words (the keys' bits) made on `device`: the keys of segment s = [off[s], off[s + 1]) are of kind
     segment_kinds()[s] -- uniform bits | half zeros (a heavy value) | one live byte, the other three constant (every key of a tile
     in one digit in three of the four passes) | four values (tie runs, where stability shows) | all equal | float32 only: normal
-    variates with SPECIALS mixed in.  Keys in front of off[0] and behind off[-1] are uniform."""
+    variates with _key_oracle's SPECIALS32 mixed in.  Keys in front of off[0] and behind off[-1] are uniform."""
     g = torch.Generator(device=device).manual_seed(seed)
     segs = len(off) - 1
     sizes = torch.from_numpy(np.diff(off)).to(device)
@@ -174,7 +173,7 @@ def make_keys(off, n, key_type, seed, device="cuda", shift=0):
     keys = torch.where(kind == 4, torch.full_like(keys, 0x9E3779B9), keys)
     if key_type == "float32":
         f = torch.randn(n, generator=g, device=device).view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-        special = torch.tensor(SPECIALS, dtype=torch.int64, device=device)[(uniform >> 9) % len(SPECIALS)]
+        special = torch.tensor(SPECIALS.tolist(), dtype=torch.int64, device=device)[(uniform >> 9) % len(SPECIALS)]
         f = torch.where(torch.rand(n, generator=g, device=device) < 0.3, special, f)
         keys = torch.where(kind == 5, f, keys)
     return _wrap32(keys)

@@ -9,10 +9,10 @@ import pytest
 
 from _guarded import assert_intact, guarded, guarded_workspace
 from _guarded16 import assert_intact16, bits_of, guarded16
+from _key_oracle import ALL_TYPES16 as KEY_TYPES
 
 pytestmark = pytest.mark.gpu
 
-KEY_TYPES = ("uint16", "int16", "float16", "bfloat16")
 SIZES = [1, 7, 8, 9, 63, 64, 65, 1023, 16384, 16385, 65535, 65536, 65537, (1 << 20) + 13, (1 << 22) + 5]
 WIDEN, COUNT = 0, 1
 

@@ -12,63 +12,15 @@ import pytest
 import torch
 
 import lsdradixsort_amd as lsd
+from _device_arrays import bits, to_dev
 from _guarded import assert_intact, assert_unchanged, guarded, guarded_workspace, without_sentinel
+from _key_oracle import KEY_TYPES32 as KEY_TYPES, expected_np, inputs32 as inputs
 
 pytestmark = pytest.mark.gpu
-
-KEY_TYPES = {"uint32": 0, "int32": 1, "float32": 2}
-SPECIALS = np.array([0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x00000001, 0x80000001, 0x007FFFFF, 0x807FFFFF,
-                     0x7FC00000, 0xFFC00000, 0x7F800001, 0xFFFFFFFF, 0x7FFFFFFF, 0x3F800000, 0xBF800000], dtype=np.uint32)
-
-
-def sortable_np(u, key_type, descending):
-    u = u.astype(np.uint32)
-    if key_type == "int32":
-        u = u ^ np.uint32(0x80000000)
-    elif key_type == "float32":
-        u = u ^ ((u >> np.uint32(31)) * np.uint32(0x7FFFFFFF) | np.uint32(0x80000000))
-    return ~u if descending else u
-
-
-def expected_np(keys, key_type, largest):
-    """keys: [rows, cols] uint32 bits -> the full stable order of every row: (sorted keys, positions)"""
-    order = np.argsort(sortable_np(keys, key_type, largest), axis=1, kind="stable")
-    return np.take_along_axis(keys, order, axis=1), order.astype(np.uint32)
 
 
 def ranks_of(cols):
     return sorted({r for r in (0, 1, cols // 2, cols - 2, cols - 1) if 0 <= r < cols})
-
-
-def inputs(rows, cols, key_type, seed):
-    """name -> [rows, cols] uint32"""
-    rng = np.random.default_rng(seed)
-    out = {"uniform bits": rng.integers(0, 1 << 32, (rows, cols), dtype=np.uint64).astype(np.uint32)}
-    four = np.array([5, 0x00010000, 0x7FFFFFFF, 0xFFFFFFF0], dtype=np.uint32)
-    out["four values"] = four[rng.integers(0, 4, (rows, cols))]                    # tie runs across lanes, waves and chunks
-    out["all equal"] = np.full((rows, cols), 0x9E3779B9, dtype=np.uint32)          # the position must equal the rank
-    out["shared top 24 bits"] = np.uint32(0xABCDEF00) | rng.integers(0, 256, (rows, cols)).astype(np.uint32)   # every level runs
-    out["bit 0 only"] = np.uint32(0x40302010) | rng.integers(0, 2, (rows, cols)).astype(np.uint32)
-    if key_type == "float32":
-        f = rng.standard_normal(rows * cols).astype(np.float32).view(np.uint32).copy()
-        pick = rng.random(rows * cols) < 0.3
-        f[pick] = SPECIALS[rng.integers(0, SPECIALS.size, int(pick.sum()))]        # +-0, +-inf, NaNs of both signs, denormals
-        out["float specials"] = f.reshape(rows, cols)
-    return out
-
-
-def to_dev(keys, key_type, offset=0):
-    """the keys on the device as a contiguous [rows, cols] view `offset` elements into a 512-byte aligned buffer"""
-    rows, cols = keys.shape
-    flat = torch.empty(rows * cols + offset, dtype=torch.int32, device="cuda")
-    view = flat[offset:].view(rows, cols)
-    view.copy_(torch.from_numpy(np.ascontiguousarray(keys).view(np.int32)))
-    assert view.is_contiguous() and view.data_ptr() % 16 == (4 * offset) % 16
-    return view.view(torch.float32) if key_type == "float32" else view
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32).cpu().numpy().view(np.uint32)
 
 
 def check_ranks(dk, keys, key_type, what, ranks=None):

@@ -13,84 +13,16 @@ import pytest
 import torch
 
 import lsdradixsort_amd as lsd
+from _device_arrays import DTYPES, bits, to_dev
 from _guarded import assert_intact, guarded, guarded_workspace
 from _guarded16 import assert_intact16, bits_of, guarded16
+from _key_oracle import ALL_TYPES16 as ALL_TYPES, KEY_TYPES16 as KEY_TYPES, expected_np, inputs16 as inputs
 
 pytestmark = pytest.mark.gpu
-
-KEY_TYPES = {"uint16": 0, "int16": 1, "float16": 2, "bfloat16": 3}
-DTYPES = {"uint16": torch.int16, "int16": torch.int16, "float16": torch.float16, "bfloat16": torch.bfloat16}
-ALL_TYPES = list(KEY_TYPES)
-# +-0, +-inf, NaNs of both signs (quiet, signalling, all ones), denormals, the largest finite values
-SPECIALS = {
-    "float16": np.array([0x0000, 0x8000, 0x7C00, 0xFC00, 0x7E00, 0xFE00, 0x7C01, 0xFC01, 0xFFFF, 0x7FFF, 0x0001, 0x8001, 0x03FF,
-                         0x83FF, 0x7BFF, 0xFBFF], dtype=np.uint16),
-    "bfloat16": np.array([0x0000, 0x8000, 0x7F80, 0xFF80, 0x7FC0, 0xFFC0, 0x7F81, 0xFF81, 0xFFFF, 0x7FFF, 0x0001, 0x8001, 0x007F,
-                          0x807F, 0x7F7F, 0xFF7F], dtype=np.uint16),
-}
-
-
-def sortable16_np(u, key_type, largest):
-    """the map of include/lsdsort.h restated: the uint16 whose unsigned order is the requested one"""
-    u = u.astype(np.uint32)
-    if key_type == "int16":
-        u = u ^ np.uint32(0x8000)
-    elif key_type in ("float16", "bfloat16"):
-        u = u ^ np.where(u & np.uint32(0x8000), np.uint32(0xFFFF), np.uint32(0x8000))
-    return ((u ^ np.uint32(0xFFFF)) if largest else u).astype(np.uint16)
-
-
-def expected_np(keys, key_type, largest):
-    """keys: [rows, cols] uint16 bits -> the full stable order of every row: (sorted keys, positions)"""
-    order = np.argsort(sortable16_np(keys, key_type, largest), axis=1, kind="stable")
-    return np.take_along_axis(keys, order, axis=1), order.astype(np.uint32)
 
 
 def ranks_of(cols):
     return sorted({r for r in (0, 1, cols // 2, cols - 2, cols - 1) if 0 <= r < cols})
-
-
-def inputs(rows, cols, key_type, seed):
-    """name -> [rows, cols] uint16 bit patterns"""
-    rng = np.random.default_rng(seed)
-
-    def rnd(hi):
-        return rng.integers(0, hi, (rows, cols), dtype=np.uint32).astype(np.uint16)
-
-    out = {"uniform bits": rnd(1 << 16)}
-    four = np.array([5, 0x0100, 0x7FFF, 0xFFF0], dtype=np.uint16)
-    out["four values"] = four[rng.integers(0, 4, (rows, cols))]                  # tie runs across lanes, waves and chunks
-    out["all equal"] = np.full((rows, cols), 0x9E37, dtype=np.uint16)            # the position must equal the rank
-    out["shared top 11 bits"] = np.uint16(0xABC0) | rnd(32)                      # the second level decides; long rows are all ties
-    out["shared top 8 bits"] = np.uint16(0xAB00) | rnd(256)
-    lone = np.full((rows, cols), 0x4000, dtype=np.uint16)                        # one 0x0001 among 0x4000s: the select stops after
-    lone[np.arange(rows), rng.integers(0, cols, rows)] = 0x0001                  # the first level or round, with a nonzero shift
-    out["lone minimum"] = lone
-    if key_type in SPECIALS:
-        f = rnd(1 << 16).reshape(-1)
-        pick = rng.random(rows * cols) < 0.3
-        f[pick] = SPECIALS[key_type][rng.integers(0, SPECIALS[key_type].size, int(pick.sum()))]
-        out["float specials"] = f.reshape(rows, cols)
-    return out
-
-
-def to_dev(keys, key_type, offset=0):
-    """the keys on the device as a contiguous [rows, cols] view `offset` elements into a 512-byte aligned buffer"""
-    rows, cols = keys.shape
-    flat = torch.empty(rows * cols + offset, dtype=torch.int16, device="cuda")
-    assert flat.data_ptr() % 512 == 0
-    view = flat[offset:].view(rows, cols)
-    view.copy_(torch.from_numpy(np.ascontiguousarray(keys).view(np.int16)))
-    assert view.is_contiguous() and view.data_ptr() % 16 == (2 * offset) % 16
-    return view.view(DTYPES[key_type])
-
-
-def bits(t):
-    """uint16 bit patterns of a 16-bit tensor, uint32 of an int32 one"""
-    t = t.contiguous()
-    if t.dtype == torch.int32:
-        return t.cpu().numpy().view(np.uint32)
-    return t.view(torch.int16).cpu().numpy().view(np.uint16)
 
 
 def check_ranks(dk, keys, key_type, what, ranks=None):

@@ -19,47 +19,14 @@ import torch
 
 import _row_rounds as rr
 import lsdradixsort_amd as lsd
+from _device_arrays import DTYPES, bits, to_dev
 from _guarded import assert_intact, guarded, guarded_workspace
 from _guarded16 import assert_intact16, bits_of, guarded16
+from _key_oracle import (
+    ALL_TYPES16 as ALL_TYPES, KEY_TYPES16 as KEY_TYPES, MULTI_RANK16, SPECIALS16 as SPECIALS, expected_np, inputs16 as inputs,
+)
 
 pytestmark = pytest.mark.gpu
-
-KEY_TYPES = {"uint16": 0, "int16": 1, "float16": 2, "bfloat16": 3}
-DTYPES = {"uint16": torch.int16, "int16": torch.int16, "float16": torch.float16, "bfloat16": torch.bfloat16}
-ALL_TYPES = list(KEY_TYPES)
-# +-0, +-inf, NaNs of both signs (quiet, signalling, all ones), denormals, the largest finite values
-SPECIALS = {
-    "float16": np.array([0x0000, 0x8000, 0x7C00, 0xFC00, 0x7E00, 0xFE00, 0x7C01, 0xFC01, 0xFFFF, 0x7FFF, 0x0001, 0x8001, 0x03FF,
-                         0x83FF, 0x7BFF, 0xFBFF], dtype=np.uint16),
-    "bfloat16": np.array([0x0000, 0x8000, 0x7F80, 0xFF80, 0x7FC0, 0xFFC0, 0x7F81, 0xFF81, 0xFFFF, 0x7FFF, 0x0001, 0x8001, 0x007F,
-                          0x807F, 0x7F7F, 0xFF7F], dtype=np.uint16),
-}
-
-
-def sortable16_np(u, key_type, largest):
-    """the map of include/lsdsort.h restated: the uint16 whose unsigned order is the requested one"""
-    u = u.astype(np.uint32)
-    if key_type == "int16":
-        u = u ^ np.uint32(0x8000)
-    elif key_type in ("float16", "bfloat16"):
-        u = u ^ np.where(u & np.uint32(0x8000), np.uint32(0xFFFF), np.uint32(0x8000))
-    return ((u ^ np.uint32(0xFFFF)) if largest else u).astype(np.uint16)
-
-
-def from_sortable16_np(s, key_type):
-    """the key whose ascending sortable value is s"""
-    s = s.astype(np.uint32)
-    if key_type == "int16":
-        s = s ^ np.uint32(0x8000)
-    elif key_type in ("float16", "bfloat16"):
-        s = np.where(s & np.uint32(0x8000), s ^ np.uint32(0x8000), s ^ np.uint32(0xFFFF))
-    return s.astype(np.uint16)
-
-
-def expected_np(keys, key_type, largest):
-    """keys: [rows, cols] uint16 bits -> the full stable order of every row: (sorted keys, positions)"""
-    order = np.argsort(sortable16_np(keys, key_type, largest), axis=1, kind="stable")
-    return np.take_along_axis(keys, order, axis=1), order.astype(np.uint32)
 
 
 def rank_sets(cols):
@@ -67,58 +34,6 @@ def rank_sets(cols):
     sets = [[cols // 2], [(cols - 1) // 2, cols // 2], [cols // 4, cols // 2, 3 * cols // 4],
             [cols - 1, 0, cols // 2, cols // 2, 1, cols // 4, 3 * cols // 4, cols - 2]]
     return [[min(max(r, 0), cols - 1) for r in ranks] for ranks in sets]
-
-
-def inputs(rows, cols, key_type, seed):
-    """name -> [rows, cols] uint16 bit patterns"""
-    rng = np.random.default_rng(seed)
-
-    def rnd(hi):
-        return rng.integers(0, hi, (rows, cols), dtype=np.uint32).astype(np.uint16)
-
-    out = {"uniform bits": rnd(1 << 16)}                                         # 70001 columns: every slot its own leader at level 1
-    four = np.array([5, 0x0100, 0x7FFF, 0xFFF0], dtype=np.uint16)
-    out["four values"] = four[rng.integers(0, 4, (rows, cols))]                  # tie runs: slots share a final prefix, needs differ
-    out["all equal"] = np.full((rows, cols), 0x9E37, dtype=np.uint16)            # every slot's position must equal its rank
-    shared = np.uint16(0xABC0) | rnd(32)
-    out["shared top 11 bits"] = shared                                           # one leader for all slots at level 1
-    lone = np.full((rows, cols), 0x4000, dtype=np.uint16)                        # one 0x0001 among 0x4000s: rank 0 stops after the
-    lone[np.arange(rows), rng.integers(0, cols, rows)] = 0x0001                  # first level or round, with a nonzero shift
-    out["lone minimum"] = lone
-    if key_type in SPECIALS:
-        f = rnd(1 << 16).reshape(-1)
-        pick = rng.random(rows * cols) < 0.3
-        f[pick] = SPECIALS[key_type][rng.integers(0, SPECIALS[key_type].size, int(pick.sum()))]
-        out["float specials"] = f.reshape(rows, cols)
-    if cols >= 8:
-        # In sortable order: three keys of unique top 11 bits at each end of a row that otherwise shares its top 11 bits.  Ranks 0, 1
-        # and cols - 1 finish at level 0 while the middle slots run level 1: done and live slots side by side.
-        s = shared.copy()
-        ends = np.array([0x0020, 0x0040, 0x0060, 0xFFA0, 0xFFC0, 0xFFE0], dtype=np.uint16)
-        for r in range(rows):
-            where = rng.choice(cols, ends.size, replace=False)
-            s[r, where] = ends | rng.integers(0, 32, ends.size).astype(np.uint16)
-        out["outliers"] = from_sortable16_np(s, key_type)
-    return out
-
-
-def to_dev(keys, key_type, offset=0):
-    """the keys on the device as a contiguous [rows, cols] view `offset` elements into a 512-byte aligned buffer"""
-    rows, cols = keys.shape
-    flat = torch.empty(rows * cols + offset, dtype=torch.int16, device="cuda")
-    assert flat.data_ptr() % 512 == 0
-    view = flat[offset:].view(rows, cols)
-    view.copy_(torch.from_numpy(np.ascontiguousarray(keys).view(np.int16)))
-    assert view.is_contiguous() and view.data_ptr() % 16 == (2 * offset) % 16
-    return view.view(DTYPES[key_type])
-
-
-def bits(t):
-    """uint16 bit patterns of a 16-bit tensor, uint32 of an int32 one"""
-    t = t.contiguous()
-    if t.dtype == torch.int32:
-        return t.cpu().numpy().view(np.uint32)
-    return t.view(torch.int16).cpu().numpy().view(np.uint16)
 
 
 def check_sets(dk, keys, key_type, what, sets=None, orders=(False, True)):
@@ -146,7 +61,7 @@ def check_sets(dk, keys, key_type, what, sets=None, orders=(False, True)):
 
 
 def check_shape(rows, cols, key_type):
-    for name, keys in inputs(rows, cols, key_type, seed=1000 * rows + cols).items():
+    for name, keys in inputs(rows, cols, key_type, seed=1000 * rows + cols, families=MULTI_RANK16).items():
         check_sets(to_dev(keys, key_type), keys, key_type, name)
 
 
@@ -187,7 +102,7 @@ def test_values_only_one_rank_and_one_row_input(shape, key_type):
     """without an index buffer: the same values (the long shapes take the launch sequence without a locate, where every slot runs
     both levels: `lone minimum` and `outliers` hold slots that would have stopped after the first); one rank is GPUKth16; 1-D input"""
     rows, cols = shape
-    kinds = inputs(rows, cols, key_type, seed=cols)
+    kinds = inputs(rows, cols, key_type, seed=cols, families=MULTI_RANK16)
     for name in ("four values", "shared top 11 bits", "lone minimum", "uniform bits", "outliers"):
         keys = kinds[name]
         dk = to_dev(keys, key_type, 3)
@@ -221,7 +136,7 @@ def test_values_only_one_rank_and_one_row_input(shape, key_type):
 @pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_views_off_the_16_byte_line(shape, offset):
     rows, cols = shape
-    for name, keys in inputs(rows, cols, "bfloat16", seed=offset + cols).items():
+    for name, keys in inputs(rows, cols, "bfloat16", seed=offset + cols, families=MULTI_RANK16).items():
         if name in ("uniform bits", "four values", "outliers"):
             check_sets(to_dev(keys, "bfloat16", offset), keys, "bfloat16", f"{name} offset {offset}", sets=rank_sets(cols)[2:])
 
@@ -248,7 +163,7 @@ def raw_call(keys, ranks, key_type, largest, with_idx, skip_bytes, short_by=0):
 @pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_guard_bands_exact_workspace_and_null_indices(shape, skip_bytes):
     rows, cols = shape
-    keys = inputs(rows, cols, "float16", seed=cols + skip_bytes)["float specials"]
+    keys = inputs(rows, cols, "float16", seed=cols + skip_bytes, families=MULTI_RANK16)["float specials"]
     ranks = [3 * cols // 4, cols // 4, cols // 2]
     ek, ei = expected_np(keys, "float16", True)
     st, *_ = raw_call(keys, ranks, "float16", True, True, skip_bytes, short_by=1)
@@ -271,7 +186,7 @@ def test_guard_bands_exact_workspace_and_null_indices(shape, skip_bytes):
 @pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_same_result_without_the_returning_add_rank_form(shape):
     rows, cols = shape
-    keys = inputs(rows, cols, "int16", seed=cols + 1)["outliers"]
+    keys = inputs(rows, cols, "int16", seed=cols + 1, families=MULTI_RANK16)["outliers"]
     dk = to_dev(keys, "int16")
     lsd.set_rank_method(0)
     try:
@@ -289,7 +204,7 @@ def test_same_result_without_the_returning_add_rank_form(shape):
 @pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_two_calls_on_one_workspace_agree(shape):
     rows, cols = shape
-    keys = inputs(rows, cols, "uint16", seed=cols + 2)["four values"]
+    keys = inputs(rows, cols, "uint16", seed=cols + 2, families=MULTI_RANK16)["four values"]
     dk = to_dev(keys, "uint16")
     ranks = rank_sets(cols)[3]
     ws = torch.empty(lsd.kth16_multi_workspace_bytes(rows, cols, len(ranks)), dtype=torch.uint8, device="cuda")
@@ -324,7 +239,7 @@ def test_graph_replay_on_changed_input(shape, with_idx):
                                           int(torch.cuda.current_stream().cuda_stream))
         assert st == 0, st
 
-    kinds = inputs(rows, cols, "int16", seed=cols + 3)
+    kinds = inputs(rows, cols, "int16", seed=cols + 3, families=MULTI_RANK16)
     dk.copy_(torch.from_numpy(kinds["uniform bits"].view(np.int16)))
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())

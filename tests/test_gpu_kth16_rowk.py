@@ -16,45 +16,19 @@ import torch
 
 import lsdradixsort_amd as lsd
 import _rowk16 as rk
+from _device_arrays import DTYPES, bits, captured, fault_word, stream_ptr, to_dev
 from _guarded import assert_intact, guarded, guarded_workspace
 from _guarded16 import assert_intact16, bits_of, guarded16
+from _key_oracle import KEY_TYPES16 as KEY_TYPES
 
 pytestmark = pytest.mark.gpu
 
-KEY_TYPES = rk.KEY_TYPES
-DTYPES = {"uint16": torch.int16, "int16": torch.int16, "float16": torch.float16, "bfloat16": torch.bfloat16}
 FAULT_RANK = 4096
-
-
-def to_dev(keys, key_type, offset=0):
-    """the keys on the device as a contiguous [rows, cols] view `offset` elements into a 512-byte aligned buffer"""
-    rows, cols = keys.shape
-    flat = torch.empty(rows * cols + offset, dtype=torch.int16, device="cuda")
-    assert flat.data_ptr() % 512 == 0
-    view = flat[offset:].view(rows, cols)
-    view.copy_(torch.from_numpy(np.ascontiguousarray(keys).view(np.int16)))
-    return view.view(DTYPES[key_type])
 
 
 def dev_u32(values):
     """[n] uint32 -> the int32 CUDA tensor with the same bits"""
     return torch.from_numpy(np.ascontiguousarray(values, dtype=np.uint32).view(np.int32).copy()).cuda()
-
-
-def bits(t):
-    """uint16 bit patterns of a 16-bit tensor, uint32 of an int32 one"""
-    t = t.contiguous()
-    if t.dtype == torch.int32:
-        return t.cpu().numpy().view(np.uint32)
-    return t.view(torch.int16).cpu().numpy().view(np.uint16)
-
-
-def stream_ptr():
-    return int(torch.cuda.current_stream().cuda_stream)
-
-
-def fault_word(ws):
-    return int(ws[:4].view(torch.int32).item()) & 0xFFFFFFFF
 
 
 # ---- the two checks every shape goes through -------------------------------------------------------------------------------------
@@ -259,19 +233,6 @@ def test_guard_bands_exact_workspace_and_null_indices(shape, skip_bytes):
 
 
 # ---- graph replay: the point of the entries ---------------------------------------------------------------------------------------
-def captured(call):
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        call()   # warm-up: device set-up stays out of the capture
-    torch.cuda.current_stream().wait_stream(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        call()
-    return g
-
-
 @pytest.mark.parametrize("with_idx", [True, False], ids=["indices", "values"])
 @pytest.mark.parametrize("shape", [(3, 70001), (17, 1000)], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_perrow_graph_replay_follows_ranks_and_keys(shape, with_idx):

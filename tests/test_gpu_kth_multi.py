@@ -18,38 +18,11 @@ import torch
 
 import _row_rounds as rr
 import lsdradixsort_amd as lsd
+from _device_arrays import bits, to_dev
 from _guarded import assert_intact, assert_unchanged, guarded, guarded_workspace, without_sentinel
+from _key_oracle import KEY_TYPES32 as KEY_TYPES, MULTI_RANK32, SPECIALS32 as SPECIALS, expected_np, inputs32 as inputs
 
 pytestmark = pytest.mark.gpu
-
-KEY_TYPES = {"uint32": 0, "int32": 1, "float32": 2}
-SPECIALS = np.array([0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x00000001, 0x80000001, 0x007FFFFF, 0x807FFFFF,
-                     0x7FC00000, 0xFFC00000, 0x7F800001, 0xFFFFFFFF, 0x7FFFFFFF, 0x3F800000, 0xBF800000], dtype=np.uint32)
-
-
-def sortable_np(u, key_type, descending):
-    u = u.astype(np.uint32)
-    if key_type == "int32":
-        u = u ^ np.uint32(0x80000000)
-    elif key_type == "float32":
-        u = u ^ ((u >> np.uint32(31)) * np.uint32(0x7FFFFFFF) | np.uint32(0x80000000))
-    return ~u if descending else u
-
-
-def from_sortable_np(s, key_type):
-    """the key whose ascending sortable value is s"""
-    s = s.astype(np.uint32)
-    if key_type == "int32":
-        return s ^ np.uint32(0x80000000)
-    if key_type == "float32":
-        return np.where(s >> np.uint32(31) != 0, s ^ np.uint32(0x80000000), ~s).astype(np.uint32)
-    return s
-
-
-def expected_np(keys, key_type, largest):
-    """keys: [rows, cols] uint32 bits -> the full stable order of every row: (sorted keys, positions)"""
-    order = np.argsort(sortable_np(keys, key_type, largest), axis=1, kind="stable")
-    return np.take_along_axis(keys, order, axis=1), order.astype(np.uint32)
 
 
 def rank_sets(cols):
@@ -57,47 +30,6 @@ def rank_sets(cols):
     sets = [[cols // 2], [(cols - 1) // 2, cols // 2], [cols // 4, cols // 2, 3 * cols // 4],
             [cols - 1, 0, cols // 2, cols // 2, 1, cols // 4, 3 * cols // 4, cols - 2]]
     return [[min(max(r, 0), cols - 1) for r in ranks] for ranks in sets]
-
-
-def inputs(rows, cols, key_type, seed):
-    """name -> [rows, cols] uint32"""
-    rng = np.random.default_rng(seed)
-    out = {"uniform bits": rng.integers(0, 1 << 32, (rows, cols), dtype=np.uint64).astype(np.uint32)}
-    four = np.array([5, 0x00010000, 0x7FFFFFFF, 0xFFFFFFF0], dtype=np.uint32)
-    out["four values"] = four[rng.integers(0, 4, (rows, cols))]                    # tie runs: slots share a final prefix, needs differ
-    out["all equal"] = np.full((rows, cols), 0x9E3779B9, dtype=np.uint32)          # every slot's position must equal its rank
-    shared = np.uint32(0xABCDEF00) | rng.integers(0, 256, (rows, cols)).astype(np.uint32)
-    out["shared top 24 bits"] = shared                                             # one leader through level 1, every level runs
-    out["bit 0 only"] = np.uint32(0x40302010) | rng.integers(0, 2, (rows, cols)).astype(np.uint32)
-    if key_type == "float32":
-        f = rng.standard_normal(rows * cols).astype(np.float32).view(np.uint32).copy()
-        pick = rng.random(rows * cols) < 0.3
-        f[pick] = SPECIALS[rng.integers(0, SPECIALS.size, int(pick.sum()))]        # +-0, +-inf, NaNs of both signs, denormals
-        out["float specials"] = f.reshape(rows, cols)
-    if cols >= 8:
-        # In sortable order: three keys of unique top bits at each end of a row that otherwise shares its top 24 bits.  Ranks 0, 1
-        # and cols - 1 stop at level 0 while the middle slots run every level: done and live slots side by side.
-        s = shared.copy()
-        ends = np.array([0x00200000, 0x00400000, 0x00600000, 0xFFA00000, 0xFFC00000, 0xFFE00000], dtype=np.uint32)
-        for r in range(rows):
-            where = rng.choice(cols, ends.size, replace=False)
-            s[r, where] = ends | rng.integers(0, 1 << 20, ends.size).astype(np.uint32)
-        out["outliers"] = from_sortable_np(s, key_type)
-    return out
-
-
-def to_dev(keys, key_type, offset=0):
-    """the keys on the device as a contiguous [rows, cols] view `offset` elements into a 512-byte aligned buffer"""
-    rows, cols = keys.shape
-    flat = torch.empty(rows * cols + offset, dtype=torch.int32, device="cuda")
-    view = flat[offset:].view(rows, cols)
-    view.copy_(torch.from_numpy(np.ascontiguousarray(keys).view(np.int32)))
-    assert view.is_contiguous() and view.data_ptr() % 16 == (4 * offset) % 16
-    return view.view(torch.float32) if key_type == "float32" else view
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32).cpu().numpy().view(np.uint32)
 
 
 def check_sets(dk, keys, key_type, what, sets=None, orders=(False, True)):
@@ -125,7 +57,7 @@ def check_sets(dk, keys, key_type, what, sets=None, orders=(False, True)):
 
 
 def check_shape(rows, cols, key_type):
-    for name, keys in inputs(rows, cols, key_type, seed=1000 * rows + cols).items():
+    for name, keys in inputs(rows, cols, key_type, seed=1000 * rows + cols, families=MULTI_RANK32).items():
         check_sets(to_dev(keys, key_type), keys, key_type, name)
 
 
@@ -163,7 +95,7 @@ TIER_SHAPES = [(9, 1000), (3, 4097), (3, 70001)]   # one per tier, all with odd 
 @pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_one_rank_values_only_and_one_row_input(shape):
     rows, cols = shape
-    keys = inputs(rows, cols, "int32", seed=cols)["four values"]
+    keys = inputs(rows, cols, "int32", seed=cols, families=MULTI_RANK32)["four values"]
     dk = to_dev(keys, "int32")
     ek, ei = expected_np(keys, "int32", False)
     for rank in (0, cols // 2, cols - 1):   # num_ranks = 1 is GPUKth
@@ -182,7 +114,7 @@ def test_one_rank_values_only_and_one_row_input(shape):
 @pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_views_off_the_16_byte_line(shape, offset):
     rows, cols = shape
-    for name, keys in inputs(rows, cols, "float32", seed=offset + cols).items():
+    for name, keys in inputs(rows, cols, "float32", seed=offset + cols, families=MULTI_RANK32).items():
         if name in ("uniform bits", "four values", "outliers"):
             check_sets(to_dev(keys, "float32", offset), keys, "float32", f"{name} offset {offset}", sets=rank_sets(cols)[2:])
 
@@ -209,7 +141,7 @@ def raw_call(keys, ranks, key_type, largest, with_idx, skip_bytes, short_by=0):
 @pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_guard_bands_exact_workspace_and_null_indices(shape, skip_bytes):
     rows, cols = shape
-    keys = without_sentinel(inputs(rows, cols, "float32", seed=cols + skip_bytes)["float specials"])
+    keys = without_sentinel(inputs(rows, cols, "float32", seed=cols + skip_bytes, families=MULTI_RANK32)["float specials"])
     ranks = [3 * cols // 4, cols // 4, cols // 2]
     ek, ei = expected_np(keys, "float32", True)
     st, *_ = raw_call(keys, ranks, "float32", True, True, skip_bytes, short_by=1)
@@ -230,7 +162,7 @@ def test_guard_bands_exact_workspace_and_null_indices(shape, skip_bytes):
 @pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_same_result_without_the_returning_add_rank_form(shape):
     rows, cols = shape
-    keys = inputs(rows, cols, "int32", seed=cols + 1)["outliers"]
+    keys = inputs(rows, cols, "int32", seed=cols + 1, families=MULTI_RANK32)["outliers"]
     dk = to_dev(keys, "int32")
     lsd.set_rank_method(0)
     try:
@@ -246,7 +178,7 @@ def test_same_result_without_the_returning_add_rank_form(shape):
 @pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_two_calls_on_one_workspace_agree(shape):
     rows, cols = shape
-    keys = inputs(rows, cols, "uint32", seed=cols + 2)["four values"]
+    keys = inputs(rows, cols, "uint32", seed=cols + 2, families=MULTI_RANK32)["four values"]
     dk = to_dev(keys, "uint32")
     ranks = rank_sets(cols)[3]
     ws = torch.empty(lsd.kth_multi_workspace_bytes(rows, cols, len(ranks)), dtype=torch.uint8, device="cuda")
@@ -277,7 +209,7 @@ def test_graph_replay_on_changed_input(shape):
                                         ws.data_ptr(), ws.numel(), int(torch.cuda.current_stream().cuda_stream))
         assert st == 0, st
 
-    kinds = inputs(rows, cols, "int32", seed=cols + 3)
+    kinds = inputs(rows, cols, "int32", seed=cols + 3, families=MULTI_RANK32)
     dk.copy_(torch.from_numpy(kinds["uniform bits"].view(np.int32)))
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())

@@ -14,8 +14,8 @@ the library says.  The OUTPUTS are prefilled with the sentinel and the inputs ho
 to write shows as such; torch's caching allocator could hand a wrapper the previous call's correct answer instead.  After every
 call: status, fault word, both zones of every buffer, the input unchanged.
 
-Expected: the order-preserving map restated in numpy, then np.argsort(axis=1, kind="stable") -- expected_np of test_gpu_kth.py and
-test_gpu_kth16.py.  A mismatch is reported by row, round (row // stride) and slot within the round (row % stride)."""
+Expected: the order-preserving map restated in numpy, then np.argsort(axis=1, kind="stable") -- expected_np of _key_oracle.py.  A
+mismatch is reported by row, round (row // stride) and slot within the round (row % stride)."""
 import functools
 import zlib
 
@@ -25,10 +25,10 @@ import torch
 
 import _row_rounds as rr
 import lsdradixsort_amd as lsd
+from _device_arrays import DTYPES, stream_ptr
 from _guarded import SENT32, assert_intact, assert_unchanged, guarded, guarded_workspace, without_sentinel
 from _guarded16 import SENT16, assert_intact16, bits_of, guarded16
-from test_gpu_kth import KEY_TYPES as KEY_TYPES32, SPECIALS as SPECIALS32, expected_np as expected32
-from test_gpu_kth16 import DTYPES as DTYPES16, KEY_TYPES as KEY_TYPES16, SPECIALS as SPECIALS16, expected_np as expected16
+from _key_oracle import KEY_TYPES16, KEY_TYPES32, SPECIALS16, SPECIALS32, expected_np
 
 pytestmark = pytest.mark.gpu
 
@@ -55,7 +55,7 @@ def case(shape_name, stride, key_type, shift=0):
         without_sentinel(keys)
     else:
         keys[keys == SENT16] ^= np.uint16(1)
-    expected = {largest: (expected32 if wide else expected16)(keys, key_type, largest) for largest in ORDERS}
+    expected = {largest: expected_np(keys, key_type, largest) for largest in ORDERS}
     for a in (keys,) + expected[False] + expected[True]:
         a.setflags(write=False)
     return keys, expected
@@ -87,7 +87,7 @@ class Input:
     def __init__(self, keys, key_type):
         self.keys, self.wide = keys, key_type in KEY_TYPES32
         self.code = (KEY_TYPES32 if self.wide else KEY_TYPES16)[key_type]
-        self.whole, self.view = guarded(keys) if self.wide else guarded16(keys, 0, DTYPES16[key_type])
+        self.whole, self.view = guarded(keys) if self.wide else guarded16(keys, 0, DTYPES[key_type])
 
     def check(self):
         if self.wide:
@@ -130,10 +130,6 @@ class Outputs:
         if not with_idx:
             assert (idx == SENT32).all(), "no index buffer was given: nothing may be written"
         return (self.vals.cpu().numpy().view(np.uint32) if self.wide else bits_of(self.vals)), idx
-
-
-def stream_ptr():
-    return int(torch.cuda.current_stream().cuda_stream)
 
 
 def sent(inp):

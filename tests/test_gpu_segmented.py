@@ -8,21 +8,13 @@ import pytest
 import torch
 
 import lsdradixsort_amd as lsd
+from _device_arrays import assert_equal
+from _key_oracle import sortable_np
 from _seg_plan import expected_dev   # the large shapes' reference: shared with test_gpu_segmented_plan.py
 
 pytestmark = pytest.mark.gpu
 
 WAVE_CAP = 1024
-KEY_TYPES = {"uint32": 0, "int32": 1, "float32": 2}
-
-
-def sortable_np(u, key_type, descending):
-    u = u.astype(np.uint32)
-    if key_type == "int32":
-        u = u ^ np.uint32(0x80000000)
-    elif key_type == "float32":
-        u = u ^ ((u >> np.uint32(31)) * np.uint32(0x7FFFFFFF) | np.uint32(0x80000000))
-    return ~u if descending else u
 
 
 def expected(keys, offsets, vals=None, key_type="uint32", descending=False):
@@ -49,12 +41,6 @@ def run(keys, offsets, vals=None, key_type="uint32", descending=False, check=Tru
     gk = dk.cpu().numpy().view(np.uint32)
     gv = None if dv is None else dv.cpu().numpy().view(np.uint32)
     return gk, gv
-
-
-def assert_equal(a, b, what):
-    if not np.array_equal(a, b):
-        bad = np.flatnonzero(a != b)
-        raise AssertionError(f"{what}: {bad.size} words differ, first at {bad[0]}: got {a[bad[0]]:#x} want {b[bad[0]]:#x}")
 
 
 def boundary_offsets(head=0, tail=0, big=True):

@@ -14,23 +14,20 @@ import torch
 
 import lsdradixsort_amd as lsd
 import _seg_plan as sp
+from _device_arrays import stream_ptr
 from _guarded import GUARD, SENT32, assert_intact, guarded_workspace
+from _key_oracle import KEY_TYPES32 as KEY_TYPES
 
 pytestmark = pytest.mark.gpu
 
-KEY_TYPES = {"uint32": 0, "int32": 1, "float32": 2}
 _inputs, _wanted = {}, {}   # made once per module and left unchanged
-
-
-def stream_ptr():
-    return int(torch.cuda.current_stream().cuda_stream)
 
 
 def offsets_dev(off):
     return torch.from_numpy(off.astype(np.uint32).view(np.int32)).cuda()
 
 
-def inputs(name, key_type, seed):
+def shape_inputs(name, key_type, seed):
     """(offsets, n, keys' bits as int32 on the device) of a shape"""
     key = (name, key_type, seed)
     if key not in _inputs:
@@ -43,7 +40,7 @@ def wanted(name, key_type, seed, descending):
     """(sorted keys, payloads of an arange) of the reference"""
     key = (name, key_type, seed, descending)
     if key not in _wanted:
-        off, n, keys = inputs(name, key_type, seed)
+        off, n, keys = shape_inputs(name, key_type, seed)
         want, idx = sp.expected_dev(keys, off, key_type, descending)
         vals = torch.arange(n, dtype=torch.int64, device="cuda")
         vals[int(off[0]):int(off[-1])] = idx
@@ -109,7 +106,7 @@ class Call:
 
 
 def run_shape(name, key_type="uint32", descending=False, pairs=True, seed=1):
-    off, n, keys = inputs(name, key_type, seed)
+    off, n, keys = shape_inputs(name, key_type, seed)
     want_keys, want_vals = wanted(name, key_type, seed, descending)
     call = Call(keys, off, pairs, key_type, descending).launch()
     call.check(want_keys, want_vals, sp.plan_of(name), f"{name} {key_type} descending={descending} pairs={pairs}")
@@ -139,7 +136,7 @@ def test_fallback_form_past_the_item_cap(name):
         lsd.set_rank_method(-1)
     if name == "ITEMS_FALLBACK":
         # the default form on the same input: wave and workgroup tiers, no item at all
-        off, n, keys = inputs(name, "float32", 1)
+        off, n, keys = shape_inputs(name, "float32", 1)
         sizes = sp.SHAPES[name][0]
         default = Call(keys, off, True, "float32", True).launch()
         default.check(*wanted(name, "float32", 1, True), sp.plan(sizes, True, n), f"{name} float32 descending, default form")
@@ -158,7 +155,7 @@ def test_tiles_second_round_of_hist_scatter_and_the_scan_carry(key_type, descend
 def test_mixed_all_three_tiers_and_the_item_round():
     name = "MIXED"
     call = run_shape(name)
-    off, n, keys = inputs(name, "uint32", 1)
+    off, n, keys = shape_inputs(name, "uint32", 1)
     head, tail = sp.SHAPES[name][2:]
     assert int(off[0]) == head and n - int(off[-1]) == tail and head and tail
     assert_same(call.keys[:head], keys[:head], "untouched head")
@@ -170,7 +167,7 @@ def test_mixed_all_three_tiers_and_the_item_round():
 def test_same_bits_twice():
     """the planner fills its lists by atomics, so the tile table's order differs from call to call: the result must not"""
     name = "ITEMS"
-    off, n, keys = inputs(name, "uint32", 1)
+    off, n, keys = shape_inputs(name, "uint32", 1)
     want = wanted(name, "uint32", 1, False)
     ws = guarded_workspace(lsd.lib().lsdsort_segmented_workspace_bytes(n, off.size - 1, 1))
     first = Call(keys, off, True, ws=ws).launch()
@@ -186,7 +183,7 @@ def test_graph_replay_across_the_regime():
     """captured with offsets that leave the large tier's tables empty (every workgroup of its launches leaves), replayed with those,
     with ITEMS' offsets and fresh keys, and with the short ones again"""
     name = "ITEMS"
-    off_large, n, _ = inputs(name, "uint32", 1)
+    off_large, n, _ = shape_inputs(name, "uint32", 1)
     segs = off_large.size - 1
     short_sizes = np.full(segs, sp.SHORT_SIZE, dtype=np.int64)
     off_short = np.concatenate([[0], np.cumsum(short_sizes)])

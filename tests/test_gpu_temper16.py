@@ -16,41 +16,20 @@ import _rowk16 as rk
 import _sample16 as sm
 import _temper16 as tm
 import _topp16 as tp
+from _device_arrays import DTYPES, bits, captured, fault_word, stream_ptr, to_dev
 from _guarded import assert_intact, guarded, guarded_workspace
 from _guarded16 import assert_intact16, bits_of, guarded16
+from _key_oracle import KEY_TYPES16 as KEY_TYPES
 
 pytestmark = pytest.mark.gpu
 
-KEY_TYPES = rk.KEY_TYPES
-DTYPES = {"float16": torch.float16, "bfloat16": torch.bfloat16}
 SHARP_COLS = (64, 257, 1024, 1025, 16384, 16385, 40000)
 TIER_SHAPES = [(17, 1000), (3, 4099), (3, 70001)]   # one per tier, all with odd or unaligned rows
 SENT_INDEX, SENT_LOGPROB = 0x5A5A5A5A, 0x5B5B5B5B
 
 
-def to_dev(keys, key_type, offset=0):
-    """the keys on the device as a contiguous [rows, cols] view `offset` elements into a 512-byte aligned buffer"""
-    rows, cols = keys.shape
-    flat = torch.empty(rows * cols + offset, dtype=torch.int16, device="cuda")
-    view = flat[offset:].view(rows, cols)
-    view.copy_(torch.from_numpy(np.ascontiguousarray(keys).view(np.int16)))
-    return view.view(DTYPES[key_type])
-
-
 def dev_f32(values):
     return None if values is None else torch.from_numpy(np.ascontiguousarray(values, dtype=np.float32).copy()).cuda()
-
-
-def bits(t):
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
-
-
-def stream_ptr():
-    return int(torch.cuda.current_stream().cuda_stream)
-
-
-def fault_word(ws):
-    return int(ws[:4].view(torch.int32).item()) & 0xFFFFFFFF
 
 
 def ptr(t):
@@ -440,19 +419,6 @@ def test_same_bits_on_ten_calls_and_row_by_row(shape, key_type):
 
 
 # ---- graph replay --------------------------------------------------------------------------------------------------------------------------
-def captured(call):
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        call()   # warm-up: device set-up stays out of the capture
-    torch.cuda.current_stream().wait_stream(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        call()
-    return g
-
-
 @pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_graph_replay_follows_every_array_and_the_keys(shape):
     """the ex filter in place and the ex draw on its result, captured once; T, mp, p, u and the keys change between replays and every

@@ -22,10 +22,9 @@ import _sample16 as sm
 import _temper16 as tm
 import _tier_bits as tb
 import _topp16 as tp
+from _device_arrays import DTYPES
 
 pytestmark = pytest.mark.gpu
-
-DTYPES = {"float16": torch.float16, "bfloat16": torch.bfloat16}
 
 
 class DeviceOps:

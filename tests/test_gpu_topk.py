@@ -13,32 +13,10 @@ import pytest
 import torch
 
 import lsdradixsort_amd as lsd
+from _device_arrays import assert_equal, bits, to_dev
+from _key_oracle import KEY_TYPES32 as KEY_TYPES, expected_np, make_keys32 as make_keys
 
 pytestmark = pytest.mark.gpu
-
-KEY_TYPES = {"uint32": 0, "int32": 1, "float32": 2}
-SPECIALS = np.array([0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x00000001, 0x80000001, 0x007FFFFF, 0x807FFFFF,
-                     0x7FC00000, 0xFFC00000, 0x7F800001, 0xFFFFFFFF, 0x7FFFFFFF, 0x3F800000, 0xBF800000], dtype=np.uint32)
-
-
-def sortable_np(u, key_type, descending):
-    u = u.astype(np.uint32)
-    if key_type == "int32":
-        u = u ^ np.uint32(0x80000000)
-    elif key_type == "float32":
-        u = u ^ ((u >> np.uint32(31)) * np.uint32(0x7FFFFFFF) | np.uint32(0x80000000))
-    return ~u if descending else u
-
-
-def expected_np(keys, key_type, largest):
-    """keys: [rows, cols] uint32 bits -> the full stable order of every row: (sorted keys, positions), to be cut to k columns"""
-    s = sortable_np(keys, key_type, largest)
-    rows, cols = keys.shape
-    pos = np.arange(cols)
-    order = np.empty((rows, cols), dtype=np.int64)
-    for r in range(rows):
-        order[r] = np.lexsort((pos, s[r]))
-    return np.take_along_axis(keys, order, axis=1), order.astype(np.uint32)
 
 
 def k_values(cols):
@@ -46,37 +24,6 @@ def k_values(cols):
     thr = 3 * cols // 4   # the largest k of the select route
     ks = {1, 2, 63, 64, 65, 1023, 1024, 1025, 16383, 16384, 16385, thr - 1, thr, thr + 1, cols - 1, cols}
     return sorted(k for k in ks if 1 <= k <= cols)
-
-
-def make_keys(rows, cols, key_type, seed):
-    rng = np.random.default_rng(seed)
-    n = rows * cols
-    if key_type == "float32":
-        keys = rng.standard_normal(n).astype(np.float32).view(np.uint32).copy()
-        pick = rng.random(n) < 0.3
-        keys[pick] = SPECIALS[rng.integers(0, SPECIALS.size, int(pick.sum()))]
-    else:
-        keys = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
-        keys[rng.random(n) < 0.1] = np.uint32(0x80000000)
-        keys[rng.random(n) < 0.1] = np.uint32(0x7FFFFFFF)
-    return keys.reshape(rows, cols)
-
-
-def to_dev(keys, key_type):
-    return torch.from_numpy(np.ascontiguousarray(keys).view(np.float32 if key_type == "float32" else np.int32)).cuda()
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32).cpu().numpy().view(np.uint32)
-
-
-def assert_equal(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape, f"{what}: shape {a.shape} against {b.shape}"
-    if not np.array_equal(a, b):
-        bad = np.argwhere(a != b)
-        at = tuple(bad[0])
-        raise AssertionError(f"{what}: {len(bad)} words differ, first at {at}: got {a[at]:#x} want {b[at]:#x}")
 
 
 def check_case(dk, key_type, largest, k, ek, ei, what):

@@ -15,44 +15,15 @@ import pytest
 import torch
 
 import lsdradixsort_amd as lsd
+from _device_arrays import DTYPES, assert_equal, stream_ptr
 from _guarded import assert_intact, guarded, guarded_workspace
 from _guarded16 import assert_intact16, bits_of, guarded16
+from _key_oracle import ALL_TYPES16 as ALL_TYPES, KEY_TYPES16 as KEY_TYPES, expected_np, make_keys16 as make_keys, sortable16_np
 
 pytestmark = pytest.mark.gpu
 
-KEY_TYPES = {"uint16": 0, "int16": 1, "float16": 2, "bfloat16": 3}
-DTYPES = {"uint16": torch.int16, "int16": torch.int16, "float16": torch.float16, "bfloat16": torch.bfloat16}
-ALL_TYPES = ["uint16", "int16", "float16", "bfloat16"]
 OFFSETS = (0, 2, 6, 14)
-# +-0, +-inf, +-NaN (quiet, signalling, all ones), denormals, the largest finite values
-SPECIALS = {
-    "float16": np.array([0x0000, 0x8000, 0x7C00, 0xFC00, 0x7E00, 0xFE00, 0x7C01, 0xFFFF, 0x7FFF, 0x0001, 0x8001, 0x03FF, 0x83FF,
-                         0x7BFF, 0xFBFF, 0x3C00, 0xBC00], dtype=np.uint16),
-    "bfloat16": np.array([0x0000, 0x8000, 0x7F80, 0xFF80, 0x7FC0, 0xFFC0, 0x7F81, 0xFFFF, 0x7FFF, 0x0001, 0x8001, 0x007F, 0x807F,
-                          0x7F7F, 0xFF7F, 0x3F80, 0xBF80], dtype=np.uint16),
-}
 FILL16, FILL32 = 0xA5A5, 0x3C3C3C3C   # what the outputs hold before a call
-
-
-def sortable16_np(u, key_type, largest):
-    """the map of include/lsdsort.h restated: the uint16 whose unsigned order is the requested one"""
-    u = u.astype(np.uint32)
-    if key_type == "int16":
-        u = u ^ np.uint32(0x8000)
-    elif key_type in ("float16", "bfloat16"):
-        u = u ^ np.where(u & np.uint32(0x8000), np.uint32(0xFFFF), np.uint32(0x8000))
-    return (u ^ np.uint32(0xFFFF)) if largest else u
-
-
-def expected_np(keys, key_type, largest):
-    """keys: [rows, cols] uint16 bits -> the full stable order of every row: (sorted keys, positions), to be cut to k columns"""
-    s = sortable16_np(keys, key_type, largest)
-    rows, cols = keys.shape
-    pos = np.arange(cols)
-    order = np.empty((rows, cols), dtype=np.int64)
-    for r in range(rows):
-        order[r] = np.lexsort((pos, s[r]))
-    return np.take_along_axis(keys, order, axis=1), order.astype(np.uint32)
 
 
 def k_values(cols):
@@ -60,30 +31,6 @@ def k_values(cols):
     thr = 3 * cols // 4   # the largest k of the select route
     ks = {1, 2, 63, 64, 65, 1023, 1024, 1025, 16383, 16384, 16385, thr - 1, thr, thr + 1, cols - 1, cols}
     return sorted(k for k in ks if 1 <= k <= cols)
-
-
-def make_keys(rows, cols, key_type, seed):
-    """random bits; the float types with 30 % specials"""
-    rng = np.random.default_rng(seed)
-    n = rows * cols
-    keys = rng.integers(0, 1 << 16, n, dtype=np.uint32).astype(np.uint16)
-    if key_type in SPECIALS:
-        pick = rng.random(n) < 0.3
-        keys[pick] = SPECIALS[key_type][rng.integers(0, SPECIALS[key_type].size, int(pick.sum()))]
-    return keys.reshape(rows, cols)
-
-
-def assert_equal(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape, f"{what}: shape {a.shape} against {b.shape}"
-    if not np.array_equal(a, b):
-        bad = np.argwhere(a != b)
-        at = tuple(bad[0])
-        raise AssertionError(f"{what}: {len(bad)} words differ, first at {at}: got {a[at]:#x} want {b[at]:#x}")
-
-
-def stream_ptr(stream=None):
-    return int((stream or torch.cuda.current_stream()).cuda_stream)
 
 
 class Call:

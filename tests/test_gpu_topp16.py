@@ -15,42 +15,21 @@ import torch
 import lsdradixsort_amd as lsd
 import _rowk16 as rk
 import _topp16 as tp
+from _device_arrays import DTYPES, bits, captured, fault_word, stream_ptr, to_dev
 from _guarded import assert_intact, guarded, guarded_workspace
 from _guarded16 import assert_intact16, bits_of, guarded16
+from _key_oracle import KEY_TYPES16 as KEY_TYPES
 
 pytestmark = pytest.mark.gpu
 
-KEY_TYPES = rk.KEY_TYPES
-DTYPES = {"float16": torch.float16, "bfloat16": torch.bfloat16}
 COLS = (1, 2, 63, 64, 65, 1023, 1024, 1025, 4097, 16383, 16384, 16385, 20481, 40000, 70001)
 ROWS = (1, 3, 8, 9, 17)
 SHARP_COLS = (64, 257, 1024, 1025, 16384, 16385, 40000)
 TIER_SHAPES = [(17, 1000), (3, 4099), (3, 70001)]   # one per tier, all with odd or unaligned rows
 
 
-def to_dev(keys, key_type, offset=0):
-    """the keys on the device as a contiguous [rows, cols] view `offset` elements into a 512-byte aligned buffer"""
-    rows, cols = keys.shape
-    flat = torch.empty(rows * cols + offset, dtype=torch.int16, device="cuda")
-    view = flat[offset:].view(rows, cols)
-    view.copy_(torch.from_numpy(np.ascontiguousarray(keys).view(np.int16)))
-    return view.view(DTYPES[key_type])
-
-
 def dev_f32(values):
     return torch.from_numpy(np.ascontiguousarray(values, dtype=np.float32).copy()).cuda()
-
-
-def bits(t):
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
-
-
-def stream_ptr():
-    return int(torch.cuda.current_stream().cuda_stream)
-
-
-def fault_word(ws):
-    return int(ws[:4].view(torch.int32).item()) & 0xFFFFFFFF
 
 
 def run_both(keys, p, key_type, what, offset=0):
@@ -190,19 +169,6 @@ def test_same_bits_on_every_call_and_row_by_row(shape, key_type):
 
 
 # ---- graph replay ------------------------------------------------------------------------------------------------------------------
-def captured(call):
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        call()   # warm-up: device set-up stays out of the capture
-    torch.cuda.current_stream().wait_stream(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        call()
-    return g
-
-
 @pytest.mark.parametrize("in_place", [False, True], ids=["copy", "in place"])
 @pytest.mark.parametrize("shape", TIER_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_graph_replay_follows_p_and_keys(shape, in_place):

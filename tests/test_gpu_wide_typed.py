@@ -5,10 +5,10 @@ gathered; (2) where the type's native order is unambiguous, numpy / torch sort t
 import numpy as np
 import pytest
 
+from _key_oracle import ALL_TYPES64 as KEY_TYPES, KEY_TYPES64 as CODES
+
 pytestmark = pytest.mark.gpu
 
-KEY_TYPES = ("uint64", "int64", "float64")
-CODES = {"uint64": 3, "int64": 4, "float64": 5}
 TOP = np.uint64(1 << 63)
 ONES = np.uint64(0xFFFFFFFFFFFFFFFF)
 SIZES = [0, 1, 2, 255, 4097, 16385, (1 << 20) + 5]   # 16385: the first size past the one-launch small sort

@@ -6,17 +6,12 @@ import re
 
 import pytest
 
+from _faces import FakeCuda, lib as _lib, no_library
 from _kernel_resources import hipcc, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U16, I16, F16, BF16 = range(4)
 ENTRIES = ("lsdsort_keys16_workspace_bytes", "lsdsort_keys16_device", "lsdsort_keys16_check_device", "lsdsort_set_keys16_route")
-
-
-def _lib():
-    from lsdradixsort_amd import lib
-
-    return lib()
 
 
 def test_header_ctypes_table_and_faces_have_the_entries():
@@ -130,18 +125,6 @@ def test_route_setter():
         assert L.lsdsort_set_keys16_route(-1) == E.LSDSORT_OK
 
 
-@pytest.fixture
-def no_library(monkeypatch):
-    """The argument checks come first: the library must not even be asked for."""
-    import lsdradixsort_amd as lsd
-
-    def refuse():
-        raise AssertionError("the library was reached before the arguments were checked")
-
-    monkeypatch.setattr(lsd.api, "lib", refuse)
-    return lsd
-
-
 def test_wrappers_check_their_tensors_before_the_library(no_library):
     import torch
 
@@ -164,9 +147,6 @@ def test_dtype_and_key_type_must_agree(no_library, monkeypatch):
     import torch
 
     lsd = no_library
-
-    class FakeCuda(torch.Tensor):
-        is_cuda = True
 
     def fake(dtype):
         return torch.zeros(8, dtype=dtype).as_subclass(FakeCuda)

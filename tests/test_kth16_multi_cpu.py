@@ -8,6 +8,7 @@ import re
 import pytest
 
 import _row_rounds as rr
+from _faces import FakeCuda, lib as _lib, no_library
 from _kernel_resources import hipcc, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,12 +17,6 @@ GOLDEN_32 = os.path.join(ROOT, "tests", "golden", "kernel_resources_kth_multi.js
 U16, I16, F16, BF16 = range(4)
 ENTRIES = ("lsdsort_kth16_multi_workspace_bytes", "lsdsort_kth16_multi_device")
 NAMES = ("GPUKth16Multi", "kth16_multi_workspace_bytes", "quantile16_rows")
-
-
-def _lib():
-    from lsdradixsort_amd import lib
-
-    return lib()
 
 
 def test_header_ctypes_table_and_package_have_the_entries():
@@ -195,18 +190,6 @@ def test_workspace_figure():
         assert f(rows, cols, 9) == 0 and f(rows, cols, 100) == 0, (rows, cols)
 
 
-@pytest.fixture
-def no_library(monkeypatch):
-    """The argument checks come first: the library must not even be asked for."""
-    import lsdradixsort_amd as lsd
-
-    def refuse():
-        raise AssertionError("the library was reached before the arguments were checked")
-
-    monkeypatch.setattr(lsd.api, "lib", refuse)
-    return lsd
-
-
 def test_wrappers_check_their_tensors_before_the_library(no_library):
     import torch
 
@@ -229,9 +212,6 @@ def test_dtype_key_type_ranks_q_and_mode(no_library):
     import torch
 
     lsd = no_library
-
-    class FakeCuda(torch.Tensor):
-        is_cuda = True
 
     def fake(dtype, shape=(2, 4)):
         return torch.zeros(shape, dtype=dtype).as_subclass(FakeCuda)

@@ -11,6 +11,7 @@ import pytest
 
 import _row_rounds as rr
 import _rowk16 as rk
+from _faces import FakeCuda, lib as _lib, no_library
 from _kernel_resources import hipcc, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,12 +20,6 @@ U16, I16, F16, BF16 = range(4)
 ENTRIES = ("lsdsort_kth16_perrow_workspace_bytes", "lsdsort_kth16_perrow_device", "lsdsort_topk16_filter_workspace_bytes",
            "lsdsort_topk16_filter_device")
 NAMES = ("GPUKth16PerRow", "kth16_perrow_workspace_bytes", "GPUTopK16Filter", "topk16_filter_workspace_bytes", "topk16_filter_rows")
-
-
-def _lib():
-    from lsdradixsort_amd import lib
-
-    return lib()
 
 
 def test_header_ctypes_table_and_package_have_the_entries():
@@ -237,18 +232,6 @@ def test_workspace_figure(entry):
             assert f(rows, cols) == L.lsdsort_kth16_workspace_bytes(rows, cols), (rows, cols)
 
 
-@pytest.fixture
-def no_library(monkeypatch):
-    """The argument checks come first: the library must not even be asked for."""
-    import lsdradixsort_amd as lsd
-
-    def refuse():
-        raise AssertionError("the library was reached before the arguments were checked")
-
-    monkeypatch.setattr(lsd.api, "lib", refuse)
-    return lsd
-
-
 def test_wrappers_check_their_tensors_before_the_library(no_library):
     import torch
 
@@ -274,9 +257,6 @@ def test_dtype_key_type_per_row_arrays_fill_and_k(no_library):
     import torch
 
     lsd = no_library
-
-    class FakeCuda(torch.Tensor):
-        is_cuda = True
 
     def fake(dtype, shape=(2, 4)):
         return torch.zeros(shape, dtype=dtype).as_subclass(FakeCuda)

@@ -5,17 +5,12 @@ import re
 
 import pytest
 
+from _faces import FakeCuda, lib as _lib, no_library
 from _kernel_resources import hipcc, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U32, I32, F32 = range(3)
 ENTRIES = ("lsdsort_kth_workspace_bytes", "lsdsort_kth_device")
-
-
-def _lib():
-    from lsdradixsort_amd import lib
-
-    return lib()
 
 
 def test_header_ctypes_table_and_faces_have_the_entries():
@@ -152,18 +147,6 @@ def test_workspace_figure():
     assert f(1, BIG) > 0 and f(BIG, 1) > 0
 
 
-@pytest.fixture
-def no_library(monkeypatch):
-    """The argument checks come first: the library must not even be asked for."""
-    import lsdradixsort_amd as lsd
-
-    def refuse():
-        raise AssertionError("the library was reached before the arguments were checked")
-
-    monkeypatch.setattr(lsd.api, "lib", refuse)
-    return lsd
-
-
 def test_wrappers_check_their_tensors_before_the_library(no_library):
     import torch
 
@@ -190,9 +173,6 @@ def test_dtype_key_type_rank_and_k(no_library):
     import torch
 
     lsd = no_library
-
-    class FakeCuda(torch.Tensor):
-        is_cuda = True
 
     def fake(dtype, shape=(2, 4)):
         return torch.zeros(shape, dtype=dtype).as_subclass(FakeCuda)

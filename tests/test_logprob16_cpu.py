@@ -13,6 +13,7 @@ import pytest
 import _logprob16 as lg
 import _temper16 as tm
 import _topp16 as tp
+from _faces import FakeCuda, lib as _lib, no_library
 from _kernel_resources import hipcc, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,12 +22,6 @@ U16, I16, F16, BF16 = range(4)
 ENTRIES = ("lsdsort_logprob16_workspace_bytes", "lsdsort_logprob16_device")
 NAMES = ("GPULogprob16", "logprob16_workspace_bytes", "logprobs16_rows", "top_logprobs16_rows")
 MAX_SLOTS = 32
-
-
-def _lib():
-    from lsdradixsort_amd import lib
-
-    return lib()
 
 
 def test_header_ctypes_table_and_package_have_the_entries():
@@ -193,25 +188,10 @@ def test_workspace_figure():
     assert L.lsdsort_logprob16_workspace_bytes.argtypes == [L.lsdsort_logprob16_workspace_bytes.argtypes[0]] * 3
 
 
-@pytest.fixture
-def no_library(monkeypatch):
-    """The argument checks come first: the library must not even be asked for."""
-    import lsdradixsort_amd as lsd
-
-    def refuse():
-        raise AssertionError("the library was reached before the arguments were checked")
-
-    monkeypatch.setattr(lsd.api, "lib", refuse)
-    return lsd
-
-
 def test_wrappers_check_their_arguments_before_the_library(no_library):
     import torch
 
     lsd = no_library
-
-    class FakeCuda(torch.Tensor):
-        is_cuda = True
 
     def fake(dtype, shape=(2, 4)):
         return torch.zeros(shape, dtype=dtype).as_subclass(FakeCuda)

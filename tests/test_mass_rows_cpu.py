@@ -8,7 +8,7 @@ import subprocess
 
 import pytest
 
-from _kernel_resources import CSRC, hipcc
+from _kernel_resources import CSRC, code, defined_in, hipcc, includes, sources
 
 HEADER = "mass_rows16.hpp"
 UNITS = ("topp16.hip", "sample16.hip", "logprob16.hip")
@@ -16,24 +16,6 @@ FUNCTIONS = ("read_body", "read_front", "wave_least", "best_number", "wave_add64
 CONSTANTS = ("kAbsent",)
 ALIASES = ("RowKeys",)
 HOST = {"sizes_ok": "radix_select.hpp", "float16_values": "keys16_map.hpp"}   # helper -> the one header that defines it
-
-
-def sources():
-    return {name: open(os.path.join(CSRC, name)).read() for name in sorted(os.listdir(CSRC)) if name.endswith((".hip", ".hpp"))}
-
-
-def code(text):
-    return re.sub(r"//.*", "", text)
-
-
-def defined_in(pattern):
-    """{file: number of definitions} over csrc/, comments aside"""
-    found = {name: len(re.findall(pattern, code(text), flags=re.M)) for name, text in sources().items()}
-    return {name: n for name, n in found.items() if n}
-
-
-def includes(text):
-    return set(re.findall(r'#include "([^"]+)"', text))
 
 
 def test_each_helper_is_defined_once_and_in_the_header():

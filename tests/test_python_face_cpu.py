@@ -10,6 +10,8 @@ import sys
 import numpy as np
 import pytest
 
+from _faces import FakeCuda, no_library
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -71,18 +73,6 @@ def test_importing_the_package_does_not_import_torch():
     out = subprocess.run([sys.executable, "-c", code], env=env, cwd=ROOT, capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
     assert out.stdout.strip() == "False"
-
-
-@pytest.fixture
-def no_library(monkeypatch):
-    """The argument checks come first: the library must not even be asked for."""
-    import lsdradixsort_amd as lsd
-
-    def refuse():
-        raise AssertionError("the library was reached before the arguments were checked")
-
-    monkeypatch.setattr(lsd.api, "lib", refuse)
-    return lsd
 
 
 def _calls(lsd, t):
@@ -221,9 +211,6 @@ def test_a_refused_size_raises_the_entrys_own_error(monkeypatch):
     from lsdradixsort_amd import errors
 
     monkeypatch.setattr(lsd.api, "lib", lambda: _Refuses())
-
-    class FakeCuda(torch.Tensor):
-        is_cuda = True
 
     def fake(dtype, *shape):
         return torch.zeros(shape, dtype=dtype).as_subclass(FakeCuda)

@@ -10,6 +10,7 @@ import pytest
 
 import _reduce as rd
 import _unique as un
+from _faces import FakeCuda, lib as _lib, no_library
 from _kernel_resources import hipcc, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,12 +21,6 @@ ENTRIES = ("lsdsort_reduce_runs_workspace_bytes", "lsdsort_reduce_runs_device", 
 NAMES = ("GPUReduceRuns", "GPUReduceByKey", "reduce_runs_workspace_bytes", "reduce_by_key_workspace_bytes", "reduce_by_key",
          "reduce_consecutive")
 FAKE = 1 << 20   # an address that is never dereferenced: every call that gets it returns before a device is touched
-
-
-def _lib():
-    from lsdradixsort_amd import lib
-
-    return lib()
 
 
 def _header():
@@ -307,16 +302,6 @@ def test_value_families():
 
 
 # ---- the Python face ---------------------------------------------------------------------------------------------------------
-@pytest.fixture
-def no_library(monkeypatch):
-    """The argument checks come first: the library must not even be asked for."""
-    import lsdradixsort_amd as lsd
-
-    def refuse():
-        raise AssertionError("the library was reached before the arguments were checked")
-
-    monkeypatch.setattr(lsd.api, "lib", refuse)
-    return lsd
 
 
 def test_wrappers_check_their_tensors_before_the_library(no_library):
@@ -332,9 +317,6 @@ def test_wrappers_check_their_tensors_before_the_library(no_library):
     for call in calls:
         with pytest.raises(TypeError):
             call([3, 1, 2], [1, 1, 1])
-
-    class FakeCuda(torch.Tensor):
-        is_cuda = True
 
     def fake(dtype, n=8):
         return torch.zeros(n, dtype=dtype).as_subclass(FakeCuda)

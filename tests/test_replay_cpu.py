@@ -8,8 +8,7 @@ import pytest
 
 import _replay as rp
 import _unique as un
-
-KEY_TYPES = ("uint32", "int32", "float32", "uint64", "int64", "float64")
+from _unique import KEY_TYPES
 
 
 def test_constants_are_the_sources():

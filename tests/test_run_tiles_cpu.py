@@ -16,7 +16,7 @@ import pytest
 
 import _replay as rp
 import _unique as un
-from _kernel_resources import CSRC, hipcc
+from _kernel_resources import CSRC, code, defined_in, hipcc, includes, sources
 
 HEADER = "run_tiles.hpp"
 UNITS = ("unique.hip", "reduce_by_key.hip")
@@ -29,24 +29,6 @@ HOST = ("key_bits_of", "aligned_to", "store_zero_runs", "make_tile_arrays", "mak
 GONE = (r"kRle\w*", r"kRbk\w*", "load_positions", "load_values", "load_tile_heads", "RleArrays", "RunArrays",
         "UniqueLayout", "ByKeyLayout", "rle_store_kernel", "rbk_store_kernel")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "run_units_workspace.json")
-
-
-def sources():
-    return {name: open(os.path.join(CSRC, name)).read() for name in sorted(os.listdir(CSRC)) if name.endswith((".hip", ".hpp"))}
-
-
-def code(text):
-    return re.sub(r"//.*", "", text)
-
-
-def defined_in(pattern):
-    """{file: number of definitions} over csrc/, comments aside"""
-    found = {name: len(re.findall(pattern, code(text), flags=re.M)) for name, text in sources().items()}
-    return {name: n for name, n in found.items() if n}
-
-
-def includes(text):
-    return set(re.findall(r'#include "([^"]+)"', text))
 
 
 def test_each_shared_piece_is_defined_once_and_in_the_header():

@@ -12,6 +12,7 @@ import pytest
 
 import _sample16 as sm
 import _topp16 as tp
+from _faces import FakeCuda, lib as _lib, no_library
 from _kernel_resources import hipcc, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,12 +21,6 @@ U16, I16, F16, BF16 = range(4)
 ENTRIES = ("lsdsort_sample16_workspace_bytes", "lsdsort_sample16_device")
 NAMES = ("GPUSample16", "sample16_workspace_bytes", "sample16_rows")
 SHARP_COLS = (64, 257, 1024, 1025, 16384, 16385, 32769, 40000)   # test_gpu_sample16.py's
-
-
-def _lib():
-    from lsdradixsort_amd import lib
-
-    return lib()
 
 
 def test_header_ctypes_table_and_package_have_the_entries():
@@ -166,25 +161,10 @@ def test_workspace_figure():
         assert f(rows, cols) == want == figure(rows, cols), (rows, cols, f(rows, cols), want)
 
 
-@pytest.fixture
-def no_library(monkeypatch):
-    """The argument checks come first: the library must not even be asked for."""
-    import lsdradixsort_amd as lsd
-
-    def refuse():
-        raise AssertionError("the library was reached before the arguments were checked")
-
-    monkeypatch.setattr(lsd.api, "lib", refuse)
-    return lsd
-
-
 def test_wrappers_check_their_arguments_before_the_library(no_library):
     import torch
 
     lsd = no_library
-
-    class FakeCuda(torch.Tensor):
-        is_cuda = True
 
     def fake(dtype, shape=(2, 4)):
         return torch.zeros(shape, dtype=dtype).as_subclass(FakeCuda)

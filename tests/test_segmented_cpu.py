@@ -5,14 +5,10 @@ import re
 
 import pytest
 
+from _faces import lib as _lib
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("lsdsort_segmented_workspace_bytes", "lsdsort_segmented_device")
-
-
-def _lib():
-    from lsdradixsort_amd import lib
-
-    return lib()
 
 
 def test_header_and_ctypes_table_have_the_segmented_entries():

@@ -12,16 +12,11 @@ import pytest
 import _sample16 as sm
 import _temper16 as tm
 import _topp16 as tp
+from _faces import FakeCuda, lib as _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U16, I16, F16, BF16 = range(4)
 ENTRIES = ("lsdsort_topp16_filter_ex_device", "lsdsort_sample16_ex_device")
-
-
-def _lib():
-    from lsdradixsort_amd import lib
-
-    return lib()
 
 
 def test_header_ctypes_table_and_units_have_the_entries():
@@ -162,9 +157,6 @@ def face(monkeypatch):
     monkeypatch.setattr(lsd.api, "lib", lambda: rec)
     monkeypatch.setattr(lsd.api, "_temp_workspace", lambda nbytes, device, stream: torch.zeros(nbytes, dtype=torch.uint8))
     monkeypatch.setattr(lsd.api, "_stream", lambda stream: None)
-
-    class FakeCuda(torch.Tensor):
-        is_cuda = True
 
     def fake(dtype, shape):
         return torch.zeros(shape, dtype=dtype).as_subclass(FakeCuda)

@@ -8,7 +8,7 @@ import subprocess
 
 import pytest
 
-from _kernel_resources import CSRC, hipcc
+from _kernel_resources import CSRC, code, defined_in, hipcc, sources
 
 H16, H32, SLOTS, SELECT = "select_tiles16.hpp", "select_tiles32.hpp", "kth_slots.hpp", "radix_select.hpp"
 UNITS = {"topk16.hip": H16, "kth16.hip": H16, "kth16_multi.hip": H16, "kth16_rowk.hip": H16, "topp16.hip": H16,
@@ -29,20 +29,6 @@ KERNEL_TEMPLATES = {"pick_rows_kernel": SELECT, "pick_slots_kernel": SLOTS, "cou
 # kernel templates now, instantiated by both units (DESIGN.md section 6.14 says why that form keeps the instructions where a shared
 # device function did not).
 STILL_DOUBLE = set()
-
-
-def sources():
-    return {name: open(os.path.join(CSRC, name)).read() for name in sorted(os.listdir(CSRC)) if name.endswith((".hip", ".hpp"))}
-
-
-def code(text):
-    return re.sub(r"//.*", "", text)
-
-
-def defined_in(pattern):
-    """{file: number of definitions} over csrc/, comments aside"""
-    found = {name: len(re.findall(pattern, code(text), flags=re.M)) for name, text in sources().items()}
-    return {name: n for name, n in found.items() if n}
 
 
 def test_each_helper_is_defined_once_and_in_its_header():

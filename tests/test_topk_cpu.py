@@ -5,17 +5,12 @@ import re
 
 import pytest
 
+from _faces import lib as _lib
 from _kernel_resources import hipcc, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lsdradixsort_amd", "csrc")
 NEW = ("lsdsort_topk_workspace_bytes", "lsdsort_topk_device")
-
-
-def _lib():
-    from lsdradixsort_amd import lib
-
-    return lib()
 
 
 def test_header_and_ctypes_table_have_the_topk_entries():

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import _topp16 as tp
+from _faces import FakeCuda, lib as _lib, no_library
 from _kernel_resources import hipcc, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,12 +19,6 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "kernel_resources_topp16.json")
 U16, I16, F16, BF16 = range(4)
 ENTRIES = ("lsdsort_topp16_filter_workspace_bytes", "lsdsort_topp16_filter_device")
 NAMES = ("GPUTopP16Filter", "topp16_filter_workspace_bytes", "topp16_filter_rows")
-
-
-def _lib():
-    from lsdradixsort_amd import lib
-
-    return lib()
 
 
 def test_header_ctypes_table_and_package_have_the_entries():
@@ -155,25 +150,10 @@ def test_workspace_figure():
         assert f(rows, cols) == want, (rows, cols, f(rows, cols), want)
 
 
-@pytest.fixture
-def no_library(monkeypatch):
-    """The argument checks come first: the library must not even be asked for."""
-    import lsdradixsort_amd as lsd
-
-    def refuse():
-        raise AssertionError("the library was reached before the arguments were checked")
-
-    monkeypatch.setattr(lsd.api, "lib", refuse)
-    return lsd
-
-
 def test_wrappers_check_their_arguments_before_the_library(no_library):
     import torch
 
     lsd = no_library
-
-    class FakeCuda(torch.Tensor):
-        is_cuda = True
 
     def fake(dtype, shape=(2, 4)):
         return torch.zeros(shape, dtype=dtype).as_subclass(FakeCuda)

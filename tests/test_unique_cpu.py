@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import _unique as un
+from _faces import FakeCuda, lib as _lib, no_library
 from _kernel_resources import hipcc, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,12 +19,6 @@ ENTRIES = ("lsdsort_rle_workspace_bytes", "lsdsort_rle_device", "lsdsort_unique_
            "lsdsort_unique_check_device")
 NAMES = ("GPURunLength", "GPUUnique", "rle_workspace_bytes", "unique_workspace_bytes", "unique", "unique_consecutive")
 FAKE = 1 << 20   # an address that is never dereferenced: every call that gets it returns before a device is touched
-
-
-def _lib():
-    from lsdradixsort_amd import lib
-
-    return lib()
 
 
 # ---- surface ---------------------------------------------------------------------------------------------------------------------
@@ -324,16 +319,6 @@ def test_model_at_the_size_past_every_first_round():
 
 
 # ---- the Python face ---------------------------------------------------------------------------------------------------------
-@pytest.fixture
-def no_library(monkeypatch):
-    """The argument checks come first: the library must not even be asked for."""
-    import lsdradixsort_amd as lsd
-
-    def refuse():
-        raise AssertionError("the library was reached before the arguments were checked")
-
-    monkeypatch.setattr(lsd.api, "lib", refuse)
-    return lsd
 
 
 def test_wrappers_check_their_tensors_before_the_library(no_library):
@@ -348,9 +333,6 @@ def test_wrappers_check_their_tensors_before_the_library(no_library):
     for call in (lsd.GPURunLength, lsd.GPUUnique, lsd.unique, lsd.unique_consecutive):
         with pytest.raises(TypeError):
             call([3, 1, 2])
-
-    class FakeCuda(torch.Tensor):
-        is_cuda = True
 
     def fake(dtype, n=8):
         return torch.zeros(n, dtype=dtype).as_subclass(FakeCuda)

@@ -5,16 +5,11 @@ import re
 
 import pytest
 
+from _faces import lib as _lib
 from _kernel_resources import hipcc, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U32, I32, F32, U64, I64, F64 = range(6)
-
-
-def _lib():
-    from lsdradixsort_amd import lib
-
-    return lib()
 
 
 def test_header_ctypes_table_and_faces_have_the_entry():
